@@ -3,17 +3,25 @@
 problems/s on synthetic multi-robot Manhattan RA-SLAM graphs, with the HBM roofline of the KKT
 SpMV and a CPU baseline timed on the same box).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 The primary metric is the same at every N: SOCP iterations/s on BASELINE.json configs[3] (one 20-robot x
 1000-pose x 4-beacon SOCP per GPU, resident in HBM), weak scaling -- every rank solves its own headline
 problem, a step = one cold-start solve to eps = 1e-7 with the operator-splitting loop alone, `value` = ADMM
-iterations of all ranks / the slowest rank's time.  N = 1 is the line the driver records as BENCH.
-Every N also carries BASELINE configs[4] as `config5_montecarlo`: 64 independent 4-robot x 1000-pose
+iterations of all ranks / the slowest rank's time, `ms_per_step` = the slowest rank's time / K.  N = 1 is the
+line the driver records as BENCH.
+
+A plain run (no --full) does only what that figure needs: it builds the workload, runs W warm-up and K timed
+steps, writes the outputs of the last timed step if --dump-outputs is given, and prints the result line
+(`roofline` and `cpu_baseline` are null in it).  --dump-outputs DIR writes rank 0's x / y / s of the last timed
+step (every problem of the handle, concatenated; float64) and its per-problem solver info to DIR/<name>.npy;
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
+With --full, every N also carries BASELINE configs[4] as `config5_montecarlo`: 64 independent 4-robot x 1000-pose
 trials, trial t on rank t mod N (strong scaling), the product's default solver, and after every sweep ONE
 all_gather of the result records (RCCL over xGMI; score_amd.distributed.all_gather_records) -- problems/s of
 the whole job.
-N = 1 additionally carries: the product's default solver (ADMM warm-up + semismooth-Newton polish) on the
+With --full, N = 1 additionally carries: the product's default solver (ADMM warm-up + semismooth-Newton polish) on the
 headline problem, the in-loop roofline of the KKT SpMV (single problem and a lock-step batch of 16), the
 roofline of the kernel that dominates GPU time (the chain preconditioner), the end-to-end legs and the CPU
 baselines.  (`--workload montecarlo`: configs[4] alone as the primary metric -- profiling runs only.)
@@ -23,8 +31,8 @@ BEFORE anything in this process touches the GPU; RCCL rendezvous on 127.0.0.1); 
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` (RANK / WORLD_SIZE already in
 the environment) it is one of the ranks.  Rank 0 prints ONE JSON line on stdout: the compact contract record
 (<= 4 KB: contract keys, config, roofline of the KKT SpMV + the dominant kernel + the batch of 16, cpu_baseline, a
-few scalars per leg).  The FULL record (every leg, per-call arrays, notes) goes to --full-out
-(gpurun_out/bench_full.json) and, as one line, to stderr.
+few scalars per leg).  The FULL record (every leg, per-call arrays, notes) goes, as one line, to stderr and, if
+--full-out PATH is given, to that file.
 """
 from __future__ import annotations
 
@@ -63,8 +71,13 @@ def parse_args(argv=None):
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-e2e", action="store_true", help="skip the end_to_end leg (profiler runs: eight host threads creating handles at once)")
     ap.add_argument("--cpu-baseline-only", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg beyond the headline figure: config 5, default solver, rooflines, 3-D, long chains, end to end, "
+                         "CPU baselines (off: set up, warm up, time the steps, print the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0: x, y, s, solver info) to DIR/<name>.npy")
     ap.add_argument("--no-probes", action="store_true",
-                    help="timed region only (loop-only profiler traces): no roofline probes, no extra legs")
+                    help="timed region only (loop-only profiler traces): no roofline probes, no extra legs (what a run without --full does)")
     ap.add_argument("--kkt-reps", type=int, default=1000)
     ap.add_argument("--roofline-batch", type=int, default=16, help="problems in the lock-step handle of roofline_batch16")
     ap.add_argument("--force-dist", action="store_true", help="initialise the process group even for one rank (testing)")
@@ -77,12 +90,16 @@ def parse_args(argv=None):
     ap.add_argument("--mc-robots", type=int, default=4)
     ap.add_argument("--mc-poses", type=int, default=1000)
     ap.add_argument("--mc-beacons", type=int, default=4)
-    ap.add_argument("--full-out", default=os.path.join(ROOT, "gpurun_out", "bench_full.json"),
-                    help="where rank 0 writes the FULL record (every leg, every note); stdout carries the compact contract line only")
+    ap.add_argument("--full-out", default=None,
+                    help="a file for rank 0's FULL record (every leg, every note; always printed to stderr); stdout carries the compact contract line only")
     ap.add_argument("--test-cpu-twin", action="store_true",
                     help="TEST ONLY (tests/test_bench_contract.py): gloo + the oracle's CPU twin instead of RCCL + "
                          "the HIP library, to exercise the N-rank launcher without GPUs; its numbers are not measurements")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    # a plain run is the timed region alone: every other leg needs --full
+    args.no_probes = args.no_probes or not args.full
     if args.test_cpu_twin and os.environ.get("SCORE_BENCH_TEST_MODE") != "1":
         ap.error("--test-cpu-twin runs the oracle's CPU twin in place of the HIP library: it exists for the launcher tests "
                  "only and needs SCORE_BENCH_TEST_MODE=1 in the environment (nothing it prints is a measurement)")
@@ -182,15 +199,16 @@ def compact_record(rec):
 
 
 def emit(args, rec):
-    """Rank 0's output: the full record to --full-out (and one stderr line), the compact contract record as the ONE stdout line."""
+    """Rank 0's output: the full record as one stderr line (and to --full-out if given), the compact contract record as the ONE stdout line."""
     path = args.full_out
-    try:
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "w") as fh:
-            json.dump(rec, fh)
-        rec["full_record"] = os.path.relpath(path, ROOT) if os.path.abspath(path).startswith(ROOT) else path
-    except OSError as e:  # a read-only tree must not cost the contract line
-        print(f"bench.py: could not write {path}: {e}", file=sys.stderr)
+    if path:
+        try:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            with open(path, "w") as fh:
+                json.dump(rec, fh)
+            rec["full_record"] = os.path.relpath(path, ROOT) if os.path.abspath(path).startswith(ROOT) else path
+        except OSError as e:  # a read-only tree must not cost the contract line
+            print(f"bench.py: could not write {path}: {e}", file=sys.stderr)
     print(json.dumps(rec), file=sys.stderr, flush=True)
     line = json.dumps(compact_record(rec), separators=(",", ":"))
     if len(line) > CONTRACT_MAX_BYTES:  # never again: drop the optional legs before the contract fields
@@ -200,6 +218,32 @@ def emit(args, rec):
     assert len(line) <= CONTRACT_MAX_BYTES, len(line)
     sys.stderr.flush()
     print(line, flush=True)
+
+
+# ---------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path returned in its last step
+# ---------------------------------------------------------------------------------------------
+DUMP_MAX_BYTES = 64 << 20
+# the solver info a caller receives, timings left out (they differ from run to run)
+DUMP_INFO = ("status", "iters", "cg_iters", "rho_updates", "rho", "pobj", "dobj", "res_pri", "res_dual", "gap",
+             "newton_iters", "newton_cg_iters")
+
+
+def dump_outputs(path, sols):
+    """The ConicSolutions of the last timed step as float64 .npy files: x.npy, y.npy, s.npy (the problems of the handle
+    concatenated in order) and info.npy (one row per problem, columns DUMP_INFO).  Above DUMP_MAX_BYTES in all, x / y / s
+    are cut down to the same fixed, seeded sample of positions in every run with these arguments."""
+    os.makedirs(path, exist_ok=True)
+    out = {k: np.concatenate([np.asarray(getattr(s, k), dtype=np.float64) for s in sols]) for k in ("x", "y", "s")}
+    info = np.array([[float(s.info[k]) for k in DUMP_INFO] for s in sols], dtype=np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total + info.nbytes > DUMP_MAX_BYTES:
+        keep = (DUMP_MAX_BYTES - info.nbytes) / total
+        rng = np.random.default_rng(0)
+        out = {k: a[np.sort(rng.choice(a.size, int(a.size * keep), replace=False))] for k, a in out.items()}
+    out["info"] = info
+    for k, a in out.items():
+        np.save(os.path.join(path, f"{k}.npy"), a)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -313,10 +357,14 @@ def run_headline(args, D: Dist):
                              "pcg_iters_per_admm_iter": tot[3] / max(1.0, tot[0]),
                              "final": {"pobj": info["pobj"], "res_pri": info["res_pri"], "res_dual": info["res_dual"], "rho": info["rho"]}},
         }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last)
     if args.no_probes:
         if rec is not None:
             rec["roofline"] = None
             rec["cpu_baseline"] = None
+            if args.test_cpu_twin:
+                rec["test_mode"] = "gloo + oracle CPU twin: launcher test, NOT a measurement"
             emit(args, rec)
         solver.close()
         D.close()
@@ -330,7 +378,7 @@ def run_headline(args, D: Dist):
             rec["config5_montecarlo"] = c5
             rec["roofline"] = None
             rec["cpu_baseline"] = None
-            rec["note"] = "roofline and cpu_baseline are measured by the single-GPU line (python bench.py)"
+            rec["note"] = "roofline and cpu_baseline are measured by the single-GPU line (python bench.py --full)"
             if args.test_cpu_twin:
                 rec["test_mode"] = "gloo + oracle CPU twin: launcher test, NOT a measurement"
             emit(args, rec)
@@ -478,7 +526,7 @@ def main():
     if workload == "auto":  # the same primary metric at every N (a 1 -> 8 curve compares like with like)
         workload = "headline"
     if workload == "montecarlo":
-        rec = run_montecarlo_leg(args, D)
+        rec = run_montecarlo_leg(args, D, dump=dump_outputs if args.dump_outputs else None)
         if rec is not None:
             emit(args, rec)
         D.close()

@@ -16,7 +16,7 @@ timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/loop" -o loop --outp
 #  handles at once -- it aborted with a malformed AQL packet and then hung in its own finalisation for the rest of the call's
 #  limit: that leg is left out of the trace (--no-e2e) and every profiler command runs under `timeout`)
 for try in 1 2; do
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/full" -o full --output-format csv -- python3 "$REPO/bench.py" --steps 5 --warmup 1 --no-cpu-baseline --no-e2e > "$OUT/full_bench.json" 2> "$OUT/full.err" && break
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/full" -o full --output-format csv -- python3 "$REPO/bench.py" --full --steps 5 --warmup 1 --no-cpu-baseline --no-e2e > "$OUT/full_bench.json" 2> "$OUT/full.err" && break
   rm -rf "$OUT/full"
 done
 for C in FETCH_SIZE WRITE_SIZE; do

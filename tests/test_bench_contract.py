@@ -30,7 +30,7 @@ def run_bench(argv, tmp_path, env=None, timeout=900, **kw):
 
 def test_bench_cpu_baseline_leg_runs_and_reports(twin_lib, tmp_path):
     """The cpu_baseline leg of bench.py (oracle's CPU twin on a bounded sample)."""
-    out, compact, rec = run_bench(["--cpu-baseline-only", "--robots", "2", "--poses", "60",
+    out, compact, rec = run_bench(["--full", "--cpu-baseline-only", "--robots", "2", "--poses", "60",
                                    "--mc-robots", "3", "--mc-poses", "80", "--cpu-seconds", "5"], tmp_path, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     cc = compact["cpu_baseline"]
@@ -60,7 +60,7 @@ def test_bench_gpus_flag_launches_that_many_ranks(twin_lib, tmp_path):
     env = dict(os.environ, OMP_NUM_THREADS="2", SCORE_BENCH_TEST_MODE="1")
     env.pop("RANK", None); env.pop("WORLD_SIZE", None)
     out, compact, rec = run_bench(
-        ["--gpus", "2", "--test-cpu-twin", "--robots", "2", "--poses", "30",
+        ["--full", "--gpus", "2", "--test-cpu-twin", "--robots", "2", "--poses", "30",
          "--montecarlo", "5", "--mc-robots", "2", "--mc-poses", "30", "--mc-batch", "2", "--mc-threads", "1", "--steps", "1",
          "--warmup", "0"], tmp_path, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -91,13 +91,49 @@ def test_bench_is_one_of_the_ranks_under_a_launcher(twin_lib, tmp_path):
     env = dict(os.environ, OMP_NUM_THREADS="2", SCORE_BENCH_TEST_MODE="1", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
                MASTER_PORT="29533")
     out, compact, rec = run_bench(
-        ["--gpus", "1", "--test-cpu-twin", "--force-dist", "--robots", "1",
+        ["--full", "--gpus", "1", "--test-cpu-twin", "--force-dist", "--robots", "1",
          "--poses", "30", "--beacons", "2", "--montecarlo", "2", "--mc-robots", "1", "--mc-poses", "30", "--mc-beacons", "2",
          "--steps", "1", "--warmup", "0"], tmp_path, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     assert compact["n_gpus"] == 1 and compact["metric"] == "socp_iters_per_sec"
     assert rec["n_gpus"] == 1 and rec["metric"] == "socp_iters_per_sec"
     assert rec["config5_montecarlo"]["solved_last_sweep"] == 2 and rec["config5_montecarlo"]["results_gathered"] == 2
+
+
+def test_a_plain_run_times_the_steps_and_dumps_the_same_outputs_every_time(twin_lib, tmp_path):
+    """Without --full, bench.py is the timed region alone: exactly --steps timed steps, ms_per_step, no other leg.
+    --dump-outputs writes what the last timed step returned (x, y, s, solver info) as float64 .npy files, and the
+    seeded inputs make two runs with the same arguments write the same arrays."""
+    import numpy as np
+
+    env = dict(os.environ, OMP_NUM_THREADS="2", SCORE_BENCH_TEST_MODE="1")
+    env.pop("RANK", None); env.pop("WORLD_SIZE", None)
+    dumps = []
+    for run in ("a", "b"):
+        dump = os.path.join(str(tmp_path), f"dump_{run}")
+        out, compact, rec = run_bench(["--test-cpu-twin", "--robots", "1", "--poses", "30", "--beacons", "2", "--steps", "3",
+                                       "--warmup", "1", "--dump-outputs", dump], tmp_path, env=env)
+        assert out.returncode == 0, out.stderr[-3000:]
+        for key in CONTRACT_KEYS:
+            assert key in compact
+        assert compact["steps"] == 3 and compact["ms_per_step"] > 0 and compact["metric"] == "socp_iters_per_sec"
+        assert rec["timed_region"]["problems_total"] == 3  # one problem per step
+        assert compact["roofline"] is None and compact["cpu_baseline"] is None
+        for leg in ("config5_montecarlo", "product_default_solver", "end_to_end", "three_d", "long_chains", "roofline_dominant"):
+            assert leg not in rec
+        arrays = {k: np.load(os.path.join(dump, f"{k}.npy")) for k in ("x", "y", "s", "info")}
+        assert all(a.dtype == np.float64 for a in arrays.values())
+        assert arrays["x"].shape == (rec["config"]["n"],) and arrays["y"].shape == arrays["s"].shape == (rec["config"]["m"],)
+        assert arrays["info"].shape == (1, 12) and arrays["info"][0, 0] == 1  # status: solved
+        dumps.append(arrays)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+
+
+def test_the_steps_flag_must_ask_for_a_timed_step():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"],
+                         capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert out.returncode != 0 and "--steps" in out.stderr
 
 
 def test_a_failing_rank_takes_the_launch_down_promptly(twin_lib):
@@ -150,7 +186,7 @@ def test_four_ranks_on_four_cpus_do_not_starve_each_other(twin_lib, tmp_path):
     if len(cpus) < 8:
         import pytest
         pytest.skip("needs 8 CPUs for the unpinned run")
-    cmd = ["--gpus", "4", "--test-cpu-twin", "--robots", "2", "--poses", "40",
+    cmd = ["--full", "--gpus", "4", "--test-cpu-twin", "--robots", "2", "--poses", "40",
            "--montecarlo", "8", "--mc-robots", "2", "--mc-poses", "30", "--mc-batch", "2", "--steps", "1", "--warmup", "0"]
     env = dict(os.environ, OMP_NUM_THREADS="1", SCORE_BENCH_TEST_MODE="1")
     env.pop("RANK", None); env.pop("WORLD_SIZE", None)
