@@ -36,14 +36,29 @@ from . import compat
 from .native import graph_arrays
 
 
+def _weighted_ranges(a: dict, range_weights) -> dict:
+    """The graph's arrays with every range precision scaled by its weight (``range_weights``: one per range, in the order of
+    ``graph_arrays``' ``rng_*`` -- what ``solve_score_robust`` returns in ``info["robust"]["weights"]``); None: as they are."""
+    if range_weights is None:
+        return a
+    w = np.asarray(range_weights, dtype=np.float64)
+    if w.shape != (len(a["rng_a"]),):
+        raise ValueError(f"range_weights: {len(a['rng_a'])} weights expected (one per range), got shape {w.shape}")
+    if not (np.all(np.isfinite(w)) and np.all(w >= 0)):
+        raise ValueError("range_weights must be finite and non-negative")
+    out = dict(a)
+    out["rng_prec"] = np.ascontiguousarray(np.asarray(a["rng_prec"], dtype=np.float64) * w)
+    return out
+
+
 class _Problem:
     """Residuals and sparse Jacobian of the 2-D RA-SLAM least-squares problem in the minimal
     parametrisation u = [theta_1.., x_1, y_1.. | landmarks]; pose 0 (first pose of chain 0) is fixed."""
 
-    def __init__(self, data):
+    def __init__(self, data, range_weights=None):
         if data.dimension != 2:
             raise ValueError("refine_estimate: 2-D graphs only")
-        a = graph_arrays(data)
+        a = _weighted_ranges(graph_arrays(data), range_weights)
         self.a = a
         self.Np, self.Nl = len(a["pose_names"]), len(a["landmark_names"])
         self.n = 3 * (self.Np - 1) + 2 * self.Nl
@@ -191,10 +206,10 @@ class _Problem3D:
     tangent space, (omega, v) per free pose and a 3-vector per landmark, applied by the retraction
     R <- R Exp(omega), t <- t + v.  Columns of pose p >= 1: 6 (p - 1) .. +5 = [omega | v]; pose 0 is fixed."""
 
-    def __init__(self, data):
+    def __init__(self, data, range_weights=None):
         if data.dimension != 3:
             raise ValueError("_Problem3D: 3-D graphs only")
-        a = graph_arrays(data)
+        a = _weighted_ranges(graph_arrays(data), range_weights)
         self.a = a
         self.Np, self.Nl = len(a["pose_names"]), len(a["landmark_names"])
         self.n = 6 * (self.Np - 1) + 3 * self.Nl
@@ -415,19 +430,21 @@ def _refine_native(prob: _Problem, u0: np.ndarray, max_iters: int, tol: float, l
 
 def refine_estimate(data, results, max_iters: int = 50, tol: float = 1e-10, verbose: bool = False,
                     linear_solver: str = "device", lib_path: Optional[str] = None, solver_settings: Optional[dict] = None,
-                    pcg_rel_tol: float = 1e-9, engine: str = "native"):
+                    pcg_rel_tol: float = 1e-9, engine: str = "native", range_weights=None):
     """Refine a SCORE estimate (``SolverResults``) to a local minimiser of the RA-SLAM maximum-likelihood
     cost.  Returns ``(refined SolverResults, info)``; ``info`` holds the cost before / after, iterations,
-    the final gradient norm and (device path) the PCG iterations spent in the linear solves."""
+    the final gradient norm and (device path) the PCG iterations spent in the linear solves.
+    ``range_weights`` (one per range, in the graph's range order): the range precisions are scaled by them -- the weights of
+    ``solve_score_robust`` (``info["robust"]["weights"]``) keep the ranges it flagged out of the maximum-likelihood step."""
     if linear_solver not in ("device", "scipy"):
         raise ValueError("linear_solver must be 'device' or 'scipy'")
     if engine not in ("native", "python"):
         raise ValueError("engine must be 'native' or 'python'")
     if data.dimension == 3:
-        prob = _Problem3D(data)
+        prob = _Problem3D(data, range_weights)
         u = prob.initial_state(results)
     else:
-        prob = _Problem(data)
+        prob = _Problem(data, range_weights)
         u = _initial_point(prob, results)
     if engine == "native" and linear_solver == "device" and prob.n > 0:
         u, ni = _refine_native(prob, u, max_iters, tol, lib_path, solver_settings)
