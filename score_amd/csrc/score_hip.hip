@@ -903,28 +903,21 @@ struct HipBackend {
     // (a band view of the Newton matrix was measured without effect -- 64 config-5 trials 7.0 ms per solve with and without,
     //  headline default solve 4.5 ms either way -- and cost setup time: removed in round 6, profiles/TRIED.md)
     static constexpr bool band_h(const HostSystem&) { return false; }
-    int kblocks() const { return Kb.on ? Kb.nblocks : K.nblocks; }   // tiles of the K product (= p'w partials per launch)
-    int hblocks() const { return Hb.on ? Hb.nblocks : Hm.nblocks; }
     DevBuf<int32_t> A_ptr, A_col;
     DevBuf<double> A_val;
-    DevBuf<double> q, b, invD, invE, rho, fac, dinv, K0d, K1d;
-    DevBuf<int32_t> kposd, kposs, kdiagpos;  // K.val positions of the chain blocks / Jacobi diagonals
+    DevBuf<double> q, b, invD, invE, rho, K0d, K1d;
     DevBuf<int32_t> done, cone_row, cone_dim, cone_type, cone_block_first, cone_block_prob;
     DevBuf<int4> cone_meta;
     DevBuf<int2> cone_large;    // {cone, problem} of the cones with more than kWaveCone rows (k_cone_wave)
     int n_large_cones = 0;
     DevBuf<int32_t> cone_cols;  // 8 per cone (two int4)
     DevBuf<double> cone_vals;   // 8 per cone (four double2)
-    DevBuf<int32_t> node_col, diag_cols, prec_part_ptr, kblk_part_ptr;
+    DevBuf<int32_t> node_col, diag_cols, prec_part_ptr;
     DevBuf<PrecWork> prec_work, factor_work;   // factor_work: what a factorisation of K visits (HostSystem::factor_work)
-    DevBuf<ChainDesc> chains, chainsH;         // chainsH / levelsH: the same chains with factors of their own (Newton matrix)
-    DevBuf<ChainLevelDesc> levels, levelsH;
-    DevBuf<PrecRecord> prec_rec, prec_recH;    // one record per work item: work + chain + level table (k_prec_pre)
-    DevBuf<int64_t> fac_rangeK, fac_rangeH;    // per chain: its factor range (k_fac_round_items)
     DevBuf<int64_t> q_entpart;                 // per problem: its entry range in the Newton matrix
     int64_t q_ent_max = 0;
     static constexpr int64_t kHelpEntries = (int64_t)kPrecThreads * kPrecChunk;  // vector entries per update helper
-    int n_help = 0;                            // update-helper records appended to prec_rec / prec_recH
+    int n_help = 0;                            // update-helper records appended to both sets' PrecSet::rec
     DevBuf<int32_t> vb_first, vb_end, vb_prob; // blocks of <= 256 vector entries per problem (k_xupdate)
     int n_vblocks = 0;
     DevBuf<double> xtu, xy, s, r, z, p, p2, w, kx, step;
@@ -936,30 +929,60 @@ struct HipBackend {
         const int32_t* rng_a; const int32_t* rng_b; const double* rng_dist; const double* rng_prec;
     };
     const GenSource* gen_src = nullptr;  // (set by score_create_from_generated for the duration of the create)
-    // ---- segmented long chains (score_join.hpp): K's set, the Newton matrix's set ----
+    // ---- segmented long chains (score_join.hpp): the plan and the scratch both factor sets share ----
     int n_join_items = 0, n_join_chains = 0, n_join_seps = 0;
-    bool join_suspend = false;  // the spike solves of a refresh: the chain kernel alone
     DevBuf<JoinChain> join_jc;
     DevBuf<JoinItem> join_items;
-    DevBuf<int32_t> join_sep_col, join_sep_diag, join_pcol, join_pprev, join_posd_K, join_poss_K, join_posd_H, join_poss_H, join_zero;
-    DevBuf<double> join_W_K, join_W_H, join_data_K, join_data_H, join_rhs, join_tmp_p, join_tmp_rz, join_zb;
+    DevBuf<int32_t> join_sep_col, join_sep_diag, join_pcol, join_pprev, join_zero;
+    DevBuf<double> join_rhs, join_tmp_p, join_tmp_rz, join_zb;
     // ---- semismooth-Newton polish (score_polish*.hpp) ----
-    DevBuf<float> fac32, q_fac32;  // float copies of the chain factors (ADMM / Newton), see k_fac_round
-    DevBuf<float> deepK, deepH;    // lane-major copies of their coarse levels (k_deep_pack -> k_prec_pre<.., float, true>)
     DevBuf<int32_t> deep_map;
     bool prec_reg = false;         // every chain has a lane plan: the register-resident variant serves the 4-byte streams
     size_t prec_reg_lds = 0;
-    bool use_fac32 = false;     // ADMM-loop factors (K)
-    bool newton_fac32 = false;  // Newton-polish factors (H): fac_fp32 = 2 only, see DESIGN.md section 4
     PolishData Q;
     std::future<void> polish_build;  // build_polish (or only its structure check) runs beside the uploads of init()
     bool polish_on_device = false;   // the Newton matrix's pattern and lists come from score_polish_device.hpp
     bool derive_ag = false;          // the equilibrated A, G1, G2 were derived on the device (k_derive_a / k_derive_g)
     int64_t hm_nnz = 0;              // entries of the Newton matrix
     CsrBufs Hm;
-    DevBuf<double> q_Pon, q_ccoef, q_Bbuf, q_fpart, q_X0, q_X1, q_g, q_delta, q_fac, q_dinv, q_work, q_dummy, q_gd, q_pw;
+    // One factor set of the chain preconditioner: everything that differs between the ADMM loop's matrix K (set 0) and the
+    // Newton polish's matrix (set 1).  What the two share -- prec_work as the list an application walks, node_col, diag_cols,
+    // prec_part_ptr, q_work, the join and link plans and scratch -- stays with the backend.
+    struct PrecSet {
+        const CsrBufs& mat;                 // the matrix whose chains the set factors (K / Hm) ...
+        const BandBufs& band;               // ... its band view, when that serves the products
+        const DevBuf<PrecWork>& fac_work;   // the work list a factorisation walks (factor_work / prec_work)
+        PrecSet(const CsrBufs& m, const BandBufs& b, const DevBuf<PrecWork>& fw) : mat(m), band(b), fac_work(fw) {}
+        // (the Newton set's chains / levels / rec are views of K's when rep == 1: the same chains; with replicas every chain
+        //  has factors of its own there)
+        DevBuf<ChainDesc> chains;
+        DevBuf<ChainLevelDesc> levels;
+        DevBuf<PrecRecord> rec;             // one record per work item: work + chain + level table (k_prec_pre)
+        DevBuf<int64_t> fac_range;          // per chain: its factor range (k_fac_round_items)
+        DevBuf<double> fac, dinv;           // chain factors, inverse Jacobi diagonals
+        DevBuf<float> fac32;                // float copy of the chain factors, see k_fac_round
+        DevBuf<float> deep;                 // lane-major copy of its coarse levels (k_deep_pack -> k_prec_pre<.., float, true>)
+        size_t fac_doubles = 0;             // HostSystem::fac_doubles[_H], deep_floats[_H]
+        int64_t deep_floats = 0;
+        bool use_fac32 = false;             // the applications read the 4-byte stream (K: fac_fp32 != 0; Newton: see init())
+        bool use_owner = false;             // replicated K: the matrix blocks of a join chain are its owner's
+        DevBuf<int32_t> posd, poss, diagpos;  // mat.val positions of the chain blocks / Jacobi diagonals
+        DevBuf<int32_t> blk_part;           // per problem: its tiles of the product with mat
+        int blocks() const { return band.on ? band.nblocks : mat.nblocks; }  // tiles of that product (= p'w partials per launch)
+        // segmented long chains (score_join.hpp)
+        DevBuf<double> join_W, join_data;
+        DevBuf<int32_t> join_posd, join_poss;
+        // loop closures (score_link.hpp)
+        bool link_on = false;
+        DevBuf<int32_t> link_pcol, link_pshift, link_pos, link_status;
+        DevBuf<double> link_Qt, link_Zr;
+    };
+    PrecSet pset[2] = {{K, Kb, factor_work}, {Hm, Hb, prec_work}};
+    PrecSet &Kset = pset[0], &Hset = pset[1];
+    enum class PrecDepth { chain, join, all };  // how far an application goes: chain kernel / + second level / + loop closures
+    DevBuf<double> q_Pon, q_ccoef, q_Bbuf, q_fpart, q_X0, q_X1, q_g, q_delta, q_work, q_dummy, q_gd, q_pw;
     DevBuf<double> q_aabs, q_ck, q_theta, q_xstar;
-    DevBuf<int32_t> q_cptr, q_ccone, q_cab, q_head, q_ishead, q_posd, q_poss, q_diagpos, q_hblk_part, q_long, q_long_prob;
+    DevBuf<int32_t> q_cptr, q_ccone, q_cab, q_head, q_ishead, q_long, q_long_prob;
     int n_long = 0;
     // lock-step polish of a batch (count > 1)
     DevBuf<int32_t> q_skip, q_reref, q_fskip, q_act;  // (q_skip, q_reref, q_fskip: views into ctl)
@@ -1876,11 +1899,14 @@ struct HipBackend {
             if (n_large_cones) cone_large.upload(lg);
         }
         node_col.upload(h.node_col); diag_cols.upload(h.diag_cols);
-        prec_work.upload(h.prec_work); chains.upload(h.chains); levels.upload(h.levels);
-        fac_rangeK.upload(h.fac_range); fac_rangeH.upload(h.fac_range_H);
+        prec_work.upload(h.prec_work); Kset.chains.upload(h.chains); Kset.levels.upload(h.levels);
+        Kset.fac_range.upload(h.fac_range); Hset.fac_range.upload(h.fac_range_H);
         factor_work.upload(h.factor_work);
-        if (h.rep > 1) { chainsH.upload(h.chainsH); levelsH.upload(h.levelsH); }
-        else { chainsH.view(chains.d, chains.n); levelsH.view(levels.d, levels.n); }
+        if (h.rep > 1) { Hset.chains.upload(h.chainsH); Hset.levels.upload(h.levelsH); }
+        else { Hset.chains.view(Kset.chains.d, Kset.chains.n); Hset.levels.view(Kset.levels.d, Kset.levels.n); }
+        Kset.fac_doubles = h.fac_doubles; Hset.fac_doubles = h.fac_doubles_H;
+        Kset.deep_floats = h.deep_floats; Hset.deep_floats = h.deep_floats_H;
+        Kset.use_owner = h.rep > 1;
         {   // the records k_prec_pre reads (PrecRecord), for the factors of K and for those of the Newton matrix
             auto build = [&](const std::vector<ChainDesc>& cs, const std::vector<ChainLevelDesc>& ls) {
                 std::vector<PrecRecord> rec(h.prec_work.size());
@@ -1911,9 +1937,9 @@ struct HipBackend {
                 const bool on = h.count == 1 && (int)h.prec_work.size() + want <= cus;  // the whole launch resident at once
                 n_help = on ? want : 0;
             }
-            prec_rec.upload(build(h.chains, h.levels));
-            if (h.rep > 1 && st.polish) prec_recH.upload(build(h.chainsH, h.levelsH));
-            else prec_recH.view(prec_rec.d, prec_rec.n);
+            Kset.rec.upload(build(h.chains, h.levels));
+            if (h.rep > 1 && st.polish) Hset.rec.upload(build(h.chainsH, h.levelsH));
+            else Hset.rec.view(Kset.rec.d, Kset.rec.n);
         }
         n_prec = (int)h.prec_work.size();
         active_part_ptr = h.prec_part_ptr;
@@ -2003,10 +2029,7 @@ struct HipBackend {
             const bool fallback = !prec_pre || (h.bs >= 4 && st.fac_fp32 == 0);
             if (fallback && prec_lds > 144 * 1024) throw std::runtime_error("chain too long: more than 129 segments of 1023 nodes (132 k) for the segmented chain solver, and beyond what the streaming kernel keeps in LDS");
         }
-        if (n_prec_chains(h)) {
-            if (h.bs <= 1) allow_big_lds<1>(); else if (h.bs == 2) allow_big_lds<2>();
-            else if (h.bs == 3) allow_big_lds<3>(); else allow_big_lds<4>();
-        }
+        if (n_prec_chains(h)) with_bs([&](auto bs) { allow_big_lds<decltype(bs)::value>(); });
         if (st.polish) init_polish_build(h);
         pt.mark("polish: structure (before the band view is waited for)");
         if (band_layout_job.valid()) {  // band view of K (score_band.hpp), laid out beside everything above
@@ -2018,19 +2041,19 @@ struct HipBackend {
                              Kb.L.n_band, Kb.L.n_csr, Kb.L.n_diag, Kb.L.S);
             pt.mark("band view of K (wait + upload)");
         }
-        kblk_part_ptr.upload(Kb.on ? Kb.L.part_ptr : h.rbK.part_ptr);
+        Kset.blk_part.upload(Kb.on ? Kb.L.part_ptr : h.rbK.part_ptr);
         {   // the iterates and partial sums a reset zeroes: ONE block (a reset is one fill instead of fifteen -- each a 4 us
             // dispatch, on every solve)
             auto pad = [](size_t c) { return (std::max<size_t>(1, c) + 31) & ~(size_t)31; };  // (256-byte aligned pieces)
             const size_t nm = pad((size_t)(h.n_tot + h.m_tot)), nn = pad((size_t)h.n_tot), mm = pad((size_t)h.m_tot), cc = pad((size_t)h.count);
-            const size_t kb = pad((size_t)kblocks()), np_ = pad((size_t)n_prec);
+            const size_t kb = pad((size_t)Kset.blocks()), np_ = pad((size_t)n_prec);
             iter_block.alloc(2 * nm + mm + 6 * nn + cc + kb + 4 * np_);
             double* o = iter_block.d;
             auto take = [&](DevBuf<double>& b, size_t count, size_t padded) { b.view(o, count); o += padded; };
             take(xtu, (size_t)(h.n_tot + h.m_tot), nm); take(xy, (size_t)(h.n_tot + h.m_tot), nm); take(s, (size_t)h.m_tot, mm);
             take(r, (size_t)h.n_tot, nn); take(z, (size_t)h.n_tot, nn); take(p, (size_t)h.n_tot, nn); take(p2, (size_t)h.n_tot, nn);
             take(w, (size_t)h.n_tot, nn); take(kx, (size_t)h.n_tot, nn); take(step, (size_t)h.count, cc);
-            take(pw_part, (size_t)kblocks(), kb); take(rz_part0, (size_t)n_prec, np_); take(rz_part1, (size_t)n_prec, np_);
+            take(pw_part, (size_t)Kset.blocks(), kb); take(rz_part0, (size_t)n_prec, np_); take(rz_part1, (size_t)n_prec, np_);
             take(rz_meas0, (size_t)n_prec, np_); take(rz_meas1, (size_t)n_prec, np_);
         }
         cg_iters = st.cg_iters;
@@ -2040,13 +2063,13 @@ struct HipBackend {
         {   // positions of the chain blocks and the Jacobi diagonals in K's value array: looked up on the device (binary
             // search per block entry; on the host this was 0.5 ms of a headline create and 2.4 of an 8-trial handle's)
             const int b2 = h.bs * h.bs;
-            kposd.alloc(h.node_col.size() * (size_t)b2); kposs.alloc(h.node_col.size() * (size_t)b2); kdiagpos.alloc(h.diag_cols.size());
+            Kset.posd.alloc(h.node_col.size() * (size_t)b2); Kset.poss.alloc(h.node_col.size() * (size_t)b2); Kset.diagpos.alloc(h.diag_cols.size());
             DevBuf<int32_t> prevc, drow;
             prevc.upload(h.node_prev_owned); drow.upload(h.diag_row0);
             HPosArgs pa{};
             pa.Hptr = K.ptr.d; pa.Hcol = K.col.d; pa.node_col = node_col.d; pa.prev_col = prevc.d;
-            pa.n_nodes = (int64_t)h.node_col.size(); pa.bs = h.bs; pa.pos_diag = kposd.d; pa.pos_sub = kposs.d;
-            pa.diag_cols = drow.d; pa.n_diag = (int64_t)h.diag_cols.size(); pa.diag_pos = kdiagpos.d;
+            pa.n_nodes = (int64_t)h.node_col.size(); pa.bs = h.bs; pa.pos_diag = Kset.posd.d; pa.pos_sub = Kset.poss.d;
+            pa.diag_cols = drow.d; pa.n_diag = (int64_t)h.diag_cols.size(); pa.diag_pos = Kset.diagpos.d;
             const int64_t npos = std::max<int64_t>(pa.n_nodes * b2, pa.n_diag);
             if (npos > 0) hipLaunchKernelGGL(k_hb_positions, dim3((unsigned)((npos + 255) / 256)), dim3(256), 0, stream, pa);
             HIP_CHECK(hipGetLastError());
@@ -2054,8 +2077,8 @@ struct HipBackend {
         join_init(h);
         // (separator slots of the spike region are never written, nor used: zeroed once, with the float copy, in one fill)
         ZeroGroup zfac;
-        zfac.add(fac, h.fac_doubles);
-        use_fac32 = st.fac_fp32 != 0;
+        zfac.add(Kset.fac, Kset.fac_doubles);
+        Kset.use_fac32 = st.fac_fp32 != 0;
         // 4 x 4 blocks (3-D problems): the LDS-resident chain kernel only exists for the 4-byte stream, and the streaming
         // kernel is three times slower (22 / 30 us against 66 / 74 us per application on 1000-pose chains) -- the Newton
         // factors follow the ADMM ones there (same Newton and PCG counts on the 3-D BASELINE-sized problems)
@@ -2065,11 +2088,11 @@ struct HipBackend {
         // iterations with floats on the 144-graph sweep of round 2).
         int min_chain = 1 << 30;
         for (const auto& ch : h.chains) min_chain = std::min(min_chain, (int)ch.N);
-        newton_fac32 = st.fac_fp32 >= 2 || (st.fac_fp32 == 1 && prec_pre && (h.bs >= 4 || min_chain >= 256));
-        if (use_fac32) zfac.add(fac32, h.fac_doubles);
+        Hset.use_fac32 = st.fac_fp32 >= 2 || (st.fac_fp32 == 1 && prec_pre && (h.bs >= 4 || min_chain >= 256));
+        if (Kset.use_fac32) zfac.add(Kset.fac32, Kset.fac_doubles);
         zfac.commit(stream);
-        if (use_fac32 && prec_reg) deepK.alloc((size_t)std::max<int64_t>(1, h.deep_floats));
-        dinv.alloc(h.dinv.size()); rho.upload(h.rho);
+        if (Kset.use_fac32 && prec_reg) Kset.deep.alloc((size_t)std::max<int64_t>(1, Kset.deep_floats));
+        Kset.dinv.alloc(h.dinv.size()); rho.upload(h.rho);
         q_work.alloc((size_t)std::max<int64_t>(1, h.scratch_nodes) * 2 * std::max(1, h.bs * h.bs));
         plan_factor_lds();
         derive_rho_data(false);
@@ -2135,13 +2158,7 @@ struct HipBackend {
             hipLaunchKernelGGL(k_band_pack, dim3((unsigned)((nnz + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, (const int32_t*)Kb.dst.d,
                                (const double*)K.val.d, Kb.V.d, nnz);
         }
-        if (!h.factor_work.empty()) {
-            FactorArgs fa{};
-            fa.work = factor_work.d; fa.chains = chains.d; fa.levels = levels.d; fa.Hval = K.val.d;
-            fa.pos_diag = kposd.d; fa.pos_sub = kposs.d; fa.fac = fac.d; fa.work_mat = q_work.d; fa.skip = nullptr;
-            fa.diag_pos = kdiagpos.d; fa.dinv = dinv.d;
-            launch_factor(fa, (int)h.factor_work.size(), false);
-        }
+        launch_factor(Kset, nullptr);
         HIP_CHECK(hipGetLastError());
     }
     // ---- segmented long chains (score_join.hpp) ----
@@ -2171,20 +2188,20 @@ struct HipBackend {
         ub_join.reset();
         const size_t b2 = (size_t)h.bs * h.bs, nb = 2 * (size_t)h.bs;
         ZeroGroup zj;
-        zj.add(join_W_K, nb * (size_t)h.n_tot); zj.add(join_rhs, (size_t)h.n_tot); zj.add(join_data_K, 5 * b2 * (size_t)n_join_seps);
+        zj.add(Kset.join_W, nb * (size_t)h.n_tot); zj.add(join_rhs, (size_t)h.n_tot); zj.add(Kset.join_data, 5 * b2 * (size_t)n_join_seps);
         zj.add(join_zero, (size_t)h.count); zj.add(join_zb, (size_t)h.bs * n_join_seps);
         zj.commit(stream);
         join_tmp_p.alloc((size_t)h.n_tot); join_tmp_rz.alloc(h.prec_work.size() + 4096);  // (every workgroup of a chain-kernel launch has a slot: work items + update helpers)
-        join_positions(K.ptr.d, K.col.d, join_posd_K, join_poss_K);
+        join_positions(Kset);
         if (st.verbose) std::fprintf(stderr, "[score setup] long chains: %d in %d segments of <= %d nodes (second level: score_join.hpp)\n",
                                      n_join_chains, n_join_items, seg_max_nodes());
     }
-    void join_positions(const int32_t* ptr, const int32_t* col, DevBuf<int32_t>& posd, DevBuf<int32_t>& poss) {
+    void join_positions(PrecSet& S) {
         const size_t b2 = (size_t)H->bs * H->bs;
-        posd.alloc(2 * (size_t)n_join_seps * b2); poss.alloc(2 * (size_t)n_join_seps * b2);
+        S.join_posd.alloc(2 * (size_t)n_join_seps * b2); S.join_poss.alloc(2 * (size_t)n_join_seps * b2);
         HPosArgs pa{};
-        pa.Hptr = ptr; pa.Hcol = col; pa.node_col = join_pcol.d; pa.prev_col = join_pprev.d;
-        pa.n_nodes = 2 * (int64_t)n_join_seps; pa.bs = H->bs; pa.pos_diag = posd.d; pa.pos_sub = poss.d;
+        pa.Hptr = S.mat.ptr.d; pa.Hcol = S.mat.col.d; pa.node_col = join_pcol.d; pa.prev_col = join_pprev.d;
+        pa.n_nodes = 2 * (int64_t)n_join_seps; pa.bs = H->bs; pa.pos_diag = S.join_posd.d; pa.pos_sub = S.join_poss.d;
         pa.diag_cols = nullptr; pa.n_diag = 0; pa.diag_pos = nullptr;
         hipLaunchKernelGGL(k_hb_positions, dim3((unsigned)((pa.n_nodes * (int64_t)b2 + 255) / 256)), dim3(256), 0, stream, pa);
         HIP_CHECK(hipGetLastError());
@@ -2193,58 +2210,73 @@ struct HipBackend {
         if (!n_join_items) return;
         const size_t b2 = (size_t)h.bs * h.bs, nb = 2 * (size_t)h.bs;
         ZeroGroup zj;
-        zj.add(join_W_H, nb * (size_t)h.n_tot); zj.add(join_data_H, 5 * b2 * (size_t)n_join_seps);
+        zj.add(Hset.join_W, nb * (size_t)h.n_tot); zj.add(Hset.join_data, 5 * b2 * (size_t)n_join_seps);
         zj.commit(stream);
-        join_positions(Hm.ptr.d, Hm.col.d, join_posd_H, join_poss_H);
+        join_positions(Hset);
     }
-    JoinArgs join_args(bool newton_set) {
+    // H->bs as a compile-time constant: f(std::integral_constant<int, BS>) with BS = 1 (bs <= 1), 2, 3 or 4 (everything else)
+    template <class F>
+    void with_bs(F&& f) const {
+        const int bs = H->bs;
+        if (bs <= 1) f(std::integral_constant<int, 1>{});
+        else if (bs == 2) f(std::integral_constant<int, 2>{});
+        else if (bs == 3) f(std::integral_constant<int, 3>{});
+        else f(std::integral_constant<int, 4>{});
+    }
+    // What an application of a set's chain preconditioner reads, whoever asks for it: the caller adds its vectors, partial
+    // sums and flags (r, r_in, z, p, w, xt, kx, pw_part, rz_*, done, gate_*)
+    PrecArgs prec_args(const PrecSet& S) const {
+        PrecArgs pa{};
+        pa.work = prec_work.d; pa.chains = S.chains.d; pa.levels = S.levels.d; pa.rec = S.rec.d; pa.fac = S.fac.d;
+        pa.fac32 = S.fac32.d; pa.deep = S.deep.d;
+        pa.node_col = node_col.d; pa.diag_cols = diag_cols.d; pa.dinv = S.dinv.d;
+        pa.prec_part_ptr = prec_part_ptr.d; pa.kblk_part_ptr = S.blk_part.d; pa.uni = uni_for(S.blocks());
+        return pa;
+    }
+    FactorArgs factor_args(const PrecSet& S, const int32_t* skip) const {
+        FactorArgs fa{};
+        fa.work = S.fac_work.d; fa.chains = S.chains.d; fa.levels = S.levels.d; fa.Hval = S.mat.val.d;
+        fa.pos_diag = S.posd.d; fa.pos_sub = S.poss.d; fa.fac = S.fac.d; fa.work_mat = q_work.d; fa.skip = skip;
+        fa.diag_pos = S.diagpos.d; fa.dinv = S.dinv.d;
+        fa.lds_wmat = factor_lds_wmat;
+        return fa;
+    }
+    JoinArgs join_args(const PrecSet& S) const {
         JoinArgs ja{};
-        ja.jc = join_jc.d; ja.items = join_items.d; ja.chains = newton_set ? chainsH.d : chains.d; ja.node_col = node_col.d;
+        ja.jc = join_jc.d; ja.items = join_items.d; ja.chains = S.chains.d; ja.node_col = node_col.d;
         ja.sep_col = join_sep_col.d; ja.sep_nodes = join_pcol.d; ja.sep_prev = join_pprev.d; ja.done = join_zero.d;
-        ja.use_owner = (!newton_set && H->rep > 1) ? 1 : 0;
-        ja.W = newton_set ? join_W_H.d : join_W_K.d; ja.n_tot = H->n_tot;
-        ja.data = newton_set ? join_data_H.d : join_data_K.d;
-        ja.val = newton_set ? Hm.val.d : K.val.d;
-        ja.pos_diag = newton_set ? join_posd_H.d : join_posd_K.d; ja.pos_sub = newton_set ? join_poss_H.d : join_poss_K.d;
+        ja.use_owner = S.use_owner ? 1 : 0;
+        ja.W = S.join_W.d; ja.n_tot = H->n_tot;
+        ja.data = S.join_data.d;
+        ja.val = S.mat.val.d;
+        ja.pos_diag = S.join_posd.d; ja.pos_sub = S.join_poss.d;
         ja.rhs = join_rhs.d; ja.zb = join_zb.d;
-        ja.sep_diag = join_sep_diag.d; ja.dinv = newton_set ? q_dinv.d : dinv.d; ja.n_sep_entries = (int)H->join_sep_diag.size();
+        ja.sep_diag = join_sep_diag.d; ja.dinv = S.dinv.d; ja.n_sep_entries = (int)H->join_sep_diag.size();
         return ja;
     }
-    template <int BS>
-    void join_refresh_bs(bool newton_set) {
-        JoinArgs ja = join_args(newton_set);
+    void join_refresh(const PrecSet& S) {
+        if (!n_join_items) return;
+        JoinArgs ja = join_args(S);
         hipLaunchKernelGGL(k_join_dinv, dim3((unsigned)((ja.n_sep_entries + kJoinThreads - 1) / kJoinThreads)), dim3(kJoinThreads), 0, stream, ja);
         // the spikes: 2 BS applications of the chain kernel alone to the coupling columns
-        PrecArgs pa{};
-        pa.work = prec_work.d; pa.chains = newton_set ? chainsH.d : chains.d; pa.levels = newton_set ? levelsH.d : levels.d;
-        pa.rec = newton_set ? prec_recH.d : prec_rec.d; pa.fac = newton_set ? q_fac.d : fac.d;
-        pa.node_col = node_col.d; pa.diag_cols = diag_cols.d; pa.dinv = newton_set ? q_dinv.d : dinv.d; pa.done = join_zero.d;
-        pa.prec_part_ptr = prec_part_ptr.d; pa.kblk_part_ptr = newton_set ? q_hblk_part.d : kblk_part_ptr.d;
-        pa.uni = uni_for(newton_set ? hblocks() : kblocks());
+        PrecArgs pa = prec_args(S);
+        pa.done = join_zero.d;
         pa.r = join_rhs.d; pa.r_in = join_rhs.d; pa.p = join_tmp_p.d; pa.w = w.d; pa.xt = join_tmp_p.d; pa.kx = join_tmp_p.d;
         pa.pw_part = nullptr; pa.rz_in = nullptr; pa.rz_out = join_tmp_rz.d;
-        join_suspend = true;
-        for (int c = 0; c < 2 * BS; ++c) {
-            ja.column = c;
-            hipLaunchKernelGGL(k_join_rhs<BS>, dim3((unsigned)((n_join_items * BS + kJoinThreads - 1) / kJoinThreads)), dim3(kJoinThreads), 0, stream, ja, n_join_items);
-            pa.z = ja.W + (size_t)c * (size_t)H->n_tot;
-            launch_prec<PREC_INIT>(pa);
-        }
-        join_suspend = false;
-        hipLaunchKernelGGL(k_join_schur<BS>, dim3((unsigned)((n_join_chains + 63) / 64)), dim3(64), 0, stream, ja, n_join_chains);
+        with_bs([&](auto bs) {
+            constexpr int BS = decltype(bs)::value;
+            for (int c = 0; c < 2 * BS; ++c) {
+                ja.column = c;
+                hipLaunchKernelGGL(k_join_rhs<BS>, dim3((unsigned)((n_join_items * BS + kJoinThreads - 1) / kJoinThreads)), dim3(kJoinThreads), 0, stream, ja, n_join_items);
+                pa.z = ja.W + (size_t)c * (size_t)H->n_tot;
+                launch_prec<PREC_INIT>(S, pa, -1, PrecDepth::chain);
+            }
+            hipLaunchKernelGGL(k_join_schur<BS>, dim3((unsigned)((n_join_chains + 63) / 64)), dim3(64), 0, stream, ja, n_join_chains);
+        });
     }
-    void join_refresh(bool newton_set) {
-        if (!n_join_items) return;
-        switch (H->bs) {
-            case 1: join_refresh_bs<1>(newton_set); break;
-            case 2: join_refresh_bs<2>(newton_set); break;
-            case 3: join_refresh_bs<3>(newton_set); break;
-            default: join_refresh_bs<4>(newton_set); break;
-        }
-    }
-    template <int BS, int MODE>
-    void join_apply_bs(const PrecArgs& pa, bool newton_set) {
-        JoinArgs ja = join_args(newton_set);
+    template <int MODE>
+    void join_apply(const PrecSet& S, const PrecArgs& pa) {
+        JoinArgs ja = join_args(S);
         ja.done = pa.done;
         ja.r = (MODE == PREC_INIT) ? pa.r_in : pa.r;
         ja.z = pa.z; ja.p = pa.p; ja.rz_out = pa.rz_out;
@@ -2254,33 +2286,25 @@ struct HipBackend {
             ja.n_vec = pa.n_vec; ja.vec_stride = pa.vec_stride; ja.zb_stride = (long long)H->bs * n_join_seps; ja.rz_stride = (long long)n_prec;
             ja.zb = link_zb.d;
         }
-        hipLaunchKernelGGL(k_join_solve<BS>, dim3((unsigned)n_join_chains, nv), dim3(64), 0, stream, ja);
-        hipLaunchKernelGGL((k_join_apply<BS, MODE>), dim3((unsigned)n_join_items, nv), dim3(kJoinThreads), 0, stream, ja);
-    }
-    template <int MODE>
-    void join_apply(const PrecArgs& pa, bool newton_set) {
-        switch (H->bs) {
-            case 1: join_apply_bs<1, MODE>(pa, newton_set); break;
-            case 2: join_apply_bs<2, MODE>(pa, newton_set); break;
-            case 3: join_apply_bs<3, MODE>(pa, newton_set); break;
-            default: join_apply_bs<4, MODE>(pa, newton_set); break;
-        }
+        with_bs([&](auto bs) {
+            constexpr int BS = decltype(bs)::value;
+            hipLaunchKernelGGL(k_join_solve<BS>, dim3((unsigned)n_join_chains, nv), dim3(64), 0, stream, ja);
+            hipLaunchKernelGGL((k_join_apply<BS, MODE>), dim3((unsigned)n_join_items, nv), dim3(kJoinThreads), 0, stream, ja);
+        });
     }
 
     // ---- loop closures inside the preconditioners (score_link.hpp): Woodbury correction of the chain solve, for the ADMM
     //      loop's K (set 0) and for the Newton matrix (set 1) -- one plan, the sets' own positions, columns Z and matrices Q ----
     LinkPlan link_plan;
     int n_link_items = 0, n_link_probs = 0, n_link_u = 0, link_rounds = 0, link_max_u = 0;
-    bool link_suspend = false;
-    bool link_set_on[2] = {false, false};
     DevBuf<LinkProb> link_probs;
     DevBuf<LinkItem> link_items;
-    DevBuf<int32_t> link_ucol, link_uround, link_usuper, link_pcol[2], link_pshift[2], link_pos[2], link_zero, link_status[2];
+    DevBuf<int32_t> link_ucol, link_uround, link_usuper, link_zero;
     DevBuf<uint8_t> link_mask;
-    DevBuf<double> link_Qt[2], link_Zr[2], link_t, link_rhs, link_tmp_p, link_tmp_rz, link_zb;
+    DevBuf<double> link_t, link_rhs, link_tmp_p, link_tmp_rz, link_zb;
     void link_init(const HostSystem& h, const score_problem* probs, const score_graph* graphs) {
         n_link_items = n_link_probs = n_link_u = link_rounds = 0;
-        link_set_on[0] = link_set_on[1] = false;
+        Kset.link_on = Hset.link_on = false;
         if (h.chains.empty() || split.active || std::getenv("SCORE_NO_LINKS") != nullptr) return;
         std::vector<int32_t> pairs;
         if (graphs) find_link_pairs_graphs(h, graphs, pairs);
@@ -2307,15 +2331,15 @@ struct HipBackend {
                 if (!sets[set]) continue;
                 std::vector<int32_t> pc((size_t)n_link_u), ps((size_t)n_link_u, 0);
                 for (int u = 0; u < n_link_u; ++u) pc[(size_t)u] = set == 0 ? link_owner_col(h, prob_of[(size_t)u], L.ucol[(size_t)u], &ps[(size_t)u]) : L.ucol[(size_t)u];
-                link_pcol[set].upload(pc); link_pshift[set].upload(ps);
+                pset[set].link_pcol.upload(pc); pset[set].link_pshift.upload(ps);
             }
         }
         ub_link.reset();
         ZeroGroup zl;
         for (int set = 0; set < 2; ++set) {
             if (!sets[set]) continue;
-            link_pos[set].alloc(L.mask.size());
-            zl.add(link_status[set], (size_t)n_link_probs); zl.add(link_Qt[set], L.mask.size()); zl.add(link_Zr[set], (size_t)link_rounds * (size_t)h.n_tot);
+            pset[set].link_pos.alloc(L.mask.size());
+            zl.add(pset[set].link_status, (size_t)n_link_probs); zl.add(pset[set].link_Qt, L.mask.size()); zl.add(pset[set].link_Zr, (size_t)link_rounds * (size_t)h.n_tot);
         }
         zl.add(link_t, (size_t)n_link_u);
         zl.add(link_rhs, (size_t)link_rounds * (size_t)h.n_tot); zl.add(link_zero, (size_t)h.count);
@@ -2327,78 +2351,60 @@ struct HipBackend {
         HIP_CHECK(hipFuncSetAttribute((const void*)k_link_cap<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kLinkMaxU * kLinkMaxU * (int)sizeof(double)));
         for (int set = 0; set < 2; ++set) {
             if (!sets[set]) continue;
-            link_set_on[set] = true;
-            LinkArgs la = link_args(set == 1);
+            pset[set].link_on = true;
+            LinkArgs la = link_args(pset[set]);
             hipLaunchKernelGGL(k_link_positions, dim3(16), dim3(kLinkThreads), 0, stream, la, n_link_probs);
         }
-        LinkArgs la = link_args(false);
+        LinkArgs la = link_args(Kset);
         hipLaunchKernelGGL(k_link_rhs, dim3((unsigned)((n_link_u + kLinkThreads - 1) / kLinkThreads)), dim3(kLinkThreads), 0, stream, la);
         HIP_CHECK(hipGetLastError());
-        link_refresh(false);  // (K's chains were factored before the plan existed; the Newton set's follow its first factorisation)
+        link_refresh(Kset);  // (K's chains were factored before the plan existed; the Newton set's follow its first factorisation)
     }
-    LinkArgs link_args(bool newton_set) {
-        const int set = newton_set ? 1 : 0;
+    LinkArgs link_args(const PrecSet& S) const {
         LinkArgs la{};
         la.probs = link_probs.d; la.items = link_items.d; la.ucol = link_ucol.d; la.uround = link_uround.d; la.usuper = link_usuper.d;
-        la.mask = link_mask.d; la.pcol = link_pcol[set].d; la.pshift = link_pshift[set].d; la.pos = link_pos[set].d;
-        la.Qt = link_Qt[set].d; la.t = link_t.d; la.Zr = link_Zr[set].d; la.rhs = link_rhs.d;
+        la.mask = link_mask.d; la.pcol = S.link_pcol.d; la.pshift = S.link_pshift.d; la.pos = S.link_pos.d;
+        la.Qt = S.link_Qt.d; la.t = link_t.d; la.Zr = S.link_Zr.d; la.rhs = link_rhs.d;
         la.n_tot = H->n_tot; la.rounds = link_rounds; la.n_u_total = n_link_u;
-        if (newton_set) { la.Hptr = Hm.ptr.d; la.Hcol = Hm.col.d; la.Hval = Hm.val.d; }
-        else { la.Hptr = K.ptr.d; la.Hcol = K.col.d; la.Hval = K.val.d; }
-        la.chains = newton_set ? chainsH.d : chains.d; la.node_col = node_col.d; la.done = link_zero.d; la.status = link_status[set].d;
+        la.Hptr = S.mat.ptr.d; la.Hcol = S.mat.col.d; la.Hval = S.mat.val.d;
+        la.chains = S.chains.d; la.node_col = node_col.d; la.done = link_zero.d; la.status = S.link_status.d;
         return la;
     }
     // after every factorisation of a set's chains: the columns Z = T^-1 U (one application of the chain kernel -- second level
     // included -- to every round's right-hand side at once) and Q = (I + G Z[U,:])^-1 G
-    void link_refresh(bool newton_set) {
-        if (!n_link_items || !link_set_on[newton_set ? 1 : 0]) return;
-        LinkArgs la = link_args(newton_set);
-        PrecArgs pa{};
-        pa.work = prec_work.d; pa.chains = newton_set ? chainsH.d : chains.d; pa.levels = newton_set ? levelsH.d : levels.d;
-        pa.rec = newton_set ? prec_recH.d : prec_rec.d; pa.fac = newton_set ? q_fac.d : fac.d;
-        pa.node_col = node_col.d; pa.diag_cols = diag_cols.d; pa.dinv = newton_set ? q_dinv.d : dinv.d; pa.done = link_zero.d;
-        pa.prec_part_ptr = prec_part_ptr.d; pa.kblk_part_ptr = newton_set ? q_hblk_part.d : kblk_part_ptr.d;
-        pa.uni = uni_for(newton_set ? hblocks() : kblocks());
+    void link_refresh(const PrecSet& S) {
+        if (!n_link_items || !S.link_on) return;
+        LinkArgs la = link_args(S);
+        PrecArgs pa = prec_args(S);
+        pa.done = link_zero.d;
         pa.r = link_rhs.d; pa.r_in = link_rhs.d; pa.p = link_tmp_p.d; pa.w = w.d; pa.xt = link_tmp_p.d; pa.kx = link_tmp_p.d;
         pa.pw_part = nullptr; pa.rz_in = nullptr; pa.rz_out = link_tmp_rz.d;
         // (the right-hand sides -- unit vectors, round r's in vector r -- were written once, at link_init: the chain kernel does
         //  not touch r_in)
         pa.z = la.Zr;
-        link_suspend = true;
-        if (link_rounds == 1) launch_prec<PREC_INIT>(pa);
-        else {
-            pa.n_vec = link_rounds; pa.vec_stride = (long long)H->n_tot;
-            launch_prec<PREC_INIT>(pa);
-        }
-        link_suspend = false;
+        if (link_rounds > 1) { pa.n_vec = link_rounds; pa.vec_stride = (long long)H->n_tot; }
+        launch_prec<PREC_INIT>(S, pa, -1, PrecDepth::join);
         // (up to 48 unknowns: Gauss-Jordan on one wavefront, no block barriers; beyond: four wavefronts)
         if (link_max_u <= 48) hipLaunchKernelGGL(k_link_cap<true>, dim3((unsigned)n_link_probs), dim3(256), (size_t)2 * link_max_u * link_max_u * sizeof(double), stream, la);
         else hipLaunchKernelGGL(k_link_cap<false>, dim3((unsigned)n_link_probs), dim3(256), (size_t)2 * link_max_u * link_max_u * sizeof(double), stream, la);
     }
-    template <int BS, int MODE>
-    void link_apply_bs(const PrecArgs& pa, bool newton_set) {
-        LinkArgs la = link_args(newton_set);
+    template <int MODE>
+    void link_apply(const PrecSet& S, const PrecArgs& pa) {
+        LinkArgs la = link_args(S);
         la.done = pa.done;
         la.r = (MODE == PREC_INIT) ? pa.r_in : pa.r;
         la.z = pa.z; la.p = pa.p; la.rz_out = pa.rz_out;
-        if (link_plan.max_items <= kLinkGroupItems) {  // (a workgroup per group: t and the group's chains in one launch)
-            hipLaunchKernelGGL((k_link_group<BS, MODE>), dim3((unsigned)n_link_probs), dim3(kLinkApplyThreads), 0, stream, la);
-            return;
-        }
-        hipLaunchKernelGGL(k_link_solve, dim3((unsigned)n_link_probs), dim3(128), 0, stream, la);
-        hipLaunchKernelGGL((k_link_apply<BS, MODE>), dim3((unsigned)n_link_items), dim3(kLinkApplyThreads), 0, stream, la);
-    }
-    template <int MODE>
-    void link_apply(const PrecArgs& pa, bool newton_set) {
-        switch (H->bs) {
-            case 1: link_apply_bs<1, MODE>(pa, newton_set); break;
-            case 2: link_apply_bs<2, MODE>(pa, newton_set); break;
-            case 3: link_apply_bs<3, MODE>(pa, newton_set); break;
-            default: link_apply_bs<4, MODE>(pa, newton_set); break;
-        }
+        with_bs([&](auto bs) {
+            constexpr int BS = decltype(bs)::value;
+            if (link_plan.max_items <= kLinkGroupItems) {  // (a workgroup per group: t and the group's chains in one launch)
+                hipLaunchKernelGGL((k_link_group<BS, MODE>), dim3((unsigned)n_link_probs), dim3(kLinkApplyThreads), 0, stream, la);
+                return;
+            }
+            hipLaunchKernelGGL(k_link_solve, dim3((unsigned)n_link_probs), dim3(128), 0, stream, la);
+            hipLaunchKernelGGL((k_link_apply<BS, MODE>), dim3((unsigned)n_link_items), dim3(kLinkApplyThreads), 0, stream, la);
+        });
     }
 
-    int n_prec_items() const { return (int)H->prec_work.size(); }
     // k_factor keeps the level-to-level matrices in LDS when the longest chain fits
     int factor_lds_wmat = 0;
     size_t factor_lds_bytes = 0;
@@ -2421,40 +2427,33 @@ struct HipBackend {
             HIP_CHECK(hipFuncSetAttribute((const void*)k_factor<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
         }
     }
-    void launch_factor_kernels(const FactorArgs& fa, int np) {
-        const int bs = H->bs;
-        if (bs <= 1) hipLaunchKernelGGL(k_factor<1>, dim3(np), dim3(kThreads), factor_lds_bytes, stream, fa);
-        else if (bs == 2) hipLaunchKernelGGL(k_factor<2>, dim3(np), dim3(kThreads), factor_lds_bytes, stream, fa);
-        else if (bs == 3) hipLaunchKernelGGL(k_factor<3>, dim3(np), dim3(kThreads), factor_lds_bytes, stream, fa);
-        else hipLaunchKernelGGL(k_factor<4>, dim3(np), dim3(kThreads), factor_lds_bytes, stream, fa);
-    }
-    // newton_set: the factors of the Newton matrix (every chain its own: chainsH / levelsH / q_fac)
-    void launch_factor(FactorArgs fa, int np, bool newton_set) {
+    // One factorisation of a set's chains from its matrix' present values (skip: per problem, leave its factors alone), the
+    // float copies its applications read, and the second level and the loop-closure correction that rest on the factors
+    void launch_factor(const PrecSet& S, const int32_t* skip) {
+        const int np = (int)S.fac_work.n;
         if (np == 0) return;
-        fa.lds_wmat = factor_lds_wmat;
+        FactorArgs fa = factor_args(S, skip);
         const int bs = H->bs;
         if (np > 65535) throw std::runtime_error("too many preconditioner work items for one handle (65535): split the batch");
-        const int64_t nf = (int64_t)(newton_set ? H->fac_doubles_H : H->fac_doubles);
         // When every application of this factor set goes through k_prec_pre<.., float> (the 4-byte stream), k_factor writes the
         // float copy itself and nobody reads the doubles: no rounding launch (33 us a time on the headline problem, seven times
         // per default solve).  The streaming kernel reads `fac`: then the factors are rounded in place as before.
-        const bool want32 = (newton_set ? newton_fac32 : use_fac32) && nf > 0;
+        const bool want32 = S.use_fac32 && S.fac_doubles > 0;
         const bool direct32 = want32 && prec_pre && !split.active;
-        fa.fac32 = direct32 ? (newton_set ? q_fac32.d : fac32.d) : nullptr;
-        launch_factor_kernels(fa, np);
+        fa.fac32 = direct32 ? S.fac32.d : nullptr;
+        with_bs([&](auto b) { hipLaunchKernelGGL(k_factor<decltype(b)::value>, dim3(np), dim3(kThreads), factor_lds_bytes, stream, fa); });
         if (want32) {
-            float* shadow = newton_set ? q_fac32.d : fac32.d;
             if (!direct32)
             // (chain by chain, honouring the launch's skip flags: the Newton polish re-factors only the problems whose
             //  active set has moved, and rounding the whole array again cost as much as re-factoring them)
             hipLaunchKernelGGL(k_fac_round_items, dim3(16, (unsigned)np), dim3(kThreads), 0, stream, fa.work,
-                               (const int64_t*)(newton_set ? fac_rangeH.d : fac_rangeK.d), fa.skip, fa.fac, shadow);
+                               (const int64_t*)S.fac_range.d, fa.skip, fa.fac, S.fac32.d);
             if (prec_reg)  // ... and the lane-major copy of the coarse levels the register-resident chain kernel loads
                 hipLaunchKernelGGL(k_deep_pack, dim3((unsigned)(deep_padded_slots(bs) / 4), (unsigned)np), dim3(kThreads), 0, stream, fa.work, fa.chains,
-                                   fa.levels, (const int32_t*)deep_map.d, (const float*)shadow, newton_set ? deepH.d : deepK.d, fa.skip, bs * bs);
+                                   fa.levels, (const int32_t*)deep_map.d, (const float*)S.fac32.d, S.deep.d, fa.skip, bs * bs);
         }
-        join_refresh(newton_set);  // (segmented long chains: separators' inverse diagonals, spikes, Schur factors)
-        link_refresh(newton_set);  // (loop closures: the Woodbury columns and the capacitance matrix, score_link.hpp)
+        join_refresh(S);  // (segmented long chains: separators' inverse diagonals, spikes, Schur factors)
+        link_refresh(S);  // (loop closures: the Woodbury columns and the capacitance matrix, score_link.hpp)
     }
 
     ConeArgs cone_args(const double* gathered) {
@@ -2469,8 +2468,8 @@ struct HipBackend {
         a.s_in = a.s; a.y_in = a.y;
         a.alpha_relax = st.alpha; a.invE = invE.d; a.pres_part = pres_part.d;
         a.apply_alpha = 0; a.pfin = p.d; a.pw_in = pw_part.d; a.rz_in = rz_part0.d;
-        a.prec_part_ptr = prec_part_ptr.d; a.kblk_part_ptr = kblk_part_ptr.d; a.step_out = step.d;
-        a.uni = uni_for(kblocks());
+        a.prec_part_ptr = prec_part_ptr.d; a.kblk_part_ptr = Kset.blk_part.d; a.step_out = step.d;
+        a.uni = uni_for(Kset.blocks());
         a.skip_large = n_large_cones > 0 ? 1 : 0;
         return a;
     }
@@ -2621,14 +2620,11 @@ struct HipBackend {
             hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, args...);
     }
 
+    // One application of set S's preconditioner; pa: prec_args(S) plus the caller's vectors.  depth: where to stop (the
+    // refreshes of the second level and of the loop-closure correction apply the levels below their own).
     template <int MODE>
-    void launch_prec(const PrecArgs& pa_in, int slot = -1) {
+    void launch_prec(const PrecSet& S, const PrecArgs& pa, int slot = -1, PrecDepth depth = PrecDepth::all) {
         if (n_prec == 0) return;
-        PrecArgs pa = pa_in;
-        const bool newton_set = (pa.fac == q_fac.d) && q_fac.d;
-        pa.fac32 = newton_set ? q_fac32.d : fac32.d;  // the float copy of whichever factor set is applied
-        pa.deep = newton_set ? deepH.d : deepK.d;
-        const bool use_fac32 = newton_set ? newton_fac32 : this->use_fac32;
         if (split.active) {
             if (pa.n_vec > 1) throw std::runtime_error("internal: several right-hand sides through the split chain kernel");
             WaveArgs wa{};
@@ -2637,17 +2633,12 @@ struct HipBackend {
             wa.items = split_items.d; wa.plans = split_plans.d; wa.stage_rel = split_stage.d;
             wa.xbuf = split_xbuf.d; wa.xflag = split_xflag.d; wa.epoch = split_epoch.d; wa.poll_limit = split_poll_limit;
             launch_on_stream(k_prec_wave<MODE>, dim3(n_prec), dim3(kWaveThreads), split_lds, slot, wa);
-        } else {
-            const int bs = H->bs;
-            if (bs <= 1) launch_prec_bs<1, MODE>(pa, slot, use_fac32);
-            else if (bs == 2) launch_prec_bs<2, MODE>(pa, slot, use_fac32);
-            else if (bs == 3) launch_prec_bs<3, MODE>(pa, slot, use_fac32);
-            else launch_prec_bs<4, MODE>(pa, slot, use_fac32);
-        }
+        } else with_bs([&](auto bs) { launch_prec_bs<decltype(bs)::value, MODE>(pa, slot, S.use_fac32); });
+        if (pa.debug_skip) return;
         // segmented long chains: the second level (score_join.hpp) after every application of the chain kernel
-        if (n_join_items && !join_suspend && !pa.debug_skip) join_apply<MODE>(pa, newton_set);
-        // loop closures (score_link.hpp): the Woodbury correction of the Newton set's chain solve
-        if (n_link_items && link_set_on[newton_set ? 1 : 0] && !link_suspend && !join_suspend && !pa.debug_skip) link_apply<MODE>(pa, newton_set);
+        if (n_join_items && depth >= PrecDepth::join) join_apply<MODE>(S, pa);
+        // loop closures (score_link.hpp): the Woodbury correction of the set's chain solve
+        if (n_link_items && S.link_on && depth == PrecDepth::all) link_apply<MODE>(S, pa);
     }
     template <int BS, int MODE>
     void launch_prec_bs(const PrecArgs& pa_in, int slot, bool use_fac32) {
@@ -2787,10 +2778,10 @@ struct HipBackend {
         if (Hb.on) { for (double b : Hb.L.bytes) hbytes += b; }
         else hbytes = 12.0 * (double)hm_nnz + 4.0 * (double)(h.n_tot + 1);
         hbytes += 40.0 * (double)h.n_tot;
-        const double fbytes = (newton_fac32 ? 4.0 : 8.0) * (double)h.fac_doubles_H;
+        const double fbytes = (Hset.use_fac32 ? 4.0 : 8.0) * (double)Hset.fac_doubles;
         np_out[0] = cnt[0]; np_out[1] = cnt[0] ? sum[0] / cnt[0] : 0.0; np_out[2] = hbytes;
         np_out[3] = cnt[1]; np_out[4] = cnt[1] ? sum[1] / cnt[1] : 0.0; np_out[5] = fbytes;
-        np_out[6] = (double)hblocks(); np_out[7] = (double)n_prec;
+        np_out[6] = (double)Hset.blocks(); np_out[7] = (double)n_prec;
         for (hipEvent_t e : np_ev) (void)hipEventDestroy(e);
         np_ev.clear(); np_slots.clear();
         np_armed = false;
@@ -2817,8 +2808,8 @@ struct HipBackend {
         a.n_tiles = M.nblocks;  // (a launch through xcd_grid restates it)
         a.x = xy.d; a.q = q.d; a.kx = kx.d; a.r = r.d; a.sigma = H->sigma;
         a.p = p.d; a.w = w.d; a.pw_part = pw_part.d;
-        a.prec_part_ptr = prec_part_ptr.d; a.kblk_part_ptr = kblk_part_ptr.d;
-        a.uni = uni_for(kblocks());
+        a.prec_part_ptr = prec_part_ptr.d; a.kblk_part_ptr = Kset.blk_part.d;
+        a.uni = uni_for(Kset.blocks());
         a.apply_update = 0; a.pfin = p.d; a.wfin = w.d; a.xt_rw = xtu.d; a.kx_rw = kx.d; a.x_rw = xy.d;
         a.alpha_relax = st.alpha; a.step_in = step.d;
         a.invD = invD.d; a.dres_part = dres_part.d;
@@ -2877,10 +2868,8 @@ struct HipBackend {
             ra.pfin = last_p;
             launch_spmv<MODE_RHS>(G1, ra, 0);
         }
-        PrecArgs pa{};
-        pa.work = prec_work.d; pa.chains = chains.d; pa.levels = levels.d; pa.rec = prec_rec.d; pa.fac = fac.d;
-        pa.node_col = node_col.d; pa.diag_cols = diag_cols.d; pa.dinv = dinv.d; pa.done = done.d;
-        pa.prec_part_ptr = prec_part_ptr.d; pa.kblk_part_ptr = kblk_part_ptr.d; pa.uni = uni_for(kblocks());
+        PrecArgs pa = prec_args(Kset);
+        pa.done = done.d;
         pa.r = r.d; pa.r_in = r.d; pa.z = z.d; pa.p = p.d; pa.w = w.d; pa.xt = xtu.d; pa.kx = kx.d;
         pa.pw_part = pw_part.d;
         double* rz_cur = measure ? rz_meas0.d : rz_part0.d;
@@ -2888,13 +2877,13 @@ struct HipBackend {
         double* p_oth = p2.d;
         pa.p = p_cur; pa.rz_in = nullptr; pa.rz_out = rz_cur;
         pa.tstamp = slot(1);
-        launch_prec<PREC_INIT>(pa, 1);
+        launch_prec<PREC_INIT>(Kset, pa, 1);
         launch_kp(p_cur, slot(2), 2);
         for (int j = 2; j <= cg_iters; ++j) {
             double* rz_nxt = (rz_cur == rz_part0.d) ? rz_part1.d : rz_part0.d;
             pa.p = p_cur; pa.rz_in = rz_cur; pa.rz_out = rz_nxt;
             pa.tstamp = (j == 2) ? slot(3) : nullptr;
-            launch_prec<PREC_STEP>(pa, (j == 2) ? 3 : -1);
+            launch_prec<PREC_STEP>(Kset, pa, (j == 2) ? 3 : -1);
             launch_kpb(p_cur, p_oth, rz_nxt, rz_cur, (j == 2) ? slot(4) : nullptr, (j == 2) ? 4 : -1);
             std::swap(p_cur, p_oth);
             rz_cur = rz_nxt;
@@ -2904,10 +2893,10 @@ struct HipBackend {
         if (measure) {
             pa.tstamp = nullptr;
             pa.p = p_cur; pa.rz_in = rz_cur; pa.rz_out = rz_meas1.d;
-            launch_prec<PREC_STEP>(pa);  // also applies xt += a p, kx += a w, r -= a w
+            launch_prec<PREC_STEP>(Kset, pa);  // also applies xt += a p, kx += a w, r -= a w
             VecArgs va{};
             va.first_row = vb_first.d; va.end_row = vb_end.d; va.blk_prob = vb_prob.d; va.done = done.d;
-            va.prec_part_ptr = prec_part_ptr.d; va.kblk_part_ptr = kblk_part_ptr.d;
+            va.prec_part_ptr = prec_part_ptr.d; va.kblk_part_ptr = Kset.blk_part.d;
             va.pw_part = pw_part.d; va.p = p_cur; va.w = w.d; va.kx = kx.d; va.xt = xtu.d; va.x = xy.d;
             va.alpha_relax = st.alpha; va.rz_old = rz_cur; va.apply_alpha = 0;
             hipLaunchKernelGGL(k_xupdate, dim3(n_vblocks), dim3(kThreads), 0, stream, va);
@@ -2943,7 +2932,7 @@ struct HipBackend {
         HIP_CHECK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, st.device));
         if (khz <= 0) throw std::runtime_error("score_time_iteration: no wall clock rate");
         for (int k = 0; k < 12; ++k) us[k] = 0.0;
-        const int maxb = std::max(std::max(G1.nblocks, kblocks()) + 8, std::max(n_prec + n_help, n_cone_blocks + 8));  // (grids: XCD rounding, update helpers)
+        const int maxb = std::max(std::max(G1.nblocks, Kset.blocks()) + 8, std::max(n_prec + n_help, n_cone_blocks + 8));  // (grids: XCD rounding, update helpers)
         ts_stride = (size_t)2 * maxb;
         const size_t per_iter = 6 * ts_stride, nslot = per_iter * iters;
         {
@@ -3253,8 +3242,8 @@ struct HipBackend {
                 std::vector<int32_t> stt((size_t)n_link_probs);
                 HIP_CHECK(sync_stream(stream));
                 for (int set = 0; set < 2; ++set) {
-                    if (!link_set_on[set]) continue;
-                    HIP_CHECK(hipMemcpy(stt.data(), link_status[set].d, sizeof(int32_t) * (size_t)n_link_probs, hipMemcpyDeviceToHost));
+                    if (!pset[set].link_on) continue;
+                    HIP_CHECK(hipMemcpy(stt.data(), pset[set].link_status.d, sizeof(int32_t) * (size_t)n_link_probs, hipMemcpyDeviceToHost));
                     for (int32_t x : stt) v[5] += x;
                 }
             }
@@ -3267,7 +3256,7 @@ struct HipBackend {
             if (out) for (int64_t i = 0; i < np_ && i < len; ++i) out[i] = (double)pc[(size_t)i];
             return np_;
         }
-        else if (nm == "fac") { src = fac.d; sz = (int64_t)h.fac_doubles; }
+        else if (nm == "fac") { src = Kset.fac.d; sz = (int64_t)Kset.fac_doubles; }
         else if (nm == "newton_probe_arm") {  // the next polish times its PCG launches (see probe_slot)
             if (!Q.available) return -1;
             if (out && len > 0) {
@@ -3356,9 +3345,9 @@ struct HipBackend {
                 out[7] = mism(down_i(q_ccone.d, nc), R.ccone);
                 out[8] = mism(down_i(q_cab.d, nc), R.cab);
                 out[9] = maxd(down_d(q_ccoef.d, nc), R.ccoef);
-                out[10] = mism(down_i(q_posd.d, R.pos_diag.size()), R.pos_diag);
-                out[11] = mism(down_i(q_poss.d, R.pos_sub.size()), R.pos_sub);
-                out[12] = mism(down_i(q_diagpos.d, R.diag_pos.size()), R.diag_pos);
+                out[10] = mism(down_i(Hset.posd.d, R.pos_diag.size()), R.pos_diag);
+                out[11] = mism(down_i(Hset.poss.d, R.pos_sub.size()), R.pos_sub);
+                out[12] = mism(down_i(Hset.diagpos.d, R.diag_pos.size()), R.diag_pos);
                 out[13] = mism(Q.long_ent, R.long_ent) + mism(Q.long_prob, R.long_prob);
             }
             return 14;
@@ -3397,13 +3386,11 @@ struct HipBackend {
             // the chain kernel the PCG uses
             if (!Q.available) return -1;
             if (out && len > 0) {
-                PrecArgs pa{};
-                pa.work = prec_work.d; pa.chains = chainsH.d; pa.levels = levelsH.d; pa.rec = prec_recH.d; pa.fac = q_fac.d;
-                pa.node_col = node_col.d; pa.diag_cols = diag_cols.d; pa.dinv = q_dinv.d; pa.done = q_skip.d;
-                pa.prec_part_ptr = prec_part_ptr.d; pa.kblk_part_ptr = q_hblk_part.d; pa.uni = uni_for(hblocks());
+                PrecArgs pa = prec_args(Hset);
+                pa.done = q_skip.d;
                 pa.r = r.d; pa.r_in = q_negg.d; pa.z = z.d; pa.p = p.d; pa.w = w.d; pa.xt = q_delta.d; pa.kx = q_dummy.d;
                 pa.pw_part = q_pw.d; pa.rz_in = nullptr; pa.rz_out = rz_part0.d;
-                launch_prec<PREC_INIT>(pa);
+                launch_prec<PREC_INIT>(Hset, pa);
             }
             src = z.d; sz = h.n_tot;
         }
@@ -3496,10 +3483,8 @@ struct HipBackend {
         const double tol2 = rel_tol * rel_tol;
         HIP_CHECK(hipMemcpyAsync(lin_tol2.d, &tol2, sizeof(double), hipMemcpyHostToDevice, stream));
         HIP_CHECK(hipMemsetAsync(lin_flag.d, 0, 2 * sizeof(int32_t), stream));
-        PrecArgs pa{};
-        pa.work = prec_work.d; pa.chains = chains.d; pa.levels = levels.d; pa.rec = prec_rec.d; pa.fac = fac.d;
-        pa.node_col = node_col.d; pa.diag_cols = diag_cols.d; pa.dinv = dinv.d; pa.done = lin_flag.d;
-        pa.prec_part_ptr = prec_part_ptr.d; pa.kblk_part_ptr = kblk_part_ptr.d; pa.uni = uni_for(kblocks());
+        PrecArgs pa = prec_args(Kset);
+        pa.done = lin_flag.d;
         pa.r = r.d; pa.r_in = rhs_dev; pa.z = z.d; pa.w = w.d; pa.xt = xtu.d; pa.kx = kx.d; pa.pw_part = pw_part.d;
         pa.gate_used = lin_flag.d + 1;
         pa.early_done = 1;
@@ -3507,7 +3492,7 @@ struct HipBackend {
         double* p_cur = p.d;
         double* p_oth = p2.d;
         pa.p = p_cur; pa.rz_in = nullptr; pa.rz_out = rz_cur;
-        launch_prec<PREC_INIT>(pa);  // z = M^-1 rhs, p = z
+        launch_prec<PREC_INIT>(Kset, pa);  // z = M^-1 rhs, p = z
         {
             SpmvArgs a = spmv_args(K, p_cur);
             a.p = p_cur; a.done = lin_flag.d;
@@ -3525,7 +3510,7 @@ struct HipBackend {
                 pa.gate_first = first ? 1 : 0;
                 pa.r_in = first ? rhs_dev : r.d;
                 pa.xt_zero = first ? 1 : 0;
-                launch_prec<PREC_STEP>(pa);  // x += a p ; r -= a w ; z = M^-1 r   (or the gate fires)
+                launch_prec<PREC_STEP>(Kset, pa);  // x += a p ; r -= a w ; z = M^-1 r   (or the gate fires)
                 SpmvArgs a = spmv_args(K, p_cur);
                 a.p = p_cur; a.z = z.d; a.p_out = p_oth; a.rz_new = rz_nxt; a.rz_old = rz_cur; a.done = lin_flag.d;
                 a.early_done = 1;
@@ -3572,7 +3557,7 @@ struct HipBackend {
         }
         q_Pon.alloc((size_t)rec_max); q_cptr.alloc((size_t)rec_max + 1);
         q_ccone.alloc((size_t)std::max<int64_t>(1, con_max)); q_cab.alloc((size_t)std::max<int64_t>(1, con_max)); q_ccoef.alloc((size_t)std::max<int64_t>(1, con_max));
-        q_posd.alloc(h.node_col.size() * (size_t)b2); q_poss.alloc(h.node_col.size() * (size_t)b2); q_diagpos.alloc(h.diag_cols.size());
+        Hset.posd.alloc(h.node_col.size() * (size_t)b2); Hset.poss.alloc(h.node_col.size() * (size_t)b2); Hset.diagpos.alloc(h.diag_cols.size());
         std::vector<long long> res(3, 0);
         std::vector<int32_t> longs((size_t)long_max);
         Q.Hm.nrows = Q.Hm.ncols = n;
@@ -3651,8 +3636,8 @@ struct HipBackend {
             hipLaunchKernelGGL(k_hb_rows, dim3(grec), dim3(256), 0, stream, sa);
             HPosArgs pa{};
             pa.Hptr = Hm.ptr.d; pa.Hcol = Hm.col.d; pa.node_col = node_col.d; pa.prev_col = prev_col.d;
-            pa.n_nodes = (int64_t)h.node_col.size(); pa.bs = bs; pa.pos_diag = q_posd.d; pa.pos_sub = q_poss.d;
-            pa.diag_cols = diag_cols.d; pa.n_diag = (int64_t)h.diag_cols.size(); pa.diag_pos = q_diagpos.d;
+            pa.n_nodes = (int64_t)h.node_col.size(); pa.bs = bs; pa.pos_diag = Hset.posd.d; pa.pos_sub = Hset.poss.d;
+            pa.diag_cols = diag_cols.d; pa.n_diag = (int64_t)h.diag_cols.size(); pa.diag_pos = Hset.diagpos.d;
             const int64_t npos = std::max<int64_t>(pa.n_nodes * b2, pa.n_diag);
             if (npos > 0) hipLaunchKernelGGL(k_hb_positions, dim3((unsigned)((npos + 255) / 256)), dim3(256), 0, stream, pa);
             HIP_CHECK(hipGetLastError());
@@ -3769,7 +3754,7 @@ struct HipBackend {
             q_Pon.upload(Q.Pon); q_ccoef.upload(Q.ccoef); q_cptr.upload(Q.cptr); q_ccone.upload(Q.ccone); q_cab.upload(Q.cab);
             q_head.upload(Q.head_col); q_ishead.upload(Q.is_head); q_aabs.upload(Q.a_abs); q_ck.upload(Q.ck);
             q_theta.upload(Q.theta); q_xstar.upload(Q.xstar);
-            q_posd.upload(Q.pos_diag); q_poss.upload(Q.pos_sub); q_diagpos.upload(Q.diag_pos);
+            Hset.posd.upload(Q.pos_diag); Hset.poss.upload(Q.pos_sub); Hset.diagpos.upload(Q.diag_pos);
         }
         pt.mark("  polish: uploads");
         std::optional<UploadBatch> ub_polish;  // (tables and zeroed buffers only from here to join_init_newton: nothing is launched)
@@ -3778,7 +3763,7 @@ struct HipBackend {
         if (st.verbose)
             std::fprintf(stderr, "[score setup] band view of H: %s (%d band + %d csr + %d diag tiles, %d slots per row)\n", Hb.on ? "on" : "off",
                          Hb.L.n_band, Hb.L.n_csr, Hb.L.n_diag, Hb.L.S);
-        q_hblk_part.upload(Hb.on ? Hb.L.part_ptr : Q.rbH.part_ptr);
+        Hset.blk_part.upload(Hb.on ? Hb.L.part_ptr : Q.rbH.part_ptr);
         {   // entry range of every problem in H (k_hassemble runs problem by problem)
             std::vector<int64_t> ep((size_t)h.count + 1);
             q_ent_max = 0;
@@ -3795,13 +3780,13 @@ struct HipBackend {
         n_fpart = 2 * std::max<size_t>((nc + kThreads - 1) / kThreads, (size_t)n_cone_blocks);  // F partials, then active-set flips
         q_X0.alloc(h.n_tot + h.m_tot); q_X1.alloc(h.n_tot + h.m_tot);
         q_g.alloc(h.n_tot); q_delta.alloc(h.n_tot); q_dummy.alloc(h.n_tot); q_negg.alloc(h.n_tot);
-        q_dinv.alloc(h.dinv.size());
-        zq.add(q_fac, h.fac_doubles_H);  // separator slots of the spike region are never written (nor used)
-        if (newton_fac32) zq.add(q_fac32, h.fac_doubles_H);
+        Hset.dinv.alloc(h.dinv.size());
+        zq.add(Hset.fac, Hset.fac_doubles);  // separator slots of the spike region are never written (nor used)
+        if (Hset.use_fac32) zq.add(Hset.fac32, Hset.fac_doubles);
         zq.commit(stream);
-        if (newton_fac32 && prec_reg) deepH.alloc((size_t)std::max<int64_t>(1, h.deep_floats_H));
+        if (Hset.use_fac32 && prec_reg) Hset.deep.alloc((size_t)std::max<int64_t>(1, Hset.deep_floats));
         n_gd = std::max<size_t>((h.n_tot + kThreads - 1) / kThreads, (size_t)Hm.nblocks);
-        q_pw.alloc(hblocks());
+        q_pw.alloc(Hset.blocks());
         {
             q_gate_ref.alloc(h.count);
             std::vector<int64_t> sb(2 * h.count), se(2 * h.count);
@@ -3853,7 +3838,7 @@ struct HipBackend {
         ha.nnz = hm_nnz; ha.Pon = q_Pon.d; ha.cptr = q_cptr.d; ha.ccone = q_ccone.d; ha.cab = q_cab.d;
         ha.ccoef = q_ccoef.d; ha.Bbuf = q_Bbuf.d; ha.T2 = Q.T * Q.T; ha.Hval = Hm.val.d;
         ha.dst = Hb.on ? Hb.dst.d : nullptr; ha.V = Hb.on ? Hb.V.d : nullptr;
-        ha.ndiag = (int)h.diag_cols.size(); ha.diag_pos = q_diagpos.d; ha.dinv = q_dinv.d;
+        ha.ndiag = (int)h.diag_cols.size(); ha.diag_pos = Hset.diagpos.d; ha.dinv = Hset.dinv.d;
         ha.ent_part = q_entpart.d; ha.skip = q_skip.d;  // (the live mask: a frozen problem's matrix is not read any more)
         const int base_blocks = (int)((q_ent_max + kThreads - 1) / kThreads);
         hipLaunchKernelGGL(k_hassemble, dim3((unsigned)((int64_t)base_blocks * h.count + n_long)), dim3(kThreads), 0, stream, ha, (const int32_t*)q_long.d,
@@ -3863,13 +3848,7 @@ struct HipBackend {
     void newton_hessian(const int32_t* skip = nullptr, bool refactor = true) {
         if (!hassemble_queued) launch_hassemble();  // (queued ahead by prequeue_control() otherwise)
         hassemble_queued = false;
-        if (n_prec_items() && refactor) {  // chain factors and the reciprocal Jacobi diagonal, one launch
-            FactorArgs fa{};
-            fa.work = prec_work.d; fa.chains = chainsH.d; fa.levels = levelsH.d; fa.Hval = Hm.val.d;
-            fa.pos_diag = q_posd.d; fa.pos_sub = q_poss.d; fa.fac = q_fac.d; fa.work_mat = q_work.d; fa.skip = skip;
-            fa.diag_pos = q_diagpos.d; fa.dinv = q_dinv.d;
-            launch_factor(fa, n_prec_items(), true);
-        }
+        if (refactor) launch_factor(Hset, skip);  // chain factors and the reciprocal Jacobi diagonal, one launch
     }
 
     // ---- Newton polish, all problems of the handle in lock-step (a single problem is a batch of
@@ -4019,10 +3998,8 @@ struct HipBackend {
     void newton_pcg_begin() {
         const HostSystem& h = *H;
         PrecArgs& pa = pcg_pa;
-        pa = PrecArgs{};
-        pa.work = prec_work.d; pa.chains = chainsH.d; pa.levels = levelsH.d; pa.rec = prec_recH.d; pa.fac = q_fac.d;
-        pa.node_col = node_col.d; pa.diag_cols = diag_cols.d; pa.dinv = q_dinv.d; pa.done = q_skip.d;
-        pa.prec_part_ptr = prec_part_ptr.d; pa.kblk_part_ptr = q_hblk_part.d; pa.uni = uni_for(hblocks());
+        pa = prec_args(Hset);
+        pa.done = q_skip.d;
         pa.r = r.d; pa.r_in = r.d; pa.z = z.d; pa.w = w.d; pa.xt = q_delta.d; pa.kx = q_dummy.d; pa.pw_part = q_pw.d;
         pa.gate_used = q_gate_used.d;
         pa.early_done = 1;  // launches queued beyond the gate are no-ops: keep them cheap
@@ -4036,7 +4013,7 @@ struct HipBackend {
             pa.p = pcg_p_cur; pa.rz_in = nullptr; pa.rz_out = pcg_rz_cur;
             pa.r_in = q_negg.d;
             pa.gate_init = q_pcgdone.d;  // gate flags start as the host's skip flags
-            launch_prec<PREC_INIT>(pa);
+            launch_prec<PREC_INIT>(Hset, pa);
             pa.gate_init = nullptr;
             SpmvArgs a = spmv_args(Hm, pcg_p_cur);
             a.p = pcg_p_cur; a.pw_part = q_pw.d; a.done = q_skip.d;
@@ -4058,7 +4035,7 @@ struct HipBackend {
         pa.gate_first = first ? 1 : 0;
         pa.r_in = first ? q_negg.d : r.d;
         pa.xt_zero = first ? 1 : 0;
-        launch_prec<PREC_STEP>(pa, probe_slot(1, pcg_steps_queued));
+        launch_prec<PREC_STEP>(Hset, pa, probe_slot(1, pcg_steps_queued));
         tev = nullptr;
         SpmvArgs a = spmv_args(Hm, pcg_p_cur);
         a.p = pcg_p_cur; a.z = z.d; a.p_out = pcg_p_oth; a.rz_new = rz_nxt; a.rz_old = pcg_rz_cur; a.pw_part = q_pw.d; a.done = q_pcgdone.d;
@@ -4316,28 +4293,26 @@ struct HipBackend {
     }
 
     void time_kernel(const std::string& which, int reps, double* ms) {
-        PrecArgs pa{};
-        pa.work = prec_work.d; pa.chains = chains.d; pa.levels = levels.d; pa.rec = prec_rec.d; pa.fac = fac.d;
-        pa.node_col = node_col.d; pa.diag_cols = diag_cols.d; pa.dinv = dinv.d; pa.done = done.d;
-        pa.prec_part_ptr = prec_part_ptr.d; pa.kblk_part_ptr = kblk_part_ptr.d; pa.uni = uni_for(kblocks());
+        PrecArgs pa = prec_args(Kset);
+        pa.done = done.d;
         pa.r = r.d; pa.r_in = r.d; pa.z = z.d; pa.p = p.d; pa.w = w.d; pa.xt = xtu.d; pa.kx = kx.d;
         pa.pw_part = pw_part.d; pa.rz_in = rz_part0.d; pa.rz_out = rz_part1.d;
         VecArgs va{};
         va.first_row = vb_first.d; va.end_row = vb_end.d; va.blk_prob = vb_prob.d; va.done = done.d;
-        va.prec_part_ptr = prec_part_ptr.d; va.kblk_part_ptr = kblk_part_ptr.d;
+        va.prec_part_ptr = prec_part_ptr.d; va.kblk_part_ptr = Kset.blk_part.d;
         va.pw_part = pw_part.d; va.p = p.d; va.w = w.d; va.kx = kx.d; va.xt = xtu.d; va.x = xy.d;
         va.alpha_relax = st.alpha; va.rz_old = rz_part0.d; va.apply_alpha = 1;
         auto once = [&]() {
             if (which == "rhs") { SpmvArgs ra = spmv_args(G1, xtu.d); ra.apply_update = 1; launch_spmv<MODE_RHS>(G1, ra); }
-            else if (which.rfind("prec_init:", 0) == 0) { pa.debug_skip = std::atoi(which.c_str() + 10); launch_prec<PREC_INIT>(pa); }
-            else if (which == "prec_init") launch_prec<PREC_INIT>(pa);
-            else if (which.rfind("prec_step:", 0) == 0) { pa.debug_skip = std::atoi(which.c_str() + 10); launch_prec<PREC_STEP>(pa); }
-            else if (which == "prec_step") launch_prec<PREC_STEP>(pa);
+            else if (which.rfind("prec_init:", 0) == 0) { pa.debug_skip = std::atoi(which.c_str() + 10); launch_prec<PREC_INIT>(Kset, pa); }
+            else if (which == "prec_init") launch_prec<PREC_INIT>(Kset, pa);
+            else if (which.rfind("prec_step:", 0) == 0) { pa.debug_skip = std::atoi(which.c_str() + 10); launch_prec<PREC_STEP>(Kset, pa); }
+            else if (which == "prec_step") launch_prec<PREC_STEP>(Kset, pa);
             // (segmented long chains: the chain kernel alone / the second level alone -- k_join_solve + k_join_apply)
-            else if (which == "prec_init_chain") { join_suspend = true; launch_prec<PREC_INIT>(pa); join_suspend = false; }
-            else if (which == "prec_step_chain") { join_suspend = true; launch_prec<PREC_STEP>(pa); join_suspend = false; }
-            else if (which == "join_init") { if (n_join_items) join_apply<PREC_INIT>(pa, false); }
-            else if (which == "join_step") { if (n_join_items) join_apply<PREC_STEP>(pa, false); }
+            else if (which == "prec_init_chain") launch_prec<PREC_INIT>(Kset, pa, -1, PrecDepth::chain);
+            else if (which == "prec_step_chain") launch_prec<PREC_STEP>(Kset, pa, -1, PrecDepth::chain);
+            else if (which == "join_init") { if (n_join_items) join_apply<PREC_INIT>(Kset, pa); }
+            else if (which == "join_step") { if (n_join_items) join_apply<PREC_STEP>(Kset, pa); }
             else if (which == "kp") launch_kp(p.d);
             else if (which == "kpb") launch_kpb(p.d, p2.d, rz_part1.d, rz_part0.d);
             else if (which == "xupdate") hipLaunchKernelGGL(k_xupdate, dim3(n_vblocks), dim3(kThreads), 0, stream, va);
