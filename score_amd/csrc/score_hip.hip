@@ -335,7 +335,6 @@ thread_local DevArena* tl_arena = nullptr;  // set while a handle is being initi
 // the headline create.  Measured (round 4): create of 1 x 100 poses 2.11 -> 1.17 ms, 1 x 500: 2.40 -> 1.48, 4 x 1000: 4.06 ->
 // 2.82, 20 x 1000: 9.2 -> 8.6-9.0 ms.  Round 5: EVERYTHING goes through pinned memory of the library's own -- see staged_d2h
 // below for why no pageable pointer is ever handed to the runtime (the size-limit switches of rounds 4-5 are gone: TRIED.md).
-inline size_t stage_limit_bytes() { return ~(size_t)0; }
 struct StageArena {
     int dev = 0;
     std::vector<size_t> chunk_bytes;
@@ -367,11 +366,10 @@ struct StageArena {
         left -= bytes;
         return r;
     }
-    // copy `bytes` from src into a pinned slot and queue its transfer to `dst` on `st`; false: too large, the caller
-    // takes its own path
+    // copy `bytes` from src into a pinned slot and queue its transfer to `dst` on `st` (always true: no size is too large
+    // to stage; the callers' own paths serve the threads without a StageArena)
     bool upload(void* dst, const void* src, size_t bytes, hipStream_t st) {
         if (!bytes) return true;
-        if (bytes > stage_limit_bytes()) return false;
         if (inflight + bytes > kMaxInflight && inflight > 0) {  // everything queued so far has to leave its slots: start over
             flush();
             HIP_CHECK(sync_stream(st));
@@ -805,8 +803,7 @@ struct RuizDevice : RuizOffload {
             struct Scope {
                 DevArena* a_; hipStream_t s_; StageArena* g_;
                 Scope(DevArena* a, hipStream_t s, StageArena* g) : a_(tl_arena), s_(tl_copy_stream), g_(tl_stage) {
-                    tl_arena = a; tl_copy_stream = s;
-                    if (stage_limit_bytes() > 0) tl_stage = g;
+                    tl_arena = a; tl_copy_stream = s; tl_stage = g;
                 }
                 ~Scope() { tl_arena = a_; tl_copy_stream = s_; tl_stage = g_; }
             } scope(&arena, st, &stage);
@@ -1029,7 +1026,6 @@ struct HipBackend {
 
     // (Rounds 4-5 could evaluate the previous iteration's cones inside the right-hand-side kernel -- five launches per ADMM
     //  iteration instead of six, opt-in, measured no faster: 13.9 us against 6.6 + 7.0 + 1.4 -- removed in round 6, TRIED.md.)
-    void begin_sequence() {}
     int cg_iters = 2;
     const double* last_rz = nullptr;  // r'z partials / direction of the pending end-of-PCG update
     const double* last_p = nullptr;
@@ -1730,7 +1726,7 @@ struct HipBackend {
             hipStream_t st;
             StageScope(int dev, hipStream_t s) : st(s) {
                 a.dev = dev;
-                if (stage_limit_bytes() > 0) tl_stage = &a;
+                tl_stage = &a;
             }
             ~StageScope() {
                 tl_stage = nullptr;
@@ -2233,6 +2229,12 @@ struct HipBackend {
         pa.prec_part_ptr = prec_part_ptr.d; pa.kblk_part_ptr = S.blk_part.d; pa.uni = uni_for(S.blocks());
         return pa;
     }
+    // ... its vectors: residual (r: updated in place; r_in: as it stands at entry), z = M^-1 r, direction, product w, solution
+    // xt with its carried product kx, and the p'w partials of the last product
+    static void prec_vectors(PrecArgs& pa, double* r, const double* r_in, double* z, double* p, const double* w, double* xt, double* kx,
+                             const double* pw_part) {
+        pa.r = r; pa.r_in = r_in; pa.z = z; pa.p = p; pa.w = w; pa.xt = xt; pa.kx = kx; pa.pw_part = pw_part;
+    }
     FactorArgs factor_args(const PrecSet& S, const int32_t* skip) const {
         FactorArgs fa{};
         fa.work = S.fac_work.d; fa.chains = S.chains.d; fa.levels = S.levels.d; fa.Hval = S.mat.val.d;
@@ -2261,8 +2263,8 @@ struct HipBackend {
         // the spikes: 2 BS applications of the chain kernel alone to the coupling columns
         PrecArgs pa = prec_args(S);
         pa.done = join_zero.d;
-        pa.r = join_rhs.d; pa.r_in = join_rhs.d; pa.p = join_tmp_p.d; pa.w = w.d; pa.xt = join_tmp_p.d; pa.kx = join_tmp_p.d;
-        pa.pw_part = nullptr; pa.rz_in = nullptr; pa.rz_out = join_tmp_rz.d;
+        prec_vectors(pa, join_rhs.d, join_rhs.d, nullptr, join_tmp_p.d, w.d, join_tmp_p.d, join_tmp_p.d, nullptr);  // (z: a column of W, below)
+        pa.rz_in = nullptr; pa.rz_out = join_tmp_rz.d;
         with_bs([&](auto bs) {
             constexpr int BS = decltype(bs)::value;
             for (int c = 0; c < 2 * BS; ++c) {
@@ -2377,11 +2379,10 @@ struct HipBackend {
         LinkArgs la = link_args(S);
         PrecArgs pa = prec_args(S);
         pa.done = link_zero.d;
-        pa.r = link_rhs.d; pa.r_in = link_rhs.d; pa.p = link_tmp_p.d; pa.w = w.d; pa.xt = link_tmp_p.d; pa.kx = link_tmp_p.d;
-        pa.pw_part = nullptr; pa.rz_in = nullptr; pa.rz_out = link_tmp_rz.d;
+        prec_vectors(pa, link_rhs.d, link_rhs.d, la.Zr, link_tmp_p.d, w.d, link_tmp_p.d, link_tmp_p.d, nullptr);
+        pa.rz_in = nullptr; pa.rz_out = link_tmp_rz.d;
         // (the right-hand sides -- unit vectors, round r's in vector r -- were written once, at link_init: the chain kernel does
         //  not touch r_in)
-        pa.z = la.Zr;
         if (link_rounds > 1) { pa.n_vec = link_rounds; pa.vec_stride = (long long)H->n_tot; }
         launch_prec<PREC_INIT>(S, pa, -1, PrecDepth::join);
         // (up to 48 unknowns: Gauss-Jordan on one wavefront, no block barriers; beyond: four wavefronts)
@@ -2480,7 +2481,7 @@ struct HipBackend {
         {   // K changed: the carried product kx = K xt is recomputed once
             SpmvArgs a = spmv_args(K, xtu.d);
             a.p = xtu.d; a.w = kx.d;
-            launch_spmv<MODE_KP>(K, a);
+            launch_product<MODE_KP>(Kset, a);
             HIP_CHECK(hipGetLastError());
         }
         if (n_cone_blocks) {
@@ -2703,10 +2704,9 @@ struct HipBackend {
     }
     // partial-sum ranges by value for single-problem handles (UniRanges, score_kernels.hpp); kblocks = row blocks of the
     // matrix whose p'w partials the launch reads (K in the ADMM loop, H in the Newton PCG)
-    static constexpr bool uni_ranges = true;
     UniRanges uni_for(int kblocks) const {
         UniRanges u{};
-        u.on = (uni_ranges && H->count == 1 && active_part_ptr.size() == 2) ? 1 : 0;
+        u.on = (H->count == 1 && active_part_ptr.size() == 2) ? 1 : 0;
         u.l0 = 0; u.l1 = u.on ? active_part_ptr[1] : 0;
         u.k0 = 0; u.k1 = kblocks;
         return u;
@@ -2731,14 +2731,6 @@ struct HipBackend {
         if (M.rep == 2) launch_band_s<MODE, 2>(Bv, a, grid, slot);
         else if (M.rep == 3) launch_band_s<MODE, 3>(Bv, a, grid, slot);
         else launch_band_s<MODE, 1>(Bv, a, grid, slot);
-    }
-    // the products with the Newton matrix (plain rows)
-    template <int MODE>
-    void launch_h(const SpmvArgs& a_in, int slot = -1) {
-        if (Hb.on) { launch_band<MODE>(Hm, Hb, a_in, slot); return; }
-        SpmvArgs a = a_in;
-        const unsigned grid = xcd_grid(a, Hm.nblocks);
-        launch_on_stream(k_spmv<MODE>, dim3(grid), dim3(kThreads), 0, slot, a);
     }
     // ---- probe of the Newton PCG's launches (score_debug_get "newton_probe_arm" / "newton_probe"): the next polish
     //      binds start / stop events to its chain-kernel STEPs and H products (as score_time_iteration does for the ADMM
@@ -2786,12 +2778,10 @@ struct HipBackend {
         np_ev.clear(); np_slots.clear();
         np_armed = false;
     }
+    // product over the plain rows of M (the matrices that belong to no set -- G1, G2 -- and launch_product's other half)
     template <int MODE>
     void launch_spmv(const CsrBufs& M, const SpmvArgs& a_in, int slot = -1) {
         static_assert(MODE == MODE_RHS || MODE == MODE_KP || MODE == MODE_KPB, "the residual / gradient modes run on plain rows (G2, H)");
-        if constexpr (MODE != MODE_RHS) {
-            if (&M == &K && Kb.on) { launch_band<MODE>(K, Kb, a_in, slot); return; }
-        }
         SpmvArgs a = a_in;
         const unsigned grid = xcd_grid(a, M.nblocks);
         const bool half = (M.unroll == kUnroll / 2);
@@ -2800,6 +2790,13 @@ struct HipBackend {
         if (M.rep == 2) { launch_on_stream(k_spmv<MODE, 2>, dim3(grid), dim3(kThreads), 0, slot, a); return; }
         if (M.rep == 3) { launch_on_stream(k_spmv<MODE, 3>, dim3(grid), dim3(kThreads), 0, slot, a); return; }
         launch_on_stream(k_spmv<MODE, 1>, dim3(grid), dim3(kThreads), 0, slot, a);
+    }
+    // product with a set's matrix (K p in the ADMM loop and in linear mode, H p in the Newton PCG): over its band view when
+    // it has one, over its plain rows otherwise
+    template <int MODE>
+    void launch_product(const PrecSet& S, const SpmvArgs& a, int slot = -1) {
+        if (S.band.on) launch_band<MODE>(S.mat, S.band, a, slot);
+        else launch_spmv<MODE>(S.mat, a, slot);
     }
 
     SpmvArgs spmv_args(const CsrBufs& M, const double* xin) {
@@ -2820,7 +2817,7 @@ struct HipBackend {
     void launch_kp(const double* pdir, unsigned long long* ts = nullptr, int slot = -1) {
         SpmvArgs a = spmv_args(K, pdir);
         a.p = pdir; a.tstamp = ts;
-        launch_spmv<MODE_KP>(K, a, slot);
+        launch_product<MODE_KP>(Kset, a, slot);
     }
     // p_new = z + beta p_old ; w = K p_new
     void launch_kpb(const double* p_old, double* p_new, const double* rz_new, const double* rz_old,
@@ -2828,7 +2825,7 @@ struct HipBackend {
         SpmvArgs a = spmv_args(K, p_old);
         a.tstamp = ts;
         a.p = p_old; a.z = z.d; a.p_out = p_new; a.rz_new = rz_new; a.rz_old = rz_old;
-        launch_spmv<MODE_KPB>(K, a, slot);
+        launch_product<MODE_KPB>(Kset, a, slot);
     }
 
     void set_cg_iters(int k) {
@@ -2870,8 +2867,7 @@ struct HipBackend {
         }
         PrecArgs pa = prec_args(Kset);
         pa.done = done.d;
-        pa.r = r.d; pa.r_in = r.d; pa.z = z.d; pa.p = p.d; pa.w = w.d; pa.xt = xtu.d; pa.kx = kx.d;
-        pa.pw_part = pw_part.d;
+        prec_vectors(pa, r.d, r.d, z.d, p.d, w.d, xtu.d, kx.d, pw_part.d);
         double* rz_cur = measure ? rz_meas0.d : rz_part0.d;
         double* p_cur = p.d;
         double* p_oth = p2.d;
@@ -3175,6 +3171,30 @@ struct HipBackend {
         int64_t sz = 0;
         bool host = false;
         std::string nm(name);
+        // the device-against-host checks ("ag_device_check", "polish_build_check"): a device array on the host; entries that
+        // differ (+ the difference in length); largest difference (1e300 when the lengths differ)
+        auto down_i = [&](const int32_t* d, size_t cnt) {
+            std::vector<int32_t> v(cnt);
+            if (cnt) staged_d2h(v.data(), d, cnt * sizeof(int32_t), stream);
+            HIP_CHECK(sync_stream(stream));
+            return v;
+        };
+        auto down_d = [&](const double* d, size_t cnt) {
+            std::vector<double> v(cnt);
+            if (cnt) staged_d2h(v.data(), d, cnt * sizeof(double), stream);
+            HIP_CHECK(sync_stream(stream));
+            return v;
+        };
+        auto mism = [](const std::vector<int32_t>& x, const std::vector<int32_t>& y) {
+            double c = (double)(x.size() > y.size() ? x.size() - y.size() : y.size() - x.size());
+            for (size_t i = 0; i < std::min(x.size(), y.size()); ++i) c += x[i] != y[i];
+            return c;
+        };
+        auto maxd = [](const std::vector<double>& x, const std::vector<double>& y) {
+            double c = x.size() == y.size() ? 0.0 : 1e300;
+            for (size_t i = 0; i < std::min(x.size(), y.size()); ++i) c = std::max(c, std::fabs(x[i] - y[i]));
+            return c;
+        };
         if (nm == "xt") { src = xtu.d; sz = h.n_tot; }
         else if (nm == "u") { src = xtu.d + h.n_tot; sz = h.m_tot; }
         else if (nm == "x") { src = xy.d; sz = h.n_tot; }
@@ -3275,28 +3295,6 @@ struct HipBackend {
             // the equilibrated A, G1, G2 on the device against the host arrays: [derived on the device (0/1), mismatching
             // columns of A, max |A value difference|, the same for G1, for G2]
             if (out && len >= 7) {
-                auto down_i = [&](const int32_t* d, size_t cnt) {
-                    std::vector<int32_t> v(cnt);
-                    if (cnt) staged_d2h(v.data(), d, cnt * sizeof(int32_t), stream);
-                    HIP_CHECK(sync_stream(stream));
-                    return v;
-                };
-                auto down_d = [&](const double* d, size_t cnt) {
-                    std::vector<double> v(cnt);
-                    if (cnt) staged_d2h(v.data(), d, cnt * sizeof(double), stream);
-                    HIP_CHECK(sync_stream(stream));
-                    return v;
-                };
-                auto mism = [](const std::vector<int32_t>& x, const std::vector<int32_t>& y) {
-                    double c = 0;
-                    for (size_t i = 0; i < y.size(); ++i) c += x[i] != y[i];
-                    return c;
-                };
-                auto maxd = [](const std::vector<double>& x, const std::vector<double>& y) {
-                    double c = 0;
-                    for (size_t i = 0; i < y.size(); ++i) c = std::max(c, std::fabs(x[i] - y[i]));
-                    return c;
-                };
                 out[0] = derive_ag ? 1.0 : 0.0;
                 out[1] = mism(down_i(A_col.d, h.A.col.size()), h.A.col); out[2] = maxd(down_d(A_val.d, h.A.val.size()), h.A.val);
                 out[3] = mism(down_i(G1.col.d, h.G1.col.size()), h.G1.col); out[4] = maxd(down_d(G1.val.d, h.G1.val.size()), h.G1.val);
@@ -3313,28 +3311,6 @@ struct HipBackend {
             if (out && len >= 14) {
                 PolishData R;
                 build_polish(h, R, false, false);
-                auto down_i = [&](const int32_t* d, size_t cnt) {
-                    std::vector<int32_t> v(cnt);
-                    if (cnt) staged_d2h(v.data(), d, cnt * sizeof(int32_t), stream);
-                    HIP_CHECK(sync_stream(stream));
-                    return v;
-                };
-                auto down_d = [&](const double* d, size_t cnt) {
-                    std::vector<double> v(cnt);
-                    if (cnt) staged_d2h(v.data(), d, cnt * sizeof(double), stream);
-                    HIP_CHECK(sync_stream(stream));
-                    return v;
-                };
-                auto mism = [](const std::vector<int32_t>& x, const std::vector<int32_t>& y) {
-                    double c = (double)(x.size() > y.size() ? x.size() - y.size() : y.size() - x.size());
-                    for (size_t i = 0; i < std::min(x.size(), y.size()); ++i) c += x[i] != y[i];
-                    return c;
-                };
-                auto maxd = [](const std::vector<double>& x, const std::vector<double>& y) {
-                    double c = x.size() == y.size() ? 0.0 : 1e300;
-                    for (size_t i = 0; i < std::min(x.size(), y.size()); ++i) c = std::max(c, std::fabs(x[i] - y[i]));
-                    return c;
-                };
                 const size_t nz = (size_t)hm_nnz, nc = R.ccone.size();
                 out[0] = polish_on_device ? 1.0 : 0.0;
                 out[1] = (double)hm_nnz; out[2] = (double)R.Hm.col.size();
@@ -3388,8 +3364,8 @@ struct HipBackend {
             if (out && len > 0) {
                 PrecArgs pa = prec_args(Hset);
                 pa.done = q_skip.d;
-                pa.r = r.d; pa.r_in = q_negg.d; pa.z = z.d; pa.p = p.d; pa.w = w.d; pa.xt = q_delta.d; pa.kx = q_dummy.d;
-                pa.pw_part = q_pw.d; pa.rz_in = nullptr; pa.rz_out = rz_part0.d;
+                prec_vectors(pa, r.d, q_negg.d, z.d, p.d, w.d, q_delta.d, q_dummy.d, q_pw.d);
+                pa.rz_in = nullptr; pa.rz_out = rz_part0.d;
                 launch_prec<PREC_INIT>(Hset, pa);
             }
             src = z.d; sz = h.n_tot;
@@ -3418,8 +3394,7 @@ struct HipBackend {
                 tmp.assign(h.n_tot, -1.0);
                 for (size_t ci = 0; ci < h.chains.size(); ++ci)
                     for (int i = 0; i < h.chains[ci].N; ++i)
-                        for (int c = 0; c < h.bs; ++c) tmp[h.node_col[h.chains[ci].node_begin + i] + c] = (double)(h.chains[ci].node_begin + i) + 1e-3 * 0;
-                // chain boundaries: encode the chain id in a second pass through "chain_id_of_col"
+                        for (int c = 0; c < h.bs; ++c) tmp[h.node_col[h.chains[ci].node_begin + i] + c] = (double)(h.chains[ci].node_begin + i);
             }
             sz = (int64_t)tmp.size();
             if (out && len > 0) std::memcpy(out, tmp.data(), sizeof(double) * (size_t)std::min(len, sz));
@@ -3459,7 +3434,6 @@ struct HipBackend {
     //      r'M^-1 r <= rel_tol^2 r0'M^-1 r0.  The host looks at one flag per chunk of iterations. ----
     DevBuf<double> lin_rhs, lin_tol2, lin_ref;
     DevBuf<int32_t> lin_flag;  // [gate flag | STEPs executed] per problem
-    static constexpr int kDirectEvery = 32;  // PCG: a direct product w = K p every so many recursive ones
     void linear_buffers(const HostSystem& h) {
         if (h.m_tot != 0 || h.count != 1) throw std::runtime_error("linear mode: one unconstrained pattern per handle");
         if (!lin_flag.d) {
@@ -3476,6 +3450,65 @@ struct HipBackend {
         staged_d2h(x, xtu.d, n * sizeof(double), stream);
         return ok;
     }
+    // ---- one gated PCG solve queued on the stream: linear mode (K x = rhs) and the Newton polish (H delta = -g) ----
+    struct QueuedPcg {
+        // what is solved, prepared by the caller: the set, and prec_args(set) + prec_vectors (r_in: the right-hand side, xt:
+        // the solution) + done / gate words; the buffer the products leave their p'w partials in (== pa.pw_part).  The products
+        // test the done words of `pa`.
+        const PrecSet* set = nullptr;
+        PrecArgs pa{};
+        double* pw_part = nullptr;
+        bool probe = false;           // the launches of an iteration take event slots of the Newton probe (probe_slot)
+        // what is running
+        const double* rhs = nullptr;  // pa.r_in as the caller gave it: read until the first STEP has written r
+        double* rz_cur = nullptr;     // r'z partials of the last application (rz_part0 / rz_part1 in turn)
+        double* p_cur = nullptr;      // the direction of the last product, and the buffer the next one writes (p / p2 in turn)
+        double* p_oth = nullptr;
+        int queued = 0;               // iterations queued
+        bool first = true;            // the next STEP is the solve's first: sets the gate's threshold, starts xt from zero
+    };
+    static constexpr int kDirectEvery = 32;  // a direct product w = M p every so many recursive ones
+    SpmvArgs pcg_product_args(const QueuedPcg& q) {
+        SpmvArgs a = spmv_args(q.set->mat, q.p_cur);
+        a.p = q.p_cur; a.pw_part = q.pw_part; a.done = q.pa.done;
+        return a;
+    }
+    // z = M^-1 rhs, p = z ; w = M p.  The caller arms the gate (gate_flag, gate_tol2, gate_ref ...) after this: the INIT and
+    // the first product run on the done words the solve starts with, and without early_done in the product.
+    void pcg_begin(QueuedPcg& q) {
+        q.rhs = q.pa.r_in;
+        q.rz_cur = rz_part0.d; q.p_cur = p.d; q.p_oth = p2.d;
+        q.queued = 0; q.first = true;
+        q.pa.p = q.p_cur; q.pa.rz_in = nullptr; q.pa.rz_out = q.rz_cur;
+        launch_prec<PREC_INIT>(*q.set, q.pa);
+        launch_product<MODE_KP>(*q.set, pcg_product_args(q));
+    }
+    // one iteration: STEP (x += a p ; r -= a w ; z = M^-1 r -- or: the gate fires, nothing happens), then p = z + beta p ; w = M p
+    void pcg_step(QueuedPcg& q) {
+        PrecArgs& pa = q.pa;
+        double* rz_nxt = (q.rz_cur == rz_part0.d) ? rz_part1.d : rz_part0.d;
+        pa.p = q.p_cur; pa.rz_in = q.rz_cur; pa.rz_out = rz_nxt;
+        pa.gate_first = q.first ? 1 : 0;
+        pa.r_in = q.first ? q.rhs : r.d;
+        pa.xt_zero = q.first ? 1 : 0;
+        launch_prec<PREC_STEP>(*q.set, pa, q.probe ? probe_slot(1, q.queued) : -1);
+        tev = nullptr;
+        SpmvArgs a = pcg_product_args(q);
+        a.z = z.d; a.p_out = q.p_oth; a.rz_new = rz_nxt; a.rz_old = q.rz_cur;
+        a.early_done = 1;
+        launch_product<MODE_KPB>(*q.set, a, q.probe ? probe_slot(0, q.queued) : -1);
+        tev = nullptr;
+        std::swap(q.p_cur, q.p_oth);
+        if (++q.queued % kDirectEvery == 0) {
+            // the recurrence w = M z + beta w_old accumulates rounding over a long solve: every kDirectEvery-th
+            // product is recomputed directly, w = M p (and its p'w)
+            SpmvArgs d = pcg_product_args(q);
+            d.early_done = 1;
+            launch_product<MODE_KP>(*q.set, d);
+        }
+        q.rz_cur = rz_nxt;
+        q.first = false;
+    }
     // K0d holds the values and rhs_dev the right-hand side, both on the device; the solution is left in xtu
     bool linear_solve_core(const HostSystem& h, const double* rhs_dev, double rel_tol, int max_iters, int* used_out) {
         linear_buffers(h);
@@ -3483,50 +3516,20 @@ struct HipBackend {
         const double tol2 = rel_tol * rel_tol;
         HIP_CHECK(hipMemcpyAsync(lin_tol2.d, &tol2, sizeof(double), hipMemcpyHostToDevice, stream));
         HIP_CHECK(hipMemsetAsync(lin_flag.d, 0, 2 * sizeof(int32_t), stream));
-        PrecArgs pa = prec_args(Kset);
-        pa.done = lin_flag.d;
-        pa.r = r.d; pa.r_in = rhs_dev; pa.z = z.d; pa.w = w.d; pa.xt = xtu.d; pa.kx = kx.d; pa.pw_part = pw_part.d;
-        pa.gate_used = lin_flag.d + 1;
-        pa.early_done = 1;
-        double* rz_cur = rz_part0.d;
-        double* p_cur = p.d;
-        double* p_oth = p2.d;
-        pa.p = p_cur; pa.rz_in = nullptr; pa.rz_out = rz_cur;
-        launch_prec<PREC_INIT>(Kset, pa);  // z = M^-1 rhs, p = z
-        {
-            SpmvArgs a = spmv_args(K, p_cur);
-            a.p = p_cur; a.done = lin_flag.d;
-            launch_spmv<MODE_KP>(K, a);
-        }
-        pa.gate_flag = lin_flag.d; pa.gate_tol2 = lin_tol2.d; pa.gate_ref = lin_ref.d;
+        QueuedPcg q;
+        q.set = &Kset;
+        q.pw_part = pw_part.d;
+        q.pa = prec_args(Kset);
+        q.pa.done = lin_flag.d;
+        prec_vectors(q.pa, r.d, rhs_dev, z.d, p.d, w.d, xtu.d, kx.d, q.pw_part);
+        q.pa.gate_used = lin_flag.d + 1;
+        q.pa.early_done = 1;
+        pcg_begin(q);
+        q.pa.gate_flag = lin_flag.d; q.pa.gate_tol2 = lin_tol2.d; q.pa.gate_ref = lin_ref.d;
         int32_t state[2] = {0, 0};
-        int queued = 0;
-        bool first = true;
-        while (!state[0] && queued < max_iters) {
-            const int chunk = std::min(max_iters - queued, queued == 0 ? 16 : 32);
-            for (int j = 0; j < chunk; ++j) {
-                double* rz_nxt = (rz_cur == rz_part0.d) ? rz_part1.d : rz_part0.d;
-                pa.p = p_cur; pa.rz_in = rz_cur; pa.rz_out = rz_nxt;
-                pa.gate_first = first ? 1 : 0;
-                pa.r_in = first ? rhs_dev : r.d;
-                pa.xt_zero = first ? 1 : 0;
-                launch_prec<PREC_STEP>(Kset, pa);  // x += a p ; r -= a w ; z = M^-1 r   (or the gate fires)
-                SpmvArgs a = spmv_args(K, p_cur);
-                a.p = p_cur; a.z = z.d; a.p_out = p_oth; a.rz_new = rz_nxt; a.rz_old = rz_cur; a.done = lin_flag.d;
-                a.early_done = 1;
-                launch_spmv<MODE_KPB>(K, a);
-                std::swap(p_cur, p_oth);
-                if ((queued + j + 1) % kDirectEvery == 0) {
-                    // the recurrence w = K z + beta w_old accumulates rounding over a long solve: every kDirectEvery-th
-                    // product is recomputed directly, w = K p (and its p'w)
-                    SpmvArgs d = spmv_args(K, p_cur);
-                    d.p = p_cur; d.done = lin_flag.d; d.early_done = 1;
-                    launch_spmv<MODE_KP>(K, d);
-                }
-                rz_cur = rz_nxt;
-                first = false;
-            }
-            queued += chunk;
+        while (!state[0] && q.queued < max_iters) {
+            const int chunk = std::min(max_iters - q.queued, q.queued == 0 ? 16 : 32);
+            for (int j = 0; j < chunk; ++j) pcg_step(q);
             HIP_CHECK(hipGetLastError());
             HIP_CHECK(hipMemcpyAsync(state, lin_flag.d, sizeof(state), hipMemcpyDeviceToHost, stream));
             HIP_CHECK(sync_stream(stream));
@@ -3989,66 +3992,29 @@ struct HipBackend {
     // host-side cost of queueing the Newton PCG (SCORE_TRACE=host: printed when the handle goes)
     double enq_ms = 0.0, wait_ms = 0.0;
     long enq_launches = 0, waits = 0;
-    int pcg_steps_queued = 0;
-    double* pcg_rz_cur = nullptr;
-    double* pcg_p_cur = nullptr;
-    double* pcg_p_oth = nullptr;
-    PrecArgs pcg_pa{};
+    QueuedPcg newton_pcg;
     // start a PCG solve (INIT + first product); the control words -- skip flags, tolerances -- were uploaded by the caller
     void newton_pcg_begin() {
-        const HostSystem& h = *H;
-        PrecArgs& pa = pcg_pa;
+        QueuedPcg& q = newton_pcg;
+        q.set = &Hset;
+        q.pw_part = q_pw.d;
+        q.probe = true;
+        PrecArgs& pa = q.pa;
         pa = prec_args(Hset);
         pa.done = q_skip.d;
-        pa.r = r.d; pa.r_in = r.d; pa.z = z.d; pa.w = w.d; pa.xt = q_delta.d; pa.kx = q_dummy.d; pa.pw_part = q_pw.d;
+        // the right-hand side is read where the evaluation left it (-g in q_negg) and the solution
+        // starts from zero without a memset: the first STEP writes r and delta
+        prec_vectors(pa, r.d, q_negg.d, z.d, p.d, w.d, q_delta.d, q_dummy.d, q.pw_part);
         pa.gate_used = q_gate_used.d;
         pa.early_done = 1;  // launches queued beyond the gate are no-ops: keep them cheap
-        {
-            // the right-hand side is read where the evaluation left it (-g in q_negg) and the solution
-            // starts from zero without a memset: the first STEP writes r and delta
-            pcg_rz_cur = rz_part0.d; pcg_p_cur = p.d; pcg_p_oth = p2.d;
-            pcg_steps_queued = 0;
-            gate_epoch = (gate_epoch + 1) & 0x7ffff;
-            if (gate_epoch == 0) gate_epoch = 1;
-            pa.p = pcg_p_cur; pa.rz_in = nullptr; pa.rz_out = pcg_rz_cur;
-            pa.r_in = q_negg.d;
-            pa.gate_init = q_pcgdone.d;  // gate flags start as the host's skip flags
-            launch_prec<PREC_INIT>(Hset, pa);
-            pa.gate_init = nullptr;
-            SpmvArgs a = spmv_args(Hm, pcg_p_cur);
-            a.p = pcg_p_cur; a.pw_part = q_pw.d; a.done = q_skip.d;
-            launch_h<MODE_KP>(a);
-        }
+        gate_epoch = (gate_epoch + 1) & 0x7ffff;
+        if (gate_epoch == 0) gate_epoch = 1;
+        pa.gate_init = q_pcgdone.d;  // gate flags start as the host's skip flags
+        pcg_begin(q);
+        pa.gate_init = nullptr;
         pa.done = q_pcgdone.d;
         pa.gate_flag = q_pcgdone.d; pa.gate_tol2 = q_gate_tol2.d; pa.gate_ref = q_gate_ref.d;
-        pa.gate_host = d_gate_live; pa.gate_epoch = gate_epoch; pa.gate_count = h.count;
-        pcg_first = true;
-    }
-    bool pcg_first = false;
-    // one PCG iteration: STEP (delta += a p ; r -= a w ; z = M^-1 r -- or: the gate fires, nothing happens), then the product
-    void newton_pcg_pair() {
-        PrecArgs& pa = pcg_pa;
-        double* rz_nxt = (pcg_rz_cur == rz_part0.d) ? rz_part1.d : rz_part0.d;
-        const bool first = pcg_first;
-        pcg_first = false;
-        pa.p = pcg_p_cur; pa.rz_in = pcg_rz_cur; pa.rz_out = rz_nxt;
-        pa.gate_first = first ? 1 : 0;
-        pa.r_in = first ? q_negg.d : r.d;
-        pa.xt_zero = first ? 1 : 0;
-        launch_prec<PREC_STEP>(Hset, pa, probe_slot(1, pcg_steps_queued));
-        tev = nullptr;
-        SpmvArgs a = spmv_args(Hm, pcg_p_cur);
-        a.p = pcg_p_cur; a.z = z.d; a.p_out = pcg_p_oth; a.rz_new = rz_nxt; a.rz_old = pcg_rz_cur; a.pw_part = q_pw.d; a.done = q_pcgdone.d;
-        a.early_done = 1;
-        launch_h<MODE_KPB>(a, probe_slot(0, pcg_steps_queued));
-        tev = nullptr;
-        std::swap(pcg_p_cur, pcg_p_oth);
-        if (++pcg_steps_queued % kDirectEvery == 0) {  // (see linear_solve_core)
-            SpmvArgs d = spmv_args(Hm, pcg_p_cur);
-            d.p = pcg_p_cur; d.pw_part = q_pw.d; d.done = q_pcgdone.d; d.early_done = 1;
-            launch_h<MODE_KP>(d);
-        }
-        pcg_rz_cur = rz_nxt;
+        pa.gate_host = d_gate_live; pa.gate_epoch = gate_epoch; pa.gate_count = H->count;
     }
     // The PCG queued a few iterations AHEAD of the device instead of to a guessed length: pcg_gate's lead workgroups publish
     // "fired" and "STEPs executed" in host-mapped memory as they go (PrecArgs::gate_host); the host keeps `depth` iterations
@@ -4086,7 +4052,7 @@ struct HipBackend {
             }
             if (all || queued >= cap) break;
             if (queued - used < depth) {
-                newton_pcg_pair();
+                pcg_step(newton_pcg);
                 ++queued;
                 spins = 0;
                 continue;
@@ -4284,7 +4250,7 @@ struct HipBackend {
         {
             SpmvArgs a = spmv_args(K, xtu.d);
             a.p = xtu.d; a.w = kx.d; a.done = q_skip.d;
-            launch_spmv<MODE_KP>(K, a);
+            launch_product<MODE_KP>(Kset, a);
         }
         HIP_CHECK(sync_stream(stream));
         HIP_CHECK(hipGetLastError());
@@ -4295,8 +4261,8 @@ struct HipBackend {
     void time_kernel(const std::string& which, int reps, double* ms) {
         PrecArgs pa = prec_args(Kset);
         pa.done = done.d;
-        pa.r = r.d; pa.r_in = r.d; pa.z = z.d; pa.p = p.d; pa.w = w.d; pa.xt = xtu.d; pa.kx = kx.d;
-        pa.pw_part = pw_part.d; pa.rz_in = rz_part0.d; pa.rz_out = rz_part1.d;
+        prec_vectors(pa, r.d, r.d, z.d, p.d, w.d, xtu.d, kx.d, pw_part.d);
+        pa.rz_in = rz_part0.d; pa.rz_out = rz_part1.d;
         VecArgs va{};
         va.first_row = vb_first.d; va.end_row = vb_end.d; va.blk_prob = vb_prob.d; va.done = done.d;
         va.prec_part_ptr = prec_part_ptr.d; va.kblk_part_ptr = Kset.blk_part.d;
