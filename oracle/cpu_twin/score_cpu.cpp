@@ -33,7 +33,6 @@ namespace {
 
 using namespace score;
 
-thread_local std::string g_err;
 
 struct CpuBackend {
     static constexpr bool kFactorOnHost = true;
@@ -589,9 +588,6 @@ struct CpuBackend {
 
 }  // namespace
 
-struct score_assembled {
-    score::AssembledQP qp;
-};
 
 struct score_handle {
     score::Solver<CpuBackend> solver;
@@ -696,12 +692,11 @@ struct score_refine {
 
 struct score_generated { score::GeneratedBatch B; };
 
-extern "C" {
-
-void score_default_settings(score_settings* s) { score::default_settings(s); }
-
-int score_create_batch(const score_problem* p, int32_t count, const score_settings* s, score_handle** out) {
-    try {
+// What the shared boundary (score_abi.hpp) has to know about this library: a call on a handle holds nothing, and a
+// create caps the OpenMP team once.
+struct AbiEnv {
+    struct Scope { Scope(int /*device*/, bool /*solving*/) {} };
+    static void before_create() {
 #ifdef _OPENMP
         // Default team of the twin: at most 16 threads.  Its loops are short (a test problem has a
         // few hundred rows); on a 256-thread host the default team makes every parallel region
@@ -712,29 +707,20 @@ int score_create_batch(const score_problem* p, int32_t count, const score_settin
             if (omp_get_max_threads() > 16) omp_set_num_threads(16);
         });
 #endif
-        score_settings st;
-        if (s) st = *s; else score::default_settings(&st);
-        auto* h = new score_handle();
-        try {
-            h->solver.create(p, count, st);
-        } catch (...) {
-            delete h;
-            throw;
-        }
-        *out = h;
-        return 0;
-    } catch (const std::exception& e) {
-        g_err = e.what();
-        return -1;
     }
-}
-int score_create(const score_problem* p, const score_settings* s, score_handle** out) {
-    return score_create_batch(p, 1, s, out);
-}
+    static void require_device(int) {}
+};
+inline void time_kkt(CpuBackend& be, int reps, double* ms, double* bytes) { be.time_kkt(reps, ms, bytes); }
+inline int64_t get_vec(CpuBackend& be, const char* name, double* out, int64_t len) { return be.get_vec(name, out, len); }
+
+#include "../../score_amd/csrc/score_abi.hpp"
+
+extern "C" {
+
 // (the twin builds the model with the host assembler -- the specification the product's device assembler is tested against)
 int score_create_from_graphs(const score_graph* graphs, int32_t count, const score_settings* s, score_handle** out) {
-    try {
-        if (!graphs || !out || count <= 0) throw std::runtime_error("null argument");
+    return abi_call([&] {
+        require(graphs && out && count > 0);
         std::vector<score::AssembledQP> qps((size_t)count);
         std::vector<score::AssembledQP*> ptrs((size_t)count);
         for (int i = 0; i < count; ++i) ptrs[(size_t)i] = &qps[(size_t)i];
@@ -749,84 +735,18 @@ int score_create_from_graphs(const score_graph* graphs, int32_t count, const sco
         const int rc = score_create_batch(probs.data(), count, s, out);
         if (rc == 0) score::est_layout_from_graphs(graphs, count, (*out)->solver.H.xoff, (*out)->solver.est, (*out)->solver.hf.empty() ? -1 : 0);
         return rc;
-    } catch (const std::exception& e) {
-        g_err = e.what();
-        return -1;
-    }
+    });
 }
 int score_read_estimates(score_handle* h, int32_t qcqp_directions, double* poses, double* relaxed, double* landmarks, double* ranges,
                          int32_t* degenerate) {
-    try {
-        if (!h) throw std::runtime_error("null handle");
-        if (!h->solver.est.valid()) throw std::runtime_error("score_read_estimates: the handle was not made by score_create_from_graphs");
+    return abi_call([&] {
+        require(h != nullptr, "null handle");
+        require(h->solver.est.valid(), "score_read_estimates: the handle was not made by score_create_from_graphs");
         std::vector<double> x((size_t)h->solver.H.n_tot);
         h->solver.be.download(h->solver.H, x.data(), nullptr, nullptr);
         score::read_estimates_host(h->solver.est, (qcqp_directions || h->solver.est.dirs_always) ? 1 : 0, x.data(), poses, relaxed, landmarks, ranges, degenerate);
         return 0;
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
-}
-int score_graphs_connected(const score_graph* graphs, int32_t count) {
-    if (!graphs || count < 0) { g_err = "null argument"; return -1; }
-    for (int32_t i = 0; i < count; ++i)
-        if (!score::graph_connected(graphs[i])) return i + 1;
-    return 0;
-}
-int score_dims(const score_handle* h, int64_t* n_total, int64_t* m_total, int32_t* count) {
-    if (!h) { g_err = "null handle"; return -1; }
-    if (n_total) *n_total = h->solver.user_n();  // (the programs as given: score_headform.hpp)
-    if (m_total) *m_total = h->solver.user_m();
-    if (count) *count = h->solver.H.count;
-    return 0;
-}
-int score_solve(score_handle* h, double* x, double* y, double* s, score_info* infos) {
-    try { return h->solver.solve(x, y, s, infos); }
-    catch (const std::exception& e) { g_err = e.what(); return -1; }
-}
-int score_reset(score_handle* h) {
-    try { h->solver.reset(); return 0; }
-    catch (const std::exception& e) { g_err = e.what(); return -1; }
-}
-int score_solve_steps(score_handle* h, int32_t iters, double* x, double* y, double* s, score_info* infos) {
-    try { return h->solver.steps(iters, x, y, s, infos); }
-    catch (const std::exception& e) { g_err = e.what(); return -1; }
-}
-int score_newton_steps(score_handle* h, int32_t iters, double* x, double* y, double* s, score_info* infos) {
-    try {
-        if (!h) throw std::runtime_error("null handle");
-        return h->solver.newton_steps(iters, x, y, s, infos);
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
-}
-int score_linear_create(const score_problem* pattern, const score_settings* s, score_handle** out) {
-    try {
-        if (!pattern || !out) throw std::runtime_error("null argument");
-        score::LinearPattern L;
-        score::make_linear_pattern(*pattern, s, L);
-        score_handle* h = nullptr;
-        if (score_create_batch(&L.prob, 1, &L.st, &h) != 0) return -1;
-        auto& S = h->solver;
-        if ((int64_t)S.H.K0.size() != (int64_t)pattern->P_rowptr[pattern->n]) {
-            score_destroy(h);
-            throw std::runtime_error("score_linear_create: internal pattern differs from the given one");
-        }
-        S.linear_mode = true;
-        S.linear_nnz = (int64_t)S.H.K0.size();
-        *out = h;
-        return 0;
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
-}
-int score_linear_solve(score_handle* h, const double* values, const double* rhs, double* x, double rel_tol,
-                       int32_t max_iters, int32_t* iters_used, double* rel_residual) {
-    try {
-        if (!h) throw std::runtime_error("null handle");
-        int used = 0;
-        const int rc = h->solver.linear_solve(values, rhs, x, rel_tol, max_iters, &used, rel_residual);
-        if (iters_used) *iters_used = used;
-        return rc;
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
-}
-int score_time_kkt_apply(score_handle* h, int32_t reps, double* ms, double* bytes) {
-    try { h->solver.be.time_kkt(reps, ms, bytes); return 0; }
-    catch (const std::exception& e) { g_err = e.what(); return -1; }
+    });
 }
 int score_time_iteration(score_handle*, int32_t, int32_t, double* us, int32_t) {
     if (us) for (int k = 0; k < 12; ++k) us[k] = 0.0;  // the twin has no kernels to time
@@ -836,82 +756,17 @@ int score_debug_time(score_handle*, const char*, int32_t, double* ms) {
     if (ms) *ms = 0.0;  // the twin has no kernels to time
     return 0;
 }
-int64_t score_debug_get(score_handle* h, const char* name, double* out, int64_t len) {
-    return h->solver.be.get_vec(name, out, len);
-}
 void score_destroy(score_handle* h) { delete h; }
-int score_assemble(const score_graph* g, score_assembled** out) {
-    try {
-        if (!g || !out) throw std::runtime_error("null argument");
-        auto* a = new score_assembled();
-        try {
-            score::assemble_graph(*g, a->qp);
-        } catch (...) {
-            delete a;
-            throw;
-        }
-        *out = a;
-        return 0;
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
-}
-int score_assemble_batch(const score_graph* graphs, int32_t count, score_assembled** out) {
-    try {
-        if (!graphs || !out || count <= 0) throw std::runtime_error("null argument");
-        std::vector<score_assembled*> made((size_t)count, nullptr);
-        std::vector<score::AssembledQP*> qps((size_t)count, nullptr);
-        try {
-            for (int i = 0; i < count; ++i) { made[(size_t)i] = new score_assembled(); qps[(size_t)i] = &made[(size_t)i]->qp; }
-            score::assemble_graphs(graphs, count, qps.data());
-        } catch (...) {
-            for (auto* a : made) delete a;
-            throw;
-        }
-        for (int i = 0; i < count; ++i) out[i] = made[(size_t)i];
-        return 0;
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
-}
-int score_assembled_view(const score_assembled* a, score_problem* view) {
-    if (!a || !view) { g_err = "null argument"; return -1; }
-    a->qp.view(view);
-    return 0;
-}
-void score_assembled_free(score_assembled* a) { delete a; }
 // (the generator as host loops: the specification the product's kernels are tested against)
 int score_generate_manhattan(const score_manhattan_spec* spec, int32_t count, int32_t /*device*/, score_generated** out) {
-    try {
-        if (!spec || !out) throw std::runtime_error("null argument");
-        score::GenSpec S{spec->n_robots, spec->n_poses, spec->n_beacons, spec->side, spec->p_range, spec->sigma_t, spec->sigma_theta, spec->sigma_range, spec->seed,
-                         spec->dim == 0 ? 2 : spec->dim};
-        auto* g = new score_generated();
-        try { score::generate_manhattan_host(S, count, g->B); } catch (...) { delete g; throw; }
-        *out = g;
+    return abi_call([&] {
+        require(spec && out);
+        publish_new(out, [&](score_generated& g) { score::generate_manhattan_host(gen_spec(*spec), count, g.B); });
         return 0;
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+    });
 }
-int score_generated_graph(const score_generated* g, int32_t index, score_graph* view) {
-    try {
-        if (!g || !view) throw std::runtime_error("null argument");
-        g->B.view(index, view);
-        return 0;
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
-}
-int score_generated_truth(const score_generated* g, int32_t index, double* poses, double* beacons) {
-    try {
-        if (!g) throw std::runtime_error("null argument");
-        g->B.truth(index, poses, beacons);
-        return 0;
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
-}
-void score_generated_free(score_generated* g) { delete g; }
 int score_create_from_generated(const score_generated* g, int32_t first, int32_t count, int32_t relaxation, const score_settings* s, score_handle** out) {
-    try {
-        if (!g || !out) throw std::runtime_error("null argument");
-        if (first < 0 || count <= 0 || first + count > g->B.count) throw std::runtime_error("score_create_from_generated: worlds out of range");
-        if (relaxation != 0 && relaxation != 1) throw std::runtime_error("score_create_from_generated: relaxation must be 0 (SOCP) or 1 (QCQP)");
-        std::vector<score_graph> views((size_t)count);
-        for (int i = 0; i < count; ++i) { g->B.view(first + i, &views[(size_t)i]); views[(size_t)i].relaxation = relaxation; }
-        return score_create_from_graphs(views.data(), count, s, out);
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+    return abi_call([&] { return score_create_from_graphs(generated_views(g, first, count, relaxation, out).data(), count, s, out); });
 }
 int score_round_to_so(int32_t dim, int64_t n, const double* blocks, double* rotations, int32_t* degenerate, int32_t /*device*/) {
     if (dim != 2 && dim != 3) { g_err = "score_round_to_so: dim must be 2 or 3"; return -1; }
@@ -927,8 +782,6 @@ int32_t score_host_counters(double* out, int32_t len) {  // (the twin waits for 
     if (out) for (int i = 0; i < len && i < 4; ++i) out[i] = 0.0;
     return 4;
 }
-const char* score_last_error(void) { return g_err.c_str(); }
-int32_t score_abi_version(void) { return SCORE_ABI_VERSION * 1000 + (int32_t)sizeof(score_problem); }
 const char* score_backend(void) { return "cpu-twin"; }
 }
 
@@ -965,23 +818,16 @@ bool score_refine::solve(double lambda, double rel_tol, int* used) {
 
 extern "C" {
 int score_refine_create(const score_graph* g, const score_settings* s, score_refine** out) {
-    try {
-        if (!g || !out) throw std::runtime_error("null argument");
-        auto* r = new score_refine();
-        try {
-            r->create(*g, s);
-        } catch (...) {
-            delete r;
-            throw;
-        }
-        *out = r;
+    return abi_call([&] {
+        require(g && out);
+        publish_new(out, [&](score_refine& r) { r.create(*g, s); });
         return 0;
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+    });
 }
 int score_refine_run(score_refine* r, const double* poses_in, const double* landmarks_in, int32_t max_iters, double tol,
                      double* poses_out, double* landmarks_out, score_refine_info* info) {
-    try {
-        if (!r || !poses_in || !poses_out || (r->P.Nl > 0 && (!landmarks_in || !landmarks_out))) throw std::runtime_error("null argument");
+    return abi_call([&] {
+        require(r && poses_in && poses_out && (r->P.Nl == 0 || (landmarks_in && landmarks_out)));
         const double t0 = score::now_ms();
         score::GnInfo gi;
         r->run(poses_in, landmarks_in, max_iters, tol, poses_out, landmarks_out, gi);
@@ -991,7 +837,7 @@ int score_refine_run(score_refine* r, const double* poses_in, const double* land
             info->setup_ms = r->setup_ms; info->solve_ms = score::now_ms() - t0;
         }
         return 0;
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+    });
 }
 void score_refine_destroy(score_refine* r) { delete r; }
 }

@@ -50,8 +50,6 @@ namespace {
 
 using namespace score;
 
-thread_local std::string g_err;
-
 #define HIP_CHECK(expr)                                                                          \
     do {                                                                                         \
         hipError_t _e = (expr);                                                                  \
@@ -114,6 +112,14 @@ struct DeviceGuard {
     DeviceGuard(const DeviceGuard&) = delete;
     DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
+
+// The product runs on a HIP device or not at all.  `range_msg`: what the caller calls an index outside the devices present.
+inline void require_hip_device(int device, const char* range_msg = "score_settings.device out of range") {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        throw std::runtime_error("no HIP device available (the SCORE solver has no CPU fallback)");
+    if (device < 0 || device >= ndev) throw std::runtime_error(range_msg);
+}
 
 // ---------------------------------------------------------------------------
 // backend
@@ -871,6 +877,14 @@ struct RuizDevice : RuizOffload {
         return ok;
     }
 };
+
+// The Newton probe (score_inspect.hpp) is the one piece of the inspection surface the solver itself calls: the polish takes an
+// event slot per PCG launch, marks the steps that did work, and collects when it is done.
+struct HipBackend;
+struct NewtonProbe;
+int probe_slot(HipBackend& be, int kind, int step);
+void probe_mark(HipBackend& be, int used);
+void probe_collect(HipBackend& be);
 
 struct HipBackend {
     // K's values, the chain factors and the Jacobi diagonal are derived on the device from K0, K1 and
@@ -1708,11 +1722,7 @@ struct HipBackend {
         H = &h;
         st = s_;
         PhaseTimer pt(st.verbose != 0);
-        int ndev = 0;
-        hipError_t e = hipGetDeviceCount(&ndev);
-        if (e != hipSuccess || ndev <= 0)
-            throw std::runtime_error("no HIP device available (the SCORE solver has no CPU fallback)");
-        if (st.device < 0 || st.device >= ndev) throw std::runtime_error("score_settings.device out of range");
+        require_hip_device(st.device);
         HIP_CHECK(hipSetDevice(st.device));
         arena.dev = st.device;
         stream = stream_pool().take(st.device);
@@ -2613,6 +2623,7 @@ struct HipBackend {
     // timestamps (what a profiler's kernel trace shows) without inserting a command between two
     // kernels of the loop.
     hipEvent_t* tev = nullptr;
+    std::shared_ptr<NewtonProbe> probe;  // (made by score_debug_get "newton_probe_arm")
     template <class Kern, class... Args>
     void launch_on_stream(Kern kernel, dim3 grid, dim3 block, size_t lds_bytes, int slot, Args... args) {
         if (tev && slot >= 0)
@@ -2696,11 +2707,15 @@ struct HipBackend {
     // SpMV launch: matrices of a replicated problem (K, G1) run with rep right-hand sides per stored row
     // XCD-aware tile order (SpmvArgs::xcd_chunk): returns the grid size.  Measured: KKT SpMV of a 16-problem batch
     // 48.0 -> 45.6 us (3.06 -> 3.23 TB/s), single problem 8.2 -> 7.8 us; kpb and rhs gain 2-3 %.
+    // The rule (the SpMV launches and the loop's cone launch): 16 tiles or more run as 8 chunks of ceil(n / 8) tiles, one chunk
+    // per XCD; fewer run in plain order (chunk = 0).
+    static unsigned xcd_grid_of(int n, int& chunk) {
+        chunk = n >= 16 ? (n + 7) / 8 : 0;
+        return chunk ? 8u * (unsigned)chunk : (unsigned)n;
+    }
     unsigned xcd_grid(SpmvArgs& a, int nblocks) const {
         a.n_tiles = nblocks;
-        if (nblocks < 16) { a.xcd_chunk = 0; return (unsigned)nblocks; }
-        a.xcd_chunk = (nblocks + 7) / 8;
-        return (unsigned)(8 * a.xcd_chunk);
+        return xcd_grid_of(nblocks, a.xcd_chunk);
     }
     // partial-sum ranges by value for single-problem handles (UniRanges, score_kernels.hpp); kblocks = row blocks of the
     // matrix whose p'w partials the launch reads (K in the ADMM loop, H in the Newton PCG)
@@ -2731,52 +2746,6 @@ struct HipBackend {
         if (M.rep == 2) launch_band_s<MODE, 2>(Bv, a, grid, slot);
         else if (M.rep == 3) launch_band_s<MODE, 3>(Bv, a, grid, slot);
         else launch_band_s<MODE, 1>(Bv, a, grid, slot);
-    }
-    // ---- probe of the Newton PCG's launches (score_debug_get "newton_probe_arm" / "newton_probe"): the next polish
-    //      binds start / stop events to its chain-kernel STEPs and H products (as score_time_iteration does for the ADMM
-    //      loop) and reports the mean dispatch duration of those that did work (launches queued beyond a solve's
-    //      convergence are no-ops and are left out) ----
-    static constexpr int kProbeCap = 1024;
-    bool np_armed = false;
-    std::vector<hipEvent_t> np_ev;
-    struct ProbeSlot { int kind, newton_it, step; bool real; };
-    std::vector<ProbeSlot> np_slots;
-    int np_newton_it = 0;
-    double np_out[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int probe_slot(int kind, int step) {
-        if (!np_armed || (int)np_slots.size() >= kProbeCap) return -1;
-        np_slots.push_back(ProbeSlot{kind, np_newton_it, step, false});
-        tev = np_ev.data();
-        return (int)np_slots.size() - 1;
-    }
-    void probe_mark(int used) {  // the PCG steps of the current Newton iteration that did work
-        for (auto& sl : np_slots)
-            if (sl.newton_it == np_newton_it && sl.step < used) sl.real = true;
-    }
-    void probe_collect() {
-        if (!np_armed) return;
-        double sum[2] = {0, 0};
-        int cnt[2] = {0, 0};
-        for (size_t i = 0; i < np_slots.size(); ++i) {
-            if (!np_slots[i].real) continue;
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, np_ev[2 * i], np_ev[2 * i + 1]) != hipSuccess) continue;
-            sum[np_slots[i].kind] += 1e3 * (double)ms;
-            cnt[np_slots[i].kind] += 1;
-        }
-        const HostSystem& h = *H;
-        // algorithmic bytes: H product (KPB: + p, z, w_old in, p out), chain STEP of the Newton set (every chain its own factors)
-        double hbytes = 0.0;
-        if (Hb.on) { for (double b : Hb.L.bytes) hbytes += b; }
-        else hbytes = 12.0 * (double)hm_nnz + 4.0 * (double)(h.n_tot + 1);
-        hbytes += 40.0 * (double)h.n_tot;
-        const double fbytes = (Hset.use_fac32 ? 4.0 : 8.0) * (double)Hset.fac_doubles;
-        np_out[0] = cnt[0]; np_out[1] = cnt[0] ? sum[0] / cnt[0] : 0.0; np_out[2] = hbytes;
-        np_out[3] = cnt[1]; np_out[4] = cnt[1] ? sum[1] / cnt[1] : 0.0; np_out[5] = fbytes;
-        np_out[6] = (double)Hset.blocks(); np_out[7] = (double)n_prec;
-        for (hipEvent_t e : np_ev) (void)hipEventDestroy(e);
-        np_ev.clear(); np_slots.clear();
-        np_armed = false;
     }
     // product over the plain rows of M (the matrices that belong to no set -- G1, G2 -- and launch_product's other half)
     template <int MODE>
@@ -2848,6 +2817,16 @@ struct HipBackend {
         }
     }
 
+    // k_xupdate: xt += a p, kx += a w, x relaxed, with the step of r'z partials `rz_old`
+    VecArgs xupdate_args(const double* p_dir, const double* rz_old, int apply_alpha) {
+        VecArgs va{};
+        va.first_row = vb_first.d; va.end_row = vb_end.d; va.blk_prob = vb_prob.d; va.done = done.d;
+        va.prec_part_ptr = prec_part_ptr.d; va.kblk_part_ptr = Kset.blk_part.d;
+        va.pw_part = pw_part.d; va.p = p_dir; va.w = w.d; va.kx = kx.d; va.xt = xtu.d; va.x = xy.d;
+        va.alpha_relax = st.alpha; va.rz_old = rz_old; va.apply_alpha = apply_alpha;
+        return va;
+    }
+
     // enqueue one ADMM iteration on `stream`; a measuring iteration additionally
     // leaves r'z before and after the PCG sweep in rz_meas0 / rz_meas1
     // The end-of-PCG update of an iteration (xt += a p, kx += a w, x relaxed) is applied by
@@ -2890,12 +2869,7 @@ struct HipBackend {
             pa.tstamp = nullptr;
             pa.p = p_cur; pa.rz_in = rz_cur; pa.rz_out = rz_meas1.d;
             launch_prec<PREC_STEP>(Kset, pa);  // also applies xt += a p, kx += a w, r -= a w
-            VecArgs va{};
-            va.first_row = vb_first.d; va.end_row = vb_end.d; va.blk_prob = vb_prob.d; va.done = done.d;
-            va.prec_part_ptr = prec_part_ptr.d; va.kblk_part_ptr = Kset.blk_part.d;
-            va.pw_part = pw_part.d; va.p = p_cur; va.w = w.d; va.kx = kx.d; va.xt = xtu.d; va.x = xy.d;
-            va.alpha_relax = st.alpha; va.rz_old = rz_cur; va.apply_alpha = 0;
-            hipLaunchKernelGGL(k_xupdate, dim3(n_vblocks), dim3(kThreads), 0, stream, va);
+            hipLaunchKernelGGL(k_xupdate, dim3(n_vblocks), dim3(kThreads), 0, stream, xupdate_args(p_cur, rz_cur, 0));
         } else {
             ca.apply_alpha = 1; ca.pfin = p_cur; ca.rz_in = rz_cur;
             last_rz = rz_cur;  // what the next iteration's right-hand-side kernel has to apply
@@ -2903,8 +2877,9 @@ struct HipBackend {
         }
         ca.tstamp = slot(5);
         if (n_cone_blocks) {
-            unsigned cgrid = (unsigned)n_cone_blocks;
-            if (n_cone_blocks >= 16) { ca.xcd_chunk = (n_cone_blocks + 7) / 8; ca.n_blocks = n_cone_blocks; cgrid = 8u * (unsigned)ca.xcd_chunk; }
+            int chunk = 0;
+            const unsigned cgrid = xcd_grid_of(n_cone_blocks, chunk);
+            if (chunk) { ca.xcd_chunk = chunk; ca.n_blocks = n_cone_blocks; }
             launch_on_stream(k_cone, dim3(cgrid), dim3(kThreads), 0, 5, ca);
             ca.xcd_chunk = 0;
         }
@@ -2913,79 +2888,6 @@ struct HipBackend {
             hipLaunchKernelGGL(k_cone_wave, dim3((unsigned)((n_large_cones + 3) / 4)), dim3(kThreads), 0, stream, ca,
                                (const int2*)cone_large.d, n_large_cones);
         }
-    }
-
-    // in-loop duration of the six kernels of an iteration (see score_time_iteration):
-    //   us[0..5]   device wall clock, first workgroup in -> last workgroup out
-    //   us[6..11]  begin -> end of the dispatch as the runtime records it (start/stop events bound to
-    //              the launch itself: the interval rocprofv3 --kernel-trace reports); 0 when with_events == 0
-    // The two are taken in separate passes over the same iterations (the per-launch events make
-    // the runtime wait for each dispatch's completion signal, which the plain pass does not).
-    void time_iteration(int warmup, int iters, double* us, int with_events) {
-        if (cg_iters != 2) throw std::runtime_error("score_time_iteration: needs cg_iters == 2");
-        iters = std::max(1, iters);
-        int khz = 0;
-        HIP_CHECK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, st.device));
-        if (khz <= 0) throw std::runtime_error("score_time_iteration: no wall clock rate");
-        for (int k = 0; k < 12; ++k) us[k] = 0.0;
-        const int maxb = std::max(std::max(G1.nblocks, Kset.blocks()) + 8, std::max(n_prec + n_help, n_cone_blocks + 8));  // (grids: XCD rounding, update helpers)
-        ts_stride = (size_t)2 * maxb;
-        const size_t per_iter = 6 * ts_stride, nslot = per_iter * iters;
-        {
-            std::vector<unsigned long long> hts(nslot);
-            for (size_t i = 0; i < nslot; i += 2) { hts[i] = ~0ull; hts[i + 1] = 0ull; }
-            DevBuf<unsigned long long> dts;  // (tl_arena is null outside init: a plain hipMalloc on the handle's device)
-            dts.alloc(nslot);
-            HIP_CHECK(hipMemcpyAsync(dts.d, hts.data(), nslot * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
-            HIP_CHECK(sync_stream(stream));
-            for (int i = 0; i < warmup; ++i) enqueue_iteration(false, i == 0);
-            for (int i = 0; i < iters; ++i) enqueue_iteration(false, warmup == 0 && i == 0, dts.d + per_iter * i);
-            HIP_CHECK(hipMemcpyAsync(hts.data(), dts.d, nslot * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-            HIP_CHECK(sync_stream(stream));
-            HIP_CHECK(hipGetLastError());
-            for (int i = 0; i < iters; ++i)
-                for (int k = 0; k < 6; ++k) {
-                    const unsigned long long* p = &hts[per_iter * i + ts_stride * k];
-                    unsigned long long t0 = ~0ull, t1 = 0ull;
-                    for (int b = 0; b < maxb; ++b) { t0 = std::min(t0, p[2 * b]); t1 = std::max(t1, p[2 * b + 1]); }
-                    if (t1 > t0) us[k] += (double)(t1 - t0) * 1e3 / (double)khz / iters;
-                }
-            if (trace_on("stamps")) {
-                // per-workgroup timeline of the last timed iteration: kernel, workgroup, entry and exit in us after the
-                // iteration's first entry (stdout; profiles/scripts/r04_timeline.py draws it)
-                const unsigned long long* base = &hts[per_iter * (size_t)(iters - 1)];
-                unsigned long long t00 = ~0ull;
-                for (size_t j = 0; j < per_iter; j += 2) t00 = std::min(t00, base[j]);
-                for (int k = 0; k < 6; ++k)
-                    for (int b = 0; b < maxb; ++b) {
-                        const unsigned long long a0 = base[ts_stride * k + 2 * (size_t)b], a1 = base[ts_stride * k + 2 * (size_t)b + 1];
-                        if (a0 == ~0ull || a1 == 0ull) continue;
-                        std::printf("STAMP %d %d %.3f %.3f\n", k, b, (double)(a0 - t00) * 1e3 / (double)khz, (double)(a1 - t00) * 1e3 / (double)khz);
-                    }
-            }
-        }
-        if (!with_events) return;
-        std::vector<hipEvent_t> evs((size_t)12 * iters, nullptr);
-        struct EvFree {
-            std::vector<hipEvent_t>& v;
-            ~EvFree() { for (hipEvent_t e : v) if (e) (void)hipEventDestroy(e); }
-        } ev_free{evs};
-        for (auto& e : evs) HIP_CHECK(hipEventCreate(&e));
-        for (int i = 0; i < warmup; ++i) enqueue_iteration(false, false);
-        for (int i = 0; i < iters; ++i) {
-            tev = evs.data() + (size_t)12 * i;
-            enqueue_iteration(false, false);
-        }
-        tev = nullptr;
-        HIP_CHECK(sync_stream(stream));
-        HIP_CHECK(hipGetLastError());
-        for (int i = 0; i < iters; ++i)
-            for (int k = 0; k < 6; ++k) {
-                if (k == 5 && !n_cone_blocks) continue;
-                float ms = 0.f;
-                HIP_CHECK(hipEventElapsedTime(&ms, evs[(size_t)12 * i + 2 * k], evs[(size_t)12 * i + 2 * k + 1]));
-                us[6 + k] += 1e3 * (double)ms / iters;
-            }
     }
 
     void build_graph(int iters) {
@@ -3165,270 +3067,6 @@ struct HipBackend {
         if (s_out) for (int64_t i = 0; i < m; ++i) s_out[i] = hs[i] / h.E[i];
     }
 
-    int64_t get_vec(const char* name, double* out, int64_t len) {
-        const HostSystem& h = *H;
-        const double* src = nullptr;
-        int64_t sz = 0;
-        bool host = false;
-        std::string nm(name);
-        // the device-against-host checks ("ag_device_check", "polish_build_check"): a device array on the host; entries that
-        // differ (+ the difference in length); largest difference (1e300 when the lengths differ)
-        auto down_i = [&](const int32_t* d, size_t cnt) {
-            std::vector<int32_t> v(cnt);
-            if (cnt) staged_d2h(v.data(), d, cnt * sizeof(int32_t), stream);
-            HIP_CHECK(sync_stream(stream));
-            return v;
-        };
-        auto down_d = [&](const double* d, size_t cnt) {
-            std::vector<double> v(cnt);
-            if (cnt) staged_d2h(v.data(), d, cnt * sizeof(double), stream);
-            HIP_CHECK(sync_stream(stream));
-            return v;
-        };
-        auto mism = [](const std::vector<int32_t>& x, const std::vector<int32_t>& y) {
-            double c = (double)(x.size() > y.size() ? x.size() - y.size() : y.size() - x.size());
-            for (size_t i = 0; i < std::min(x.size(), y.size()); ++i) c += x[i] != y[i];
-            return c;
-        };
-        auto maxd = [](const std::vector<double>& x, const std::vector<double>& y) {
-            double c = x.size() == y.size() ? 0.0 : 1e300;
-            for (size_t i = 0; i < std::min(x.size(), y.size()); ++i) c = std::max(c, std::fabs(x[i] - y[i]));
-            return c;
-        };
-        if (nm == "xt") { src = xtu.d; sz = h.n_tot; }
-        else if (nm == "u") { src = xtu.d + h.n_tot; sz = h.m_tot; }
-        else if (nm == "x") { src = xy.d; sz = h.n_tot; }
-        else if (nm == "y") { src = xy.d + h.n_tot; sz = h.m_tot; }
-        else if (nm == "s") { src = s.d; sz = h.m_tot; }
-        else if (nm == "r") { src = r.d; sz = h.n_tot; }
-        else if (nm == "z") { src = z.d; sz = h.n_tot; }
-        else if (nm == "p") { src = dbg_p ? dbg_p : ((cg_iters % 2 == 1) ? p.d : p2.d); sz = h.n_tot; }  // last PCG direction
-        else if (nm == "w") { src = w.d; sz = h.n_tot; }
-        else if (nm == "kx") { src = kx.d; sz = h.n_tot; }
-        else if (nm == "D" && h.device_setup) { src = Dd.d; sz = h.n_tot; }
-        else if (nm == "E" && h.device_setup) { src = Ed.d; sz = h.m_tot; }
-        else if (nm == "D") { src = h.D.data(); sz = h.n_tot; host = true; }
-        else if (nm == "E") { src = h.E.data(); sz = h.m_tot; host = true; }
-        else if (nm == "K0" || nm == "K1" || nm == "Aval" || nm == "G1val" || nm == "G2val" || nm == "qs" || nm == "bs" || nm == "invD" || nm == "invE") {
-            // the setup's value arrays as the kernels read them (tests: device setup against host setup, bit for bit)
-            const int64_t nk = (int64_t)h.K.col.size(), na = (int64_t)h.A.ptr[(size_t)h.m_tot];
-            const int64_t n1 = h.device_setup ? g1_nnz : (int64_t)h.G1.col.size(), n2 = (int64_t)h.G2.ptr[(size_t)h.n_tot];
-            if (nm == "K0") { src = K0d.d; sz = nk; } else if (nm == "K1") { src = K1d.d; sz = nk; }
-            else if (nm == "Aval") { src = A_val.d; sz = na; } else if (nm == "G1val") { src = G1.val.d; sz = n1; }
-            else if (nm == "G2val") { src = G2.val.d; sz = n2; } else if (nm == "qs") { src = q.d; sz = h.n_tot; }
-            else if (nm == "bs") { src = b.d; sz = h.m_tot; } else if (nm == "invD") { src = invD.d; sz = h.n_tot; }
-            else { src = invE.d; sz = h.m_tot; }
-        }
-        else if (nm == "Acol" || nm == "Aptr" || nm == "G1col" || nm == "G1ptr" || nm == "G2col" || nm == "G2ptr" || nm == "G2split" || nm == "Kcol_dev" || nm == "Kptr_dev") {
-            const int64_t nk = (int64_t)h.K.col.size(), na = (int64_t)h.A.ptr[(size_t)h.m_tot];
-            const int64_t n1 = h.device_setup ? g1_nnz : (int64_t)h.G1.col.size(), n2 = (int64_t)h.G2.ptr[(size_t)h.n_tot];
-            const int32_t* isrc = nullptr;
-            if (nm == "Acol") { isrc = A_col.d; sz = na; } else if (nm == "Aptr") { isrc = A_ptr.d; sz = h.m_tot + 1; }
-            else if (nm == "G1col") { isrc = G1.col.d; sz = n1; } else if (nm == "G1ptr") { isrc = G1.ptr.d; sz = h.n_tot + 1; }
-            else if (nm == "G2col") { isrc = G2.col.d; sz = n2; } else if (nm == "G2ptr") { isrc = G2.ptr.d; sz = h.n_tot + 1; }
-            else if (nm == "G2split") { isrc = G2.split.d; sz = h.n_tot; } else if (nm == "Kcol_dev") { isrc = K.col.d; sz = nk; }
-            else { isrc = K.ptr.d; sz = h.n_tot + 1; }
-            if (out && len > 0) {
-                std::vector<int32_t> tmp((size_t)std::min(len, sz));
-                HIP_CHECK(sync_stream(stream));
-                staged_d2h(tmp.data(), isrc, tmp.size() * sizeof(int32_t), stream);
-                HIP_CHECK(sync_stream(stream));
-                for (size_t i = 0; i < tmp.size(); ++i) out[i] = (double)tmp[i];
-            }
-            return sz;
-        }
-        else if (nm == "setup_scalars") {  // per problem: |q|_inf, |b|_inf unscaled and scaled, kkt_bytes
-            sz = 5 * (int64_t)h.count;
-            if (out && len >= sz)
-                for (int p = 0; p < h.count; ++p) {
-                    out[5 * p] = h.qnorm_u[(size_t)p]; out[5 * p + 1] = h.qnorm_s[(size_t)p]; out[5 * p + 2] = h.bnorm_u[(size_t)p];
-                    out[5 * p + 3] = h.bnorm_s[(size_t)p]; out[5 * p + 4] = h.kkt_bytes[(size_t)p];
-                }
-            return sz;
-        }
-        else if (nm == "device_setup") {
-            if (out && len > 0) out[0] = h.device_setup ? 1.0 : 0.0;
-            return 1;
-        }
-        else if (nm == "Kval") { src = K.val.d; sz = (int64_t)h.K.col.size(); }
-        else if (nm == "rep") {  // [replicas the kernels run with (1 = general problem), nnz of the stored K, of the stored A']
-            const double v[3] = {(double)h.rep, (double)h.K.col.size(), (double)(h.device_setup ? (size_t)g1_nnz : h.G1.col.size())};
-            if (out && len > 0) std::memcpy(out, v, sizeof(double) * (size_t)std::min<int64_t>(len, 3));
-            return 3;
-        }
-        else if (nm == "links") {  // [node pairs outside the chains, pairs inside the preconditioner, unknowns, affected chains, rounds, problems whose capacitance matrix was singular]
-            double v[6] = {(double)link_plan.pairs_total, (double)link_plan.pairs_used, (double)n_link_u, (double)n_link_items, (double)link_rounds, 0.0};
-            if (n_link_probs && out) {
-                std::vector<int32_t> stt((size_t)n_link_probs);
-                HIP_CHECK(sync_stream(stream));
-                for (int set = 0; set < 2; ++set) {
-                    if (!pset[set].link_on) continue;
-                    HIP_CHECK(hipMemcpy(stt.data(), pset[set].link_status.d, sizeof(int32_t) * (size_t)n_link_probs, hipMemcpyDeviceToHost));
-                    for (int32_t x : stt) v[5] += x;
-                }
-            }
-            if (out && len > 0) std::memcpy(out, v, sizeof(double) * (size_t)std::min<int64_t>(len, 6));
-            return 6;
-        }
-        else if (nm == "link_pairs") {  // first columns of the node pairs inside the Newton preconditioner (two per pair)
-            const std::vector<int32_t>& pc = link_plan.pair_cols;
-            const int64_t np_ = n_link_items ? (int64_t)pc.size() : 0;
-            if (out) for (int64_t i = 0; i < np_ && i < len; ++i) out[i] = (double)pc[(size_t)i];
-            return np_;
-        }
-        else if (nm == "fac") { src = Kset.fac.d; sz = (int64_t)Kset.fac_doubles; }
-        else if (nm == "newton_probe_arm") {  // the next polish times its PCG launches (see probe_slot)
-            if (!Q.available) return -1;
-            if (out && len > 0) {
-                for (hipEvent_t e : np_ev) (void)hipEventDestroy(e);
-                np_ev.assign((size_t)2 * kProbeCap, nullptr);
-                for (auto& e : np_ev)
-                    if (hipEventCreate(&e) != hipSuccess) return -2;
-                np_slots.clear();
-                np_armed = true;
-                out[0] = 1.0;
-            }
-            return 1;
-        }
-        else if ((nm == "ag_device_check" || nm == "polish_build_check") && h.device_setup) return -1;  // (no host matrices to compare with: SCORE_HOST_SETUP=1)
-        else if (nm == "ag_device_check") {
-            // the equilibrated A, G1, G2 on the device against the host arrays: [derived on the device (0/1), mismatching
-            // columns of A, max |A value difference|, the same for G1, for G2]
-            if (out && len >= 7) {
-                out[0] = derive_ag ? 1.0 : 0.0;
-                out[1] = mism(down_i(A_col.d, h.A.col.size()), h.A.col); out[2] = maxd(down_d(A_val.d, h.A.val.size()), h.A.val);
-                out[3] = mism(down_i(G1.col.d, h.G1.col.size()), h.G1.col); out[4] = maxd(down_d(G1.val.d, h.G1.val.size()), h.G1.val);
-                out[5] = mism(down_i(G2.col.d, h.G2.col.size()), h.G2.col); out[6] = maxd(down_d(G2.val.d, h.G2.val.size()), h.G2.val);
-            }
-            return 7;
-        }
-        else if (nm == "polish_build_check") {
-            // the Newton matrix built on the device against the host loop's (score_polish_host.hpp): [built on the device (0/1),
-            // entries device, entries host, mismatching row pointers, columns, max |P-on-pattern difference|, mismatching
-            // list pointers, cones, block indices, max |coefficient difference|, mismatching chain positions (diagonal,
-            // sub-diagonal), Jacobi positions, long entries]
-            if (!Q.available) return -1;
-            if (out && len >= 14) {
-                PolishData R;
-                build_polish(h, R, false, false);
-                const size_t nz = (size_t)hm_nnz, nc = R.ccone.size();
-                out[0] = polish_on_device ? 1.0 : 0.0;
-                out[1] = (double)hm_nnz; out[2] = (double)R.Hm.col.size();
-                out[3] = mism(down_i(Hm.ptr.d, (size_t)h.n_tot + 1), R.Hm.ptr);
-                out[4] = mism(down_i(Hm.col.d, nz), R.Hm.col);
-                out[5] = maxd(down_d(q_Pon.d, nz), R.Pon);
-                out[6] = mism(down_i(q_cptr.d, nz + 1), R.cptr);
-                out[7] = mism(down_i(q_ccone.d, nc), R.ccone);
-                out[8] = mism(down_i(q_cab.d, nc), R.cab);
-                out[9] = maxd(down_d(q_ccoef.d, nc), R.ccoef);
-                out[10] = mism(down_i(Hset.posd.d, R.pos_diag.size()), R.pos_diag);
-                out[11] = mism(down_i(Hset.poss.d, R.pos_sub.size()), R.pos_sub);
-                out[12] = mism(down_i(Hset.diagpos.d, R.diag_pos.size()), R.diag_pos);
-                out[13] = mism(Q.long_ent, R.long_ent) + mism(Q.long_prob, R.long_prob);
-            }
-            return 14;
-        }
-        else if (nm == "newton_probe") {
-            // [H products timed, mean us, bytes per launch, chain STEPs timed, mean us, factor bytes per launch, H tiles, prec work items]
-            if (out && len > 0) std::memcpy(out, np_out, sizeof(double) * (size_t)std::min<int64_t>(len, 8));
-            return 8;
-        }
-        // ---- kernel-level checks of the Newton polish (tests/test_gpu_parity.py) ----
-        else if (nm == "polish_assemble_at_x") {
-            // evaluate F, gradient, generalised Hessian and its chain factors at the current ADMM
-            // iterate x (what the first Newton iteration does); returns F
-            if (!Q.available) return -1;
-            if (out && len > 0) {
-                try {
-                    c_step.assign(h.count, 1.0); c_tol2.assign(h.count, 0.0); c_skip.assign(h.count, 0);
-                    std::vector<char> all(h.count, 1);
-                    NewtonVecArgs va{};
-                    va.n = h.n_tot; va.is_head = q_ishead.d; va.g = q_g.d; va.part = q_gd.d;
-                    HIP_CHECK(hipMemsetAsync(q_g.d, 0, q_g.n * sizeof(double), stream));
-                    va.u = xy.d; va.delta = xy.d; va.step = 0.0; va.out = q_X0.d;
-                    hipLaunchKernelGGL(k_newton_trial, dim3((unsigned)((h.n_tot + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, va);
-                    upload_skip(all);
-                    std::vector<double> F(h.count), gn(h.count);
-                    newton_eval_batch(q_X0.d, all, F, gn);
-                    newton_hessian(q_skip.d);
-                    HIP_CHECK(sync_stream(stream));
-                    out[0] = F[0];
-                } catch (const std::exception&) { return -2; }
-            }
-            return 1;
-        }
-        else if (nm == "polish_prec_of_negg") {
-            // z = M^-1 (-g) with the Newton preconditioner as factored on the device (k_factor), applied by
-            // the chain kernel the PCG uses
-            if (!Q.available) return -1;
-            if (out && len > 0) {
-                PrecArgs pa = prec_args(Hset);
-                pa.done = q_skip.d;
-                prec_vectors(pa, r.d, q_negg.d, z.d, p.d, w.d, q_delta.d, q_dummy.d, q_pw.d);
-                pa.rz_in = nullptr; pa.rz_out = rz_part0.d;
-                launch_prec<PREC_INIT>(Hset, pa);
-            }
-            src = z.d; sz = h.n_tot;
-        }
-        else if (nm == "polish_g") { src = q_g.d; sz = Q.available ? h.n_tot : 0; }
-        else if (nm == "Hval") { src = Hm.val.d; sz = Q.available ? hm_nnz : 0; }
-        else if (nm == "Hcol" || nm == "Hptr" || nm == "is_head" || nm == "chain_of_col") {
-            if (!Q.available) return -1;
-            std::vector<double> tmp;
-            if (nm == "is_head" && h.device_setup) {  // (made on the device: the host never held it)
-                std::vector<int32_t> ih((size_t)h.n_tot);
-                staged_d2h(ih.data(), q_ishead.d, sizeof(int32_t) * ih.size(), stream);
-                HIP_CHECK(sync_stream(stream));
-                tmp.assign(ih.begin(), ih.end());
-            } else
-            if (nm == "Hcol" && polish_on_device) {  // (built on the device: the host never held it)
-                std::vector<int32_t> hc((size_t)hm_nnz);
-                staged_d2h(hc.data(), Hm.col.d, sizeof(int32_t) * hc.size(), stream);
-                HIP_CHECK(sync_stream(stream));
-                tmp.assign(hc.begin(), hc.end());
-            }
-            else if (nm == "Hcol") tmp.assign(Q.Hm.col.begin(), Q.Hm.col.end());
-            else if (nm == "Hptr") tmp.assign(Q.Hm.ptr.begin(), Q.Hm.ptr.end());
-            else if (nm == "is_head") tmp.assign(Q.is_head.begin(), Q.is_head.end());
-            else {  // per column: chain node index (global numbering over all chains) or -1
-                tmp.assign(h.n_tot, -1.0);
-                for (size_t ci = 0; ci < h.chains.size(); ++ci)
-                    for (int i = 0; i < h.chains[ci].N; ++i)
-                        for (int c = 0; c < h.bs; ++c) tmp[h.node_col[h.chains[ci].node_begin + i] + c] = (double)(h.chains[ci].node_begin + i);
-            }
-            sz = (int64_t)tmp.size();
-            if (out && len > 0) std::memcpy(out, tmp.data(), sizeof(double) * (size_t)std::min(len, sz));
-            return sz;
-        }
-        else if (nm == "Kcol" || nm == "Kptr") {  // pattern of the K the kernels stream (a replicated problem: replica 0 + tail rows)
-            std::vector<double> tmp;
-            if (nm == "Kcol") tmp.assign(h.K.col.begin(), h.K.col.end());
-            else tmp.assign(h.K.ptr.begin(), h.K.ptr.end());
-            sz = (int64_t)tmp.size();
-            if (out && len > 0) std::memcpy(out, tmp.data(), sizeof(double) * (size_t)std::min(len, sz));
-            return sz;
-        }
-        else if (nm == "chain_id_of_col") {
-            std::vector<double> tmp(h.n_tot, -1.0);
-            for (size_t ci = 0; ci < h.chains.size(); ++ci)
-                for (int i = 0; i < h.chains[ci].N; ++i)
-                    for (int c = 0; c < h.bs; ++c) tmp[h.node_col[h.chains[ci].node_begin + i] + c] = (double)ci;
-            sz = (int64_t)tmp.size();
-            if (out && len > 0) std::memcpy(out, tmp.data(), sizeof(double) * (size_t)std::min(len, sz));
-            return sz;
-        }
-        else return -1;
-        if (out && len > 0) {
-            const size_t bytes = sizeof(double) * (size_t)std::min(len, sz);
-            if (host) std::memcpy(out, src, bytes);
-            else {
-                if (sync_stream(stream) != hipSuccess) return -2;
-                try { staged_d2h(out, src, bytes, stream); } catch (const std::exception&) { return -2; }
-            }
-        }
-        return sz;
-    }
-
     // ---- linear mode: K x = rhs by the chain-preconditioned PCG of the ADMM loop (k_prec_pre / k_prec +
     //      k_spmv), K factored on the device (k_factor), termination on the device (pcg_gate):
     //      r'M^-1 r <= rel_tol^2 r0'M^-1 r0.  The host looks at one flag per chunk of iterations. ----
@@ -3491,12 +3129,12 @@ struct HipBackend {
         pa.gate_first = q.first ? 1 : 0;
         pa.r_in = q.first ? q.rhs : r.d;
         pa.xt_zero = q.first ? 1 : 0;
-        launch_prec<PREC_STEP>(*q.set, pa, q.probe ? probe_slot(1, q.queued) : -1);
+        launch_prec<PREC_STEP>(*q.set, pa, q.probe ? probe_slot(*this, 1, q.queued) : -1);
         tev = nullptr;
         SpmvArgs a = pcg_product_args(q);
         a.z = z.d; a.p_out = q.p_oth; a.rz_new = rz_nxt; a.rz_old = q.rz_cur;
         a.early_done = 1;
-        launch_product<MODE_KPB>(*q.set, a, q.probe ? probe_slot(0, q.queued) : -1);
+        launch_product<MODE_KPB>(*q.set, a, q.probe ? probe_slot(*this, 0, q.queued) : -1);
         tev = nullptr;
         std::swap(q.p_cur, q.p_oth);
         if (++q.queued % kDirectEvery == 0) {
@@ -4150,7 +3788,6 @@ struct HipBackend {
                 std::fprintf(stderr, "[score] newton it %d: active-set flips since the last factorisation (max over live problems) %.0f -> %d problems refactor\n", it + 1, mx, nre);
             }
             upload_skip(live, /*consume=*/true);
-            np_newton_it = it;
             newton_hessian(q_fskip.d, refactor);  // (a frozen problem's short entries keep their values, see k_hassemble)
             newton_pcg_follow(live, 400);  // (queued a few iterations ahead of the device until every live problem's gate has fired)
             int used_now = 0;
@@ -4182,7 +3819,7 @@ struct HipBackend {
                         for (int b = Q.rbH.part_ptr[p]; b < Q.rbH.part_ptr[p + 1]; ++b) gd[p] += h_gd[b];
                     }
                     pcg_used_total += used_now;
-                    probe_mark(used_now);
+                    probe_mark(*this, used_now);
                 }
                 std::vector<int32_t> acc_now(count, 0);
                 bool any_acc = false, any_ls = false;
@@ -4254,91 +3891,12 @@ struct HipBackend {
         }
         HIP_CHECK(sync_stream(stream));
         HIP_CHECK(hipGetLastError());
-        probe_collect();
+        probe_collect(*this);
         return true;
     }
-
-    void time_kernel(const std::string& which, int reps, double* ms) {
-        PrecArgs pa = prec_args(Kset);
-        pa.done = done.d;
-        prec_vectors(pa, r.d, r.d, z.d, p.d, w.d, xtu.d, kx.d, pw_part.d);
-        pa.rz_in = rz_part0.d; pa.rz_out = rz_part1.d;
-        VecArgs va{};
-        va.first_row = vb_first.d; va.end_row = vb_end.d; va.blk_prob = vb_prob.d; va.done = done.d;
-        va.prec_part_ptr = prec_part_ptr.d; va.kblk_part_ptr = Kset.blk_part.d;
-        va.pw_part = pw_part.d; va.p = p.d; va.w = w.d; va.kx = kx.d; va.xt = xtu.d; va.x = xy.d;
-        va.alpha_relax = st.alpha; va.rz_old = rz_part0.d; va.apply_alpha = 1;
-        auto once = [&]() {
-            if (which == "rhs") { SpmvArgs ra = spmv_args(G1, xtu.d); ra.apply_update = 1; launch_spmv<MODE_RHS>(G1, ra); }
-            else if (which.rfind("prec_init:", 0) == 0) { pa.debug_skip = std::atoi(which.c_str() + 10); launch_prec<PREC_INIT>(Kset, pa); }
-            else if (which == "prec_init") launch_prec<PREC_INIT>(Kset, pa);
-            else if (which.rfind("prec_step:", 0) == 0) { pa.debug_skip = std::atoi(which.c_str() + 10); launch_prec<PREC_STEP>(Kset, pa); }
-            else if (which == "prec_step") launch_prec<PREC_STEP>(Kset, pa);
-            // (segmented long chains: the chain kernel alone / the second level alone -- k_join_solve + k_join_apply)
-            else if (which == "prec_init_chain") launch_prec<PREC_INIT>(Kset, pa, -1, PrecDepth::chain);
-            else if (which == "prec_step_chain") launch_prec<PREC_STEP>(Kset, pa, -1, PrecDepth::chain);
-            else if (which == "join_init") { if (n_join_items) join_apply<PREC_INIT>(Kset, pa); }
-            else if (which == "join_step") { if (n_join_items) join_apply<PREC_STEP>(Kset, pa); }
-            else if (which == "kp") launch_kp(p.d);
-            else if (which == "kpb") launch_kpb(p.d, p2.d, rz_part1.d, rz_part0.d);
-            else if (which == "xupdate") hipLaunchKernelGGL(k_xupdate, dim3(n_vblocks), dim3(kThreads), 0, stream, va);
-            else if (which == "cone") { if (n_cone_blocks) { ConeArgs ca = cone_args(xtu.d); ca.apply_alpha = 1; hipLaunchKernelGGL(k_cone, dim3(n_cone_blocks), dim3(kThreads), 0, stream, ca); } }
-            else if (which == "nop") hipLaunchKernelGGL(k_nop, dim3(K.nblocks), dim3(kThreads), 0, stream, (int*)nullptr);
-            else if (which == "nop1") hipLaunchKernelGGL(k_nop, dim3(1), dim3(64), 0, stream, (int*)nullptr);
-            else if (which == "nop_load") hipLaunchKernelGGL(k_nop_load, dim3(K.nblocks), dim3(kThreads), 0, stream, K.blk_prob.d, done.d, (int*)nullptr);
-            else throw std::runtime_error("unknown kernel name");
-        };
-        // problems that have converged are skipped by every kernel: time them as active
-        const HostSystem& h = *H;
-        std::vector<int32_t> zero(h.count, 0), keep(h.count);
-        HIP_CHECK(sync_stream(stream));
-        HIP_CHECK(hipMemcpyAsync(keep.data(), done.d, keep.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(sync_stream(stream));
-        HIP_CHECK(hipMemcpyAsync(done.d, zero.data(), zero.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-        HIP_CHECK(sync_stream(stream));
-        for (int i = 0; i < 5; ++i) once();
-        HIP_CHECK(sync_stream(stream));
-        HIP_CHECK(hipEventRecord(ev0, stream));
-        for (int i = 0; i < reps; ++i) once();
-        HIP_CHECK(hipEventRecord(ev1, stream));
-        HIP_CHECK(hipEventSynchronize(ev1));
-        float t = 0;
-        HIP_CHECK(hipEventElapsedTime(&t, ev0, ev1));
-        *ms = (double)t / std::max(1, reps);
-        HIP_CHECK(hipMemcpyAsync(done.d, keep.data(), keep.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-        HIP_CHECK(sync_stream(stream));
-    }
-
-    // roofline probe: average launch duration of the KKT SpMV (w = K p), HIP
-    // events on the stream the solver launches on
-    void time_kkt(int reps, double* ms, double* bytes) {
-        const HostSystem& h = *H;
-        std::vector<double> hp(h.n_tot);
-        for (int64_t i = 0; i < h.n_tot; ++i) hp[i] = 1.0 + 1e-3 * (double)(i % 7);
-        HIP_CHECK(sync_stream(stream));
-        staged_h2d(p.d, hp.data(), hp.size() * sizeof(double), stream);
-        HIP_CHECK(sync_stream(stream));
-        std::vector<int32_t> zero(h.count, 0), keep(h.count);
-        HIP_CHECK(hipMemcpyAsync(keep.data(), done.d, keep.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(sync_stream(stream));
-        HIP_CHECK(hipMemcpyAsync(done.d, zero.data(), zero.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-        HIP_CHECK(sync_stream(stream));
-        for (int i = 0; i < 10; ++i) launch_kp(p.d);
-        HIP_CHECK(sync_stream(stream));
-        HIP_CHECK(hipEventRecord(ev0, stream));
-        for (int i = 0; i < reps; ++i) launch_kp(p.d);
-        HIP_CHECK(hipEventRecord(ev1, stream));
-        HIP_CHECK(hipEventSynchronize(ev1));
-        float t = 0;
-        HIP_CHECK(hipEventElapsedTime(&t, ev0, ev1));
-        *ms = (double)t / std::max(1, reps);
-        double bsum = 0;
-        for (double v : h.kkt_bytes) bsum += v;
-        *bytes = bsum;
-        HIP_CHECK(hipMemcpyAsync(done.d, keep.data(), keep.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-        HIP_CHECK(sync_stream(stream));
-    }
 };
+
+#include "score_inspect.hpp"
 
 }  // namespace
 
@@ -4358,13 +3916,51 @@ __global__ __launch_bounds__(256) void k_round_so(const double* __restrict__ M, 
     degenerate[i] = bad;
 }
 
-struct score_assembled {
-    score::AssembledQP qp;
-};
-
 struct score_handle {
     score::Solver<HipBackend> solver;
 };
+
+// (the generated arrays stay in device memory for as long as the batch lives: score_create_from_generated builds handles
+//  from them without another transfer)
+struct score_generated {
+    score::GeneratedBatch B;
+    DevArena arena;
+    int device = -1;
+    const int32_t* d_rel_base = nullptr; const int32_t* d_rel_to = nullptr; const int32_t* d_ra = nullptr; const int32_t* d_rb = nullptr;
+    const double* d_rel_t = nullptr; const double* d_rel_R = nullptr; const double* d_rel_kappa = nullptr; const double* d_rel_tau = nullptr;
+    const double* d_dist = nullptr; const double* d_prec = nullptr;
+    // (nothing to wait for when the batch goes: score_create_from_generated returns with its handle's setup -- the only reader of
+    //  these arrays -- complete; the arena's blocks go back to the cache)
+};
+
+// Setup builds (and teardown frees) a few hundred megabytes of host vectors per handle.  With glibc's
+// default thresholds each of them is an mmap / munmap pair with fresh page faults; raising the
+// thresholds once keeps that memory in the process heap, where the next handle finds it again.
+static void tune_host_allocator_once() {
+    static std::once_flag once;
+    std::call_once(once, [] {
+        // (glibc refuses an mmap threshold above HEAP_MAX_SIZE / 2 = 32 MiB and then keeps its default -- a
+        //  larger request here used to be a silent no-op)
+        mallopt(M_MMAP_THRESHOLD, 32 << 20);
+        mallopt(M_TRIM_THRESHOLD, 1 << 30);
+        mallopt(M_TOP_PAD, 64 << 20);
+    });
+}
+
+// What the shared boundary (score_abi.hpp) has to know about this library.
+struct AbiEnv {
+    // a call on a handle runs with the handle's device current (DeviceGuard), and counts as an active solve where it
+    // creates, solves, reads estimates or destroys (ActiveSolve)
+    struct Scope {
+        std::optional<ActiveSolve> active;
+        DeviceGuard guard;
+        Scope(int device, bool solving) : guard(device) { if (solving) active.emplace(); }
+    };
+    static void before_create() { tune_host_allocator_once(); }
+    static void require_device(int device) { require_hip_device(device); }
+};
+
+#include "score_abi.hpp"
 
 // Local refinement after SCORE on the device (score_gn.hpp): state, blocks and gathers here, the damped
 // normal equations through the linear-mode handle `lin` (its K0 values and right-hand side are written
@@ -4502,214 +4098,64 @@ struct score_refine {
 
 extern "C" {
 
-void score_default_settings(score_settings* s) { score::default_settings(s); }
-
-// Setup builds (and teardown frees) a few hundred megabytes of host vectors per handle.  With glibc's
-// default thresholds each of them is an mmap / munmap pair with fresh page faults; raising the
-// thresholds once keeps that memory in the process heap, where the next handle finds it again.
-static void tune_host_allocator_once() {
-    static std::once_flag once;
-    std::call_once(once, [] {
-        // (glibc refuses an mmap threshold above HEAP_MAX_SIZE / 2 = 32 MiB and then keeps its default -- a
-        //  larger request here used to be a silent no-op)
-        mallopt(M_MMAP_THRESHOLD, 32 << 20);
-        mallopt(M_TRIM_THRESHOLD, 1 << 30);
-        mallopt(M_TOP_PAD, 64 << 20);
-    });
-}
-
-int score_create_batch(const score_problem* p, int32_t count, const score_settings* s, score_handle** out) {
-    try {
-        ActiveSolve active;
-        tune_host_allocator_once();
-        if (!p || !out) throw std::runtime_error("null argument");
-        score_settings st;
-        if (s) st = *s; else score::default_settings(&st);
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-            throw std::runtime_error("no HIP device available (the SCORE solver has no CPU fallback)");
-        if (st.device < 0 || st.device >= ndev) throw std::runtime_error("score_settings.device out of range");
-        DeviceGuard guard(st.device);
-        auto* h = new score_handle();
-        try {
-            h->solver.create(p, count, st);
-        } catch (...) {
-            delete h;
-            throw;
-        }
-        *out = h;
-        return 0;
-    } catch (const std::exception& e) {
-        g_err = e.what();
-        return -1;
-    }
-}
-int score_create(const score_problem* p, const score_settings* s, score_handle** out) {
-    return score_create_batch(p, 1, s, out);
-}
 static int score_create_from_graphs_impl(const score_graph* graphs, int32_t count, const score_settings* s, score_handle** out, const HipBackend::GenSource* gen_src) {
-    try {
-        ActiveSolve active;
-        tune_host_allocator_once();
-        if (!graphs || !out) throw std::runtime_error("null argument");
-        score_settings st;
-        if (s) st = *s; else score::default_settings(&st);
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-            throw std::runtime_error("no HIP device available (the SCORE solver has no CPU fallback)");
-        if (st.device < 0 || st.device >= ndev) throw std::runtime_error("score_settings.device out of range");
-        DeviceGuard guard(st.device);
-        auto* h = new score_handle();
-        h->solver.be.gen_src = gen_src;
-        struct ClearSrc { score_handle* h; ~ClearSrc() { h->solver.be.gen_src = nullptr; } };
-        try {
-            ClearSrc clear{h};
-            h->solver.create_from_graphs(graphs, count, st, [&](const score_graph* gs, bool keep_hf) {
+    return abi_call([&] {
+        AbiEnv::before_create();
+        require(graphs && out);
+        const score_settings st = resolve_settings(s);
+        AbiEnv::require_device(st.device);
+        AbiEnv::Scope scope(st.device, true);
+        publish_new(out, [&](score_handle& h) {
+            h.solver.be.gen_src = gen_src;
+            struct ClearSrc { score_handle& h; ~ClearSrc() { h.solver.be.gen_src = nullptr; } } clear{h};
+            h.solver.create_from_graphs(graphs, count, st, [&](const score_graph* gs, bool keep_hf) {
                 std::vector<score::AssembledQP> qps((size_t)count);
                 std::vector<score::AssembledQP*> ptrs((size_t)count);
                 for (int i = 0; i < count; ++i) ptrs[(size_t)i] = &qps[(size_t)i];
                 score::assemble_graphs(gs, count, ptrs.data());
                 std::vector<score_problem> probs((size_t)count);
                 for (int i = 0; i < count; ++i) qps[(size_t)i].view(&probs[(size_t)i]);
-                h->solver.create(probs.data(), count, st, keep_hf);
+                h.solver.create(probs.data(), count, st, keep_hf);
             });
-        } catch (...) {
-            delete h;
-            throw;
-        }
-        *out = h;
+        });
         return 0;
-    } catch (const std::exception& e) {
-        g_err = e.what();
-        return -1;
-    }
+    });
 }
 int score_create_from_graphs(const score_graph* graphs, int32_t count, const score_settings* s, score_handle** out) {
     return score_create_from_graphs_impl(graphs, count, s, out, nullptr);
 }
 int score_read_estimates(score_handle* h, int32_t qcqp_directions, double* poses, double* relaxed, double* landmarks, double* ranges,
                          int32_t* degenerate) {
-    try {
-        if (!h) throw std::runtime_error("null handle");
-        if (!h->solver.est.valid()) throw std::runtime_error("score_read_estimates: the handle was not made by score_create_from_graphs");
-        DeviceGuard guard(h->solver.st.device);
-        ActiveSolve active;
+    return abi_call([&] {
+        require(h != nullptr, "null handle");
+        require(h->solver.est.valid(), "score_read_estimates: the handle was not made by score_create_from_graphs");
+        auto scope = handle_scope(h, true);
         h->solver.be.read_estimates(h->solver.H, h->solver.est, (qcqp_directions || h->solver.est.dirs_always) ? 1 : 0, poses, relaxed, landmarks, ranges, degenerate);
         return 0;
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
-}
-int score_graphs_connected(const score_graph* graphs, int32_t count) {
-    if (!graphs || count < 0) { g_err = "null argument"; return -1; }
-    for (int32_t i = 0; i < count; ++i)
-        if (!score::graph_connected(graphs[i])) return i + 1;
-    return 0;
-}
-int score_dims(const score_handle* h, int64_t* n_total, int64_t* m_total, int32_t* count) {
-    if (!h) { g_err = "null handle"; return -1; }
-    if (n_total) *n_total = h->solver.user_n();  // (the programs as given: score_headform.hpp)
-    if (m_total) *m_total = h->solver.user_m();
-    if (count) *count = h->solver.H.count;
-    return 0;
-}
-int score_solve(score_handle* h, double* x, double* y, double* s, score_info* infos) {
-    try {
-        if (!h) throw std::runtime_error("null handle");
-        DeviceGuard guard(h->solver.st.device);
-        ActiveSolve active;
-        return h->solver.solve(x, y, s, infos);
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
-}
-int score_reset(score_handle* h) {
-    try {
-        if (!h) throw std::runtime_error("null handle");
-        DeviceGuard guard(h->solver.st.device);
-        h->solver.reset();
-        return 0;
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
-}
-int score_solve_steps(score_handle* h, int32_t iters, double* x, double* y, double* s, score_info* infos) {
-    try {
-        if (!h) throw std::runtime_error("null handle");
-        DeviceGuard guard(h->solver.st.device);
-        ActiveSolve active;
-        return h->solver.steps(iters, x, y, s, infos);
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
-}
-int score_newton_steps(score_handle* h, int32_t iters, double* x, double* y, double* s, score_info* infos) {
-    try {
-        if (!h) throw std::runtime_error("null handle");
-        DeviceGuard guard(h->solver.st.device);
-        ActiveSolve active;
-        return h->solver.newton_steps(iters, x, y, s, infos);
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
-}
-int score_linear_create(const score_problem* pattern, const score_settings* s, score_handle** out) {
-    try {
-        if (!pattern || !out) throw std::runtime_error("null argument");
-        score::LinearPattern L;
-        score::make_linear_pattern(*pattern, s, L);
-        score_handle* h = nullptr;
-        if (score_create_batch(&L.prob, 1, &L.st, &h) != 0) return -1;
-        auto& S = h->solver;
-        if ((int64_t)S.H.K0.size() != (int64_t)pattern->P_rowptr[pattern->n]) {
-            score_destroy(h);
-            throw std::runtime_error("score_linear_create: internal pattern differs from the given one");
-        }
-        S.linear_mode = true;
-        S.linear_nnz = (int64_t)S.H.K0.size();
-        *out = h;
-        return 0;
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
-}
-int score_linear_solve(score_handle* h, const double* values, const double* rhs, double* x, double rel_tol,
-                       int32_t max_iters, int32_t* iters_used, double* rel_residual) {
-    try {
-        if (!h) throw std::runtime_error("null handle");
-        DeviceGuard guard(h->solver.st.device);
-        int used = 0;
-        const int rc = h->solver.linear_solve(values, rhs, x, rel_tol, max_iters, &used, rel_residual);
-        if (iters_used) *iters_used = used;
-        return rc;
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
-}
-int score_time_kkt_apply(score_handle* h, int32_t reps, double* ms, double* bytes) {
-    try {
-        if (!h) throw std::runtime_error("null handle");
-        DeviceGuard guard(h->solver.st.device);
-        h->solver.be.time_kkt(reps, ms, bytes);
-        return 0;
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+    });
 }
 int score_time_iteration(score_handle* h, int32_t warmup, int32_t iters, double* us, int32_t with_events) {
-    try {
-        if (!h || !us) throw std::runtime_error("null argument");
-        DeviceGuard guard(h->solver.st.device);
+    return abi_call([&] {
+        require(h && us);
+        auto scope = handle_scope(h);
         // the driver's reset: iterates, penalties AND the PCG count an adaptive solve may have raised
         h->solver.reset();
-        h->solver.be.time_iteration(warmup, iters, us, with_events);
+        time_iteration(h->solver.be, warmup, iters, us, with_events);
         return 0;
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+    });
 }
 int score_debug_time(score_handle* h, const char* kernel, int32_t reps, double* ms) {
-    try {
-        if (!h || !kernel || !ms) throw std::runtime_error("null argument");
-        DeviceGuard guard(h->solver.st.device);
-        h->solver.be.time_kernel(kernel, reps, ms);
+    return abi_call([&] {
+        require(h && kernel && ms);
+        auto scope = handle_scope(h);
+        time_kernel(h->solver.be, kernel, reps, ms);
         return 0;
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
-}
-int64_t score_debug_get(score_handle* h, const char* name, double* out, int64_t len) {
-    if (!h || !name) return -1;
-    try {
-        DeviceGuard guard(h->solver.st.device);
-        return h->solver.be.get_vec(name, out, len);
-    } catch (const std::exception& e) { g_err = e.what(); return -2; }
+    });
 }
 void score_destroy(score_handle* h) {
     if (!h) return;
     try {
-        ActiveSolve active;
-        DeviceGuard guard(h->solver.st.device);
+        AbiEnv::Scope scope(h->solver.st.device, true);
         score::PhaseTimer pt(h->solver.st.verbose != 0);
         delete h;
         pt.mark("destroy: total");
@@ -4717,68 +4163,21 @@ void score_destroy(score_handle* h) {
         delete h;
     }
 }
-int score_assemble(const score_graph* g, score_assembled** out) {
-    try {
-        if (!g || !out) throw std::runtime_error("null argument");
-        auto* a = new score_assembled();
-        try {
-            score::assemble_graph(*g, a->qp);
-        } catch (...) {
-            delete a;
-            throw;
-        }
-        *out = a;
-        return 0;
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
-}
-int score_assemble_batch(const score_graph* graphs, int32_t count, score_assembled** out) {
-    try {
-        if (!graphs || !out || count <= 0) throw std::runtime_error("null argument");
-        std::vector<score_assembled*> made((size_t)count, nullptr);
-        std::vector<score::AssembledQP*> qps((size_t)count, nullptr);
-        try {
-            for (int i = 0; i < count; ++i) { made[(size_t)i] = new score_assembled(); qps[(size_t)i] = &made[(size_t)i]->qp; }
-            score::assemble_graphs(graphs, count, qps.data());
-        } catch (...) {
-            for (auto* a : made) delete a;
-            throw;
-        }
-        for (int i = 0; i < count; ++i) out[i] = made[(size_t)i];
-        return 0;
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
-}
-int score_assembled_view(const score_assembled* a, score_problem* view) {
-    if (!a || !view) { g_err = "null argument"; return -1; }
-    a->qp.view(view);
-    return 0;
-}
-void score_assembled_free(score_assembled* a) { delete a; }
 int score_refine_create(const score_graph* g, const score_settings* s, score_refine** out) {
-    try {
-        if (!g || !out) throw std::runtime_error("null argument");
-        score_settings st;
-        if (s) st = *s; else score::default_settings(&st);
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-            throw std::runtime_error("no HIP device available (the SCORE solver has no CPU fallback)");
-        if (st.device < 0 || st.device >= ndev) throw std::runtime_error("score_settings.device out of range");
-        DeviceGuard guard(st.device);  // the refinement's own buffers live on the handle's device too
-        auto* r = new score_refine();
-        try {
-            r->create(*g, s);
-        } catch (...) {
-            delete r;
-            throw;
-        }
-        *out = r;
+    return abi_call([&] {
+        require(g && out);
+        const score_settings st = resolve_settings(s);
+        AbiEnv::require_device(st.device);
+        AbiEnv::Scope scope(st.device, false);  // the refinement's own buffers live on the handle's device too
+        publish_new(out, [&](score_refine& r) { r.create(*g, s); });
         return 0;
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+    });
 }
 int score_refine_run(score_refine* r, const double* poses_in, const double* landmarks_in, int32_t max_iters, double tol,
                      double* poses_out, double* landmarks_out, score_refine_info* info) {
-    try {
-        if (!r || !poses_in || !poses_out || (r->P.Nl > 0 && (!landmarks_in || !landmarks_out))) throw std::runtime_error("null argument");
-        DeviceGuard guard(r->device);
+    return abi_call([&] {
+        require(r && poses_in && poses_out && (r->P.Nl == 0 || (landmarks_in && landmarks_out)));
+        AbiEnv::Scope scope(r->device, false);
         const double t0 = score::now_ms();
         score::GnInfo gi;
         r->run(poses_in, landmarks_in, max_iters, tol, poses_out, landmarks_out, gi);
@@ -4788,7 +4187,7 @@ int score_refine_run(score_refine* r, const double* poses_in, const double* land
             info->setup_ms = r->setup_ms; info->solve_ms = score::now_ms() - t0;
         }
         return 0;
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+    });
 }
 void score_refine_destroy(score_refine* r) {
     if (!r) return;
@@ -4800,18 +4199,6 @@ void score_refine_destroy(score_refine* r) {
 }
 }  // extern "C"
 
-// (the generated arrays stay in device memory for as long as the batch lives: score_create_from_generated builds handles
-//  from them without another transfer)
-struct score_generated {
-    score::GeneratedBatch B;
-    DevArena arena;
-    int device = -1;
-    const int32_t* d_rel_base = nullptr; const int32_t* d_rel_to = nullptr; const int32_t* d_ra = nullptr; const int32_t* d_rb = nullptr;
-    const double* d_rel_t = nullptr; const double* d_rel_R = nullptr; const double* d_rel_kappa = nullptr; const double* d_rel_tau = nullptr;
-    const double* d_dist = nullptr; const double* d_prec = nullptr;
-    // (nothing to wait for when the batch goes: score_create_from_generated returns with its handle's setup -- the only reader of
-    //  these arrays -- complete; the arena's blocks go back to the cache)
-};
 namespace {
 // The generator on the device: walks + beacons (one thread per robot / beacon), the ranges counted per (trial, group, time),
 // scanned, filled; the arrays come back through pinned staging (the host lays out the handles from them:
@@ -4820,9 +4207,7 @@ void generate_manhattan_device(const score::GenSpec& S, int count, int device, s
     using namespace score;
     GeneratedBatch& B = Gd.B;
     gen_check_spec(S, count);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) throw std::runtime_error("no HIP device available (the SCORE solver has no CPU fallback)");
-    if (device < 0 || device >= ndev) throw std::runtime_error("score_generate_manhattan: device out of range");
+    require_hip_device(device, "score_generate_manhattan: device out of range");
     DeviceGuard guard(device);
     B = GeneratedBatch();
     B.S = S; B.count = count;
@@ -4913,40 +4298,16 @@ void generate_manhattan_device(const score::GenSpec& S, int count, int device, s
 
 extern "C" {
 int score_generate_manhattan(const score_manhattan_spec* spec, int32_t count, int32_t device, score_generated** out) {
-    try {
-        if (!spec || !out) throw std::runtime_error("null argument");
-        score::GenSpec S{spec->n_robots, spec->n_poses, spec->n_beacons, spec->side, spec->p_range, spec->sigma_t, spec->sigma_theta, spec->sigma_range, spec->seed,
-                         spec->dim == 0 ? 2 : spec->dim};
-        auto* g = new score_generated();
-        try { generate_manhattan_device(S, count, device, *g); } catch (...) { delete g; throw; }
-        *out = g;
+    return abi_call([&] {
+        require(spec && out);
+        publish_new(out, [&](score_generated& g) { generate_manhattan_device(gen_spec(*spec), count, device, g); });
         return 0;
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+    });
 }
-int score_generated_graph(const score_generated* g, int32_t index, score_graph* view) {
-    try {
-        if (!g || !view) throw std::runtime_error("null argument");
-        g->B.view(index, view);
-        return 0;
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
-}
-int score_generated_truth(const score_generated* g, int32_t index, double* poses, double* beacons) {
-    try {
-        if (!g) throw std::runtime_error("null argument");
-        g->B.truth(index, poses, beacons);
-        return 0;
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
-}
-void score_generated_free(score_generated* g) { delete g; }
 int score_create_from_generated(const score_generated* g, int32_t first, int32_t count, int32_t relaxation, const score_settings* s, score_handle** out) {
-    try {
-        if (!g || !out) throw std::runtime_error("null argument");
-        if (first < 0 || count <= 0 || first + count > g->B.count) throw std::runtime_error("score_create_from_generated: worlds out of range");
-        if (relaxation != 0 && relaxation != 1) throw std::runtime_error("score_create_from_generated: relaxation must be 0 (SOCP) or 1 (QCQP)");
-        std::vector<score_graph> views((size_t)count);
-        for (int i = 0; i < count; ++i) { g->B.view(first + i, &views[(size_t)i]); views[(size_t)i].relaxation = relaxation; }
-        score_settings st;
-        if (s) st = *s; else score::default_settings(&st);
+    return abi_call([&] {
+        std::vector<score_graph> views = generated_views(g, first, count, relaxation, out);
+        const score_settings st = resolve_settings(s);
         HipBackend::GenSource src{};
         const bool resident = g->device >= 0 && st.device == g->device;
         if (resident) {  // the measurement arrays where the generator left them (world `first` onwards: the worlds follow each other)
@@ -4957,7 +4318,7 @@ int score_create_from_generated(const score_generated* g, int32_t first, int32_t
             src.rng_a = g->d_ra + ro; src.rng_b = g->d_rb + ro; src.rng_dist = g->d_dist + ro; src.rng_prec = g->d_prec + ro;
         }
         return score_create_from_graphs_impl(views.data(), count, &st, out, resident ? &src : nullptr);
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+    });
 }
 }  // extern "C"
 
@@ -4983,15 +4344,14 @@ void score_robust_default_settings(score_robust_settings* rs) {
 int score_robust_solve(const score_graph* graphs, int32_t count, const score_settings* s, const score_robust_settings* rs,
                        double* weights, double* residuals, double* poses, double* relaxed, double* landmarks, double* ranges,
                        int32_t* degenerate, score_info* infos, score_robust_info* rinfos) {
-    try {
+    return abi_call([&] {
         if (!graphs || !rs || count <= 0) throw std::runtime_error("score_robust_solve: null argument or count < 1");
         const double c = rs->inlier_threshold, step = rs->mu_step, mw = rs->min_weight;
         if (!(c > 0.0) || !std::isfinite(c)) throw std::runtime_error("score_robust_solve: inlier_threshold must be positive and finite");
         if (!(step > 1.0) || !std::isfinite(step)) throw std::runtime_error("score_robust_solve: mu_step must be finite and > 1");
         if (!(mw > 0.0 && mw <= 1.0)) throw std::runtime_error("score_robust_solve: min_weight must lie in (0, 1]");
         if (rs->max_outer < 1) throw std::runtime_error("score_robust_solve: max_outer must be >= 1");
-        score_settings st;
-        if (s) st = *s; else score::default_settings(&st);
+        const score_settings st = resolve_settings(s);
         const int d = graphs[0].dim;
         if (d != 2 && d != 3) throw std::runtime_error("score_robust_solve: dim must be 2 or 3");
         int qdirs = rs->qcqp_directions ? 1 : 0;
@@ -5014,9 +4374,7 @@ int score_robust_solve(const score_graph* graphs, int32_t count, const score_set
         }
         const int64_t n_rel = rel_off[(size_t)count], n_rng = rng_off[(size_t)count];
         if (n_rel >= ((int64_t)1 << 31) || n_rng >= ((int64_t)1 << 31)) throw std::runtime_error("score_robust_solve: too many measurements");
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) throw std::runtime_error("no HIP device available (the SCORE solver has no CPU fallback)");
-        if (st.device < 0 || st.device >= ndev) throw std::runtime_error("score_settings.device out of range");
+        AbiEnv::require_device(st.device);
         DeviceGuard guard(st.device);
         const double t0 = score::now_ms();
         const int rw = qdirs ? d : 1, D1 = d + 1;
@@ -5226,13 +4584,13 @@ int score_robust_solve(const score_graph* graphs, int32_t count, const score_set
         }
         if (rinfos) std::memcpy(rinfos, rec.data(), (size_t)count * sizeof(score_robust_info));
         return 0;
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+    });
 }
 }  // extern "C"
 
 extern "C" {
 int score_round_to_so(int32_t dim, int64_t n, const double* blocks, double* rotations, int32_t* degenerate, int32_t device) {
-    try {
+    return abi_call([&] {
         if (dim != 2 && dim != 3) throw std::runtime_error("score_round_to_so: dim must be 2 or 3");
         if (n < 0 || (n > 0 && (!blocks || !rotations || !degenerate))) throw std::runtime_error("score_round_to_so: null argument");
         if (n == 0) return 0;
@@ -5243,8 +4601,7 @@ int score_round_to_so(int32_t dim, int64_t n, const double* blocks, double* rota
         size_t cap = 2 * in_bytes + flag_bytes;
         char* stage = (char*)block_cache().take(cap, device, true);
         hipStream_t st = stream_pool().take(device);
-        int rc = 0;
-        try {
+        const int rc = abi_call([&] {
             std::memcpy(stage, blocks, in_bytes);
             char* dstage = nullptr;
             HIP_CHECK(hipHostGetDevicePointer((void**)&dstage, stage, 0));
@@ -5258,7 +4615,8 @@ int score_round_to_so(int32_t dim, int64_t n, const double* blocks, double* rota
             HIP_CHECK(sync_stream(st));
             std::memcpy(rotations, stage + in_bytes, in_bytes);
             std::memcpy(degenerate, stage + 2 * in_bytes, flag_bytes);
-        } catch (const std::exception& e) { g_err = e.what(); rc = -1; }
+            return 0;
+        });
         // After an error the kernel may still be running on the staging block: hand block and stream back only once
         // the stream has drained; if even that fails, drop them (a leak of one block beats a kernel writing into a
         // block another handle has been given).
@@ -5269,7 +4627,7 @@ int score_round_to_so(int32_t dim, int64_t n, const double* blocks, double* rota
             (void)hipGetLastError();
         }
         return rc;
-    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+    });
 }
 int64_t score_trim_caches(void) {
     const size_t freed = block_cache().trim();
@@ -5283,7 +4641,5 @@ int32_t score_host_counters(double* out, int32_t len) {
     if (out) for (int i = 0; i < len && i < 4; ++i) out[i] = v[i];
     return 4;
 }
-const char* score_last_error(void) { return g_err.c_str(); }
-int32_t score_abi_version(void) { return SCORE_ABI_VERSION * 1000 + (int32_t)sizeof(score_problem); }
 const char* score_backend(void) { return "hip-gfx950"; }
 }
