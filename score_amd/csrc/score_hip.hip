@@ -4323,10 +4323,11 @@ int score_create_from_generated(const score_generated* g, int32_t first, int32_t
 }  // extern "C"
 
 // ---------------------------------------------------------------------------
-// score_robust_solve (include/score_robust.h): GNC-TLS outer loop.  The graphs' measurement arrays go up once ("home" arrays,
+// score_robust_solve_rel (include/score_robust.h): GNC-TLS outer loop.  The graphs' measurement arrays go up once ("home" arrays,
 // graph after graph); every outer solve's handle is built from compact copies of the running members' arrays through the
-// generator's path (GenSource), its rng_prec the weighted precisions k_robust_weight wrote (score_robust.hpp).  The create
-// path's host fallback (the host assembler) reads rng_prec from the views: they point at a host mirror of the same values.
+// generator's path (GenSource), its rng_prec the weighted precisions k_robust_weight wrote and the rel_kappa / rel_tau of its
+// loop closures those k_robust_weight_rel wrote (score_robust.hpp).  The create path's host fallback (the host assembler) reads
+// the precisions from the views: they point at host mirrors of the same values.  score_robust_solve is the ranges' family alone.
 // ---------------------------------------------------------------------------
 namespace {
 struct RobustHandle {  // (an outer solve's handle goes whatever happens)
@@ -4344,8 +4345,20 @@ void score_robust_default_settings(score_robust_settings* rs) {
 int score_robust_solve(const score_graph* graphs, int32_t count, const score_settings* s, const score_robust_settings* rs,
                        double* weights, double* residuals, double* poses, double* relaxed, double* landmarks, double* ranges,
                        int32_t* degenerate, score_info* infos, score_robust_info* rinfos) {
+    return score_robust_solve_rel(graphs, count, s, rs, 1, 0.0, weights, residuals, nullptr, nullptr, poses, relaxed, landmarks, ranges,
+                                  degenerate, infos, rinfos);
+}
+
+int score_robust_solve_rel(const score_graph* graphs, int32_t count, const score_settings* s, const score_robust_settings* rs,
+                           int32_t families, double rel_threshold, double* weights, double* residuals, double* rel_weights,
+                           double* rel_residuals, double* poses, double* relaxed, double* landmarks, double* ranges,
+                           int32_t* degenerate, score_info* infos, score_robust_info* rinfos) {
     return abi_call([&] {
         if (!graphs || !rs || count <= 0) throw std::runtime_error("score_robust_solve: null argument or count < 1");
+        if (families < 1 || families > 3) throw std::runtime_error("score_robust_solve_rel: families must be 1 (ranges), 2 (loop closures) or 3 (both)");
+        const bool f_rng = (families & 1) != 0, f_rel = (families & 2) != 0;
+        const double c_rel = f_rel ? rel_threshold : 0.0;
+        if (f_rel && (!(c_rel > 0.0) || !std::isfinite(c_rel))) throw std::runtime_error("score_robust_solve_rel: rel_threshold must be positive and finite");
         const double c = rs->inlier_threshold, step = rs->mu_step, mw = rs->min_weight;
         if (!(c > 0.0) || !std::isfinite(c)) throw std::runtime_error("score_robust_solve: inlier_threshold must be positive and finite");
         if (!(step > 1.0) || !std::isfinite(step)) throw std::runtime_error("score_robust_solve: mu_step must be finite and > 1");
@@ -4356,6 +4369,7 @@ int score_robust_solve(const score_graph* graphs, int32_t count, const score_set
         if (d != 2 && d != 3) throw std::runtime_error("score_robust_solve: dim must be 2 or 3");
         int qdirs = rs->qcqp_directions ? 1 : 0;
         std::vector<int64_t> rel_off((size_t)count + 1, 0), rng_off((size_t)count + 1, 0), pose_off((size_t)count + 1, 0), lm_off((size_t)count + 1, 0);
+        std::vector<int64_t> lc_off((size_t)count + 1, 0);   // loop closures: the trailing n_rel - sum(chain_len - 1) relative-pose entries
         for (int p = 0; p < count; ++p) {
             const score_graph& g = graphs[p];
             if (g.dim != d) throw std::runtime_error("score_robust_solve: graphs of one dimension only");
@@ -4367,12 +4381,21 @@ int score_robust_solve(const score_graph* graphs, int32_t count, const score_set
                 if (!(g.rng_prec[r] > 0.0) || !std::isfinite(g.rng_prec[r]))
                     throw std::runtime_error("score_robust_solve: graph " + std::to_string(p) + ": range " + std::to_string(r) +
                                              " has a precision that is not positive and finite");
+            const int64_t n_lc = f_rel ? (int64_t)g.n_rel - (Np - g.n_chains) : 0;
+            if (n_lc < 0) throw std::runtime_error("score_robust_solve_rel: graph " + std::to_string(p) + " has fewer relative-pose entries than odometry steps");
+            for (int64_t e = 0; e < n_lc; ++e) {
+                const double ka = g.rel_kappa[g.n_rel - n_lc + e], ta = g.rel_tau[g.n_rel - n_lc + e];
+                if (!(ka > 0.0) || !std::isfinite(ka) || !(ta > 0.0) || !std::isfinite(ta))
+                    throw std::runtime_error("score_robust_solve_rel: graph " + std::to_string(p) + ": loop closure " + std::to_string(e) +
+                                             " has a precision that is not positive and finite");
+            }
+            lc_off[(size_t)p + 1] = lc_off[(size_t)p] + n_lc;
             rel_off[(size_t)p + 1] = rel_off[(size_t)p] + g.n_rel;
             rng_off[(size_t)p + 1] = rng_off[(size_t)p] + g.n_rng;
             pose_off[(size_t)p + 1] = pose_off[(size_t)p] + Np;
             lm_off[(size_t)p + 1] = lm_off[(size_t)p] + g.n_landmarks;
         }
-        const int64_t n_rel = rel_off[(size_t)count], n_rng = rng_off[(size_t)count];
+        const int64_t n_rel = rel_off[(size_t)count], n_rng = rng_off[(size_t)count], n_lc = lc_off[(size_t)count];
         if (n_rel >= ((int64_t)1 << 31) || n_rng >= ((int64_t)1 << 31)) throw std::runtime_error("score_robust_solve: too many measurements");
         AbiEnv::require_device(st.device);
         DeviceGuard guard(st.device);
@@ -4391,6 +4414,7 @@ int score_robust_solve(const score_graph* graphs, int32_t count, const score_set
         const size_t o_rel_kappa = region(n_rel * f8), o_rel_tau = region(n_rel * f8);
         const size_t o_rng_a = region(n_rng * i4), o_rng_b = region(n_rng * i4), o_rng_dist = region(n_rng * f8), o_prec = region(n_rng * f8);
         const size_t o_w = region(n_rng * f8), o_mu_in = region(count * f8), o_hrel = region((count + 1) * i4), o_hrng = region((count + 1) * i4);
+        const size_t o_w_rel = f_rel ? region(n_lc * f8) : 0, o_hlc = f_rel ? region((count + 1) * i4) : 0;
         const size_t home_bytes = off;
         std::vector<char> hp(home_bytes, 0);
         for (int p = 0; p < count; ++p) {
@@ -4407,7 +4431,9 @@ int score_robust_solve(const score_graph* graphs, int32_t count, const score_set
         for (int p = 0; p <= count; ++p) {
             ((int32_t*)(hp.data() + o_hrel))[p] = (int32_t)rel_off[(size_t)p];
             ((int32_t*)(hp.data() + o_hrng))[p] = (int32_t)rng_off[(size_t)p];
+            if (f_rel) ((int32_t*)(hp.data() + o_hlc))[p] = (int32_t)lc_off[(size_t)p];
         }
+        if (f_rel) std::fill((double*)(hp.data() + o_w_rel), (double*)(hp.data() + o_w_rel) + n_lc, 1.0);
         char* home = (char*)ar.take(home_bytes);
         staged_h2d(home, hp.data(), home_bytes, rsm);
         hp.clear(); hp.shrink_to_fit();
@@ -4418,11 +4444,14 @@ int score_robust_solve(const score_graph* graphs, int32_t count, const score_set
         char* work = (char*)ar.take(off);
         off = 0;
         const size_t r_wn = region(n_rng * f8), r_pn = region(n_rng * f8), r_res = region(n_rng * f8), r_mu = region(count * f8);
-        const size_t r_ctl = region(count * sizeof(RobustCtl));
+        const size_t r_ctl = region(count * sizeof(RobustCtl) * (f_rel ? 2 : 1));   // the ranges' records, then the loop closures'
+        const size_t r_wn_rel = f_rel ? region(n_lc * f8) : 0, r_kn = f_rel ? region(n_lc * f8) : 0, r_tn = f_rel ? region(n_lc * f8) : 0;
+        const size_t r_res_rel = f_rel ? region(n_lc * f8) : 0;
         const size_t out_bytes = off;
         char* outd = (char*)ar.take(out_bytes);
         off = 0;
         const size_t t_mem = region(count * i4), t_rel = region((count + 1) * i4), t_rng = region((count + 1) * i4);
+        const size_t t_lc = f_rel ? region((count + 1) * i4) : 0;
         const size_t tab_bytes = off;
         char* tab = (char*)ar.take(tab_bytes);
         EstProb* d_probs = (EstProb*)ar.take(count * sizeof(EstProb));
@@ -4437,6 +4466,15 @@ int score_robust_solve(const score_graph* graphs, int32_t count, const score_set
         std::vector<double> w_host((size_t)n_rng, 1.0), prec_host((size_t)n_rng);
         for (int p = 0; p < count; ++p)
             if (graphs[p].n_rng) std::memcpy(prec_host.data() + rng_off[(size_t)p], graphs[p].rng_prec, (size_t)graphs[p].n_rng * f8);
+        std::vector<double> w_rel_host((size_t)n_lc, 1.0), kappa_host, tau_host;   // (the mirrors: whole relative-pose arrays)
+        if (f_rel) {
+            kappa_host.resize((size_t)n_rel); tau_host.resize((size_t)n_rel);
+            for (int p = 0; p < count; ++p)
+                if (graphs[p].n_rel) {
+                    std::memcpy(kappa_host.data() + rel_off[(size_t)p], graphs[p].rel_kappa, (size_t)graphs[p].n_rel * f8);
+                    std::memcpy(tau_host.data() + rel_off[(size_t)p], graphs[p].rel_tau, (size_t)graphs[p].n_rel * f8);
+                }
+        }
         std::vector<double> mu_host((size_t)count, 0.0);
         std::vector<score_robust_info> rec((size_t)count);
         std::memset(rec.data(), 0, rec.size() * sizeof(score_robust_info));
@@ -4447,7 +4485,7 @@ int score_robust_solve(const score_graph* graphs, int32_t count, const score_set
             const int na = (int)active.size();
             std::vector<score_graph> views((size_t)na);
             std::vector<int32_t> tb(tab_bytes / i4, 0);
-            int64_t nrel_c = 0, nrng_c = 0;
+            int64_t nrel_c = 0, nrng_c = 0, nlc_c = 0;
             for (int j = 0; j < na; ++j) {
                 const int m = active[(size_t)j];
                 views[(size_t)j] = graphs[m];
@@ -4456,8 +4494,15 @@ int score_robust_solve(const score_graph* graphs, int32_t count, const score_set
                 tb[t_mem / i4 + j] = m;
                 tb[t_rel / i4 + j] = (int32_t)nrel_c; tb[t_rng / i4 + j] = (int32_t)nrng_c;
                 nrel_c += graphs[m].n_rel; nrng_c += graphs[m].n_rng;
+                if (f_rel) {
+                    views[(size_t)j].rel_kappa = kappa_host.data() + rel_off[(size_t)m];
+                    views[(size_t)j].rel_tau = tau_host.data() + rel_off[(size_t)m];
+                    tb[t_lc / i4 + j] = (int32_t)nlc_c;
+                    nlc_c += lc_off[(size_t)m + 1] - lc_off[(size_t)m];
+                }
             }
             tb[t_rel / i4 + na] = (int32_t)nrel_c; tb[t_rng / i4 + na] = (int32_t)nrng_c;
+            if (f_rel) tb[t_lc / i4 + na] = (int32_t)nlc_c;
             if (changed) {  // the running members' arrays, compacted (k == 1: all of them, the measured precisions)
                 staged_h2d(tab, tb.data(), tab_bytes, rsm);
                 RobustGatherArgs ga{};
@@ -4468,7 +4513,8 @@ int score_robust_solve(const score_graph* graphs, int32_t count, const score_set
                 ga.h_rel_base = HI(home, o_rel_base); ga.h_rel_to = HI(home, o_rel_to); ga.h_rel_t = HD(home, o_rel_t); ga.h_rel_R = HD(home, o_rel_R);
                 ga.h_rel_kappa = HD(home, o_rel_kappa); ga.h_rel_tau = HD(home, o_rel_tau);
                 ga.h_rng_a = HI(home, o_rng_a); ga.h_rng_b = HI(home, o_rng_b); ga.h_rng_dist = HD(home, o_rng_dist);
-                ga.h_prec = k == 1 ? HD(home, o_prec) : HD(outd, r_pn);
+                ga.h_prec = k == 1 || !f_rng ? HD(home, o_prec) : HD(outd, r_pn);
+                if (f_rel && k > 1) { ga.home_lc_off = HI(home, o_hlc); ga.h_kappa_next = HD(outd, r_kn); ga.h_tau_next = HD(outd, r_tn); }
                 ga.rel_base = HI(work, c_rel_base); ga.rel_to = HI(work, c_rel_to); ga.rel_t = HD(work, c_rel_t); ga.rel_R = HD(work, c_rel_R);
                 ga.rel_kappa = HD(work, c_rel_kappa); ga.rel_tau = HD(work, c_rel_tau);
                 ga.rng_a = HI(work, c_rng_a); ga.rng_b = HI(work, c_rng_b); ga.rng_dist = HD(work, c_rng_dist); ga.prec = HD(work, c_prec);
@@ -4499,7 +4545,9 @@ int score_robust_solve(const score_graph* graphs, int32_t count, const score_set
                 staged_h2d(d_D, S.H.D.data(), need * f8, hs);
                 Dp = d_D;
             }
-            HIP_CHECK(hipMemsetAsync(outd + r_ctl, 0, (size_t)count * sizeof(RobustCtl), hs));
+            HIP_CHECK(hipMemsetAsync(outd + r_ctl, 0, (size_t)count * sizeof(RobustCtl) * (f_rel ? 2 : 1), hs));
+            RobustCtl* ctl_rng = (RobustCtl*)(outd + r_ctl);
+            RobustCtl* ctl_rel = f_rel ? ctl_rng + count : nullptr;
             RobustArgs a{};
             a.d = d; a.count = na; a.first = k == 1 ? 1 : 0;
             a.probs = d_probs; a.rng_off = HI(tab, t_rng); a.member = HI(tab, t_mem); a.home_rng_off = HI(home, o_hrng);
@@ -4508,37 +4556,65 @@ int score_robust_solve(const score_graph* graphs, int32_t count, const score_set
             a.rng_a = HI(work, c_rng_a); a.rng_b = HI(work, c_rng_b); a.rng_dist = HD(work, c_rng_dist);
             a.prec = HD(home, o_prec); a.w = HD(home, o_w); a.resid = HD(outd, r_res);
             a.w_next = HD(outd, r_wn); a.prec_next = HD(outd, r_pn); a.prec_work = HD(work, c_prec);
-            a.ctl = (RobustCtl*)(outd + r_ctl); a.mu_in = HD(home, o_mu_in); a.mu_out = HD(outd, r_mu);
-            a.c = c; a.mu_step = step; a.min_weight = mw;
-            if (nrng_c > 0) {
-                const dim3 grid((unsigned)((nrng_c + 255) / 256));
-                hipLaunchKernelGGL(k_robust_resid, grid, dim3(256), 0, hs, a);
-                hipLaunchKernelGGL(k_robust_weight, grid, dim3(256), 0, hs, a);
+            a.ctl = ctl_rng; a.ctl_other = ctl_rel; a.mu_in = HD(home, o_mu_in); a.mu_out = HD(outd, r_mu);
+            a.c = c; a.c_other = c_rel; a.mu_step = step; a.min_weight = mw;
+            RobustRelArgs b{};
+            if (f_rel) {
+                b.d = d; b.count = na; b.first = a.first;
+                b.probs = d_probs; b.lc_off = HI(tab, t_lc); b.rel_off = HI(tab, t_rel); b.member = HI(tab, t_mem);
+                b.home_lc_off = HI(home, o_hlc); b.home_rel_off = HI(home, o_hrel);
+                b.n_lc = nlc_c;
+                b.x = a.x; b.D = Dp;
+                b.rel_base = HI(work, c_rel_base); b.rel_to = HI(work, c_rel_to); b.rel_t = HD(work, c_rel_t); b.rel_R = HD(work, c_rel_R);
+                b.kappa = HD(home, o_rel_kappa); b.tau = HD(home, o_rel_tau); b.w = HD(home, o_w_rel); b.resid = HD(outd, r_res_rel);
+                b.w_next = HD(outd, r_wn_rel); b.kappa_next = HD(outd, r_kn); b.tau_next = HD(outd, r_tn);
+                b.kappa_work = HD(work, c_rel_kappa); b.tau_work = HD(work, c_rel_tau);
+                b.ctl = ctl_rel; b.ctl_other = f_rng ? ctl_rng : nullptr; b.mu_in = a.mu_in; b.mu_out = a.mu_out;
+                b.c = c_rel; b.c_other = c; b.mu_step = step; b.min_weight = mw;
             }
+            // (both families' residuals before either family's weights: the first mu needs both maxima)
+            const dim3 grid((unsigned)((nrng_c + 255) / 256)), grid_rel((unsigned)((nlc_c + 255) / 256));
+            const bool run_rel = f_rel && nlc_c > 0;   // (the ranges' residuals are reported also where only the loop closures are re-weighted)
+            if (nrng_c > 0) hipLaunchKernelGGL(k_robust_resid, grid, dim3(256), 0, hs, a);
+            if (run_rel) hipLaunchKernelGGL(k_robust_resid_rel, grid_rel, dim3(256), 0, hs, b);
+            if (f_rng && nrng_c > 0) hipLaunchKernelGGL(k_robust_weight, grid, dim3(256), 0, hs, a);
+            if (run_rel) hipLaunchKernelGGL(k_robust_weight_rel, grid_rel, dim3(256), 0, hs, b);
             HIP_CHECK(hipGetLastError());
             HIP_CHECK(hipMemcpyAsync(outh, outd, out_bytes, hipMemcpyDeviceToHost, hs));
             HIP_CHECK(sync_stream(hs));
             const double* Wn = HD(outh, r_wn); const double* Pn = HD(outh, r_pn); const double* Rs = HD(outh, r_res); const double* Mu = HD(outh, r_mu);
             const RobustCtl* Cl = (const RobustCtl*)(outh + r_ctl);
+            const RobustCtl* Cr = Cl + count;   // (read with f_rel only)
+            const double* Wr = HD(outh, r_wn_rel); const double* Kn = HD(outh, r_kn); const double* Tn = HD(outh, r_tn); const double* Rr = HD(outh, r_res_rel);
             // ---- who stops ----
             std::vector<int> next, stop_j;
             for (int j = 0; j < na; ++j) {
                 const int m = active[(size_t)j];
-                double r2max;
-                std::memcpy(&r2max, &Cl[m].r2max, sizeof(double));
+                double r2max = 0.0, r2max_rel = 0.0;
+                if (f_rng) std::memcpy(&r2max, &Cl[m].r2max, sizeof(double));
+                if (f_rel) std::memcpy(&r2max_rel, &Cr[m].r2max, sizeof(double));
                 const int64_t r0 = rng_off[(size_t)m], nr = rng_off[(size_t)m + 1] - r0;
+                const int64_t l0 = lc_off[(size_t)m], nl = lc_off[(size_t)m + 1] - l0;
+                const bool out_rng = f_rng && nr > 0 && 2.0 * r2max > c * c, out_rel = f_rel && nl > 0 && 2.0 * r2max_rel > c_rel * c_rel;
+                const int32_t nonbinary = (f_rng ? Cl[m].nonbinary : 0) + (f_rel ? Cr[m].nonbinary : 0);
                 score_robust_info& R = rec[(size_t)m];
                 R.setup_ms += inf[(size_t)j].setup_ms; R.solve_ms += inf[(size_t)j].solve_ms;
                 bool stop = false, conv = false;
-                if (!std::isfinite(r2max)) stop = true;                                          // (a solve gone non-finite)
-                else if (k == 1 && (nr == 0 || 2.0 * r2max <= c * c)) stop = conv = true;          // no outliers at all
-                else if (k > 1 && Cl[m].nonbinary == 0) stop = conv = true;                      // solved on binary weights
+                if (!std::isfinite(r2max) || !std::isfinite(r2max_rel)) stop = true;             // (a solve gone non-finite)
+                else if (k == 1 && !out_rng && !out_rel) stop = conv = true;                     // no outliers at all
+                else if (k > 1 && nonbinary == 0) stop = conv = true;                            // solved on binary weights
                 else if (k >= rs->max_outer) stop = true;
                 if (!stop) {
                     next.push_back(m);
-                    if (nr) {
+                    if (f_rng && nr) {
                         std::memcpy(w_host.data() + r0, Wn + r0, (size_t)nr * f8);
                         std::memcpy(prec_host.data() + r0, Pn + r0, (size_t)nr * f8);
+                    }
+                    if (nl) {
+                        const size_t e0 = (size_t)(rel_off[(size_t)m + 1] - nl);   // the member's loop closures in the mirrors
+                        std::memcpy(w_rel_host.data() + l0, Wr + l0, (size_t)nl * f8);
+                        std::memcpy(kappa_host.data() + e0, Kn + l0, (size_t)nl * f8);
+                        std::memcpy(tau_host.data() + e0, Tn + l0, (size_t)nl * f8);
                     }
                     mu_host[(size_t)m] = Mu[m];
                     continue;
@@ -4547,9 +4623,13 @@ int score_robust_solve(const score_graph* graphs, int32_t count, const score_set
                 R.outer_iterations = k; R.converged = conv ? 1 : 0; R.mu = mu_host[(size_t)m];
                 R.outliers = 0;
                 for (int64_t r = 0; r < nr; ++r) R.outliers += w_host[(size_t)(r0 + r)] < 0.5 ? 1 : 0;
+                R.rel_outliers = 0;
+                for (int64_t e = 0; e < nl; ++e) R.rel_outliers += w_rel_host[(size_t)(l0 + e)] < 0.5 ? 1 : 0;
                 R.total_ms = score::now_ms() - t0;
                 if (weights && nr) std::memcpy(weights + r0, w_host.data() + r0, (size_t)nr * f8);
                 if (residuals && nr) std::memcpy(residuals + r0, Rs + r0, (size_t)nr * f8);
+                if (rel_weights && nl) std::memcpy(rel_weights + l0, w_rel_host.data() + l0, (size_t)nl * f8);
+                if (rel_residuals && nl) std::memcpy(rel_residuals + l0, Rr + l0, (size_t)nl * f8);
                 if (infos) infos[m] = inf[(size_t)j];
             }
             // ---- the estimates of the members that stopped ----
@@ -4575,7 +4655,8 @@ int score_robust_solve(const score_graph* graphs, int32_t count, const score_set
             }
             // ---- the next solve's weights and mu on the device (members that stopped are not read again) ----
             if (!next.empty()) {
-                if (n_rng) HIP_CHECK(hipMemcpyAsync(HD(home, o_w), HD(outd, r_wn), (size_t)n_rng * f8, hipMemcpyDeviceToDevice, hs));
+                if (f_rng && n_rng) HIP_CHECK(hipMemcpyAsync(HD(home, o_w), HD(outd, r_wn), (size_t)n_rng * f8, hipMemcpyDeviceToDevice, hs));
+                if (n_lc) HIP_CHECK(hipMemcpyAsync(HD(home, o_w_rel), HD(outd, r_wn_rel), (size_t)n_lc * f8, hipMemcpyDeviceToDevice, hs));
                 HIP_CHECK(hipMemcpyAsync(HD(home, o_mu_in), HD(outd, r_mu), (size_t)count * f8, hipMemcpyDeviceToDevice, hs));
                 HIP_CHECK(sync_stream(hs));
             }

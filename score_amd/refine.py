@@ -51,14 +51,34 @@ def _weighted_ranges(a: dict, range_weights) -> dict:
     return out
 
 
+def _weighted_loop_closures(a: dict, loop_closure_weights) -> dict:
+    """The graph's arrays with kappa and tau of every loop closure (the trailing relative-pose entries) scaled by its weight
+    (``loop_closure_weights``: one per loop closure, in the order of ``data.loop_closure_measurements`` -- what
+    ``solve_score_robust`` returns in ``info["robust"]["loop_closure_weights"]``); None: as they are."""
+    if loop_closure_weights is None:
+        return a
+    n_lc = int(len(a["rel_base"]) - int(np.sum(np.asarray(a["chain_len"], dtype=np.int64) - 1)))
+    w = np.asarray(loop_closure_weights, dtype=np.float64)
+    if w.shape != (n_lc,):
+        raise ValueError(f"loop_closure_weights: {n_lc} weights expected (one per loop closure), got shape {w.shape}")
+    if not (np.all(np.isfinite(w)) and np.all(w >= 0)):
+        raise ValueError("loop_closure_weights must be finite and non-negative")
+    out = dict(a)
+    for key in ("rel_kappa", "rel_tau"):
+        v = np.array(a[key], dtype=np.float64)
+        v[len(v) - n_lc:] *= w
+        out[key] = v
+    return out
+
+
 class _Problem:
     """Residuals and sparse Jacobian of the 2-D RA-SLAM least-squares problem in the minimal
     parametrisation u = [theta_1.., x_1, y_1.. | landmarks]; pose 0 (first pose of chain 0) is fixed."""
 
-    def __init__(self, data, range_weights=None):
+    def __init__(self, data, range_weights=None, loop_closure_weights=None):
         if data.dimension != 2:
             raise ValueError("refine_estimate: 2-D graphs only")
-        a = _weighted_ranges(graph_arrays(data), range_weights)
+        a = _weighted_loop_closures(_weighted_ranges(graph_arrays(data), range_weights), loop_closure_weights)
         self.a = a
         self.Np, self.Nl = len(a["pose_names"]), len(a["landmark_names"])
         self.n = 3 * (self.Np - 1) + 2 * self.Nl
@@ -206,10 +226,10 @@ class _Problem3D:
     tangent space, (omega, v) per free pose and a 3-vector per landmark, applied by the retraction
     R <- R Exp(omega), t <- t + v.  Columns of pose p >= 1: 6 (p - 1) .. +5 = [omega | v]; pose 0 is fixed."""
 
-    def __init__(self, data, range_weights=None):
+    def __init__(self, data, range_weights=None, loop_closure_weights=None):
         if data.dimension != 3:
             raise ValueError("_Problem3D: 3-D graphs only")
-        a = _weighted_ranges(graph_arrays(data), range_weights)
+        a = _weighted_loop_closures(_weighted_ranges(graph_arrays(data), range_weights), loop_closure_weights)
         self.a = a
         self.Np, self.Nl = len(a["pose_names"]), len(a["landmark_names"])
         self.n = 6 * (self.Np - 1) + 3 * self.Nl
@@ -430,21 +450,24 @@ def _refine_native(prob: _Problem, u0: np.ndarray, max_iters: int, tol: float, l
 
 def refine_estimate(data, results, max_iters: int = 50, tol: float = 1e-10, verbose: bool = False,
                     linear_solver: str = "device", lib_path: Optional[str] = None, solver_settings: Optional[dict] = None,
-                    pcg_rel_tol: float = 1e-9, engine: str = "native", range_weights=None):
+                    pcg_rel_tol: float = 1e-9, engine: str = "native", range_weights=None,
+                    loop_closure_weights=None):
     """Refine a SCORE estimate (``SolverResults``) to a local minimiser of the RA-SLAM maximum-likelihood
     cost.  Returns ``(refined SolverResults, info)``; ``info`` holds the cost before / after, iterations,
     the final gradient norm and (device path) the PCG iterations spent in the linear solves.
     ``range_weights`` (one per range, in the graph's range order): the range precisions are scaled by them -- the weights of
-    ``solve_score_robust`` (``info["robust"]["weights"]``) keep the ranges it flagged out of the maximum-likelihood step."""
+    ``solve_score_robust`` (``info["robust"]["weights"]``) keep the ranges it flagged out of the maximum-likelihood step.
+    ``loop_closure_weights`` (one per loop closure, in the order of ``data.loop_closure_measurements``) scale kappa and tau of
+    the loop closures in the same way (``info["robust"]["loop_closure_weights"]``)."""
     if linear_solver not in ("device", "scipy"):
         raise ValueError("linear_solver must be 'device' or 'scipy'")
     if engine not in ("native", "python"):
         raise ValueError("engine must be 'native' or 'python'")
     if data.dimension == 3:
-        prob = _Problem3D(data, range_weights)
+        prob = _Problem3D(data, range_weights, loop_closure_weights)
         u = prob.initial_state(results)
     else:
-        prob = _Problem(data, range_weights)
+        prob = _Problem(data, range_weights, loop_closure_weights)
         u = _initial_point(prob, results)
     if engine == "native" and linear_solver == "device" and prob.n > 0:
         u, ni = _refine_native(prob, u, max_iters, tol, lib_path, solver_settings)
