@@ -4294,6 +4294,8 @@ void generate_manhattan_device(const score::GenSpec& S, int count, int device, s
     }
     stream_pool().give(device, st);
 }
+// (the GNC-TLS outer loop of score_robust_solve_rel: it needs score_create_from_graphs_impl, GenSource and the abi frame)
+#include "score_robust_driver.hpp"
 }  // namespace
 
 extern "C" {
@@ -4323,18 +4325,10 @@ int score_create_from_generated(const score_generated* g, int32_t first, int32_t
 }  // extern "C"
 
 // ---------------------------------------------------------------------------
-// score_robust_solve_rel (include/score_robust.h): GNC-TLS outer loop.  The graphs' measurement arrays go up once ("home" arrays,
-// graph after graph); every outer solve's handle is built from compact copies of the running members' arrays through the
-// generator's path (GenSource), its rng_prec the weighted precisions k_robust_weight wrote and the rel_kappa / rel_tau of its
-// loop closures those k_robust_weight_rel wrote (score_robust.hpp).  The create path's host fallback (the host assembler) reads
-// the precisions from the views: they point at host mirrors of the same values.  score_robust_solve is the ranges' family alone.
+// score_robust_solve_rel (include/score_robust.h): the GNC-TLS outer loop is score_robust_driver.hpp, included above where
+// score_create_from_graphs_impl is complete (its kernels: score_robust.hpp).
+// score_robust_solve is the ranges' family alone.
 // ---------------------------------------------------------------------------
-namespace {
-struct RobustHandle {  // (an outer solve's handle goes whatever happens)
-    score_handle* h = nullptr;
-    ~RobustHandle() { if (h) score_destroy(h); }
-};
-}  // namespace
 
 extern "C" {
 void score_robust_default_settings(score_robust_settings* rs) {
@@ -4354,317 +4348,11 @@ int score_robust_solve_rel(const score_graph* graphs, int32_t count, const score
                            double* rel_residuals, double* poses, double* relaxed, double* landmarks, double* ranges,
                            int32_t* degenerate, score_info* infos, score_robust_info* rinfos) {
     return abi_call([&] {
-        if (!graphs || !rs || count <= 0) throw std::runtime_error("score_robust_solve: null argument or count < 1");
-        if (families < 1 || families > 3) throw std::runtime_error("score_robust_solve_rel: families must be 1 (ranges), 2 (loop closures) or 3 (both)");
-        const bool f_rng = (families & 1) != 0, f_rel = (families & 2) != 0;
-        const double c_rel = f_rel ? rel_threshold : 0.0;
-        if (f_rel && (!(c_rel > 0.0) || !std::isfinite(c_rel))) throw std::runtime_error("score_robust_solve_rel: rel_threshold must be positive and finite");
-        const double c = rs->inlier_threshold, step = rs->mu_step, mw = rs->min_weight;
-        if (!(c > 0.0) || !std::isfinite(c)) throw std::runtime_error("score_robust_solve: inlier_threshold must be positive and finite");
-        if (!(step > 1.0) || !std::isfinite(step)) throw std::runtime_error("score_robust_solve: mu_step must be finite and > 1");
-        if (!(mw > 0.0 && mw <= 1.0)) throw std::runtime_error("score_robust_solve: min_weight must lie in (0, 1]");
-        if (rs->max_outer < 1) throw std::runtime_error("score_robust_solve: max_outer must be >= 1");
-        const score_settings st = resolve_settings(s);
-        const int d = graphs[0].dim;
-        if (d != 2 && d != 3) throw std::runtime_error("score_robust_solve: dim must be 2 or 3");
-        int qdirs = rs->qcqp_directions ? 1 : 0;
-        std::vector<int64_t> rel_off((size_t)count + 1, 0), rng_off((size_t)count + 1, 0), pose_off((size_t)count + 1, 0), lm_off((size_t)count + 1, 0);
-        std::vector<int64_t> lc_off((size_t)count + 1, 0);   // loop closures: the trailing n_rel - sum(chain_len - 1) relative-pose entries
-        for (int p = 0; p < count; ++p) {
-            const score_graph& g = graphs[p];
-            if (g.dim != d) throw std::runtime_error("score_robust_solve: graphs of one dimension only");
-            if (g.relaxation == 1) qdirs = 1;
-            else if (g.relaxation != 0) throw std::runtime_error("score_robust_solve: relaxation must be 0 (SOCP) or 1 (QCQP)");
-            int64_t Np = 0;
-            for (int ch = 0; ch < g.n_chains; ++ch) Np += g.chain_len[ch];
-            for (int64_t r = 0; r < g.n_rng; ++r)
-                if (!(g.rng_prec[r] > 0.0) || !std::isfinite(g.rng_prec[r]))
-                    throw std::runtime_error("score_robust_solve: graph " + std::to_string(p) + ": range " + std::to_string(r) +
-                                             " has a precision that is not positive and finite");
-            const int64_t n_lc = f_rel ? (int64_t)g.n_rel - (Np - g.n_chains) : 0;
-            if (n_lc < 0) throw std::runtime_error("score_robust_solve_rel: graph " + std::to_string(p) + " has fewer relative-pose entries than odometry steps");
-            for (int64_t e = 0; e < n_lc; ++e) {
-                const double ka = g.rel_kappa[g.n_rel - n_lc + e], ta = g.rel_tau[g.n_rel - n_lc + e];
-                if (!(ka > 0.0) || !std::isfinite(ka) || !(ta > 0.0) || !std::isfinite(ta))
-                    throw std::runtime_error("score_robust_solve_rel: graph " + std::to_string(p) + ": loop closure " + std::to_string(e) +
-                                             " has a precision that is not positive and finite");
-            }
-            lc_off[(size_t)p + 1] = lc_off[(size_t)p] + n_lc;
-            rel_off[(size_t)p + 1] = rel_off[(size_t)p] + g.n_rel;
-            rng_off[(size_t)p + 1] = rng_off[(size_t)p] + g.n_rng;
-            pose_off[(size_t)p + 1] = pose_off[(size_t)p] + Np;
-            lm_off[(size_t)p + 1] = lm_off[(size_t)p] + g.n_landmarks;
-        }
-        const int64_t n_rel = rel_off[(size_t)count], n_rng = rng_off[(size_t)count], n_lc = lc_off[(size_t)count];
-        if (n_rel >= ((int64_t)1 << 31) || n_rng >= ((int64_t)1 << 31)) throw std::runtime_error("score_robust_solve: too many measurements");
-        AbiEnv::require_device(st.device);
-        DeviceGuard guard(st.device);
-        const double t0 = score::now_ms();
-        const int rw = qdirs ? d : 1, D1 = d + 1;
-        const size_t i4 = sizeof(int32_t), f8 = sizeof(double);
-        // ---- device memory: home arrays (up once), compact work arrays, the read-back block, per-iteration tables ----
-        DevArena ar;
-        ar.dev = st.device;
-        hipStream_t rsm = stream_pool().take(st.device);
-        struct StreamBack { int dev; hipStream_t s; ~StreamBack() { (void)sync_stream(s); stream_pool().give(dev, s); } } sback{st.device, rsm};
-        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        size_t off = 0;
-        auto region = [&](size_t bytes) { const size_t o = off; off += al(std::max<size_t>(bytes, 8)); return o; };
-        const size_t o_rel_base = region(n_rel * i4), o_rel_to = region(n_rel * i4), o_rel_t = region(n_rel * d * f8), o_rel_R = region(n_rel * d * d * f8);
-        const size_t o_rel_kappa = region(n_rel * f8), o_rel_tau = region(n_rel * f8);
-        const size_t o_rng_a = region(n_rng * i4), o_rng_b = region(n_rng * i4), o_rng_dist = region(n_rng * f8), o_prec = region(n_rng * f8);
-        const size_t o_w = region(n_rng * f8), o_mu_in = region(count * f8), o_hrel = region((count + 1) * i4), o_hrng = region((count + 1) * i4);
-        const size_t o_w_rel = f_rel ? region(n_lc * f8) : 0, o_hlc = f_rel ? region((count + 1) * i4) : 0;
-        const size_t home_bytes = off;
-        std::vector<char> hp(home_bytes, 0);
-        for (int p = 0; p < count; ++p) {
-            const score_graph& g = graphs[p];
-            const size_t eo = (size_t)rel_off[(size_t)p], ro = (size_t)rng_off[(size_t)p];
-            auto cp = [&](size_t o, const void* src, size_t bytes) { if (bytes) std::memcpy(hp.data() + o, src, bytes); };
-            cp(o_rel_base + eo * i4, g.rel_base, g.n_rel * i4); cp(o_rel_to + eo * i4, g.rel_to, g.n_rel * i4);
-            cp(o_rel_t + eo * d * f8, g.rel_t, g.n_rel * d * f8); cp(o_rel_R + eo * d * d * f8, g.rel_R, g.n_rel * d * d * f8);
-            cp(o_rel_kappa + eo * f8, g.rel_kappa, g.n_rel * f8); cp(o_rel_tau + eo * f8, g.rel_tau, g.n_rel * f8);
-            cp(o_rng_a + ro * i4, g.rng_a, g.n_rng * i4); cp(o_rng_b + ro * i4, g.rng_b, g.n_rng * i4);
-            cp(o_rng_dist + ro * f8, g.rng_dist, g.n_rng * f8); cp(o_prec + ro * f8, g.rng_prec, g.n_rng * f8);
-        }
-        std::fill((double*)(hp.data() + o_w), (double*)(hp.data() + o_w) + n_rng, 1.0);
-        for (int p = 0; p <= count; ++p) {
-            ((int32_t*)(hp.data() + o_hrel))[p] = (int32_t)rel_off[(size_t)p];
-            ((int32_t*)(hp.data() + o_hrng))[p] = (int32_t)rng_off[(size_t)p];
-            if (f_rel) ((int32_t*)(hp.data() + o_hlc))[p] = (int32_t)lc_off[(size_t)p];
-        }
-        if (f_rel) std::fill((double*)(hp.data() + o_w_rel), (double*)(hp.data() + o_w_rel) + n_lc, 1.0);
-        char* home = (char*)ar.take(home_bytes);
-        staged_h2d(home, hp.data(), home_bytes, rsm);
-        hp.clear(); hp.shrink_to_fit();
-        off = 0;
-        const size_t c_rel_base = region(n_rel * i4), c_rel_to = region(n_rel * i4), c_rel_t = region(n_rel * d * f8), c_rel_R = region(n_rel * d * d * f8);
-        const size_t c_rel_kappa = region(n_rel * f8), c_rel_tau = region(n_rel * f8);
-        const size_t c_rng_a = region(n_rng * i4), c_rng_b = region(n_rng * i4), c_rng_dist = region(n_rng * f8), c_prec = region(n_rng * f8);
-        char* work = (char*)ar.take(off);
-        off = 0;
-        const size_t r_wn = region(n_rng * f8), r_pn = region(n_rng * f8), r_res = region(n_rng * f8), r_mu = region(count * f8);
-        const size_t r_ctl = region(count * sizeof(RobustCtl) * (f_rel ? 2 : 1));   // the ranges' records, then the loop closures'
-        const size_t r_wn_rel = f_rel ? region(n_lc * f8) : 0, r_kn = f_rel ? region(n_lc * f8) : 0, r_tn = f_rel ? region(n_lc * f8) : 0;
-        const size_t r_res_rel = f_rel ? region(n_lc * f8) : 0;
-        const size_t out_bytes = off;
-        char* outd = (char*)ar.take(out_bytes);
-        off = 0;
-        const size_t t_mem = region(count * i4), t_rel = region((count + 1) * i4), t_rng = region((count + 1) * i4);
-        const size_t t_lc = f_rel ? region((count + 1) * i4) : 0;
-        const size_t tab_bytes = off;
-        char* tab = (char*)ar.take(tab_bytes);
-        EstProb* d_probs = (EstProb*)ar.take(count * sizeof(EstProb));
-        double* d_D = nullptr;   // (a handle whose scales live on the host: SCORE_HOST_SETUP and friends)
-        size_t d_D_cap = 0;
-        size_t got_out = std::max<size_t>(out_bytes, 256);
-        char* outh = (char*)block_cache().take(got_out, st.device, true);
-        struct PinBack { char* p; size_t n; int dev; ~PinBack() { block_cache().give(p, n, dev, true); } } pinback{outh, got_out, st.device};
-        auto HI = [&](char* b, size_t o) { return (int32_t*)(b + o); };
-        auto HD = [&](char* b, size_t o) { return (double*)(b + o); };
-        // ---- host state: weights of the next solve and the mirror of its precisions, mu, the loop's records ----
-        std::vector<double> w_host((size_t)n_rng, 1.0), prec_host((size_t)n_rng);
-        for (int p = 0; p < count; ++p)
-            if (graphs[p].n_rng) std::memcpy(prec_host.data() + rng_off[(size_t)p], graphs[p].rng_prec, (size_t)graphs[p].n_rng * f8);
-        std::vector<double> w_rel_host((size_t)n_lc, 1.0), kappa_host, tau_host;   // (the mirrors: whole relative-pose arrays)
-        if (f_rel) {
-            kappa_host.resize((size_t)n_rel); tau_host.resize((size_t)n_rel);
-            for (int p = 0; p < count; ++p)
-                if (graphs[p].n_rel) {
-                    std::memcpy(kappa_host.data() + rel_off[(size_t)p], graphs[p].rel_kappa, (size_t)graphs[p].n_rel * f8);
-                    std::memcpy(tau_host.data() + rel_off[(size_t)p], graphs[p].rel_tau, (size_t)graphs[p].n_rel * f8);
-                }
-        }
-        std::vector<double> mu_host((size_t)count, 0.0);
-        std::vector<score_robust_info> rec((size_t)count);
-        std::memset(rec.data(), 0, rec.size() * sizeof(score_robust_info));
-        std::vector<int> active((size_t)count);
-        for (int p = 0; p < count; ++p) active[(size_t)p] = p;
-        bool changed = true;
-        for (int k = 1; !active.empty(); ++k) {
-            const int na = (int)active.size();
-            std::vector<score_graph> views((size_t)na);
-            std::vector<int32_t> tb(tab_bytes / i4, 0);
-            int64_t nrel_c = 0, nrng_c = 0, nlc_c = 0;
-            for (int j = 0; j < na; ++j) {
-                const int m = active[(size_t)j];
-                views[(size_t)j] = graphs[m];
-                views[(size_t)j].relaxation = 0;
-                views[(size_t)j].rng_prec = prec_host.data() + rng_off[(size_t)m];
-                tb[t_mem / i4 + j] = m;
-                tb[t_rel / i4 + j] = (int32_t)nrel_c; tb[t_rng / i4 + j] = (int32_t)nrng_c;
-                nrel_c += graphs[m].n_rel; nrng_c += graphs[m].n_rng;
-                if (f_rel) {
-                    views[(size_t)j].rel_kappa = kappa_host.data() + rel_off[(size_t)m];
-                    views[(size_t)j].rel_tau = tau_host.data() + rel_off[(size_t)m];
-                    tb[t_lc / i4 + j] = (int32_t)nlc_c;
-                    nlc_c += lc_off[(size_t)m + 1] - lc_off[(size_t)m];
-                }
-            }
-            tb[t_rel / i4 + na] = (int32_t)nrel_c; tb[t_rng / i4 + na] = (int32_t)nrng_c;
-            if (f_rel) tb[t_lc / i4 + na] = (int32_t)nlc_c;
-            if (changed) {  // the running members' arrays, compacted (k == 1: all of them, the measured precisions)
-                staged_h2d(tab, tb.data(), tab_bytes, rsm);
-                RobustGatherArgs ga{};
-                ga.d = d; ga.count = na; ga.with_static = 1;
-                ga.member = HI(tab, t_mem); ga.rel_off = HI(tab, t_rel); ga.rng_off = HI(tab, t_rng);
-                ga.home_rel_off = HI(home, o_hrel); ga.home_rng_off = HI(home, o_hrng);
-                ga.n_rel = nrel_c; ga.n_rng = nrng_c;
-                ga.h_rel_base = HI(home, o_rel_base); ga.h_rel_to = HI(home, o_rel_to); ga.h_rel_t = HD(home, o_rel_t); ga.h_rel_R = HD(home, o_rel_R);
-                ga.h_rel_kappa = HD(home, o_rel_kappa); ga.h_rel_tau = HD(home, o_rel_tau);
-                ga.h_rng_a = HI(home, o_rng_a); ga.h_rng_b = HI(home, o_rng_b); ga.h_rng_dist = HD(home, o_rng_dist);
-                ga.h_prec = k == 1 || !f_rng ? HD(home, o_prec) : HD(outd, r_pn);
-                if (f_rel && k > 1) { ga.home_lc_off = HI(home, o_hlc); ga.h_kappa_next = HD(outd, r_kn); ga.h_tau_next = HD(outd, r_tn); }
-                ga.rel_base = HI(work, c_rel_base); ga.rel_to = HI(work, c_rel_to); ga.rel_t = HD(work, c_rel_t); ga.rel_R = HD(work, c_rel_R);
-                ga.rel_kappa = HD(work, c_rel_kappa); ga.rel_tau = HD(work, c_rel_tau);
-                ga.rng_a = HI(work, c_rng_a); ga.rng_b = HI(work, c_rng_b); ga.rng_dist = HD(work, c_rng_dist); ga.prec = HD(work, c_prec);
-                const int64_t nmax = std::max(nrel_c, nrng_c);
-                if (nmax > 0) hipLaunchKernelGGL(k_robust_gather, dim3((unsigned)((nmax + 255) / 256)), dim3(256), 0, rsm, ga);
-                HIP_CHECK(hipGetLastError());
-            }
-            // (unchanged members: k_robust_weight wrote the compact precisions already)
-            HIP_CHECK(sync_stream(rsm));
-            HipBackend::GenSource src{};
-            src.rel_base = HI(work, c_rel_base); src.rel_to = HI(work, c_rel_to); src.rel_t = HD(work, c_rel_t); src.rel_R = HD(work, c_rel_R);
-            src.rel_kappa = HD(work, c_rel_kappa); src.rel_tau = HD(work, c_rel_tau);
-            src.rng_a = HI(work, c_rng_a); src.rng_b = HI(work, c_rng_b); src.rng_dist = HD(work, c_rng_dist); src.rng_prec = HD(work, c_prec);
-            RobustHandle rh;
-            if (score_create_from_graphs_impl(views.data(), na, &st, &rh.h, &src) != 0) throw std::runtime_error(std::string(g_err));
-            std::vector<score_info> inf((size_t)na);
-            if (score_solve(rh.h, nullptr, nullptr, nullptr, inf.data()) < 0) throw std::runtime_error(std::string(g_err));
-            auto& S = rh.h->solver;
-            hipStream_t hs = S.be.stream;
-            // ---- residuals, weights, control records from the solution on the device; one read ----
-            std::vector<EstProb> pr = S.est.probs;
-            if ((int)pr.size() != na) throw std::runtime_error("score_robust_solve: handle layout does not match the members");
-            staged_h2d(d_probs, pr.data(), (size_t)na * sizeof(EstProb), hs);
-            const double* Dp = S.be.Dd.d;
-            if (!S.H.device_setup) {
-                const size_t need = (size_t)S.H.n_tot;
-                if (need > d_D_cap) { d_D = (double*)ar.take(need * f8); d_D_cap = need; }
-                staged_h2d(d_D, S.H.D.data(), need * f8, hs);
-                Dp = d_D;
-            }
-            HIP_CHECK(hipMemsetAsync(outd + r_ctl, 0, (size_t)count * sizeof(RobustCtl) * (f_rel ? 2 : 1), hs));
-            RobustCtl* ctl_rng = (RobustCtl*)(outd + r_ctl);
-            RobustCtl* ctl_rel = f_rel ? ctl_rng + count : nullptr;
-            RobustArgs a{};
-            a.d = d; a.count = na; a.first = k == 1 ? 1 : 0;
-            a.probs = d_probs; a.rng_off = HI(tab, t_rng); a.member = HI(tab, t_mem); a.home_rng_off = HI(home, o_hrng);
-            a.n_rng = nrng_c;
-            a.x = S.be.xy.d; a.D = Dp;
-            a.rng_a = HI(work, c_rng_a); a.rng_b = HI(work, c_rng_b); a.rng_dist = HD(work, c_rng_dist);
-            a.prec = HD(home, o_prec); a.w = HD(home, o_w); a.resid = HD(outd, r_res);
-            a.w_next = HD(outd, r_wn); a.prec_next = HD(outd, r_pn); a.prec_work = HD(work, c_prec);
-            a.ctl = ctl_rng; a.ctl_other = ctl_rel; a.mu_in = HD(home, o_mu_in); a.mu_out = HD(outd, r_mu);
-            a.c = c; a.c_other = c_rel; a.mu_step = step; a.min_weight = mw;
-            RobustRelArgs b{};
-            if (f_rel) {
-                b.d = d; b.count = na; b.first = a.first;
-                b.probs = d_probs; b.lc_off = HI(tab, t_lc); b.rel_off = HI(tab, t_rel); b.member = HI(tab, t_mem);
-                b.home_lc_off = HI(home, o_hlc); b.home_rel_off = HI(home, o_hrel);
-                b.n_lc = nlc_c;
-                b.x = a.x; b.D = Dp;
-                b.rel_base = HI(work, c_rel_base); b.rel_to = HI(work, c_rel_to); b.rel_t = HD(work, c_rel_t); b.rel_R = HD(work, c_rel_R);
-                b.kappa = HD(home, o_rel_kappa); b.tau = HD(home, o_rel_tau); b.w = HD(home, o_w_rel); b.resid = HD(outd, r_res_rel);
-                b.w_next = HD(outd, r_wn_rel); b.kappa_next = HD(outd, r_kn); b.tau_next = HD(outd, r_tn);
-                b.kappa_work = HD(work, c_rel_kappa); b.tau_work = HD(work, c_rel_tau);
-                b.ctl = ctl_rel; b.ctl_other = f_rng ? ctl_rng : nullptr; b.mu_in = a.mu_in; b.mu_out = a.mu_out;
-                b.c = c_rel; b.c_other = c; b.mu_step = step; b.min_weight = mw;
-            }
-            // (both families' residuals before either family's weights: the first mu needs both maxima)
-            const dim3 grid((unsigned)((nrng_c + 255) / 256)), grid_rel((unsigned)((nlc_c + 255) / 256));
-            const bool run_rel = f_rel && nlc_c > 0;   // (the ranges' residuals are reported also where only the loop closures are re-weighted)
-            if (nrng_c > 0) hipLaunchKernelGGL(k_robust_resid, grid, dim3(256), 0, hs, a);
-            if (run_rel) hipLaunchKernelGGL(k_robust_resid_rel, grid_rel, dim3(256), 0, hs, b);
-            if (f_rng && nrng_c > 0) hipLaunchKernelGGL(k_robust_weight, grid, dim3(256), 0, hs, a);
-            if (run_rel) hipLaunchKernelGGL(k_robust_weight_rel, grid_rel, dim3(256), 0, hs, b);
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipMemcpyAsync(outh, outd, out_bytes, hipMemcpyDeviceToHost, hs));
-            HIP_CHECK(sync_stream(hs));
-            const double* Wn = HD(outh, r_wn); const double* Pn = HD(outh, r_pn); const double* Rs = HD(outh, r_res); const double* Mu = HD(outh, r_mu);
-            const RobustCtl* Cl = (const RobustCtl*)(outh + r_ctl);
-            const RobustCtl* Cr = Cl + count;   // (read with f_rel only)
-            const double* Wr = HD(outh, r_wn_rel); const double* Kn = HD(outh, r_kn); const double* Tn = HD(outh, r_tn); const double* Rr = HD(outh, r_res_rel);
-            // ---- who stops ----
-            std::vector<int> next, stop_j;
-            for (int j = 0; j < na; ++j) {
-                const int m = active[(size_t)j];
-                double r2max = 0.0, r2max_rel = 0.0;
-                if (f_rng) std::memcpy(&r2max, &Cl[m].r2max, sizeof(double));
-                if (f_rel) std::memcpy(&r2max_rel, &Cr[m].r2max, sizeof(double));
-                const int64_t r0 = rng_off[(size_t)m], nr = rng_off[(size_t)m + 1] - r0;
-                const int64_t l0 = lc_off[(size_t)m], nl = lc_off[(size_t)m + 1] - l0;
-                const bool out_rng = f_rng && nr > 0 && 2.0 * r2max > c * c, out_rel = f_rel && nl > 0 && 2.0 * r2max_rel > c_rel * c_rel;
-                const int32_t nonbinary = (f_rng ? Cl[m].nonbinary : 0) + (f_rel ? Cr[m].nonbinary : 0);
-                score_robust_info& R = rec[(size_t)m];
-                R.setup_ms += inf[(size_t)j].setup_ms; R.solve_ms += inf[(size_t)j].solve_ms;
-                bool stop = false, conv = false;
-                if (!std::isfinite(r2max) || !std::isfinite(r2max_rel)) stop = true;             // (a solve gone non-finite)
-                else if (k == 1 && !out_rng && !out_rel) stop = conv = true;                     // no outliers at all
-                else if (k > 1 && nonbinary == 0) stop = conv = true;                            // solved on binary weights
-                else if (k >= rs->max_outer) stop = true;
-                if (!stop) {
-                    next.push_back(m);
-                    if (f_rng && nr) {
-                        std::memcpy(w_host.data() + r0, Wn + r0, (size_t)nr * f8);
-                        std::memcpy(prec_host.data() + r0, Pn + r0, (size_t)nr * f8);
-                    }
-                    if (nl) {
-                        const size_t e0 = (size_t)(rel_off[(size_t)m + 1] - nl);   // the member's loop closures in the mirrors
-                        std::memcpy(w_rel_host.data() + l0, Wr + l0, (size_t)nl * f8);
-                        std::memcpy(kappa_host.data() + e0, Kn + l0, (size_t)nl * f8);
-                        std::memcpy(tau_host.data() + e0, Tn + l0, (size_t)nl * f8);
-                    }
-                    mu_host[(size_t)m] = Mu[m];
-                    continue;
-                }
-                stop_j.push_back(j);
-                R.outer_iterations = k; R.converged = conv ? 1 : 0; R.mu = mu_host[(size_t)m];
-                R.outliers = 0;
-                for (int64_t r = 0; r < nr; ++r) R.outliers += w_host[(size_t)(r0 + r)] < 0.5 ? 1 : 0;
-                R.rel_outliers = 0;
-                for (int64_t e = 0; e < nl; ++e) R.rel_outliers += w_rel_host[(size_t)(l0 + e)] < 0.5 ? 1 : 0;
-                R.total_ms = score::now_ms() - t0;
-                if (weights && nr) std::memcpy(weights + r0, w_host.data() + r0, (size_t)nr * f8);
-                if (residuals && nr) std::memcpy(residuals + r0, Rs + r0, (size_t)nr * f8);
-                if (rel_weights && nl) std::memcpy(rel_weights + l0, w_rel_host.data() + l0, (size_t)nl * f8);
-                if (rel_residuals && nl) std::memcpy(rel_residuals + l0, Rr + l0, (size_t)nl * f8);
-                if (infos) infos[m] = inf[(size_t)j];
-            }
-            // ---- the estimates of the members that stopped ----
-            if (!stop_j.empty() && (poses || relaxed || landmarks || ranges || degenerate)) {
-                const EstLayout& L = S.est;
-                std::vector<double> T((size_t)L.n_pose * D1 * D1), B((size_t)L.n_pose * d * D1), Lm((size_t)std::max<int64_t>(1, L.n_lm) * d),
-                    Rg((size_t)std::max<int64_t>(1, L.n_rng) * rw);
-                std::vector<int32_t> F((size_t)L.n_pose);
-                {
-                    ActiveSolve act;
-                    S.be.read_estimates(S.H, L, qdirs, T.data(), B.data(), Lm.data(), Rg.data(), F.data());
-                }
-                for (int j : stop_j) {
-                    const int m = active[(size_t)j];
-                    const EstProb& P = L.probs[(size_t)j];
-                    const size_t po = (size_t)pose_off[(size_t)m], lo = (size_t)lm_off[(size_t)m], ro = (size_t)rng_off[(size_t)m];
-                    if (poses) std::memcpy(poses + po * D1 * D1, T.data() + (size_t)P.pose_off * D1 * D1, (size_t)P.Np * D1 * D1 * f8);
-                    if (relaxed) std::memcpy(relaxed + po * d * D1, B.data() + (size_t)P.pose_off * d * D1, (size_t)P.Np * d * D1 * f8);
-                    if (landmarks && P.Nl) std::memcpy(landmarks + lo * d, Lm.data() + (size_t)P.lm_off * d, (size_t)P.Nl * d * f8);
-                    if (ranges && P.Nr) std::memcpy(ranges + ro * rw, Rg.data() + (size_t)P.rng_off * rw, (size_t)P.Nr * rw * f8);
-                    if (degenerate) std::memcpy(degenerate + po, F.data() + P.pose_off, (size_t)P.Np * sizeof(int32_t));
-                }
-            }
-            // ---- the next solve's weights and mu on the device (members that stopped are not read again) ----
-            if (!next.empty()) {
-                if (f_rng && n_rng) HIP_CHECK(hipMemcpyAsync(HD(home, o_w), HD(outd, r_wn), (size_t)n_rng * f8, hipMemcpyDeviceToDevice, hs));
-                if (n_lc) HIP_CHECK(hipMemcpyAsync(HD(home, o_w_rel), HD(outd, r_wn_rel), (size_t)n_lc * f8, hipMemcpyDeviceToDevice, hs));
-                HIP_CHECK(hipMemcpyAsync(HD(home, o_mu_in), HD(outd, r_mu), (size_t)count * f8, hipMemcpyDeviceToDevice, hs));
-                HIP_CHECK(sync_stream(hs));
-            }
-            changed = next.size() != active.size();
-            active.swap(next);
-        }
-        if (rinfos) std::memcpy(rinfos, rec.data(), (size_t)count * sizeof(score_robust_info));
-        return 0;
+        RobustRun R{};
+        R.graphs = graphs; R.count = count; R.rs = rs;
+        R.rng.weights_out = weights; R.rng.resid_out = residuals; R.lc.weights_out = rel_weights; R.lc.resid_out = rel_residuals;
+        R.poses = poses; R.relaxed = relaxed; R.landmarks = landmarks; R.ranges = ranges; R.degenerate = degenerate; R.infos = infos;
+        return R.solve(s, families, rel_threshold, rinfos);
     });
 }
 }  // extern "C"

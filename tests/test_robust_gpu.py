@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from conftest import graph_by_name
+from robust_helpers import _bit_equal, _poses_close
 from score_amd.manhattan import make_manhattan
 from score_amd.native import ArrayGraph, graph_arrays
 from score_amd.robust import corrupt_ranges, solve_score_robust, solve_score_robust_batch
@@ -12,20 +13,6 @@ from score_amd.solve_score import solve_score
 pytestmark = pytest.mark.gpu
 
 CORRUPT = dict(n_robots=2, n_poses=60, n_beacons=3, p_range=0.5, sigma_range=0.1)
-
-
-def _poses_close(a, b, rel):
-    scale = max(1.0, max(float(np.max(np.abs(T[:-1, -1]))) for T in b.poses.values()))
-    worst = max(float(np.max(np.abs(a.poses[k] - b.poses[k]))) for k in b.poses) / scale
-    assert worst <= rel, worst
-
-
-def _bit_equal(a, b):
-    for k in b.poses:
-        np.testing.assert_array_equal(a.poses[k], b.poses[k])
-    for k in b.landmarks:
-        np.testing.assert_array_equal(a.landmarks[k], b.landmarks[k])
-    np.testing.assert_array_equal(a.relaxed_poses.array, b.relaxed_poses.array)
 
 
 @pytest.mark.parametrize("seed", [2, 4])
@@ -80,3 +67,21 @@ def test_lockstep_batch_members_stop_on_their_own(hip_lib):
         assert b.info["robust"]["outer_iterations"] == one.info["robust"]["outer_iterations"]
         np.testing.assert_array_equal(b.info["robust"]["outliers"], one.info["robust"]["outliers"])
         _poses_close(b, one, 1e-7)
+
+
+def test_both_families_without_loop_closures_is_the_range_family(hip_lib):
+    # a graph without loop closures: the second family has no item, launches nothing, and its zeroed control records do not
+    # lower the graph's mu -- every decision and every bit is the range family's
+    g, _ = corrupt_ranges(make_manhattan(seed=2, **CORRUPT), 0.08, seed=2)
+    both = solve_score_robust(g, "SOCP", robust_loop_closures=True)
+    rng = solve_score_robust(g, "SOCP")
+    a, b = both.info["robust"], rng.info["robust"]
+    print(a["outer_iterations"], a["mu"], a["outliers"])
+    assert a["outer_iterations"] == b["outer_iterations"] and a["converged"] == b["converged"]
+    np.testing.assert_array_equal(a["outliers"], b["outliers"])
+    np.testing.assert_array_equal(a["weights"], b["weights"])
+    np.testing.assert_array_equal(a["residuals"], b["residuals"])
+    assert a["mu"] == b["mu"]
+    _bit_equal(both, rng)
+    assert len(a["loop_closure_weights"]) == 0 and len(a["loop_closure_outliers"]) == 0
+    assert a["outer_iterations"] > 1

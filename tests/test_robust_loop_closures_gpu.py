@@ -7,11 +7,12 @@ import numpy as np
 import pytest
 
 from conftest import graph_by_name
+from robust_helpers import _bit_equal, _poses_close
 from score_amd import compat
 from score_amd.manhattan import make_manhattan, make_manhattan_3d
 from score_amd.native import ArrayGraph, ScoreGraph, graph_arrays, score_graph_struct
 from score_amd.robust import (ScoreRobustInfo, ScoreRobustSettings, _bind, corrupt_loop_closures, corrupt_ranges,
-                              relaxed_loop_closure_residuals, solve_score_robust, solve_score_robust_batch)
+                              relaxed_loop_closure_residuals, relaxed_range_residuals, solve_score_robust, solve_score_robust_batch)
 from score_amd.solve_score import solve_score
 from score_amd.solver import ScoreInfo, ScoreSettings, _f64p, _i32p, load_library
 
@@ -21,20 +22,6 @@ G2 = dict(n_robots=1, n_poses=80, n_beacons=3, p_range=0.5, sigma_range=0.1, n_l
 G3 = dict(n_robots=1, n_poses=40, n_beacons=3, p_range=0.5, sigma_range=0.1, n_loop_closures=6)
 LC_ONLY = dict(robust_ranges=False, robust_loop_closures=True)
 BOTH = dict(robust_loop_closures=True)
-
-
-def _poses_close(a, b, rel):
-    scale = max(1.0, max(float(np.max(np.abs(T[:-1, -1]))) for T in b.poses.values()))
-    worst = max(float(np.max(np.abs(a.poses[k] - b.poses[k]))) for k in b.poses) / scale
-    assert worst <= rel, worst
-
-
-def _bit_equal(a, b):
-    for k in b.poses:
-        np.testing.assert_array_equal(a.poses[k], b.poses[k])
-    for k in b.landmarks:
-        np.testing.assert_array_equal(a.landmarks[k], b.landmarks[k])
-    np.testing.assert_array_equal(a.relaxed_poses.array, b.relaxed_poses.array)
 
 
 def _arrays(g):
@@ -89,6 +76,22 @@ def test_device_engine_matches_python_engine(case, hip_lib):
     ref = solve_score(ArrayGraph(arr), "SOCP")
     _bit_equal(dev, ref)
     assert dev.info["pobj"] == ref.info["pobj"]
+
+
+@pytest.mark.parametrize("case", [_g2_seed5_both, _g2_seed3])
+def test_reported_residuals_are_those_of_the_returned_solution(case, hip_lib):
+    g, kw = case()
+    res = solve_score_robust(g, "SOCP", **kw)
+    info = res.info["robust"]
+    arrays = _arrays(g)
+    for got, r in ((info["residuals"], relaxed_range_residuals(arrays, res.relaxed_poses.array, res.landmarks.array)),
+                   (info["loop_closure_residuals"], relaxed_loop_closure_residuals(arrays, res.relaxed_poses.array))):
+        assert got.shape == r.shape and len(r) > 0
+        err = np.abs(got - r) / np.maximum(1.0, r)
+        print(case.__name__, len(r), info["outer_iterations"], float(np.max(err)))
+        assert float(np.max(err)) <= 1e-9, float(np.max(err))
+    if kw is LC_ONLY:  # the ranges are measured, not re-weighted
+        np.testing.assert_array_equal(info["weights"], np.ones(len(arrays["rng_a"])))
 
 
 def _indexing_graph(n_lc, seed):
