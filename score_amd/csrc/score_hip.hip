@@ -2286,6 +2286,7 @@ struct HipBackend {
             hipLaunchKernelGGL(k_join_schur<BS>, dim3((unsigned)((n_join_chains + 63) / 64)), dim3(64), 0, stream, ja, n_join_chains);
         });
     }
+    double* join_vec_zb = nullptr;  // the separators' solutions of an INIT over several vectors, when the caller brings the buffer (score_marginals.hpp)
     template <int MODE>
     void join_apply(const PrecSet& S, const PrecArgs& pa) {
         JoinArgs ja = join_args(S);
@@ -2296,7 +2297,7 @@ struct HipBackend {
         if (MODE == PREC_INIT && pa.n_vec > 1) {  // (score_link.hpp's refresh: every round's vector in one launch)
             nv = (unsigned)pa.n_vec;
             ja.n_vec = pa.n_vec; ja.vec_stride = pa.vec_stride; ja.zb_stride = (long long)H->bs * n_join_seps; ja.rz_stride = (long long)n_prec;
-            ja.zb = link_zb.d;
+            ja.zb = join_vec_zb ? join_vec_zb : link_zb.d;
         }
         with_bs([&](auto bs) {
             constexpr int BS = decltype(bs)::value;
@@ -3962,6 +3963,8 @@ struct AbiEnv {
 
 #include "score_abi.hpp"
 
+#include "score_marginals.hpp"
+
 // Local refinement after SCORE on the device (score_gn.hpp): state, blocks and gathers here, the damped
 // normal equations through the linear-mode handle `lin` (its K0 values and right-hand side are written
 // in place by the gather kernels; the step is read from its solution vector).
@@ -3975,6 +3978,7 @@ struct score_refine {
     DevBuf<double> u, ut, hblk, gblk, rhs, cost_part, gmax_part;
     int n_mblocks = 0, n_ublocks = 0, n_hblocks = 0, n_sblocks = 0;
     std::vector<double> part_host;
+    score::MvWork mv;  // marginal covariances (score_marginals.hpp)
 
     HipBackend& be() { return lin->solver.be; }
     hipStream_t stream() { return lin->solver.be.stream; }
@@ -4061,14 +4065,17 @@ struct score_refine {
         for (double v : part_host) m = std::max(m, v);
         return m;
     }
-    bool solve(double lambda, double rel_tol, int* used) {  // (J'J + lambda I) step = -g, step left in the handle's xtu
+    void gather_h(double lambda) {  // J'J + lambda I from the blocks of the last evaluation, into the handle's K0
         hipLaunchKernelGGL(score::k_gn_gather_h, dim3(n_hblocks), dim3(kThreads), 0, stream(), (const int32_t*)hc_ptr.d,
                            (const int32_t*)hc_slot.d, (const double*)hblk.d, (const int32_t*)is_diag.d, lambda, be().K0d.d,
                            (int64_t)P.hcol.size());
+    }
+    bool solve(double lambda, double rel_tol, int* used) {  // (J'J + lambda I) step = -g, step left in the handle's xtu
+        gather_h(lambda);
         return be().linear_solve_core(lin->solver.H, rhs.d, rel_tol, 4000, used);
     }
-    void run(const double* poses_in, const double* lms_in, int max_iters, double tol, double* poses_out, double* lms_out,
-             score::GnInfo& info) {
+    // the caller's point becomes the current one (u); returns the state as uploaded
+    std::vector<double> set_point(const double* poses_in, const double* lms_in) {
         std::vector<double> u0((size_t)P.state_size());
         if (P.dim == 2) {
             for (int64_t p = 1; p < P.Np; ++p)
@@ -4081,6 +4088,11 @@ struct score_refine {
         }
         staged_h2d(u.d, u0.data(), u0.size() * sizeof(double), stream());
         HIP_CHECK(sync_stream(stream()));
+        return u0;
+    }
+    void run(const double* poses_in, const double* lms_in, int max_iters, double tol, double* poses_out, double* lms_out,
+             score::GnInfo& info) {
+        std::vector<double> u0 = set_point(poses_in, lms_in);
         score::gn_levenberg_marquardt(*this, max_iters, tol, 1e-9, info);
         staged_d2h(u0.data(), u.d, u0.size() * sizeof(double), stream());
         HIP_CHECK(sync_stream(stream()));
@@ -4187,6 +4199,15 @@ int score_refine_run(score_refine* r, const double* poses_in, const double* land
             info->setup_ms = r->setup_ms; info->solve_ms = score::now_ms() - t0;
         }
         return 0;
+    });
+}
+int score_refine_marginals(score_refine* r, const double* poses, const double* landmarks, const int32_t* vars, int32_t n_vars,
+                           double rel_tol, int32_t max_iters, int32_t block_width, double* joint, double* residuals, int32_t* iters,
+                           score_marginals_info* info) {
+    return abi_call([&] {
+        require(r && poses && (r->P.Nl == 0 || landmarks));
+        AbiEnv::Scope scope(r->device, false);
+        return score::mv_solve(*r, poses, landmarks, vars, n_vars, rel_tol, max_iters, block_width, joint, residuals, iters, info);
     });
 }
 void score_refine_destroy(score_refine* r) {

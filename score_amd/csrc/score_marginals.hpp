@@ -1,0 +1,446 @@
+// score_marginals.hpp -- marginal covariances of the refined estimate (include/score_marginals.h): H X = E_S with
+// H = J'J at the given point, one unit column per scalar unknown of the selected variables, by a chain-preconditioned
+// conjugate-gradient iteration over BLOCKS of up to kMvMaxWidth columns that advance in lock-step.
+//
+// What exists already and is used as it is: the per-measurement blocks (k_gn_blocks / k_gn_blocks3), the gather of H on the
+// linear-mode handle's pattern (k_gn_gather_h, lambda = 0), the chain factorisation (derive_rho_data -> k_factor) and the
+// application of M^-1 to several vectors in one launch (launch_prec<PREC_INIT> with PrecArgs::n_vec: chains, the second
+// level of score_join.hpp, Jacobi on the landmark columns; the loop-closure correction is left out -- the preconditioner
+// only has to be one fixed SPD operator for the whole solve).  New here: the product over several vectors and the
+// vector updates of the block.
+//
+// Vectors of a block are stored one after the other, stride n (the layout PrecArgs::vec_stride expects).  One iteration:
+//   k_mv_product    w_c = H p_c for every live column from ONE pass over the CSR matrix, per-workgroup partials of p_c'w_c
+//   k_mv_step       alpha_c = r'z / p'w (both re-reduced from the partials in a fixed order), x_c += alpha p_c, r_c -= alpha w_c
+//   launch_prec     z_c = M^-1 r_c, partials of r_c'z_c
+//   k_mv_direction  beta = r'z_new / r'z_old, p_c = z_c + beta p_c; the gate r'z_new <= rel_tol^2 r0'z0 raises the column's
+//                   done word (the stopping rule of score_linear_solve)
+// Every kernel tests the column's done word first and leaves a done column's x, r and p as they are (the chain kernel
+// keeps writing the scratch z of such a column: it is never read again).  1: converged, 2: broken down (a non-finite r'z or
+// p'w, or p'w <= 0) -- reported as not converged.  No atomics: every sum is a fixed-order reduction, and all workgroups of
+// a column reduce the same partials in the same order, so they take the same decision.
+//
+// Rows are short (a pose row holds 3-6 unknowns and a dozen neighbours) except the landmark rows (a beacon ranged from
+// every pose: 2 x poses entries).  A tile of the product is either kMvRows consecutive short rows, kMvLanes lanes each, or
+// ONE long row spread over the workgroup and reduced through LDS.
+#pragma once
+
+#include <cmath>
+#include <cstdint>
+#include <vector>
+
+#include "../../include/score_marginals.h"
+#include "score_kernels.hpp"
+
+namespace score {
+
+constexpr int kMvMaxWidth = 16;                  // columns of a block
+constexpr int kMvThreads = 256;
+constexpr int kMvLanes = 4;                      // lanes of a short row
+constexpr int kMvRows = kMvThreads / kMvLanes;   // short rows of a tile
+constexpr int kMvLongRow = 128;                  // entries beyond which a row is a tile of its own
+constexpr int kMvDone = 0, kMvIters = kMvMaxWidth, kMvZero = 2 * kMvMaxWidth, kMvFlagWords = 2 * kMvMaxWidth + 1;
+
+struct MvArgs {
+    // H on the linear-mode handle's pattern, and the product's tiles {first row, end row, long row?, 0}
+    const int32_t* ptr; const int32_t* col; const double* val;
+    const int4* tiles;
+    int n_tiles;
+    long long n;
+    int32_t* flags;            // [kMvDone + c] done word, [kMvIters + c] steps executed, [kMvZero] a zero (the chain kernel's done word)
+    int all_columns;           // product: ignore the done words (the residual's product H x)
+    // vectors of the block, column c at c * n
+    double* x; double* r; const double* z; double* p; double* w;
+    const double* p_in;        // the product's operand (p, or x for the residual)
+    double* pw_part;           // [c * n_tiles + tile]
+    const double* rz_new;      // [c * n_prec + item]: partials of the last application of M^-1
+    const double* rz_old;
+    int n_prec;
+    int first;                 // direction: p = z, the gate's threshold is set
+    double tol2;
+    double* ref;               // per column: rel_tol^2 r0'z0
+    // right-hand sides, residuals, the rows of S
+    const int32_t* sel;        // C selected unknowns
+    int c0, live, C;           // the block's first column in sel, its live columns, all columns
+    double* res_part;          // [c * gridDim.x + block]
+    double* joint;             // C x C
+};
+
+__device__ __forceinline__ bool mv_finite(double v) { return fabs(v) <= 1.79769313486231570e308; }
+
+// w_c = H p_in_c over the live columns, partials of p_in_c'w_c.  NV: columns of the block (compile time: the sums live in registers).
+template <int NV>
+__global__ __launch_bounds__(kMvThreads) void k_mv_product(MvArgs a) {
+    __shared__ double red[(kMvThreads / 64) * NV];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    unsigned live = 0;
+#pragma unroll
+    for (int c = 0; c < NV; ++c)
+        if (a.all_columns || a.flags[kMvDone + c] == 0) live |= 1u << c;
+    if (!live) return;
+    const int4 tile = a.tiles[blockIdx.x];
+    const long long n = a.n;
+    double acc[NV];
+#pragma unroll
+    for (int c = 0; c < NV; ++c) acc[c] = 0.0;
+    if (tile.z) {  // one long row over the workgroup
+        const int row = tile.x;
+        const int k1 = a.ptr[row + 1];
+        for (int k = a.ptr[row] + t; k < k1; k += kMvThreads) {
+            const double v = a.val[k];
+            const long long j = a.col[k];
+#pragma unroll
+            for (int c = 0; c < NV; ++c)
+                if (live >> c & 1) acc[c] += v * a.p_in[c * n + j];
+        }
+#pragma unroll
+        for (int c = 0; c < NV; ++c)
+            if (live >> c & 1) {
+                const double s = wave_sum(acc[c]);
+                if (lane == 0) red[wave * NV + c] = s;
+            }
+        __syncthreads();
+        if (t < NV && (live >> t & 1)) {
+            const double wv = (red[t] + red[NV + t]) + (red[2 * NV + t] + red[3 * NV + t]);
+            a.w[t * n + row] = wv;
+            a.pw_part[(size_t)t * a.n_tiles + blockIdx.x] = a.p_in[t * n + row] * wv;
+        }
+        return;
+    }
+    // short rows: kMvLanes lanes per row, their sums joined as (l0 + l1) + (l2 + l3)
+    const int row = tile.x + t / kMvLanes, sub = t % kMvLanes;
+    const bool mine = row < tile.y;
+    if (mine) {
+        const int k1 = a.ptr[row + 1];
+        for (int k = a.ptr[row] + sub; k < k1; k += kMvLanes) {
+            const double v = a.val[k];
+            const long long j = a.col[k];
+#pragma unroll
+            for (int c = 0; c < NV; ++c)
+                if (live >> c & 1) acc[c] += v * a.p_in[c * n + j];
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < NV; ++c)
+        if (live >> c & 1) {
+            double s = acc[c];
+            s += __shfl_xor(s, 1, 64);
+            s += __shfl_xor(s, 2, 64);
+            double pw = 0.0;
+            if (mine && sub == 0) {
+                a.w[c * n + row] = s;
+                pw = a.p_in[c * n + row] * s;
+            }
+            pw = wave_sum(pw);
+            if (lane == 0) red[wave * NV + c] = pw;
+        }
+    __syncthreads();
+    if (t < NV && (live >> t & 1))
+        a.pw_part[(size_t)t * a.n_tiles + blockIdx.x] = (red[t] + red[NV + t]) + (red[2 * NV + t] + red[3 * NV + t]);
+}
+
+// grid (row blocks, columns): alpha = r'z / p'w ; x += alpha p ; r -= alpha w
+__global__ __launch_bounds__(kMvThreads) void k_mv_step(MvArgs a) {
+    __shared__ double red[8];
+    const int c = blockIdx.y, t = threadIdx.x;
+    if (a.flags[kMvDone + c]) return;
+    double rz = 0.0, pw = 0.0;
+    for (int i = t; i < a.n_prec; i += kMvThreads) rz += a.rz_new[(size_t)c * a.n_prec + i];
+    for (int i = t; i < a.n_tiles; i += kMvThreads) pw += a.pw_part[(size_t)c * a.n_tiles + i];
+    block_sum2(rz, pw, red);
+    const bool lead = blockIdx.x == 0 && t == 0;
+    if (!(mv_finite(rz) && mv_finite(pw) && pw > 0.0)) {
+        if (lead) a.flags[kMvDone + c] = 2;
+        return;
+    }
+    const double alpha = rz / pw;
+    const long long i = (long long)blockIdx.x * kMvThreads + t;
+    if (i < a.n) {
+        const long long e = c * a.n + i;
+        a.x[e] += alpha * a.p[e];
+        a.r[e] -= alpha * a.w[e];
+    }
+    if (lead) a.flags[kMvIters + c] += 1;
+}
+
+// grid (row blocks, columns): the gate, then p = z + beta p (first: p = z and the gate's threshold)
+__global__ __launch_bounds__(kMvThreads) void k_mv_direction(MvArgs a) {
+    __shared__ double red[8];
+    const int c = blockIdx.y, t = threadIdx.x;
+    if (a.flags[kMvDone + c]) return;
+    double rzn = 0.0, rzo = 0.0;
+    for (int i = t; i < a.n_prec; i += kMvThreads) {
+        rzn += a.rz_new[(size_t)c * a.n_prec + i];
+        if (!a.first) rzo += a.rz_old[(size_t)c * a.n_prec + i];
+    }
+    block_sum2(rzn, rzo, red);
+    const bool lead = blockIdx.x == 0 && t == 0;
+    double beta = 0.0;
+    if (a.first) {
+        if (!(mv_finite(rzn) && rzn > 0.0)) {  // (a zero right-hand side is solved by x = 0; anything else is no SPD preconditioner)
+            if (lead) a.flags[kMvDone + c] = rzn == 0.0 ? 1 : 2;
+            return;
+        }
+        if (lead) a.ref[c] = a.tol2 * rzn;
+    } else {
+        if (!(mv_finite(rzn) && rzo > 0.0)) {
+            if (lead) a.flags[kMvDone + c] = 2;
+            return;
+        }
+        if (rzn <= a.ref[c]) {
+            if (lead) a.flags[kMvDone + c] = 1;
+            return;
+        }
+        beta = rzn / rzo;
+    }
+    const long long i = (long long)blockIdx.x * kMvThreads + t;
+    if (i < a.n) {
+        const long long e = c * a.n + i;
+        a.p[e] = a.first ? a.z[e] : a.z[e] + beta * a.p[e];
+    }
+}
+
+// grid (row blocks, columns): x = 0, r = the unit vector of the column's unknown (columns beyond `live`: zero, done from the start)
+__global__ __launch_bounds__(kMvThreads) void k_mv_rhs(MvArgs a) {
+    const int c = blockIdx.y, t = threadIdx.x;
+    const long long i = (long long)blockIdx.x * kMvThreads + t;
+    const bool on = c < a.live;
+    if (i < a.n) {
+        a.x[c * a.n + i] = 0.0;
+        a.r[c * a.n + i] = (on && i == a.sel[a.c0 + c]) ? 1.0 : 0.0;
+    }
+    if (blockIdx.x == 0 && t == 0) {
+        a.flags[kMvDone + c] = on ? 0 : 1;
+        a.flags[kMvIters + c] = 0;
+        if (c == 0) a.flags[kMvZero] = 0;
+    }
+}
+
+// grid (row blocks, live columns): partials of |e_c - w_c|^2 with w = H x
+__global__ __launch_bounds__(kMvThreads) void k_mv_residual(MvArgs a) {
+    __shared__ double red[4];
+    const int c = blockIdx.y, t = threadIdx.x;
+    const long long i = (long long)blockIdx.x * kMvThreads + t;
+    double d = 0.0;
+    if (i < a.n) d = (i == a.sel[a.c0 + c] ? 1.0 : 0.0) - a.w[c * a.n + i];
+    const double s = block_sum(d * d, red);
+    if (t == 0) a.res_part[(size_t)c * gridDim.x + blockIdx.x] = s;
+}
+
+// grid (blocks over the C rows of S, live columns): joint[s, c0 + c] = x_c[sel[s]]
+__global__ __launch_bounds__(kMvThreads) void k_mv_gather(MvArgs a) {
+    const int c = blockIdx.y;
+    const long long s = (long long)blockIdx.x * kMvThreads + threadIdx.x;
+    if (s < a.C) a.joint[s * a.C + a.c0 + c] = a.x[c * a.n + a.sel[s]];
+}
+
+// the product's tiles from the row pointers
+inline void mv_tiles(const std::vector<int32_t>& ptr, int64_t n, std::vector<int4>& tiles) {
+    tiles.clear();
+    auto len = [&](int64_t i) { return ptr[(size_t)i + 1] - ptr[(size_t)i]; };
+    int64_t row = 0;
+    while (row < n) {
+        if (len(row) > kMvLongRow) { tiles.push_back(make_int4((int)row, (int)row + 1, 1, 0)); ++row; continue; }
+        int64_t end = row;
+        while (end < n && end - row < kMvRows && len(end) <= kMvLongRow) ++end;
+        tiles.push_back(make_int4((int)row, (int)end, 0, 0));
+        row = end;
+    }
+}
+
+// the unknowns of the selected variables, in the order of include/score_marginals.h
+inline void mv_columns(const GnProblem& P, const int32_t* vars, int32_t n_vars, std::vector<int32_t>& sel) {
+    if (!vars || n_vars <= 0) throw std::runtime_error("score_refine_marginals: no variables");
+    std::vector<char> seen((size_t)(P.Np + P.Nl), 0);
+    sel.clear();
+    for (int32_t k = 0; k < n_vars; ++k) {
+        const int64_t v = vars[k];
+        if (v < 0 || v >= P.Np + P.Nl) throw std::runtime_error("score_refine_marginals: variable out of range");
+        if (v == 0) throw std::runtime_error("score_refine_marginals: pose 0 is fixed, it has no covariance");
+        if (seen[(size_t)v]) throw std::runtime_error("score_refine_marginals: a variable is listed twice");
+        seen[(size_t)v] = 1;
+        const int64_t first = v < P.Np ? P.pose_col(v) : (int64_t)P.dp() * (P.Np - 1) + (int64_t)P.dim * (v - P.Np);
+        const int cnt = v < P.Np ? P.dp() : P.dim;
+        for (int a = 0; a < cnt; ++a) sel.push_back((int32_t)(first + a));
+    }
+}
+
+// The block's buffers: they stay with the refinement handle between calls (device allocations of their own, not the
+// handle's arena: they come with the first call and go with the handle).
+struct MvWork {
+    DevBuf<double> x, r, z, p, w, p_scratch, pw_part, rz0, rz1, ref, res_part, zb;
+    DevBuf<int32_t> flags;
+    DevBuf<int4> tiles;
+    int n_tiles = 0;
+    void reserve(const GnProblem& P, int n_prec, int zb_per_vector, hipStream_t st) {
+        if (x.d) return;
+        struct NoArena {
+            DevArena* keep;
+            NoArena() : keep(tl_arena) { tl_arena = nullptr; }
+            ~NoArena() { tl_arena = keep; }
+        } no_arena;
+        std::vector<int4> t;
+        mv_tiles(P.hptr, P.n, t);
+        n_tiles = (int)t.size();
+        tiles.alloc(t.size());
+        staged_h2d(tiles.d, t.data(), t.size() * sizeof(int4), st);
+        const size_t nv = (size_t)kMvMaxWidth, n = (size_t)P.n, rb = (n + kMvThreads - 1) / kMvThreads;
+        DevBuf<double>* vecs[] = {&x, &r, &z, &p, &w, &p_scratch};
+        for (DevBuf<double>* v : vecs) { v->alloc(nv * n); v->zero(st); }
+        pw_part.alloc(nv * (size_t)n_tiles); pw_part.zero(st);
+        // (every workgroup of a chain-kernel launch has a slot, per vector)
+        rz0.alloc(nv * (size_t)n_prec + 4096); rz0.zero(st);
+        rz1.alloc(nv * (size_t)n_prec + 4096); rz1.zero(st);
+        ref.alloc(nv); ref.zero(st);
+        res_part.alloc(nv * rb); res_part.zero(st);
+        zb.alloc(nv * (size_t)std::max(1, zb_per_vector)); zb.zero(st);
+        flags.alloc((size_t)kMvFlagWords); flags.zero(st);
+    }
+};
+
+// The solve.  Refine: score_refine (its point, blocks and gather, its linear-mode handle, its MvWork).
+template <class Refine>
+int mv_solve(Refine& R, const double* poses, const double* landmarks, const int32_t* vars, int32_t n_vars, double rel_tol,
+             int32_t max_iters, int32_t block_width, double* joint, double* residuals, int32_t* iters, score_marginals_info* info) {
+    const GnProblem& P = R.P;
+    if (block_width < 0 || block_width > kMvMaxWidth) throw std::runtime_error("score_refine_marginals: block_width must be 0..16");
+    if (!(rel_tol > 0.0) || max_iters < 1) throw std::runtime_error("score_refine_marginals: rel_tol must be positive and max_iters >= 1");
+    std::vector<int32_t> sel;
+    mv_columns(P, vars, n_vars, sel);
+    const int C = (int)sel.size();
+    if ((size_t)C * (size_t)C > ((size_t)1 << 27)) throw std::runtime_error("score_refine_marginals: too many columns for one call (C x C doubles beyond 1 GiB)");
+    HipBackend& be = R.be();
+    hipStream_t st = R.stream();
+    const long long n = P.n;
+    const double t0 = now_ms();
+    // H at the point, on the handle's pattern; the chains factored once for the block path (the single solves factor per call)
+    R.set_point(poses, landmarks);
+    (void)R.eval_at(R.u.d, true);
+    R.gather_h(0.0);
+    const bool seq = block_width == 0;
+    if (!seq && be.split.active) throw std::runtime_error("score_refine_marginals: blocks of columns need the unsplit chain kernel (chain_split = 0)");
+    if (!seq && be.n_prec == 0) throw std::runtime_error("score_refine_marginals: the handle has no preconditioner work (no unknowns?)");
+    if (!seq) be.derive_rho_data(false);
+    const int NV = seq ? 1 : (block_width <= 1 ? 1 : block_width <= 2 ? 2 : block_width <= 4 ? 4 : block_width <= 8 ? 8 : 16);
+    auto& W = R.mv;
+    W.reserve(P, be.n_prec, be.H->bs * be.n_join_seps, st);
+    DevBuf<int32_t> d_sel;
+    DevBuf<double> d_joint;
+    {
+        struct NoArena {
+            DevArena* keep;
+            NoArena() : keep(tl_arena) { tl_arena = nullptr; }
+            ~NoArena() { tl_arena = keep; }
+        } no_arena;
+        d_sel.alloc((size_t)C); d_joint.alloc((size_t)C * (size_t)C);
+    }
+    staged_h2d(d_sel.d, sel.data(), (size_t)C * sizeof(int32_t), st);
+    const int n_rblocks = (int)((n + kMvThreads - 1) / kMvThreads);
+    MvArgs a{};
+    a.ptr = be.Kset.mat.ptr.d; a.col = be.Kset.mat.col.d; a.val = be.Kset.mat.val.d;
+    a.tiles = W.tiles.d; a.n_tiles = W.n_tiles; a.n = n; a.flags = W.flags.d;
+    a.x = W.x.d; a.r = W.r.d; a.z = W.z.d; a.p = W.p.d; a.w = W.w.d; a.pw_part = W.pw_part.d;
+    a.n_prec = be.n_prec; a.tol2 = rel_tol * rel_tol; a.ref = W.ref.d;
+    a.sel = d_sel.d; a.C = C; a.res_part = W.res_part.d; a.joint = d_joint.d;
+    auto product = [&](const MvArgs& m) {
+        const dim3 g((unsigned)m.n_tiles), b(kMvThreads);
+        switch (NV) {
+            case 1: hipLaunchKernelGGL(k_mv_product<1>, g, b, 0, st, m); break;
+            case 2: hipLaunchKernelGGL(k_mv_product<2>, g, b, 0, st, m); break;
+            case 4: hipLaunchKernelGGL(k_mv_product<4>, g, b, 0, st, m); break;
+            case 8: hipLaunchKernelGGL(k_mv_product<8>, g, b, 0, st, m); break;
+            default: hipLaunchKernelGGL(k_mv_product<16>, g, b, 0, st, m); break;
+        }
+    };
+    // z = M^-1 r of every column of the block, partials of r'z into `rz`
+    auto precondition = [&](double* rz) {
+        PrecArgs pa = be.prec_args(be.Kset);
+        pa.done = W.flags.d + kMvZero;
+        be.prec_vectors(pa, W.r.d, W.r.d, W.z.d, W.p_scratch.d, W.w.d, W.p_scratch.d, W.p_scratch.d, nullptr);
+        pa.rz_in = nullptr; pa.rz_out = rz;
+        if (NV > 1) { pa.n_vec = NV; pa.vec_stride = n; }
+        be.join_vec_zb = W.zb.d;
+        be.launch_prec<PREC_INIT>(be.Kset, pa, -1, HipBackend::PrecDepth::join);
+        be.join_vec_zb = nullptr;
+    };
+    const double t1 = now_ms();
+    std::vector<int32_t> flags((size_t)kMvFlagWords), col_done((size_t)C, 0), col_iters((size_t)C, 0);
+    std::vector<double> res_part((size_t)NV * (size_t)n_rblocks), col_res((size_t)C, 0.0);
+    int batches = 0, pcg_iters = 0;
+    const int width = seq ? 1 : block_width;
+    for (int c0 = 0; c0 < C; c0 += width) {
+        const int live = std::min(width, C - c0);
+        a.c0 = c0; a.live = live;
+        hipLaunchKernelGGL(k_mv_rhs, dim3((unsigned)n_rblocks, (unsigned)NV), dim3(kMvThreads), 0, st, a);
+        if (seq) {
+            // the single-right-hand-side solve of linear mode, as it is; its solution into the block's column 0
+            int used = 0;
+            const bool ok = be.linear_solve_core(R.lin->solver.H, W.r.d, rel_tol, max_iters, &used);
+            HIP_CHECK(hipMemcpyAsync(W.x.d, be.xtu.d, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
+            flags[kMvDone] = ok ? 1 : 0; flags[kMvIters] = used;
+        } else {
+            double* rz_cur = W.rz0.d; double* rz_nxt = W.rz1.d;
+            precondition(rz_cur);
+            a.first = 1; a.rz_new = rz_cur; a.rz_old = nullptr;
+            hipLaunchKernelGGL(k_mv_direction, dim3((unsigned)n_rblocks, (unsigned)NV), dim3(kMvThreads), 0, st, a);
+            a.first = 0;
+            int queued = 0;
+            bool all_done = false;
+            while (!all_done && queued < max_iters) {
+                const int chunk = std::min(max_iters - queued, queued == 0 ? 16 : 32);
+                for (int j = 0; j < chunk; ++j) {
+                    a.all_columns = 0; a.p_in = W.p.d;
+                    product(a);
+                    a.rz_new = rz_cur;
+                    hipLaunchKernelGGL(k_mv_step, dim3((unsigned)n_rblocks, (unsigned)NV), dim3(kMvThreads), 0, st, a);
+                    precondition(rz_nxt);
+                    a.rz_new = rz_nxt; a.rz_old = rz_cur;
+                    hipLaunchKernelGGL(k_mv_direction, dim3((unsigned)n_rblocks, (unsigned)NV), dim3(kMvThreads), 0, st, a);
+                    std::swap(rz_cur, rz_nxt);
+                }
+                queued += chunk;
+                HIP_CHECK(hipGetLastError());
+                staged_d2h(flags.data(), W.flags.d, (size_t)kMvFlagWords * sizeof(int32_t), st);
+                all_done = true;
+                for (int c = 0; c < NV; ++c) all_done = all_done && flags[(size_t)(kMvDone + c)] != 0;
+            }
+        }
+        // the true residual of every column of the block (one more product, w = H x), the rows of S
+        a.all_columns = 1; a.p_in = W.x.d;
+        product(a);
+        hipLaunchKernelGGL(k_mv_residual, dim3((unsigned)n_rblocks, (unsigned)live), dim3(kMvThreads), 0, st, a);
+        hipLaunchKernelGGL(k_mv_gather, dim3((unsigned)((C + kMvThreads - 1) / kMvThreads), (unsigned)live), dim3(kMvThreads), 0, st, a);
+        HIP_CHECK(hipGetLastError());
+        staged_d2h(res_part.data(), W.res_part.d, (size_t)live * (size_t)n_rblocks * sizeof(double), st);
+        int most = 0;
+        for (int c = 0; c < live; ++c) {
+            double s = 0.0;
+            for (int b = 0; b < n_rblocks; ++b) s += res_part[(size_t)c * (size_t)n_rblocks + (size_t)b];
+            const double rho = std::sqrt(s);
+            col_res[(size_t)(c0 + c)] = rho;
+            col_done[(size_t)(c0 + c)] = (flags[(size_t)(kMvDone + c)] == 1 && std::isfinite(rho)) ? 1 : 0;
+            col_iters[(size_t)(c0 + c)] = flags[(size_t)(kMvIters + c)];
+            most = std::max(most, flags[(size_t)(kMvIters + c)]);
+        }
+        pcg_iters += most;
+        ++batches;
+    }
+    if (joint) staged_d2h(joint, d_joint.d, (size_t)C * (size_t)C * sizeof(double), st);
+    HIP_CHECK(sync_stream(st));
+    const double t2 = now_ms();
+    int unconverged = 0;
+    double worst = 0.0;
+    for (int c = 0; c < C; ++c) {
+        if (!col_done[(size_t)c]) ++unconverged;
+        worst = std::isfinite(col_res[(size_t)c]) ? std::max(worst, col_res[(size_t)c]) : INFINITY;
+        if (residuals) residuals[c] = col_res[(size_t)c];
+        if (iters) iters[c] = col_done[(size_t)c] ? col_iters[(size_t)c] : -(col_iters[(size_t)c] + 1);
+    }
+    if (info) {
+        info->columns = C; info->batches = batches; info->pcg_iters = pcg_iters; info->unconverged = unconverged;
+        info->max_residual = worst; info->setup_ms = t1 - t0; info->solve_ms = t2 - t1;
+    }
+    return unconverged ? 1 : 0;
+}
+
+}  // namespace score
