@@ -44,6 +44,7 @@
 #include "score_link.hpp"
 #include "score_generate.hpp"
 #include "score_robust.hpp"
+#include "score_slab.hpp"
 #include "../../include/score_robust.h"
 
 namespace {
@@ -902,7 +903,7 @@ struct HipBackend {
     DevArena arena;  // declared before every buffer: destroyed after them
 
     CsrBufs K, G1, G2;
-    BandBufs Kb, Hb;  // band views of K and of the Newton matrix (score_band.hpp); off: the CSR-stream kernels serve them
+    BandBufs Kb, Hb;  // band view of K (score_band.hpp); off: the CSR-stream kernels serve it.  Hb: the Newton set's, never on
     // SCORE_NO_BAND=1: the CSR-stream kernels serve K (tests: both layouts against the twin)
     bool band_k(const HostSystem&) const {
         // K through its band view whatever the batch size (what a problem computes must not depend on its batch mates: the two
@@ -911,9 +912,7 @@ struct HipBackend {
         // dependent trips bound by its slowest workgroup (the landmark rows' segments): 6.4 / 7.1 us either way.
         return std::getenv("SCORE_NO_BAND") == nullptr;
     }
-    // (a band view of the Newton matrix was measured without effect -- 64 config-5 trials 7.0 ms per solve with and without,
-    //  headline default solve 4.5 ms either way -- and cost setup time: removed in round 6, profiles/TRIED.md)
-    static constexpr bool band_h(const HostSystem&) { return false; }
+    // (a band view of the Newton matrix was measured without effect and cost setup time: removed in round 6, profiles/TRIED.md)
     DevBuf<int32_t> A_ptr, A_col;
     DevBuf<double> A_val;
     DevBuf<double> q, b, invD, invE, rho, K0d, K1d;
@@ -1098,7 +1097,7 @@ struct HipBackend {
     // asked by build_system once sizes and the replication structure are known
     bool device_setup_allowed(const HostSystem& h, const score_settings& s_) const {
         if (std::getenv("SCORE_HOST_SETUP") || std::getenv("SCORE_HOST_POLISH_BUILD") || std::getenv("SCORE_NO_DEVICE_RUIZ")) return false;  // (switches that ask for a host-side piece)
-        if (h.m_tot <= 0 || s_.chain_split > 0 || band_h(h)) return false;   // (linear mode keeps K0 on the host)
+        if (h.m_tot <= 0 || s_.chain_split > 0) return false;   // (linear mode keeps K0 on the host)
         if (h.rep > 1)
             for (char ex : h.rep_exact_all)
                 if (!ex) return false;  // (replicas that differ in their last bits: the host uses every replica's own values)
@@ -1718,184 +1717,299 @@ struct HipBackend {
         h.K.col.assign(src, src + kcols_n);
         kcols_pin.reset();
     }
+    // ---- the create path: init() lists the phases of a create in their order; every phase is a member function below it ----
+    // Where the handle's matrices come from, decided once (matrix_source):
+    //   device    everything is built on the device from the raw problems or graphs (HostSystem::device_setup, setup_on_device)
+    //   derived   host build_system; the equilibrated A, G1 and G2 are derived on the device from what the equilibration left there
+    //   uploaded  host build_system; everything is uploaded
+    enum class MatrixSource { device, derived, uploaded };
+    MatrixSource source = MatrixSource::uploaded;
+    int n_cus = 0;                     // compute units of the device (device_limits)
+    std::future<BandLayout> band_job;  // the band view of K, laid out on a thread of its own (start_band_layout -> adopt_band_view)
+    MatrixSource matrix_source(const HostSystem& h) const {
+        if (h.device_setup) return MatrixSource::device;
+        // A single problem whose equilibration ran on the device: the equilibrated A, G1 = A' and G2 = [P | A'] are derived
+        // there from the raw matrices and scales those passes left behind (k_derive_a / k_derive_g; 26 MB of uploads less
+        // for the headline problem) -- a replicated problem only when its replicas' P values are bit-equal to replica 0's.
+        const bool derive = h.count == 1 && h.m_tot > 0 && ruiz_dev.kept && ruiz_dev.k_n == h.n_tot && ruiz_dev.k_m == h.m_tot &&
+                            ruiz_dev.k_nnzA == (int64_t)h.A.col.size() && ruiz_dev.k_rep == h.rep && (h.rep == 1 || h.rep_exact);
+        return derive ? MatrixSource::derived : MatrixSource::uploaded;
+    }
+    // The guards of a create, held by init() in this order: a throw from any phase unwinds them last to first.
+    struct ArenaScope {  // buffers allocated during init come from this handle's arena
+        explicit ArenaScope(DevArena* a) { tl_arena = a; }
+        ~ArenaScope() { tl_arena = nullptr; }
+    };
+    struct StageScope {  // setup uploads through pinned staging (StageArena); one synchronisation when the setup is over
+        StageArena a;
+        hipStream_t st;
+        StageScope(int dev, hipStream_t s) : st(s) {
+            a.dev = dev;
+            tl_stage = &a;
+        }
+        ~StageScope() {
+            tl_stage = nullptr;
+            (void)sync_stream(st);  // (every queued transfer has left its pinned slot)
+        }
+    };
+    struct JoinPolish {  // an exception must not leave the builder running against a dying handle
+        std::future<void>& f;
+        ~JoinPolish() { if (f.valid()) f.wait(); }
+    };
+    struct JoinBand {  // (nor the layout job)
+        std::future<BandLayout>& f;
+        ~JoinBand() { if (f.valid()) f.wait(); }
+    };
+    struct DropKept {  // (the kept buffers go back when the setup is over, whatever happens -- once nothing reads them any more)
+        RuizDevice& r;
+        hipStream_t st;
+        ~DropKept() {
+            if (r.kept) (void)sync_stream(st);
+            r.drop();
+        }
+    };
+
     void init(HostSystem& h, const score_settings& s_, const score_problem* probs = nullptr, const score_graph* graphs = nullptr) {
         H = &h;
         st = s_;
         PhaseTimer pt(st.verbose != 0);
+        decide_sources(h);
+        open_device();
+        ArenaScope arena_scope(&arena);
+        StageScope stage_scope(st.device, stream);
+        device_limits();
+        pt.mark("device + stream");
+        if (h.bs < 0 || h.bs > 4) throw std::runtime_error("unsupported block size");
+        JoinPolish join_polish{polish_build};
+        JoinBand join_band{band_job};
+        DropKept drop_kept{ruiz_dev, stream};
+        switch (source) {  // K's pattern, G1, G2, A, q, b, 1/D, 1/E and the cone table on the device
+            case MatrixSource::device: matrices_from_device(h, probs, graphs, pt); break;
+            case MatrixSource::derived: matrices_derived(h, pt); break;
+            case MatrixSource::uploaded: matrices_uploaded(h, pt); break;
+        }
+        set_replica_strides(h);
+        upload_cone_tables(h);
+        pt.mark("  uploads: cone records");
+        {   // (the chain tables: one run of uploads, nothing launched in between -- UploadBatch)
+            UploadBatch ub_tables;
+            upload_chain_tables(h);
+            plan_split_kernel(h);
+        }
+        pt.mark("uploads");
+        plan_chain_kernel(h);
+        const bool polish_from_device = st.polish && init_polish_build(h);
+        pt.mark("polish: structure (before the band view is waited for)");
+        adopt_band_view(h, pt);
+        carve_iterates(h);
+        cg_iters = st.cg_iters;
+        done.upload(std::vector<int32_t>((size_t)h.count, 0));
+        upload_k0_k1(h);
+        chain_positions(h);
+        join_init(h);
+        alloc_factors(h);
+        pt.mark("allocations + rho data (device)");
+        if (st.polish) init_polish(h, polish_from_device);
+        link_init(h, probs, graphs);
+        pt.mark("polish setup");
+        carve_report_and_control(h);
+        reset();
+        pt.mark("reset");
+        drain_setup();
+        pt.mark("staged uploads: drain");
+    }
+
+    void decide_sources(const HostSystem& h) {
+        source = matrix_source(h);
+        derive_ag = source == MatrixSource::derived;
+        // The Newton matrix: its pattern and contribution lists are built on the device (score_polish_device.hpp) from the
+        // handle's matrices -- unless SCORE_HOST_POLISH_BUILD is set: then on another host thread while this one uploads.
+        polish_on_device = st.polish && std::getenv("SCORE_HOST_POLISH_BUILD") == nullptr;
+    }
+    void drain_setup() {
+        HIP_CHECK(sync_stream(stream));
+        setup_tmp.release_all();  // (nothing in flight reads the setup's scratch any more)
+        for (auto& pb : setup_pinned) block_cache().give(pb.first, pb.second, st.device, true);
+        setup_pinned.clear();
+    }
+    void open_device() {
         require_hip_device(st.device);
         HIP_CHECK(hipSetDevice(st.device));
         arena.dev = st.device;
         stream = stream_pool().take(st.device);
         tl_copy_stream = stream;
-        struct ArenaScope {  // buffers allocated during init come from this handle's arena
-            explicit ArenaScope(DevArena* a) { tl_arena = a; }
-            ~ArenaScope() { tl_arena = nullptr; }
-        } arena_scope(&arena);
-        struct StageScope {  // setup uploads through pinned staging (StageArena); one synchronisation when the setup is over
-            StageArena a;
-            hipStream_t st;
-            StageScope(int dev, hipStream_t s) : st(s) {
-                a.dev = dev;
-                tl_stage = &a;
-            }
-            ~StageScope() {
-                tl_stage = nullptr;
-                (void)sync_stream(st);  // (every queued transfer has left its pinned slot)
-            }
-        } stage_scope(st.device, stream);
+    }
+    void device_limits() {
         HIP_CHECK(hipEventCreate(&ev0));
         HIP_CHECK(hipEventCreate(&ev1));
-        {   // split long rows finished by polling (CsrDev::long_spin) only where the whole launch is resident at once: every
-            // SpMV kernel fits two workgroups per CU (<= 216 registers), the products with the Newton matrix six (<= 82)
-            int cus = 0;
-            HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, st.device));
-            K.spin_max_tiles = G1.spin_max_tiles = G2.spin_max_tiles = cus * 3 / 2;
-            Hm.spin_max_tiles = cus * 4;
-        }
-        pt.mark("device + stream");
-        if (h.bs != 0 && h.bs != 3 && h.bs != 4 && h.bs != 1 && h.bs != 2)
-            throw std::runtime_error("unsupported block size");
-        struct JoinPolish {  // an exception below must not leave the builder running against a dying handle
-            std::future<void>& f;
-            ~JoinPolish() { if (f.valid()) f.wait(); }
-        } join_polish{polish_build};
-        // the Newton matrix pattern and its contribution lists only read the finished host system:
-        // built on another thread while this one uploads (4.3 ms beside 2.4 ms of uploads / allocations)
-        // The Newton matrix: its pattern and contribution lists are built on the device (score_polish_device.hpp) from the
-        // matrices uploaded below -- unless its band view is asked for or SCORE_HOST_POLISH_BUILD is set: then on another
-        // host thread while this one uploads.  Either way the structure check (per-cone data) runs on that thread.
-        polish_on_device = st.polish && !band_h(h) && std::getenv("SCORE_HOST_POLISH_BUILD") == nullptr;
-        if (h.device_setup && !probs && !graphs) throw std::runtime_error("device setup: the raw problems are missing");
-        if (st.polish && !h.device_setup)  // (device setup: the per-cone structure comes from a kernel, init_polish)
+        HIP_CHECK(hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, st.device));
+        // split long rows finished by polling (CsrDev::long_spin) only where the whole launch is resident at once: every
+        // SpMV kernel fits two workgroups per CU (<= 216 registers), the products with the Newton matrix six (<= 82)
+        K.spin_max_tiles = G1.spin_max_tiles = G2.spin_max_tiles = n_cus * 3 / 2;
+        Hm.spin_max_tiles = n_cus * 4;
+    }
+    // The host-side jobs that only read the finished host system, each on a thread of its own beside the uploads: the polish
+    // structure (the per-cone data; with SCORE_HOST_POLISH_BUILD the whole Newton pattern and its lists: 4.3 ms beside 2.4 ms
+    // of uploads / allocations) and the band layout of K.
+    void start_host_jobs(HostSystem& h) {
+        if (st.polish)
             polish_build = std::async(std::launch::async, [this, &h] {
                 if (polish_on_device) { Q = PolishData(); polish_structure(h, Q); }
-                else build_polish(h, Q, st.verbose != 0, band_h(h));
+                else build_polish(h, Q, st.verbose != 0);
             });
-        std::future<BandLayout> band_layout_job;
-        auto start_band_layout = [&] {
-        if (band_k(h) && !h.chains.empty())  // the band view of K only reads the finished host system: laid out on a thread of its own
-            band_layout_job = std::async(std::launch::async, [&h, this] {
-                BuildScope scope;
-                adopt_k_columns(h);  // (device setup: the columns are still in their pinned block)
-                std::vector<char> use(h.chains.size());
-                for (size_t ci = 0; ci < h.chains.size(); ++ci) use[ci] = h.chain_owner[ci] == (int32_t)ci;
-                std::vector<RowSegment> sg;
-                if (h.rep > 1) {
-                    for (int p = 0; p < h.count; ++p) {
-                        const int64_t nr = h.rep_n[(size_t)p];
-                        sg.push_back(RowSegment{h.xoff[p], h.xoff[p] + nr, p, (int32_t)nr});
-                        sg.push_back(RowSegment{h.xoff[p] + (int64_t)h.rep * nr, h.xoff[p + 1], p, 0});
-                    }
-                } else {
-                    sg = plain_segments(h.xoff);
+        start_band_layout(h);
+    }
+    void start_band_layout(HostSystem& h) {
+        if (!band_k(h) || h.chains.empty()) return;
+        band_job = std::async(std::launch::async, [&h, this] {
+            BuildScope scope;
+            adopt_k_columns(h);  // (device setup: the columns are still in their pinned block)
+            std::vector<char> use(h.chains.size());
+            for (size_t ci = 0; ci < h.chains.size(); ++ci) use[ci] = h.chain_owner[ci] == (int32_t)ci;
+            std::vector<RowSegment> sg;
+            if (h.rep > 1) {
+                for (int p = 0; p < h.count; ++p) {
+                    const int64_t nr = h.rep_n[(size_t)p];
+                    sg.push_back(RowSegment{h.xoff[p], h.xoff[p] + nr, p, (int32_t)nr});
+                    sg.push_back(RowSegment{h.xoff[p] + (int64_t)h.rep * nr, h.xoff[p + 1], p, 0});
                 }
-                return build_band_layout(h.K, sg, band_runs(h.chains, use, h.bs, h.rep, h.rep_n, true), h.bs, h.count);
-            });
-        };
-        if (!h.device_setup) start_band_layout();
-        struct JoinBand {  // (an exception below must not leave the job running against a dying handle)
-            std::future<BandLayout>& f;
-            ~JoinBand() { if (f.valid()) f.wait(); }
-        } join_band{band_layout_job};
-        if (h.device_setup) {
-            // everything matrix-shaped is built on the device from the raw problems (score_setup_device.hpp); the cone table
-            // (its rows are the equilibration's groups) goes up first
-            cone_row.upload(h.cone_row); cone_dim.upload(h.cone_dim); cone_type.upload(h.cone_type);
-            setup_on_device(h, probs, graphs);
-            start_band_layout();
-            if (!band_layout_job.valid()) adopt_k_columns(h);  // (no layout job to do it)
-            { UploadBatch ub; K.adopt_tiles(h.K, h.rbK); G1.adopt_tiles(h.G1, h.rbG1); G2.adopt_tiles(h.G2, h.rbG2); }
-            pt.mark("  device setup");
-        } else
-        K.upload(h.K, h.rbK, nullptr, false);  // (values: K0 + rho K1, on the device -- derive_rho_data)
-        // A single problem whose equilibration ran on the device: the equilibrated A, G1 = A' and G2 = [P | A'] are derived
-        // there from the raw matrices and scales those passes left behind (k_derive_a / k_derive_g; 26 MB of uploads less
-        // for the headline problem) -- a replicated problem only when its replicas' P values are bit-equal to replica 0's.
-        derive_ag = !h.device_setup && h.count == 1 && h.m_tot > 0 && ruiz_dev.kept && ruiz_dev.k_n == h.n_tot && ruiz_dev.k_m == h.m_tot &&
-                    ruiz_dev.k_nnzA == (int64_t)h.A.col.size() && ruiz_dev.k_rep == h.rep && (h.rep == 1 || h.rep_exact);
-        struct DropKept {  // (the kept buffers go back when the setup is over, whatever happens -- once nothing reads them any more)
-            RuizDevice& r;
-            hipStream_t st;
-            ~DropKept() {
-                if (r.kept) (void)sync_stream(st);
-                r.drop();
+            } else {
+                sg = plain_segments(h.xoff);
             }
-        } drop_kept{ruiz_dev, stream};
-        if (!h.device_setup) {
-        G1.upload(h.G1, h.rbG1, nullptr, !derive_ag, !derive_ag);
-        G2.upload(h.G2, h.rbG2, &h.g2_split, !derive_ag, !derive_ag);
-        }
+            return build_band_layout(h.K, sg, band_runs(h.chains, use, h.bs, h.rep, h.rep_n, true), h.bs, h.count);
+        });
+    }
+
+    // ---- the three matrix sources: each straight down, in the order the device sees the work ----
+    void matrices_from_device(HostSystem& h, const score_problem* probs, const score_graph* graphs, PhaseTimer& pt) {
+        if (!probs && !graphs) throw std::runtime_error("device setup: the raw problems are missing");
+        // everything matrix-shaped is built on the device from the raw problems (score_setup_device.hpp); the cone table
+        // (its rows are the equilibration's groups) goes up first.  (The per-cone structure of the polish comes from a kernel,
+        // polish_structure_on_device: no host job for it.)
+        cone_row.upload(h.cone_row); cone_dim.upload(h.cone_dim); cone_type.upload(h.cone_type);
+        setup_on_device(h, probs, graphs);
+        start_band_layout(h);
+        if (!band_job.valid()) adopt_k_columns(h);  // (no layout job to do it)
+        { UploadBatch ub; K.adopt_tiles(h.K, h.rbK); G1.adopt_tiles(h.G1, h.rbG1); G2.adopt_tiles(h.G2, h.rbG2); }
+        pt.mark("  device setup");
         pt.mark("  uploads: K, G1, G2");
-        // replicated problems (HostSystem::rep): K and G1 = A' hold replica 0's rows; K's operands repeat with the
-        // block's replica stride, G1's are the consecutive tail rows of a cone
+        upload_vector_blocks(h);
+        pt.mark("  uploads: A, q, b, 1/D, 1/E");
+    }
+    void matrices_derived(HostSystem& h, PhaseTimer& pt) {
+        start_host_jobs(h);
+        K.upload(h.K, h.rbK, nullptr, false);  // (values: K0 + rho K1, on the device -- derive_rho_data)
+        G1.upload(h.G1, h.rbG1, nullptr, false, false);  // (row pointers and tiles: k_derive_g fills columns and values)
+        G2.upload(h.G2, h.rbG2, &h.g2_split, false, false);
+        pt.mark("  uploads: K, G1, G2");
+        upload_vector_blocks(h);
+        A_ptr.upload(h.A.ptr);
+        const size_t nz = h.A.col.size();  // padded like the SpMV matrices: the cone kernel clamps its unconditional loads
+        A_col.alloc(nz + 64); A_val.alloc(nz + 64);
+        { UploadBatch fills; fill_zero_async(A_col.d + nz, 64 * sizeof(int32_t), stream); fill_zero_async(A_val.d + nz, 64 * sizeof(double), stream); }
+        DeriveArgs da{};
+        da.n = h.n_tot; da.m = h.m_tot; da.nnzA = (int64_t)nz; da.rep = h.rep; da.nr = h.rep > 1 ? h.rep_n[0] : 0;
+        da.P_ptr = ruiz_dev.Pp.d; da.P_col = ruiz_dev.Pc.d; da.P_val = ruiz_dev.Pv.d;
+        da.A_ptr = ruiz_dev.Ap.d; da.A_col = ruiz_dev.Ac.d; da.A_val = ruiz_dev.Av.d;
+        da.atp = ruiz_dev.dat.d; da.atpos = ruiz_dev.dpos.d; da.arow = ruiz_dev.drow.d; da.D = ruiz_dev.dD.d; da.E = ruiz_dev.dE.d;
+        da.oA_col = A_col.d; da.oA_val = A_val.d;
+        da.g1_ptr = G1.ptr.d; da.g1_col = G1.col.d; da.g1_val = G1.val.d;
+        da.g2_ptr = G2.ptr.d; da.g2_split = G2.split.d; da.g2_col = G2.col.d; da.g2_val = G2.val.d;
+        if (nz) hipLaunchKernelGGL(k_derive_a, dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, stream, da);
+        hipLaunchKernelGGL(k_derive_g, dim3((unsigned)((h.n_tot + 3) / 4)), dim3(256), 0, stream, da);
+        HIP_CHECK(hipGetLastError());
+        q.upload(h.q); b.upload(h.b);
+        invD.alloc(h.D.size()); invE.alloc(h.E.size());  // (D and E are on the device: their reciprocals too)
+        const int64_t nm = std::max<int64_t>((int64_t)h.D.size(), (int64_t)h.E.size());
+        hipLaunchKernelGGL(k_derive_inv, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, stream, (const double*)ruiz_dev.dD.d, (const double*)ruiz_dev.dE.d,
+                           invD.d, invE.d, (int64_t)h.D.size(), (int64_t)h.E.size());
+        HIP_CHECK(hipGetLastError());
+        pt.mark("  uploads: A, q, b, 1/D, 1/E");
+        cone_row.upload(h.cone_row); cone_dim.upload(h.cone_dim); cone_type.upload(h.cone_type);
+    }
+    void matrices_uploaded(HostSystem& h, PhaseTimer& pt) {
+        start_host_jobs(h);
+        K.upload(h.K, h.rbK, nullptr, false);  // (values: K0 + rho K1, on the device -- derive_rho_data)
+        G1.upload(h.G1, h.rbG1);
+        G2.upload(h.G2, h.rbG2, &h.g2_split);
+        pt.mark("  uploads: K, G1, G2");
+        upload_vector_blocks(h);
+        A_ptr.upload(h.A.ptr);
+        A_col.upload_padded(h.A.col, 64); A_val.upload_padded(h.A.val, 64);  // padded like the SpMV matrices: the cone kernel clamps its unconditional loads
+        q.upload(h.q); b.upload(h.b);
+        std::vector<double> iD(h.D.size()), iE(h.E.size());
+        parallel_ranges((int64_t)iD.size(), 32768, [&](int, int64_t i0, int64_t i1) { for (int64_t i = i0; i < i1; ++i) iD[(size_t)i] = 1.0 / h.D[(size_t)i]; });
+        parallel_ranges((int64_t)iE.size(), 32768, [&](int, int64_t i0, int64_t i1) { for (int64_t i = i0; i < i1; ++i) iE[(size_t)i] = 1.0 / h.E[(size_t)i]; });
+        invD.upload(iD); invE.upload(iE);
+        pt.mark("  uploads: A, q, b, 1/D, 1/E");
+        cone_row.upload(h.cone_row); cone_dim.upload(h.cone_dim); cone_type.upload(h.cone_type);
+    }
+    // blocks of <= 256 vector entries per problem (k_xupdate).  Common to the three sources, and called by each where it has
+    // always stood -- between G2 and A: UploadBatch merges what is neighbour in time because it is neighbour in memory.
+    void upload_vector_blocks(const HostSystem& h) {
+        std::vector<int32_t> vf, ve, vp;
+        for (int p = 0; p < h.count; ++p)
+            for (int64_t r = h.xoff[p]; r < h.xoff[p + 1]; r += kThreads) {
+                vf.push_back((int32_t)r); ve.push_back((int32_t)std::min<int64_t>(r + kThreads, h.xoff[p + 1])); vp.push_back(p);
+            }
+        n_vblocks = (int)vf.size();
+        UploadBatch ub;
+        vb_first.upload(vf); vb_end.upload(ve); vb_prob.upload(vp);
+    }
+    // K0 and K1 of the host sources go up after the iterates, as ever; the device source built them in place (setup_on_device)
+    void upload_k0_k1(const HostSystem& h) {
+        if (source == MatrixSource::device) return;
+        K0d.upload_padded(h.K0, 64); K1d.upload_padded(h.K1, 64);
+    }
+
+    // ---- what every source shares ----
+    // replicated problems (HostSystem::rep): K and G1 = A' hold replica 0's rows; K's operands repeat with the
+    // block's replica stride, G1's are the consecutive tail rows of a cone
+    void set_replica_strides(const HostSystem& h) {
         K.rep = h.rep; K.rs_in = 0;
         G1.rep = h.rep; G1.rs_in = 1;
         K.unroll = (h.rep > 1) ? h.tile_nnz / kThreads : kUnroll;
         G1.unroll = (h.rep > 1) ? kUnroll / 2 : kUnroll;  // (tiles of at most kTileNnz / 2 nonzeros, see build_system)
-        {
-            std::vector<int32_t> vf, ve, vp;
-            for (int p = 0; p < h.count; ++p)
-                for (int64_t r = h.xoff[p]; r < h.xoff[p + 1]; r += kThreads) {
-                    vf.push_back((int32_t)r); ve.push_back((int32_t)std::min<int64_t>(r + kThreads, h.xoff[p + 1])); vp.push_back(p);
-                }
-            n_vblocks = (int)vf.size();
-            UploadBatch ub;
-            vb_first.upload(vf); vb_end.upload(ve); vb_prob.upload(vp);
-        }
-        if (!h.device_setup) A_ptr.upload(h.A.ptr);
-        // padded like the SpMV matrices: the cone kernel clamps its unconditional loads
-        if (h.device_setup) {
-        } else if (derive_ag) {
-            const size_t nz = h.A.col.size();
-            A_col.alloc(nz + 64); A_val.alloc(nz + 64);
-            { UploadBatch fills; fill_zero_async(A_col.d + nz, 64 * sizeof(int32_t), stream); fill_zero_async(A_val.d + nz, 64 * sizeof(double), stream); }
-            DeriveArgs da{};
-            da.n = h.n_tot; da.m = h.m_tot; da.nnzA = (int64_t)nz; da.rep = h.rep; da.nr = h.rep > 1 ? h.rep_n[0] : 0;
-            da.P_ptr = ruiz_dev.Pp.d; da.P_col = ruiz_dev.Pc.d; da.P_val = ruiz_dev.Pv.d;
-            da.A_ptr = ruiz_dev.Ap.d; da.A_col = ruiz_dev.Ac.d; da.A_val = ruiz_dev.Av.d;
-            da.atp = ruiz_dev.dat.d; da.atpos = ruiz_dev.dpos.d; da.arow = ruiz_dev.drow.d; da.D = ruiz_dev.dD.d; da.E = ruiz_dev.dE.d;
-            da.oA_col = A_col.d; da.oA_val = A_val.d;
-            da.g1_ptr = G1.ptr.d; da.g1_col = G1.col.d; da.g1_val = G1.val.d;
-            da.g2_ptr = G2.ptr.d; da.g2_split = G2.split.d; da.g2_col = G2.col.d; da.g2_val = G2.val.d;
-            if (nz) hipLaunchKernelGGL(k_derive_a, dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, stream, da);
-            hipLaunchKernelGGL(k_derive_g, dim3((unsigned)((h.n_tot + 3) / 4)), dim3(256), 0, stream, da);
-            HIP_CHECK(hipGetLastError());
-        } else {
-            A_col.upload_padded(h.A.col, 64); A_val.upload_padded(h.A.val, 64);
-        }
-        if (!h.device_setup) { q.upload(h.q); b.upload(h.b); }
-        if (h.device_setup) {
-        } else if (derive_ag) {  // (D and E are on the device: their reciprocals too)
-            invD.alloc(h.D.size()); invE.alloc(h.E.size());
-            const int64_t nm = std::max<int64_t>((int64_t)h.D.size(), (int64_t)h.E.size());
-            hipLaunchKernelGGL(k_derive_inv, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, stream, (const double*)ruiz_dev.dD.d, (const double*)ruiz_dev.dE.d,
-                               invD.d, invE.d, (int64_t)h.D.size(), (int64_t)h.E.size());
-            HIP_CHECK(hipGetLastError());
-        } else {
-            std::vector<double> iD(h.D.size()), iE(h.E.size());
-            parallel_ranges((int64_t)iD.size(), 32768, [&](int, int64_t i0, int64_t i1) { for (int64_t i = i0; i < i1; ++i) iD[(size_t)i] = 1.0 / h.D[(size_t)i]; });
-            parallel_ranges((int64_t)iE.size(), 32768, [&](int, int64_t i0, int64_t i1) { for (int64_t i = i0; i < i1; ++i) iE[(size_t)i] = 1.0 / h.E[(size_t)i]; });
-            invD.upload(iD); invE.upload(iE);
-        }
-        pt.mark("  uploads: A, q, b, 1/D, 1/E");
-        if (!h.device_setup) { cone_row.upload(h.cone_row); cone_dim.upload(h.cone_dim); cone_type.upload(h.cone_type); }
+    }
+    void upload_cone_tables(const HostSystem& h) {
         { UploadBatch ub; cone_block_first.upload(h.cone_block_first); cone_block_prob.upload(h.cone_block_prob); }
-        {   // the cone tables (row pointers, the entries of the small cones again by cone index): from A on the device
-            const size_t nc = h.cone_row.size();
-            cone_meta.alloc(2 * nc); cone_cols.alloc(8 * nc); cone_vals.alloc(8 * nc);
-            if (nc) {
-                ConeTabArgs ca{};
-                ca.ncones = (int64_t)nc; ca.cone_row = cone_row.d; ca.cone_dim = cone_dim.d; ca.cone_type = cone_type.d;
-                ca.A_ptr = A_ptr.d; ca.A_col = A_col.d; ca.A_val = A_val.d;
-                ca.meta = cone_meta.d; ca.cols = cone_cols.d; ca.vals = cone_vals.d;
-                hipLaunchKernelGGL(k_cone_tables, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, stream, ca);
-                HIP_CHECK(hipGetLastError());
-            }
+        // the cone tables (row pointers, the entries of the small cones again by cone index): from A on the device
+        const size_t nc = h.cone_row.size();
+        cone_meta.alloc(2 * nc); cone_cols.alloc(8 * nc); cone_vals.alloc(8 * nc);
+        if (nc) {
+            ConeTabArgs ca{};
+            ca.ncones = (int64_t)nc; ca.cone_row = cone_row.d; ca.cone_dim = cone_dim.d; ca.cone_type = cone_type.d;
+            ca.A_ptr = A_ptr.d; ca.A_col = A_col.d; ca.A_val = A_val.d;
+            ca.meta = cone_meta.d; ca.cols = cone_cols.d; ca.vals = cone_vals.d;
+            hipLaunchKernelGGL(k_cone_tables, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, stream, ca);
+            HIP_CHECK(hipGetLastError());
         }
         n_cone_blocks = (int)h.cone_block_prob.size();
-        pt.mark("  uploads: cone records");
-        {   // (the chain tables below: one run of uploads, nothing launched in between -- UploadBatch)
-        UploadBatch ub_tables;
+    }
+    // the records k_prec_pre reads (PrecRecord), for the factors of K or for those of the Newton matrix
+    std::vector<PrecRecord> prec_records(const HostSystem& h, const std::vector<ChainDesc>& cs, const std::vector<ChainLevelDesc>& ls) const {
+        std::vector<PrecRecord> rec(h.prec_work.size());
+        std::memset((void*)rec.data(), 0, rec.size() * sizeof(PrecRecord));
+        for (size_t w = 0; w < rec.size(); ++w) {
+            rec[w].wk = h.prec_work[w];
+            if (rec[w].wk.kind != 0) continue;
+            rec[w].ch = cs[(size_t)rec[w].wk.index];
+            for (int l = 0; l < std::min<int>(rec[w].ch.n_levels, kRecLevels); ++l) rec[w].lv[l] = ls[(size_t)rec[w].ch.level_begin + l];
+        }
+        // update helpers (PrecArgs::split_update): a single problem's chains occupy a fraction of the CUs for the
+        // whole launch, and a third of what each of them pulls through its CU is the xt / kx update.  Extra
+        // records after the problem's own hand that update, slice by slice, to workgroups on the idle CUs.
+        // (A batch fills the chip with chains: there the update stays fused.)
+        PrecRecord hr;
+        std::memset((void*)&hr, 0, sizeof(hr));
+        for (int i = 0; i < n_help; ++i) {
+            const int64_t e0 = (int64_t)i * kHelpEntries;
+            hr.wk = PrecWork{2, (int32_t)e0, (int32_t)std::min<int64_t>(kHelpEntries, h.n_tot - e0), 0};
+            rec.push_back(hr);
+        }
+        return rec;
+    }
+    void upload_chain_tables(const HostSystem& h) {
         {
             std::vector<int2> lg;
             for (int bl = 0; bl < n_cone_blocks; ++bl)
@@ -1913,77 +2027,55 @@ struct HipBackend {
         Kset.fac_doubles = h.fac_doubles; Hset.fac_doubles = h.fac_doubles_H;
         Kset.deep_floats = h.deep_floats; Hset.deep_floats = h.deep_floats_H;
         Kset.use_owner = h.rep > 1;
-        {   // the records k_prec_pre reads (PrecRecord), for the factors of K and for those of the Newton matrix
-            auto build = [&](const std::vector<ChainDesc>& cs, const std::vector<ChainLevelDesc>& ls) {
-                std::vector<PrecRecord> rec(h.prec_work.size());
-                std::memset((void*)rec.data(), 0, rec.size() * sizeof(PrecRecord));
-                for (size_t w = 0; w < rec.size(); ++w) {
-                    rec[w].wk = h.prec_work[w];
-                    if (rec[w].wk.kind != 0) continue;
-                    rec[w].ch = cs[(size_t)rec[w].wk.index];
-                    for (int l = 0; l < std::min<int>(rec[w].ch.n_levels, kRecLevels); ++l) rec[w].lv[l] = ls[(size_t)rec[w].ch.level_begin + l];
-                }
-                // update helpers (PrecArgs::split_update): a single problem's chains occupy a fraction of the CUs for the
-                // whole launch, and a third of what each of them pulls through its CU is the xt / kx update.  Extra
-                // records after the problem's own hand that update, slice by slice, to workgroups on the idle CUs.
-                // (A batch fills the chip with chains: there the update stays fused.)
-                PrecRecord hr;
-                std::memset((void*)&hr, 0, sizeof(hr));
-                for (int i = 0; i < n_help; ++i) {
-                    const int64_t e0 = (int64_t)i * kHelpEntries;
-                    hr.wk = PrecWork{2, (int32_t)e0, (int32_t)std::min<int64_t>(kHelpEntries, h.n_tot - e0), 0};
-                    rec.push_back(hr);
-                }
-                return rec;
-            };
-            {
-                int cus = 0;
-                HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, st.device));
-                const int want = (int)((h.n_tot + kHelpEntries - 1) / kHelpEntries);
-                const bool on = h.count == 1 && (int)h.prec_work.size() + want <= cus;  // the whole launch resident at once
-                n_help = on ? want : 0;
-            }
-            Kset.rec.upload(build(h.chains, h.levels));
-            if (h.rep > 1 && st.polish) Hset.rec.upload(build(h.chainsH, h.levelsH));
-            else Hset.rec.view(Kset.rec.d, Kset.rec.n);
-        }
+        const int want = (int)((h.n_tot + kHelpEntries - 1) / kHelpEntries);  // update helpers: only when the whole launch is resident at once
+        n_help = (h.count == 1 && (int)h.prec_work.size() + want <= n_cus) ? want : 0;
+        Kset.rec.upload(prec_records(h, h.chains, h.levels));
+        if (h.rep > 1 && st.polish) Hset.rec.upload(prec_records(h, h.chainsH, h.levelsH));
+        else Hset.rec.view(Kset.rec.d, Kset.rec.n);
         n_prec = (int)h.prec_work.size();
         active_part_ptr = h.prec_part_ptr;
-        {   // split chain kernel: only when the whole launch is resident at once (one workgroup per CU)
-            int cus = 0;
-            HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, st.device));
-            const bool off = st.chain_split <= 0 || h.rep > 1;
-            if (!off && cus > 0) build_split_system(h, cus, split);
-            if (split.active && split.stage_rel.size() > 0) {
-                for (const auto& pl : split.plans)
-                    if (pl.n_stage > kWaveThreads * kWaveStage || (pl.lv[0].n + 1) * 3 > kWaveThreads * kWaveVec) split.active = false;
-            }
-            if (split.active) {
-                n_prec = (int)split.work.size();
-                active_part_ptr = split.part_ptr;
-                split_work.upload(split.work); split_items.upload(split.items); split_plans.upload(split.plans);
-                split_stage.upload(split.stage_rel.empty() ? std::vector<int32_t>(1, -1) : split.stage_rel);
-                split_xbuf.alloc((size_t)std::max(1, split.n_slots) * kSplitMaxParts * kSplitSlotDoubles); split_xbuf.zero(stream);
-                split_xflag.alloc((size_t)std::max(1, split.n_slots) * kSplitMaxParts); split_xflag.zero(stream);
-                split_epoch.alloc(split.work.size()); split_epoch.zero(stream);
-                // more than half of a CU's LDS: at most one of these workgroups per CU (the hand-off between the
-                // parts of a chain is sized and measured for that)
-                split_lds = std::max<size_t>(split.max_lds_doubles * sizeof(double), (size_t)84 * 1024);
-                HIP_CHECK(hipFuncSetAttribute((const void*)k_prec_wave<PREC_INIT>, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
-                HIP_CHECK(hipFuncSetAttribute((const void*)k_prec_wave<PREC_STEP>, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
-                int khz = 0;
-                HIP_CHECK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, st.device));
-                split_poll_limit = (unsigned long long)std::max(1, khz) * 50ull;  // 50 ms
-                if (split.max_lds_doubles * sizeof(double) > (size_t)150 * 1024) split.active = false;
-            }
-            if (!split.active) { n_prec = (int)h.prec_work.size(); active_part_ptr = h.prec_part_ptr; }
+    }
+    // split chain kernel (score_split.hpp): only when the whole launch is resident at once (one workgroup per CU)
+    void plan_split_kernel(const HostSystem& h) {
+        const bool off = st.chain_split <= 0 || h.rep > 1;
+        if (!off && n_cus > 0) build_split_system(h, n_cus, split);
+        if (split.active && split.stage_rel.size() > 0) {
+            for (const auto& pl : split.plans)
+                if (pl.n_stage > kWaveThreads * kWaveStage || (pl.lv[0].n + 1) * 3 > kWaveThreads * kWaveVec) split.active = false;
         }
+        if (split.active) {
+            n_prec = (int)split.work.size();
+            active_part_ptr = split.part_ptr;
+            split_work.upload(split.work); split_items.upload(split.items); split_plans.upload(split.plans);
+            split_stage.upload(split.stage_rel.empty() ? std::vector<int32_t>(1, -1) : split.stage_rel);
+            split_xbuf.alloc((size_t)std::max(1, split.n_slots) * kSplitMaxParts * kSplitSlotDoubles); split_xbuf.zero(stream);
+            split_xflag.alloc((size_t)std::max(1, split.n_slots) * kSplitMaxParts); split_xflag.zero(stream);
+            split_epoch.alloc(split.work.size()); split_epoch.zero(stream);
+            // more than half of a CU's LDS: at most one of these workgroups per CU (the hand-off between the
+            // parts of a chain is sized and measured for that)
+            split_lds = std::max<size_t>(split.max_lds_doubles * sizeof(double), (size_t)84 * 1024);
+            HIP_CHECK(hipFuncSetAttribute((const void*)k_prec_wave<PREC_INIT>, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
+            HIP_CHECK(hipFuncSetAttribute((const void*)k_prec_wave<PREC_STEP>, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
+            int khz = 0;
+            HIP_CHECK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, st.device));
+            split_poll_limit = (unsigned long long)std::max(1, khz) * 50ull;  // 50 ms
+            if (split.max_lds_doubles * sizeof(double) > (size_t)150 * 1024) split.active = false;
+        }
+        if (!split.active) { n_prec = (int)h.prec_work.size(); active_part_ptr = h.prec_part_ptr; }
         prec_part_ptr.upload(active_part_ptr);
-        }
         if (st.verbose)
             std::fprintf(stderr, "[score setup] chain preconditioner: %s, %d work items (%zu chains)\n",
                          split.active ? "split (one wavefront per chain part)" : "one workgroup per chain", n_prec, h.chains.size());
-        pt.mark("uploads");
+    }
+    // Which chain kernel serves the applications: the LDS budgets of the streaming kernel (k_prec), whether every chain fits
+    // k_prec_pre, and whether its coarse levels can stay in registers (k_prec_pre<.., float, true>).
+    struct ChainKernelPlan {
+        bool lds0 = true; size_t lds = 0;     // k_prec: level 0 in LDS too / its LDS bytes
+        bool pre = false; size_t pre_lds = 0;
+        bool reg = false; size_t reg_lds = 0;
+    };
+    ChainKernelPlan chain_kernel_plan(const HostSystem& h) const {
+        ChainKernelPlan pl;
         // chain vectors in LDS: level 0 (N nodes) when it fits, always the coarse levels
         int max_nodes = 0, max_all = 0;
         for (const auto& ch : h.chains) {
@@ -1992,13 +2084,13 @@ struct HipBackend {
         }
         const size_t lds_all = (16 + (size_t)max_all * std::max(1, h.bs)) * sizeof(double);
         const size_t lds_up = (16 + (size_t)max_nodes * std::max(1, h.bs)) * sizeof(double);
-        prec_lds0 = lds_all <= 144 * 1024;
-        prec_lds = prec_lds0 ? lds_all : lds_up;
+        pl.lds0 = lds_all <= 144 * 1024;
+        pl.lds = pl.lds0 ? lds_all : lds_up;
         // k_prec_pre (level 0 in registers, coarser levels staged into LDS): every chain needs
         // <= 256 level-0 runs, its vector in one chunk of loads, coarse factors that fit the
         // staging registers, and everything within the LDS budget
-        prec_pre = h.bs >= 1 && h.bs <= 4 && !h.chains.empty();
-        size_t lds_pre = 0;
+        pl.pre = h.bs >= 1 && h.bs <= 4 && !h.chains.empty();
+        size_t lds_pre = 0, lds_reg = 0;
         const int pre_chunk = h.bs >= 4 ? 8 : kPrecChunk;          // PreTile<BS>::CH
         const size_t deep_esz = h.bs >= 4 ? sizeof(float) : sizeof(double);  // coarse-level factors in LDS (k_prec_pre: LT)
         for (const auto& ch : h.chains) {
@@ -2012,34 +2104,34 @@ struct HipBackend {
             // (k_prec_pre computes a node's column as col0 + node * stride: chains with irregular columns take k_prec)
             if (ch.col_stride == 0 || ch.n_levels > kRecLevels || lv[0].nruns > kPreRunLanes || (ch.n_levels >= 2 && lv[1].N > kPrecThreads - kPreRunLanes) || (int64_t)ch.N * h.bs > (int64_t)pre_chunk * kPrecThreads ||
                 deep > (int64_t)ng * (kPrecThreads - kPreRunLanes))
-                prec_pre = false;
+                pl.pre = false;
             const ChainLevelDesc& Lend = lv[ch.n_levels - 1];
-            const size_t vec_doubles = (size_t)Lend.lds_off + (size_t)Lend.N * h.bs + 1;
-            lds_pre = std::max(lds_pre, (16 + vec_doubles + (size_t)(lv[0].nruns + 1) * h.bs) * sizeof(double) + (((size_t)deep + 1) & ~(size_t)1) * deep_esz);
+            const size_t vec_bytes = (16 + (size_t)Lend.lds_off + (size_t)Lend.N * h.bs + 1 + (size_t)(lv[0].nruns + 1) * h.bs) * sizeof(double);
+            lds_pre = std::max(lds_pre, vec_bytes + (((size_t)deep + 1) & ~(size_t)1) * deep_esz);
+            lds_reg = std::max(lds_reg, vec_bytes);
         }
-        if (lds_pre > 158 * 1024) prec_pre = false;  // 160 KiB per CU, minus the static record and slack
-        prec_pre_lds = prec_pre ? lds_pre : 0;
+        if (lds_pre > 158 * 1024) pl.pre = false;  // 160 KiB per CU, minus the static record and slack
+        pl.pre_lds = pl.pre ? lds_pre : 0;
         // register-resident coarse levels (k_prec_pre<.., float, true>): LDS holds the vectors only
-        prec_reg = prec_pre && h.deep_ok && h.bs <= 3 && st.fac_fp32 != 0;
-        if (prec_reg) {
-            size_t lds_reg = 0;
-            for (const auto& ch : h.chains) {
-                const ChainLevelDesc* lv = &h.levels[ch.level_begin];
-                const ChainLevelDesc& Lend = lv[ch.n_levels - 1];
-                lds_reg = std::max(lds_reg, (16 + (size_t)Lend.lds_off + (size_t)Lend.N * h.bs + 1 + (size_t)(lv[0].nruns + 1) * h.bs) * sizeof(double));
-            }
-            prec_reg_lds = lds_reg;
-            deep_map.upload(h.deep_map);
-        }
-        {   // does any launch fall back to the streaming kernel (k_prec)?  4 x 4 blocks: every factor set kept in double
-            const bool fallback = !prec_pre || (h.bs >= 4 && st.fac_fp32 == 0);
-            if (fallback && prec_lds > 144 * 1024) throw std::runtime_error("chain too long: more than 129 segments of 1023 nodes (132 k) for the segmented chain solver, and beyond what the streaming kernel keeps in LDS");
-        }
+        pl.reg = pl.pre && h.deep_ok && h.bs <= 3 && st.fac_fp32 != 0;
+        pl.reg_lds = pl.reg ? lds_reg : 0;
+        return pl;
+    }
+    void plan_chain_kernel(const HostSystem& h) {
+        const ChainKernelPlan pl = chain_kernel_plan(h);
+        prec_lds0 = pl.lds0; prec_lds = pl.lds;
+        prec_pre = pl.pre; prec_pre_lds = pl.pre_lds;
+        prec_reg = pl.reg; prec_reg_lds = pl.reg_lds;
+        if (prec_reg) deep_map.upload(h.deep_map);
+        // does any launch fall back to the streaming kernel (k_prec)?  4 x 4 blocks: every factor set kept in double
+        const bool fallback = !prec_pre || (h.bs >= 4 && st.fac_fp32 == 0);
+        if (fallback && prec_lds > 144 * 1024) throw std::runtime_error("chain too long: more than 129 segments of 1023 nodes (132 k) for the segmented chain solver, and beyond what the streaming kernel keeps in LDS");
         if (n_prec_chains(h)) with_bs([&](auto bs) { allow_big_lds<decltype(bs)::value>(); });
-        if (st.polish) init_polish_build(h);
-        pt.mark("polish: structure (before the band view is waited for)");
-        if (band_layout_job.valid()) {  // band view of K (score_band.hpp), laid out beside everything above
-            Kb.upload(band_layout_job.get());
+    }
+    // band view of K (score_band.hpp), laid out beside everything above
+    void adopt_band_view(HostSystem& h, PhaseTimer& pt) {
+        if (band_job.valid()) {
+            Kb.upload(band_job.get());
             if (Kb.on)
                 for (int p = 0; p < h.count; ++p) h.kkt_bytes[(size_t)p] = Kb.L.bytes[(size_t)p] + 16.0 * (double)(h.xoff[p + 1] - h.xoff[p]);
             if (st.verbose)
@@ -2048,39 +2140,36 @@ struct HipBackend {
             pt.mark("band view of K (wait + upload)");
         }
         Kset.blk_part.upload(Kb.on ? Kb.L.part_ptr : h.rbK.part_ptr);
-        {   // the iterates and partial sums a reset zeroes: ONE block (a reset is one fill instead of fifteen -- each a 4 us
-            // dispatch, on every solve)
-            auto pad = [](size_t c) { return (std::max<size_t>(1, c) + 31) & ~(size_t)31; };  // (256-byte aligned pieces)
-            const size_t nm = pad((size_t)(h.n_tot + h.m_tot)), nn = pad((size_t)h.n_tot), mm = pad((size_t)h.m_tot), cc = pad((size_t)h.count);
-            const size_t kb = pad((size_t)Kset.blocks()), np_ = pad((size_t)n_prec);
-            iter_block.alloc(2 * nm + mm + 6 * nn + cc + kb + 4 * np_);
-            double* o = iter_block.d;
-            auto take = [&](DevBuf<double>& b, size_t count, size_t padded) { b.view(o, count); o += padded; };
-            take(xtu, (size_t)(h.n_tot + h.m_tot), nm); take(xy, (size_t)(h.n_tot + h.m_tot), nm); take(s, (size_t)h.m_tot, mm);
-            take(r, (size_t)h.n_tot, nn); take(z, (size_t)h.n_tot, nn); take(p, (size_t)h.n_tot, nn); take(p2, (size_t)h.n_tot, nn);
-            take(w, (size_t)h.n_tot, nn); take(kx, (size_t)h.n_tot, nn); take(step, (size_t)h.count, cc);
-            take(pw_part, (size_t)Kset.blocks(), kb); take(rz_part0, (size_t)n_prec, np_); take(rz_part1, (size_t)n_prec, np_);
-            take(rz_meas0, (size_t)n_prec, np_); take(rz_meas1, (size_t)n_prec, np_);
-        }
-        cg_iters = st.cg_iters;
-        std::vector<int32_t> dz(h.count, 0);
-        done.upload(dz);
-        if (!h.device_setup) { K0d.upload_padded(h.K0, 64); K1d.upload_padded(h.K1, 64); }
-        {   // positions of the chain blocks and the Jacobi diagonals in K's value array: looked up on the device (binary
-            // search per block entry; on the host this was 0.5 ms of a headline create and 2.4 of an 8-trial handle's)
-            const int b2 = h.bs * h.bs;
-            Kset.posd.alloc(h.node_col.size() * (size_t)b2); Kset.poss.alloc(h.node_col.size() * (size_t)b2); Kset.diagpos.alloc(h.diag_cols.size());
-            DevBuf<int32_t> prevc, drow;
-            prevc.upload(h.node_prev_owned); drow.upload(h.diag_row0);
-            HPosArgs pa{};
-            pa.Hptr = K.ptr.d; pa.Hcol = K.col.d; pa.node_col = node_col.d; pa.prev_col = prevc.d;
-            pa.n_nodes = (int64_t)h.node_col.size(); pa.bs = h.bs; pa.pos_diag = Kset.posd.d; pa.pos_sub = Kset.poss.d;
-            pa.diag_cols = drow.d; pa.n_diag = (int64_t)h.diag_cols.size(); pa.diag_pos = Kset.diagpos.d;
-            const int64_t npos = std::max<int64_t>(pa.n_nodes * b2, pa.n_diag);
-            if (npos > 0) hipLaunchKernelGGL(k_hb_positions, dim3((unsigned)((npos + 255) / 256)), dim3(256), 0, stream, pa);
-            HIP_CHECK(hipGetLastError());
-        }
-        join_init(h);
+    }
+    // the iterates and partial sums a reset zeroes: ONE block of 256-byte aligned pieces (a reset is one fill instead of
+    // fifteen -- each a 4 us dispatch, on every solve)
+    void carve_iterates(const HostSystem& h) {
+        const size_t nm = (size_t)(h.n_tot + h.m_tot), nn = (size_t)h.n_tot, mm = (size_t)h.m_tot, cc = (size_t)h.count;
+        const size_t kb = (size_t)Kset.blocks(), np_ = (size_t)n_prec;
+        struct Piece { DevBuf<double>& buf; size_t count; Region<double> at; };
+        Piece pieces[] = {{xtu, nm}, {xy, nm}, {s, mm}, {r, nn}, {z, nn}, {p, nn}, {p2, nn}, {w, nn}, {kx, nn}, {step, cc},
+                          {pw_part, kb}, {rz_part0, np_}, {rz_part1, np_}, {rz_meas0, np_}, {rz_meas1, np_}};
+        Slab block;
+        for (Piece& pc : pieces) pc.at = block.add<double>(pc.count);
+        iter_block.alloc(block.bytes / sizeof(double));
+        for (Piece& pc : pieces) pc.buf.view(pc.at.in(iter_block.d), pc.count);
+    }
+    // positions of the chain blocks and the Jacobi diagonals in K's value array: looked up on the device (binary
+    // search per block entry; on the host this was 0.5 ms of a headline create and 2.4 of an 8-trial handle's)
+    void chain_positions(const HostSystem& h) {
+        const int b2 = h.bs * h.bs;
+        Kset.posd.alloc(h.node_col.size() * (size_t)b2); Kset.poss.alloc(h.node_col.size() * (size_t)b2); Kset.diagpos.alloc(h.diag_cols.size());
+        DevBuf<int32_t> prevc, drow;
+        prevc.upload(h.node_prev_owned); drow.upload(h.diag_row0);
+        HPosArgs pa{};
+        pa.Hptr = K.ptr.d; pa.Hcol = K.col.d; pa.node_col = node_col.d; pa.prev_col = prevc.d;
+        pa.n_nodes = (int64_t)h.node_col.size(); pa.bs = h.bs; pa.pos_diag = Kset.posd.d; pa.pos_sub = Kset.poss.d;
+        pa.diag_cols = drow.d; pa.n_diag = (int64_t)h.diag_cols.size(); pa.diag_pos = Kset.diagpos.d;
+        const int64_t npos = std::max<int64_t>(pa.n_nodes * b2, pa.n_diag);
+        if (npos > 0) hipLaunchKernelGGL(k_hb_positions, dim3((unsigned)((npos + 255) / 256)), dim3(256), 0, stream, pa);
+        HIP_CHECK(hipGetLastError());
+    }
+    void alloc_factors(const HostSystem& h) {
         // (separator slots of the spike region are never written, nor used: zeroed once, with the float copy, in one fill)
         ZeroGroup zfac;
         zfac.add(Kset.fac, Kset.fac_doubles);
@@ -2102,49 +2191,45 @@ struct HipBackend {
         q_work.alloc((size_t)std::max<int64_t>(1, h.scratch_nodes) * 2 * std::max(1, h.bs * h.bs));
         plan_factor_lds();
         derive_rho_data(false);
-        pt.mark("allocations + rho data (device)");
-        if (st.polish) init_polish(h);
-        link_init(h, probs, graphs);
-        pt.mark("polish setup");
-        {   // the report arena (see `rep`) and the control block (see `ctl`)
-            const size_t n_pres = (size_t)std::max(1, n_cone_blocks) * kPartStride, n_dres = (size_t)G2.nblocks * kPartStride;
-            const size_t n_int = (2 * (size_t)h.count + 1) / 2;  // 2 * count int32
-            const size_t n_meas = 2 * (size_t)std::max(1, n_prec);
-            const size_t total = n_pres + n_dres + n_fpart + n_gd + n_meas + 2 * n_int + 1;
-            h_rep_bytes = total * sizeof(double);
-            h_rep = (double*)block_cache().take(h_rep_bytes, st.device, true);
-            std::memset(h_rep, 0, total * sizeof(double));
-            double* d_rep = nullptr;
-            HIP_CHECK(hipHostGetDevicePointer((void**)&d_rep, h_rep, 0));
-            rep.view(d_rep, total);
-            rep_dres_off = n_pres;
-            size_t o = 0;
-            pres_part.view(d_rep + o, n_pres); h_pres = h_rep + o; o += n_pres;
-            dres_part.view(d_rep + o, n_dres); h_dres = h_rep + o; o += n_dres;
-            q_fpart.view(d_rep + o, n_fpart); h_newton = h_rep + o; o += n_fpart;
-            q_gd.view(d_rep + o, n_gd); h_gd = h_rep + o; o += n_gd;
-            h_meas = h_rep + o; d_meas = d_rep + o; o += n_meas;
-            h_gate = (int32_t*)(h_rep + o); d_gate_host = (int32_t*)(d_rep + o); o += n_int;
-            h_gate_live = (int32_t*)(h_rep + o); d_gate_live = (int32_t*)(d_rep + o); o += n_int;  // (written by pcg_gate as the PCG runs)
-            h_seq = (unsigned long long*)(h_rep + o); d_seq = (unsigned long long*)(d_rep + o);
-            // device-resident words the kernels read: gate flags and counts, control block
-            q_pcgdone.alloc(2 * (size_t)h.count);
-            q_pcgdone.zero(stream);
-            q_gate_used.view(q_pcgdone.d + h.count, h.count);
-            ctl.alloc(2 * (size_t)h.count + (3 * (size_t)h.count + 1) / 2);  // [step | tol2 | skip, reref, fskip]
-            q_step.view(ctl.d, h.count);
-            q_gate_tol2.view(ctl.d + h.count, h.count);
-            q_skip.view((int32_t*)(ctl.d + 2 * (size_t)h.count), h.count);
-            q_reref.view((int32_t*)(ctl.d + 2 * (size_t)h.count) + h.count, h.count);
-            q_fskip.view((int32_t*)(ctl.d + 2 * (size_t)h.count) + 2 * (size_t)h.count, h.count);
-        }
-        reset();
-        pt.mark("reset");
-        HIP_CHECK(sync_stream(stream));
-        setup_tmp.release_all();  // (nothing in flight reads the setup's scratch any more)
-        for (auto& pb : setup_pinned) block_cache().give(pb.first, pb.second, st.device, true);
-        setup_pinned.clear();
-        pt.mark("staged uploads: drain");
+    }
+    // The report arena (see `rep`): ONE host-mapped allocation packed in doubles,
+    //   [pres | dres | fpart | gd | meas | gate | gate_live | seq];
+    // the device view and the host view of a piece come from the same Region.  And the control block (see `ctl`):
+    //   [step | tol2 | skip, reref, fskip], two doubles and three 32-bit words per problem.
+    void carve_report_and_control(const HostSystem& h) {
+        const size_t count = (size_t)h.count;
+        const size_t n_pres = (size_t)std::max(1, n_cone_blocks) * kPartStride, n_dres = (size_t)G2.nblocks * kPartStride;
+        const size_t n_meas = 2 * (size_t)std::max(1, n_prec);
+        Slab arena_r(sizeof(double), 0);
+        const Region<double> pres = arena_r.add<double>(n_pres), dres = arena_r.add<double>(n_dres), fpart = arena_r.add<double>(n_fpart),
+                             gd = arena_r.add<double>(n_gd), meas = arena_r.add<double>(n_meas);
+        const Region<int32_t> gate = arena_r.add<int32_t>(2 * count), gate_live = arena_r.add<int32_t>(2 * count);  // (gate_live: written by pcg_gate as the PCG runs)
+        const Region<unsigned long long> seq = arena_r.add<unsigned long long>(1);
+        h_rep_bytes = arena_r.bytes;
+        h_rep = (double*)block_cache().take(h_rep_bytes, st.device, true);
+        std::memset(h_rep, 0, h_rep_bytes);
+        double* d_rep = nullptr;
+        HIP_CHECK(hipHostGetDevicePointer((void**)&d_rep, h_rep, 0));
+        rep.view(d_rep, h_rep_bytes / sizeof(double));
+        rep_dres_off = dres.off / sizeof(double);
+        pres_part.view(pres.in(d_rep), n_pres); h_pres = pres.in(h_rep);
+        dres_part.view(dres.in(d_rep), n_dres); h_dres = dres.in(h_rep);
+        q_fpart.view(fpart.in(d_rep), n_fpart); h_newton = fpart.in(h_rep);
+        q_gd.view(gd.in(d_rep), n_gd); h_gd = gd.in(h_rep);
+        d_meas = meas.in(d_rep); h_meas = meas.in(h_rep);
+        d_gate_host = gate.in(d_rep); h_gate = gate.in(h_rep);
+        d_gate_live = gate_live.in(d_rep); h_gate_live = gate_live.in(h_rep);
+        d_seq = seq.in(d_rep); h_seq = seq.in(h_rep);
+        // device-resident words the kernels read: gate flags and counts, control block
+        q_pcgdone.alloc(2 * count);
+        q_pcgdone.zero(stream);
+        q_gate_used.view(q_pcgdone.d + count, count);
+        Slab control(sizeof(int32_t), 0);
+        const Region<double> c_step = control.add<double>(count), c_tol2 = control.add<double>(count);
+        const Region<int32_t> c_skip = control.add<int32_t>(count), c_reref = control.add<int32_t>(count), c_fskip = control.add<int32_t>(count);
+        ctl.alloc((control.bytes + sizeof(double) - 1) / sizeof(double));
+        q_step.view(c_step.in(ctl.d), count); q_gate_tol2.view(c_tol2.in(ctl.d), count);
+        q_skip.view(c_skip.in(ctl.d), count); q_reref.view(c_reref.in(ctl.d), count); q_fskip.view(c_fskip.in(ctl.d), count);
     }
 
     // Everything that depends on the penalties, on the device and in stream order: K = K0 + rho K1 on
@@ -3180,16 +3265,28 @@ struct HipBackend {
     // The Newton matrix's pattern, P on it and the contribution lists, on the device (score_polish_device.hpp); the host keeps
     // the row pointers (tiles, per-problem entry ranges).  false: the program's cones are not laid out the way the kernels
     // assume -- the caller builds on the host.
+    struct HBuildScratch {  // scratch of the build: in an arena of its own, back to the block cache when the build is over
+        DevBuf<long long> cnt, off, result;
+        DevBuf<unsigned long long> key0, key1, flag, flag_s;
+        DevBuf<uint32_t> idx0, idx1;
+        DevBuf<int32_t> rcone, rab, hrow, long_ent, prev_col, long_rows, n_long_rows;
+        DevBuf<double> rcoef;
+        DevBuf<unsigned char> scan_tmp;
+        RowSort rs;  // (every row's records sorted where they lie: sort_rows)
+        int64_t rec_max = 0, long_cap = 0;
+        size_t flag_scan_bytes = 0;  // rocprim's scratch for the scan of the flags
+        int bits = 1;
+        static constexpr int long_max = 1 << 16;
+    };
     bool build_polish_on_device(const HostSystem& h) {
-        const int T = Q.T, D1 = T + 1, bs = h.bs, b2 = bs * bs;
+        const int T = Q.T, D1 = T + 1, b2 = h.bs * h.bs;
         const int64_t n = h.n_tot;
         PhaseTimer pt(st.verbose != 0);
         for (size_t k = 0; k < h.cone_row.size(); ++k)
             if ((int64_t)h.cone_row[k] != (int64_t)k * D1) return false;
         int64_t con_max = 0;
-        const int64_t rec_max = polish_record_bound(h, T, &con_max, h.device_setup ? nnzP_full : -1);
+        const int64_t rec_max = polish_record_bound(h, T, &con_max, source == MatrixSource::device ? nnzP_full : -1);
         if (rec_max + 64 >= ((int64_t)1 << 31)) return false;
-        const int long_max = 1 << 16;
         // what stays: pattern, P on it, lists, positions (the handle's arena)
         Hm.ptr.alloc((size_t)n + 1);
         {
@@ -3201,211 +3298,204 @@ struct HipBackend {
         q_ccone.alloc((size_t)std::max<int64_t>(1, con_max)); q_cab.alloc((size_t)std::max<int64_t>(1, con_max)); q_ccoef.alloc((size_t)std::max<int64_t>(1, con_max));
         Hset.posd.alloc(h.node_col.size() * (size_t)b2); Hset.poss.alloc(h.node_col.size() * (size_t)b2); Hset.diagpos.alloc(h.diag_cols.size());
         std::vector<long long> res(3, 0);
-        std::vector<int32_t> longs((size_t)long_max);
+        std::vector<int32_t> longs((size_t)HBuildScratch::long_max);
         Q.Hm.nrows = Q.Hm.ncols = n;
         Q.Hm.ptr.assign((size_t)n + 1, 0);
         {
-            // scratch of the build: its own arena, back to the block cache when the build is over
             DevArena tmp;
             tmp.dev = st.device;
-            struct Swap {
-                DevArena* keep;
-                explicit Swap(DevArena* a) : keep(tl_arena) { tl_arena = a; }
-                ~Swap() { tl_arena = keep; }
-            } swap(&tmp);
+            ArenaSwap swap(&tmp);
             try {
-            DevBuf<long long> cnt, off, result;
-            DevBuf<unsigned long long> key0, key1, flag, flag_s;
-            DevBuf<uint32_t> idx0, idx1;
-            DevBuf<int32_t> rcone, rab, hrow, long_ent, prev_col;
-            DevBuf<double> rcoef;
-            cnt.alloc((size_t)n + 1); off.alloc((size_t)n + 1); result.alloc(3);
-            key0.alloc((size_t)rec_max); key1.alloc((size_t)rec_max); idx0.alloc((size_t)rec_max); idx1.alloc((size_t)rec_max);
-            flag.alloc((size_t)rec_max); flag_s.alloc((size_t)rec_max);
-            rcone.alloc((size_t)rec_max); rab.alloc((size_t)rec_max); rcoef.alloc((size_t)rec_max); hrow.alloc((size_t)rec_max);
-            long_ent.alloc((size_t)long_max);
-            std::optional<UploadBatch> fills;  // (counters, the sort's segment list, the predecessor table: one fill launch, one transfer)
-            fills.emplace();
-            fill_zero_async(result.d, 3 * sizeof(long long), stream);
-            {
-                std::vector<int32_t> pc(h.node_col.size(), -1);  // column of the chain predecessor
-                for (const auto& ch : h.chains)
-                    for (int i = 1; i < ch.N; ++i) pc[(size_t)ch.node_begin + i] = h.node_col[(size_t)ch.node_begin + i - 1];
-                prev_col.upload(pc);
-            }
-            HBuildArgs a{};
-            a.n = n; a.T = T;
-            a.g2_ptr = G2.ptr.d; a.g2_split = G2.split.d; a.g2_col = G2.col.d; a.g2_val = G2.val.d;
-            a.A_ptr = A_ptr.d; a.A_col = A_col.d; a.A_val = A_val.d; a.is_head = q_ishead.d;
-            a.rec_max = rec_max; a.key = key0.d; a.idx = idx0.d; a.rcone = rcone.d; a.rab = rab.d; a.rcoef = rcoef.d;
-            const unsigned grec = (unsigned)((rec_max + 255) / 256);
-            // (eight lanes per row; the listed long rows -- landmark rows -- a wavefront each)
-            const int64_t long_cap = rec_max / kLongRowEntries + 1;
-            DevBuf<int32_t> long_rows, n_long_rows;
-            long_rows.alloc((size_t)long_cap); n_long_rows.alloc(1);
-            fill_zero_async(n_long_rows.d, sizeof(int32_t), stream);
-            int bits = 1;
-            while (((int64_t)1 << bits) <= n) ++bits;  // (the sentinel row n sorts last)
-            RowSort rs;  // (every row's records sorted where they lie: sort_rows)
-            sort_rows_plan(rs, n, rec_max, bits, flag.d, flag_s.d);
-            fills.reset();
-            hipLaunchKernelGGL(k_row_classify, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const int32_t*)G2.ptr.d, n, long_rows.d, n_long_rows.d);
-            const unsigned g8 = (unsigned)((n + 31) / 32), g64 = (unsigned)((long_cap + 3) / 4);
-            a.long_rows = long_rows.d; a.n_long_rows = n_long_rows.d;
-            a.rec_cnt = cnt.d;
-            hipLaunchKernelGGL(k_hb_count<8>, dim3(g8), dim3(256), 0, stream, a);
-            hipLaunchKernelGGL(k_hb_count<64>, dim3(g64), dim3(256), 0, stream, a);
-            size_t tb = 0, tb2 = rs.bytes, tb3 = 0;
-            HIP_CHECK(rocprim::exclusive_scan(nullptr, tb, cnt.d, off.d, (long long)0, (size_t)n + 1, rocprim::plus<long long>(), stream));
-            HIP_CHECK(rocprim::inclusive_scan(nullptr, tb3, flag.d, flag_s.d, (size_t)rec_max, rocprim::plus<unsigned long long>(), stream));
-            DevBuf<unsigned char> scratch;
-            scratch.alloc(std::max(tb, std::max(tb2, tb3)) + 256);
-            HIP_CHECK(rocprim::exclusive_scan((void*)scratch.d, tb, cnt.d, off.d, (long long)0, (size_t)n + 1, rocprim::plus<long long>(), stream));
-            a.rec_cnt = off.d;
-            hipLaunchKernelGGL(k_hb_expand<8>, dim3(g8), dim3(256), 0, stream, a);
-            hipLaunchKernelGGL(k_hb_expand<64>, dim3(g64), dim3(256), 0, stream, a);
-            hipLaunchKernelGGL(k_hb_pad, dim3(grec), dim3(256), 0, stream, a);
-            sort_rows(rs, n, rec_max, bits, key0.d, key1.d, idx1.d, flag.d, flag_s.d, off.d, (void*)scratch.d);
-            HScatterArgs sa{};
-            sa.n = n; sa.rec_max = rec_max; sa.key = key1.d; sa.idx = idx1.d; sa.rcone = rcone.d; sa.rab = rab.d; sa.rcoef = rcoef.d;
-            sa.flag = flag.d; sa.Hcol = Hm.col.d; sa.Hrow = hrow.d; sa.Pon = q_Pon.d; sa.cptr = q_cptr.d;
-            sa.ccone = q_ccone.d; sa.cab = q_cab.d; sa.ccoef = q_ccoef.d; sa.Hptr = Hm.ptr.d; sa.result = result.d;
-            sa.long_ent = long_ent.d; sa.long_max = long_max; sa.diag_reg = kPolishDiagReg;
-            hipLaunchKernelGGL(k_hb_flags, dim3(grec), dim3(256), 0, stream, sa);
-            HIP_CHECK(rocprim::inclusive_scan((void*)scratch.d, tb3, flag.d, flag_s.d, (size_t)rec_max, rocprim::plus<unsigned long long>(), stream));
-            sa.flag = flag_s.d;
-            hipLaunchKernelGGL(k_hb_scatter, dim3(grec), dim3(256), 0, stream, sa);
-            hipLaunchKernelGGL(k_hb_rows, dim3(grec), dim3(256), 0, stream, sa);
-            HPosArgs pa{};
-            pa.Hptr = Hm.ptr.d; pa.Hcol = Hm.col.d; pa.node_col = node_col.d; pa.prev_col = prev_col.d;
-            pa.n_nodes = (int64_t)h.node_col.size(); pa.bs = bs; pa.pos_diag = Hset.posd.d; pa.pos_sub = Hset.poss.d;
-            pa.diag_cols = diag_cols.d; pa.n_diag = (int64_t)h.diag_cols.size(); pa.diag_pos = Hset.diagpos.d;
-            const int64_t npos = std::max<int64_t>(pa.n_nodes * b2, pa.n_diag);
-            if (npos > 0) hipLaunchKernelGGL(k_hb_positions, dim3((unsigned)((npos + 255) / 256)), dim3(256), 0, stream, pa);
-            HIP_CHECK(hipGetLastError());
-            pt.mark("    polish (device): buffers + launches");
-            HIP_CHECK(hipMemcpyAsync(res.data(), result.d, 3 * sizeof(long long), hipMemcpyDeviceToHost, stream));
-            staged_d2h(Q.Hm.ptr.data(), Hm.ptr.d, ((size_t)n + 1) * sizeof(int32_t), stream);
-            staged_d2h(longs.data(), long_ent.d, (size_t)long_max * sizeof(int32_t), stream);
-            HIP_CHECK(sync_stream(stream));
-            pt.mark("    polish (device): kernels + row pointers back");
+                HBuildScratch S;
+                S.rec_max = rec_max;
+                hbuild_scratch(h, S);
+                hbuild_records(h, S);
+                hbuild_scatter(h, S);
+                pt.mark("    polish (device): buffers + launches");
+                HIP_CHECK(hipMemcpyAsync(res.data(), S.result.d, 3 * sizeof(long long), hipMemcpyDeviceToHost, stream));
+                staged_d2h(Q.Hm.ptr.data(), Hm.ptr.d, ((size_t)n + 1) * sizeof(int32_t), stream);
+                staged_d2h(longs.data(), S.long_ent.d, longs.size() * sizeof(int32_t), stream);
+                HIP_CHECK(sync_stream(stream));
+                pt.mark("    polish (device): kernels + row pointers back");
             } catch (...) {
                 (void)sync_stream(stream);  // (nothing in flight may touch the scratch once it goes back to the cache)
                 throw;
             }
         }
-        if (res[2] > long_max) return false;  // (more long entries than the device list holds: the host loop has no such limit)
+        if (res[2] > HBuildScratch::long_max) return false;  // (more long entries than the device list holds: the host loop has no such limit)
         hm_nnz = res[0];
         longs.resize((size_t)res[2]);
-        std::sort(longs.begin(), longs.end());
-        Q.long_ent = longs;
-        Q.long_prob.assign(longs.size(), 0);
-        {
-            int pr = 0;
-            for (size_t x = 0; x < longs.size(); ++x) {
-                while (pr + 1 < h.count && (int64_t)longs[x] >= (int64_t)Q.Hm.ptr[(size_t)h.xoff[pr + 1]]) ++pr;
-                Q.long_prob[x] = pr;
-            }
-        }
-        Q.rbH = make_rowblocks(Q.Hm, plain_segments(h.xoff), h.count);
-        Hm.adopt_tiles(Q.Hm, Q.rbH);
+        hbuild_adopt(h, longs);
         pt.mark("    polish (device): tiles");
         Q.available = true;
         return true;
     }
+    // the scratch buffers; counters, the sort's segment list and the predecessor table in one fill launch and one transfer
+    void hbuild_scratch(const HostSystem& h, HBuildScratch& S) {
+        const size_t n = (size_t)h.n_tot, rec = (size_t)S.rec_max;
+        S.cnt.alloc(n + 1); S.off.alloc(n + 1); S.result.alloc(3);
+        S.key0.alloc(rec); S.key1.alloc(rec); S.idx0.alloc(rec); S.idx1.alloc(rec);
+        S.flag.alloc(rec); S.flag_s.alloc(rec);
+        S.rcone.alloc(rec); S.rab.alloc(rec); S.rcoef.alloc(rec); S.hrow.alloc(rec);
+        S.long_ent.alloc((size_t)HBuildScratch::long_max);
+        UploadBatch fills;
+        fill_zero_async(S.result.d, 3 * sizeof(long long), stream);
+        {
+            std::vector<int32_t> pc(h.node_col.size(), -1);  // column of the chain predecessor
+            for (const auto& ch : h.chains)
+                for (int i = 1; i < ch.N; ++i) pc[(size_t)ch.node_begin + i] = h.node_col[(size_t)ch.node_begin + i - 1];
+            S.prev_col.upload(pc);
+        }
+        // (eight lanes per row; the listed long rows -- landmark rows -- a wavefront each)
+        S.long_cap = S.rec_max / kLongRowEntries + 1;
+        S.long_rows.alloc((size_t)S.long_cap); S.n_long_rows.alloc(1);
+        fill_zero_async(S.n_long_rows.d, sizeof(int32_t), stream);
+        while (((int64_t)1 << S.bits) <= h.n_tot) ++S.bits;  // (the sentinel row n sorts last)
+        sort_rows_plan(S.rs, h.n_tot, S.rec_max, S.bits, S.flag.d, S.flag_s.d);
+    }
+    // a record per contribution (count, scan, expand), every row's records sorted
+    void hbuild_records(const HostSystem& h, HBuildScratch& S) {
+        const int64_t n = h.n_tot;
+        HBuildArgs a{};
+        a.n = n; a.T = Q.T;
+        a.g2_ptr = G2.ptr.d; a.g2_split = G2.split.d; a.g2_col = G2.col.d; a.g2_val = G2.val.d;
+        a.A_ptr = A_ptr.d; a.A_col = A_col.d; a.A_val = A_val.d; a.is_head = q_ishead.d;
+        a.rec_max = S.rec_max; a.key = S.key0.d; a.idx = S.idx0.d; a.rcone = S.rcone.d; a.rab = S.rab.d; a.rcoef = S.rcoef.d;
+        hipLaunchKernelGGL(k_row_classify, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const int32_t*)G2.ptr.d, n, S.long_rows.d, S.n_long_rows.d);
+        const unsigned g8 = (unsigned)((n + 31) / 32), g64 = (unsigned)((S.long_cap + 3) / 4);
+        a.long_rows = S.long_rows.d; a.n_long_rows = S.n_long_rows.d;
+        a.rec_cnt = S.cnt.d;
+        hipLaunchKernelGGL(k_hb_count<8>, dim3(g8), dim3(256), 0, stream, a);
+        hipLaunchKernelGGL(k_hb_count<64>, dim3(g64), dim3(256), 0, stream, a);
+        size_t tb = 0;
+        HIP_CHECK(rocprim::exclusive_scan(nullptr, tb, S.cnt.d, S.off.d, (long long)0, (size_t)n + 1, rocprim::plus<long long>(), stream));
+        HIP_CHECK(rocprim::inclusive_scan(nullptr, S.flag_scan_bytes, S.flag.d, S.flag_s.d, (size_t)S.rec_max, rocprim::plus<unsigned long long>(), stream));
+        S.scan_tmp.alloc(std::max(tb, std::max(S.rs.bytes, S.flag_scan_bytes)) + 256);
+        HIP_CHECK(rocprim::exclusive_scan((void*)S.scan_tmp.d, tb, S.cnt.d, S.off.d, (long long)0, (size_t)n + 1, rocprim::plus<long long>(), stream));
+        a.rec_cnt = S.off.d;
+        hipLaunchKernelGGL(k_hb_expand<8>, dim3(g8), dim3(256), 0, stream, a);
+        hipLaunchKernelGGL(k_hb_expand<64>, dim3(g64), dim3(256), 0, stream, a);
+        hipLaunchKernelGGL(k_hb_pad, dim3((unsigned)((S.rec_max + 255) / 256)), dim3(256), 0, stream, a);
+        sort_rows(S.rs, n, S.rec_max, S.bits, S.key0.d, S.key1.d, S.idx1.d, S.flag.d, S.flag_s.d, S.off.d, (void*)S.scan_tmp.d);
+    }
+    // the sorted records into the pattern, P on it and the contribution lists; the chain and Jacobi positions
+    void hbuild_scatter(const HostSystem& h, HBuildScratch& S) {
+        const unsigned grec = (unsigned)((S.rec_max + 255) / 256);
+        HScatterArgs sa{};
+        sa.n = h.n_tot; sa.rec_max = S.rec_max; sa.key = S.key1.d; sa.idx = S.idx1.d; sa.rcone = S.rcone.d; sa.rab = S.rab.d; sa.rcoef = S.rcoef.d;
+        sa.flag = S.flag.d; sa.Hcol = Hm.col.d; sa.Hrow = S.hrow.d; sa.Pon = q_Pon.d; sa.cptr = q_cptr.d;
+        sa.ccone = q_ccone.d; sa.cab = q_cab.d; sa.ccoef = q_ccoef.d; sa.Hptr = Hm.ptr.d; sa.result = S.result.d;
+        sa.long_ent = S.long_ent.d; sa.long_max = HBuildScratch::long_max; sa.diag_reg = kPolishDiagReg;
+        hipLaunchKernelGGL(k_hb_flags, dim3(grec), dim3(256), 0, stream, sa);
+        HIP_CHECK(rocprim::inclusive_scan((void*)S.scan_tmp.d, S.flag_scan_bytes, S.flag.d, S.flag_s.d, (size_t)S.rec_max, rocprim::plus<unsigned long long>(), stream));
+        sa.flag = S.flag_s.d;
+        hipLaunchKernelGGL(k_hb_scatter, dim3(grec), dim3(256), 0, stream, sa);
+        hipLaunchKernelGGL(k_hb_rows, dim3(grec), dim3(256), 0, stream, sa);
+        const int b2 = h.bs * h.bs;
+        HPosArgs pa{};
+        pa.Hptr = Hm.ptr.d; pa.Hcol = Hm.col.d; pa.node_col = node_col.d; pa.prev_col = S.prev_col.d;
+        pa.n_nodes = (int64_t)h.node_col.size(); pa.bs = h.bs; pa.pos_diag = Hset.posd.d; pa.pos_sub = Hset.poss.d;
+        pa.diag_cols = diag_cols.d; pa.n_diag = (int64_t)h.diag_cols.size(); pa.diag_pos = Hset.diagpos.d;
+        const int64_t npos = std::max<int64_t>(pa.n_nodes * b2, pa.n_diag);
+        if (npos > 0) hipLaunchKernelGGL(k_hb_positions, dim3((unsigned)((npos + 255) / 256)), dim3(256), 0, stream, pa);
+        HIP_CHECK(hipGetLastError());
+    }
+    // host side of the device build: the long entries in order with their problems, the tiles of the Newton matrix
+    void hbuild_adopt(const HostSystem& h, std::vector<int32_t>& longs) {
+        std::sort(longs.begin(), longs.end());
+        Q.long_ent = longs;
+        Q.long_prob.assign(longs.size(), 0);
+        int pr = 0;
+        for (size_t x = 0; x < longs.size(); ++x) {
+            while (pr + 1 < h.count && (int64_t)longs[x] >= (int64_t)Q.Hm.ptr[(size_t)h.xoff[pr + 1]]) ++pr;
+            Q.long_prob[x] = pr;
+        }
+        Q.rbH = make_rowblocks(Q.Hm, plain_segments(h.xoff), h.count);
+        Hm.adopt_tiles(Q.Hm, Q.rbH);
+    }
+    // The device build, or false where its scratch (~60 bytes per record, sized by an upper bound) did not fit: the host loop
+    // needs none of it.  Anything else is a real failure.
+    bool try_build_polish_on_device(const HostSystem& h) {
+        try {
+            return build_polish_on_device(h);
+        } catch (const std::exception& e) {
+            if (std::strstr(e.what(), "hipMalloc") == nullptr) throw;
+            (void)hipGetLastError();
+            return false;
+        }
+    }
 
     // Two parts.  init_polish_build: the structure of the Newton system (pattern, contribution lists, cone data) -- on the device it
     // ends in a round trip, so init() starts it BEFORE it waits for the host's band layout of K (which needs none of it; the wait
-    // was 0.6 ms of a 4.2 ms headline create).  init_polish: buffers, tiles, band view of H, second level -- after K's data.
-    bool polish_built_on_device = false;
-    void init_polish_build(const HostSystem& h) {
-        polish_built_on_device = false;
+    // was 0.6 ms of a 4.2 ms headline create); true: built on the device.  init_polish: buffers, tiles, second level -- after K's data.
+    bool init_polish_build(const HostSystem& h) {
         PhaseTimer pt(st.verbose != 0);
         if (polish_build.valid()) polish_build.get();  // (rethrows what build_polish threw)
         pt.mark("  polish: host structures (wait)");
-        bool on_device = false;
-        if (h.device_setup) {
-            // the per-cone structure (polish_structure) from the device matrices: what the host can see -- uniform second-order
-            // cones of 2-4 rows -- is checked here, the head-variable conditions by k_polish_structure
-            Q = PolishData();
-            const size_t nc = h.cone_row.size();
-            const int T = nc ? h.cone_dim[0] - 1 : 0;
-            bool ok = nc > 0 && h.m_tot > 0 && T >= 1 && T <= kPolishMaxTail;
-            for (size_t k = 0; k < nc && ok; ++k) ok = h.cone_type[k] == 1 && h.cone_dim[k] - 1 == T;
-            if (!ok) return;
-            Q.T = T;
-            q_head.alloc(nc); q_aabs.alloc(nc); q_ck.alloc(nc); q_theta.alloc(nc); q_xstar.alloc(nc);
-            DevBuf<int32_t> bad;
-            {
-                ZeroGroup zg;
-                zg.add(q_ishead, (size_t)h.n_tot); zg.add(bad, 1);
-                zg.commit(stream);
-            }
-            PStructArgs pa{};
-            pa.ncones = (int64_t)nc; pa.n = h.n_tot; pa.T = T;
-            pa.cone_row = cone_row.d; pa.cone_dim = cone_dim.d; pa.cone_type = cone_type.d;
-            pa.A_ptr = A_ptr.d; pa.A_col = A_col.d; pa.A_val = A_val.d; pa.b = b.d; pa.q = q.d;
-            pa.g2_ptr = G2.ptr.d; pa.g2_split = G2.split.d; pa.g2_col = G2.col.d; pa.g2_val = G2.val.d;
-            pa.head_col = q_head.d; pa.is_head = q_ishead.d; pa.a_abs = q_aabs.d; pa.ck = q_ck.d; pa.theta = q_theta.d; pa.xstar = q_xstar.d;
-            pa.bad = bad.d;
-            hipLaunchKernelGGL(k_polish_structure, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, stream, pa);
-            std::vector<int32_t> bad_h(1, 0);
-            HIP_CHECK(hipMemcpyAsync(bad_h.data(), bad.d, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-            try {
-                on_device = build_polish_on_device(h);  // (its synchronisation brings the verdict back too)
-            } catch (const std::exception& e) {
-                if (std::strstr(e.what(), "hipMalloc") == nullptr) throw;
-                (void)hipGetLastError();
-                on_device = false;
-            }
-            pt.mark("  polish: structure + pattern + lists on the device");
-            HIP_CHECK(sync_stream(stream));
-            if (!on_device || bad_h[0] != 0) {  // (not the SCORE structure, or a build the device declined: ADMM alone)
-                Q.available = false;
-                return;
-            }
-        } else
-        if (polish_on_device && Q.T > 0) {
-            q_head.upload(Q.head_col); q_ishead.upload(Q.is_head); q_aabs.upload(Q.a_abs); q_ck.upload(Q.ck);
-            q_theta.upload(Q.theta); q_xstar.upload(Q.xstar);
-            try {
-                on_device = build_polish_on_device(h);
-            } catch (const std::exception& e) {
-                // the scratch of the device build (~60 bytes per record, sized by an upper bound) did not fit: the host loop
-                // needs none of it.  Anything else is a real failure.
-                if (std::strstr(e.what(), "hipMalloc") == nullptr) throw;
-                (void)hipGetLastError();
-                on_device = false;
-            }
-            pt.mark("  polish: pattern + lists on the device");
-            if (!on_device) {  // (cones not laid out row after row, more than 2^32 records: the host loop takes over)
-                polish_on_device = false;
-                build_polish(h, Q, st.verbose != 0, false);
-            }
+        if (source == MatrixSource::device) return polish_structure_on_device(h, pt);
+        if (!polish_on_device || Q.T <= 0) return false;
+        q_head.upload(Q.head_col); q_ishead.upload(Q.is_head); q_aabs.upload(Q.a_abs); q_ck.upload(Q.ck);
+        q_theta.upload(Q.theta); q_xstar.upload(Q.xstar);
+        const bool on_device = try_build_polish_on_device(h);
+        pt.mark("  polish: pattern + lists on the device");
+        if (!on_device) {  // (cones not laid out row after row, more than 2^32 records: the host loop takes over)
+            polish_on_device = false;
+            build_polish(h, Q, st.verbose != 0);
         }
-        polish_built_on_device = on_device;
+        return on_device;
     }
-    void init_polish(const HostSystem& h) {
-        PhaseTimer pt(st.verbose != 0);
-        const bool on_device = polish_built_on_device;
-        if (!Q.available) return;
-        if (!on_device) {
-            hm_nnz = (int64_t)Q.Hm.col.size();
-            UploadBatch ub;
-            Hm.upload(Q.Hm, Q.rbH, nullptr, false);
-            q_Pon.upload(Q.Pon); q_ccoef.upload(Q.ccoef); q_cptr.upload(Q.cptr); q_ccone.upload(Q.ccone); q_cab.upload(Q.cab);
-            q_head.upload(Q.head_col); q_ishead.upload(Q.is_head); q_aabs.upload(Q.a_abs); q_ck.upload(Q.ck);
-            q_theta.upload(Q.theta); q_xstar.upload(Q.xstar);
-            Hset.posd.upload(Q.pos_diag); Hset.poss.upload(Q.pos_sub); Hset.diagpos.upload(Q.diag_pos);
+    // The per-cone structure (polish_structure) from the device matrices: what the host can see -- uniform second-order
+    // cones of 2-4 rows -- is checked here, the head-variable conditions by k_polish_structure; then the device build.
+    bool polish_structure_on_device(const HostSystem& h, PhaseTimer& pt) {
+        Q = PolishData();
+        const size_t nc = h.cone_row.size();
+        const int T = nc ? h.cone_dim[0] - 1 : 0;
+        bool ok = nc > 0 && h.m_tot > 0 && T >= 1 && T <= kPolishMaxTail;
+        for (size_t k = 0; k < nc && ok; ++k) ok = h.cone_type[k] == 1 && h.cone_dim[k] - 1 == T;
+        if (!ok) return false;
+        Q.T = T;
+        q_head.alloc(nc); q_aabs.alloc(nc); q_ck.alloc(nc); q_theta.alloc(nc); q_xstar.alloc(nc);
+        DevBuf<int32_t> bad;
+        {
+            ZeroGroup zg;
+            zg.add(q_ishead, (size_t)h.n_tot); zg.add(bad, 1);
+            zg.commit(stream);
         }
+        PStructArgs pa{};
+        pa.ncones = (int64_t)nc; pa.n = h.n_tot; pa.T = T;
+        pa.cone_row = cone_row.d; pa.cone_dim = cone_dim.d; pa.cone_type = cone_type.d;
+        pa.A_ptr = A_ptr.d; pa.A_col = A_col.d; pa.A_val = A_val.d; pa.b = b.d; pa.q = q.d;
+        pa.g2_ptr = G2.ptr.d; pa.g2_split = G2.split.d; pa.g2_col = G2.col.d; pa.g2_val = G2.val.d;
+        pa.head_col = q_head.d; pa.is_head = q_ishead.d; pa.a_abs = q_aabs.d; pa.ck = q_ck.d; pa.theta = q_theta.d; pa.xstar = q_xstar.d;
+        pa.bad = bad.d;
+        hipLaunchKernelGGL(k_polish_structure, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, stream, pa);
+        std::vector<int32_t> bad_h(1, 0);
+        HIP_CHECK(hipMemcpyAsync(bad_h.data(), bad.d, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+        const bool on_device = try_build_polish_on_device(h);  // (its synchronisation brings the verdict back too)
+        pt.mark("  polish: structure + pattern + lists on the device");
+        HIP_CHECK(sync_stream(stream));
+        if (on_device && bad_h[0] == 0) return true;
+        Q.available = false;  // (not the SCORE structure, or a build the device declined: ADMM alone)
+        return false;
+    }
+    // the host loop's Newton structure (score_polish_host.hpp) goes up
+    void upload_host_polish() {
+        hm_nnz = (int64_t)Q.Hm.col.size();
+        UploadBatch ub;
+        Hm.upload(Q.Hm, Q.rbH, nullptr, false);
+        q_Pon.upload(Q.Pon); q_ccoef.upload(Q.ccoef); q_cptr.upload(Q.cptr); q_ccone.upload(Q.ccone); q_cab.upload(Q.cab);
+        q_head.upload(Q.head_col); q_ishead.upload(Q.is_head); q_aabs.upload(Q.a_abs); q_ck.upload(Q.ck);
+        q_theta.upload(Q.theta); q_xstar.upload(Q.xstar);
+        Hset.posd.upload(Q.pos_diag); Hset.poss.upload(Q.pos_sub); Hset.diagpos.upload(Q.diag_pos);
+    }
+    void init_polish(const HostSystem& h, bool built_on_device) {
+        PhaseTimer pt(st.verbose != 0);
+        if (!Q.available) return;
+        if (!built_on_device) upload_host_polish();
         pt.mark("  polish: uploads");
         std::optional<UploadBatch> ub_polish;  // (tables and zeroed buffers only from here to join_init_newton: nothing is launched)
         ub_polish.emplace();
-        Hb.upload(std::move(Q.band));
-        if (st.verbose)
-            std::fprintf(stderr, "[score setup] band view of H: %s (%d band + %d csr + %d diag tiles, %d slots per row)\n", Hb.on ? "on" : "off",
-                         Hb.L.n_band, Hb.L.n_csr, Hb.L.n_diag, Hb.L.S);
-        Hset.blk_part.upload(Hb.on ? Hb.L.part_ptr : Q.rbH.part_ptr);
+        Hset.blk_part.upload(Q.rbH.part_ptr);
         {   // entry range of every problem in H (k_hassemble runs problem by problem)
             std::vector<int64_t> ep((size_t)h.count + 1);
             q_ent_max = 0;
@@ -3429,15 +3519,13 @@ struct HipBackend {
         if (Hset.use_fac32 && prec_reg) Hset.deep.alloc((size_t)std::max<int64_t>(1, Hset.deep_floats));
         n_gd = std::max<size_t>((h.n_tot + kThreads - 1) / kThreads, (size_t)Hm.nblocks);
         q_pw.alloc(Hset.blocks());
-        {
-            q_gate_ref.alloc(h.count);
-            std::vector<int64_t> sb(2 * h.count), se(2 * h.count);
-            for (int p = 0; p < h.count; ++p) {
-                sb[2 * p] = h.xoff[p]; se[2 * p] = h.xoff[p + 1];
-                sb[2 * p + 1] = h.n_tot + h.roff[p]; se[2 * p + 1] = h.n_tot + h.roff[p + 1];
-            }
-            q_seg_begin.upload(sb); q_seg_end.upload(se);
+        q_gate_ref.alloc(h.count);
+        std::vector<int64_t> sb(2 * h.count), se(2 * h.count);
+        for (int p = 0; p < h.count; ++p) {
+            sb[2 * p] = h.xoff[p]; se[2 * p] = h.xoff[p + 1];
+            sb[2 * p + 1] = h.n_tot + h.roff[p]; se[2 * p + 1] = h.n_tot + h.roff[p + 1];
         }
+        q_seg_begin.upload(sb); q_seg_end.upload(se);
         ub_polish.reset();
         join_init_newton(h);
     }
@@ -3479,7 +3567,7 @@ struct HipBackend {
         HAsmArgs ha{};
         ha.nnz = hm_nnz; ha.Pon = q_Pon.d; ha.cptr = q_cptr.d; ha.ccone = q_ccone.d; ha.cab = q_cab.d;
         ha.ccoef = q_ccoef.d; ha.Bbuf = q_Bbuf.d; ha.T2 = Q.T * Q.T; ha.Hval = Hm.val.d;
-        ha.dst = Hb.on ? Hb.dst.d : nullptr; ha.V = Hb.on ? Hb.V.d : nullptr;
+        ha.dst = nullptr; ha.V = nullptr;  // (no band view of the Newton matrix)
         ha.ndiag = (int)h.diag_cols.size(); ha.diag_pos = Hset.diagpos.d; ha.dinv = Hset.dinv.d;
         ha.ent_part = q_entpart.d; ha.skip = q_skip.d;  // (the live mask: a frozen problem's matrix is not read any more)
         const int base_blocks = (int)((q_ent_max + kThreads - 1) / kThreads);

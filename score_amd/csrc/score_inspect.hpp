@@ -134,6 +134,10 @@ int64_t get_device_setup(HipBackend& be, double* out, int64_t len) {
     const double v = be.H->device_setup ? 1.0 : 0.0;
     return copy_out_min(&v, 1, out, len);
 }
+int64_t get_matrix_source(HipBackend& be, double* out, int64_t len) {  // 0: built on the device, 1: host system with A, G1, G2 derived on the device, 2: uploaded
+    const double v = (double)(int)be.source;
+    return copy_out_min(&v, 1, out, len);
+}
 int64_t get_rep(HipBackend& be, double* out, int64_t len) {  // [replicas the kernels run with (1 = general problem), nnz of the stored K, of the stored A']
     const HostSystem& h = *be.H;
     const double v[3] = {(double)h.rep, (double)h.K.col.size(), (double)(h.device_setup ? (size_t)be.g1_nnz : h.G1.col.size())};
@@ -192,7 +196,7 @@ int64_t get_polish_build_check(HipBackend& be, double* out, int64_t len) {
     if (!be.Q.available) return -1;
     if (out && len >= 14) {
         PolishData R;
-        build_polish(h, R, false, false);
+        build_polish(h, R, false);
         const size_t nz = (size_t)be.hm_nnz, nc = R.ccone.size();
         out[0] = be.polish_on_device ? 1.0 : 0.0;
         out[1] = (double)be.hm_nnz; out[2] = (double)R.Hm.col.size();
@@ -305,7 +309,7 @@ int64_t get_vec(HipBackend& be, const char* name, double* out, int64_t len) {
         {"newton_probe_arm", probe_arm}, {"newton_probe", get_newton_probe}, {"ag_device_check", get_ag_device_check},
         {"polish_build_check", get_polish_build_check}, {"polish_assemble_at_x", get_polish_assemble_at_x},
         {"polish_prec_of_negg", get_polish_prec_of_negg},
-        {"chain_of_col", get_chain_of_col}, {"chain_id_of_col", get_chain_id_of_col},
+        {"chain_of_col", get_chain_of_col}, {"chain_id_of_col", get_chain_id_of_col}, {"matrix_source", get_matrix_source},
     };
     for (const Computed& c : computed)
         if (nm == c.name) return c.fn(be, out, len);

@@ -6,19 +6,11 @@
 // Included by score_hip.hip where score_create_from_graphs_impl and the abi frame are complete.
 #pragma once
 
+#include "score_slab.hpp"  // Slab, Region: one allocation cut into typed regions (256-byte aligned, 8 bytes at least)
+
 struct RobustHandle { score_handle* h = nullptr; ~RobustHandle() { if (h) score_destroy(h); } };  // (an outer solve's handle goes whatever happens)
 struct StreamBack { int dev; hipStream_t s; ~StreamBack() { (void)sync_stream(s); stream_pool().give(dev, s); } };
 struct PinBack { char* p; size_t n; int dev; ~PinBack() { block_cache().give(p, n, dev, true); } };
-
-// One allocation cut into regions: each declared once with its element type and count (256-byte aligned, 8 bytes at least);
-// a region gives its typed pointer in any copy of the slab -- device memory, the pinned block, a staging vector.
-template <class T> struct Region { size_t off = 0; T* in(void* base) const { return (T*)((char*)base + off); } };
-struct Slab {
-    size_t bytes = 0;
-    template <class T> Region<T> add(size_t count) {
-        return Region<T>{std::exchange(bytes, bytes + ((std::max<size_t>(count * sizeof(T), 8) + 255) & ~(size_t)255))};
-    }
-};
 
 struct MeasRegions {  // the measurement arrays of score_graph: home (graph after graph) and compact (the running members)
     Region<int32_t> rel_base, rel_to, rng_a, rng_b; Region<double> rel_t, rel_R, rel_kappa, rel_tau, rng_dist, prec;

@@ -225,6 +225,64 @@ def test_device_setup_equals_the_host_setup(fixtures, hip_lib, monkeypatch):
                 break  # (the general kernels on the full K: a 2-D graph, the 3-D one, the batch)
 
 
+_SOURCE_DEVICE, _SOURCE_DERIVED, _SOURCE_UPLOADED = 0.0, 1.0, 2.0  # score_debug_get "matrix_source" (HipBackend::MatrixSource)
+
+
+@pytest.mark.parametrize("case", ["synth_a", "graph3d", "batch"])
+def test_the_three_matrix_sources_give_the_same_handle(case, fixtures, hip_lib, monkeypatch):
+    """A create takes its matrices from one of three sources, decided once (HipBackend::matrix_source): built on the device from
+    the raw program (the default), the host's build_system with the equilibrated A, G1, G2 derived on the device (SCORE_HOST_SETUP=1,
+    a single problem), or the host's build_system with everything uploaded (SCORE_HOST_SETUP=1 for a batch -- the derivation
+    needs count == 1 --, or with SCORE_NO_DEVICE_RUIZ=1 as well).  Each handle reports the source it took.  With the equilibration
+    on the device on both sides every setup array is equal bit for bit and so are the default solves (the comparisons of
+    test_device_setup_equals_the_host_setup); the host's equilibration loop against the device's as
+    test_device_equilibration_equals_the_host_loop compares them: the same formulas, D and E equal to 1e-12, K to 1e-11.
+    synth_a: one robot x 60 poses; graph3d: 40 poses, 4 x 4 blocks, a loop closure and a prior; a lock-step batch of two
+    Manhattan graphs of different sizes (2 x 40 and 3 x 70 poses)."""
+    _hip_only(hip_lib)
+    from score_amd.native import assemble_native
+
+    if case == "batch":
+        graphs = [make_manhattan(n_robots=2, n_poses=40, n_beacons=2, seed=121), make_manhattan(n_robots=3, n_poses=70, n_beacons=2, seed=122)]
+    else:
+        graphs = [graph_by_name(case, fixtures)]
+    qps = [assemble_native(g, "SOCP", lib_path=hip_lib).qp for g in graphs]
+    single = len(qps) == 1
+
+    def create(expected, **env):
+        for k in ("SCORE_HOST_SETUP", "SCORE_NO_DEVICE_RUIZ"):
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        sv = ConicSolver(qps, {}, lib_path=hip_lib)
+        for k in env:
+            monkeypatch.delenv(k, raising=False)
+        assert sv.debug_get("matrix_source")[0] == expected, (case, env, sv.debug_get("matrix_source"))
+        assert sv.debug_get("device_setup")[0] == (1.0 if expected == _SOURCE_DEVICE else 0.0)
+        return sv
+
+    dev = create(_SOURCE_DEVICE)
+    host = create(_SOURCE_DERIVED if single else _SOURCE_UPLOADED, SCORE_HOST_SETUP="1")
+    for nm in _SETUP_INT + _SETUP_VAL:
+        a, b = dev.debug_get(nm), host.debug_get(nm)
+        assert a.shape == b.shape and a.size > 0, (case, nm, a.shape, b.shape)
+        bad = np.nonzero(a != b)[0]
+        assert bad.size == 0, (case, nm, bad[:5], a[bad[:5]], b[bad[:5]])
+    for x, y in zip(dev.solve(), host.solve()):
+        assert x.solved and y.solved
+        assert np.array_equal(x.x, y.x) and np.array_equal(x.y, y.y) and np.array_equal(x.s, y.s)
+        assert x.info["newton_iters"] == y.info["newton_iters"] and x.info["pobj"] == y.info["pobj"]
+    if single:  # the host's equilibration loop, everything uploaded, against the derived handle (scales from the device's passes)
+        up = create(_SOURCE_UPLOADED, SCORE_HOST_SETUP="1", SCORE_NO_DEVICE_RUIZ="1")
+        for v in ("D", "E"):
+            a, b = host.debug_get(v), up.debug_get(v)
+            assert a.min() > 0
+            np.testing.assert_allclose(a, b, rtol=1e-12, atol=0)
+        np.testing.assert_allclose(host.debug_get("Kval"), up.debug_get("Kval"), rtol=1e-11, atol=1e-300)
+        up.close()
+    dev.close(); host.close()
+
+
 def test_device_assembler_equals_the_host_assembler(fixtures, hip_lib, monkeypatch):
     """f2: score_create_from_graphs builds the MODEL on the device (k_ga_*: every relative-pose measurement, range and prior
     writes the records score_assemble's filling pass adds, in that order; a stable sort and an in-order merge turn them into P
