@@ -264,6 +264,24 @@ SCORE_GN_HD double gn_prior_block3(const double* l, const double* t0, double pre
     return c;
 }
 
+// Per-measurement residuals of the robust refinement (include/score_refine_robust.h): r = sqrt(the measurement's own cost
+// term) -- the block functions above without H / g, so a cost term is stated once.  The caller passes the MEASURED precisions.
+//   range:          sqrt(prec) | |p_a - p_b| - dist |
+//   relative pose:  sqrt(kappa |t_j - t_i - R_i t~|^2 + tau |R_j - R_i R~|_F^2)
+SCORE_GN_HD double gn_range_resid(double xa, double ya, double xb, double yb, double dist, double prec) {
+    return sqrt(gn_range_block(xa, ya, xb, yb, dist, prec, nullptr, nullptr));
+}
+SCORE_GN_HD double gn_rel_resid(double thi, double xi, double yi, double thj, double xj, double yj, const double* tm, const double* Rm,
+                                double kappa, double tau) {
+    return sqrt(gn_rel_block(thi, xi, yi, thj, xj, yj, tm, Rm, kappa, tau, nullptr, nullptr));
+}
+SCORE_GN_HD double gn_range_resid3(const double* pa, const double* pb, double dist, double prec) {
+    return sqrt(gn_range_block3(pa, pb, dist, prec, nullptr, nullptr));
+}
+SCORE_GN_HD double gn_rel_resid3(const double* Xi, const double* Xj, const double* tm, const double* Rm, double kappa, double tau) {
+    return sqrt(gn_rel_block3(Xi, Xj, tm, Rm, kappa, tau, nullptr, nullptr));
+}
+
 // ---------------------------------------------------------------------------
 // host side: the graph, the pattern of J'J, the contribution lists
 // ---------------------------------------------------------------------------

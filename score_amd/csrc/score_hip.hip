@@ -4052,6 +4052,7 @@ struct AbiEnv {
 #include "score_abi.hpp"
 
 #include "score_marginals.hpp"
+#include "score_gn_robust.hpp"
 
 // Local refinement after SCORE on the device (score_gn.hpp): state, blocks and gathers here, the damped
 // normal equations through the linear-mode handle `lin` (its K0 values and right-hand side are written
@@ -4067,6 +4068,12 @@ struct score_refine {
     int n_mblocks = 0, n_ublocks = 0, n_hblocks = 0, n_sblocks = 0;
     std::vector<double> part_host;
     score::MvWork mv;  // marginal covariances (score_marginals.hpp)
+    // robust refinement (score_gn_robust.hpp): the measured precisions beside rng_prec / rel_kappa / rel_tau (which hold a robust
+    // run's weighted ones while it lasts), residuals, weights, per-block partials; they come with the first robust call
+    DevBuf<double> rb_prec0, rb_kappa0, rb_tau0, rb_r_rng, rb_r_lc, rb_w_rng, rb_w_lc, rb_part;
+    int64_t rb_n_lc = 0;
+    bool rb_ready = false;
+    const score_refine_robust_settings* rb_settings = nullptr;  // of the robust run under way
 
     HipBackend& be() { return lin->solver.be; }
     hipStream_t stream() { return lin->solver.be.stream; }
@@ -4182,6 +4189,10 @@ struct score_refine {
              score::GnInfo& info) {
         std::vector<double> u0 = set_point(poses_in, lms_in);
         score::gn_levenberg_marquardt(*this, max_iters, tol, 1e-9, info);
+        read_point(u0, poses_in, poses_out, lms_out);
+    }
+    // the current point (u) in the caller's layout; u0: scratch of the state's size
+    void read_point(std::vector<double>& u0, const double* poses_in, double* poses_out, double* lms_out) {
         staged_d2h(u0.data(), u.d, u0.size() * sizeof(double), stream());
         HIP_CHECK(sync_stream(stream()));
         if (P.dim == 2) {
@@ -4193,6 +4204,127 @@ struct score_refine {
             std::copy(u0.begin(), u0.begin() + (std::ptrdiff_t)(12 * P.Np), poses_out);
             if (P.Nl) std::copy(u0.begin() + (std::ptrdiff_t)(12 * P.Np), u0.end(), lms_out);
         }
+    }
+
+    // ---- robust refinement: the hooks of gn_robust_refine (score_gn_robust.hpp) ----
+    void robust_reserve() {  // the buffers, from the handle's arena; the measured precisions are what the block kernels' arrays hold now
+        if (rb_ready) return;
+        rb_n_lc = score::gn_n_loop_closures(P);
+        if (rb_n_lc < 0) throw std::runtime_error("score_refine: fewer relative-pose entries than odometry steps");
+        struct ArenaScope {
+            DevArena* keep;
+            explicit ArenaScope(DevArena* a) : keep(tl_arena) { tl_arena = a; }
+            ~ArenaScope() { tl_arena = keep; }
+        } arena_scope(&be().arena);
+        const size_t nr = (size_t)P.n_rng(), nc = (size_t)rb_n_lc, first = (size_t)P.n_rel() - nc;
+        rb_prec0.alloc(nr); rb_r_rng.alloc(nr); rb_w_rng.alloc(nr);
+        rb_kappa0.alloc(nc); rb_tau0.alloc(nc); rb_r_lc.alloc(nc); rb_w_lc.alloc(nc);
+        rb_part.alloc((size_t)score::kGnRobustPart * ((nr + nc + kThreads - 1) / kThreads));
+        const size_t f8 = sizeof(double);
+        if (nr) HIP_CHECK(hipMemcpyAsync(rb_prec0.d, rng_prec.d, nr * f8, hipMemcpyDeviceToDevice, stream()));
+        if (nc) HIP_CHECK(hipMemcpyAsync(rb_kappa0.d, rel_kappa.d + first, nc * f8, hipMemcpyDeviceToDevice, stream()));
+        if (nc) HIP_CHECK(hipMemcpyAsync(rb_tau0.d, rel_tau.d + first, nc * f8, hipMemcpyDeviceToDevice, stream()));
+        HIP_CHECK(sync_stream(stream()));
+        rb_ready = true;
+    }
+    void robust_restore() noexcept {  // the block kernels' arrays hold the measured precisions again
+        if (!rb_ready) return;
+        const size_t nr = (size_t)P.n_rng(), nc = (size_t)rb_n_lc, first = (size_t)P.n_rel() - nc, f8 = sizeof(double);
+        if (nr) (void)hipMemcpyAsync(rng_prec.d, rb_prec0.d, nr * f8, hipMemcpyDeviceToDevice, stream());
+        if (nc) (void)hipMemcpyAsync(rel_kappa.d + first, rb_kappa0.d, nc * f8, hipMemcpyDeviceToDevice, stream());
+        if (nc) (void)hipMemcpyAsync(rel_tau.d + first, rb_tau0.d, nc * f8, hipMemcpyDeviceToDevice, stream());
+        (void)sync_stream(stream());
+    }
+    score::GnRobustDev robust_dev(int families) const {
+        score::GnRobustDev a{};
+        a.g = dev(); a.dim = P.dim;
+        a.n_a = (families & score::kGnRobustRanges) ? P.n_rng() : 0;
+        a.n_b = (families & score::kGnRobustClosures) ? rb_n_lc : 0;
+        a.first_lc = P.n_rel() - rb_n_lc;
+        a.prec0 = rb_prec0.d; a.kappa0 = rb_kappa0.d; a.tau0 = rb_tau0.d;
+        a.prec = rng_prec.d; a.kappa = rel_kappa.d; a.tau = rel_tau.d;
+        a.r_rng = rb_r_rng.d; a.r_lc = rb_r_lc.d; a.w_rng = rb_w_rng.d; a.w_lc = rb_w_lc.d;
+        return a;
+    }
+    void robust_weights(int families, double mu, double c, double c_rel, double min_weight, bool apply) {
+        const score::GnRobustDev a = robust_dev(families);
+        const int64_t lanes = a.n_a + a.n_b;
+        if (lanes == 0) return;  // (an enabled family without measurements launches nothing)
+        hipLaunchKernelGGL(score::k_gn_robust_weight, dim3((unsigned)((lanes + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream(), a, mu,
+                           c, c_rel, min_weight, apply ? 1 : 0);
+    }
+    void robust_weights(int families, double mu) {
+        robust_weights(families, mu, rb_settings->inlier_threshold, rb_settings->rel_threshold, rb_settings->min_weight, true);
+    }
+    void robust_begin() { robust_weights(score::kGnRobustRanges | score::kGnRobustClosures, 0.0, 1.0, 1.0, 1.0, true); }
+    int robust_residuals(int families, score::RobustSeen* seen) {
+        const score::GnRobustDev a = robust_dev(families);
+        const int64_t lanes = a.n_a + a.n_b;
+        const int nb = (int)((lanes + kThreads - 1) / kThreads);
+        double r2[2] = {0.0, 0.0}, nonbin[2] = {0.0, 0.0};
+        if (nb > 0) {
+            hipLaunchKernelGGL(score::k_gn_robust_resid, dim3(nb), dim3(kThreads), 0, stream(), a, (const double*)u.d, rb_part.d);
+            part_host.resize((size_t)score::kGnRobustPart * (size_t)nb);
+            HIP_CHECK(hipMemcpyAsync(part_host.data(), rb_part.d, part_host.size() * sizeof(double), hipMemcpyDeviceToHost, stream()));
+            HIP_CHECK(sync_stream(stream()));
+            for (int b = 0; b < nb; ++b) {
+                const double* p = part_host.data() + (size_t)score::kGnRobustPart * (size_t)b;
+                for (int f = 0; f < 2; ++f) {
+                    r2[f] = p[f] != p[f] ? INFINITY : std::max(r2[f], p[f]);
+                    nonbin[f] += p[2 + f];
+                }
+            }
+        }
+        const double c[2] = {rb_settings ? rb_settings->inlier_threshold : 0.0, rb_settings ? rb_settings->rel_threshold : 0.0};
+        const int64_t items[2] = {P.n_rng(), rb_n_lc};
+        int n_seen = 0;
+        for (int f = 0; f < 2; ++f)
+            if (families & (1 << f)) seen[n_seen++] = score::RobustSeen{items[f], r2[f], c[f], (int32_t)nonbin[f]};
+        return n_seen;
+    }
+    // residuals and weights as they are on the device, into the caller's arrays (null: not wanted); counts the outliers
+    void robust_read(double* w, double* r, double* wl, double* rl, int32_t* outliers, int32_t* rel_outliers) {
+        const size_t nr = (size_t)P.n_rng(), nc = (size_t)rb_n_lc, f8 = sizeof(double);
+        std::vector<double> hw(nr), hwl(nc);
+        if (nr) staged_d2h(hw.data(), rb_w_rng.d, nr * f8, stream());
+        if (nc) staged_d2h(hwl.data(), rb_w_lc.d, nc * f8, stream());
+        if (r && nr) staged_d2h(r, rb_r_rng.d, nr * f8, stream());
+        if (rl && nc) staged_d2h(rl, rb_r_lc.d, nc * f8, stream());
+        HIP_CHECK(sync_stream(stream()));
+        if (w) std::copy(hw.begin(), hw.end(), w);
+        if (wl) std::copy(hwl.begin(), hwl.end(), wl);
+        if (outliers) { *outliers = 0; for (double v : hw) *outliers += v < 0.5 ? 1 : 0; }
+        if (rel_outliers) { *rel_outliers = 0; for (double v : hwl) *rel_outliers += v < 0.5 ? 1 : 0; }
+    }
+    void robust_run(const score_refine_robust_settings& s, const double* poses_in, const double* lms_in, double* poses_out, double* lms_out,
+                    double* w, double* r, double* wl, double* rl, int32_t* outliers, int32_t* rel_outliers, score::GnRobustResult& R) {
+        score::gn_robust_check(s, P);
+        robust_reserve();
+        struct Restore {  // whatever happens, the handle ends with the measured precisions
+            score_refine& h;
+            ~Restore() { h.robust_restore(); h.rb_settings = nullptr; }
+        } restore{*this};
+        rb_settings = &s;
+        std::vector<double> u0 = set_point(poses_in, lms_in);
+        score::gn_robust_refine(*this, s, 1e-9, R);
+        score::RobustSeen seen[2];
+        (void)robust_residuals(score::kGnRobustRanges | score::kGnRobustClosures, seen);  // every family's r at the final estimate
+        robust_read(w, r, wl, rl, outliers, rel_outliers);
+        if (!(s.families & score::kGnRobustClosures) && rel_outliers) *rel_outliers = 0;
+        if (poses_out) read_point(u0, poses_in, poses_out, lms_out);
+    }
+    void robust_inspect(const double* poses, const double* lms, double mu, double c, double c_rel, double* r, double* rl, double* w, double* wl) {
+        if (!(mu >= 0.0) || !std::isfinite(mu)) throw std::runtime_error("score_refine_residuals: mu must be finite and >= 0");
+        if (mu > 0.0 && !(std::isfinite(c) && c > 0.0 && std::isfinite(c_rel) && c_rel > 0.0))
+            throw std::runtime_error("score_refine_residuals: c and c_rel must be positive and finite when mu > 0");
+        const int both = score::kGnRobustRanges | score::kGnRobustClosures;
+        robust_reserve();
+        (void)set_point(poses, lms);
+        robust_begin();
+        score::RobustSeen seen[2];
+        (void)robust_residuals(both, seen);
+        robust_weights(both, mu, c, c_rel, 1.0, false);
+        robust_read(w, r, wl, rl, nullptr, nullptr);
     }
 };
 
@@ -4296,6 +4428,44 @@ int score_refine_marginals(score_refine* r, const double* poses, const double* l
         require(r && poses && (r->P.Nl == 0 || landmarks));
         AbiEnv::Scope scope(r->device, false);
         return score::mv_solve(*r, poses, landmarks, vars, n_vars, rel_tol, max_iters, block_width, joint, residuals, iters, info);
+    });
+}
+void score_refine_robust_default_settings(score_refine_robust_settings* rs) {
+    if (!rs) return;
+    rs->inlier_threshold = 3.0; rs->rel_threshold = 3.0; rs->mu_step = 1.4; rs->min_weight = 1e-6;
+    rs->families = 1; rs->max_outer = 50; rs->inner_iters = 5; rs->max_iters = 50; rs->tol = 1e-10;
+}
+int score_refine_robust_run(score_refine* r, const score_refine_robust_settings* rs, const double* poses_in, const double* landmarks_in,
+                            double* poses_out, double* landmarks_out, double* weights, double* residuals, double* rel_weights,
+                            double* rel_residuals, score_refine_robust_info* info) {
+    return abi_call([&] {
+        require(r && poses_in && (r->P.Nl == 0 || landmarks_in) && (!poses_out || r->P.Nl == 0 || landmarks_out));
+        AbiEnv::Scope scope(r->device, false);
+        const double t0 = score::now_ms();
+        score_refine_robust_settings s;
+        score_refine_robust_default_settings(&s);
+        if (rs) s = *rs;
+        score::GnRobustResult R;
+        int32_t outliers = 0, rel_outliers = 0;
+        r->robust_run(s, poses_in, landmarks_in, poses_out, landmarks_out, weights, residuals, rel_weights, rel_residuals, &outliers,
+                      &rel_outliers, R);
+        if (info) {
+            info->outer_iterations = R.outer_iterations; info->converged = R.converged ? 1 : 0;
+            info->outliers = outliers; info->rel_outliers = rel_outliers; info->mu = R.mu;
+            info->lm_iterations = R.lm_iterations; info->linear_solves = R.gi.linear_solves; info->pcg_iters = R.gi.pcg_iters;
+            info->cost_initial = R.cost_initial; info->cost_final = R.gi.cost_final; info->grad_inf = R.gi.grad_inf;
+            info->setup_ms = r->setup_ms; info->solve_ms = score::now_ms() - t0;
+        }
+        return 0;
+    });
+}
+int score_refine_residuals(score_refine* r, const double* poses, const double* landmarks, double mu, double c, double c_rel,
+                           double* residuals, double* rel_residuals, double* weights, double* rel_weights) {
+    return abi_call([&] {
+        require(r && poses && (r->P.Nl == 0 || landmarks));
+        AbiEnv::Scope scope(r->device, false);
+        r->robust_inspect(poses, landmarks, mu, c, c_rel, residuals, rel_residuals, weights, rel_weights);
+        return 0;
     });
 }
 void score_refine_destroy(score_refine* r) {

@@ -60,22 +60,6 @@ struct RobustFamilyHost : RobustFamilyKind {  // one re-weighted family of measu
     int64_t mirror_at(int m) const { return arr_off[(size_t)m + 1] - items(m); }
 };
 
-// who stops, from what the re-weighted families saw in outer solve k
-struct RobustSeen { int64_t n; double r2max, c; int32_t nonbinary; };
-enum class RobustNext { go, converged, gave_up };
-static RobustNext robust_decide(int k, int max_outer, const RobustSeen* seen, int n_seen) {
-    bool finite = true, outliers = false;
-    int32_t nonbinary = 0;
-    for (const RobustSeen* s = seen; s < seen + n_seen; ++s) {
-        finite = finite && std::isfinite(s->r2max);
-        outliers = outliers || (s->n > 0 && 2.0 * s->r2max > s->c * s->c);
-        nonbinary += s->nonbinary;
-    }
-    if (!finite) return RobustNext::gave_up;                                 // (a solve gone non-finite)
-    if (k == 1 ? !outliers : nonbinary == 0) return RobustNext::converged;   // no outliers at all | solved on binary weights
-    return k >= max_outer ? RobustNext::gave_up : RobustNext::go;
-}
-
 struct RobustRun {  // one score_robust_solve_rel call: the arguments, the layout, the memory, the host's state; the phases in order
     const score_graph* graphs; int count; const score_robust_settings* rs; score_settings st;
     double* poses; double* relaxed; double* landmarks; double* ranges; int32_t* degenerate; score_info* infos;

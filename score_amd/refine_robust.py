@@ -1,0 +1,427 @@
+"""Outlier-robust local refinement: GNC-TLS re-weighting of the ranges and / or the loop closures on the residuals of the
+maximum-likelihood cost (include/score_refine_robust.h states the loop in full).
+
+``solve_score_robust`` weighs a range by its term in the RELAXED objective, ``sqrt(prec) max(0, |t_a - t_b| - dist)``: a range
+measured too long costs nothing there and keeps weight 1.  The refinement's range term ``w (|p_a - p_b| - dist)^2`` is
+two-sided, so a long outlier drags the refined estimate; so does a false loop closure that lands where the relaxation is
+free.  ``refine_estimate_robust`` runs the GNC-TLS loop around the Levenberg-Marquardt step of ``refine_estimate``:
+
+    solve 1 as refine_estimate;  r = sqrt(prec) | |p_a - p_b| - dist |,  r = sqrt(kappa |t_j - t_i - R_i t~|^2 + tau |R_j - R_i R~|_F^2)
+    with the MEASURED precisions;  stop (first solve, no 2 max r_f^2 > c_f^2 | a later solve on binary weights | max_outer |
+    non-finite);  mu0 = min_f c_f^2 / (2 max r_f^2 - c_f^2), then mu <- mu_step mu;  w = gnc_tls_weight(r, mu, c_f);  next
+    precisions prec max(w, min_weight);  solves 2.. are at most inner_iters LM iterations from the current point;  one last run
+    with the final weights to max_iters / tol.
+
+``engine="native"`` runs the whole loop behind the C ABI on one refinement handle (``score_refine_robust_run``: two streaming
+kernels per outer iteration at the point on the device, csrc/score_gn_robust.hpp); ``engine="python"`` is the readable twin --
+the same loop around ``refine._lm_loop`` with NumPy residuals in the device's operation order -- which the tests compare with.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+
+from .refine import _as_results, _DeviceNormalEquations, _initial_point, _lm_loop, _Problem, _Problem3D
+from .robust import BINARY_TOL, _robust_info, gnc_tls_weight, initial_mu, n_loop_closures_of
+from .solver import ScoreSettings, _f64p, load_library
+
+# the symbols include/score_refine_robust.h declares
+REFINE_ROBUST_SYMBOLS = ["score_refine_robust_default_settings", "score_refine_robust_run", "score_refine_residuals"]
+
+FAMILY_RANGES, FAMILY_LOOP_CLOSURES = 1, 2
+
+
+class ScoreRefineRobustSettings(C.Structure):
+    _fields_ = [
+        ("inlier_threshold", C.c_double), ("rel_threshold", C.c_double), ("mu_step", C.c_double), ("min_weight", C.c_double),
+        ("families", C.c_int32), ("max_outer", C.c_int32), ("inner_iters", C.c_int32), ("max_iters", C.c_int32),
+        ("tol", C.c_double),
+    ]
+
+
+class ScoreRefineRobustInfo(C.Structure):
+    _fields_ = [
+        ("outer_iterations", C.c_int32), ("converged", C.c_int32), ("outliers", C.c_int32), ("rel_outliers", C.c_int32),
+        ("mu", C.c_double), ("lm_iterations", C.c_int32), ("linear_solves", C.c_int32), ("pcg_iters", C.c_int32),
+        ("cost_initial", C.c_double), ("cost_final", C.c_double), ("grad_inf", C.c_double),
+        ("setup_ms", C.c_double), ("solve_ms", C.c_double),
+    ]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def _bind(lib: C.CDLL) -> C.CDLL:
+    if getattr(lib, "_score_refine_robust_bound", False):
+        return lib
+    for sym in REFINE_ROBUST_SYMBOLS:
+        if not hasattr(lib, sym):
+            raise RuntimeError(f"{sym} is missing from the library: rebuild it (the CPU twin of the tests has no robust "
+                               "refinement: engine='python' runs there)")
+    lib.score_refine_robust_default_settings.argtypes = [C.POINTER(ScoreRefineRobustSettings)]
+    lib.score_refine_robust_default_settings.restype = None
+    lib.score_refine_robust_run.argtypes = [C.c_void_p, C.POINTER(ScoreRefineRobustSettings), _f64p, _f64p, _f64p, _f64p,
+                                            _f64p, _f64p, _f64p, _f64p, C.POINTER(ScoreRefineRobustInfo)]
+    lib.score_refine_robust_run.restype = C.c_int
+    lib.score_refine_residuals.argtypes = [C.c_void_p, _f64p, _f64p, C.c_double, C.c_double, C.c_double, _f64p, _f64p, _f64p, _f64p]
+    lib.score_refine_residuals.restype = C.c_int
+    lib._score_refine_robust_bound = True
+    return lib
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the residuals (the device's are csrc/score_gn.hpp: gn_range_resid, gn_rel_resid -- same operations, same order)
+# ---------------------------------------------------------------------------------------------------------------------
+def _translations(prob, point):
+    if isinstance(prob, _Problem3D):
+        _, t, lm = point
+    else:
+        _, t, lm = prob.split(point)
+    return t, lm
+
+
+def range_residuals(prob, point, prec) -> np.ndarray:
+    """r = sqrt(prec) | |p_a - p_b| - dist | of every range at ``point`` (the packed unknowns in 2-D, (R, t, lm) in 3-D) -- the
+    square root of the range's own term in the refinement's cost, two-sided."""
+    t, lm = _translations(prob, point)
+    pa, pb = prob._point(prob.ra, t, lm), prob._point(prob.rb, t, lm)
+    nn = np.zeros(len(prob.ra))
+    for k in range(pa.shape[1]):
+        dl = pa[:, k] - pb[:, k]
+        nn = nn + dl * dl
+    r = np.sqrt(np.asarray(prec, dtype=np.float64)) * (np.sqrt(nn) - prob.dist)
+    return np.sqrt(r * r)
+
+
+def loop_closure_residuals(prob, point, kappa, tau) -> np.ndarray:
+    """r = sqrt(kappa |t_j - t_i - R_i t~|^2 + tau |R_j - R_i R~|_F^2) of every loop closure (the trailing relative-pose
+    entries; ``kappa``, ``tau``: one per loop closure) at ``point`` -- the square root of its term in the refinement's cost."""
+    n_lc = len(kappa)
+    sl = slice(len(prob.bi) - n_lc, len(prob.bi))
+    bi, tj = prob.bi[sl], prob.tj[sl]
+    sk, st = np.sqrt(np.asarray(kappa, dtype=np.float64)), np.sqrt(np.asarray(tau, dtype=np.float64))
+    rows = []
+    if isinstance(prob, _Problem3D):
+        R, t, _ = point
+        tm, Rm = np.asarray(prob.tm).reshape(-1, 3)[sl], np.asarray(prob.Rm).reshape(-1, 3, 3)[sl]
+        Ri, Rj, ti, tjv = R[bi], R[tj], t[bi], t[tj]
+        for a in range(3):
+            rt = np.zeros(n_lc)
+            for k in range(3):
+                rt = rt + Ri[:, a, k] * tm[:, k]
+            rows.append(sk * (tjv[:, a] - ti[:, a] - rt))
+        for a in range(3):
+            for b in range(3):
+                rr = np.zeros(n_lc)
+                for k in range(3):
+                    rr = rr + Ri[:, a, k] * Rm[:, k, b]
+                rows.append(st * (Rj[:, a, b] - rr))
+    else:
+        th, t, _ = prob.split(point)
+        tm, Rm = np.asarray(prob.tm).reshape(-1, 2)[sl], np.asarray(prob.Rm).reshape(-1, 4)[sl]
+        ci, si, cj, sj = np.cos(th[bi]), np.sin(th[bi]), np.cos(th[tj]), np.sin(th[tj])
+        rows.append(sk * (t[tj, 0] - t[bi, 0] - (ci * tm[:, 0] - si * tm[:, 1])))
+        rows.append(sk * (t[tj, 1] - t[bi, 1] - (si * tm[:, 0] + ci * tm[:, 1])))
+        rows.append(st * (cj - (ci * Rm[:, 0] - si * Rm[:, 2])))
+        rows.append(st * (-sj - (ci * Rm[:, 1] - si * Rm[:, 3])))
+        rows.append(st * (sj - (si * Rm[:, 0] + ci * Rm[:, 2])))
+        rows.append(st * (cj - (si * Rm[:, 1] + ci * Rm[:, 3])))
+    cost = np.zeros(n_lc)
+    for r in rows:
+        cost = cost + r * r
+    return np.sqrt(cost)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the stop rule (the library's is csrc/score_robust.hpp: robust_decide)
+# ---------------------------------------------------------------------------------------------------------------------
+def _nonbinary(w) -> int:
+    w = np.asarray(w, dtype=np.float64)
+    return int(np.count_nonzero(~((np.abs(w) <= BINARY_TOL) | (np.abs(1.0 - w) <= BINARY_TOL))))
+
+
+def decide(k: int, max_outer: int, seen) -> str:
+    """What follows outer solve ``k``: "go", "converged", "max_outer" or "non_finite".  ``seen``: one
+    ``(items, max r^2, c, non-binary weights of this solve)`` per enabled family."""
+    if not all(np.isfinite(r2) for _, r2, _, _ in seen):
+        return "non_finite"
+    outliers = any(n > 0 and 2.0 * r2 > c * c for n, r2, c, _ in seen)
+    nonbinary = sum(nb for _, _, _, nb in seen)
+    if (not outliers) if k == 1 else (nonbinary == 0):
+        return "converged"
+    return "max_outer" if k >= max_outer else "go"
+
+
+def first_mu(seen) -> float:
+    """mu after the first solve: the smallest c_f^2 / (2 max r_f^2 - c_f^2) of the families with outliers."""
+    return min(initial_mu(r2, c) for n, r2, c, _ in seen if n > 0 and 2.0 * r2 > c * c)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the point in the C ABI's layout
+# ---------------------------------------------------------------------------------------------------------------------
+def _point_arrays(prob, point):
+    if isinstance(prob, _Problem3D):  # [R (row-major) | t] per pose, landmarks x 3
+        R, t, lm = point
+        poses = np.ascontiguousarray(np.concatenate([R.reshape(prob.Np, 9), t], axis=1), dtype=np.float64)
+        return poses, np.ascontiguousarray(lm, dtype=np.float64).reshape(-1, 3)
+    th, t, lm = prob.split(point)
+    return np.ascontiguousarray(np.column_stack([th, t]), dtype=np.float64), np.ascontiguousarray(lm, dtype=np.float64).reshape(-1, 2)
+
+
+def _point_from(prob, poses, lms):
+    if isinstance(prob, _Problem3D):
+        return poses[:, :9].reshape(-1, 3, 3).copy(), poses[:, 9:12].copy(), lms[: prob.Nl].copy()
+    return prob.pack(poses[:, 0], poses[:, 1:3], lms[: prob.Nl])
+
+
+class RobustRefineHandle:
+    """A refinement handle (``score_refine_create``) with the calls of include/score_refine_robust.h (and ``score_refine_run``)
+    as they are: points go in and come out in the problem's own form (``_Problem``: packed unknowns; ``_Problem3D``: (R, t, lm))."""
+
+    def __init__(self, prob, lib_path: Optional[str] = None, solver_settings: Optional[dict] = None):
+        from .native import score_graph_struct
+
+        self.prob = prob
+        self.lib = _bind(load_library(lib_path))
+        st = ScoreSettings()
+        self.lib.score_default_settings(C.byref(st))
+        for k, v in (solver_settings or {}).items():
+            if not hasattr(st, k):
+                raise ValueError(f"unknown solver setting {k}")
+            setattr(st, k, v)
+        g = score_graph_struct(prob.a)
+        self.h = C.c_void_p()
+        if self.lib.score_refine_create(C.byref(g), C.byref(st), C.byref(self.h)) != 0:
+            raise RuntimeError(f"score_refine_create failed: {self.lib.score_last_error().decode()}")
+        self.n_rng, self.n_lc = len(prob.ra), n_loop_closures_of(prob.a)
+
+    def default_settings(self) -> ScoreRefineRobustSettings:
+        rs = ScoreRefineRobustSettings()
+        self.lib.score_refine_robust_default_settings(C.byref(rs))
+        return rs
+
+    def _outputs(self):
+        return [np.ones(max(1, n)) for n in (self.n_rng, self.n_rng, self.n_lc, self.n_lc)]
+
+    def robust_run(self, point, rs: ScoreRefineRobustSettings):
+        """``score_refine_robust_run``: returns (point, weights, residuals, loop-closure weights, residuals, info dict)."""
+        poses_in, lms_in = _point_arrays(self.prob, point)
+        poses_out, lms_out = np.empty_like(poses_in), np.empty((max(1, len(lms_in)), lms_in.shape[1]))
+        w, r, wl, rl = self._outputs()
+        info = ScoreRefineRobustInfo()
+        p = lambda x: x.ctypes.data_as(_f64p)  # noqa: E731
+        rc = self.lib.score_refine_robust_run(self.h, C.byref(rs), p(poses_in), p(lms_in) if len(lms_in) else None, p(poses_out),
+                                              p(lms_out), p(w), p(r), p(wl), p(rl), C.byref(info))
+        if rc != 0:
+            raise RuntimeError(f"score_refine_robust_run failed: {self.lib.score_last_error().decode()}")
+        return (_point_from(self.prob, poses_out, lms_out), w[: self.n_rng], r[: self.n_rng], wl[: self.n_lc], rl[: self.n_lc],
+                info.as_dict())
+
+    def residuals(self, point, mu: float = 0.0, c: float = 3.0, c_rel: float = 3.0):
+        """``score_refine_residuals``: (residuals, loop-closure residuals, weights, loop-closure weights) at ``point``."""
+        poses_in, lms_in = _point_arrays(self.prob, point)
+        w, r, wl, rl = self._outputs()
+        p = lambda x: x.ctypes.data_as(_f64p)  # noqa: E731
+        rc = self.lib.score_refine_residuals(self.h, p(poses_in), p(lms_in) if len(lms_in) else None, float(mu), float(c), float(c_rel),
+                                             p(r), p(rl), p(w), p(wl))
+        if rc != 0:
+            raise RuntimeError(f"score_refine_residuals failed: {self.lib.score_last_error().decode()}")
+        return r[: self.n_rng], rl[: self.n_lc], w[: self.n_rng], wl[: self.n_lc]
+
+    def run(self, point, max_iters: int = 50, tol: float = 1e-10):
+        """``score_refine_run`` on this handle: (point, info dict)."""
+        from .solver import ScoreRefineInfo
+
+        poses_in, lms_in = _point_arrays(self.prob, point)
+        poses_out, lms_out = np.empty_like(poses_in), np.empty((max(1, len(lms_in)), lms_in.shape[1]))
+        info = ScoreRefineInfo()
+        p = lambda x: x.ctypes.data_as(_f64p)  # noqa: E731
+        rc = self.lib.score_refine_run(self.h, p(poses_in), p(lms_in) if len(lms_in) else None, int(max_iters), float(tol),
+                                       p(poses_out), p(lms_out), C.byref(info))
+        if rc != 0:
+            raise RuntimeError(f"score_refine_run failed: {self.lib.score_last_error().decode()}")
+        return _point_from(self.prob, poses_out, lms_out), info.as_dict()
+
+    def close(self) -> None:
+        if self.h:
+            self.lib.score_refine_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# engine="python": the readable twin
+# ---------------------------------------------------------------------------------------------------------------------
+def _python_loop(prob, u, families, c, c_rel, max_outer, inner_iters, min_weight, mu_step, max_iters, tol, linear_solver, lib_path,
+                 solver_settings, pcg_rel_tol=1e-9):
+    f_rng, f_rel = bool(families & FAMILY_RANGES), bool(families & FAMILY_LOOP_CLOSURES)
+    n_lc = n_loop_closures_of(prob.a)
+    first = len(prob.bi) - n_lc
+    prec0 = np.array(prob.a["rng_prec"], dtype=np.float64)
+    kappa0, tau0 = np.array(prob.a["rel_kappa"], dtype=np.float64)[first:], np.array(prob.a["rel_tau"], dtype=np.float64)[first:]
+    w, wl = np.ones(len(prec0)), np.ones(n_lc)
+    sk_all, st_all = prob.sk.copy(), prob.st.copy()
+
+    def weigh():  # the next solve's precisions: prec max(w, min_weight)
+        if f_rng:
+            prob.sw = np.sqrt(prec0 * np.maximum(w, min_weight))
+        if f_rel and n_lc:
+            f = np.maximum(wl, min_weight)
+            sk_all[first:], st_all[first:] = np.sqrt(kappa0 * f), np.sqrt(tau0 * f)
+            prob.sk, prob.st = sk_all, st_all
+
+    state = dict(u=u, dev=None, lm=0, f=0.0, g=np.inf)
+
+    def lm_run(iters):
+        res, J = prob.residuals(state["u"], jac=True)
+        f = float(res @ res)
+        if state["dev"] is None and linear_solver == "device" and prob.n > 0:
+            state["dev"] = _DeviceNormalEquations(prob, J, lib_path, solver_settings)
+        state["u"], state["f"], it, state["g"] = _lm_loop(prob, state["u"], res, J, f, 1e-6, iters, tol, False, state["dev"], pcg_rel_tol)
+        state["lm"] += it
+        return f
+
+    try:
+        cost_initial = lm_run(max_iters)  # solve 1: refine_estimate's
+        k, mu = 1, 0.0
+        while True:
+            seen = []
+            if f_rng:
+                r = range_residuals(prob, state["u"], prec0)
+                seen.append((len(r), float(np.max(r * r)) if len(r) else 0.0, c, _nonbinary(w)))
+            if f_rel:
+                rl = loop_closure_residuals(prob, state["u"], kappa0, tau0)
+                seen.append((len(rl), float(np.max(rl * rl)) if len(rl) else 0.0, c_rel, _nonbinary(wl)))
+            what = decide(k, max_outer, seen)
+            if what != "go":
+                break
+            mu = first_mu(seen) if k == 1 else mu * mu_step
+            if f_rng:
+                w = gnc_tls_weight(r, mu, c)
+            if f_rel:
+                wl = gnc_tls_weight(rl, mu, c_rel)
+            weigh()
+            k += 1
+            lm_run(inner_iters)
+        if k > 1 and what != "non_finite":  # the final weights, to max_iters / tol
+            lm_run(max_iters)
+        dev = state["dev"]
+        pcg = (dev.pcg_iters, dev.solves) if dev else (0, 0)
+    finally:
+        if state["dev"]:
+            state["dev"].close()
+    r = range_residuals(prob, state["u"], prec0)
+    rl = loop_closure_residuals(prob, state["u"], kappa0, tau0)
+    info = {"cost_initial": cost_initial, "cost_final": state["f"], "iterations": state["lm"], "grad_inf": state["g"],
+            "linear_solver": linear_solver, "engine": "python", "pcg_iters": pcg[0], "linear_solves": pcg[1]}
+    return state["u"], info, (w, r, wl, rl, k, mu, what == "converged")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# public interface
+# ---------------------------------------------------------------------------------------------------------------------
+def _check(inlier_threshold, c_rel, max_outer, inner_iters, min_weight, mu_step, engine, linear_solver, f_rng, f_rel) -> None:
+    if not f_rng and not f_rel:
+        raise ValueError("refine_estimate_robust: robust_ranges and robust_loop_closures are both off: nothing to re-weight")
+    if not (np.isfinite(inlier_threshold) and inlier_threshold > 0):
+        raise ValueError(f"inlier_threshold must be positive and finite, not {inlier_threshold}")
+    if not (np.isfinite(c_rel) and c_rel > 0):
+        raise ValueError(f"loop_closure_threshold must be positive and finite, not {c_rel}")
+    if int(max_outer) < 1:
+        raise ValueError(f"max_outer must be >= 1, not {max_outer}")
+    if int(inner_iters) < 1:
+        raise ValueError(f"inner_iters must be >= 1, not {inner_iters}")
+    if not (0.0 < min_weight <= 1.0):
+        raise ValueError(f"min_weight must lie in (0, 1], not {min_weight}")
+    if not (np.isfinite(mu_step) and mu_step > 1.0):
+        raise ValueError(f"mu_step must be finite and > 1, not {mu_step}")
+    if engine not in ("native", "python"):
+        raise ValueError("engine must be 'native' or 'python'")
+    if linear_solver not in ("device", "scipy"):
+        raise ValueError("linear_solver must be 'device' or 'scipy'")
+    if engine == "native" and linear_solver != "device":
+        raise ValueError("engine='native' solves on the device: linear_solver='scipy' goes with engine='python'")
+
+
+def _prior(weights, floor: float, enabled: bool):
+    """Prior weights as the precisions take them: those of a re-weighted family are floored like the loop's own weights (a
+    measurement the relaxation took out, weight 0, stays a term of precision prec * min_weight)."""
+    if weights is None or not enabled:
+        return weights
+    w = np.asarray(weights, dtype=np.float64)
+    return np.where(w < floor, floor, w) if np.all(np.isfinite(w)) and np.all(w >= 0) else w
+
+
+def refine_estimate_robust(data, results, inlier_threshold: float = 3.0, robust_ranges: bool = True, robust_loop_closures: bool = False,
+                           loop_closure_threshold: Optional[float] = None, max_outer: int = 50, inner_iters: int = 5,
+                           min_weight: float = 1e-6, mu_step: float = 1.4, max_iters: int = 50, tol: float = 1e-10,
+                           engine: str = "native", linear_solver: str = "device", range_weights=None, loop_closure_weights=None,
+                           lib_path: Optional[str] = None, solver_settings: Optional[dict] = None):
+    """``refine_estimate`` with GNC-TLS re-weighting of the ranges (``robust_ranges``) and / or the loop closures
+    (``robust_loop_closures``; threshold ``loop_closure_threshold``, None: ``inlier_threshold``) on the residuals of the
+    maximum-likelihood cost.  Returns ``(refined SolverResults, info)``: the keys of ``refine_estimate``'s info (``iterations``:
+    the Levenberg-Marquardt iterations of all solves) and ``info["robust"]`` with the keys of ``solve_score_robust``'s --
+    ``weights``, ``residuals`` (at the final estimate), ``outliers``, ``outer_iterations``, ``mu``, ``converged`` and, with the
+    loop closures on, ``loop_closure_weights`` / ``_residuals`` / ``_outliers``.  A graph without outliers takes one solve, and
+    its result is ``refine_estimate``'s.
+
+    ``range_weights`` / ``loop_closure_weights`` are prior weights (the relaxation's, say): they scale the measured precisions
+    before the loop as in ``refine_estimate`` -- a prior weight below ``min_weight`` in a re-weighted family counts as
+    ``min_weight`` there, so every precision stays positive -- and the returned weights are prior x GNC: they go straight into
+    ``marginal_covariances(..., range_weights=...)``.  ``engine="python"`` takes ``linear_solver="scipy"`` or ``"device"``;
+    ``engine="native"`` raises without the HIP library."""
+    f_rng, f_rel = bool(robust_ranges), bool(robust_loop_closures)
+    c = float(inlier_threshold)
+    c_rel = c if loop_closure_threshold is None else float(loop_closure_threshold)
+    _check(c, c_rel, max_outer, inner_iters, min_weight, mu_step, engine, linear_solver, f_rng, f_rel)
+    families = (FAMILY_RANGES if f_rng else 0) | (FAMILY_LOOP_CLOSURES if f_rel else 0)
+    pw, pwl = _prior(range_weights, float(min_weight), f_rng), _prior(loop_closure_weights, float(min_weight), f_rel)
+    if data.dimension == 3:
+        prob = _Problem3D(data, pw, pwl)
+        u = prob.initial_state(results)
+    else:
+        prob = _Problem(data, pw, pwl)
+        u = _initial_point(prob, results)
+    n_lc = n_loop_closures_of(prob.a)
+    if f_rng and len(prob.ra) and not (np.all(np.isfinite(prob.a["rng_prec"])) and np.all(np.asarray(prob.a["rng_prec"]) > 0)):
+        raise ValueError("refine_estimate_robust: every range precision must be positive and finite")
+    if f_rel:
+        if n_lc < 0:
+            raise ValueError("refine_estimate_robust: fewer relative-pose entries than odometry steps")
+        for key in ("rel_kappa", "rel_tau"):
+            v = np.asarray(prob.a[key], dtype=np.float64)[len(prob.bi) - n_lc:]
+            if v.size and not (np.all(np.isfinite(v)) and np.all(v > 0)):
+                raise ValueError(f"refine_estimate_robust: every loop closure's precision ({key}) must be positive and finite")
+    if engine == "native":
+        with RobustRefineHandle(prob, lib_path, solver_settings) as h:
+            rs = h.default_settings()
+            rs.inlier_threshold, rs.rel_threshold, rs.mu_step, rs.min_weight = c, c_rel, float(mu_step), float(min_weight)
+            rs.families, rs.max_outer, rs.inner_iters = families, int(max_outer), int(inner_iters)
+            rs.max_iters, rs.tol = int(max_iters), float(tol)
+            u, w, r, wl, rl, ni = h.robust_run(u, rs)
+        info = {"cost_initial": ni["cost_initial"], "cost_final": ni["cost_final"], "iterations": ni["lm_iterations"],
+                "grad_inf": ni["grad_inf"], "linear_solver": "device", "engine": "native", "pcg_iters": ni["pcg_iters"],
+                "linear_solves": ni["linear_solves"], "setup_ms": ni["setup_ms"], "solve_ms": ni["solve_ms"]}
+        k, mu, conv = ni["outer_iterations"], ni["mu"], bool(ni["converged"])
+    else:
+        u, info, (w, r, wl, rl, k, mu, conv) = _python_loop(prob, u, families, c, c_rel, int(max_outer), int(inner_iters), float(min_weight),
+                                                            float(mu_step), int(max_iters), float(tol), linear_solver, lib_path,
+                                                            solver_settings)
+    if range_weights is not None:  # prior x GNC
+        w = w * np.asarray(range_weights, dtype=np.float64)
+    if loop_closure_weights is not None:
+        wl = wl * np.asarray(loop_closure_weights, dtype=np.float64)
+    info["robust"] = _robust_info(w, r, k, mu, conv, wl if f_rel else None, rl if f_rel else None)
+    return _as_results(prob, u, results, info["cost_final"]), info
+
+
+__all__ = ["refine_estimate_robust", "RobustRefineHandle", "range_residuals", "loop_closure_residuals", "decide", "first_mu",
+           "REFINE_ROBUST_SYMBOLS"]
