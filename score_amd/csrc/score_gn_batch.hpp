@@ -1,0 +1,575 @@
+// score_gn_batch.hpp -- local refinement of a GROUP of graphs in lock-step (include/score_refine_batch.h).
+//
+// One union problem: member g owns the unknowns [col0_g, col0_g + n_g), H = J'J is block diagonal, and ONE linear-mode handle
+// on the union pattern -- its chain hint lists every member's chains -- gives derive_rho_data / k_factor / launch_prec<PREC_INIT>
+// for the whole group unchanged (M^-1 is block diagonal: chains and Jacobi columns never span members).  Per-member control:
+// every workgroup of every kernel here belongs to exactly one member (work is padded at member boundaries), tests that
+// member's mask or done word first, and writes nothing for a member that is masked out or done.
+//
+// The state holds every pose, pins included: 2-D [theta, x, y] per pose then the landmarks, 3-D [R | t] per pose then the
+// landmarks, member after member.  The cost functions of score_gn.hpp are called as they stand, and a member's measurements
+// are laid over workgroups exactly as k_gn_blocks lays them (local measurement m in the member's workgroup m / kThreads), so
+// a member's cost partials are those of a handle on it alone.
+//
+// The conjugate-gradient iteration (modelled on score_marginals.hpp, with "column" replaced by "member"):
+//   k_gb_product    w = H p over the tiles of the live members (64 short rows x 4 lanes, or one long row over the workgroup),
+//                   per-tile partials of p'w
+//   k_gb_step       alpha_g = r'z / p'w (both re-reduced from the member's partials in a fixed order); x += alpha p, r -= alpha w
+//   launch_prec     z = M^-1 r (the whole group; a done member's z is scratch)
+//   k_gb_rz         per-workgroup partials of r'z
+//   k_gb_direction  beta_g = r'z_new / r'z_old, p = z + beta p; the gate r'z_new <= rel_tol^2 r0'z0 raises the member's done word
+// Done words: 1 converged, 2 broken down (a non-finite r'z or p'w, or p'w <= 0) -- the member's solve reports failure.  No
+// atomics: all workgroups of a member reduce the same partials in the same order and take the same decision.
+#pragma once
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <stdexcept>
+#include <vector>
+
+#include "../../include/score_refine_batch.h"
+#include "score_gn.hpp"
+#include "score_kernels.hpp"
+
+namespace score {
+
+// ---------------------------------------------------------------------------
+// the controller: one state per member, the transitions as pure functions
+// ---------------------------------------------------------------------------
+enum GbPhase : int32_t { kGbGradient = 0, kGbSolve = 1, kGbStopped = 2 };
+
+struct GbState {
+    double f = 0, lam = 1e-6, gnorm = INFINITY, cost_initial = 0;
+    int32_t it = 1, attempts = 0, iterations = 0, linear_solves = 0, pcg_iters = 0;
+    GbPhase phase = kGbGradient;
+};
+
+inline void gb_stop(GbState& s, int max_iters) {
+    s.phase = kGbStopped;
+    s.iterations = std::min(s.it, (int32_t)max_iters);
+}
+// the member enters the loop with cost f at its start point
+inline void gb_begin(GbState& s, double f, int max_iters) {
+    s = GbState{};
+    s.f = s.cost_initial = f;
+    if (s.it > max_iters) gb_stop(s, max_iters);
+}
+// top of iteration s.it: the gradient of the current point is known
+inline void gb_after_gradient(GbState& s, double gnorm, double tol, int max_iters) {
+    s.gnorm = gnorm;
+    if (gnorm <= tol * std::max(1.0, s.f)) { gb_stop(s, max_iters); return; }
+    s.attempts = 0;
+    s.phase = kGbSolve;
+}
+// one attempt: the solve (ok, iterations used) and, where it succeeded, the cost at the trial point.  true: the step is
+// accepted (the trial point becomes the current one).
+inline bool gb_after_solve(GbState& s, bool ok, int used, double fn, int max_iters) {
+    s.linear_solves += 1;
+    s.pcg_iters += used;
+    if (ok && fn < s.f) {
+        const double dec = s.f - fn;
+        s.f = fn;
+        s.lam = std::max(s.lam * 0.1, 1e-12);
+        if (dec <= 1e-14 * std::max(1.0, s.f)) { gb_stop(s, max_iters); return true; }
+        s.it += 1;
+        if (s.it > max_iters) gb_stop(s, max_iters); else s.phase = kGbGradient;
+        return true;
+    }
+    s.lam *= 10.0;
+    s.attempts += 1;
+    if (s.attempts >= 12) gb_stop(s, max_iters);
+    return false;
+}
+
+// Backend concept (masks: one char per member):
+//   eval(mask, trial, with_blocks, cost_or_null)   blocks / cost of the current (or trial) point of the masked members
+//   gradient(mask, gnorm)                          g = J'r of the masked members from their blocks, |g|_inf
+//   solve(mask, lambda, rel_tol, ok, used)         (J'J + lambda_g I) step = -g for the masked members
+//   trial(mask)                                    trial = current + step;     accept(mask)  current = trial
+template <class Backend>
+inline int gb_lock_step(Backend& be, int count, int max_iters, double tol, double pcg_rel_tol, std::vector<GbState>& S) {
+    const size_t G = (size_t)count;
+    S.assign(G, GbState{});
+    std::vector<char> mask(G, 1), tmask(G), acc(G), ok(G);
+    std::vector<double> val(G, 0.0), lam(G, 0.0);
+    std::vector<int32_t> used(G, 0);
+    auto any = [](const std::vector<char>& m) { return std::find(m.begin(), m.end(), (char)1) != m.end(); };
+    be.eval(mask, false, true, val.data());
+    for (size_t g = 0; g < G; ++g) gb_begin(S[g], val[g], max_iters);
+    for (size_t g = 0; g < G; ++g) mask[g] = S[g].phase == kGbGradient;
+    if (any(mask)) {
+        be.gradient(mask, val.data());
+        for (size_t g = 0; g < G; ++g)
+            if (mask[g]) gb_after_gradient(S[g], val[g], tol, max_iters);
+    }
+    int rounds = 0;
+    for (;;) {
+        for (size_t g = 0; g < G; ++g) { mask[g] = S[g].phase == kGbSolve; lam[g] = S[g].lam; }
+        if (!any(mask)) break;
+        ++rounds;
+        be.solve(mask, lam.data(), pcg_rel_tol, ok.data(), used.data());
+        for (size_t g = 0; g < G; ++g) tmask[g] = mask[g] && ok[g];
+        if (any(tmask)) {
+            be.trial(tmask);
+            be.eval(tmask, true, false, val.data());
+        }
+        for (size_t g = 0; g < G; ++g) acc[g] = mask[g] ? (gb_after_solve(S[g], ok[g] != 0, used[g], val[g], max_iters) ? 1 : 0) : 0;
+        if (!any(acc)) continue;
+        be.accept(acc);
+        for (size_t g = 0; g < G; ++g) tmask[g] = acc[g] && S[g].phase == kGbGradient;
+        if (!any(tmask)) continue;
+        be.eval(tmask, false, true, nullptr);
+        be.gradient(tmask, val.data());
+        for (size_t g = 0; g < G; ++g)
+            if (tmask[g]) gb_after_gradient(S[g], val[g], tol, max_iters);
+    }
+    return rounds;
+}
+
+// ---------------------------------------------------------------------------
+// the union problem
+// ---------------------------------------------------------------------------
+constexpr int kGbLanes = 4;                       // lanes of a short row
+constexpr int kGbRows = kThreads / kGbLanes;      // short rows of a product tile
+constexpr int kGbLongRow = 128;                   // entries beyond which a row is a tile of its own
+
+struct GbMember {  // where member g lives in the union arrays
+    long long Np, Nl, n, n_rel, n_rng, n_pri;
+    long long rel0, rng0, pri0;        // first entry in the measurement arrays
+    long long state0, col0;            // first scalar of its state, its first unknown
+    long long hblk0, gblk0;            // first slot of its block storage
+    long long pose0, lm0;              // first scalar in the caller's pose / landmark arrays
+    int mblk0, mblk1, ublk0, ublk1, sblk0, sblk1, tile0, tile1;  // its workgroups: measurements, unknowns, variables, product tiles
+};
+
+struct GbUnion {
+    int dim = 2, count = 0;
+    long long n = 0, state_size = 0, hblk_size = 0, gblk_size = 0, poses_size = 0, lms_size = 0;
+    std::vector<GbMember> members;
+    std::vector<int32_t> rel_i, rel_j, rng_a, rng_b, pri_l;
+    std::vector<double> rel_t, rel_R, rel_kappa, rel_tau, rng_dist, rng_prec, pri_t, pri_prec;
+    std::vector<int32_t> hptr, hcol, hc_ptr, hc_slot, gc_ptr, gc_slot, diag_member;  // diag_member[k]: member + 1 on a diagonal entry, else 0
+    std::vector<int32_t> chain_ptr, node_first_col;
+    std::vector<int32_t> mblk_member, ublk_member, sblk_member;
+    std::vector<int4> tiles;  // {first row, end row, long row?, member}
+    int dp() const { return dim == 2 ? 3 : 6; }
+    int pose_scalars() const { return dim == 2 ? 3 : 12; }
+};
+
+template <class T>
+inline void gb_append(std::vector<T>& dst, const std::vector<T>& src) { dst.insert(dst.end(), src.begin(), src.end()); }
+
+// gn_build member by member, the members' patterns and contribution lists laid one after the other with offsets
+inline void gb_build(const score_graph* graphs, int count, GbUnion& U) {
+    if (count <= 0 || !graphs) throw std::runtime_error("score_refine_batch: no graphs");
+    U = GbUnion{};
+    U.dim = graphs[0].dim;
+    U.count = count;
+    U.hptr.assign(1, 0); U.hc_ptr.assign(1, 0); U.gc_ptr.assign(1, 0); U.chain_ptr.assign(1, 0);
+    const long long lim = (long long)1 << 31;
+    for (int g = 0; g < count; ++g) {
+        if (graphs[g].dim != U.dim) throw std::runtime_error("score_refine_batch: the graphs of a group must share dim");
+        GnProblem P;
+        gn_build(graphs[g], P);
+        if (P.n <= 0) throw std::runtime_error("score_refine_batch: a member has no unknowns");
+        GbMember M{};
+        M.Np = P.Np; M.Nl = P.Nl; M.n = P.n; M.n_rel = P.n_rel(); M.n_rng = P.n_rng(); M.n_pri = P.n_pri();
+        M.rel0 = (long long)U.rel_i.size(); M.rng0 = (long long)U.rng_a.size(); M.pri0 = (long long)U.pri_l.size();
+        M.state0 = U.state_size; M.col0 = U.n; M.hblk0 = U.hblk_size; M.gblk0 = U.gblk_size;
+        M.pose0 = U.poses_size; M.lm0 = U.lms_size;
+        const long long nnz0 = (long long)U.hcol.size(), hs0 = (long long)U.hc_slot.size(), gs0 = (long long)U.gc_slot.size();
+        if (M.col0 + P.n >= lim / 64 || nnz0 + (long long)P.hcol.size() >= lim || hs0 + (long long)P.hc_slot.size() >= lim ||
+            M.hblk0 + P.hblk_size() >= lim || M.state0 + (long long)U.pose_scalars() * P.Np + U.dim * P.Nl >= lim)
+            throw std::runtime_error("score_refine_batch: the group is too large for 32-bit positions (use smaller groups)");
+        gb_append(U.rel_i, P.rel_i); gb_append(U.rel_j, P.rel_j); gb_append(U.rng_a, P.rng_a); gb_append(U.rng_b, P.rng_b);
+        gb_append(U.pri_l, P.pri_l); gb_append(U.rel_t, P.rel_t); gb_append(U.rel_R, P.rel_R); gb_append(U.rel_kappa, P.rel_kappa);
+        gb_append(U.rel_tau, P.rel_tau); gb_append(U.rng_dist, P.rng_dist); gb_append(U.rng_prec, P.rng_prec);
+        gb_append(U.pri_t, P.pri_t); gb_append(U.pri_prec, P.pri_prec);
+        for (long long i = 0; i < P.n; ++i) {
+            U.hptr.push_back((int32_t)(nnz0 + P.hptr[(size_t)i + 1]));
+            U.gc_ptr.push_back((int32_t)(gs0 + P.gc_ptr[(size_t)i + 1]));
+        }
+        for (size_t k = 0; k < P.hcol.size(); ++k) {
+            U.hcol.push_back((int32_t)(M.col0 + P.hcol[k]));
+            U.hc_ptr.push_back((int32_t)(hs0 + P.hc_ptr[k + 1]));
+        }
+        U.diag_member.resize(U.hcol.size(), 0);
+        for (long long i = 0; i < P.n; ++i) U.diag_member[(size_t)(nnz0 + P.diag_pos[(size_t)i])] = g + 1;
+        for (int32_t s : P.hc_slot) U.hc_slot.push_back((int32_t)(M.hblk0 + s));
+        for (int32_t s : P.gc_slot) U.gc_slot.push_back((int32_t)(M.gblk0 + s));
+        const int32_t node0 = U.chain_ptr.back();
+        for (size_t c = 1; c < P.chain_ptr.size(); ++c) U.chain_ptr.push_back(node0 + P.chain_ptr[c]);
+        for (int32_t c : P.node_first_col) U.node_first_col.push_back((int32_t)(M.col0 + c));
+        // workgroups: measurements, unknowns, variables -- kThreads each, never across a member boundary
+        auto blocks = [](long long items) { return (int)std::max<long long>(1, (items + kThreads - 1) / kThreads); };
+        M.mblk0 = (int)U.mblk_member.size(); U.mblk_member.insert(U.mblk_member.end(), (size_t)blocks(P.n_meas()), g); M.mblk1 = (int)U.mblk_member.size();
+        M.ublk0 = (int)U.ublk_member.size(); U.ublk_member.insert(U.ublk_member.end(), (size_t)blocks(P.n), g); M.ublk1 = (int)U.ublk_member.size();
+        M.sblk0 = (int)U.sblk_member.size(); U.sblk_member.insert(U.sblk_member.end(), (size_t)blocks(P.Np + P.Nl), g); M.sblk1 = (int)U.sblk_member.size();
+        // product tiles of the member's rows
+        M.tile0 = (int)U.tiles.size();
+        auto len = [&](long long i) { return P.hptr[(size_t)i + 1] - P.hptr[(size_t)i]; };
+        long long row = 0;
+        while (row < P.n) {
+            if (len(row) > kGbLongRow) { U.tiles.push_back(make_int4((int)(M.col0 + row), (int)(M.col0 + row + 1), 1, g)); ++row; continue; }
+            long long end = row;
+            while (end < P.n && end - row < kGbRows && len(end) <= kGbLongRow) ++end;
+            U.tiles.push_back(make_int4((int)(M.col0 + row), (int)(M.col0 + end), 0, g));
+            row = end;
+        }
+        M.tile1 = (int)U.tiles.size();
+        U.n += P.n;
+        U.state_size += (long long)U.pose_scalars() * P.Np + (long long)U.dim * P.Nl;
+        U.hblk_size += P.hblk_size(); U.gblk_size += P.gblk_size();
+        U.poses_size += (long long)U.pose_scalars() * P.Np; U.lms_size += (long long)U.dim * P.Nl;
+        U.members.push_back(M);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// device side
+// ---------------------------------------------------------------------------
+struct GbDev {
+    const GbMember* members;
+    const int32_t *mblk_member, *ublk_member, *sblk_member;
+    const int32_t *rel_i, *rel_j, *rng_a, *rng_b, *pri_l;
+    const double *rel_t, *rel_R, *rel_kappa, *rel_tau, *rng_dist, *rng_prec, *pri_t, *pri_prec;
+};
+
+// one measurement per lane (2-D): cost partial of the workgroup and, with_blocks, its J'J / J'r block
+__global__ __launch_bounds__(kThreads) void k_gb_blocks(GbDev d, const double* __restrict__ X, double* __restrict__ hblk,
+                                                        double* __restrict__ gblk, double* __restrict__ cost_part,
+                                                        const int32_t* __restrict__ mask, int with_blocks) {
+    __shared__ double red[8];
+    const int g = d.mblk_member[blockIdx.x];
+    if (!mask[g]) return;
+    const GbMember M = d.members[g];
+    const double* Xg = X + M.state0;
+    const long long m = (long long)((int)blockIdx.x - M.mblk0) * kThreads + threadIdx.x;
+    double cost = 0.0;
+    if (m < M.n_rel) {
+        const long long e = M.rel0 + m;
+        const double* pi = Xg + 3 * (long long)d.rel_i[e];
+        const double* pj = Xg + 3 * (long long)d.rel_j[e];
+        double H[36], gv[6];
+        cost = gn_rel_block(pi[0], pi[1], pi[2], pj[0], pj[1], pj[2], d.rel_t + 2 * e, d.rel_R + 4 * e, d.rel_kappa[e], d.rel_tau[e],
+                            with_blocks ? H : nullptr, gv);
+        if (with_blocks) {
+            double* ho = hblk + M.hblk0 + 36 * m;
+            double* go = gblk + M.gblk0 + 6 * m;
+#pragma unroll
+            for (int k = 0; k < 36; ++k) ho[k] = H[k];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) go[k] = gv[k];
+        }
+    } else if (m < M.n_rel + M.n_rng) {
+        const long long r = m - M.n_rel, e = M.rng0 + r;
+        const long long va = d.rng_a[e], vb = d.rng_b[e];
+        const double* pa = va < M.Np ? Xg + 3 * va + 1 : Xg + 3 * M.Np + 2 * (va - M.Np);
+        const double* pb = vb < M.Np ? Xg + 3 * vb + 1 : Xg + 3 * M.Np + 2 * (vb - M.Np);
+        double H[16], gv[4];
+        cost = gn_range_block(pa[0], pa[1], pb[0], pb[1], d.rng_dist[e], d.rng_prec[e], with_blocks ? H : nullptr, gv);
+        if (with_blocks) {
+            double* ho = hblk + M.hblk0 + 36 * M.n_rel + 16 * r;
+            double* go = gblk + M.gblk0 + 6 * M.n_rel + 4 * r;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) ho[k] = H[k];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) go[k] = gv[k];
+        }
+    } else if (m < M.n_rel + M.n_rng + M.n_pri) {
+        const long long q = m - M.n_rel - M.n_rng, e = M.pri0 + q;
+        const double* l = Xg + 3 * M.Np + 2 * (long long)d.pri_l[e];
+        double H[2], gv[2];
+        cost = gn_prior_block(l[0], l[1], d.pri_t + 2 * e, d.pri_prec[e], with_blocks ? H : nullptr, gv);
+        if (with_blocks) {
+            double* ho = hblk + M.hblk0 + 36 * M.n_rel + 16 * M.n_rng + 2 * q;
+            double* go = gblk + M.gblk0 + 6 * M.n_rel + 4 * M.n_rng + 2 * q;
+            ho[0] = H[0]; ho[1] = H[1]; go[0] = gv[0]; go[1] = gv[1];
+        }
+    }
+    const double tot = block_sum(cost, red);
+    if (threadIdx.x == 0) cost_part[blockIdx.x] = tot;
+}
+
+// 3-D: blocks 12 x 12 / 6 x 6 / 3
+__global__ __launch_bounds__(kThreads) void k_gb_blocks3(GbDev d, const double* __restrict__ X, double* __restrict__ hblk,
+                                                         double* __restrict__ gblk, double* __restrict__ cost_part,
+                                                         const int32_t* __restrict__ mask, int with_blocks) {
+    __shared__ double red[8];
+    const int g = d.mblk_member[blockIdx.x];
+    if (!mask[g]) return;
+    const GbMember M = d.members[g];
+    const double* Xg = X + M.state0;
+    const long long m = (long long)((int)blockIdx.x - M.mblk0) * kThreads + threadIdx.x;
+    double cost = 0.0;
+    if (m < M.n_rel) {
+        const long long e = M.rel0 + m;
+        double Xi[12], Xj[12], H[144], gv[12];
+        const double* pi = Xg + 12 * (long long)d.rel_i[e];
+        const double* pj = Xg + 12 * (long long)d.rel_j[e];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) { Xi[k] = pi[k]; Xj[k] = pj[k]; }
+        cost = gn_rel_block3(Xi, Xj, d.rel_t + 3 * e, d.rel_R + 9 * e, d.rel_kappa[e], d.rel_tau[e], with_blocks ? H : nullptr, gv);
+        if (with_blocks) {
+            double* ho = hblk + M.hblk0 + 144 * m;
+            double* go = gblk + M.gblk0 + 12 * m;
+            for (int k = 0; k < 144; ++k) ho[k] = H[k];
+#pragma unroll
+            for (int k = 0; k < 12; ++k) go[k] = gv[k];
+        }
+    } else if (m < M.n_rel + M.n_rng) {
+        const long long r = m - M.n_rel, e = M.rng0 + r;
+        const double* pa = gn_point3(Xg, M.Np, d.rng_a[e]);
+        const double* pb = gn_point3(Xg, M.Np, d.rng_b[e]);
+        const double a3[3] = {pa[0], pa[1], pa[2]}, b3[3] = {pb[0], pb[1], pb[2]};
+        double H[36], gv[6];
+        cost = gn_range_block3(a3, b3, d.rng_dist[e], d.rng_prec[e], with_blocks ? H : nullptr, gv);
+        if (with_blocks) {
+            double* ho = hblk + M.hblk0 + 144 * M.n_rel + 36 * r;
+            double* go = gblk + M.gblk0 + 12 * M.n_rel + 6 * r;
+#pragma unroll
+            for (int k = 0; k < 36; ++k) ho[k] = H[k];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) go[k] = gv[k];
+        }
+    } else if (m < M.n_rel + M.n_rng + M.n_pri) {
+        const long long q = m - M.n_rel - M.n_rng, e = M.pri0 + q;
+        const double* l = Xg + 12 * M.Np + 3 * (long long)d.pri_l[e];
+        const double l3[3] = {l[0], l[1], l[2]};
+        double H[3], gv[3];
+        cost = gn_prior_block3(l3, d.pri_t + 3 * e, d.pri_prec[e], with_blocks ? H : nullptr, gv);
+        if (with_blocks) {
+            double* ho = hblk + M.hblk0 + 144 * M.n_rel + 36 * M.n_rng + 3 * q;
+            double* go = gblk + M.gblk0 + 12 * M.n_rel + 6 * M.n_rng + 3 * q;
+            for (int k = 0; k < 3; ++k) { ho[k] = H[k]; go[k] = gv[k]; }
+        }
+    }
+    const double tot = block_sum(cost, red);
+    if (threadIdx.x == 0) cost_part[blockIdx.x] = tot;
+}
+
+// one variable (pose or landmark) per lane: Xt = X (+ step) on the masked members.  step == nullptr: the copy of `accept`
+// (dst = X, src = Xt).  The pinned pose of a member has no step.
+template <int DIM>
+__global__ __launch_bounds__(kThreads) void k_gb_trial(GbDev d, const double* __restrict__ src, const double* __restrict__ step,
+                                                       double* __restrict__ dst, const int32_t* __restrict__ mask) {
+    constexpr int PS = DIM == 2 ? 3 : 12, DP = DIM == 2 ? 3 : 6;
+    const int g = d.sblk_member[blockIdx.x];
+    if (!mask[g]) return;
+    const GbMember M = d.members[g];
+    const long long i = (long long)((int)blockIdx.x - M.sblk0) * kThreads + threadIdx.x;
+    if (i < M.Np) {
+        const double* in = src + M.state0 + PS * i;
+        double* out = dst + M.state0 + PS * i;
+        if (!step || i == 0) {
+#pragma unroll
+            for (int k = 0; k < PS; ++k) out[k] = in[k];
+        } else if (DIM == 2) {
+            const double* st = step + M.col0 + DP * (i - 1);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) out[k] = in[k] + st[k];
+        } else {
+            double a[12], s6[6], o[12];
+#pragma unroll
+            for (int k = 0; k < 12; ++k) a[k] = in[k];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) s6[k] = step[M.col0 + DP * (i - 1) + k];
+            gn_pose3_retract(a, s6, o);
+#pragma unroll
+            for (int k = 0; k < 12; ++k) out[k] = o[k];
+        }
+    } else if (i < M.Np + M.Nl) {
+        const long long l = i - M.Np;
+        const double* in = src + M.state0 + PS * M.Np + DIM * l;
+        double* out = dst + M.state0 + PS * M.Np + DIM * l;
+        const double* st = step ? step + M.col0 + DP * (M.Np - 1) + DIM * l : nullptr;
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) out[k] = st ? in[k] + st[k] : in[k];
+    }
+}
+
+// one entry of H per lane: the sum of its block slots in list order (+ the member's lambda on the diagonal)
+__global__ __launch_bounds__(kThreads) void k_gb_gather_h(const int32_t* __restrict__ hc_ptr, const int32_t* __restrict__ hc_slot,
+                                                          const double* __restrict__ hblk, const int32_t* __restrict__ diag_member,
+                                                          const double* __restrict__ lambda, double* __restrict__ out, long long nnz) {
+    const long long k = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (k >= nnz) return;
+    double acc = 0.0;
+    for (int32_t c = hc_ptr[k]; c < hc_ptr[k + 1]; ++c) acc += hblk[hc_slot[c]];
+    const int dm = diag_member[k];
+    out[k] = dm ? acc + lambda[dm - 1] : acc;
+}
+
+// one unknown per lane, on the masked members: g = J'r, rhs = -g, workgroup partial of |g|_inf
+__global__ __launch_bounds__(kThreads) void k_gb_gather_g(GbDev d, const int32_t* __restrict__ gc_ptr, const int32_t* __restrict__ gc_slot,
+                                                          const double* __restrict__ gblk, double* __restrict__ rhs,
+                                                          double* __restrict__ gmax_part, const int32_t* __restrict__ mask) {
+    __shared__ double red[8];
+    const int g = d.ublk_member[blockIdx.x];
+    if (!mask[g]) return;
+    const GbMember M = d.members[g];
+    const long long li = (long long)((int)blockIdx.x - M.ublk0) * kThreads + threadIdx.x;
+    double a = 0.0;
+    if (li < M.n) {
+        const long long i = M.col0 + li;
+        double acc = 0.0;
+        for (int32_t c = gc_ptr[i]; c < gc_ptr[i + 1]; ++c) acc += gblk[gc_slot[c]];
+        rhs[i] = -acc;
+        a = acc == acc ? fabs(acc) : INFINITY;
+    }
+    const double mx = block_max(a, red);
+    if (threadIdx.x == 0) gmax_part[blockIdx.x] = mx;
+}
+
+// ---- the conjugate-gradient iteration, member by member ----
+struct GbPcg {
+    GbDev d;
+    const int32_t* ptr; const int32_t* col; const double* val;   // H on the union pattern
+    const int4* tiles;
+    int32_t* done;             // [member] done word
+    int32_t* iters;            // [member] steps executed
+    double* x; double* r; const double* z; double* p; double* w;
+    const double* rhs;
+    double* pw_part;           // [tile]
+    double* rz_part;           // [unknown workgroup]: k_gb_rz writes
+    const double* rz_new;      // partials of the last application of M^-1
+    const double* rz_old;
+    int first;                 // direction: p = z, the gate's threshold is set
+    double tol2;
+    double* ref;               // [member] rel_tol^2 r0'z0
+};
+
+__device__ __forceinline__ bool gb_finite(double v) { return fabs(v) <= 1.79769313486231570e308; }
+
+// x = 0, r = rhs on the members about to be solved (done word 0)
+__global__ __launch_bounds__(kThreads) void k_gb_pcg_begin(GbPcg a) {
+    const int g = a.d.ublk_member[blockIdx.x];
+    if (a.done[g]) return;
+    const GbMember M = a.d.members[g];
+    const long long li = (long long)((int)blockIdx.x - M.ublk0) * kThreads + threadIdx.x;
+    if (li < M.n) {
+        a.x[M.col0 + li] = 0.0;
+        a.r[M.col0 + li] = a.rhs[M.col0 + li];
+    }
+}
+
+// w = H p on the tiles of the live members, per-tile partial of p'w
+__global__ __launch_bounds__(kThreads) void k_gb_product(GbPcg a) {
+    __shared__ double red[4];
+    const int4 tile = a.tiles[blockIdx.x];
+    if (a.done[tile.w]) return;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    double acc = 0.0;
+    if (tile.z) {  // one long row over the workgroup
+        const int row = tile.x;
+        const int k1 = a.ptr[row + 1];
+        for (int k = a.ptr[row] + t; k < k1; k += kThreads) acc += a.val[k] * a.p[a.col[k]];
+        const double s = wave_sum(acc);
+        if (lane == 0) red[wave] = s;
+        __syncthreads();
+        if (t == 0) {
+            const double wv = (red[0] + red[1]) + (red[2] + red[3]);
+            a.w[row] = wv;
+            a.pw_part[blockIdx.x] = a.p[row] * wv;
+        }
+        return;
+    }
+    // short rows: kGbLanes lanes per row, their sums joined as (l0 + l1) + (l2 + l3)
+    const int row = tile.x + t / kGbLanes, sub = t % kGbLanes;
+    const bool mine = row < tile.y;
+    if (mine) {
+        const int k1 = a.ptr[row + 1];
+        for (int k = a.ptr[row] + sub; k < k1; k += kGbLanes) acc += a.val[k] * a.p[a.col[k]];
+    }
+    double s = acc;
+    s += __shfl_xor(s, 1, 64);
+    s += __shfl_xor(s, 2, 64);
+    double pw = 0.0;
+    if (mine && sub == 0) {
+        a.w[row] = s;
+        pw = a.p[row] * s;
+    }
+    pw = wave_sum(pw);
+    if (lane == 0) red[wave] = pw;
+    __syncthreads();
+    if (t == 0) a.pw_part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// alpha = r'z / p'w of the workgroup's member ; x += alpha p ; r -= alpha w
+__global__ __launch_bounds__(kThreads) void k_gb_step(GbPcg a) {
+    __shared__ double red[8];
+    const int g = a.d.ublk_member[blockIdx.x], t = threadIdx.x;
+    if (a.done[g]) return;
+    const GbMember M = a.d.members[g];
+    double rz = 0.0, pw = 0.0;
+    for (int i = M.ublk0 + t; i < M.ublk1; i += kThreads) rz += a.rz_new[i];
+    for (int i = M.tile0 + t; i < M.tile1; i += kThreads) pw += a.pw_part[i];
+    block_sum2(rz, pw, red);
+    const bool lead = (int)blockIdx.x == M.ublk0 && t == 0;
+    if (!(gb_finite(rz) && gb_finite(pw) && pw > 0.0)) {
+        if (lead) a.done[g] = 2;
+        return;
+    }
+    const double alpha = rz / pw;
+    const long long li = (long long)((int)blockIdx.x - M.ublk0) * kThreads + t;
+    if (li < M.n) {
+        const long long e = M.col0 + li;
+        a.x[e] += alpha * a.p[e];
+        a.r[e] -= alpha * a.w[e];
+    }
+    if (lead) a.iters[g] += 1;
+}
+
+// per-workgroup partials of r'z on the live members
+__global__ __launch_bounds__(kThreads) void k_gb_rz(GbPcg a) {
+    __shared__ double red[4];
+    const int g = a.d.ublk_member[blockIdx.x], t = threadIdx.x;
+    if (a.done[g]) return;
+    const GbMember M = a.d.members[g];
+    const long long li = (long long)((int)blockIdx.x - M.ublk0) * kThreads + t;
+    double v = 0.0;
+    if (li < M.n) v = a.r[M.col0 + li] * a.z[M.col0 + li];
+    const double s = block_sum(v, red);
+    if (t == 0) a.rz_part[blockIdx.x] = s;
+}
+
+// the gate of the workgroup's member, then p = z + beta p (first: p = z and the gate's threshold)
+__global__ __launch_bounds__(kThreads) void k_gb_direction(GbPcg a) {
+    __shared__ double red[8];
+    const int g = a.d.ublk_member[blockIdx.x], t = threadIdx.x;
+    if (a.done[g]) return;
+    const GbMember M = a.d.members[g];
+    double rzn = 0.0, rzo = 0.0;
+    for (int i = M.ublk0 + t; i < M.ublk1; i += kThreads) {
+        rzn += a.rz_new[i];
+        if (!a.first) rzo += a.rz_old[i];
+    }
+    block_sum2(rzn, rzo, red);
+    const bool lead = (int)blockIdx.x == M.ublk0 && t == 0;
+    double beta = 0.0;
+    if (a.first) {
+        if (!(gb_finite(rzn) && rzn > 0.0)) {  // (a zero right-hand side is solved by x = 0)
+            if (lead) a.done[g] = rzn == 0.0 ? 1 : 2;
+            return;
+        }
+        if (lead) a.ref[g] = a.tol2 * rzn;
+    } else {
+        if (!(gb_finite(rzn) && rzo > 0.0)) {
+            if (lead) a.done[g] = 2;
+            return;
+        }
+        if (rzn <= a.ref[g]) {
+            if (lead) a.done[g] = 1;
+            return;
+        }
+        beta = rzn / rzo;
+    }
+    const long long li = (long long)((int)blockIdx.x - M.ublk0) * kThreads + t;
+    if (li < M.n) {
+        const long long e = M.col0 + li;
+        a.p[e] = a.first ? a.z[e] : a.z[e] + beta * a.p[e];
+    }
+}
+
+}  // namespace score

@@ -4328,6 +4328,242 @@ struct score_refine {
     }
 };
 
+#include "score_gn_batch.hpp"
+
+// Local refinement of a group of graphs in lock-step (score_gn_batch.hpp): the union state, blocks and gathers here, the
+// chain factorisation and M^-1 through the linear-mode handle `lin` on the union pattern, the per-member conjugate-gradient
+// iteration in the k_gb_* kernels.  This struct is the backend of gb_lock_step.
+struct score_refine_batch {
+    score::GbUnion U;
+    score_handle* lin = nullptr;
+    int device = 0;
+    double setup_ms = 0;
+    int rounds = 0;  // of the last run
+    DevBuf<score::GbMember> members;
+    DevBuf<int4> tiles;
+    DevBuf<int32_t> mblk_member, ublk_member, sblk_member, rel_i, rel_j, rng_a, rng_b, pri_l, hc_ptr, hc_slot, gc_ptr, gc_slot, diag_member;
+    DevBuf<int32_t> mask, flags;  // flags: [done per member | steps per member | a zero (the chain kernel's done word)]
+    DevBuf<double> rel_t, rel_R, rel_kappa, rel_tau, rng_dist, rng_prec, pri_t, pri_prec;
+    DevBuf<double> X, Xt, hblk, gblk, rhs, cost_part, gmax_part, lambda;
+    DevBuf<double> x, r, z, p, w, scratch, pw_part, rz0, rz1, rz_prec, ref;
+    int n_mblocks = 0, n_ublocks = 0, n_sblocks = 0, n_hblocks = 0, n_tiles = 0;
+    long long nnz = 0;
+    std::vector<double> part_host;
+    std::vector<int32_t> word_host;
+
+    HipBackend& be() { return lin->solver.be; }
+    hipStream_t stream() { return lin->solver.be.stream; }
+    int count() const { return U.count; }
+    score::GbDev dev() const {
+        score::GbDev d{};
+        d.members = members.d; d.mblk_member = mblk_member.d; d.ublk_member = ublk_member.d; d.sblk_member = sblk_member.d;
+        d.rel_i = rel_i.d; d.rel_j = rel_j.d; d.rng_a = rng_a.d; d.rng_b = rng_b.d; d.pri_l = pri_l.d;
+        d.rel_t = rel_t.d; d.rel_R = rel_R.d; d.rel_kappa = rel_kappa.d; d.rel_tau = rel_tau.d;
+        d.rng_dist = rng_dist.d; d.rng_prec = rng_prec.d; d.pri_t = pri_t.d; d.pri_prec = pri_prec.d;
+        return d;
+    }
+    void create(const score_graph* graphs, int32_t n_graphs, const score_settings* s) {
+        const double t0 = score::now_ms();
+        score::PhaseTimer pt(s && s->verbose != 0);
+        score::gb_build(graphs, n_graphs, U);
+        pt.mark("refine batch: union pattern + contribution lists");
+        score_problem pat{};
+        pat.n = (int32_t)U.n; pat.m = 0;
+        pat.P_rowptr = U.hptr.data(); pat.P_col = U.hcol.data();
+        pat.block_size = 3; pat.n_chains = (int32_t)U.chain_ptr.size() - 1;
+        pat.chain_ptr = U.chain_ptr.data(); pat.node_first_col = U.node_first_col.data();
+        if (score_linear_create(&pat, s, &lin) != 0) throw std::runtime_error(g_err);
+        pt.mark("refine batch: linear-mode handle");
+        device = lin->solver.st.device;
+        if (be().split.active) throw std::runtime_error("score_refine_batch: the group needs the unsplit chain kernel (chain_split = 0)");
+        if (be().n_prec == 0) throw std::runtime_error("score_refine_batch: the handle has no preconditioner work (no pose chains?)");
+        tl_copy_stream = stream();
+        struct ArenaScope {  // the group's buffers come from (and go back with) the handle's arena
+            explicit ArenaScope(DevArena* a) { tl_arena = a; }
+            ~ArenaScope() { tl_arena = nullptr; }
+        } arena_scope(&be().arena);
+        members.upload(U.members); tiles.upload(U.tiles);
+        mblk_member.upload(U.mblk_member); ublk_member.upload(U.ublk_member); sblk_member.upload(U.sblk_member);
+        rel_i.upload(U.rel_i); rel_j.upload(U.rel_j); rng_a.upload(U.rng_a); rng_b.upload(U.rng_b); pri_l.upload(U.pri_l);
+        rel_t.upload(U.rel_t); rel_R.upload(U.rel_R); rel_kappa.upload(U.rel_kappa); rel_tau.upload(U.rel_tau);
+        rng_dist.upload(U.rng_dist); rng_prec.upload(U.rng_prec); pri_t.upload(U.pri_t); pri_prec.upload(U.pri_prec);
+        hc_ptr.upload(U.hc_ptr); hc_slot.upload(U.hc_slot); gc_ptr.upload(U.gc_ptr); gc_slot.upload(U.gc_slot);
+        diag_member.upload(U.diag_member);
+        n_mblocks = (int)U.mblk_member.size(); n_ublocks = (int)U.ublk_member.size(); n_sblocks = (int)U.sblk_member.size();
+        n_tiles = (int)U.tiles.size();
+        nnz = (long long)U.hcol.size();
+        n_hblocks = (int)std::max<long long>(1, (nnz + kThreads - 1) / kThreads);
+        const size_t G = (size_t)U.count, n = (size_t)U.n;
+        X.alloc((size_t)U.state_size); Xt.alloc((size_t)U.state_size);
+        hblk.alloc((size_t)std::max<long long>(1, U.hblk_size)); gblk.alloc((size_t)std::max<long long>(1, U.gblk_size));
+        cost_part.alloc((size_t)n_mblocks); gmax_part.alloc((size_t)n_ublocks); lambda.alloc(G);
+        mask.alloc(G); flags.alloc(2 * G + 1);
+        DevBuf<double>* vecs[] = {&rhs, &x, &r, &z, &p, &w, &scratch};
+        for (DevBuf<double>* v : vecs) { v->alloc(n); v->zero(stream()); }
+        pw_part.alloc((size_t)n_tiles); pw_part.zero(stream());
+        rz0.alloc((size_t)n_ublocks); rz0.zero(stream());
+        rz1.alloc((size_t)n_ublocks); rz1.zero(stream());
+        // (every workgroup of a chain-kernel launch has a slot for its partial of r'z: written, never read here)
+        rz_prec.alloc((size_t)be().n_prec + 4096); rz_prec.zero(stream());
+        ref.alloc(G); ref.zero(stream());
+        flags.zero(stream());
+        be().linear_buffers(lin->solver.H);
+        HIP_CHECK(sync_stream(stream()));
+        // the lists live on the device now
+        for (std::vector<int32_t>* v : {&U.hptr, &U.hcol, &U.hc_ptr, &U.hc_slot, &U.gc_ptr, &U.gc_slot, &U.diag_member, &U.rel_i, &U.rel_j,
+                                        &U.rng_a, &U.rng_b, &U.pri_l, &U.chain_ptr, &U.node_first_col})
+            std::vector<int32_t>().swap(*v);
+        for (std::vector<double>* v : {&U.rel_t, &U.rel_R, &U.rel_kappa, &U.rel_tau, &U.rng_dist, &U.rng_prec, &U.pri_t, &U.pri_prec})
+            std::vector<double>().swap(*v);
+        pt.mark("refine batch: uploads + buffers");
+        setup_ms = score::now_ms() - t0;
+    }
+    ~score_refine_batch() { if (lin) score_destroy(lin); }
+
+    void set_mask(const std::vector<char>& m) {
+        word_host.assign(m.begin(), m.end());
+        HIP_CHECK(hipMemcpyAsync(mask.d, word_host.data(), word_host.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream()));
+        HIP_CHECK(sync_stream(stream()));
+    }
+    // ---- the backend concept of gb_lock_step ----
+    void eval(const std::vector<char>& m, bool trial, bool with_blocks, double* cost) {
+        set_mask(m);
+        const double* where = trial ? Xt.d : X.d;
+        if (U.dim == 2)
+            hipLaunchKernelGGL(score::k_gb_blocks, dim3(n_mblocks), dim3(kThreads), 0, stream(), dev(), where, hblk.d, gblk.d, cost_part.d,
+                               (const int32_t*)mask.d, with_blocks ? 1 : 0);
+        else
+            hipLaunchKernelGGL(score::k_gb_blocks3, dim3(n_mblocks), dim3(kThreads), 0, stream(), dev(), where, hblk.d, gblk.d, cost_part.d,
+                               (const int32_t*)mask.d, with_blocks ? 1 : 0);
+        HIP_CHECK(hipGetLastError());
+        if (!cost) return;
+        part_host.resize((size_t)n_mblocks);
+        HIP_CHECK(hipMemcpyAsync(part_host.data(), cost_part.d, (size_t)n_mblocks * sizeof(double), hipMemcpyDeviceToHost, stream()));
+        HIP_CHECK(sync_stream(stream()));
+        for (int g = 0; g < U.count; ++g) {
+            if (!m[(size_t)g]) continue;
+            double f = 0.0;  // the member's partials in workgroup order: the sum a handle on it alone forms
+            for (int b = U.members[(size_t)g].mblk0; b < U.members[(size_t)g].mblk1; ++b) f += part_host[(size_t)b];
+            cost[g] = f;
+        }
+    }
+    void gradient(const std::vector<char>& m, double* gnorm) {
+        set_mask(m);
+        hipLaunchKernelGGL(score::k_gb_gather_g, dim3(n_ublocks), dim3(kThreads), 0, stream(), dev(), (const int32_t*)gc_ptr.d,
+                           (const int32_t*)gc_slot.d, (const double*)gblk.d, rhs.d, gmax_part.d, (const int32_t*)mask.d);
+        HIP_CHECK(hipGetLastError());
+        part_host.resize((size_t)n_ublocks);
+        HIP_CHECK(hipMemcpyAsync(part_host.data(), gmax_part.d, (size_t)n_ublocks * sizeof(double), hipMemcpyDeviceToHost, stream()));
+        HIP_CHECK(sync_stream(stream()));
+        for (int g = 0; g < U.count; ++g) {
+            if (!m[(size_t)g]) continue;
+            double mx = 0.0;
+            for (int b = U.members[(size_t)g].ublk0; b < U.members[(size_t)g].ublk1; ++b) mx = std::max(mx, part_host[(size_t)b]);
+            gnorm[g] = mx;
+        }
+    }
+    void trial(const std::vector<char>& m) {
+        set_mask(m);
+        if (U.dim == 2)
+            hipLaunchKernelGGL(score::k_gb_trial<2>, dim3(n_sblocks), dim3(kThreads), 0, stream(), dev(), (const double*)X.d, (const double*)x.d,
+                               Xt.d, (const int32_t*)mask.d);
+        else
+            hipLaunchKernelGGL(score::k_gb_trial<3>, dim3(n_sblocks), dim3(kThreads), 0, stream(), dev(), (const double*)X.d, (const double*)x.d,
+                               Xt.d, (const int32_t*)mask.d);
+    }
+    void accept(const std::vector<char>& m) {  // the trial point of the masked members becomes their current one
+        set_mask(m);
+        if (U.dim == 2)
+            hipLaunchKernelGGL(score::k_gb_trial<2>, dim3(n_sblocks), dim3(kThreads), 0, stream(), dev(), (const double*)Xt.d,
+                               (const double*)nullptr, X.d, (const int32_t*)mask.d);
+        else
+            hipLaunchKernelGGL(score::k_gb_trial<3>, dim3(n_sblocks), dim3(kThreads), 0, stream(), dev(), (const double*)Xt.d,
+                               (const double*)nullptr, X.d, (const int32_t*)mask.d);
+    }
+    // (J'J + lambda_g I) step = -g on the masked members, the steps left in x; ok / used per masked member
+    void solve(const std::vector<char>& m, const double* lam, double rel_tol, char* ok, int32_t* used) {
+        const int G = U.count;
+        HipBackend& b = be();
+        hipStream_t st = stream();
+        HIP_CHECK(hipMemcpyAsync(lambda.d, lam, (size_t)G * sizeof(double), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(score::k_gb_gather_h, dim3(n_hblocks), dim3(kThreads), 0, st, (const int32_t*)hc_ptr.d, (const int32_t*)hc_slot.d,
+                           (const double*)hblk.d, (const int32_t*)diag_member.d, (const double*)lambda.d, b.K0d.d, nnz);
+        b.derive_rho_data(false);  // K = K0, its chain factors and Jacobi inverses, for the whole group
+        word_host.assign((size_t)(2 * G + 1), 0);
+        for (int g = 0; g < G; ++g) word_host[(size_t)g] = m[(size_t)g] ? 0 : 1;
+        HIP_CHECK(hipMemcpyAsync(flags.d, word_host.data(), word_host.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIP_CHECK(sync_stream(st));
+        score::GbPcg a{};
+        a.d = dev();
+        a.ptr = b.Kset.mat.ptr.d; a.col = b.Kset.mat.col.d; a.val = b.Kset.mat.val.d;
+        a.tiles = tiles.d; a.done = flags.d; a.iters = flags.d + G;
+        a.x = x.d; a.r = r.d; a.z = z.d; a.p = p.d; a.w = w.d; a.rhs = rhs.d; a.pw_part = pw_part.d;
+        a.tol2 = rel_tol * rel_tol; a.ref = ref.d;
+        const dim3 gu((unsigned)n_ublocks), gt((unsigned)n_tiles), bt(kThreads);
+        auto precondition = [&]() {  // z = M^-1 r over the whole group (score_marginals.hpp's use of the chain kernel, one vector)
+            PrecArgs pa = b.prec_args(b.Kset);
+            pa.done = flags.d + 2 * G;
+            b.prec_vectors(pa, r.d, r.d, z.d, scratch.d, w.d, scratch.d, scratch.d, nullptr);
+            pa.rz_in = nullptr; pa.rz_out = rz_prec.d;
+            b.launch_prec<PREC_INIT>(b.Kset, pa, -1, HipBackend::PrecDepth::join);
+        };
+        double* rz_cur = rz0.d; double* rz_nxt = rz1.d;
+        hipLaunchKernelGGL(score::k_gb_pcg_begin, gu, bt, 0, st, a);
+        precondition();
+        a.rz_part = rz_cur;
+        hipLaunchKernelGGL(score::k_gb_rz, gu, bt, 0, st, a);
+        a.first = 1; a.rz_new = rz_cur; a.rz_old = nullptr;
+        hipLaunchKernelGGL(score::k_gb_direction, gu, bt, 0, st, a);
+        a.first = 0;
+        const int max_iters = 4000;
+        int queued = 0;
+        bool all_done = false;
+        while (!all_done && queued < max_iters) {
+            const int chunk = std::min(max_iters - queued, queued == 0 ? 16 : 32);
+            for (int j = 0; j < chunk; ++j) {
+                hipLaunchKernelGGL(score::k_gb_product, gt, bt, 0, st, a);
+                a.rz_new = rz_cur;
+                hipLaunchKernelGGL(score::k_gb_step, gu, bt, 0, st, a);
+                precondition();
+                a.rz_part = rz_nxt;
+                hipLaunchKernelGGL(score::k_gb_rz, gu, bt, 0, st, a);
+                a.rz_new = rz_nxt; a.rz_old = rz_cur;
+                hipLaunchKernelGGL(score::k_gb_direction, gu, bt, 0, st, a);
+                std::swap(rz_cur, rz_nxt);
+            }
+            queued += chunk;
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipMemcpyAsync(word_host.data(), flags.d, (size_t)(2 * G) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(sync_stream(st));
+            all_done = true;
+            for (int g = 0; g < G; ++g) all_done = all_done && word_host[(size_t)g] != 0;
+        }
+        for (int g = 0; g < G; ++g) {
+            if (!m[(size_t)g]) continue;
+            ok[g] = word_host[(size_t)g] == 1 ? 1 : 0;
+            used[g] = word_host[(size_t)(G + g)];
+        }
+    }
+    void run(const double* poses_in, const double* lms_in, int max_iters, double tol, double* poses_out, double* lms_out,
+             std::vector<score::GbState>& S) {
+        const int ps = U.pose_scalars(), d = U.dim;
+        std::vector<double> h((size_t)U.state_size);
+        for (const score::GbMember& M : U.members) {
+            std::copy(poses_in + M.pose0, poses_in + M.pose0 + ps * M.Np, h.begin() + (std::ptrdiff_t)M.state0);
+            if (M.Nl) std::copy(lms_in + M.lm0, lms_in + M.lm0 + d * M.Nl, h.begin() + (std::ptrdiff_t)(M.state0 + ps * M.Np));
+        }
+        staged_h2d(X.d, h.data(), h.size() * sizeof(double), stream());
+        HIP_CHECK(sync_stream(stream()));
+        rounds = score::gb_lock_step(*this, U.count, max_iters, tol, 1e-9, S);
+        staged_d2h(h.data(), X.d, h.size() * sizeof(double), stream());
+        HIP_CHECK(sync_stream(stream()));
+        for (const score::GbMember& M : U.members) {
+            std::copy(h.begin() + (std::ptrdiff_t)M.state0, h.begin() + (std::ptrdiff_t)(M.state0 + ps * M.Np), poses_out + M.pose0);
+            if (M.Nl) std::copy(h.begin() + (std::ptrdiff_t)(M.state0 + ps * M.Np), h.begin() + (std::ptrdiff_t)(M.state0 + ps * M.Np + d * M.Nl), lms_out + M.lm0);
+        }
+    }
+};
+
 extern "C" {
 
 static int score_create_from_graphs_impl(const score_graph* graphs, int32_t count, const score_settings* s, score_handle** out, const HipBackend::GenSource* gen_src) {
@@ -4474,6 +4710,46 @@ void score_refine_destroy(score_refine* r) {
     (void)hipGetDevice(&prev);
     (void)hipSetDevice(r->device);
     delete r;
+    if (prev >= 0) (void)hipSetDevice(prev);
+}
+int score_refine_batch_create(const score_graph* graphs, int32_t count, const score_settings* s, score_refine_batch** out) {
+    return abi_call([&] {
+        require(graphs && out);
+        require(count > 0, "score_refine_batch_create: count must be positive");
+        for (int32_t i = 1; i < count; ++i)
+            require(graphs[i].dim == graphs[0].dim, "score_refine_batch_create: the graphs of a group must share dim");
+        const score_settings st = resolve_settings(s);
+        AbiEnv::require_device(st.device);
+        AbiEnv::Scope scope(st.device, false);
+        publish_new(out, [&](score_refine_batch& b) { b.create(graphs, count, s); });
+        return 0;
+    });
+}
+int score_refine_batch_run(score_refine_batch* b, const double* poses_in, const double* landmarks_in, int32_t max_iters, double tol,
+                           double* poses_out, double* landmarks_out, score_refine_info* infos) {
+    return abi_call([&] {
+        require(b && poses_in && poses_out && (b->U.lms_size == 0 || (landmarks_in && landmarks_out)));
+        AbiEnv::Scope scope(b->device, false);
+        const double t0 = score::now_ms();
+        std::vector<score::GbState> S;
+        b->run(poses_in, landmarks_in, max_iters, tol, poses_out, landmarks_out, S);
+        const double ms = score::now_ms() - t0;
+        for (int g = 0; infos && g < b->U.count; ++g) {
+            const score::GbState& m = S[(size_t)g];
+            score_refine_info& info = infos[g];
+            info.cost_initial = m.cost_initial; info.cost_final = m.f; info.grad_inf = m.gnorm;
+            info.iterations = m.iterations; info.linear_solves = m.linear_solves; info.pcg_iters = m.pcg_iters;
+            info.setup_ms = b->setup_ms; info.solve_ms = ms;
+        }
+        return 0;
+    });
+}
+void score_refine_batch_destroy(score_refine_batch* b) {
+    if (!b) return;
+    int prev = -1;
+    (void)hipGetDevice(&prev);
+    (void)hipSetDevice(b->device);
+    delete b;
     if (prev >= 0) (void)hipSetDevice(prev);
 }
 }  // extern "C"

@@ -88,7 +88,9 @@ def graph_arrays(data) -> Dict[str, np.ndarray]:
     """FactorGraphData -> the flat arrays of ``score_graph`` (the only per-measurement Python work
     left on the path: attribute reads -- one pass over every measurement list with ``_objread.gather``, or one
     ``numpy.fromiter`` pass per attribute without it).  Raises the reference's errors for duplicate / unknown
-    variable names (gurobi_utils.py:62-80, :103-109)."""
+    variable names (gurobi_utils.py:62-80, :103-109).  An ``ArrayGraph`` already is its arrays."""
+    if isinstance(data, ArrayGraph):
+        return data.arrays
     d = data.dimension
     check_dimension(d)
     chain_len = [len(c) for c in data.pose_variables]

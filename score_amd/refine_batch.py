@@ -1,0 +1,261 @@
+"""Local refinement of many graphs in lock-step (include/score_refine_batch.h, csrc/score_gn_batch.hpp).
+
+``refine_estimate`` takes one graph, builds one handle and meets the device four or five times per Levenberg-Marquardt
+iteration.  A Monte-Carlo study refines dozens of small worlds; ``refine_estimate_batch`` hands them to the device as groups:
+one union problem per group (block-diagonal J'J on one linear-mode pattern), one gather / factorisation / conjugate-gradient
+solve / trial / cost per ROUND for every member that needs one, and a controller that keeps one state per member.  Members
+never influence one another: every member takes exactly the decisions ``refine._lm_loop`` takes on it alone.
+
+``engine="python"`` is the same lock-step controller in Python around ``refine._Problem`` / ``_Problem3D`` with SciPy's sparse
+LU -- the readable statement of the state machine (``_Member``: the library's is ``GbState`` with ``gb_begin`` /
+``gb_after_gradient`` / ``gb_after_solve``), and the twin the tests compare with: it only reorders independent work, so its
+results equal ``refine_estimate(engine="python", linear_solver="scipy")`` member by member, bit for bit.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import List, Optional, Sequence
+
+import numpy as np
+import scipy.sparse as sp
+import scipy.sparse.linalg as spla
+
+from .refine import _as_results, _initial_point, _Problem, _Problem3D, refine_estimate
+from .refine_robust import _point_arrays, _point_from
+
+REFINE_BATCH_SYMBOLS = ["score_refine_batch_create", "score_refine_batch_run", "score_refine_batch_destroy"]
+
+GRADIENT, SOLVE, STOPPED = "gradient", "solve", "stopped"
+
+
+class _Member:
+    """The controller's state of one member, and its transitions (pure: they read and write this record only)."""
+
+    def __init__(self, f: float, max_iters: int):
+        self.f = self.cost_initial = float(f)
+        self.lam, self.gnorm = 1e-6, float("inf")
+        self.it, self.attempts, self.iterations, self.linear_solves, self.pcg_iters = 1, 0, 0, 0, 0
+        self.phase = GRADIENT
+        if self.it > max_iters:
+            self._stop(max_iters)
+
+    def _stop(self, max_iters: int) -> None:
+        self.phase = STOPPED
+        self.iterations = min(self.it, max_iters)
+
+    def after_gradient(self, gnorm: float, tol: float, max_iters: int) -> None:
+        """Top of iteration ``it``: the gradient of the current point is known."""
+        self.gnorm = float(gnorm)
+        if gnorm <= tol * max(1.0, self.f):
+            self._stop(max_iters)
+            return
+        self.attempts = 0
+        self.phase = SOLVE
+
+    def after_solve(self, ok: bool, used: int, fn: float, max_iters: int) -> bool:
+        """One attempt: the solve and, where it succeeded, the cost at the trial point.  True: the step is accepted."""
+        self.linear_solves += 1
+        self.pcg_iters += int(used)
+        if ok and fn < self.f:
+            dec = self.f - fn
+            self.f = float(fn)
+            self.lam = max(self.lam * 0.1, 1e-12)
+            if dec <= 1e-14 * max(1.0, self.f):
+                self._stop(max_iters)
+                return True
+            self.it += 1
+            if self.it > max_iters:
+                self._stop(max_iters)
+            else:
+                self.phase = GRADIENT
+            return True
+        self.lam *= 10.0
+        self.attempts += 1
+        if self.attempts >= 12:
+            self._stop(max_iters)
+        return False
+
+
+def _weights_of(weights, count: int, what: str) -> list:
+    if weights is None:
+        return [None] * count
+    weights = list(weights)
+    if len(weights) != count:
+        raise ValueError(f"{what}: one entry per graph expected ({count}), got {len(weights)}")
+    return weights
+
+
+def _problem_of(data, results, rw, lw):
+    if data.dimension == 3:
+        prob = _Problem3D(data, rw, lw)
+        return prob, prob.initial_state(results)
+    prob = _Problem(data, rw, lw)
+    return prob, _initial_point(prob, results)
+
+
+def _python_lock_step(probs, points, max_iters: int, tol: float):
+    """The lock-step controller over ``probs`` from ``points``: returns (points, members).  Per round every member in phase
+    SOLVE gets one damped solve, one trial point and one cost; then each decides for itself."""
+    G = len(probs)
+    u = list(points)
+    lin = [prob.residuals(x, jac=True) for prob, x in zip(probs, u)]  # (res, J) of the current points
+    S = [_Member(float(res @ res), max_iters) for res, _ in lin]
+    grad: List[Optional[np.ndarray]] = [None] * G
+    H: List[Optional[sp.spmatrix]] = [None] * G
+
+    def gradient(g: int) -> None:
+        res, J = lin[g]
+        grad[g] = J.T @ res
+        S[g].after_gradient(float(np.abs(grad[g]).max()) if grad[g].size else 0.0, tol, max_iters)
+        H[g] = (J.T @ J).tocsc() if S[g].phase == SOLVE else None
+
+    for g in range(G):
+        if S[g].phase == GRADIENT:
+            gradient(g)
+    rounds = 0
+    while any(s.phase == SOLVE for s in S):
+        rounds += 1
+        for g in range(G):
+            if S[g].phase != SOLVE:
+                continue
+            prob = probs[g]
+            ok, un, fn = True, None, float("nan")
+            try:
+                step = spla.splu((H[g] + S[g].lam * sp.identity(prob.n, format="csc")).tocsc()).solve(-grad[g])
+            except RuntimeError:
+                ok = False
+            if ok:
+                un = prob.retract(u[g], step)
+                fn = prob.cost(un)
+            if S[g].after_solve(ok, 0, fn, max_iters):
+                u[g] = un
+                if S[g].phase == GRADIENT:
+                    lin[g] = prob.residuals(un, jac=True)
+                    gradient(g)
+    return u, S, rounds
+
+
+def _bind(lib):
+    from .native import ScoreGraph
+    from .solver import ScoreRefineInfo, ScoreSettings, _f64p
+
+    if getattr(lib, "_score_refine_batch_bound", False):
+        return lib
+    lib.score_refine_batch_create.argtypes = [C.POINTER(ScoreGraph), C.c_int32, C.POINTER(ScoreSettings), C.POINTER(C.c_void_p)]
+    lib.score_refine_batch_run.argtypes = [C.c_void_p, _f64p, _f64p, C.c_int32, C.c_double, _f64p, _f64p, C.POINTER(ScoreRefineInfo)]
+    lib.score_refine_batch_destroy.argtypes = [C.c_void_p]
+    lib.score_refine_batch_destroy.restype = None
+    lib._score_refine_batch_bound = True
+    return lib
+
+
+class RefineBatchHandle:
+    """A group handle (``score_refine_batch_create``) over ``probs`` (all of one dimension, every one with unknowns); ``run``
+    takes and returns points in the problems' own form (``_Problem``: packed unknowns; ``_Problem3D``: (R, t, lm))."""
+
+    def __init__(self, probs: Sequence, lib_path: Optional[str] = None, solver_settings: Optional[dict] = None):
+        from .native import ScoreGraph, score_graph_struct
+        from .solver import ScoreSettings, load_library
+
+        self.probs = list(probs)
+        self.lib = _bind(load_library(lib_path))
+        st = ScoreSettings()
+        self.lib.score_default_settings(C.byref(st))
+        for k, v in (solver_settings or {}).items():
+            if not hasattr(st, k):
+                raise ValueError(f"unknown solver setting {k}")
+            setattr(st, k, v)
+        graphs = (ScoreGraph * len(self.probs))(*[score_graph_struct(p.a) for p in self.probs])
+        self.h = C.c_void_p()
+        if self.lib.score_refine_batch_create(graphs, len(self.probs), C.byref(st), C.byref(self.h)) != 0:
+            raise RuntimeError(f"score_refine_batch_create failed: {self.lib.score_last_error().decode()}")
+
+    def run(self, points, max_iters: int = 50, tol: float = 1e-10):
+        """``score_refine_batch_run``: (points, info dicts), member by member."""
+        from .solver import ScoreRefineInfo, _f64p
+
+        if len(points) != len(self.probs):
+            raise ValueError("one point per member expected")
+        arrays = [_point_arrays(prob, x) for prob, x in zip(self.probs, points)]
+        width = arrays[0][1].shape[1]
+        poses_in = np.ascontiguousarray(np.concatenate([a[0].ravel() for a in arrays]))
+        lms_in = np.ascontiguousarray(np.concatenate([a[1].ravel() for a in arrays]))
+        poses_out, lms_out = np.empty_like(poses_in), np.empty(max(1, lms_in.size))
+        infos = (ScoreRefineInfo * len(self.probs))()
+        p = lambda x: x.ctypes.data_as(_f64p)  # noqa: E731
+        rc = self.lib.score_refine_batch_run(self.h, p(poses_in), p(lms_in) if lms_in.size else None, int(max_iters), float(tol),
+                                             p(poses_out), p(lms_out), infos)
+        if rc != 0:
+            raise RuntimeError(f"score_refine_batch_run failed: {self.lib.score_last_error().decode()}")
+        out, p0, l0 = [], 0, 0
+        for prob, (pa, la) in zip(self.probs, arrays):
+            po = poses_out[p0 : p0 + pa.size].reshape(pa.shape)
+            lo = lms_out[l0 : l0 + la.size].reshape(-1, width)
+            out.append(_point_from(prob, po, lo))
+            p0 += pa.size
+            l0 += la.size
+        return out, [infos[i].as_dict() for i in range(len(self.probs))]
+
+    def close(self) -> None:
+        if self.h:
+            self.lib.score_refine_batch_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-10, range_weights=None, loop_closure_weights=None,
+                          engine: str = "native", lib_path: Optional[str] = None, solver_settings: Optional[dict] = None,
+                          max_group: int = 64):
+    """``refine_estimate`` for many graphs at once: ``datas`` and ``results`` member by member, ``range_weights`` /
+    ``loop_closure_weights`` lists with one entry (an array as ``refine_estimate`` takes it, or None) per member -- they only
+    scale precisions.  The members are grouped by dimension, in chunks of at most ``max_group``, each group one device handle
+    (``engine="native"``) or one lock-step loop in Python with SciPy's sparse LU (``engine="python"``).  Members without
+    unknowns are answered on the host.  Returns a list of ``(refined SolverResults, info)`` in input order; ``info`` as
+    ``refine_estimate`` reports it, plus ``group`` (the group's number) and ``rounds`` (lock-step rounds of the group)."""
+    if engine not in ("native", "python"):
+        raise ValueError("engine must be 'native' or 'python'")
+    datas, results = list(datas), list(results)
+    if len(datas) != len(results):
+        raise ValueError(f"one estimate per graph expected: {len(datas)} graphs, {len(results)} estimates")
+    if int(max_group) < 1:
+        raise ValueError("max_group must be at least 1")
+    rws = _weights_of(range_weights, len(datas), "range_weights")
+    lws = _weights_of(loop_closure_weights, len(datas), "loop_closure_weights")
+    out: list = [None] * len(datas)
+    groups: dict = {}
+    for i, (data, res) in enumerate(zip(datas, results)):
+        if data.dimension not in (2, 3):
+            raise ValueError(f"graph {i}: dimension must be 2 or 3")
+        prob, point = _problem_of(data, res, rws[i], lws[i])
+        if prob.n == 0:  # nothing to refine: the host's answer, as refine_estimate gives it
+            out[i] = refine_estimate(data, res, max_iters=max_iters, tol=tol, linear_solver="scipy", engine="python",
+                                     range_weights=rws[i], loop_closure_weights=lws[i])
+            continue
+        groups.setdefault(data.dimension, []).append((i, prob, point))
+    number = 0
+    for dim in sorted(groups):
+        members = groups[dim]
+        for c0 in range(0, len(members), int(max_group)):
+            chunk = members[c0 : c0 + int(max_group)]
+            probs, points = [m[1] for m in chunk], [m[2] for m in chunk]
+            if engine == "python":
+                pts, S, rounds = _python_lock_step(probs, points, max_iters, tol)
+                infos = [{"cost_initial": s.cost_initial, "cost_final": s.f, "iterations": s.iterations, "grad_inf": s.gnorm,
+                          "linear_solver": "scipy", "engine": "python", "pcg_iters": 0, "linear_solves": s.linear_solves} for s in S]
+            else:
+                with RefineBatchHandle(probs, lib_path, solver_settings) as h:
+                    pts, raw = h.run(points, max_iters, tol)
+                rounds = max(r["linear_solves"] for r in raw)
+                infos = [{"cost_initial": r["cost_initial"], "cost_final": r["cost_final"], "iterations": r["iterations"],
+                          "grad_inf": r["grad_inf"], "linear_solver": "device", "engine": "native", "pcg_iters": r["pcg_iters"],
+                          "linear_solves": r["linear_solves"], "setup_ms": r["setup_ms"], "solve_ms": r["solve_ms"]} for r in raw]
+            for (i, prob, _), pt, info in zip(chunk, pts, infos):
+                info["group"], info["rounds"] = number, rounds
+                out[i] = (_as_results(prob, pt, results[i], info["cost_final"]), info)
+            number += 1
+    return out
