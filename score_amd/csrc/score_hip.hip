@@ -4329,6 +4329,7 @@ struct score_refine {
 };
 
 #include "score_gn_batch.hpp"
+#include "score_marginals_batch.hpp"
 
 // Local refinement of a group of graphs in lock-step (score_gn_batch.hpp): the union state, blocks and gathers here, the
 // chain factorisation and M^-1 through the linear-mode handle `lin` on the union pattern, the per-member conjugate-gradient
@@ -4350,6 +4351,7 @@ struct score_refine_batch {
     long long nnz = 0;
     std::vector<double> part_host;
     std::vector<int32_t> word_host;
+    score::GbmWork mvb;  // marginal covariances of the members (score_marginals_batch.hpp)
 
     HipBackend& be() { return lin->solver.be; }
     hipStream_t stream() { return lin->solver.be.stream; }
@@ -4480,14 +4482,20 @@ struct score_refine_batch {
             hipLaunchKernelGGL(score::k_gb_trial<3>, dim3(n_sblocks), dim3(kThreads), 0, stream(), dev(), (const double*)Xt.d,
                                (const double*)nullptr, X.d, (const int32_t*)mask.d);
     }
+    // J'J + lambda_g I of every member from the blocks of the last evaluation, into the handle's K0 (lam: one per member; read
+    // by the time the stream is next waited for)
+    void gather_h(const double* lam) {
+        hipStream_t st = stream();
+        HIP_CHECK(hipMemcpyAsync(lambda.d, lam, (size_t)U.count * sizeof(double), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(score::k_gb_gather_h, dim3(n_hblocks), dim3(kThreads), 0, st, (const int32_t*)hc_ptr.d, (const int32_t*)hc_slot.d,
+                           (const double*)hblk.d, (const int32_t*)diag_member.d, (const double*)lambda.d, be().K0d.d, nnz);
+    }
     // (J'J + lambda_g I) step = -g on the masked members, the steps left in x; ok / used per masked member
     void solve(const std::vector<char>& m, const double* lam, double rel_tol, char* ok, int32_t* used) {
         const int G = U.count;
         HipBackend& b = be();
         hipStream_t st = stream();
-        HIP_CHECK(hipMemcpyAsync(lambda.d, lam, (size_t)G * sizeof(double), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(score::k_gb_gather_h, dim3(n_hblocks), dim3(kThreads), 0, st, (const int32_t*)hc_ptr.d, (const int32_t*)hc_slot.d,
-                           (const double*)hblk.d, (const int32_t*)diag_member.d, (const double*)lambda.d, b.K0d.d, nnz);
+        gather_h(lam);
         b.derive_rho_data(false);  // K = K0, its chain factors and Jacobi inverses, for the whole group
         word_host.assign((size_t)(2 * G + 1), 0);
         for (int g = 0; g < G; ++g) word_host[(size_t)g] = m[(size_t)g] ? 0 : 1;
@@ -4544,8 +4552,8 @@ struct score_refine_batch {
             used[g] = word_host[(size_t)(G + g)];
         }
     }
-    void run(const double* poses_in, const double* lms_in, int max_iters, double tol, double* poses_out, double* lms_out,
-             std::vector<score::GbState>& S) {
+    // the caller's points become the members' current ones (X); returns the state as uploaded
+    std::vector<double> set_point(const double* poses_in, const double* lms_in) {
         const int ps = U.pose_scalars(), d = U.dim;
         std::vector<double> h((size_t)U.state_size);
         for (const score::GbMember& M : U.members) {
@@ -4554,6 +4562,12 @@ struct score_refine_batch {
         }
         staged_h2d(X.d, h.data(), h.size() * sizeof(double), stream());
         HIP_CHECK(sync_stream(stream()));
+        return h;
+    }
+    void run(const double* poses_in, const double* lms_in, int max_iters, double tol, double* poses_out, double* lms_out,
+             std::vector<score::GbState>& S) {
+        const int ps = U.pose_scalars(), d = U.dim;
+        std::vector<double> h = set_point(poses_in, lms_in);
         rounds = score::gb_lock_step(*this, U.count, max_iters, tol, 1e-9, S);
         staged_d2h(h.data(), X.d, h.size() * sizeof(double), stream());
         HIP_CHECK(sync_stream(stream()));
@@ -4742,6 +4756,17 @@ int score_refine_batch_run(score_refine_batch* b, const double* poses_in, const 
             info.setup_ms = b->setup_ms; info.solve_ms = ms;
         }
         return 0;
+    });
+}
+int score_refine_batch_marginals(score_refine_batch* b, const double* poses, const double* landmarks, const int32_t* var_ptr,
+                                 const int32_t* vars, double rel_tol, int32_t max_iters, int32_t block_width, double* joint,
+                                 double* residuals, int32_t* iters, score_marginals_batch_info* info) {
+    return abi_call([&] {
+        require(b != nullptr, "score_refine_batch_marginals: null handle");
+        require(var_ptr != nullptr, "score_refine_batch_marginals: var_ptr is null");
+        require(poses && (b->U.lms_size == 0 || landmarks), "score_refine_batch_marginals: the points are missing");
+        AbiEnv::Scope scope(b->device, false);
+        return score::gbm_solve(*b, poses, landmarks, var_ptr, vars, rel_tol, max_iters, block_width, joint, residuals, iters, info);
     });
 }
 void score_refine_batch_destroy(score_refine_batch* b) {

@@ -68,30 +68,28 @@ struct MvArgs {
 
 __device__ __forceinline__ bool mv_finite(double v) { return fabs(v) <= 1.79769313486231570e308; }
 
-// w_c = H p_in_c over the live columns, partials of p_in_c'w_c.  NV: columns of the block (compile time: the sums live in registers).
+// The product of one tile: w_c = H p_in_c for the columns of `live`, the tile's partial of p_in_c'w_c into
+// pw_part[c * part_stride + part_slot].  Stated once: k_mv_product (the columns of one graph) and k_gbm_product
+// (score_marginals_batch.hpp: the slots of the tile's member inside a union) call it with their live mask and partial slot.
+// NV: vectors of the block (compile time: the sums live in registers).  red: (kMvThreads / 64) * NV doubles of LDS.  Every
+// lane of the workgroup enters with the same tile and the same (non-empty) mask.
 template <int NV>
-__global__ __launch_bounds__(kMvThreads) void k_mv_product(MvArgs a) {
-    __shared__ double red[(kMvThreads / 64) * NV];
+__device__ __forceinline__ void mv_product_tile(const int32_t* ptr, const int32_t* col, const double* val, const int4 tile, const long long n,
+                                                const double* p_in, double* w, double* pw_part, const size_t part_stride,
+                                                const size_t part_slot, const unsigned live, double* red) {
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    unsigned live = 0;
-#pragma unroll
-    for (int c = 0; c < NV; ++c)
-        if (a.all_columns || a.flags[kMvDone + c] == 0) live |= 1u << c;
-    if (!live) return;
-    const int4 tile = a.tiles[blockIdx.x];
-    const long long n = a.n;
     double acc[NV];
 #pragma unroll
     for (int c = 0; c < NV; ++c) acc[c] = 0.0;
     if (tile.z) {  // one long row over the workgroup
         const int row = tile.x;
-        const int k1 = a.ptr[row + 1];
-        for (int k = a.ptr[row] + t; k < k1; k += kMvThreads) {
-            const double v = a.val[k];
-            const long long j = a.col[k];
+        const int k1 = ptr[row + 1];
+        for (int k = ptr[row] + t; k < k1; k += kMvThreads) {
+            const double v = val[k];
+            const long long j = col[k];
 #pragma unroll
             for (int c = 0; c < NV; ++c)
-                if (live >> c & 1) acc[c] += v * a.p_in[c * n + j];
+                if (live >> c & 1) acc[c] += v * p_in[c * n + j];
         }
 #pragma unroll
         for (int c = 0; c < NV; ++c)
@@ -102,8 +100,8 @@ __global__ __launch_bounds__(kMvThreads) void k_mv_product(MvArgs a) {
         __syncthreads();
         if (t < NV && (live >> t & 1)) {
             const double wv = (red[t] + red[NV + t]) + (red[2 * NV + t] + red[3 * NV + t]);
-            a.w[t * n + row] = wv;
-            a.pw_part[(size_t)t * a.n_tiles + blockIdx.x] = a.p_in[t * n + row] * wv;
+            w[t * n + row] = wv;
+            pw_part[(size_t)t * part_stride + part_slot] = p_in[t * n + row] * wv;
         }
         return;
     }
@@ -111,13 +109,13 @@ __global__ __launch_bounds__(kMvThreads) void k_mv_product(MvArgs a) {
     const int row = tile.x + t / kMvLanes, sub = t % kMvLanes;
     const bool mine = row < tile.y;
     if (mine) {
-        const int k1 = a.ptr[row + 1];
-        for (int k = a.ptr[row] + sub; k < k1; k += kMvLanes) {
-            const double v = a.val[k];
-            const long long j = a.col[k];
+        const int k1 = ptr[row + 1];
+        for (int k = ptr[row] + sub; k < k1; k += kMvLanes) {
+            const double v = val[k];
+            const long long j = col[k];
 #pragma unroll
             for (int c = 0; c < NV; ++c)
-                if (live >> c & 1) acc[c] += v * a.p_in[c * n + j];
+                if (live >> c & 1) acc[c] += v * p_in[c * n + j];
         }
     }
 #pragma unroll
@@ -128,15 +126,27 @@ __global__ __launch_bounds__(kMvThreads) void k_mv_product(MvArgs a) {
             s += __shfl_xor(s, 2, 64);
             double pw = 0.0;
             if (mine && sub == 0) {
-                a.w[c * n + row] = s;
-                pw = a.p_in[c * n + row] * s;
+                w[c * n + row] = s;
+                pw = p_in[c * n + row] * s;
             }
             pw = wave_sum(pw);
             if (lane == 0) red[wave * NV + c] = pw;
         }
     __syncthreads();
     if (t < NV && (live >> t & 1))
-        a.pw_part[(size_t)t * a.n_tiles + blockIdx.x] = (red[t] + red[NV + t]) + (red[2 * NV + t] + red[3 * NV + t]);
+        pw_part[(size_t)t * part_stride + part_slot] = (red[t] + red[NV + t]) + (red[2 * NV + t] + red[3 * NV + t]);
+}
+
+// w_c = H p_in_c over the live columns, partials of p_in_c'w_c
+template <int NV>
+__global__ __launch_bounds__(kMvThreads) void k_mv_product(MvArgs a) {
+    __shared__ double red[(kMvThreads / 64) * NV];
+    unsigned live = 0;
+#pragma unroll
+    for (int c = 0; c < NV; ++c)
+        if (a.all_columns || a.flags[kMvDone + c] == 0) live |= 1u << c;
+    if (!live) return;
+    mv_product_tile<NV>(a.ptr, a.col, a.val, a.tiles[blockIdx.x], a.n, a.p_in, a.w, a.pw_part, (size_t)a.n_tiles, (size_t)blockIdx.x, live, red);
 }
 
 // grid (row blocks, columns): alpha = r'z / p'w ; x += alpha p ; r -= alpha w

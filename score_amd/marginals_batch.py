@@ -1,0 +1,198 @@
+"""Marginal covariances of many graphs at once (include/score_marginals_batch.h, csrc/score_marginals_batch.hpp).
+
+``marginal_covariances`` takes one graph, builds one refinement handle and runs a block PCG whose launches are latency-bound
+on a small world.  ``marginal_covariances_batch`` hands the graphs to the device as groups, as ``refine_estimate_batch``
+does: the group handle's union matrix H = J'J is block diagonal, so one union vector carries one unit column of every
+member, and a block of up to 16 union vectors advances 16 columns of all members per pass over the union matrix
+(``score_refine_batch_marginals``).  Every (member, column) pair has its own alpha, beta, stopping gate and verdict: a
+member's result is what ``marginal_covariances`` computes on it alone, up to the rounding of the two iterations.
+
+``RefineBatchHandle.marginals`` is the raw call on a kept group handle, so a study refines and takes covariances with one
+create; ``refine_estimate_batch(..., marginals=True)`` does exactly that.  ``engine="python"`` is the dense inverse of
+``marginals._python_columns`` member by member.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+
+from .marginals import MAX_BLOCK_WIDTH, _problem_and_point, _python_columns, _select
+from .refine import _Problem3D
+from .refine_robust import _point_arrays
+from .solver import _f64p, _i32p
+
+# the symbols include/score_marginals_batch.h declares
+MARGINALS_BATCH_SYMBOLS = ["score_refine_batch_marginals"]
+
+
+class ScoreMarginalsBatchInfo(C.Structure):
+    _fields_ = [
+        ("columns", C.c_int32), ("passes", C.c_int32), ("pcg_iters", C.c_int32), ("unconverged", C.c_int32),
+        ("max_residual", C.c_double), ("setup_ms", C.c_double), ("solve_ms", C.c_double),
+    ]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def _bind(lib: C.CDLL) -> C.CDLL:
+    if getattr(lib, "_score_marginals_batch_bound", False):
+        return lib
+    for sym in MARGINALS_BATCH_SYMBOLS:
+        if not hasattr(lib, sym):
+            raise RuntimeError(f"{sym} is missing from the library: rebuild it (the oracle's CPU twin has no marginals: "
+                               "engine='python' runs there)")
+    lib.score_refine_batch_marginals.argtypes = [C.c_void_p, _f64p, _f64p, _i32p, _i32p, C.c_double, C.c_int32, C.c_int32,
+                                                 _f64p, _f64p, _i32p, C.POINTER(ScoreMarginalsBatchInfo)]
+    lib.score_refine_batch_marginals.restype = C.c_int
+    lib._score_marginals_batch_bound = True
+    return lib
+
+
+def batch_columns(handle, points, ids_per_member, rel_tol=1e-10, max_iters=4000, block_width=MAX_BLOCK_WIDTH):
+    """``score_refine_batch_marginals`` as it is, on a ``RefineBatchHandle``: ``points`` in the problems' own form,
+    ``ids_per_member`` the member-local variable ids of every member (an empty list: none).  Returns (return code, per member
+    ``(A, residuals, steps, converged)`` -- A is C_g x C_g, column c is x_c on the selected rows, not symmetrised --, the
+    call's info record)."""
+    probs = handle.probs
+    if len(points) != len(probs) or len(ids_per_member) != len(probs):
+        raise ValueError("one point and one list of variables per member expected")
+    lib = _bind(handle.lib)
+    arrays = [_point_arrays(prob, x) for prob, x in zip(probs, points)]
+    poses = np.ascontiguousarray(np.concatenate([a[0].ravel() for a in arrays]))
+    lms = np.ascontiguousarray(np.concatenate([a[1].ravel() for a in arrays]))
+    ids = [np.asarray(v, dtype=np.int32).ravel() for v in ids_per_member]
+    var_ptr = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(v) for v in ids])]), dtype=np.int32)
+    flat = np.ascontiguousarray(np.concatenate(ids + [np.zeros(0, np.int32)]), dtype=np.int32)
+    dim = 3 if isinstance(probs[0], _Problem3D) else 2
+    ncol = [int(np.where(v < prob.Np, 3 * (dim - 1), dim).sum()) for prob, v in zip(probs, ids)]
+    joint = np.zeros(max(1, sum(c * c for c in ncol)))
+    res = np.zeros(max(1, sum(ncol)))
+    its = np.zeros(max(1, sum(ncol)), dtype=np.int32)
+    info = ScoreMarginalsBatchInfo()
+    rc = lib.score_refine_batch_marginals(handle.h, poses.ctypes.data_as(_f64p), lms.ctypes.data_as(_f64p) if lms.size else None,
+                                          var_ptr.ctypes.data_as(_i32p), flat.ctypes.data_as(_i32p) if flat.size else None,
+                                          float(rel_tol), int(max_iters), int(block_width), joint.ctypes.data_as(_f64p),
+                                          res.ctypes.data_as(_f64p), its.ctypes.data_as(_i32p), C.byref(info))
+    if rc < 0:
+        raise RuntimeError(f"score_refine_batch_marginals failed: {lib.score_last_error().decode()}")
+    out, j0, c0 = [], 0, 0
+    for c in ncol:
+        it = its[c0 : c0 + c]
+        converged = it >= 0  # (a column that did not converge reports -(steps + 1))
+        out.append((joint[j0 : j0 + c * c].reshape(c, c).copy(), res[c0 : c0 + c].copy(), np.where(converged, it, -it - 1), converged))
+        j0 += c * c
+        c0 += c
+    return rc, out, info.as_dict()
+
+
+def _member_result(where, names, size, A, res, steps, converged, rec, engine, joint, max_iters):
+    """What ``marginal_covariances`` returns for one graph, from its columns (the same operations in the same order)."""
+    off = np.concatenate([[0], np.cumsum(size)])
+    if not np.all(converged):
+        bad = [nm for k, nm in enumerate(names) if not np.all(converged[off[k]:off[k + 1]])]
+        raise RuntimeError(f"marginal_covariances_batch: {where}: the columns of {', '.join(bad)} did not converge in {max_iters} "
+                           "iterations (a variable the measurements do not determine?)")
+    S = 0.5 * (A + A.T)
+    out = {nm: S[off[k]:off[k + 1], off[k]:off[k + 1]].copy() for k, nm in enumerate(names)}
+    info = {"order": names, "residuals": res, "iterations": steps, "asymmetry": float(np.max(np.abs(A - A.T))),
+            "pcg_iters": int(rec["pcg_iters"]), "batches": int(rec["batches"]), "setup_ms": float(rec["setup_ms"]),
+            "solve_ms": float(rec["solve_ms"]), "engine": engine}
+    if joint:
+        info["joint"] = S
+        info["joint_raw"] = A
+    return out, info
+
+
+def group_marginals(handle, probs, points, selections, indices, number, rel_tol=1e-10, max_iters=4000,
+                    block_width=MAX_BLOCK_WIDTH, engine="device", joint=False):
+    """The covariances of one group: ``selections[k]`` is ``marginals._select`` of member k, ``indices[k]`` its graph's number
+    in the caller's list (for messages), ``handle`` the group's ``RefineBatchHandle`` (None with ``engine="python"``).
+    Returns ``(cov, info)`` per member."""
+    if engine == "python":
+        cols = []
+        for prob, point, (_, _, _, c) in zip(probs, points, selections):
+            A, res = _python_columns(prob, point, c)
+            cols.append((A, res, np.zeros(len(c), dtype=np.int64), np.isfinite(res)))
+        rec = {"pcg_iters": 0, "passes": 0, "setup_ms": 0.0, "solve_ms": 0.0}
+    else:
+        _, cols, rec = handle.marginals(points, [sel[1] for sel in selections], rel_tol, max_iters, block_width)
+    out = []
+    for (names, _, size, c), (A, res, steps, converged), i in zip(selections, cols, indices):
+        mine = dict(rec, batches=0 if engine == "python" else -(-len(c) // int(block_width)))
+        cov, info = _member_result(f"graph {i}", names, size, A, res, steps, converged, mine, engine, joint, max_iters)
+        info["group"], info["passes"] = number, int(rec["passes"])
+        out.append((cov, info))
+    return out
+
+
+def _variables_of(variables, count: int) -> list:
+    if variables is None:
+        return [None] * count
+    variables = list(variables)
+    if len(variables) != count:
+        raise ValueError(f"variables: one entry per graph expected ({count}), got {len(variables)}")
+    return variables
+
+
+def marginal_covariances_batch(datas, results, variables=None, joint: bool = False, range_weights=None, loop_closure_weights=None,
+                               rel_tol: float = 1e-10, max_iters: int = 4000, block_width: int = MAX_BLOCK_WIDTH,
+                               engine: str = "device", lib_path: Optional[str] = None, solver_settings: Optional[dict] = None,
+                               max_group: int = 64):
+    """``marginal_covariances`` for many graphs at once: ``datas`` and ``results`` graph by graph, ``variables`` None or a list
+    with one entry per graph (None: that graph's default, every landmark and the last pose of every chain; else a list of
+    names), ``range_weights`` / ``loop_closure_weights`` lists with one entry per graph.  The graphs are grouped by dimension,
+    in chunks of at most ``max_group``, as ``refine_estimate_batch`` groups them; each group is one device handle and one
+    ``score_refine_batch_marginals`` call (``engine="device"``) or the dense inverse graph by graph (``engine="python"``).
+    Returns a list of ``(dict name -> k x k ndarray, info)`` in input order: per graph what ``marginal_covariances`` returns,
+    plus ``group`` (the group's number) and ``passes`` (passes of the group's call; ``batches`` counts those in which the
+    graph itself had columns; ``pcg_iters``, ``setup_ms`` and ``solve_ms`` are the group's).
+    ``block_width``: 1..16 columns of every member advance together.  The single call's ValueErrors are raised with
+    ``graph i:`` in front; a column that does not converge raises RuntimeError naming the graph and the variable."""
+    from .refine_batch import RefineBatchHandle, _weights_of
+
+    if engine not in ("device", "python"):
+        raise ValueError("engine must be 'device' or 'python'")
+    if int(block_width) != block_width or not 1 <= int(block_width) <= MAX_BLOCK_WIDTH:
+        raise ValueError(f"block_width must be an integer in 1..{MAX_BLOCK_WIDTH}")
+    if not rel_tol > 0 or max_iters < 1:
+        raise ValueError("rel_tol must be positive and max_iters at least 1")
+    datas, results = list(datas), list(results)
+    if len(datas) != len(results):
+        raise ValueError(f"one estimate per graph expected: {len(datas)} graphs, {len(results)} estimates")
+    if int(max_group) < 1:
+        raise ValueError("max_group must be at least 1")
+    rws = _weights_of(range_weights, len(datas), "range_weights")
+    lws = _weights_of(loop_closure_weights, len(datas), "loop_closure_weights")
+    wanted = _variables_of(variables, len(datas))
+    groups: dict = {}
+    for i, (data, res) in enumerate(zip(datas, results)):
+        if data.dimension not in (2, 3):
+            raise ValueError(f"graph {i}: dimension must be 2 or 3")
+        try:
+            prob, point = _problem_and_point(data, res, rws[i], lws[i])
+            sel = _select(prob, wanted[i])
+        except ValueError as e:
+            raise ValueError(f"graph {i}: {e}") from None
+        groups.setdefault(data.dimension, []).append((i, prob, point, sel))
+    out: list = [None] * len(datas)
+    number = 0
+    for dim in sorted(groups):
+        members = groups[dim]
+        for c0 in range(0, len(members), int(max_group)):
+            chunk = members[c0 : c0 + int(max_group)]
+            idx, probs, points, sels = ([m[k] for m in chunk] for k in range(4))
+            if engine == "python":
+                got = group_marginals(None, probs, points, sels, idx, number, rel_tol, max_iters, int(block_width), engine, joint)
+            else:
+                with RefineBatchHandle(probs, lib_path, solver_settings) as h:
+                    got = group_marginals(h, probs, points, sels, idx, number, rel_tol, max_iters, int(block_width), engine, joint)
+            for i, g in zip(idx, got):
+                out[i] = g
+            number += 1
+    return out
+
+
+__all__ = ["marginal_covariances_batch", "batch_columns", "group_marginals", "MARGINALS_BATCH_SYMBOLS"]

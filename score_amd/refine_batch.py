@@ -196,6 +196,14 @@ class RefineBatchHandle:
             l0 += la.size
         return out, [infos[i].as_dict() for i in range(len(self.probs))]
 
+    def marginals(self, points, ids_per_member, rel_tol: float = 1e-10, max_iters: int = 4000, block_width: int = 16):
+        """``score_refine_batch_marginals`` at ``points`` (include/score_marginals_batch.h): ``ids_per_member`` lists the
+        member-local variable ids of every member (an empty list: none).  Returns (return code, per member
+        ``(A, residuals, steps, converged)``, the call's info record); the handle is left as it was found."""
+        from .marginals_batch import batch_columns
+
+        return batch_columns(self, points, ids_per_member, rel_tol, max_iters, block_width)
+
     def close(self) -> None:
         if self.h:
             self.lib.score_refine_batch_destroy(self.h)
@@ -210,13 +218,20 @@ class RefineBatchHandle:
 
 def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-10, range_weights=None, loop_closure_weights=None,
                           engine: str = "native", lib_path: Optional[str] = None, solver_settings: Optional[dict] = None,
-                          max_group: int = 64):
+                          max_group: int = 64, marginals=None):
     """``refine_estimate`` for many graphs at once: ``datas`` and ``results`` member by member, ``range_weights`` /
     ``loop_closure_weights`` lists with one entry (an array as ``refine_estimate`` takes it, or None) per member -- they only
     scale precisions.  The members are grouped by dimension, in chunks of at most ``max_group``, each group one device handle
     (``engine="native"``) or one lock-step loop in Python with SciPy's sparse LU (``engine="python"``).  Members without
     unknowns are answered on the host.  Returns a list of ``(refined SolverResults, info)`` in input order; ``info`` as
-    ``refine_estimate`` reports it, plus ``group`` (the group's number) and ``rounds`` (lock-step rounds of the group)."""
+    ``refine_estimate`` reports it, plus ``group`` (the group's number) and ``rounds`` (lock-step rounds of the group).
+    ``marginals``: True, or a list with one entry per graph as ``marginal_covariances_batch`` takes ``variables`` -- every
+    group's handle then also computes the marginal covariances at the refined points before it is closed (one create for
+    both), and ``info["marginals"]`` is the ``(cov, marginals_info)`` of ``marginal_covariances_batch`` for that graph (None
+    for a graph without unknowns)."""
+    from .marginals import _select
+    from .marginals_batch import _variables_of, group_marginals
+
     if engine not in ("native", "python"):
         raise ValueError("engine must be 'native' or 'python'")
     datas, results = list(datas), list(results)
@@ -226,8 +241,11 @@ def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-1
         raise ValueError("max_group must be at least 1")
     rws = _weights_of(range_weights, len(datas), "range_weights")
     lws = _weights_of(loop_closure_weights, len(datas), "loop_closure_weights")
+    with_marginals = marginals is not None and marginals is not False
+    wanted = _variables_of(None if marginals is True else marginals, len(datas)) if with_marginals else None
     out: list = [None] * len(datas)
     groups: dict = {}
+    sel_of: dict = {}
     for i, (data, res) in enumerate(zip(datas, results)):
         if data.dimension not in (2, 3):
             raise ValueError(f"graph {i}: dimension must be 2 or 3")
@@ -235,7 +253,14 @@ def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-1
         if prob.n == 0:  # nothing to refine: the host's answer, as refine_estimate gives it
             out[i] = refine_estimate(data, res, max_iters=max_iters, tol=tol, linear_solver="scipy", engine="python",
                                      range_weights=rws[i], loop_closure_weights=lws[i])
+            if with_marginals:
+                out[i][1]["marginals"] = None
             continue
+        if with_marginals:  # (the selection's errors before any work)
+            try:
+                sel_of[i] = _select(prob, wanted[i])
+            except ValueError as e:
+                raise ValueError(f"graph {i}: {e}") from None
         groups.setdefault(data.dimension, []).append((i, prob, point))
     number = 0
     for dim in sorted(groups):
@@ -243,19 +268,26 @@ def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-1
         for c0 in range(0, len(members), int(max_group)):
             chunk = members[c0 : c0 + int(max_group)]
             probs, points = [m[1] for m in chunk], [m[2] for m in chunk]
+            covs, sels = None, [sel_of.get(m[0]) for m in chunk]
             if engine == "python":
                 pts, S, rounds = _python_lock_step(probs, points, max_iters, tol)
+                if with_marginals:
+                    covs = group_marginals(None, probs, pts, sels, [m[0] for m in chunk], number, engine="python")
                 infos = [{"cost_initial": s.cost_initial, "cost_final": s.f, "iterations": s.iterations, "grad_inf": s.gnorm,
                           "linear_solver": "scipy", "engine": "python", "pcg_iters": 0, "linear_solves": s.linear_solves} for s in S]
             else:
                 with RefineBatchHandle(probs, lib_path, solver_settings) as h:
                     pts, raw = h.run(points, max_iters, tol)
+                    if with_marginals:
+                        covs = group_marginals(h, probs, pts, sels, [m[0] for m in chunk], number)
                 rounds = max(r["linear_solves"] for r in raw)
                 infos = [{"cost_initial": r["cost_initial"], "cost_final": r["cost_final"], "iterations": r["iterations"],
                           "grad_inf": r["grad_inf"], "linear_solver": "device", "engine": "native", "pcg_iters": r["pcg_iters"],
                           "linear_solves": r["linear_solves"], "setup_ms": r["setup_ms"], "solve_ms": r["solve_ms"]} for r in raw]
-            for (i, prob, _), pt, info in zip(chunk, pts, infos):
+            for k, ((i, prob, _), pt, info) in enumerate(zip(chunk, pts, infos)):
                 info["group"], info["rounds"] = number, rounds
+                if with_marginals:
+                    info["marginals"] = covs[k]
                 out[i] = (_as_results(prob, pt, results[i], info["cost_final"]), info)
             number += 1
     return out
