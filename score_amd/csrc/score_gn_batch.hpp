@@ -87,43 +87,66 @@ inline bool gb_after_solve(GbState& s, bool ok, int used, double fn, int max_ite
 //   gradient(mask, gnorm)                          g = J'r of the masked members from their blocks, |g|_inf
 //   solve(mask, lambda, rel_tol, ok, used)         (J'J + lambda_g I) step = -g for the masked members
 //   trial(mask)                                    trial = current + step;     accept(mask)  current = trial
+// what a round works with: one entry per member
+struct GbRoundWork {
+    std::vector<char> mask, tmask, acc, ok;
+    std::vector<double> val, lam;
+    std::vector<int32_t> used;
+    explicit GbRoundWork(size_t G) : mask(G, 1), tmask(G), acc(G), ok(G), val(G, 0.0), lam(G, 0.0), used(G, 0) {}
+    static bool any(const std::vector<char>& m) { return std::find(m.begin(), m.end(), (char)1) != m.end(); }
+};
+
+// One round: every member in phase kGbSolve gets one damped solve, one trial point and one cost, then decides for itself;
+// those that go on get the blocks and the gradient of their new point.  max_iters(g) / tol(g): the limits of member g's run.
+// false: no member is in phase kGbSolve (nothing was done).
+template <class Backend, class MaxIters, class Tol>
+inline bool gb_round(Backend& be, std::vector<GbState>& S, MaxIters max_iters, Tol tol, double pcg_rel_tol, GbRoundWork& W) {
+    const size_t G = S.size();
+    for (size_t g = 0; g < G; ++g) { W.mask[g] = S[g].phase == kGbSolve; W.lam[g] = S[g].lam; }
+    if (!W.any(W.mask)) return false;
+    be.solve(W.mask, W.lam.data(), pcg_rel_tol, W.ok.data(), W.used.data());
+    for (size_t g = 0; g < G; ++g) W.tmask[g] = W.mask[g] && W.ok[g];
+    if (W.any(W.tmask)) {
+        be.trial(W.tmask);
+        be.eval(W.tmask, true, false, W.val.data());
+    }
+    for (size_t g = 0; g < G; ++g)
+        W.acc[g] = W.mask[g] ? (gb_after_solve(S[g], W.ok[g] != 0, W.used[g], W.val[g], max_iters(g)) ? 1 : 0) : 0;
+    if (!W.any(W.acc)) return true;
+    be.accept(W.acc);
+    for (size_t g = 0; g < G; ++g) W.tmask[g] = W.acc[g] && S[g].phase == kGbGradient;
+    if (!W.any(W.tmask)) return true;
+    be.eval(W.tmask, false, true, nullptr);
+    be.gradient(W.tmask, W.val.data());
+    for (size_t g = 0; g < G; ++g)
+        if (W.tmask[g]) gb_after_gradient(S[g], W.val[g], tol(g), max_iters(g));
+    return true;
+}
+
+// The masked members enter a run at their current points: blocks and cost, gb_begin, then the gradient of those that iterate.
+template <class Backend, class MaxIters, class Tol>
+inline void gb_start(Backend& be, std::vector<GbState>& S, const std::vector<char>& members, MaxIters max_iters, Tol tol, GbRoundWork& W) {
+    const size_t G = S.size();
+    be.eval(members, false, true, W.val.data());
+    for (size_t g = 0; g < G; ++g)
+        if (members[g]) gb_begin(S[g], W.val[g], max_iters(g));
+    for (size_t g = 0; g < G; ++g) W.tmask[g] = members[g] && S[g].phase == kGbGradient;
+    if (!W.any(W.tmask)) return;
+    be.gradient(W.tmask, W.val.data());
+    for (size_t g = 0; g < G; ++g)
+        if (W.tmask[g]) gb_after_gradient(S[g], W.val[g], tol(g), max_iters(g));
+}
+
 template <class Backend>
 inline int gb_lock_step(Backend& be, int count, int max_iters, double tol, double pcg_rel_tol, std::vector<GbState>& S) {
     const size_t G = (size_t)count;
     S.assign(G, GbState{});
-    std::vector<char> mask(G, 1), tmask(G), acc(G), ok(G);
-    std::vector<double> val(G, 0.0), lam(G, 0.0);
-    std::vector<int32_t> used(G, 0);
-    auto any = [](const std::vector<char>& m) { return std::find(m.begin(), m.end(), (char)1) != m.end(); };
-    be.eval(mask, false, true, val.data());
-    for (size_t g = 0; g < G; ++g) gb_begin(S[g], val[g], max_iters);
-    for (size_t g = 0; g < G; ++g) mask[g] = S[g].phase == kGbGradient;
-    if (any(mask)) {
-        be.gradient(mask, val.data());
-        for (size_t g = 0; g < G; ++g)
-            if (mask[g]) gb_after_gradient(S[g], val[g], tol, max_iters);
-    }
+    GbRoundWork W(G);
+    auto iters_of = [max_iters](size_t) { return max_iters; };
+    auto tol_of = [tol](size_t) { return tol; };
+    gb_start(be, S, std::vector<char>(G, 1), iters_of, tol_of, W);
     int rounds = 0;
-    for (;;) {
-        for (size_t g = 0; g < G; ++g) { mask[g] = S[g].phase == kGbSolve; lam[g] = S[g].lam; }
-        if (!any(mask)) break;
-        ++rounds;
-        be.solve(mask, lam.data(), pcg_rel_tol, ok.data(), used.data());
-        for (size_t g = 0; g < G; ++g) tmask[g] = mask[g] && ok[g];
-        if (any(tmask)) {
-            be.trial(tmask);
-            be.eval(tmask, true, false, val.data());
-        }
-        for (size_t g = 0; g < G; ++g) acc[g] = mask[g] ? (gb_after_solve(S[g], ok[g] != 0, used[g], val[g], max_iters) ? 1 : 0) : 0;
-        if (!any(acc)) continue;
-        be.accept(acc);
-        for (size_t g = 0; g < G; ++g) tmask[g] = acc[g] && S[g].phase == kGbGradient;
-        if (!any(tmask)) continue;
-        be.eval(tmask, false, true, nullptr);
-        be.gradient(tmask, val.data());
-        for (size_t g = 0; g < G; ++g)
-            if (tmask[g]) gb_after_gradient(S[g], val[g], tol, max_iters);
-    }
+    while (gb_round(be, S, iters_of, tol_of, pcg_rel_tol, W)) ++rounds;
     return rounds;
 }
 
@@ -141,17 +164,22 @@ struct GbMember {  // where member g lives in the union arrays
     long long hblk0, gblk0;            // first slot of its block storage
     long long pose0, lm0;              // first scalar in the caller's pose / landmark arrays
     int mblk0, mblk1, ublk0, ublk1, sblk0, sblk1, tile0, tile1;  // its workgroups: measurements, unknowns, variables, product tiles
+    // the robust refinement (score_gn_robust_batch.hpp): its loop closures are the trailing n_lc relative-pose entries, lc0 is
+    // the first of them in the group's loop-closure order; its workgroups over ranges + loop closures
+    long long n_lc, lc0;
+    int rblk0, rblk1;
 };
 
 struct GbUnion {
     int dim = 2, count = 0;
-    long long n = 0, state_size = 0, hblk_size = 0, gblk_size = 0, poses_size = 0, lms_size = 0;
+    long long n = 0, state_size = 0, hblk_size = 0, gblk_size = 0, poses_size = 0, lms_size = 0, lcs_size = 0;
+    std::vector<char> lc_short;  // [member] fewer relative-pose entries than odometry steps: its loop closures cannot be re-weighted
     std::vector<GbMember> members;
     std::vector<int32_t> rel_i, rel_j, rng_a, rng_b, pri_l;
     std::vector<double> rel_t, rel_R, rel_kappa, rel_tau, rng_dist, rng_prec, pri_t, pri_prec;
     std::vector<int32_t> hptr, hcol, hc_ptr, hc_slot, gc_ptr, gc_slot, diag_member;  // diag_member[k]: member + 1 on a diagonal entry, else 0
     std::vector<int32_t> chain_ptr, node_first_col;
-    std::vector<int32_t> mblk_member, ublk_member, sblk_member;
+    std::vector<int32_t> mblk_member, ublk_member, sblk_member, rblk_member;
     std::vector<int4> tiles;  // {first row, end row, long row?, member}
     int dp() const { return dim == 2 ? 3 : 6; }
     int pose_scalars() const { return dim == 2 ? 3 : 12; }
@@ -178,9 +206,15 @@ inline void gb_build(const score_graph* graphs, int count, GbUnion& U) {
         M.rel0 = (long long)U.rel_i.size(); M.rng0 = (long long)U.rng_a.size(); M.pri0 = (long long)U.pri_l.size();
         M.state0 = U.state_size; M.col0 = U.n; M.hblk0 = U.hblk_size; M.gblk0 = U.gblk_size;
         M.pose0 = U.poses_size; M.lm0 = U.lms_size;
+        long long odometry = 0;
+        for (int32_t len : P.chain_len) odometry += (long long)len - 1;
+        M.n_lc = std::max<long long>(0, M.n_rel - odometry); M.lc0 = U.lcs_size;
+        U.lc_short.push_back(M.n_rel < odometry ? 1 : 0);
         const long long nnz0 = (long long)U.hcol.size(), hs0 = (long long)U.hc_slot.size(), gs0 = (long long)U.gc_slot.size();
         if (M.col0 + P.n >= lim / 64 || nnz0 + (long long)P.hcol.size() >= lim || hs0 + (long long)P.hc_slot.size() >= lim ||
-            M.hblk0 + P.hblk_size() >= lim || M.state0 + (long long)U.pose_scalars() * P.Np + U.dim * P.Nl >= lim)
+            M.hblk0 + P.hblk_size() >= lim || M.state0 + (long long)U.pose_scalars() * P.Np + U.dim * P.Nl >= lim ||
+            M.rel0 + M.n_rel >= lim || M.rng0 + M.n_rng >= lim || M.lc0 + M.n_lc >= lim ||
+            4 * ((long long)U.rblk_member.size() + (M.n_rng + M.n_lc) / kThreads + 1) >= lim)
             throw std::runtime_error("score_refine_batch: the group is too large for 32-bit positions (use smaller groups)");
         gb_append(U.rel_i, P.rel_i); gb_append(U.rel_j, P.rel_j); gb_append(U.rng_a, P.rng_a); gb_append(U.rng_b, P.rng_b);
         gb_append(U.pri_l, P.pri_l); gb_append(U.rel_t, P.rel_t); gb_append(U.rel_R, P.rel_R); gb_append(U.rel_kappa, P.rel_kappa);
@@ -206,6 +240,7 @@ inline void gb_build(const score_graph* graphs, int count, GbUnion& U) {
         M.mblk0 = (int)U.mblk_member.size(); U.mblk_member.insert(U.mblk_member.end(), (size_t)blocks(P.n_meas()), g); M.mblk1 = (int)U.mblk_member.size();
         M.ublk0 = (int)U.ublk_member.size(); U.ublk_member.insert(U.ublk_member.end(), (size_t)blocks(P.n), g); M.ublk1 = (int)U.ublk_member.size();
         M.sblk0 = (int)U.sblk_member.size(); U.sblk_member.insert(U.sblk_member.end(), (size_t)blocks(P.Np + P.Nl), g); M.sblk1 = (int)U.sblk_member.size();
+        M.rblk0 = (int)U.rblk_member.size(); U.rblk_member.insert(U.rblk_member.end(), (size_t)blocks(M.n_rng + M.n_lc), g); M.rblk1 = (int)U.rblk_member.size();
         // product tiles of the member's rows
         M.tile0 = (int)U.tiles.size();
         auto len = [&](long long i) { return P.hptr[(size_t)i + 1] - P.hptr[(size_t)i]; };
@@ -221,7 +256,7 @@ inline void gb_build(const score_graph* graphs, int count, GbUnion& U) {
         U.n += P.n;
         U.state_size += (long long)U.pose_scalars() * P.Np + (long long)U.dim * P.Nl;
         U.hblk_size += P.hblk_size(); U.gblk_size += P.gblk_size();
-        U.poses_size += (long long)U.pose_scalars() * P.Np; U.lms_size += (long long)U.dim * P.Nl;
+        U.poses_size += (long long)U.pose_scalars() * P.Np; U.lms_size += (long long)U.dim * P.Nl; U.lcs_size += M.n_lc;
         U.members.push_back(M);
     }
 }
@@ -231,7 +266,7 @@ inline void gb_build(const score_graph* graphs, int count, GbUnion& U) {
 // ---------------------------------------------------------------------------
 struct GbDev {
     const GbMember* members;
-    const int32_t *mblk_member, *ublk_member, *sblk_member;
+    const int32_t *mblk_member, *ublk_member, *sblk_member, *rblk_member;
     const int32_t *rel_i, *rel_j, *rng_a, *rng_b, *pri_l;
     const double *rel_t, *rel_R, *rel_kappa, *rel_tau, *rng_dist, *rng_prec, *pri_t, *pri_prec;
 };

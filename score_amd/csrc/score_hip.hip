@@ -4329,6 +4329,7 @@ struct score_refine {
 };
 
 #include "score_gn_batch.hpp"
+#include "score_gn_robust_batch.hpp"
 #include "score_marginals_batch.hpp"
 
 // Local refinement of a group of graphs in lock-step (score_gn_batch.hpp): the union state, blocks and gathers here, the
@@ -4342,7 +4343,7 @@ struct score_refine_batch {
     int rounds = 0;  // of the last run
     DevBuf<score::GbMember> members;
     DevBuf<int4> tiles;
-    DevBuf<int32_t> mblk_member, ublk_member, sblk_member, rel_i, rel_j, rng_a, rng_b, pri_l, hc_ptr, hc_slot, gc_ptr, gc_slot, diag_member;
+    DevBuf<int32_t> mblk_member, ublk_member, sblk_member, rblk_member, rel_i, rel_j, rng_a, rng_b, pri_l, hc_ptr, hc_slot, gc_ptr, gc_slot, diag_member;
     DevBuf<int32_t> mask, flags;  // flags: [done per member | steps per member | a zero (the chain kernel's done word)]
     DevBuf<double> rel_t, rel_R, rel_kappa, rel_tau, rng_dist, rng_prec, pri_t, pri_prec;
     DevBuf<double> X, Xt, hblk, gblk, rhs, cost_part, gmax_part, lambda;
@@ -4352,6 +4353,14 @@ struct score_refine_batch {
     std::vector<double> part_host;
     std::vector<int32_t> word_host;
     score::GbmWork mvb;  // marginal covariances of the members (score_marginals_batch.hpp)
+    // robust refinement (score_gn_robust_batch.hpp): the measured precisions beside rng_prec / rel_kappa / rel_tau (which hold the
+    // weighted ones during a robust run, and after one with keep_weights), residuals, weights, per-workgroup partials, the
+    // members' parameters; they come with the first robust call.  U keeps rng_prec / rel_kappa / rel_tau on the host for them.
+    DevBuf<double> rb_prec0, rb_kappa0, rb_tau0, rb_r_rng, rb_r_lc, rb_w_rng, rb_w_lc, rb_part;
+    DevBuf<score::GbrParam> rb_params;
+    std::vector<double> rb_kappa0_host, rb_tau0_host;   // loop-closure order
+    bool rb_ready = false;
+    int robust_rounds = 0, stage_rounds = 0;  // of the last robust run: its rounds, the passes in which some member changed stage
 
     HipBackend& be() { return lin->solver.be; }
     hipStream_t stream() { return lin->solver.be.stream; }
@@ -4359,6 +4368,7 @@ struct score_refine_batch {
     score::GbDev dev() const {
         score::GbDev d{};
         d.members = members.d; d.mblk_member = mblk_member.d; d.ublk_member = ublk_member.d; d.sblk_member = sblk_member.d;
+        d.rblk_member = rblk_member.d;
         d.rel_i = rel_i.d; d.rel_j = rel_j.d; d.rng_a = rng_a.d; d.rng_b = rng_b.d; d.pri_l = pri_l.d;
         d.rel_t = rel_t.d; d.rel_R = rel_R.d; d.rel_kappa = rel_kappa.d; d.rel_tau = rel_tau.d;
         d.rng_dist = rng_dist.d; d.rng_prec = rng_prec.d; d.pri_t = pri_t.d; d.pri_prec = pri_prec.d;
@@ -4386,6 +4396,7 @@ struct score_refine_batch {
         } arena_scope(&be().arena);
         members.upload(U.members); tiles.upload(U.tiles);
         mblk_member.upload(U.mblk_member); ublk_member.upload(U.ublk_member); sblk_member.upload(U.sblk_member);
+        rblk_member.upload(U.rblk_member);
         rel_i.upload(U.rel_i); rel_j.upload(U.rel_j); rng_a.upload(U.rng_a); rng_b.upload(U.rng_b); pri_l.upload(U.pri_l);
         rel_t.upload(U.rel_t); rel_R.upload(U.rel_R); rel_kappa.upload(U.rel_kappa); rel_tau.upload(U.rel_tau);
         rng_dist.upload(U.rng_dist); rng_prec.upload(U.rng_prec); pri_t.upload(U.pri_t); pri_prec.upload(U.pri_prec);
@@ -4411,11 +4422,11 @@ struct score_refine_batch {
         flags.zero(stream());
         be().linear_buffers(lin->solver.H);
         HIP_CHECK(sync_stream(stream()));
-        // the lists live on the device now
+        // the lists live on the device now (the precisions a robust run re-weights stay: its checks and prec0 read them)
         for (std::vector<int32_t>* v : {&U.hptr, &U.hcol, &U.hc_ptr, &U.hc_slot, &U.gc_ptr, &U.gc_slot, &U.diag_member, &U.rel_i, &U.rel_j,
                                         &U.rng_a, &U.rng_b, &U.pri_l, &U.chain_ptr, &U.node_first_col})
             std::vector<int32_t>().swap(*v);
-        for (std::vector<double>* v : {&U.rel_t, &U.rel_R, &U.rel_kappa, &U.rel_tau, &U.rng_dist, &U.rng_prec, &U.pri_t, &U.pri_prec})
+        for (std::vector<double>* v : {&U.rel_t, &U.rel_R, &U.rng_dist, &U.pri_t, &U.pri_prec})
             std::vector<double>().swap(*v);
         pt.mark("refine batch: uploads + buffers");
         setup_ms = score::now_ms() - t0;
@@ -4566,15 +4577,180 @@ struct score_refine_batch {
     }
     void run(const double* poses_in, const double* lms_in, int max_iters, double tol, double* poses_out, double* lms_out,
              std::vector<score::GbState>& S) {
-        const int ps = U.pose_scalars(), d = U.dim;
         std::vector<double> h = set_point(poses_in, lms_in);
         rounds = score::gb_lock_step(*this, U.count, max_iters, tol, 1e-9, S);
+        read_points(h, poses_out, lms_out);
+    }
+    // the members' current points (X) in the caller's layout; h: scratch of the state's size
+    void read_points(std::vector<double>& h, double* poses_out, double* lms_out) {
+        const int ps = U.pose_scalars(), d = U.dim;
         staged_d2h(h.data(), X.d, h.size() * sizeof(double), stream());
         HIP_CHECK(sync_stream(stream()));
         for (const score::GbMember& M : U.members) {
             std::copy(h.begin() + (std::ptrdiff_t)M.state0, h.begin() + (std::ptrdiff_t)(M.state0 + ps * M.Np), poses_out + M.pose0);
             if (M.Nl) std::copy(h.begin() + (std::ptrdiff_t)(M.state0 + ps * M.Np), h.begin() + (std::ptrdiff_t)(M.state0 + ps * M.Np + d * M.Nl), lms_out + M.lm0);
         }
+    }
+
+    // ---- robust refinement: the hooks of gbr_lock_step (score_gn_robust_batch.hpp) ----
+    // the measured precisions of member g's loop closures on the host (before robust_reserve: from U)
+    void robust_host_precisions() {
+        if (!rb_kappa0_host.empty() || U.lcs_size == 0) return;
+        rb_kappa0_host.reserve((size_t)U.lcs_size); rb_tau0_host.reserve((size_t)U.lcs_size);
+        for (const score::GbMember& M : U.members)
+            for (long long q = 0; q < M.n_lc; ++q) {
+                const size_t m = (size_t)(M.rel0 + (M.n_rel - M.n_lc) + q);
+                rb_kappa0_host.push_back(U.rel_kappa[m]); rb_tau0_host.push_back(U.rel_tau[m]);
+            }
+    }
+    void robust_check(const score_refine_robust_settings* rs, int n_settings) {
+        if (n_settings != 1 && n_settings != U.count)
+            throw std::runtime_error("score_refine_batch_robust_run: n_settings must be 1 or the number of members");
+        robust_host_precisions();
+        for (int g = 0; g < U.count; ++g) {
+            const score::GbMember& M = U.members[(size_t)g];
+            if ((rs[n_settings == 1 ? 0 : g].families & score::kGnRobustClosures) && U.lc_short[(size_t)g])
+                throw std::runtime_error("score_refine_batch_robust_run: member " + std::to_string(g) +
+                                         ": fewer relative-pose entries than odometry steps");
+            score::gbr_check(rs[n_settings == 1 ? 0 : g], g, U.rng_prec.data() + M.rng0, M.n_rng, rb_kappa0_host.data() + M.lc0,
+                             rb_tau0_host.data() + M.lc0, M.n_lc);
+        }
+    }
+    void robust_reserve() {  // the buffers, from the handle's arena
+        if (rb_ready) return;
+        robust_host_precisions();
+        struct ArenaScope {
+            DevArena* keep;
+            explicit ArenaScope(DevArena* a) : keep(tl_arena) { tl_arena = a; }
+            ~ArenaScope() { tl_arena = keep; }
+        } arena_scope(&be().arena);
+        tl_copy_stream = stream();
+        const size_t nr = U.rng_prec.size(), nc = (size_t)U.lcs_size;
+        rb_prec0.upload(U.rng_prec); rb_kappa0.upload(rb_kappa0_host); rb_tau0.upload(rb_tau0_host);
+        rb_r_rng.alloc(nr); rb_w_rng.alloc(nr); rb_r_lc.alloc(nc); rb_w_lc.alloc(nc);
+        rb_part.alloc((size_t)score::kGnRobustPart * U.rblk_member.size());
+        rb_params.alloc((size_t)U.count);
+        if (nr) rb_w_rng.zero(stream());  // (k_gbr_resid counts the non-binary weights of whatever was last written)
+        if (nc) rb_w_lc.zero(stream());
+        HIP_CHECK(sync_stream(stream()));
+        rb_ready = true;
+    }
+    score::GbrDev robust_dev() const {
+        score::GbrDev a{};
+        a.d = dev();
+        a.prec0 = rb_prec0.d; a.kappa0 = rb_kappa0.d; a.tau0 = rb_tau0.d;
+        a.prec = rng_prec.d; a.kappa = rel_kappa.d; a.tau = rel_tau.d;
+        a.r_rng = rb_r_rng.d; a.r_lc = rb_r_lc.d; a.w_rng = rb_w_rng.d; a.w_lc = rb_w_lc.d;
+        a.params = rb_params.d;
+        return a;
+    }
+    void robust_weights(const std::vector<char>& m, const score::GbrParam* params) {
+        set_mask(m);
+        HIP_CHECK(hipMemcpyAsync(rb_params.d, params, (size_t)U.count * sizeof(score::GbrParam), hipMemcpyHostToDevice, stream()));
+        hipLaunchKernelGGL(score::k_gbr_weight, dim3((unsigned)U.rblk_member.size()), dim3(kThreads), 0, stream(), robust_dev(),
+                           (const int32_t*)mask.d);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(sync_stream(stream()));  // (params is the caller's)
+    }
+    void robust_all(double mu, double min_weight, int32_t mode) {  // every member, both families
+        const int both = score::kGnRobustRanges | score::kGnRobustClosures;
+        std::vector<score::GbrParam> params((size_t)U.count, score::GbrParam{mu, 1.0, 1.0, min_weight, both, mode});
+        robust_weights(std::vector<char>((size_t)U.count, 1), params.data());
+    }
+    void robust_begin() { robust_all(0.0, 1.0, score::kGbrNext); }
+    void robust_restore() noexcept {
+        if (!rb_ready) return;
+        try { robust_all(0.0, 1.0, score::kGbrRestore); } catch (...) {}
+    }
+    void robust_residuals(const std::vector<char>& m, score::GbrSeen* seen) {
+        set_mask(m);
+        const unsigned nb = (unsigned)U.rblk_member.size();
+        if (U.dim == 2)
+            hipLaunchKernelGGL(score::k_gbr_resid<2>, dim3(nb), dim3(kThreads), 0, stream(), robust_dev(), (const double*)X.d, rb_part.d,
+                               (const int32_t*)mask.d);
+        else
+            hipLaunchKernelGGL(score::k_gbr_resid<3>, dim3(nb), dim3(kThreads), 0, stream(), robust_dev(), (const double*)X.d, rb_part.d,
+                               (const int32_t*)mask.d);
+        HIP_CHECK(hipGetLastError());
+        part_host.resize((size_t)score::kGnRobustPart * nb);
+        HIP_CHECK(hipMemcpyAsync(part_host.data(), rb_part.d, part_host.size() * sizeof(double), hipMemcpyDeviceToHost, stream()));
+        HIP_CHECK(sync_stream(stream()));
+        for (int g = 0; g < U.count; ++g) {
+            if (!m[(size_t)g]) continue;
+            const score::GbMember& M = U.members[(size_t)g];
+            double r2[2] = {0.0, 0.0}, nonbin[2] = {0.0, 0.0};
+            for (int b = M.rblk0; b < M.rblk1; ++b) {  // the member's partials in workgroup order
+                const double* p = part_host.data() + (size_t)score::kGnRobustPart * (size_t)b;
+                for (int f = 0; f < 2; ++f) {
+                    r2[f] = p[f] != p[f] ? INFINITY : std::max(r2[f], p[f]);
+                    nonbin[f] += p[2 + f];
+                }
+            }
+            seen[g].f[0] = score::RobustSeen{(int64_t)M.n_rng, r2[0], 0.0, (int32_t)nonbin[0]};
+            seen[g].f[1] = score::RobustSeen{(int64_t)M.n_lc, r2[1], 0.0, (int32_t)nonbin[1]};
+        }
+    }
+    // residuals and weights as they are on the device, into the caller's arrays (null: not wanted); hw / hwl: the weights
+    void robust_read(double* w, double* r, double* wl, double* rl, std::vector<double>& hw, std::vector<double>& hwl) {
+        const size_t nr = rb_r_rng.n, nc = rb_r_lc.n, f8 = sizeof(double);
+        hw.resize(nr); hwl.resize(nc);
+        if (nr) staged_d2h(hw.data(), rb_w_rng.d, nr * f8, stream());
+        if (nc) staged_d2h(hwl.data(), rb_w_lc.d, nc * f8, stream());
+        if (r && nr) staged_d2h(r, rb_r_rng.d, nr * f8, stream());
+        if (rl && nc) staged_d2h(rl, rb_r_lc.d, nc * f8, stream());
+        HIP_CHECK(sync_stream(stream()));
+        if (w) std::copy(hw.begin(), hw.end(), w);
+        if (wl) std::copy(hwl.begin(), hwl.end(), wl);
+    }
+    // rs: one record per member
+    void robust_run(const score_refine_robust_settings* rs, const double* poses_in, const double* lms_in, double* poses_out, double* lms_out,
+                    double* w, double* r, double* wl, double* rl, bool keep, std::vector<score::GbState>& S, std::vector<score::GbrState>& R,
+                    std::vector<int32_t>& outliers, std::vector<int32_t>& rel_outliers) {
+        robust_reserve();
+        struct Restore {  // unless the weights are kept, the handle ends with the measured precisions
+            score_refine_batch& h;
+            bool armed = true;
+            ~Restore() { if (armed) h.robust_restore(); }
+        } restore{*this};
+        std::vector<double> h = set_point(poses_in, lms_in);
+        rounds = robust_rounds = score::gbr_lock_step(*this, U.count, rs, 1e-9, S, R, &stage_rounds);
+        const std::vector<char> all((size_t)U.count, 1);
+        std::vector<score::GbrSeen> seen((size_t)U.count);
+        robust_residuals(all, seen.data());  // every family's r at the final estimates
+        std::vector<double> hw, hwl;
+        robust_read(w, r, wl, rl, hw, hwl);
+        outliers.assign((size_t)U.count, 0); rel_outliers.assign((size_t)U.count, 0);
+        for (int g = 0; g < U.count; ++g) {
+            const score::GbMember& M = U.members[(size_t)g];
+            for (long long e = M.rng0; e < M.rng0 + M.n_rng; ++e) outliers[(size_t)g] += hw[(size_t)e] < 0.5 ? 1 : 0;
+            if (rs[g].families & score::kGnRobustClosures)
+                for (long long e = M.lc0; e < M.lc0 + M.n_lc; ++e) rel_outliers[(size_t)g] += hwl[(size_t)e] < 0.5 ? 1 : 0;
+        }
+        if (poses_out) read_points(h, poses_out, lms_out);
+        if (keep) {
+            robust_all(0.0, 1.0, score::kGbrKeep);
+            restore.armed = false;
+        }
+    }
+    void robust_inspect(const double* poses, const double* lms, const double* mu, const double* c, const double* c_rel, double* r, double* rl,
+                        double* w, double* wl) {
+        const int both = score::kGnRobustRanges | score::kGnRobustClosures;
+        std::vector<score::GbrParam> params((size_t)U.count);
+        for (int g = 0; g < U.count; ++g) {
+            const std::string who = "score_refine_batch_residuals: member " + std::to_string(g);
+            if (!(mu[g] >= 0.0) || !std::isfinite(mu[g])) throw std::runtime_error(who + ": mu must be finite and >= 0");
+            if (mu[g] > 0.0 && !(std::isfinite(c[g]) && c[g] > 0.0 && std::isfinite(c_rel[g]) && c_rel[g] > 0.0))
+                throw std::runtime_error(who + ": c and c_rel must be positive and finite when mu > 0");
+            params[(size_t)g] = score::GbrParam{mu[g], c[g], c_rel[g], 1.0, both, score::kGbrInspect};
+        }
+        robust_reserve();
+        (void)set_point(poses, lms);
+        const std::vector<char> all((size_t)U.count, 1);
+        std::vector<score::GbrSeen> seen((size_t)U.count);
+        robust_residuals(all, seen.data());
+        robust_weights(all, params.data());
+        std::vector<double> hw, hwl;
+        robust_read(w, r, wl, rl, hw, hwl);
     }
 };
 
@@ -4767,6 +4943,70 @@ int score_refine_batch_marginals(score_refine_batch* b, const double* poses, con
         require(poses && (b->U.lms_size == 0 || landmarks), "score_refine_batch_marginals: the points are missing");
         AbiEnv::Scope scope(b->device, false);
         return score::gbm_solve(*b, poses, landmarks, var_ptr, vars, rel_tol, max_iters, block_width, joint, residuals, iters, info);
+    });
+}
+int score_refine_batch_robust_run(score_refine_batch* b, const score_refine_robust_settings* rs, int32_t n_settings, const double* poses_in,
+                                  const double* landmarks_in, double* poses_out, double* landmarks_out, double* weights, double* residuals,
+                                  double* rel_weights, double* rel_residuals, int32_t keep_weights, score_refine_robust_info* infos) {
+    return abi_call([&] {
+        require(b != nullptr, "score_refine_batch_robust_run: null handle");
+        AbiEnv::Scope scope(b->device, false);
+        try {   // (host only: nothing on the device is touched before the arguments and the settings stand)
+            require(rs != nullptr, "score_refine_batch_robust_run: the settings are missing");
+            require(poses_in && (b->U.lms_size == 0 || landmarks_in), "score_refine_batch_robust_run: the points are missing");
+            require(!poses_out || b->U.lms_size == 0 || landmarks_out, "score_refine_batch_robust_run: landmarks_out is missing");
+            b->robust_check(rs, n_settings);
+        } catch (...) {
+            b->robust_restore();               // (weights a previous call kept do not survive an error return)
+            throw;
+        }
+        const double t0 = score::now_ms();
+        std::vector<score_refine_robust_settings> per((size_t)b->U.count);
+        for (int g = 0; g < b->U.count; ++g) per[(size_t)g] = rs[n_settings == 1 ? 0 : g];
+        std::vector<score::GbState> S;
+        std::vector<score::GbrState> R;
+        std::vector<int32_t> outliers, rel_outliers;
+        b->robust_run(per.data(), poses_in, landmarks_in, poses_out, landmarks_out, weights, residuals, rel_weights, rel_residuals,
+                      keep_weights != 0, S, R, outliers, rel_outliers);
+        const double ms = score::now_ms() - t0;
+        for (int g = 0; infos && g < b->U.count; ++g) {
+            const score::GbState& m = S[(size_t)g];
+            const score::GbrState& o = R[(size_t)g];
+            score_refine_robust_info& info = infos[g];
+            info.outer_iterations = o.k; info.converged = o.converged ? 1 : 0;
+            info.outliers = outliers[(size_t)g]; info.rel_outliers = rel_outliers[(size_t)g]; info.mu = o.mu;
+            info.lm_iterations = o.lm_iterations; info.linear_solves = o.linear_solves; info.pcg_iters = o.pcg_iters;
+            info.cost_initial = o.cost_initial; info.cost_final = m.f; info.grad_inf = m.gnorm;
+            info.setup_ms = b->setup_ms; info.solve_ms = ms;
+        }
+        return 0;
+    });
+}
+int score_refine_batch_residuals(score_refine_batch* b, const double* poses, const double* landmarks, const double* mu, const double* c,
+                                 const double* c_rel, double* residuals, double* rel_residuals, double* weights, double* rel_weights) {
+    return abi_call([&] {
+        require(b != nullptr, "score_refine_batch_residuals: null handle");
+        require(poses && (b->U.lms_size == 0 || landmarks), "score_refine_batch_residuals: the points are missing");
+        require(mu && c && c_rel, "score_refine_batch_residuals: mu, c and c_rel take one entry per member");
+        AbiEnv::Scope scope(b->device, false);
+        b->robust_inspect(poses, landmarks, mu, c, c_rel, residuals, rel_residuals, weights, rel_weights);
+        return 0;
+    });
+}
+int score_refine_batch_restore(score_refine_batch* b) {
+    return abi_call([&] {
+        require(b != nullptr, "score_refine_batch_restore: null handle");
+        AbiEnv::Scope scope(b->device, false);
+        if (b->rb_ready) b->robust_all(0.0, 1.0, score::kGbrRestore);
+        return 0;
+    });
+}
+int score_refine_batch_robust_rounds(score_refine_batch* b, int32_t* rounds, int32_t* stage_rounds) {
+    return abi_call([&] {
+        require(b != nullptr, "score_refine_batch_robust_rounds: null handle");
+        if (rounds) *rounds = b->robust_rounds;
+        if (stage_rounds) *stage_rounds = b->stage_rounds;
+        return 0;
     });
 }
 void score_refine_batch_destroy(score_refine_batch* b) {

@@ -204,6 +204,84 @@ class RefineBatchHandle:
 
         return batch_columns(self, points, ids_per_member, rel_tol, max_iters, block_width)
 
+    def _flat_points(self, points):
+        if len(points) != len(self.probs):
+            raise ValueError("one point per member expected")
+        arrays = [_point_arrays(prob, x) for prob, x in zip(self.probs, points)]
+        poses = np.ascontiguousarray(np.concatenate([a[0].ravel() for a in arrays]))
+        lms = np.ascontiguousarray(np.concatenate([a[1].ravel() for a in arrays]))
+        return arrays, poses, lms
+
+    def _per_member(self, flat, counts):
+        offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        return [flat[offs[g] : offs[g + 1]].copy() for g in range(len(counts))]
+
+    def robust_run(self, points, settings, keep_weights: bool = False):
+        """``score_refine_batch_robust_run`` (include/score_refine_robust_batch.h): ``settings`` is one
+        ``ScoreRefineRobustSettings`` (shared) or a sequence with one per member.  Returns (points, per member
+        ``(weights, residuals, loop-closure weights, loop-closure residuals)``, info dicts)."""
+        from .refine_robust import ScoreRefineRobustInfo, ScoreRefineRobustSettings
+        from .refine_robust_batch import _bind as bind_robust, member_counts
+        from .solver import _f64p
+
+        lib = bind_robust(self.lib)
+        G = len(self.probs)
+        recs = [settings] if isinstance(settings, ScoreRefineRobustSettings) else list(settings)
+        rs = (ScoreRefineRobustSettings * max(1, len(recs)))(*recs)
+        arrays, poses_in, lms_in = self._flat_points(points)
+        width = arrays[0][1].shape[1]
+        poses_out, lms_out = np.empty_like(poses_in), np.empty(max(1, lms_in.size))
+        n_rng, n_lc = member_counts(self.probs)
+        w, r, wl, rl = (np.ones(max(1, int(sum(n)))) for n in (n_rng, n_rng, n_lc, n_lc))
+        infos = (ScoreRefineRobustInfo * G)()
+        p = lambda x: x.ctypes.data_as(_f64p)  # noqa: E731
+        rc = lib.score_refine_batch_robust_run(self.h, rs, len(recs), p(poses_in), p(lms_in) if lms_in.size else None, p(poses_out),
+                                               p(lms_out), p(w), p(r), p(wl), p(rl), 1 if keep_weights else 0, infos)
+        if rc != 0:
+            raise RuntimeError(f"score_refine_batch_robust_run failed: {self.lib.score_last_error().decode()}")
+        out, p0, l0 = [], 0, 0
+        for prob, (pa, la) in zip(self.probs, arrays):
+            out.append(_point_from(prob, poses_out[p0 : p0 + pa.size].reshape(pa.shape), lms_out[l0 : l0 + la.size].reshape(-1, width)))
+            p0 += pa.size
+            l0 += la.size
+        per = list(zip(self._per_member(w, n_rng), self._per_member(r, n_rng), self._per_member(wl, n_lc), self._per_member(rl, n_lc)))
+        return out, per, [infos[i].as_dict() for i in range(G)]
+
+    def residuals(self, points, mu=0.0, c=3.0, c_rel=3.0):
+        """``score_refine_batch_residuals`` at ``points``: ``mu``, ``c``, ``c_rel`` a scalar or one entry per member.  Returns
+        per member ``(residuals, loop-closure residuals, weights, loop-closure weights)``."""
+        from .refine_robust_batch import _bind as bind_robust, member_counts
+        from .solver import _f64p
+
+        lib = bind_robust(self.lib)
+        G = len(self.probs)
+        mu, c, c_rel = (np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (G,))) for v in (mu, c, c_rel))
+        _, poses, lms = self._flat_points(points)
+        n_rng, n_lc = member_counts(self.probs)
+        w, r, wl, rl = (np.ones(max(1, int(sum(n)))) for n in (n_rng, n_rng, n_lc, n_lc))
+        p = lambda x: x.ctypes.data_as(_f64p)  # noqa: E731
+        rc = lib.score_refine_batch_residuals(self.h, p(poses), p(lms) if lms.size else None, p(mu), p(c), p(c_rel), p(r), p(rl), p(w), p(wl))
+        if rc != 0:
+            raise RuntimeError(f"score_refine_batch_residuals failed: {self.lib.score_last_error().decode()}")
+        return list(zip(self._per_member(r, n_rng), self._per_member(rl, n_lc), self._per_member(w, n_rng), self._per_member(wl, n_lc)))
+
+    def robust_rounds(self):
+        """``score_refine_batch_robust_rounds``: (lock-step rounds, passes in which some member changed stage) of the last
+        ``robust_run``."""
+        from .refine_robust_batch import _bind as bind_robust
+
+        rounds, stages = C.c_int32(0), C.c_int32(0)
+        if bind_robust(self.lib).score_refine_batch_robust_rounds(self.h, C.byref(rounds), C.byref(stages)) != 0:
+            raise RuntimeError(f"score_refine_batch_robust_rounds failed: {self.lib.score_last_error().decode()}")
+        return int(rounds.value), int(stages.value)
+
+    def restore(self) -> None:
+        """``score_refine_batch_restore``: the handle's cost reads the measured precisions again (after ``keep_weights``)."""
+        from .refine_robust_batch import _bind as bind_robust
+
+        if bind_robust(self.lib).score_refine_batch_restore(self.h) != 0:
+            raise RuntimeError(f"score_refine_batch_restore failed: {self.lib.score_last_error().decode()}")
+
     def close(self) -> None:
         if self.h:
             self.lib.score_refine_batch_destroy(self.h)

@@ -1,0 +1,338 @@
+"""Outlier-robust local refinement of many graphs in lock-step (include/score_refine_robust_batch.h,
+csrc/score_gn_robust_batch.hpp): the GNC-TLS loop of ``refine_estimate_robust``, one per member, on the group handles of
+``refine_estimate_batch``.
+
+Every member has its own ``mu``, its own count of outer solves and its own place in the schedule (first run, inner runs, last
+run).  When a member's Levenberg-Marquardt run stops it gets its residuals, the stop rule, ``mu`` and its weights, and is solved
+again in the next round while others are mid-run or finished; members whose runs stop in the same round share the launches.
+Members never influence one another: member by member the result is ``refine_estimate_robust``'s.
+
+``engine="python"`` is the same controller in Python with SciPy's sparse LU (``_Stage`` is the library's ``GbrState``, around
+``refine_batch._Member``): it only reorders independent work, so member by member it EQUALS
+``refine_estimate_robust(engine="python", linear_solver="scipy")``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+import scipy.sparse as sp
+import scipy.sparse.linalg as spla
+
+from .refine import _as_results
+from .refine_batch import GRADIENT, SOLVE, STOPPED, RefineBatchHandle, _Member, _problem_of, _weights_of
+from .refine_robust import (FAMILY_LOOP_CLOSURES, FAMILY_RANGES, ScoreRefineRobustInfo, ScoreRefineRobustSettings, _check, _nonbinary,
+                            _prior, decide, first_mu, loop_closure_residuals, range_residuals, refine_estimate_robust)
+from .robust import _robust_info, gnc_tls_weight, n_loop_closures_of
+from .solver import _f64p
+
+# the symbols include/score_refine_robust_batch.h declares
+REFINE_ROBUST_BATCH_SYMBOLS = ["score_refine_batch_robust_run", "score_refine_batch_residuals", "score_refine_batch_restore",
+                               "score_refine_batch_robust_rounds"]
+
+FIRST, INNER, LAST, DONE = "first", "inner", "last", "done"
+
+
+def _bind(lib: C.CDLL) -> C.CDLL:
+    if getattr(lib, "_score_refine_robust_batch_bound", False):
+        return lib
+    for sym in REFINE_ROBUST_BATCH_SYMBOLS:
+        if not hasattr(lib, sym):
+            raise RuntimeError(f"{sym} is missing from the library: rebuild it (the CPU twin of the tests has no robust "
+                               "refinement: engine='python' runs there)")
+    lib.score_refine_batch_robust_run.argtypes = [C.c_void_p, C.POINTER(ScoreRefineRobustSettings), C.c_int32, _f64p, _f64p, _f64p,
+                                                  _f64p, _f64p, _f64p, _f64p, _f64p, C.c_int32, C.POINTER(ScoreRefineRobustInfo)]
+    lib.score_refine_batch_robust_run.restype = C.c_int
+    lib.score_refine_batch_residuals.argtypes = [C.c_void_p] + [_f64p] * 9
+    lib.score_refine_batch_residuals.restype = C.c_int
+    lib.score_refine_batch_restore.argtypes = [C.c_void_p]
+    lib.score_refine_batch_restore.restype = C.c_int
+    lib.score_refine_batch_robust_rounds.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.score_refine_batch_robust_rounds.restype = C.c_int
+    lib._score_refine_robust_batch_bound = True
+    return lib
+
+
+def member_counts(probs):
+    """(ranges, loop closures) of every member."""
+    return [len(p.ra) for p in probs], [n_loop_closures_of(p.a) for p in probs]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# engine="python": the lock-step twin
+# ---------------------------------------------------------------------------------------------------------------------
+class _Stage:
+    """One member's place in the loop of ``refine_estimate_robust`` (``refine_robust._python_loop``, the same operations in the
+    same order), and what it does when one of its runs stops."""
+
+    def __init__(self, prob, s: dict):
+        self.prob, self.s = prob, s
+        self.f_rng, self.f_rel = bool(s["families"] & FAMILY_RANGES), bool(s["families"] & FAMILY_LOOP_CLOSURES)
+        self.n_lc = n_loop_closures_of(prob.a)
+        self.first = len(prob.bi) - self.n_lc
+        self.prec0 = np.array(prob.a["rng_prec"], dtype=np.float64)
+        self.kappa0 = np.array(prob.a["rel_kappa"], dtype=np.float64)[self.first:]
+        self.tau0 = np.array(prob.a["rel_tau"], dtype=np.float64)[self.first:]
+        self.w, self.wl = np.ones(len(self.prec0)), np.ones(self.n_lc)
+        self.sk_all, self.st_all = prob.sk.copy(), prob.st.copy()
+        self.stage, self.k, self.mu, self.what = FIRST, 1, 0.0, "go"
+        self.lm = self.linear_solves = 0
+        self.cost_initial = 0.0
+
+    def cap(self) -> int:
+        return self.s["inner_iters"] if self.stage == INNER else self.s["max_iters"]
+
+    def weigh(self, floor: Optional[float]) -> None:
+        """The precisions the cost reads: prec max(w, floor) in the enabled families (floor None: prec w)."""
+        prob = self.prob
+        fl = (lambda w: np.maximum(w, floor)) if floor is not None else (lambda w: w)
+        if self.f_rng:
+            prob.sw = np.sqrt(self.prec0 * fl(self.w))
+        if self.f_rel and self.n_lc:
+            f = fl(self.wl)
+            self.sk_all[self.first:], self.st_all[self.first:] = np.sqrt(self.kappa0 * f), np.sqrt(self.tau0 * f)
+            prob.sk, prob.st = self.sk_all, self.st_all
+
+    def run_stopped(self, u, member: _Member) -> bool:
+        """The member's run has stopped at ``u``: True when another run follows."""
+        s = self.s
+        self.lm += member.iterations
+        self.linear_solves += member.linear_solves
+        if self.stage == LAST:
+            self.stage = DONE
+            return False
+        seen = []
+        if self.f_rng:
+            r = range_residuals(self.prob, u, self.prec0)
+            seen.append((len(r), float(np.max(r * r)) if len(r) else 0.0, s["c"], _nonbinary(self.w)))
+        if self.f_rel:
+            rl = loop_closure_residuals(self.prob, u, self.kappa0, self.tau0)
+            seen.append((len(rl), float(np.max(rl * rl)) if len(rl) else 0.0, s["c_rel"], _nonbinary(self.wl)))
+        self.what = decide(self.k, s["max_outer"], seen)
+        if self.what == "go":
+            self.mu = first_mu(seen) if self.k == 1 else self.mu * s["mu_step"]
+            if self.f_rng:
+                self.w = gnc_tls_weight(r, self.mu, s["c"])
+            if self.f_rel:
+                self.wl = gnc_tls_weight(rl, self.mu, s["c_rel"])
+            self.weigh(s["min_weight"])
+            self.k += 1
+            self.stage = INNER
+            return True
+        if self.k > 1 and self.what != "non_finite":  # the final weights, to max_iters / tol
+            self.stage = LAST
+            return True
+        self.stage = DONE
+        return False
+
+
+def _python_robust_lock_step(probs, points, settings):
+    """``refine_batch._python_lock_step`` with a stage per member.  Returns (points, last-run members, stages, rounds, the
+    passes in which some member changed stage)."""
+    G = len(probs)
+    u = list(points)
+    R = [_Stage(prob, s) for prob, s in zip(probs, settings)]
+    S: list = [None] * G
+    lin: list = [None] * G
+    grad: list = [None] * G
+    H: list = [None] * G
+
+    def gradient(g: int) -> None:
+        res, J = lin[g]
+        grad[g] = J.T @ res
+        S[g].after_gradient(float(np.abs(grad[g]).max()) if grad[g].size else 0.0, settings[g]["tol"], R[g].cap())
+        H[g] = (J.T @ J).tocsc() if S[g].phase == SOLVE else None
+
+    def start(g: int) -> None:  # a run from the member's current point, under the precisions as they stand
+        lin[g] = probs[g].residuals(u[g], jac=True)
+        res = lin[g][0]
+        S[g] = _Member(float(res @ res), R[g].cap())
+        if S[g].phase == GRADIENT:
+            gradient(g)
+
+    for g in range(G):
+        start(g)
+        R[g].cost_initial = S[g].cost_initial
+    rounds = stage_rounds = 0
+    while True:
+        ended = [g for g in range(G) if R[g].stage != DONE and S[g].phase == STOPPED]
+        if ended:
+            stage_rounds += 1
+            for g in ended:
+                if R[g].run_stopped(u[g], S[g]):
+                    start(g)
+            continue
+        live = [g for g in range(G) if S[g].phase == SOLVE]
+        if not live:
+            break
+        rounds += 1
+        for g in live:
+            prob, cap = probs[g], R[g].cap()
+            ok, un, fn = True, None, float("nan")
+            try:
+                step = spla.splu((H[g] + S[g].lam * sp.identity(prob.n, format="csc")).tocsc()).solve(-grad[g])
+            except RuntimeError:
+                ok = False
+            if ok:
+                un = prob.retract(u[g], step)
+                fn = prob.cost(un)
+            if S[g].after_solve(ok, 0, fn, cap):
+                u[g] = un
+                if S[g].phase == GRADIENT:
+                    lin[g] = prob.residuals(un, jac=True)
+                    gradient(g)
+    return u, S, R, rounds, stage_rounds
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# public interface
+# ---------------------------------------------------------------------------------------------------------------------
+def _per_graph(value, count: int, what: str) -> list:
+    if value is None or np.ndim(value) == 0:
+        return [value] * count
+    value = list(value)
+    if len(value) != count:
+        raise ValueError(f"{what}: a scalar or one entry per graph expected ({count}), got {len(value)}")
+    return value
+
+
+def _check_precisions(prob, f_rng: bool, f_rel: bool) -> None:
+    n_lc = n_loop_closures_of(prob.a)
+    if f_rng and len(prob.ra) and not (np.all(np.isfinite(prob.a["rng_prec"])) and np.all(np.asarray(prob.a["rng_prec"]) > 0)):
+        raise ValueError("every range precision must be positive and finite")
+    if f_rel:
+        if n_lc < 0:
+            raise ValueError("fewer relative-pose entries than odometry steps")
+        for key in ("rel_kappa", "rel_tau"):
+            v = np.asarray(prob.a[key], dtype=np.float64)[len(prob.bi) - n_lc:]
+            if v.size and not (np.all(np.isfinite(v)) and np.all(v > 0)):
+                raise ValueError(f"every loop closure's precision ({key}) must be positive and finite")
+
+
+def refine_estimate_robust_batch(datas, results, inlier_threshold=3.0, robust_ranges: bool = True, robust_loop_closures: bool = False,
+                                 loop_closure_threshold=None, max_outer: int = 50, inner_iters: int = 5, min_weight: float = 1e-6,
+                                 mu_step: float = 1.4, max_iters: int = 50, tol: float = 1e-10, engine: str = "native",
+                                 range_weights=None, loop_closure_weights=None, lib_path: Optional[str] = None,
+                                 solver_settings: Optional[dict] = None, max_group: int = 64, marginals=None):
+    """``refine_estimate_robust`` for many graphs at once.  ``inlier_threshold`` and ``loop_closure_threshold`` take a scalar or
+    a sequence with one entry per graph (``loop_closure_threshold`` None: the graph's ``inlier_threshold``); ``range_weights`` /
+    ``loop_closure_weights`` are lists with one entry per graph (prior weights as ``refine_estimate_robust`` takes them: floored
+    at ``min_weight`` in a re-weighted family, and the returned weights are prior x GNC).  The graphs are grouped by dimension,
+    in chunks of at most ``max_group``, as ``refine_estimate_batch`` groups them: each group is one device handle and one
+    ``score_refine_batch_robust_run`` (``engine="native"``) or one lock-step loop in Python with SciPy's sparse LU
+    (``engine="python"``).  Graphs without unknowns are answered on the host.  Returns ``[(refined SolverResults, info), ...]``
+    in input order, ``info`` as ``refine_estimate_robust`` builds it (``info["robust"]`` included) plus ``group``, ``rounds``
+    (lock-step rounds of the group) and ``stage_rounds`` (the passes in which some member of the group changed stage).
+
+    ``marginals``: True, or a list with one entry per graph as ``marginal_covariances_batch`` takes ``variables`` -- the group's
+    handle then keeps the final weights (``keep_weights=1``: precisions prec x w, the plain weight) and computes the marginal
+    covariances at the refined points before it is closed; ``info["marginals"]`` is the ``(cov, marginals_info)`` of
+    ``marginal_covariances_batch`` for that graph with the returned weights (None for a graph without unknowns).  Where a prior
+    weight lies below ``min_weight`` in a re-weighted family, the kept precisions carry the floor (prec x min_weight x w), not
+    the prior weight itself.  Errors about one graph are raised with ``graph i:`` in front."""
+    from .marginals import _select
+    from .marginals_batch import _variables_of, group_marginals
+
+    f_rng, f_rel = bool(robust_ranges), bool(robust_loop_closures)
+    datas, results = list(datas), list(results)
+    if len(datas) != len(results):
+        raise ValueError(f"one estimate per graph expected: {len(datas)} graphs, {len(results)} estimates")
+    if int(max_group) < 1:
+        raise ValueError("max_group must be at least 1")
+    N = len(datas)
+    cs = _per_graph(inlier_threshold, N, "inlier_threshold")
+    crs = _per_graph(loop_closure_threshold, N, "loop_closure_threshold")
+    cs = [float(c) for c in cs]
+    crs = [c if cr is None else float(cr) for c, cr in zip(cs, crs)]
+    linear_solver = "scipy" if engine == "python" else "device"
+    _check(1.0, 1.0, max_outer, inner_iters, min_weight, mu_step, engine, linear_solver, f_rng, f_rel)  # what every graph shares
+    for i in range(N):
+        try:
+            _check(cs[i], crs[i], max_outer, inner_iters, min_weight, mu_step, engine, linear_solver, f_rng, f_rel)
+        except ValueError as e:
+            raise ValueError(f"graph {i}: {e}") from None
+    families = (FAMILY_RANGES if f_rng else 0) | (FAMILY_LOOP_CLOSURES if f_rel else 0)
+    rws = _weights_of(range_weights, N, "range_weights")
+    lws = _weights_of(loop_closure_weights, N, "loop_closure_weights")
+    with_marginals = marginals is not None and marginals is not False
+    wanted = _variables_of(None if marginals is True else marginals, N) if with_marginals else None
+    common = dict(max_outer=int(max_outer), inner_iters=int(inner_iters), min_weight=float(min_weight), mu_step=float(mu_step),
+                  max_iters=int(max_iters), tol=float(tol), families=families)
+    out: list = [None] * N
+    groups: dict = {}
+    sel_of: dict = {}
+    for i, (data, res) in enumerate(zip(datas, results)):
+        if data.dimension not in (2, 3):
+            raise ValueError(f"graph {i}: dimension must be 2 or 3")
+        prob, point = _problem_of(data, res, _prior(rws[i], float(min_weight), f_rng), _prior(lws[i], float(min_weight), f_rel))
+        try:
+            _check_precisions(prob, f_rng, f_rel)
+        except ValueError as e:
+            raise ValueError(f"graph {i}: {e}") from None
+        if prob.n == 0:  # nothing to refine: the host's answer, as refine_estimate_robust gives it
+            out[i] = refine_estimate_robust(data, res, inlier_threshold=cs[i], robust_ranges=f_rng, robust_loop_closures=f_rel,
+                                            loop_closure_threshold=crs[i], max_outer=max_outer, inner_iters=inner_iters,
+                                            min_weight=min_weight, mu_step=mu_step, max_iters=max_iters, tol=tol, engine="python",
+                                            linear_solver="scipy", range_weights=rws[i], loop_closure_weights=lws[i])
+            if with_marginals:
+                out[i][1]["marginals"] = None
+            continue
+        if with_marginals:  # (the selection's errors before any work)
+            try:
+                sel_of[i] = _select(prob, wanted[i])
+            except ValueError as e:
+                raise ValueError(f"graph {i}: {e}") from None
+        groups.setdefault(data.dimension, []).append((i, prob, point))
+    number = 0
+    for dim in sorted(groups):
+        members = groups[dim]
+        for c0 in range(0, len(members), int(max_group)):
+            chunk = members[c0 : c0 + int(max_group)]
+            idx, probs, points = ([m[k] for m in chunk] for k in range(3))
+            sels, covs = [sel_of.get(i) for i in idx], None
+            if engine == "python":
+                settings = [dict(common, c=cs[i], c_rel=crs[i]) for i in idx]
+                pts, S, R, rounds, stage_rounds = _python_robust_lock_step(probs, points, settings)
+                per, infos, loops = [], [], []
+                for prob, pt, s, st in zip(probs, pts, S, R):
+                    per.append((st.w, range_residuals(prob, pt, st.prec0), st.wl, loop_closure_residuals(prob, pt, st.kappa0, st.tau0)))
+                    infos.append({"cost_initial": st.cost_initial, "cost_final": s.f, "iterations": st.lm, "grad_inf": s.gnorm,
+                                  "linear_solver": "scipy", "engine": "python", "pcg_iters": 0, "linear_solves": st.linear_solves})
+                    loops.append((st.k, st.mu, st.what == "converged"))
+                if with_marginals:
+                    for st in R:
+                        st.weigh(None)  # the kept precisions: prec w
+                    covs = group_marginals(None, probs, pts, sels, idx, number, engine="python")
+            else:
+                recs = []
+                for i in idx:
+                    rs = ScoreRefineRobustSettings()
+                    rs.inlier_threshold, rs.rel_threshold, rs.mu_step, rs.min_weight = cs[i], crs[i], float(mu_step), float(min_weight)
+                    rs.families, rs.max_outer, rs.inner_iters = families, int(max_outer), int(inner_iters)
+                    rs.max_iters, rs.tol = int(max_iters), float(tol)
+                    recs.append(rs)
+                with RefineBatchHandle(probs, lib_path, solver_settings) as h:
+                    pts, per, raw = h.robust_run(points, recs, keep_weights=with_marginals)
+                    if with_marginals:
+                        covs = group_marginals(h, probs, pts, sels, idx, number)
+                    rounds, stage_rounds = h.robust_rounds()
+                infos = [{"cost_initial": r["cost_initial"], "cost_final": r["cost_final"], "iterations": r["lm_iterations"],
+                          "grad_inf": r["grad_inf"], "linear_solver": "device", "engine": "native", "pcg_iters": r["pcg_iters"],
+                          "linear_solves": r["linear_solves"], "setup_ms": r["setup_ms"], "solve_ms": r["solve_ms"]} for r in raw]
+                loops = [(r["outer_iterations"], r["mu"], bool(r["converged"])) for r in raw]
+            for k, (i, prob, pt, info, (w, r, wl, rl), (outer, mu, conv)) in enumerate(zip(idx, probs, pts, infos, per, loops)):
+                if rws[i] is not None:  # prior x GNC
+                    w = w * np.asarray(rws[i], dtype=np.float64)
+                if lws[i] is not None:
+                    wl = wl * np.asarray(lws[i], dtype=np.float64)
+                info["robust"] = _robust_info(w, r, outer, mu, conv, wl if f_rel else None, rl if f_rel else None)
+                info["group"], info["rounds"], info["stage_rounds"] = number, rounds, stage_rounds
+                if with_marginals:
+                    info["marginals"] = covs[k]
+                out[i] = (_as_results(prob, pt, results[i], info["cost_final"]), info)
+            number += 1
+    return out
+
+
+__all__ = ["refine_estimate_robust_batch", "REFINE_ROBUST_BATCH_SYMBOLS"]
