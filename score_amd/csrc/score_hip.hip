@@ -4052,6 +4052,7 @@ struct AbiEnv {
 #include "score_abi.hpp"
 
 #include "score_marginals.hpp"
+#include "score_spectrum.hpp"
 #include "score_gn_robust.hpp"
 
 // Local refinement after SCORE on the device (score_gn.hpp): state, blocks and gathers here, the damped
@@ -4068,6 +4069,7 @@ struct score_refine {
     int n_mblocks = 0, n_ublocks = 0, n_hblocks = 0, n_sblocks = 0;
     std::vector<double> part_host;
     score::MvWork mv;  // marginal covariances (score_marginals.hpp)
+    score::SpWork sp;  // lowest eigenpairs of H (score_spectrum.hpp)
     // robust refinement (score_gn_robust.hpp): the measured precisions beside rng_prec / rel_kappa / rel_tau (which hold a robust
     // run's weighted ones while it lasts), residuals, weights, per-block partials; they come with the first robust call
     DevBuf<double> rb_prec0, rb_kappa0, rb_tau0, rb_r_rng, rb_r_lc, rb_w_rng, rb_w_lc, rb_part;
@@ -4854,6 +4856,14 @@ int score_refine_marginals(score_refine* r, const double* poses, const double* l
         require(r && poses && (r->P.Nl == 0 || landmarks));
         AbiEnv::Scope scope(r->device, false);
         return score::mv_solve(*r, poses, landmarks, vars, n_vars, rel_tol, max_iters, block_width, joint, residuals, iters, info);
+    });
+}
+int score_refine_spectrum(score_refine* r, const double* poses, const double* landmarks, int32_t k, double rel_tol, int32_t max_iters,
+                          double shift_rel, double* values, double* vectors, double* residuals, score_spectrum_info* info) {
+    return abi_call([&] {
+        require(r && poses && (r->P.Nl == 0 || landmarks));
+        AbiEnv::Scope scope(r->device, false);
+        return score::sp_solve(*r, poses, landmarks, k, rel_tol, max_iters, shift_rel, values, vectors, residuals, info);
     });
 }
 void score_refine_robust_default_settings(score_refine_robust_settings* rs) {

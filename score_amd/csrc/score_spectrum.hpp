@@ -1,0 +1,443 @@
+// score_spectrum.hpp -- the lowest eigenpairs of the information matrix H = J'J at a point of a refinement handle
+// (include/score_spectrum.h): LOBPCG (Knyazev 2001) with a block of kSpBlock = 16 vectors on A = H + sigma I.
+//
+// What exists already and is used as it is: the per-measurement blocks and the gather of H on the linear-mode handle's
+// pattern (gather_h(sigma)), the chain factorisation (derive_rho_data), the application of M^-1 to 16 vectors in one launch
+// (launch_prec<PREC_INIT>, PrecArgs::n_vec = 16, depth join, no loop-closure correction -- set up exactly as mv_solve's
+// `precondition` in score_marginals.hpp) and the product over 16 vectors (k_mv_product<16>, all_columns = 1).  M is the chain
+// part of A -- tridiagonal pose blocks per chain, diagonal blocks of the landmarks -- and exists for a singular H because of
+// the shift.  New here: the Gram kernel, the combine kernel, and the small kernels around them (start block, residuals,
+// done words, max diag H).
+//
+// The six blocks X, W, P (S) and AX, AW, AP (AS) are n x 16 each, column c at c * n (the layout PrecArgs::vec_stride
+// expects).  One iteration:
+//   k_sp_residual   R_c = AX_c - theta_c X_c, per-workgroup partials of |R_c|^2
+//   k_sp_done       |R_c| re-reduced in a fixed order; done word of column c: |R_c| <= rel_tol * h_max (recomputed every
+//                   iteration: soft locking -- a done column stays in X and in the Rayleigh-Ritz basis, its W and P leave)
+//   launch_prec     W = M^-1 R, all 16 columns in one launch
+//   k_mv_product    AW = A W.  AX and AP are NOT products: they follow X and P through the combine step (the same linear
+//                   combination of AS that forms X and P from S), which saves two of three passes over the matrix; the
+//                   drift this recurrence accumulates is bounded by a true product A X whenever the first k columns
+//                   look done -- the iteration ends only on residuals of that product, and goes on with it otherwise
+//   k_sp_gram       S'AS and S'S (48 x 48 each) from ONE pass over the six blocks, per-workgroup partials;
+//   k_sp_gram_sum   the partials re-reduced in workgroup order.  No atomics anywhere: two calls give the same bits
+//   (host)          both matrices and the 16 norms in one read (37 KB); Rayleigh-Ritz in score_spectrum_rr.hpp
+//   k_sp_combine    X <- S C, P <- [W | P] C_wp (grid.y = 0) and AX <- (AS) C, AP <- [AW | AP] C_wp (grid.y = 1): six blocks
+//                   read, four written, C (48 x 16) broadcast from LDS
+// Every kernel of the iteration tests the done words first: a done column's W / P (and AW / AP) is neither read by the Gram
+// and combine kernels -- it enters both as zero -- nor needed (the chain kernel keeps writing it, as in score_marginals.hpp).
+//
+// The Gram kernel: plain FMAs over an LDS-staged row tile, not v_mfma_f64_16x16x4_f64.  The pass moves 96 doubles per row
+// and does 2 x 48 x 48 FMAs on them; at the headline n = 60 000 that is 46 MB and 0.28 GFMA -- the kernel is bound by the
+// read of the six blocks and by launch latency, not by arithmetic (the vector units do the FMAs in a few microseconds), so
+// the matrix cores would buy nothing, and the FMA form has a summation order that is plain to read: rows in order inside a
+// workgroup, workgroups in order in k_sp_gram_sum.  A tile is kSpRows = 32 rows of all 96 columns, staged column-major with a
+// leading dimension of 33 doubles: lanes load 32 consecutive rows of one column (256 contiguous bytes; a column starts at
+// c * n, which is 16-byte aligned only for even n, so the loads stay 8 bytes wide), and in the FMA loop the 16 lanes that
+// differ in their column triple are 3 * 33 = 99 doubles apart -- 198 banks, 6 modulo 64: sixteen distinct even banks, no
+// conflict; the other lanes of the wavefront read the same addresses (broadcast).  Thread (ti, tj) of the 16 x 16 workgroup
+// owns the 3 x 3 entries (3 ti + a, 3 tj + b) of both matrices: 18 accumulators, 9 LDS reads per row.  25 KB of LDS per
+// workgroup leaves six workgroups per CU.
+#pragma once
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <vector>
+
+#include "../../include/score_spectrum.h"
+#include "score_marginals.hpp"
+#include "score_spectrum_rr.hpp"
+
+namespace score {
+
+constexpr int kSpBlock = 16;                 // vectors iterated
+constexpr int kSpM = 3 * kSpBlock;           // columns of S = [X | W | P]
+constexpr int kSpRows = 32;                  // rows of a Gram tile
+constexpr int kSpLd = kSpRows + 1;           // its leading dimension in LDS
+constexpr int kSpGramWgs = 128;              // workgroups of the Gram pass at most (= partial matrices)
+constexpr int kSpGramOut = 2 * kSpM * kSpM;  // S'AS then S'S
+constexpr int kSpMinN = kSpM;                // below this S cannot have full rank
+
+struct SpTheta { double v[kSpBlock]; };
+
+struct SpArgs {
+    long long n;
+    double* S[3];            // X, W, P
+    double* AS[3];           // AX, AW, AP
+    double* R;               // residual block, the preconditioner's operand
+    int32_t* flags;          // [c] done word of column c, [kSpBlock] a zero (the chain kernel's done word)
+    int x_only;              // Gram / combine: W and P are not in use (orthonormalisation of the start block)
+    int has_p;               // P holds directions
+    double tol;              // rel_tol * h_max
+    double* res_part;        // [c * n_rblocks + block]
+    int n_rblocks;
+    double* gram_part;       // [workgroup][2][48][48]
+    int n_gram_wgs, n_row_tiles;
+    double* out;             // [2][48][48] S'AS, S'S; then the 16 residual norms
+    const double* coef;      // 48 x 16 row-major
+};
+
+// the directions of S in use, bit b * 16 + c for block b, column c
+__device__ __forceinline__ unsigned long long sp_active(const SpArgs& a) {
+    unsigned long long act = 0xFFFFull;
+    if (a.x_only) return act;
+#pragma unroll
+    for (int c = 0; c < kSpBlock; ++c)
+        if (a.flags[c] == 0) act |= (1ull << (kSpBlock + c)) | (a.has_p ? 1ull << (2 * kSpBlock + c) : 0ull);
+    return act;
+}
+
+// grid (row blocks, 16): the start block from a fixed integer hash of (unknown, column), in (-1, 1); the done words cleared
+__global__ __launch_bounds__(kMvThreads) void k_sp_start(SpArgs a) {
+    const int c = blockIdx.y;
+    const long long i = (long long)blockIdx.x * kMvThreads + threadIdx.x;
+    if (i < a.n) {
+        unsigned long long h = (unsigned long long)i * kSpBlock + (unsigned long long)c + 0x9E3779B97F4A7C15ull;
+        h = (h ^ (h >> 30)) * 0xBF58476D1CE4E5B9ull;
+        h = (h ^ (h >> 27)) * 0x94D049BB133111EBull;
+        h ^= h >> 31;
+        a.S[0][c * a.n + i] = (double)(h >> 11) * (2.0 / 9007199254740992.0) - 1.0;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        a.flags[c] = 0;
+        if (c == 0) a.flags[kSpBlock] = 0;
+    }
+}
+
+// per-workgroup maxima of the diagonal of the gathered matrix
+__global__ __launch_bounds__(kThreads) void k_sp_hmax(const double* __restrict__ val, const int32_t* __restrict__ is_diag, int64_t nnz,
+                                                      double* __restrict__ part) {
+    __shared__ double red[4];
+    const int64_t k = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    double v = 0.0;
+    if (k < nnz && is_diag[k]) v = val[k] == val[k] ? val[k] : INFINITY;  // (fmax would drop a NaN)
+    v = block_max(v, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = v;
+}
+
+// grid (row blocks, 16): R_c = AX_c - theta_c X_c, partials of |R_c|^2
+__global__ __launch_bounds__(kMvThreads) void k_sp_residual(SpArgs a, SpTheta th) {
+    __shared__ double red[4];
+    const int c = blockIdx.y;
+    const long long i = (long long)blockIdx.x * kMvThreads + threadIdx.x;
+    double d = 0.0;
+    if (i < a.n) {
+        const long long e = c * a.n + i;
+        d = a.AS[0][e] - th.v[c] * a.S[0][e];
+        a.R[e] = d;
+    }
+    const double s = block_sum(d * d, red);
+    if (threadIdx.x == 0) a.res_part[(size_t)c * (size_t)a.n_rblocks + blockIdx.x] = s;
+}
+
+// one workgroup: the norms in a fixed order, the done words
+__global__ __launch_bounds__(kThreads) void k_sp_done(SpArgs a) {
+    __shared__ double red[4];
+    for (int c = 0; c < kSpBlock; ++c) {
+        const double s = reduce_partials(a.res_part + (size_t)c * (size_t)a.n_rblocks, 0, a.n_rblocks, red);
+        if (threadIdx.x == 0) {
+            const double nrm = sqrt(s);
+            a.out[kSpGramOut + c] = nrm;
+            a.flags[c] = nrm <= a.tol ? 1 : 0;  // (a non-finite norm is not done)
+        }
+    }
+}
+
+// S'AS and S'S of the directions in use, per-workgroup partials (see the head of the file)
+__global__ __launch_bounds__(kMvThreads) void k_sp_gram(SpArgs a) {
+    __shared__ double s[kSpM * kSpLd], as[kSpM * kSpLd];
+    const int t = threadIdx.x, tj = t & 15, ti = t >> 4;
+    const unsigned long long act = sp_active(a);
+    double ga[3][3], gb[3][3];
+#pragma unroll
+    for (int x = 0; x < 3; ++x)
+#pragma unroll
+        for (int y = 0; y < 3; ++y) ga[x][y] = gb[x][y] = 0.0;
+    for (int tile = blockIdx.x; tile < a.n_row_tiles; tile += gridDim.x) {
+        const long long row0 = (long long)tile * kSpRows;
+        for (int e = t; e < 2 * kSpM * kSpRows; e += kMvThreads) {
+            const int col = e / kSpRows, rr = e % kSpRows, cc = col % kSpM;
+            const long long row = row0 + rr;
+            double v = 0.0;
+            if (row < a.n && (act >> cc & 1)) {
+                const double* src = col < kSpM ? a.S[cc / kSpBlock] : a.AS[cc / kSpBlock];
+                v = src[(cc % kSpBlock) * a.n + row];
+            }
+            (col < kSpM ? s : as)[cc * kSpLd + rr] = v;
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int rr = 0; rr < kSpRows; ++rr) {
+            double si[3], sj[3], aj[3];
+#pragma unroll
+            for (int x = 0; x < 3; ++x) {
+                si[x] = s[(3 * ti + x) * kSpLd + rr];
+                sj[x] = s[(3 * tj + x) * kSpLd + rr];
+                aj[x] = as[(3 * tj + x) * kSpLd + rr];
+            }
+#pragma unroll
+            for (int x = 0; x < 3; ++x)
+#pragma unroll
+                for (int y = 0; y < 3; ++y) {
+                    gb[x][y] += si[x] * sj[y];
+                    ga[x][y] += si[x] * aj[y];
+                }
+        }
+        __syncthreads();
+    }
+    double* part = a.gram_part + (size_t)blockIdx.x * (size_t)kSpGramOut;
+#pragma unroll
+    for (int x = 0; x < 3; ++x)
+#pragma unroll
+        for (int y = 0; y < 3; ++y) {
+            const int e = (3 * ti + x) * kSpM + 3 * tj + y;
+            part[e] = ga[x][y];
+            part[kSpM * kSpM + e] = gb[x][y];
+        }
+}
+
+// grid (kSpGramOut / 256): the partial matrices summed in workgroup order
+__global__ __launch_bounds__(kMvThreads) void k_sp_gram_sum(SpArgs a) {
+    const int e = blockIdx.x * kMvThreads + threadIdx.x;
+    if (e >= kSpGramOut) return;
+    double acc = 0.0;
+    for (int w = 0; w < a.n_gram_wgs; ++w) acc += a.gram_part[(size_t)w * (size_t)kSpGramOut + (size_t)e];
+    a.out[e] = acc;
+}
+
+// grid (row blocks, 2), one row per lane: y = 0: X <- S C, P <- [W | P] C_wp; y = 1: the same combination of AS into AX, AP.
+// A lane reads its row of all three blocks before it writes: in place.
+__global__ __launch_bounds__(kMvThreads) void k_sp_combine(SpArgs a) {
+    __shared__ double c[kSpM * kSpBlock];
+    for (int e = threadIdx.x; e < kSpM * kSpBlock; e += kMvThreads) c[e] = a.coef[e];
+    __syncthreads();
+    const unsigned long long act = sp_active(a);
+    const long long i = (long long)blockIdx.x * kMvThreads + threadIdx.x;
+    if (i >= a.n) return;
+    double* const* blk = blockIdx.y ? a.AS : a.S;
+    double x[kSpBlock], p[kSpBlock];
+#pragma unroll
+    for (int j = 0; j < kSpBlock; ++j) x[j] = p[j] = 0.0;
+    // (four loads in flight per lane; unrolled further the 32 sums no longer fit the registers of a 256-lane workgroup)
+#pragma unroll 4
+    for (int cc = 0; cc < kSpBlock; ++cc) {
+        const double v = blk[0][cc * a.n + i];
+#pragma unroll
+        for (int j = 0; j < kSpBlock; ++j) x[j] += v * c[cc * kSpBlock + j];
+    }
+#pragma unroll 1
+    for (int b = 1; b < 3; ++b)
+#pragma unroll 4
+        for (int cc = 0; cc < kSpBlock; ++cc) {
+            if (!(act >> (b * kSpBlock + cc) & 1)) continue;
+            const double v = blk[b][cc * a.n + i];
+#pragma unroll
+            for (int j = 0; j < kSpBlock; ++j) p[j] += v * c[(b * kSpBlock + cc) * kSpBlock + j];
+        }
+#pragma unroll
+    for (int j = 0; j < kSpBlock; ++j) {
+        blk[0][j * a.n + i] = x[j] + p[j];
+        blk[2][j * a.n + i] = p[j];
+    }
+}
+
+// The solver's buffers: they stay with the refinement handle between calls (device allocations of their own, as MvWork's).
+struct SpWork {
+    DevBuf<double> x, w, p, ax, aw, ap, r, p_scratch, pw_part, rz, zb, res_part, gram_part, out, coef, hmax_part;
+    DevBuf<int32_t> flags;
+    DevBuf<int4> tiles;
+    int n_tiles = 0, n_rblocks = 0, n_row_tiles = 0, n_gram_wgs = 0, n_hblocks = 0;
+    void reserve(const GnProblem& P, int n_prec, int zb_per_vector, int hblocks, hipStream_t st) {
+        if (x.d) return;
+        struct NoArena {
+            DevArena* keep;
+            NoArena() : keep(tl_arena) { tl_arena = nullptr; }
+            ~NoArena() { tl_arena = keep; }
+        } no_arena;
+        std::vector<int4> t;
+        mv_tiles(P.hptr, P.n, t);
+        n_tiles = (int)t.size();
+        tiles.alloc(t.size());
+        staged_h2d(tiles.d, t.data(), t.size() * sizeof(int4), st);
+        const size_t nv = (size_t)kSpBlock, n = (size_t)P.n;
+        n_rblocks = (int)((n + kMvThreads - 1) / kMvThreads);
+        n_row_tiles = (int)((n + kSpRows - 1) / kSpRows);
+        n_gram_wgs = std::min(n_row_tiles, kSpGramWgs);
+        n_hblocks = hblocks;
+        DevBuf<double>* vecs[] = {&x, &w, &p, &ax, &aw, &ap, &r, &p_scratch};
+        for (DevBuf<double>* v : vecs) { v->alloc(nv * n); v->zero(st); }
+        pw_part.alloc(nv * (size_t)n_tiles); pw_part.zero(st);
+        rz.alloc(nv * (size_t)n_prec + 4096); rz.zero(st);  // (every workgroup of a chain-kernel launch has a slot, per vector)
+        zb.alloc(nv * (size_t)std::max(1, zb_per_vector)); zb.zero(st);
+        res_part.alloc(nv * (size_t)n_rblocks); res_part.zero(st);
+        gram_part.alloc((size_t)n_gram_wgs * (size_t)kSpGramOut); gram_part.zero(st);
+        out.alloc((size_t)kSpGramOut + nv); out.zero(st);
+        coef.alloc((size_t)kSpM * nv); coef.zero(st);
+        hmax_part.alloc((size_t)std::max(1, hblocks)); hmax_part.zero(st);
+        flags.alloc(nv + 1); flags.zero(st);
+    }
+};
+
+// The solve.  Refine: score_refine (its point, blocks and gather, its linear-mode handle, its SpWork `sp`).
+template <class Refine>
+int sp_solve(Refine& R, const double* poses, const double* landmarks, int32_t k, double rel_tol, int32_t max_iters, double shift_rel,
+             double* values, double* vectors, double* residuals, score_spectrum_info* info) {
+    const GnProblem& P = R.P;
+    if (k < 1 || k > kSpBlock) throw std::runtime_error("score_refine_spectrum: k must be 1..16");
+    if (!(rel_tol > 0.0) || !std::isfinite(rel_tol) || max_iters < 1)
+        throw std::runtime_error("score_refine_spectrum: rel_tol must be positive and max_iters >= 1");
+    if (!(shift_rel > 0.0) || !std::isfinite(shift_rel)) throw std::runtime_error("score_refine_spectrum: shift_rel must be positive");
+    HipBackend& be = R.be();
+    hipStream_t st = R.stream();
+    const long long n = P.n;
+    if (be.split.active) throw std::runtime_error("score_refine_spectrum: the block needs the unsplit chain kernel (chain_split = 0)");
+    if (be.n_prec == 0) throw std::runtime_error("score_refine_spectrum: the handle has no preconditioner work (no unknowns?)");
+    if (n < kSpMinN)
+        throw std::runtime_error("score_refine_spectrum: fewer than 48 unknowns -- use the dense solver (engine=\"python\") for a graph this small");
+    const double t0 = now_ms();
+    auto& W = R.sp;
+    W.reserve(P, be.n_prec, be.H->bs * be.n_join_seps, R.n_hblocks, st);
+    // the point, the blocks, max diag H; then A = H + sigma I on the handle's pattern and its chain factors
+    R.set_point(poses, landmarks);
+    (void)R.eval_at(R.u.d, true);
+    R.gather_h(0.0);
+    hipLaunchKernelGGL(k_sp_hmax, dim3((unsigned)W.n_hblocks), dim3(kThreads), 0, st, (const double*)be.K0d.d, (const int32_t*)R.is_diag.d,
+                       (int64_t)P.hcol.size(), W.hmax_part.d);
+    HIP_CHECK(hipGetLastError());
+    std::vector<double> hpart((size_t)W.n_hblocks);
+    staged_d2h(hpart.data(), W.hmax_part.d, hpart.size() * sizeof(double), st);
+    double h_max = 0.0;
+    for (double v : hpart) h_max = std::max(h_max, v);
+    if (!(h_max > 0.0) || !std::isfinite(h_max)) throw std::runtime_error("score_refine_spectrum: the diagonal of H is zero or not finite at this point");
+    const double sigma = shift_rel * h_max, tol = rel_tol * h_max;
+    R.gather_h(sigma);
+    be.derive_rho_data(false);
+
+    SpArgs a{};
+    a.n = n;
+    a.S[0] = W.x.d; a.S[1] = W.w.d; a.S[2] = W.p.d;
+    a.AS[0] = W.ax.d; a.AS[1] = W.aw.d; a.AS[2] = W.ap.d;
+    a.R = W.r.d; a.flags = W.flags.d; a.tol = tol;
+    a.res_part = W.res_part.d; a.n_rblocks = W.n_rblocks;
+    a.gram_part = W.gram_part.d; a.n_gram_wgs = W.n_gram_wgs; a.n_row_tiles = W.n_row_tiles;
+    a.out = W.out.d; a.coef = W.coef.d;
+    MvArgs m{};
+    m.ptr = be.Kset.mat.ptr.d; m.col = be.Kset.mat.col.d; m.val = be.Kset.mat.val.d;
+    m.tiles = W.tiles.d; m.n_tiles = W.n_tiles; m.n = n; m.flags = W.flags.d; m.all_columns = 1; m.pw_part = W.pw_part.d;
+    auto product = [&](const double* in, double* out) {
+        m.p_in = in; m.w = out;
+        hipLaunchKernelGGL(k_mv_product<kSpBlock>, dim3((unsigned)W.n_tiles), dim3(kMvThreads), 0, st, m);
+    };
+    auto precondition = [&]() {  // W = M^-1 R, as mv_solve's
+        PrecArgs pa = be.prec_args(be.Kset);
+        pa.done = W.flags.d + kSpBlock;
+        be.prec_vectors(pa, W.r.d, W.r.d, W.w.d, W.p_scratch.d, W.aw.d, W.p_scratch.d, W.p_scratch.d, nullptr);
+        pa.rz_in = nullptr; pa.rz_out = W.rz.d;
+        pa.n_vec = kSpBlock; pa.vec_stride = n;
+        be.join_vec_zb = W.zb.d;
+        be.launch_prec<PREC_INIT>(be.Kset, pa, -1, HipBackend::PrecDepth::join);
+        be.join_vec_zb = nullptr;
+    };
+    const dim3 g16((unsigned)W.n_rblocks, (unsigned)kSpBlock), g2((unsigned)W.n_rblocks, 2u), blk(kMvThreads);
+    auto gram = [&]() {
+        hipLaunchKernelGGL(k_sp_gram, dim3((unsigned)W.n_gram_wgs), blk, 0, st, a);
+        hipLaunchKernelGGL(k_sp_gram_sum, dim3((unsigned)((kSpGramOut + kMvThreads - 1) / kMvThreads)), blk, 0, st, a);
+    };
+    std::vector<double> host((size_t)kSpGramOut + kSpBlock), coef((size_t)kSpM * kSpBlock);
+    SpTheta th{};
+    double* norms = host.data() + kSpGramOut;
+    int kept = 0;
+    auto ritz_and_combine = [&]() -> bool {  // false: breakdown
+        SpTheta next{};
+        const int status = sp_rayleigh_ritz(kSpM, kSpBlock, host.data(), host.data() + kSpM * kSpM, next.v, coef.data(), &kept);
+        if (status == kSpRrBreakdown) return false;  // (X and its values stay as they are)
+        th = next;
+        staged_h2d(W.coef.d, coef.data(), coef.size() * sizeof(double), st);
+        hipLaunchKernelGGL(k_sp_combine, g2, blk, 0, st, a);
+        return true;
+    };
+    auto residual = [&]() {
+        hipLaunchKernelGGL(k_sp_residual, g16, blk, 0, st, a, th);
+        hipLaunchKernelGGL(k_sp_done, dim3(1), dim3(kThreads), 0, st, a);
+    };
+    auto first_k_done = [&]() {
+        for (int c = 0; c < k; ++c)
+            if (!(norms[c] <= tol)) return false;
+        return true;
+    };
+    const double t1 = now_ms();
+    // the start block, orthonormalised by the Gram and combine kernels with W and P out of use
+    hipLaunchKernelGGL(k_sp_start, g16, blk, 0, st, a);
+    product(W.x.d, W.ax.d);
+    a.x_only = 1; a.has_p = 0;
+    gram();
+    HIP_CHECK(hipGetLastError());
+    staged_d2h(host.data(), W.out.d, (size_t)kSpGramOut * sizeof(double), st);
+    bool broke = !ritz_and_combine();
+    a.x_only = 0;
+    int iterations = 0;
+    bool final_ready = false;
+    while (!broke && iterations < max_iters) {
+        residual();
+        precondition();
+        product(W.w.d, W.aw.d);
+        gram();
+        HIP_CHECK(hipGetLastError());
+        staged_d2h(host.data(), W.out.d, host.size() * sizeof(double), st);  // the one read of the iteration
+        if (first_k_done()) {  // ... by the recurrence's AX: look again with the product
+            product(W.x.d, W.ax.d);
+            residual();
+            HIP_CHECK(hipGetLastError());
+            staged_d2h(norms, W.out.d + kSpGramOut, (size_t)kSpBlock * sizeof(double), st);
+            if (first_k_done()) { final_ready = true; break; }
+            continue;  // AX is exact again; the next pass has columns to work on
+        }
+        if (!ritz_and_combine()) { broke = true; break; }
+        a.has_p = 1;
+        ++iterations;
+    }
+    if (!final_ready) {
+        product(W.x.d, W.ax.d);
+        residual();
+        HIP_CHECK(hipGetLastError());
+        staged_d2h(norms, W.out.d + kSpGramOut, (size_t)kSpBlock * sizeof(double), st);
+    }
+    // ascending; unit 2-norm on the way out (X is orthonormal to the rounding of the combine step)
+    std::vector<int> order((size_t)k);
+    for (int c = 0; c < k; ++c) order[(size_t)c] = c;
+    std::stable_sort(order.begin(), order.end(), [&](int p, int q) { return th.v[p] < th.v[q]; });
+    std::vector<double> X;
+    if (vectors) {
+        X.resize((size_t)k * (size_t)n);
+        staged_d2h(X.data(), W.x.d, X.size() * sizeof(double), st);
+    }
+    HIP_CHECK(sync_stream(st));
+    int unconverged = 0;
+    double worst = 0.0;
+    for (int j = 0; j < k; ++j) {
+        const int c = order[(size_t)j];
+        const double rho = norms[c];
+        if (!(rho <= tol)) ++unconverged;
+        worst = std::isfinite(rho) ? std::max(worst, rho) : INFINITY;
+        if (values) values[j] = th.v[c] - sigma;
+        if (residuals) residuals[j] = rho;
+        if (vectors) {
+            const double* src = X.data() + (size_t)c * (size_t)n;
+            double* dst = vectors + (size_t)j * (size_t)n;
+            long double s = 0.0L;
+            for (long long i = 0; i < n; ++i) s += (long double)src[i] * (long double)src[i];
+            const double inv = s > 0.0L && std::isfinite((double)s) ? (double)(1.0L / sqrtl(s)) : 1.0;
+            for (long long i = 0; i < n; ++i) dst[i] = src[i] * inv;
+        }
+    }
+    const double t2 = now_ms();
+    if (info) {
+        info->modes = k; info->block = kSpBlock; info->iterations = iterations; info->unconverged = unconverged;
+        info->h_max = h_max; info->shift = sigma; info->max_residual = worst;
+        info->setup_ms = t1 - t0; info->solve_ms = t2 - t1;
+    }
+    return unconverged ? 1 : 0;
+}
+
+}  // namespace score
