@@ -422,14 +422,15 @@ __global__ __launch_bounds__(256) void k_link_cap(LinkArgs a) {
             int idx = wi[0];
             for (int w = 1; w < NT / 64; ++w)
                 if (wv[w] > v || (wv[w] == v && wi[w] < idx)) { v = wv[w]; idx = wi[w]; }
-            if (!(v > 1e-300)) bad = 1;
-            piv_of[k] = idx; used[idx] = 1;
+            // (a non-finite column wins no comparison and leaves idx at its start value: marked bad before idx indexes anything)
+            if (!(v > 1e-300) || idx >= n) bad = 1;
+            else { piv_of[k] = idx; used[idx] = 1; }
         }
         sync();
         if (bad) break;  // (uniform)
         const int pr = piv_of[k];
-        const double inv = 1.0 / S[pr * n + k];
-        for (int i = t; i < n; i += NT) fcol[i] = (i == pr) ? 0.0 : S[i * n + k] * inv;
+        const double piv = S[pr * n + k];
+        for (int i = t; i < n; i += NT) fcol[i] = (i == pr) ? 0.0 : S[i * n + k] / piv;
         sync();
         // every other row: row_i -= (S[i][k] / pivot) * row_pr; a lane owns columns of [S | G] and walks down the rows eight at a
         // time (every read requested before the first write)
@@ -446,9 +447,12 @@ __global__ __launch_bounds__(256) void k_link_cap(LinkArgs a) {
                         const int i = min(i0 + q, n - 1);
                         mv[q] = M[i * n + cc]; fv[q] = fcol[i];
                     }
+                    // (fcol[pr] = 0: the pivot row stays.  Column k itself becomes exactly 0 off the pivot row, as in any elimination:
+                    //  S[i][k] - fcol[i] S[pr][k] leaves eps |S[i][k]|, which the read-out below takes for zero -- against pivots of
+                    //  1e-4 that cost three digits of t on a graph with weakly determined robots)
 #pragma unroll
                     for (int q = 0; q < kRows; ++q)
-                        if (i0 + q < n) M[(i0 + q) * n + cc] = mv[q] - fv[q] * pv;  // (fcol[pr] = 0: the pivot row stays)
+                        if (i0 + q < n) M[(i0 + q) * n + cc] = (c == k && i0 + q != pr) ? 0.0 : mv[q] - fv[q] * pv;
                 }
             }
         }

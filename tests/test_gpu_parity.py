@@ -1018,23 +1018,16 @@ def test_newton_kernels_against_the_oracle(name, fixtures, hip_lib):
     assert Hh.nnz == int(head.sum()) and np.all(Hh.data == 1.0)
     # chain factorisation: z = M^-1 (-g) must solve the block-tridiagonal chain part T of the SAME H exactly,
     # and be the Jacobi quotient on the other columns
+    from operator_helpers import chain_nodes_of_ids, preconditioned_matrix
+
     z = sol.debug_get("polish_prec_of_negg")
-    chain = sol.debug_get("chain_id_of_col").astype(np.int64)
     bs = mdl.qp.block_size
-    coo = Hm.tocoo()
-    first = np.full(chain.max() + 2, n, dtype=np.int64)
-    np.minimum.at(first, chain[chain >= 0], np.nonzero(chain >= 0)[0])
-    node = np.where(chain >= 0, (np.arange(n) - first[np.maximum(chain, 0)]) // bs, -1)
-    keep = (chain[coo.row] >= 0) & (chain[coo.row] == chain[coo.col]) & (np.abs(node[coo.row] - node[coo.col]) <= 1)
+    chain, node = chain_nodes_of_ids(sol.debug_get("chain_id_of_col"), bs)
     # ... plus the loop-closure blocks (round 6, csrc/score_link.hpp: the Woodbury correction makes the preconditioner the exact
     # inverse of chains + the blocks between linked nodes; graph3d has one loop closure)
     pairs = sol.debug_get("link_pairs").astype(np.int64).reshape(-1, 2)
     assert len(pairs) == (3 if name == "graph3d" else 0)
-    for ca, cb in pairs:
-        ra, rb = (coo.row >= ca) & (coo.row < ca + bs), (coo.row >= cb) & (coo.row < cb + bs)
-        keep |= (ra & (coo.col >= cb) & (coo.col < cb + bs)) | (rb & (coo.col >= ca) & (coo.col < ca + bs))
-    T = sp.csr_matrix((coo.data[keep], (coo.row[keep], coo.col[keep])), shape=(n, n))
-    inchain = chain >= 0
+    T, inchain = preconditioned_matrix(Hm, chain, node, bs, pairs)
     resid = (T @ z + g)[inchain]
     assert np.abs(resid).max() <= 1e-9 * max(1.0, np.abs(g).max()), np.abs(resid).max()
     other = ~inchain
