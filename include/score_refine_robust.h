@@ -12,7 +12,7 @@
  *   loop closure  r = sqrt( kappa |t_j - t_i - R_i t~|^2 + tau |R_j - R_i R~|_F^2 )
  *                 -- the square root of the relative-pose term of the refinement's cost (R = R(theta) in 2-D; pose 0 is where
  *                 the caller put it).  The loop closures are the trailing n_rel - sum(chain_len - 1) relative-pose entries.
- * Both are the square root of what the refinement's own block functions cost (csrc/score_gn.hpp: gn_range_resid, gn_rel_resid).
+ * Both are the square root of what the refinement's own block functions cost (csrc/score_gn.hpp: gn_robust_residual<DIM>).
  *
  * The loop (enabled families f: ranges c_f = inlier_threshold, loop closures c_f = rel_threshold):
  *   1. weights w = 1; solve 1 is the Levenberg-Marquardt loop exactly as score_refine_run runs it (max_iters, tol);

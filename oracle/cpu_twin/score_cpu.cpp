@@ -602,57 +602,21 @@ struct score_refine {
     std::vector<double> u, ut, step, hblk, gblk, rhs, vals;
     ~score_refine();
     void create(const score_graph& g, const score_settings* s);
-    double eval_at(const std::vector<double>& w, bool with_blocks) {
-        if (P.dim == 3) return eval_at3(w, with_blocks);
-        const double* uu = w.data();
+    template <int DIM>
+    double eval_at_dim(const std::vector<double>& w, bool with_blocks) {  // the cost sums in measurement order
+        const score::GnView v = P.view(w.data(), hblk.data(), gblk.data());
         double f = 0.0;
-        for (int64_t m = 0; m < P.n_rel(); ++m) {
-            double thi, xi, yi, thj, xj, yj;
-            score::gn_pose(uu, P.pin, P.rel_i[m], thi, xi, yi);
-            score::gn_pose(uu, P.pin, P.rel_j[m], thj, xj, yj);
-            f += score::gn_rel_block(thi, xi, yi, thj, xj, yj, &P.rel_t[2 * m], &P.rel_R[4 * m], P.rel_kappa[m], P.rel_tau[m],
-                                     with_blocks ? &hblk[36 * m] : nullptr, with_blocks ? &gblk[6 * m] : nullptr);
-        }
-        const int64_t hb = 36 * P.n_rel(), gb = 6 * P.n_rel();
-        for (int64_t r = 0; r < P.n_rng(); ++r) {
-            double xa, ya, xb, yb;
-            score::gn_point(uu, P.pin, P.Np, P.rng_a[r], xa, ya);
-            score::gn_point(uu, P.pin, P.Np, P.rng_b[r], xb, yb);
-            f += score::gn_range_block(xa, ya, xb, yb, P.rng_dist[r], P.rng_prec[r], with_blocks ? &hblk[hb + 16 * r] : nullptr,
-                                       with_blocks ? &gblk[gb + 4 * r] : nullptr);
-        }
-        const int64_t hp = hb + 16 * P.n_rng(), gp = gb + 4 * P.n_rng();
-        for (int64_t e = 0; e < P.n_pri(); ++e) {
-            const double* l = uu + 3 * (P.Np - 1) + 2 * (int64_t)P.pri_l[e];
-            f += score::gn_prior_block(l[0], l[1], &P.pri_t[2 * e], P.pri_prec[e], with_blocks ? &hblk[hp + 2 * e] : nullptr,
-                                       with_blocks ? &gblk[gp + 2 * e] : nullptr);
-        }
+        for (int64_t m = 0; m < P.n_meas(); ++m) f += score::gn_measurement<DIM>(v, m, with_blocks);
         return f;
     }
-    // 3-D: state X = [R | t] of every pose, then the landmarks (score_gn.hpp)
-    double eval_at3(const std::vector<double>& w, bool with_blocks) {
-        const double* X = w.data();
-        double f = 0.0;
-        for (int64_t m = 0; m < P.n_rel(); ++m)
-            f += score::gn_rel_block3(X + 12 * (int64_t)P.rel_i[m], X + 12 * (int64_t)P.rel_j[m], &P.rel_t[3 * m], &P.rel_R[9 * m],
-                                      P.rel_kappa[m], P.rel_tau[m], with_blocks ? &hblk[144 * m] : nullptr, with_blocks ? &gblk[12 * m] : nullptr);
-        const int64_t hb = 144 * P.n_rel(), gb = 12 * P.n_rel();
-        for (int64_t r = 0; r < P.n_rng(); ++r)
-            f += score::gn_range_block3(score::gn_point3(X, P.Np, P.rng_a[r]), score::gn_point3(X, P.Np, P.rng_b[r]), P.rng_dist[r],
-                                        P.rng_prec[r], with_blocks ? &hblk[hb + 36 * r] : nullptr, with_blocks ? &gblk[gb + 6 * r] : nullptr);
-        const int64_t hp = hb + 36 * P.n_rng(), gp = gb + 6 * P.n_rng();
-        for (int64_t e = 0; e < P.n_pri(); ++e)
-            f += score::gn_prior_block3(X + 12 * P.Np + 3 * (int64_t)P.pri_l[e], &P.pri_t[3 * e], P.pri_prec[e],
-                                        with_blocks ? &hblk[hp + 3 * e] : nullptr, with_blocks ? &gblk[gp + 3 * e] : nullptr);
-        return f;
+    double eval_at(const std::vector<double>& w, bool with_blocks) {
+        return P.dim == 2 ? eval_at_dim<2>(w, with_blocks) : eval_at_dim<3>(w, with_blocks);
     }
     double eval_current(bool with_blocks) { return eval_at(u, with_blocks); }
-    double eval_trial() {
-        if (P.dim == 2) {
-            for (int64_t i = 0; i < P.n; ++i) ut[i] = u[i] + step[i];
-        } else {  // retraction: R <- R Exp(omega), t <- t + v; landmarks additive
-            for (int64_t p = 0; p < P.Np; ++p) score::gn_pose3_retract(&u[12 * p], p > 0 ? &step[6 * (p - 1)] : nullptr, &ut[12 * p]);
-            for (int64_t l = 0; l < 3 * P.Nl; ++l) ut[12 * P.Np + l] = u[12 * P.Np + l] + step[6 * (P.Np - 1) + l];
+    double eval_trial() {  // 3-D poses by the retraction R <- R Exp(omega), t <- t + v; everything else additive
+        for (int64_t i = 0; i < P.Np + P.Nl; ++i) {
+            if (P.dim == 2) score::gn_retract_variable<2>(u.data(), step.data(), ut.data(), P.Np, P.Nl, i);
+            else score::gn_retract_variable<3>(u.data(), step.data(), ut.data(), P.Np, P.Nl, i);
         }
         return eval_at(ut, false);
     }
@@ -670,23 +634,13 @@ struct score_refine {
     bool solve(double lambda, double rel_tol, int* used);
     void run(const double* poses_in, const double* lms_in, int max_iters, double tol, double* poses_out, double* lms_out,
              score::GnInfo& info) {
-        if (P.dim == 3) {
-            std::copy(poses_in, poses_in + 12 * P.Np, u.begin());
-            if (P.Nl) std::copy(lms_in, lms_in + 3 * P.Nl, u.begin() + (std::ptrdiff_t)(12 * P.Np));
-            score::gn_levenberg_marquardt(*this, max_iters, tol, 1e-9, info);
-            std::copy(u.begin(), u.begin() + (std::ptrdiff_t)(12 * P.Np), poses_out);
-            if (P.Nl) std::copy(u.begin() + (std::ptrdiff_t)(12 * P.Np), u.begin() + (std::ptrdiff_t)(12 * P.Np + 3 * P.Nl), lms_out);
-            return;
-        }
-        for (int k = 0; k < 3; ++k) P.pin[k] = poses_in[k];
-        for (int64_t p = 1; p < P.Np; ++p)
-            for (int k = 0; k < 3; ++k) u[3 * (p - 1) + k] = poses_in[3 * p + k];
-        for (int64_t l = 0; l < 2 * P.Nl; ++l) u[3 * (P.Np - 1) + l] = lms_in[l];
+        // the state is the caller's layout: the poses (pose 0 included), then the landmarks
+        const std::ptrdiff_t np = (std::ptrdiff_t)(P.state_size() - P.dim * P.Nl);
+        std::copy(poses_in, poses_in + np, u.begin());
+        if (P.Nl) std::copy(lms_in, lms_in + P.dim * P.Nl, u.begin() + np);
         score::gn_levenberg_marquardt(*this, max_iters, tol, 1e-9, info);
-        for (int k = 0; k < 3; ++k) poses_out[k] = poses_in[k];
-        for (int64_t p = 1; p < P.Np; ++p)
-            for (int k = 0; k < 3; ++k) poses_out[3 * p + k] = u[3 * (p - 1) + k];
-        for (int64_t l = 0; l < 2 * P.Nl; ++l) lms_out[l] = u[3 * (P.Np - 1) + l];
+        std::copy(u.begin(), u.begin() + np, poses_out);
+        if (P.Nl) std::copy(u.begin() + np, u.end(), lms_out);
     }
 };
 

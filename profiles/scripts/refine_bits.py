@@ -1,0 +1,103 @@
+"""Every array and counter the four refinement entry points return on the tests' small fixtures, for a bit-for-bit comparison of
+two builds of the library (a refactor of the refinement kernels must not move one bit).
+
+  python profiles/scripts/refine_bits.py OUT.npz [--lib PATH]        record
+  python profiles/scripts/refine_bits.py --compare A.npz B.npz        compare two records with array_equal (NaNs equal); exit 1
+                                                                      if any entry differs or is missing
+
+Runs, each on a fresh handle: refine_estimate on the 2-D members A..E and the 3-D members of tests/refine_batch_helpers.py,
+refine_estimate_batch on the 2-D group and on the 3-D group, refine_estimate_robust (both families) on G1..G4 and the clean 3-D
+graph of tests/refine_robust_batch_helpers.py, refine_estimate_robust_batch on (G1, G2, G4) and on (G3, clean 3-D).  Recorded per
+run: poses and landmarks in the graph's order and every numeric entry of the info record, nested ones included (iteration
+counters, costs, gradient norm, mu, weights, residuals, outlier sets); timings (*_ms) are left out."""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def flatten(prefix, value, out):
+    if isinstance(value, dict):
+        for k, v in value.items():
+            if not str(k).endswith("_ms"):
+                flatten(f"{prefix}/{k}", v, out)
+    elif isinstance(value, (bool, int, float, np.integer, np.floating, np.bool_)):
+        out[prefix] = np.asarray(value)
+    elif isinstance(value, np.ndarray) and value.dtype.kind in "fiub":
+        out[prefix] = value
+    elif isinstance(value, (list, tuple)) and value and all(isinstance(v, (int, float, np.integer, np.floating)) for v in value):
+        out[prefix] = np.asarray(value)
+
+
+def record(lib):
+    from refine_batch_helpers import KEYS_2D, arrays_of, group, member
+    from refine_robust_batch_helpers import CLEAN3, SCHEDULE, THRESHOLD, graph
+    from score_amd.refine import refine_estimate
+    from score_amd.refine_batch import refine_estimate_batch
+    from score_amd.refine_robust import refine_estimate_robust
+    from score_amd.refine_robust_batch import refine_estimate_robust_batch
+
+    out = {}
+
+    def keep(name, fg, res, info):
+        poses, lms = arrays_of(fg, res)
+        out[f"{name}/poses"], out[f"{name}/landmarks"] = poses, lms
+        flatten(f"{name}/info", info, out)
+
+    for k in KEYS_2D + ("3D0", "3D1"):
+        fg, start = member(k)
+        keep(f"refine_estimate/{k}", fg, *refine_estimate(fg, start, engine="native", lib_path=lib))
+    for keys in (KEYS_2D, ("3D0", "3D1")):
+        fgs, starts = group(keys)
+        for k, fg, (res, info) in zip(keys, fgs, refine_estimate_batch(fgs, starts, lib_path=lib)):
+            keep(f"refine_estimate_batch/{'+'.join(keys)}/{k}", fg, res, info)
+    for k in ("G1", "G2", "G3", "G4", CLEAN3):
+        fg, start = graph(k)[:2]
+        keep(f"refine_estimate_robust/{k}", fg, *refine_estimate_robust(fg, start, inlier_threshold=THRESHOLD[k], robust_loop_closures=True,
+                                                                        engine="native", lib_path=lib, **SCHEDULE[k]))
+    for keys in (("G1", "G2", "G4"), ("G3", CLEAN3)):
+        fgs, starts = [graph(k)[0] for k in keys], [graph(k)[1] for k in keys]
+        got = refine_estimate_robust_batch(fgs, starts, inlier_threshold=[THRESHOLD[k] for k in keys], robust_loop_closures=True,
+                                           engine="native", lib_path=lib, **SCHEDULE[keys[0]])
+        for k, fg, (res, info) in zip(keys, fgs, got):
+            keep(f"refine_estimate_robust_batch/{'+'.join(keys)}/{k}", fg, res, info)
+    return out
+
+
+def compare(path_a, path_b):
+    a, b = np.load(path_a), np.load(path_b)
+    bad = sorted(set(a.files) ^ set(b.files))
+    for k in bad:
+        print("only in one record:", k)
+    for k in sorted(set(a.files) & set(b.files)):
+        if not (a[k].shape == b[k].shape and np.array_equal(a[k], b[k], equal_nan=a[k].dtype.kind == "f")):
+            worst = float(np.max(np.abs(a[k].astype(float) - b[k].astype(float)))) if a[k].shape == b[k].shape and a[k].size else float("nan")
+            print("differs:", k, a[k].shape, b[k].shape, "worst difference", worst)
+            bad.append(k)
+    print(f"{len(a.files)} entries in {path_a}, {len(b.files)} in {path_b}: {len(bad)} differ or are missing")
+    return 1 if bad else 0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("paths", nargs="+")
+    ap.add_argument("--lib", default=None)
+    ap.add_argument("--compare", action="store_true")
+    args = ap.parse_args()
+    if args.compare:
+        if len(args.paths) != 2:
+            ap.error("--compare takes two records")
+        sys.exit(compare(*args.paths))
+    out = record(args.lib)
+    os.makedirs(os.path.dirname(os.path.abspath(args.paths[0])), exist_ok=True)
+    np.savez(args.paths[0], **out)
+    print(len(out), "entries ->", args.paths[0])
+
+
+if __name__ == "__main__":
+    main()

@@ -18,9 +18,11 @@
 //     + sum_rng  w (|p_a - p_b| - d)^2  +  sum_prior  w |l - l0|^2
 //
 // Unknowns u = [th_p, x_p, y_p for poses p = 1.. | landmarks (x, y)]; pose 0 (first pose of chain 0) is
-// held where SCORE put it.  Per measurement a small dense block J_e'J_e and gradient J_e'r_e is
-// computed (one lane / loop iteration each: `gn_rel_block`, `gn_range_block`, `gn_prior_block`, compiled
-// for both sides), every entry of H = J'J and g = J'r then sums its contributions in a fixed order
+// held where SCORE put it.  The state holds every pose, pose 0 included ([theta, x, y] per pose, then the
+// landmarks; 3-D below): pose 0 has no unknowns, so it never receives a step.  Per measurement a small dense
+// block J_e'J_e and gradient J_e'r_e is computed (one lane / loop iteration each: `gn_measurement` over
+// `gn_rel_block`, `gn_range_block`, `gn_prior_block`, compiled for both sides and for the single handle and
+// the group alike), every entry of H = J'J and g = J'r then sums its contributions in a fixed order
 // (contribution lists built once on the host) -- no atomics, same sums on both backends.  The damped
 // normal equations go through the handle's linear mode (score_linear_solve's core: k_factor on the pose
 // chains, k_prec_pre + k_spmv PCG).  The LM loop (`gn_levenberg_marquardt`) mirrors
@@ -44,17 +46,9 @@
 
 namespace score {
 
-// pose p of the state: (theta, x, y); pose 0 is the pin
-SCORE_GN_HD void gn_pose(const double* u, const double* pin, int64_t p, double& th, double& x, double& y) {
-    if (p == 0) { th = pin[0]; x = pin[1]; y = pin[2]; return; }
-    const double* q = u + 3 * (p - 1);
-    th = q[0]; x = q[1]; y = q[2];
-}
-// point of a range endpoint (variable id: pose or landmark)
-SCORE_GN_HD void gn_point(const double* u, const double* pin, int64_t Np, int64_t v, double& x, double& y) {
-    if (v < Np) { double th; gn_pose(u, pin, v, th, x, y); return; }
-    const double* q = u + 3 * (Np - 1) + 2 * (v - Np);
-    x = q[0]; y = q[1];
+// point of a range endpoint (variable id: pose or landmark) in the 2-D state: [theta, x, y] of every pose, then the landmarks
+SCORE_GN_HD const double* gn_point2(const double* X, int64_t Np, int64_t v) {
+    return v < Np ? X + 3 * v + 1 : X + 3 * Np + 2 * (v - Np);
 }
 
 // relative-pose measurement i -> j.  Local unknowns [th_i, x_i, y_i, th_j, x_j, y_j].
@@ -264,22 +258,142 @@ SCORE_GN_HD double gn_prior_block3(const double* l, const double* t0, double pre
     return c;
 }
 
-// Per-measurement residuals of the robust refinement (include/score_refine_robust.h): r = sqrt(the measurement's own cost
-// term) -- the block functions above without H / g, so a cost term is stated once.  The caller passes the MEASURED precisions.
-//   range:          sqrt(prec) | |p_a - p_b| - dist |
-//   relative pose:  sqrt(kappa |t_j - t_i - R_i t~|^2 + tau |R_j - R_i R~|_F^2)
-SCORE_GN_HD double gn_range_resid(double xa, double ya, double xb, double yb, double dist, double prec) {
-    return sqrt(gn_range_block(xa, ya, xb, yb, dist, prec, nullptr, nullptr));
+// ---------------------------------------------------------------------------
+// One graph as a lane sees it, and what a lane does with one measurement / one variable of it: stated here once, compiled
+// into the single handle's kernels (score_gn_kernels.hpp, score_gn_robust.hpp), the group's (score_gn_batch.hpp,
+// score_gn_robust_batch.hpp: a workgroup's view is its member's) and the CPU twin's loops.
+// ---------------------------------------------------------------------------
+struct GnView {
+    int64_t Np, Nl, n_rel, n_rng, n_pri;
+    const int32_t *rel_i, *rel_j, *rng_a, *rng_b, *pri_l;   // the measurement arrays, from this graph's first entry
+    const double *rel_t, *rel_R, *rel_kappa, *rel_tau, *rng_dist, *rng_prec, *pri_t, *pri_prec;
+    const double* X;       // its state: every pose (2-D [theta, x, y], 3-D [R | t]), then the landmarks
+    double *hblk, *gblk;   // its block storage: relative-pose blocks, then range blocks, then prior blocks
+};
+
+// relative-pose entry m at the view's point with the precisions given: cost, with H / g also J'J and J'r
+template <int DIM>
+SCORE_GN_HD double gn_rel_at(const GnView& v, int64_t m, double kappa, double tau, double* H, double* g) {
+    constexpr int PS = DIM == 2 ? 3 : 12;
+    const double* pi = v.X + PS * (int64_t)v.rel_i[m];
+    const double* pj = v.X + PS * (int64_t)v.rel_j[m];
+    if (DIM == 2) return gn_rel_block(pi[0], pi[1], pi[2], pj[0], pj[1], pj[2], v.rel_t + 2 * m, v.rel_R + 4 * m, kappa, tau, H, g);
+    return gn_rel_block3(pi, pj, v.rel_t + 3 * m, v.rel_R + 9 * m, kappa, tau, H, g);
 }
-SCORE_GN_HD double gn_rel_resid(double thi, double xi, double yi, double thj, double xj, double yj, const double* tm, const double* Rm,
-                                double kappa, double tau) {
-    return sqrt(gn_rel_block(thi, xi, yi, thj, xj, yj, tm, Rm, kappa, tau, nullptr, nullptr));
+// range r at the view's point with the precision given
+template <int DIM>
+SCORE_GN_HD double gn_range_at(const GnView& v, int64_t r, double prec, double* H, double* g) {
+    if (DIM == 2) {
+        const double* pa = gn_point2(v.X, v.Np, v.rng_a[r]);
+        const double* pb = gn_point2(v.X, v.Np, v.rng_b[r]);
+        return gn_range_block(pa[0], pa[1], pb[0], pb[1], v.rng_dist[r], prec, H, g);
+    }
+    const double* pa = gn_point3(v.X, v.Np, v.rng_a[r]);
+    const double* pb = gn_point3(v.X, v.Np, v.rng_b[r]);
+    const double a3[3] = {pa[0], pa[1], pa[2]}, b3[3] = {pb[0], pb[1], pb[2]};
+    return gn_range_block3(a3, b3, v.rng_dist[r], prec, H, g);
 }
-SCORE_GN_HD double gn_range_resid3(const double* pa, const double* pb, double dist, double prec) {
-    return sqrt(gn_range_block3(pa, pb, dist, prec, nullptr, nullptr));
+
+template <int N>
+SCORE_GN_HD void gn_store(double* dst, const double* src) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) dst[k] = src[k];
 }
-SCORE_GN_HD double gn_rel_resid3(const double* Xi, const double* Xj, const double* tm, const double* Rm, double kappa, double tau) {
-    return sqrt(gn_rel_block3(Xi, Xj, tm, Rm, kappa, tau, nullptr, nullptr));
+
+// measurement m of the view (relative poses, then ranges, then landmark priors; beyond them: nothing): its cost and,
+// with_blocks, its J'J / J'r block into the view's storage (2-D 36 + 6 / 16 + 4 / 2 + 2 scalars, 3-D 144 + 12 / 36 + 6 / 3 + 3)
+template <int DIM>
+SCORE_GN_HD double gn_measurement(const GnView& v, int64_t m, bool with_blocks) {
+    constexpr int PS = DIM == 2 ? 3 : 12, NR = DIM == 2 ? 6 : 12, NG = 2 * DIM;
+    double cost = 0.0;
+    if (m < v.n_rel) {
+        double H[NR * NR], g[NR];
+        cost = gn_rel_at<DIM>(v, m, v.rel_kappa[m], v.rel_tau[m], with_blocks ? H : nullptr, g);
+        if (with_blocks) {
+            double* ho = v.hblk + NR * NR * m;
+            for (int k = 0; k < NR * NR; ++k) ho[k] = H[k];
+            gn_store<NR>(v.gblk + NR * m, g);
+        }
+    } else if (m < v.n_rel + v.n_rng) {
+        const int64_t r = m - v.n_rel;
+        double H[NG * NG], g[NG];
+        cost = gn_range_at<DIM>(v, r, v.rng_prec[r], with_blocks ? H : nullptr, g);
+        if (with_blocks) {
+            gn_store<NG * NG>(v.hblk + NR * NR * v.n_rel + NG * NG * r, H);
+            gn_store<NG>(v.gblk + NR * v.n_rel + NG * r, g);
+        }
+    } else if (m < v.n_rel + v.n_rng + v.n_pri) {
+        const int64_t e = m - v.n_rel - v.n_rng;
+        const double* l = v.X + PS * v.Np + DIM * (int64_t)v.pri_l[e];
+        double H[DIM], g[DIM];
+        if (DIM == 2) {
+            cost = gn_prior_block(l[0], l[1], v.pri_t + 2 * e, v.pri_prec[e], with_blocks ? H : nullptr, g);
+        } else {
+            const double l3[3] = {l[0], l[1], l[2]};
+            cost = gn_prior_block3(l3, v.pri_t + 3 * e, v.pri_prec[e], with_blocks ? H : nullptr, g);
+        }
+        if (with_blocks) {
+            gn_store<DIM>(v.hblk + NR * NR * v.n_rel + NG * NG * v.n_rng + DIM * e, H);
+            gn_store<DIM>(v.gblk + NR * v.n_rel + NG * v.n_rng + DIM * e, g);
+        }
+    }
+    return cost;
+}
+
+// Residual of the robust refinement (include/score_refine_robust.h): r = sqrt(the measurement's own cost term) -- the block
+// functions without H / g -- with the MEASURED precisions, which the caller passes.
+//   kGnRobustRanges    range m:                sqrt(p0) | |p_a - p_b| - dist |
+//   kGnRobustClosures  relative-pose entry m:  sqrt(p0 |t_j - t_i - R_i t~|^2 + p1 |R_j - R_i R~|_F^2)   (p0 = kappa, p1 = tau)
+constexpr int kGnRobustRanges = 1, kGnRobustClosures = 2;   // the bits of `families`
+template <int DIM>
+SCORE_GN_HD double gn_robust_residual(const GnView& v, int family, int64_t m, double p0, double p1) {
+    return sqrt(family == kGnRobustRanges ? gn_range_at<DIM>(v, m, p0, nullptr, nullptr) : gn_rel_at<DIM>(v, m, p0, p1, nullptr, nullptr));
+}
+
+// variable i (pose or landmark) of a graph: dst = retract(src, step) -- a pose's step added (3-D: R Exp(omega), t + v), a
+// landmark's added; step: the graph's first unknown, pose p >= 1 owns [DP (p - 1), DP p), the landmarks follow.  The copy:
+// pose 0 (it has no unknowns), and every variable with step == nullptr.
+template <int DIM>
+SCORE_GN_HD void gn_retract_variable(const double* src, const double* step, double* dst, int64_t Np, int64_t Nl, int64_t i) {
+    constexpr int PS = DIM == 2 ? 3 : 12, DP = DIM == 2 ? 3 : 6;
+    if (i < Np) {
+        const double* in = src + PS * i;
+        double* out = dst + PS * i;
+        if (!step || i == 0) {
+            gn_store<PS>(out, in);
+        } else if (DIM == 2) {
+            const double* st = step + DP * (i - 1);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) out[k] = in[k] + st[k];
+        } else {
+            double a[12], s6[6], o[12];
+            gn_store<12>(a, in);
+            gn_store<6>(s6, step + DP * (i - 1));
+            gn_pose3_retract(a, s6, o);
+            gn_store<12>(out, o);
+        }
+    } else if (i < Np + Nl) {
+        const int64_t l = i - Np;
+        const double* in = src + PS * Np + DIM * l;
+        double* out = dst + PS * Np + DIM * l;
+        const double* st = step ? step + DP * (Np - 1) + DIM * l : nullptr;
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) out[k] = st ? in[k] + st[k] : in[k];
+    }
+}
+
+// Not used in this tree any more.  The 2-D state used to hold the unknowns alone, u = [theta, x, y of poses 1.. | landmarks],
+// with pose 0 beside it in GnProblem::pin; these are that layout's accessors.  They and GnProblem::pin stay for one revision so
+// that the CPU twin's previous source still builds against this header, and go with the next change here.
+SCORE_GN_HD void gn_pose(const double* u, const double* pin, int64_t p, double& th, double& x, double& y) {
+    if (p == 0) { th = pin[0]; x = pin[1]; y = pin[2]; return; }
+    const double* q = u + 3 * (p - 1);
+    th = q[0]; x = q[1]; y = q[2];
+}
+SCORE_GN_HD void gn_point(const double* u, const double* pin, int64_t Np, int64_t v, double& x, double& y) {
+    if (v < Np) { double th; gn_pose(u, pin, v, th, x, y); return; }
+    const double* q = u + 3 * (Np - 1) + 2 * (v - Np);
+    x = q[0]; y = q[1];
 }
 
 // ---------------------------------------------------------------------------
@@ -291,11 +405,11 @@ struct GnProblem {
     int dp() const { return dim == 2 ? 3 : 6; }          // unknowns per pose
     int rel_nb() const { return 2 * dp(); }              // local unknowns of a relative-pose block
     int rng_nb() const { return 2 * dim; }
-    int64_t state_size() const { return dim == 2 ? n : 12 * Np + 3 * Nl; }  // 3-D: [R | t] of every pose, landmarks
+    int64_t state_size() const { return (dim == 2 ? 3 : 12) * Np + dim * Nl; }  // every pose (2-D [theta, x, y], 3-D [R | t]), landmarks
     std::vector<int32_t> chain_len;
     std::vector<int32_t> rel_i, rel_j, rng_a, rng_b, pri_l;
     std::vector<double> rel_t, rel_R, rel_kappa, rel_tau, rng_dist, rng_prec, pri_t, pri_prec;
-    double pin[3] = {0, 0, 0};
+    double pin[3] = {0, 0, 0};  // (not used any more: see gn_pose)
     int64_t n_rel() const { return (int64_t)rel_i.size(); }
     int64_t n_rng() const { return (int64_t)rng_a.size(); }
     int64_t n_pri() const { return (int64_t)pri_l.size(); }
@@ -307,6 +421,11 @@ struct GnProblem {
     std::vector<int32_t> hptr, hcol, hc_ptr, hc_slot, gc_ptr, gc_slot, diag_pos;
     std::vector<int32_t> chain_ptr, node_first_col;
 
+    GnView view(const double* X, double* hblk, double* gblk) const {  // the graph from host memory
+        return GnView{Np, Nl, n_rel(), n_rng(), n_pri(), rel_i.data(), rel_j.data(), rng_a.data(), rng_b.data(), pri_l.data(),
+                      rel_t.data(), rel_R.data(), rel_kappa.data(), rel_tau.data(), rng_dist.data(), rng_prec.data(), pri_t.data(),
+                      pri_prec.data(), X, hblk, gblk};
+    }
     int64_t pose_col(int64_t p) const { return p == 0 ? -1 : dp() * (p - 1); }
     // first column of the translation of a range endpoint (2-D: after theta; 3-D: after omega)
     int64_t point_col(int64_t v) const { return v < Np ? (v == 0 ? -1 : dp() * (v - 1) + (dp() - dim)) : dp() * (Np - 1) + dim * (v - Np); }

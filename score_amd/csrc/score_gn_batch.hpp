@@ -7,9 +7,10 @@
 // member's mask or done word first, and writes nothing for a member that is masked out or done.
 //
 // The state holds every pose, pins included: 2-D [theta, x, y] per pose then the landmarks, 3-D [R | t] per pose then the
-// landmarks, member after member.  The cost functions of score_gn.hpp are called as they stand, and a member's measurements
-// are laid over workgroups exactly as k_gn_blocks lays them (local measurement m in the member's workgroup m / kThreads), so
-// a member's cost partials are those of a handle on it alone.
+// landmarks, member after member -- the single handle's layout.  A workgroup builds its member's GnView (gb_view) and calls the
+// lane functions of score_gn.hpp that the single handle's kernels call, and a member's measurements are laid over workgroups
+// exactly as k_gn_blocks lays them (local measurement m in the member's workgroup m / kThreads), so a member's cost partials
+// are those of a handle on it alone.
 //
 // The conjugate-gradient iteration (modelled on score_marginals.hpp, with "column" replaced by "member"):
 //   k_gb_product    w = H p over the tiles of the live members (64 short rows x 4 lanes, or one long row over the workgroup),
@@ -271,7 +272,26 @@ struct GbDev {
     const double *rel_t, *rel_R, *rel_kappa, *rel_tau, *rng_dist, *rng_prec, *pri_t, *pri_prec;
 };
 
-// one measurement per lane (2-D): cost partial of the workgroup and, with_blocks, its J'J / J'r block
+// member M of the group as a lane sees it (GnView, score_gn.hpp): the union arrays from its first entry, its state in X, its
+// block storage in hblk / gblk (null: none)
+template <int DIM>
+__device__ __forceinline__ GnView gb_view(const GbDev& d, const GbMember& M, const double* X, double* hblk, double* gblk) {
+    GnView v;
+    v.Np = M.Np; v.Nl = M.Nl; v.n_rel = M.n_rel; v.n_rng = M.n_rng; v.n_pri = M.n_pri;
+    v.rel_i = d.rel_i + M.rel0; v.rel_j = d.rel_j + M.rel0; v.rng_a = d.rng_a + M.rng0; v.rng_b = d.rng_b + M.rng0;
+    v.pri_l = d.pri_l + M.pri0;
+    v.rel_t = d.rel_t + DIM * M.rel0; v.rel_R = d.rel_R + DIM * DIM * M.rel0;
+    v.rel_kappa = d.rel_kappa + M.rel0; v.rel_tau = d.rel_tau + M.rel0;
+    v.rng_dist = d.rng_dist + M.rng0; v.rng_prec = d.rng_prec + M.rng0;
+    v.pri_t = d.pri_t + DIM * M.pri0; v.pri_prec = d.pri_prec + M.pri0;
+    v.X = X + M.state0;
+    v.hblk = hblk ? hblk + M.hblk0 : nullptr; v.gblk = gblk ? gblk + M.gblk0 : nullptr;
+    return v;
+}
+
+// one measurement per lane (gn_measurement on the member's view): cost partial of the workgroup and, with_blocks, its
+// J'J / J'r block
+template <int DIM>
 __global__ __launch_bounds__(kThreads) void k_gb_blocks(GbDev d, const double* __restrict__ X, double* __restrict__ hblk,
                                                         double* __restrict__ gblk, double* __restrict__ cost_part,
                                                         const int32_t* __restrict__ mask, int with_blocks) {
@@ -279,149 +299,21 @@ __global__ __launch_bounds__(kThreads) void k_gb_blocks(GbDev d, const double* _
     const int g = d.mblk_member[blockIdx.x];
     if (!mask[g]) return;
     const GbMember M = d.members[g];
-    const double* Xg = X + M.state0;
     const long long m = (long long)((int)blockIdx.x - M.mblk0) * kThreads + threadIdx.x;
-    double cost = 0.0;
-    if (m < M.n_rel) {
-        const long long e = M.rel0 + m;
-        const double* pi = Xg + 3 * (long long)d.rel_i[e];
-        const double* pj = Xg + 3 * (long long)d.rel_j[e];
-        double H[36], gv[6];
-        cost = gn_rel_block(pi[0], pi[1], pi[2], pj[0], pj[1], pj[2], d.rel_t + 2 * e, d.rel_R + 4 * e, d.rel_kappa[e], d.rel_tau[e],
-                            with_blocks ? H : nullptr, gv);
-        if (with_blocks) {
-            double* ho = hblk + M.hblk0 + 36 * m;
-            double* go = gblk + M.gblk0 + 6 * m;
-#pragma unroll
-            for (int k = 0; k < 36; ++k) ho[k] = H[k];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) go[k] = gv[k];
-        }
-    } else if (m < M.n_rel + M.n_rng) {
-        const long long r = m - M.n_rel, e = M.rng0 + r;
-        const long long va = d.rng_a[e], vb = d.rng_b[e];
-        const double* pa = va < M.Np ? Xg + 3 * va + 1 : Xg + 3 * M.Np + 2 * (va - M.Np);
-        const double* pb = vb < M.Np ? Xg + 3 * vb + 1 : Xg + 3 * M.Np + 2 * (vb - M.Np);
-        double H[16], gv[4];
-        cost = gn_range_block(pa[0], pa[1], pb[0], pb[1], d.rng_dist[e], d.rng_prec[e], with_blocks ? H : nullptr, gv);
-        if (with_blocks) {
-            double* ho = hblk + M.hblk0 + 36 * M.n_rel + 16 * r;
-            double* go = gblk + M.gblk0 + 6 * M.n_rel + 4 * r;
-#pragma unroll
-            for (int k = 0; k < 16; ++k) ho[k] = H[k];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) go[k] = gv[k];
-        }
-    } else if (m < M.n_rel + M.n_rng + M.n_pri) {
-        const long long q = m - M.n_rel - M.n_rng, e = M.pri0 + q;
-        const double* l = Xg + 3 * M.Np + 2 * (long long)d.pri_l[e];
-        double H[2], gv[2];
-        cost = gn_prior_block(l[0], l[1], d.pri_t + 2 * e, d.pri_prec[e], with_blocks ? H : nullptr, gv);
-        if (with_blocks) {
-            double* ho = hblk + M.hblk0 + 36 * M.n_rel + 16 * M.n_rng + 2 * q;
-            double* go = gblk + M.gblk0 + 6 * M.n_rel + 4 * M.n_rng + 2 * q;
-            ho[0] = H[0]; ho[1] = H[1]; go[0] = gv[0]; go[1] = gv[1];
-        }
-    }
-    const double tot = block_sum(cost, red);
+    const double tot = block_sum(gn_measurement<DIM>(gb_view<DIM>(d, M, X, hblk, gblk), m, with_blocks != 0), red);
     if (threadIdx.x == 0) cost_part[blockIdx.x] = tot;
 }
 
-// 3-D: blocks 12 x 12 / 6 x 6 / 3
-__global__ __launch_bounds__(kThreads) void k_gb_blocks3(GbDev d, const double* __restrict__ X, double* __restrict__ hblk,
-                                                         double* __restrict__ gblk, double* __restrict__ cost_part,
-                                                         const int32_t* __restrict__ mask, int with_blocks) {
-    __shared__ double red[8];
-    const int g = d.mblk_member[blockIdx.x];
-    if (!mask[g]) return;
-    const GbMember M = d.members[g];
-    const double* Xg = X + M.state0;
-    const long long m = (long long)((int)blockIdx.x - M.mblk0) * kThreads + threadIdx.x;
-    double cost = 0.0;
-    if (m < M.n_rel) {
-        const long long e = M.rel0 + m;
-        double Xi[12], Xj[12], H[144], gv[12];
-        const double* pi = Xg + 12 * (long long)d.rel_i[e];
-        const double* pj = Xg + 12 * (long long)d.rel_j[e];
-#pragma unroll
-        for (int k = 0; k < 12; ++k) { Xi[k] = pi[k]; Xj[k] = pj[k]; }
-        cost = gn_rel_block3(Xi, Xj, d.rel_t + 3 * e, d.rel_R + 9 * e, d.rel_kappa[e], d.rel_tau[e], with_blocks ? H : nullptr, gv);
-        if (with_blocks) {
-            double* ho = hblk + M.hblk0 + 144 * m;
-            double* go = gblk + M.gblk0 + 12 * m;
-            for (int k = 0; k < 144; ++k) ho[k] = H[k];
-#pragma unroll
-            for (int k = 0; k < 12; ++k) go[k] = gv[k];
-        }
-    } else if (m < M.n_rel + M.n_rng) {
-        const long long r = m - M.n_rel, e = M.rng0 + r;
-        const double* pa = gn_point3(Xg, M.Np, d.rng_a[e]);
-        const double* pb = gn_point3(Xg, M.Np, d.rng_b[e]);
-        const double a3[3] = {pa[0], pa[1], pa[2]}, b3[3] = {pb[0], pb[1], pb[2]};
-        double H[36], gv[6];
-        cost = gn_range_block3(a3, b3, d.rng_dist[e], d.rng_prec[e], with_blocks ? H : nullptr, gv);
-        if (with_blocks) {
-            double* ho = hblk + M.hblk0 + 144 * M.n_rel + 36 * r;
-            double* go = gblk + M.gblk0 + 12 * M.n_rel + 6 * r;
-#pragma unroll
-            for (int k = 0; k < 36; ++k) ho[k] = H[k];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) go[k] = gv[k];
-        }
-    } else if (m < M.n_rel + M.n_rng + M.n_pri) {
-        const long long q = m - M.n_rel - M.n_rng, e = M.pri0 + q;
-        const double* l = Xg + 12 * M.Np + 3 * (long long)d.pri_l[e];
-        const double l3[3] = {l[0], l[1], l[2]};
-        double H[3], gv[3];
-        cost = gn_prior_block3(l3, d.pri_t + 3 * e, d.pri_prec[e], with_blocks ? H : nullptr, gv);
-        if (with_blocks) {
-            double* ho = hblk + M.hblk0 + 144 * M.n_rel + 36 * M.n_rng + 3 * q;
-            double* go = gblk + M.gblk0 + 12 * M.n_rel + 6 * M.n_rng + 3 * q;
-            for (int k = 0; k < 3; ++k) { ho[k] = H[k]; go[k] = gv[k]; }
-        }
-    }
-    const double tot = block_sum(cost, red);
-    if (threadIdx.x == 0) cost_part[blockIdx.x] = tot;
-}
-
-// one variable (pose or landmark) per lane: Xt = X (+ step) on the masked members.  step == nullptr: the copy of `accept`
-// (dst = X, src = Xt).  The pinned pose of a member has no step.
+// one variable (pose or landmark) per lane: dst = retract(src, step) on the masked members (gn_retract_variable).
+// step == nullptr: the copy of `accept` (dst = X, src = Xt).  The pinned pose of a member has no step.
 template <int DIM>
 __global__ __launch_bounds__(kThreads) void k_gb_trial(GbDev d, const double* __restrict__ src, const double* __restrict__ step,
                                                        double* __restrict__ dst, const int32_t* __restrict__ mask) {
-    constexpr int PS = DIM == 2 ? 3 : 12, DP = DIM == 2 ? 3 : 6;
     const int g = d.sblk_member[blockIdx.x];
     if (!mask[g]) return;
     const GbMember M = d.members[g];
     const long long i = (long long)((int)blockIdx.x - M.sblk0) * kThreads + threadIdx.x;
-    if (i < M.Np) {
-        const double* in = src + M.state0 + PS * i;
-        double* out = dst + M.state0 + PS * i;
-        if (!step || i == 0) {
-#pragma unroll
-            for (int k = 0; k < PS; ++k) out[k] = in[k];
-        } else if (DIM == 2) {
-            const double* st = step + M.col0 + DP * (i - 1);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) out[k] = in[k] + st[k];
-        } else {
-            double a[12], s6[6], o[12];
-#pragma unroll
-            for (int k = 0; k < 12; ++k) a[k] = in[k];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) s6[k] = step[M.col0 + DP * (i - 1) + k];
-            gn_pose3_retract(a, s6, o);
-#pragma unroll
-            for (int k = 0; k < 12; ++k) out[k] = o[k];
-        }
-    } else if (i < M.Np + M.Nl) {
-        const long long l = i - M.Np;
-        const double* in = src + M.state0 + PS * M.Np + DIM * l;
-        double* out = dst + M.state0 + PS * M.Np + DIM * l;
-        const double* st = step ? step + M.col0 + DP * (M.Np - 1) + DIM * l : nullptr;
-#pragma unroll
-        for (int k = 0; k < DIM; ++k) out[k] = st ? in[k] + st[k] : in[k];
-    }
+    gn_retract_variable<DIM>(src + M.state0, step ? step + M.col0 : nullptr, dst + M.state0, M.Np, M.Nl, i);
 }
 
 // one entry of H per lane: the sum of its block slots in list order (+ the member's lambda on the diagonal)

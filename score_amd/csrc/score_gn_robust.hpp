@@ -3,14 +3,14 @@
 // of score_gn.hpp on one refinement handle.
 //
 // Device: two streaming kernels, one measurement of the asked families per lane (ranges first, then the loop closures -- the
-// trailing relative-pose entries):
-//   k_gn_robust_resid   r = gn_range_resid / gn_rel_resid (score_gn.hpp: the square root of the block functions' own cost) at the
-//                       point, with the MEASURED precisions the handle keeps beside the arrays the block kernels read; per block
-//                       and family: max r^2 (non-finite r: +inf) and how many weights of this solve are more than 1e-6 from 0 and
-//                       from 1.  block_max / block_sum only: the host folds the partials in block order, as eval_at does.
-//   k_gn_robust_weight  w = gnc_tls_weight(r, mu, c_f) (score_robust.hpp, as it stands; mu is an argument, mu = 0: w = 1) and,
-//                       with `apply`, the next solve's precisions prec * max(w, min_weight) into the very arrays k_gn_blocks /
-//                       k_gn_blocks3 read (rng_prec, rel_kappa, rel_tau): the block kernels stay as they are.
+// trailing relative-pose entries).  What a lane does is stated once for this handle and the group (score_gn_robust_batch.hpp):
+//   k_gn_robust_resid   gn_robust_resid_lane: r = gn_robust_residual (score_gn.hpp: the square root of the block functions' own
+//                       cost) at the point, with the MEASURED precisions the handle keeps beside the arrays the block kernels read;
+//                       per block and family: max r^2 (non-finite r: +inf) and how many weights of this solve are more than 1e-6
+//                       from 0 and from 1.  block_max / block_sum only: the host folds the partials in block order (gn_robust_fold).
+//   k_gn_robust_weight  gn_robust_weight: w = gnc_tls_weight(r, mu, c_f) (score_robust.hpp, as it stands; mu is an argument,
+//                       mu = 0: w = 1) and, in mode kGbrNext, the next solve's precisions prec * max(w, min_weight) into the very
+//                       arrays k_gn_blocks reads (rng_prec, rel_kappa, rel_tau): the block kernels stay as they are.
 // Host: gn_robust_refine, a template over the backend concept of gn_levenberg_marquardt plus three hooks; the stop rule is the
 // pure function robust_decide of score_robust.hpp, the relaxation's.  One device-to-host read per outer iteration (the
 // partials) beyond what the LM loop reads.
@@ -22,89 +22,91 @@
 
 namespace score {
 
-constexpr int kGnRobustRanges = 1, kGnRobustClosures = 2;   // the bits of `families`
 constexpr int kGnRobustPart = 4;   // doubles per block in the partials: max r^2 (ranges, closures), non-binary weights (ranges, closures)
 
-struct GnRobustDev {
-    GnDev g;                  // the graph as the block kernels see it
-    int dim;
-    int64_t n_a, n_b;         // lanes: ranges [0, n_a), loop closures [n_a, n_a + n_b)  (a family that is not asked for: 0)
-    int64_t first_lc;         // loop closure e is relative-pose entry first_lc + e
-    const double *prec0, *kappa0, *tau0;   // the measured precisions (kappa0, tau0: loop-closure order)
+// what a weight kernel does with a measurement (the group's k_gbr_weight: by member)
+enum GbrMode : int32_t {
+    kGbrNext = 0,     // w from r in the enabled families; precisions prec0 * max(w, min_weight) there
+    kGbrKeep = 1,     // precisions prec0 * w of the weights as they stand (every family: a family that is off holds w = 1)
+    kGbrRestore = 2,  // precisions prec0
+    kGbrInspect = 3,  // w from r in the enabled families; the precisions are not touched
+};
+
+struct GnRobustArrays {   // ranges in range order, loop closures in loop-closure order (kappa, tau: relative-pose order)
+    const double *prec0, *kappa0, *tau0;   // the measured precisions
     double *prec, *kappa, *tau;            // what the block kernels read: rng_prec, rel_kappa, rel_tau
     double *r_rng, *r_lc, *w_rng, *w_lc;   // residuals, weights
 };
 
+struct GnRobustDev {
+    GnView g;                 // the graph as the block kernels see it, at the point whose residuals are asked for
+    int64_t n_a, n_b;         // lanes: ranges [0, n_a), loop closures [n_a, n_a + n_b)  (a family that is not asked for: 0)
+    int64_t first_lc;         // loop closure e is relative-pose entry first_lc + e
+    GnRobustArrays a;
+};
+
 __device__ __forceinline__ double gn_robust_nonbinary(double w) { return (fabs(w) <= 1e-6 || fabs(1.0 - w) <= 1e-6) ? 0.0 : 1.0; }
 
-__global__ __launch_bounds__(kThreads) void k_gn_robust_resid(GnRobustDev a, const double* __restrict__ u, double* __restrict__ part) {
-    __shared__ double red[8];
-    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    const GnDev& d = a.g;
+// One lane of a residual kernel on view v: range i (i < n_a; entry e_rng of the arrays) or loop closure q = i - n_a < n_b
+// (entry e_lc of the arrays, relative-pose entry first_lc + q of the view); then the workgroup's four partials into p.
+template <int DIM>
+__device__ __forceinline__ void gn_robust_resid_lane(const GnView& v, const GnRobustArrays& a, int64_t i, int64_t n_a, int64_t n_b,
+                                                     int64_t e_rng, int64_t e_lc, int64_t first_lc, double* red, double* p) {
     double r2a = 0.0, r2b = 0.0, nba = 0.0, nbb = 0.0;
-    if (i < a.n_a) {
-        double r;
-        if (a.dim == 2) {
-            double xa, ya, xb, yb;
-            gn_point(u, d.pin, d.Np, d.rng_a[i], xa, ya);
-            gn_point(u, d.pin, d.Np, d.rng_b[i], xb, yb);
-            r = gn_range_resid(xa, ya, xb, yb, d.rng_dist[i], a.prec0[i]);
-        } else {
-            const double* pa = gn_point3(u, d.Np, d.rng_a[i]);
-            const double* pb = gn_point3(u, d.Np, d.rng_b[i]);
-            const double a3[3] = {pa[0], pa[1], pa[2]}, b3[3] = {pb[0], pb[1], pb[2]};
-            r = gn_range_resid3(a3, b3, d.rng_dist[i], a.prec0[i]);
-        }
-        a.r_rng[i] = r;
+    if (i < n_a) {
+        const double r = gn_robust_residual<DIM>(v, kGnRobustRanges, i, a.prec0[e_rng], 0.0);
+        a.r_rng[e_rng] = r;
         r2a = r == r ? r * r : INFINITY;
-        nba = gn_robust_nonbinary(a.w_rng[i]);
-    } else if (i < a.n_a + a.n_b) {
-        const int64_t e = i - a.n_a, m = a.first_lc + e;
-        double r;
-        if (a.dim == 2) {
-            double thi, xi, yi, thj, xj, yj;
-            gn_pose(u, d.pin, d.rel_i[m], thi, xi, yi);
-            gn_pose(u, d.pin, d.rel_j[m], thj, xj, yj);
-            r = gn_rel_resid(thi, xi, yi, thj, xj, yj, d.rel_t + 2 * m, d.rel_R + 4 * m, a.kappa0[e], a.tau0[e]);
-        } else {
-            double Xi[12], Xj[12];
-            const double* pi = u + 12 * (int64_t)d.rel_i[m];
-            const double* pj = u + 12 * (int64_t)d.rel_j[m];
-#pragma unroll
-            for (int k = 0; k < 12; ++k) { Xi[k] = pi[k]; Xj[k] = pj[k]; }
-            r = gn_rel_resid3(Xi, Xj, d.rel_t + 3 * m, d.rel_R + 9 * m, a.kappa0[e], a.tau0[e]);
-        }
-        a.r_lc[e] = r;
+        nba = gn_robust_nonbinary(a.w_rng[e_rng]);
+    } else if (i < n_a + n_b) {
+        const double r = gn_robust_residual<DIM>(v, kGnRobustClosures, first_lc + (i - n_a), a.kappa0[e_lc], a.tau0[e_lc]);
+        a.r_lc[e_lc] = r;
         r2b = r == r ? r * r : INFINITY;
-        nbb = gn_robust_nonbinary(a.w_lc[e]);
+        nbb = gn_robust_nonbinary(a.w_lc[e_lc]);
     }
     r2a = block_max(r2a, red);
     r2b = block_max(r2b, red);
     nba = block_sum(nba, red);
     nbb = block_sum(nbb, red);
-    if (threadIdx.x == 0) {
-        double* p = part + (int64_t)kGnRobustPart * blockIdx.x;
-        p[0] = r2a; p[1] = r2b; p[2] = nba; p[3] = nbb;
-    }
+    if (threadIdx.x == 0) { p[0] = r2a; p[1] = r2b; p[2] = nba; p[3] = nbb; }
 }
 
-__global__ __launch_bounds__(kThreads) void k_gn_robust_weight(GnRobustDev a, double mu, double c_rng, double c_lc, double min_weight,
-                                                               int apply) {
+// The weight rule on one measurement, by mode: the weight *w from the residual *r (kGbrNext, kGbrInspect: written) or as it
+// stands.  Returns the factor on the measurement's measured precisions; the caller stores prec0 * factor in every mode but
+// kGbrInspect.
+__device__ __forceinline__ double gn_robust_weight(int32_t mode, const double* r, double* w, double mu, double c, double min_weight) {
 #pragma clang fp contract(off)
+    if (mode == kGbrNext || mode == kGbrInspect) {
+        const double wn = mu > 0.0 ? gnc_tls_weight(*r, mu, c) : 1.0;
+        *w = wn;
+        return fmax(wn, min_weight);
+    }
+    return mode == kGbrKeep ? *w : 1.0;
+}
+
+// (8 waves per SIMD asked for, for one reason only: the kernel with a runtime `dim` that this template replaces ran at that
+// occupancy, and the 3-D instance would otherwise come out two registers past it, at 7 -- where k_gbr_resid<3>, the same lane
+// function in the group's kernel, has always been and stays)
+template <int DIM>
+__global__ __launch_bounds__(kThreads, 8) void k_gn_robust_resid(GnRobustDev a, double* __restrict__ part) {
+    __shared__ double red[8];
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (i < a.n_a) {
-        const double w = mu > 0.0 ? gnc_tls_weight(a.r_rng[i], mu, c_rng) : 1.0;
-        a.w_rng[i] = w;
-        if (apply) a.prec[i] = a.prec0[i] * fmax(w, min_weight);
-    } else if (i < a.n_a + a.n_b) {
-        const int64_t e = i - a.n_a, m = a.first_lc + e;
-        const double w = mu > 0.0 ? gnc_tls_weight(a.r_lc[e], mu, c_lc) : 1.0;
-        a.w_lc[e] = w;
-        if (apply) {
-            const double f = fmax(w, min_weight);
-            a.kappa[m] = a.kappa0[e] * f;
-            a.tau[m] = a.tau0[e] * f;
-        }
+    gn_robust_resid_lane<DIM>(a.g, a.a, i, a.n_a, a.n_b, i, i - a.n_a, a.first_lc, red, part + (int64_t)kGnRobustPart * blockIdx.x);
+}
+
+// mode: kGbrNext (the next solve's precisions are written) or kGbrInspect
+__global__ __launch_bounds__(kThreads) void k_gn_robust_weight(GnRobustDev d, double mu, double c_rng, double c_lc, double min_weight,
+                                                               int32_t mode) {
+#pragma clang fp contract(off)
+    const GnRobustArrays& a = d.a;
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i < d.n_a) {
+        const double f = gn_robust_weight(mode, a.r_rng + i, a.w_rng + i, mu, c_rng, min_weight);
+        if (mode != kGbrInspect) a.prec[i] = a.prec0[i] * f;
+    } else if (i < d.n_a + d.n_b) {
+        const int64_t e = i - d.n_a, m = d.first_lc + e;
+        const double f = gn_robust_weight(mode, a.r_lc + e, a.w_lc + e, mu, c_lc, min_weight);
+        if (mode != kGbrInspect) { a.kappa[m] = a.kappa0[e] * f; a.tau[m] = a.tau0[e] * f; }
     }
 }
 
@@ -130,8 +132,11 @@ inline double gn_robust_mu0(const RobustSeen* seen, int n_seen) {
     return mu;
 }
 
-inline void gn_robust_check(const score_refine_robust_settings& s, const GnProblem& P) {
-    auto bad = [](const char* what) { throw std::runtime_error(std::string("score_refine_robust_run: ") + what); };
+// the settings of a robust run and the measured precisions of the families they enable (prec: the ranges; kappa, tau: the
+// n_lc loop closures); who: the prefix of the message
+inline void gn_robust_check_settings(const std::string& who, const score_refine_robust_settings& s, const double* prec, int64_t n_rng,
+                                     const double* kappa, const double* tau, int64_t n_lc) {
+    auto bad = [&who](const char* what) { throw std::runtime_error(who + what); };
     if ((s.families & ~(kGnRobustRanges | kGnRobustClosures)) || s.families == 0) bad("families must be 1 (ranges), 2 (loop closures) or 3");
     if (!(std::isfinite(s.inlier_threshold) && s.inlier_threshold > 0.0)) bad("inlier_threshold must be positive and finite");
     if ((s.families & kGnRobustClosures) && !(std::isfinite(s.rel_threshold) && s.rel_threshold > 0.0)) bad("rel_threshold must be positive and finite");
@@ -141,13 +146,29 @@ inline void gn_robust_check(const score_refine_robust_settings& s, const GnProbl
     if (s.inner_iters < 1) bad("inner_iters must be >= 1");
     auto positive = [](double v) { return std::isfinite(v) && v > 0.0; };
     if (s.families & kGnRobustRanges)
-        for (double v : P.rng_prec)
-            if (!positive(v)) bad("every range precision must be positive and finite");
+        for (int64_t e = 0; e < n_rng; ++e)
+            if (!positive(prec[e])) bad("every range precision must be positive and finite");
     if (s.families & kGnRobustClosures) {
-        const int64_t n_lc = gn_n_loop_closures(P);
         if (n_lc < 0) bad("fewer relative-pose entries than odometry steps");
-        for (int64_t e = P.n_rel() - n_lc; e < P.n_rel(); ++e)
-            if (!positive(P.rel_kappa[(size_t)e]) || !positive(P.rel_tau[(size_t)e])) bad("every loop closure's precisions must be positive and finite");
+        for (int64_t e = 0; e < n_lc; ++e)
+            if (!positive(kappa[e]) || !positive(tau[e])) bad("every loop closure's precisions must be positive and finite");
+    }
+}
+inline void gn_robust_check(const score_refine_robust_settings& s, const GnProblem& P) {
+    const int64_t n_lc = gn_n_loop_closures(P), first = P.n_rel() - std::max<int64_t>(n_lc, 0);
+    gn_robust_check_settings("score_refine_robust_run: ", s, P.rng_prec.data(), P.n_rng(), P.rel_kappa.data() + first, P.rel_tau.data() + first, n_lc);
+}
+
+// the partials of workgroups [b0, b1) of a residual kernel, in workgroup order: per family max r^2 (a NaN: +inf) and the
+// count of non-binary weights
+inline void gn_robust_fold(const double* part, int b0, int b1, double r2[2], double nonbin[2]) {
+    r2[0] = r2[1] = nonbin[0] = nonbin[1] = 0.0;
+    for (int b = b0; b < b1; ++b) {
+        const double* p = part + (size_t)kGnRobustPart * (size_t)b;
+        for (int f = 0; f < 2; ++f) {
+            r2[f] = p[f] != p[f] ? INFINITY : std::max(r2[f], p[f]);
+            nonbin[f] += p[2 + f];
+        }
     }
 }
 

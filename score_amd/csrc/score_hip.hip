@@ -331,6 +331,13 @@ struct DevArena {
     ~DevArena() { release_all(); }
 };
 thread_local DevArena* tl_arena = nullptr;  // set while a handle is being initialised on this thread
+struct ArenaScope {  // buffers allocated in this scope come from (and go back with) the arena given; then the previous one again
+    DevArena* keep;
+    explicit ArenaScope(DevArena* a) : keep(tl_arena) { tl_arena = a; }
+    ~ArenaScope() { tl_arena = keep; }
+    ArenaScope(const ArenaScope&) = delete;
+    ArenaScope& operator=(const ArenaScope&) = delete;
+};
 
 // Uploads of a handle under construction go through pinned staging when they are SMALL.  hipMemcpyAsync from pageable
 // memory blocks the caller for the whole transfer and every array is followed by a stream synchronisation: a create issues
@@ -1736,10 +1743,7 @@ struct HipBackend {
         return derive ? MatrixSource::derived : MatrixSource::uploaded;
     }
     // The guards of a create, held by init() in this order: a throw from any phase unwinds them last to first.
-    struct ArenaScope {  // buffers allocated during init come from this handle's arena
-        explicit ArenaScope(DevArena* a) { tl_arena = a; }
-        ~ArenaScope() { tl_arena = nullptr; }
-    };
+    // (ArenaScope: buffers allocated during init come from this handle's arena)
     struct StageScope {  // setup uploads through pinned staging (StageArena); one synchronisation when the setup is over
         StageArena a;
         hipStream_t st;
@@ -4055,6 +4059,21 @@ struct AbiEnv {
 #include "score_spectrum.hpp"
 #include "score_gn_robust.hpp"
 
+// Residuals and weights of a robust refinement handle (the single one or the group: rb_* buffers, ranges then loop closures) as
+// they are on the device, into the caller's arrays (null: not wanted); hw / hwl: the weights
+template <class Handle>
+static void robust_read(Handle& h, double* w, double* r, double* wl, double* rl, std::vector<double>& hw, std::vector<double>& hwl) {
+    const size_t nr = h.rb_r_rng.n, nc = h.rb_r_lc.n, f8 = sizeof(double);
+    hw.resize(nr); hwl.resize(nc);
+    if (nr) staged_d2h(hw.data(), h.rb_w_rng.d, nr * f8, h.stream());
+    if (nc) staged_d2h(hwl.data(), h.rb_w_lc.d, nc * f8, h.stream());
+    if (r && nr) staged_d2h(r, h.rb_r_rng.d, nr * f8, h.stream());
+    if (rl && nc) staged_d2h(rl, h.rb_r_lc.d, nc * f8, h.stream());
+    HIP_CHECK(sync_stream(h.stream()));
+    if (w) std::copy(hw.begin(), hw.end(), w);
+    if (wl) std::copy(hwl.begin(), hwl.end(), wl);
+}
+
 // Local refinement after SCORE on the device (score_gn.hpp): state, blocks and gathers here, the damped
 // normal equations through the linear-mode handle `lin` (its K0 values and right-hand side are written
 // in place by the gather kernels; the step is read from its solution vector).
@@ -4064,7 +4083,7 @@ struct score_refine {
     int device = 0;
     double setup_ms = 0;
     DevBuf<int32_t> rel_i, rel_j, rng_a, rng_b, pri_l, hc_ptr, hc_slot, gc_ptr, gc_slot, is_diag;
-    DevBuf<double> rel_t, rel_R, rel_kappa, rel_tau, rng_dist, rng_prec, pri_t, pri_prec, pin;
+    DevBuf<double> rel_t, rel_R, rel_kappa, rel_tau, rng_dist, rng_prec, pri_t, pri_prec;
     DevBuf<double> u, ut, hblk, gblk, rhs, cost_part, gmax_part;
     int n_mblocks = 0, n_ublocks = 0, n_hblocks = 0, n_sblocks = 0;
     std::vector<double> part_host;
@@ -4079,13 +4098,9 @@ struct score_refine {
 
     HipBackend& be() { return lin->solver.be; }
     hipStream_t stream() { return lin->solver.be.stream; }
-    score::GnDev dev() const {
-        score::GnDev d{};
-        d.Np = P.Np; d.Nl = P.Nl; d.n = P.n; d.n_rel = P.n_rel(); d.n_rng = P.n_rng(); d.n_pri = P.n_pri();
-        d.rel_i = rel_i.d; d.rel_j = rel_j.d; d.rng_a = rng_a.d; d.rng_b = rng_b.d; d.pri_l = pri_l.d;
-        d.rel_t = rel_t.d; d.rel_R = rel_R.d; d.rel_kappa = rel_kappa.d; d.rel_tau = rel_tau.d;
-        d.rng_dist = rng_dist.d; d.rng_prec = rng_prec.d; d.pri_t = pri_t.d; d.pri_prec = pri_prec.d; d.pin = pin.d;
-        return d;
+    score::GnView view(const double* where) const {  // the graph on the device, at the point `where`
+        return score::GnView{P.Np, P.Nl, P.n_rel(), P.n_rng(), P.n_pri(), rel_i.d, rel_j.d, rng_a.d, rng_b.d, pri_l.d,
+                             rel_t.d, rel_R.d, rel_kappa.d, rel_tau.d, rng_dist.d, rng_prec.d, pri_t.d, pri_prec.d, where, hblk.d, gblk.d};
     }
     void create(const score_graph& g, const score_settings* s) {
         const double t0 = score::now_ms();
@@ -4101,10 +4116,7 @@ struct score_refine {
         pt.mark("refine: linear-mode handle");
         device = lin->solver.st.device;
         tl_copy_stream = stream();
-        struct ArenaScope {  // the refinement's buffers come from (and go back with) the handle's arena
-            explicit ArenaScope(DevArena* a) { tl_arena = a; }
-            ~ArenaScope() { tl_arena = nullptr; }
-        } arena_scope(&be().arena);
+        ArenaScope arena_scope(&be().arena);  // the refinement's buffers come from (and go back with) the handle's arena
         rel_i.upload(P.rel_i); rel_j.upload(P.rel_j); rng_a.upload(P.rng_a); rng_b.upload(P.rng_b); pri_l.upload(P.pri_l);
         rel_t.upload(P.rel_t); rel_R.upload(P.rel_R); rel_kappa.upload(P.rel_kappa); rel_tau.upload(P.rel_tau);
         rng_dist.upload(P.rng_dist); rng_prec.upload(P.rng_prec); pri_t.upload(P.pri_t); pri_prec.upload(P.pri_prec);
@@ -4112,8 +4124,8 @@ struct score_refine {
         std::vector<int32_t> dg(P.hcol.size(), 0);
         for (int64_t i = 0; i < P.n; ++i) dg[(size_t)P.diag_pos[(size_t)i]] = 1;
         is_diag.upload(dg);
-        // state: 2-D the unknowns themselves (theta, x, y per free pose; landmarks); 3-D [R | t] of every pose, landmarks
-        pin.alloc(3); u.alloc((size_t)P.state_size()); ut.alloc((size_t)P.state_size()); rhs.alloc((size_t)P.n);
+        // state: every pose (2-D [theta, x, y], 3-D [R | t]), then the landmarks -- the caller's layout
+        u.alloc((size_t)P.state_size()); ut.alloc((size_t)P.state_size()); rhs.alloc((size_t)P.n);
         hblk.alloc((size_t)std::max<int64_t>(1, P.hblk_size())); gblk.alloc((size_t)std::max<int64_t>(1, P.gblk_size()));
         n_mblocks = (int)std::max<int64_t>(1, (P.n_meas() + kThreads - 1) / kThreads);
         n_ublocks = (int)std::max<int64_t>(1, (P.n + kThreads - 1) / kThreads);
@@ -4129,11 +4141,9 @@ struct score_refine {
     // ---- the backend concept of gn_levenberg_marquardt ----
     double eval_at(const double* where, bool with_blocks) {
         if (P.dim == 2)
-            hipLaunchKernelGGL(score::k_gn_blocks, dim3(n_mblocks), dim3(kThreads), 0, stream(), dev(), where, hblk.d, gblk.d,
-                               cost_part.d, with_blocks ? 1 : 0);
+            hipLaunchKernelGGL(score::k_gn_blocks<2>, dim3(n_mblocks), dim3(kThreads), 0, stream(), view(where), cost_part.d, with_blocks ? 1 : 0);
         else
-            hipLaunchKernelGGL(score::k_gn_blocks3, dim3(n_mblocks), dim3(kThreads), 0, stream(), dev(), where, hblk.d, gblk.d,
-                               cost_part.d, with_blocks ? 1 : 0);
+            hipLaunchKernelGGL(score::k_gn_blocks<3>, dim3(n_mblocks), dim3(kThreads), 0, stream(), view(where), cost_part.d, with_blocks ? 1 : 0);
         part_host.resize((size_t)n_mblocks);
         HIP_CHECK(hipMemcpyAsync(part_host.data(), cost_part.d, (size_t)n_mblocks * sizeof(double), hipMemcpyDeviceToHost, stream()));
         HIP_CHECK(sync_stream(stream()));
@@ -4144,10 +4154,10 @@ struct score_refine {
     double eval_current(bool with_blocks) { return eval_at(u.d, with_blocks); }
     double eval_trial() {
         if (P.dim == 2)
-            hipLaunchKernelGGL(score::k_gn_trial, dim3(n_ublocks), dim3(kThreads), 0, stream(), (const double*)u.d,
-                               (const double*)be().xtu.d, ut.d, (int64_t)P.n);
+            hipLaunchKernelGGL(score::k_gn_trial<2>, dim3(n_sblocks), dim3(kThreads), 0, stream(), (const double*)u.d,
+                               (const double*)be().xtu.d, ut.d, (int64_t)P.Np, (int64_t)P.Nl);
         else  // retraction: R <- R Exp(omega), t <- t + v
-            hipLaunchKernelGGL(score::k_gn_trial3, dim3(n_sblocks), dim3(kThreads), 0, stream(), (const double*)u.d,
+            hipLaunchKernelGGL(score::k_gn_trial<3>, dim3(n_sblocks), dim3(kThreads), 0, stream(), (const double*)u.d,
                                (const double*)be().xtu.d, ut.d, (int64_t)P.Np, (int64_t)P.Nl);
         return eval_at(ut.d, false);
     }
@@ -4171,18 +4181,13 @@ struct score_refine {
         gather_h(lambda);
         return be().linear_solve_core(lin->solver.H, rhs.d, rel_tol, 4000, used);
     }
-    // the caller's point becomes the current one (u); returns the state as uploaded
+    // the caller's point becomes the current one (u); returns the state as uploaded.  The state is the input layout: the poses
+    // (pose 0 included), then the landmarks
     std::vector<double> set_point(const double* poses_in, const double* lms_in) {
+        const int64_t np = P.state_size() - P.dim * P.Nl;
         std::vector<double> u0((size_t)P.state_size());
-        if (P.dim == 2) {
-            for (int64_t p = 1; p < P.Np; ++p)
-                for (int k = 0; k < 3; ++k) u0[(size_t)(3 * (p - 1) + k)] = poses_in[3 * p + k];
-            for (int64_t l = 0; l < 2 * P.Nl; ++l) u0[(size_t)(3 * (P.Np - 1) + l)] = lms_in[l];
-            HIP_CHECK(hipMemcpyAsync(pin.d, poses_in, 3 * sizeof(double), hipMemcpyHostToDevice, stream()));
-        } else {  // the state is the input layout: [R | t] per pose, then the landmarks
-            std::copy(poses_in, poses_in + 12 * P.Np, u0.begin());
-            if (P.Nl) std::copy(lms_in, lms_in + 3 * P.Nl, u0.begin() + (std::ptrdiff_t)(12 * P.Np));
-        }
+        std::copy(poses_in, poses_in + np, u0.begin());
+        if (P.Nl) std::copy(lms_in, lms_in + P.dim * P.Nl, u0.begin() + (std::ptrdiff_t)np);
         staged_h2d(u.d, u0.data(), u0.size() * sizeof(double), stream());
         HIP_CHECK(sync_stream(stream()));
         return u0;
@@ -4191,21 +4196,15 @@ struct score_refine {
              score::GnInfo& info) {
         std::vector<double> u0 = set_point(poses_in, lms_in);
         score::gn_levenberg_marquardt(*this, max_iters, tol, 1e-9, info);
-        read_point(u0, poses_in, poses_out, lms_out);
+        read_point(u0, poses_out, lms_out);
     }
     // the current point (u) in the caller's layout; u0: scratch of the state's size
-    void read_point(std::vector<double>& u0, const double* poses_in, double* poses_out, double* lms_out) {
+    void read_point(std::vector<double>& u0, double* poses_out, double* lms_out) {
+        const std::ptrdiff_t np = (std::ptrdiff_t)(P.state_size() - P.dim * P.Nl);
         staged_d2h(u0.data(), u.d, u0.size() * sizeof(double), stream());
         HIP_CHECK(sync_stream(stream()));
-        if (P.dim == 2) {
-            for (int k = 0; k < 3; ++k) poses_out[k] = poses_in[k];
-            for (int64_t p = 1; p < P.Np; ++p)
-                for (int k = 0; k < 3; ++k) poses_out[3 * p + k] = u0[(size_t)(3 * (p - 1) + k)];
-            for (int64_t l = 0; l < 2 * P.Nl; ++l) lms_out[l] = u0[(size_t)(3 * (P.Np - 1) + l)];
-        } else {
-            std::copy(u0.begin(), u0.begin() + (std::ptrdiff_t)(12 * P.Np), poses_out);
-            if (P.Nl) std::copy(u0.begin() + (std::ptrdiff_t)(12 * P.Np), u0.end(), lms_out);
-        }
+        std::copy(u0.begin(), u0.begin() + np, poses_out);
+        if (P.Nl) std::copy(u0.begin() + np, u0.end(), lms_out);
     }
 
     // ---- robust refinement: the hooks of gn_robust_refine (score_gn_robust.hpp) ----
@@ -4213,11 +4212,7 @@ struct score_refine {
         if (rb_ready) return;
         rb_n_lc = score::gn_n_loop_closures(P);
         if (rb_n_lc < 0) throw std::runtime_error("score_refine: fewer relative-pose entries than odometry steps");
-        struct ArenaScope {
-            DevArena* keep;
-            explicit ArenaScope(DevArena* a) : keep(tl_arena) { tl_arena = a; }
-            ~ArenaScope() { tl_arena = keep; }
-        } arena_scope(&be().arena);
+        ArenaScope arena_scope(&be().arena);
         const size_t nr = (size_t)P.n_rng(), nc = (size_t)rb_n_lc, first = (size_t)P.n_rel() - nc;
         rb_prec0.alloc(nr); rb_r_rng.alloc(nr); rb_w_rng.alloc(nr);
         rb_kappa0.alloc(nc); rb_tau0.alloc(nc); rb_r_lc.alloc(nc); rb_w_lc.alloc(nc);
@@ -4239,13 +4234,11 @@ struct score_refine {
     }
     score::GnRobustDev robust_dev(int families) const {
         score::GnRobustDev a{};
-        a.g = dev(); a.dim = P.dim;
+        a.g = view(u.d);
         a.n_a = (families & score::kGnRobustRanges) ? P.n_rng() : 0;
         a.n_b = (families & score::kGnRobustClosures) ? rb_n_lc : 0;
         a.first_lc = P.n_rel() - rb_n_lc;
-        a.prec0 = rb_prec0.d; a.kappa0 = rb_kappa0.d; a.tau0 = rb_tau0.d;
-        a.prec = rng_prec.d; a.kappa = rel_kappa.d; a.tau = rel_tau.d;
-        a.r_rng = rb_r_rng.d; a.r_lc = rb_r_lc.d; a.w_rng = rb_w_rng.d; a.w_lc = rb_w_lc.d;
+        a.a = score::GnRobustArrays{rb_prec0.d, rb_kappa0.d, rb_tau0.d, rng_prec.d, rel_kappa.d, rel_tau.d, rb_r_rng.d, rb_r_lc.d, rb_w_rng.d, rb_w_lc.d};
         return a;
     }
     void robust_weights(int families, double mu, double c, double c_rel, double min_weight, bool apply) {
@@ -4253,7 +4246,7 @@ struct score_refine {
         const int64_t lanes = a.n_a + a.n_b;
         if (lanes == 0) return;  // (an enabled family without measurements launches nothing)
         hipLaunchKernelGGL(score::k_gn_robust_weight, dim3((unsigned)((lanes + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream(), a, mu,
-                           c, c_rel, min_weight, apply ? 1 : 0);
+                           c, c_rel, min_weight, (int32_t)(apply ? score::kGbrNext : score::kGbrInspect));
     }
     void robust_weights(int families, double mu) {
         robust_weights(families, mu, rb_settings->inlier_threshold, rb_settings->rel_threshold, rb_settings->min_weight, true);
@@ -4265,17 +4258,12 @@ struct score_refine {
         const int nb = (int)((lanes + kThreads - 1) / kThreads);
         double r2[2] = {0.0, 0.0}, nonbin[2] = {0.0, 0.0};
         if (nb > 0) {
-            hipLaunchKernelGGL(score::k_gn_robust_resid, dim3(nb), dim3(kThreads), 0, stream(), a, (const double*)u.d, rb_part.d);
+            if (P.dim == 2) hipLaunchKernelGGL(score::k_gn_robust_resid<2>, dim3(nb), dim3(kThreads), 0, stream(), a, rb_part.d);
+            else hipLaunchKernelGGL(score::k_gn_robust_resid<3>, dim3(nb), dim3(kThreads), 0, stream(), a, rb_part.d);
             part_host.resize((size_t)score::kGnRobustPart * (size_t)nb);
             HIP_CHECK(hipMemcpyAsync(part_host.data(), rb_part.d, part_host.size() * sizeof(double), hipMemcpyDeviceToHost, stream()));
             HIP_CHECK(sync_stream(stream()));
-            for (int b = 0; b < nb; ++b) {
-                const double* p = part_host.data() + (size_t)score::kGnRobustPart * (size_t)b;
-                for (int f = 0; f < 2; ++f) {
-                    r2[f] = p[f] != p[f] ? INFINITY : std::max(r2[f], p[f]);
-                    nonbin[f] += p[2 + f];
-                }
-            }
+            score::gn_robust_fold(part_host.data(), 0, nb, r2, nonbin);
         }
         const double c[2] = {rb_settings ? rb_settings->inlier_threshold : 0.0, rb_settings ? rb_settings->rel_threshold : 0.0};
         const int64_t items[2] = {P.n_rng(), rb_n_lc};
@@ -4283,20 +4271,6 @@ struct score_refine {
         for (int f = 0; f < 2; ++f)
             if (families & (1 << f)) seen[n_seen++] = score::RobustSeen{items[f], r2[f], c[f], (int32_t)nonbin[f]};
         return n_seen;
-    }
-    // residuals and weights as they are on the device, into the caller's arrays (null: not wanted); counts the outliers
-    void robust_read(double* w, double* r, double* wl, double* rl, int32_t* outliers, int32_t* rel_outliers) {
-        const size_t nr = (size_t)P.n_rng(), nc = (size_t)rb_n_lc, f8 = sizeof(double);
-        std::vector<double> hw(nr), hwl(nc);
-        if (nr) staged_d2h(hw.data(), rb_w_rng.d, nr * f8, stream());
-        if (nc) staged_d2h(hwl.data(), rb_w_lc.d, nc * f8, stream());
-        if (r && nr) staged_d2h(r, rb_r_rng.d, nr * f8, stream());
-        if (rl && nc) staged_d2h(rl, rb_r_lc.d, nc * f8, stream());
-        HIP_CHECK(sync_stream(stream()));
-        if (w) std::copy(hw.begin(), hw.end(), w);
-        if (wl) std::copy(hwl.begin(), hwl.end(), wl);
-        if (outliers) { *outliers = 0; for (double v : hw) *outliers += v < 0.5 ? 1 : 0; }
-        if (rel_outliers) { *rel_outliers = 0; for (double v : hwl) *rel_outliers += v < 0.5 ? 1 : 0; }
     }
     void robust_run(const score_refine_robust_settings& s, const double* poses_in, const double* lms_in, double* poses_out, double* lms_out,
                     double* w, double* r, double* wl, double* rl, int32_t* outliers, int32_t* rel_outliers, score::GnRobustResult& R) {
@@ -4311,9 +4285,12 @@ struct score_refine {
         score::gn_robust_refine(*this, s, 1e-9, R);
         score::RobustSeen seen[2];
         (void)robust_residuals(score::kGnRobustRanges | score::kGnRobustClosures, seen);  // every family's r at the final estimate
-        robust_read(w, r, wl, rl, outliers, rel_outliers);
+        std::vector<double> hw, hwl;
+        robust_read(*this, w, r, wl, rl, hw, hwl);
+        if (outliers) { *outliers = 0; for (double v : hw) *outliers += v < 0.5 ? 1 : 0; }
+        if (rel_outliers) { *rel_outliers = 0; for (double v : hwl) *rel_outliers += v < 0.5 ? 1 : 0; }
         if (!(s.families & score::kGnRobustClosures) && rel_outliers) *rel_outliers = 0;
-        if (poses_out) read_point(u0, poses_in, poses_out, lms_out);
+        if (poses_out) read_point(u0, poses_out, lms_out);
     }
     void robust_inspect(const double* poses, const double* lms, double mu, double c, double c_rel, double* r, double* rl, double* w, double* wl) {
         if (!(mu >= 0.0) || !std::isfinite(mu)) throw std::runtime_error("score_refine_residuals: mu must be finite and >= 0");
@@ -4326,7 +4303,8 @@ struct score_refine {
         score::RobustSeen seen[2];
         (void)robust_residuals(both, seen);
         robust_weights(both, mu, c, c_rel, 1.0, false);
-        robust_read(w, r, wl, rl, nullptr, nullptr);
+        std::vector<double> hw, hwl;
+        robust_read(*this, w, r, wl, rl, hw, hwl);
     }
 };
 
@@ -4392,10 +4370,7 @@ struct score_refine_batch {
         if (be().split.active) throw std::runtime_error("score_refine_batch: the group needs the unsplit chain kernel (chain_split = 0)");
         if (be().n_prec == 0) throw std::runtime_error("score_refine_batch: the handle has no preconditioner work (no pose chains?)");
         tl_copy_stream = stream();
-        struct ArenaScope {  // the group's buffers come from (and go back with) the handle's arena
-            explicit ArenaScope(DevArena* a) { tl_arena = a; }
-            ~ArenaScope() { tl_arena = nullptr; }
-        } arena_scope(&be().arena);
+        ArenaScope arena_scope(&be().arena);  // the group's buffers come from (and go back with) the handle's arena
         members.upload(U.members); tiles.upload(U.tiles);
         mblk_member.upload(U.mblk_member); ublk_member.upload(U.ublk_member); sblk_member.upload(U.sblk_member);
         rblk_member.upload(U.rblk_member);
@@ -4445,10 +4420,10 @@ struct score_refine_batch {
         set_mask(m);
         const double* where = trial ? Xt.d : X.d;
         if (U.dim == 2)
-            hipLaunchKernelGGL(score::k_gb_blocks, dim3(n_mblocks), dim3(kThreads), 0, stream(), dev(), where, hblk.d, gblk.d, cost_part.d,
+            hipLaunchKernelGGL(score::k_gb_blocks<2>, dim3(n_mblocks), dim3(kThreads), 0, stream(), dev(), where, hblk.d, gblk.d, cost_part.d,
                                (const int32_t*)mask.d, with_blocks ? 1 : 0);
         else
-            hipLaunchKernelGGL(score::k_gb_blocks3, dim3(n_mblocks), dim3(kThreads), 0, stream(), dev(), where, hblk.d, gblk.d, cost_part.d,
+            hipLaunchKernelGGL(score::k_gb_blocks<3>, dim3(n_mblocks), dim3(kThreads), 0, stream(), dev(), where, hblk.d, gblk.d, cost_part.d,
                                (const int32_t*)mask.d, with_blocks ? 1 : 0);
         HIP_CHECK(hipGetLastError());
         if (!cost) return;
@@ -4621,11 +4596,7 @@ struct score_refine_batch {
     void robust_reserve() {  // the buffers, from the handle's arena
         if (rb_ready) return;
         robust_host_precisions();
-        struct ArenaScope {
-            DevArena* keep;
-            explicit ArenaScope(DevArena* a) : keep(tl_arena) { tl_arena = a; }
-            ~ArenaScope() { tl_arena = keep; }
-        } arena_scope(&be().arena);
+        ArenaScope arena_scope(&be().arena);
         tl_copy_stream = stream();
         const size_t nr = U.rng_prec.size(), nc = (size_t)U.lcs_size;
         rb_prec0.upload(U.rng_prec); rb_kappa0.upload(rb_kappa0_host); rb_tau0.upload(rb_tau0_host);
@@ -4640,9 +4611,7 @@ struct score_refine_batch {
     score::GbrDev robust_dev() const {
         score::GbrDev a{};
         a.d = dev();
-        a.prec0 = rb_prec0.d; a.kappa0 = rb_kappa0.d; a.tau0 = rb_tau0.d;
-        a.prec = rng_prec.d; a.kappa = rel_kappa.d; a.tau = rel_tau.d;
-        a.r_rng = rb_r_rng.d; a.r_lc = rb_r_lc.d; a.w_rng = rb_w_rng.d; a.w_lc = rb_w_lc.d;
+        a.a = score::GnRobustArrays{rb_prec0.d, rb_kappa0.d, rb_tau0.d, rng_prec.d, rel_kappa.d, rel_tau.d, rb_r_rng.d, rb_r_lc.d, rb_w_rng.d, rb_w_lc.d};
         a.params = rb_params.d;
         return a;
     }
@@ -4680,29 +4649,11 @@ struct score_refine_batch {
         for (int g = 0; g < U.count; ++g) {
             if (!m[(size_t)g]) continue;
             const score::GbMember& M = U.members[(size_t)g];
-            double r2[2] = {0.0, 0.0}, nonbin[2] = {0.0, 0.0};
-            for (int b = M.rblk0; b < M.rblk1; ++b) {  // the member's partials in workgroup order
-                const double* p = part_host.data() + (size_t)score::kGnRobustPart * (size_t)b;
-                for (int f = 0; f < 2; ++f) {
-                    r2[f] = p[f] != p[f] ? INFINITY : std::max(r2[f], p[f]);
-                    nonbin[f] += p[2 + f];
-                }
-            }
+            double r2[2], nonbin[2];
+            score::gn_robust_fold(part_host.data(), M.rblk0, M.rblk1, r2, nonbin);  // the member's partials in workgroup order
             seen[g].f[0] = score::RobustSeen{(int64_t)M.n_rng, r2[0], 0.0, (int32_t)nonbin[0]};
             seen[g].f[1] = score::RobustSeen{(int64_t)M.n_lc, r2[1], 0.0, (int32_t)nonbin[1]};
         }
-    }
-    // residuals and weights as they are on the device, into the caller's arrays (null: not wanted); hw / hwl: the weights
-    void robust_read(double* w, double* r, double* wl, double* rl, std::vector<double>& hw, std::vector<double>& hwl) {
-        const size_t nr = rb_r_rng.n, nc = rb_r_lc.n, f8 = sizeof(double);
-        hw.resize(nr); hwl.resize(nc);
-        if (nr) staged_d2h(hw.data(), rb_w_rng.d, nr * f8, stream());
-        if (nc) staged_d2h(hwl.data(), rb_w_lc.d, nc * f8, stream());
-        if (r && nr) staged_d2h(r, rb_r_rng.d, nr * f8, stream());
-        if (rl && nc) staged_d2h(rl, rb_r_lc.d, nc * f8, stream());
-        HIP_CHECK(sync_stream(stream()));
-        if (w) std::copy(hw.begin(), hw.end(), w);
-        if (wl) std::copy(hwl.begin(), hwl.end(), wl);
     }
     // rs: one record per member
     void robust_run(const score_refine_robust_settings* rs, const double* poses_in, const double* lms_in, double* poses_out, double* lms_out,
@@ -4720,7 +4671,7 @@ struct score_refine_batch {
         std::vector<score::GbrSeen> seen((size_t)U.count);
         robust_residuals(all, seen.data());  // every family's r at the final estimates
         std::vector<double> hw, hwl;
-        robust_read(w, r, wl, rl, hw, hwl);
+        robust_read(*this, w, r, wl, rl, hw, hwl);
         outliers.assign((size_t)U.count, 0); rel_outliers.assign((size_t)U.count, 0);
         for (int g = 0; g < U.count; ++g) {
             const score::GbMember& M = U.members[(size_t)g];
@@ -4752,7 +4703,7 @@ struct score_refine_batch {
         robust_residuals(all, seen.data());
         robust_weights(all, params.data());
         std::vector<double> hw, hwl;
-        robust_read(w, r, wl, rl, hw, hwl);
+        robust_read(*this, w, r, wl, rl, hw, hwl);
     }
 };
 

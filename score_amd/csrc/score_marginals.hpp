@@ -2,7 +2,7 @@
 // H = J'J at the given point, one unit column per scalar unknown of the selected variables, by a chain-preconditioned
 // conjugate-gradient iteration over BLOCKS of up to kMvMaxWidth columns that advance in lock-step.
 //
-// What exists already and is used as it is: the per-measurement blocks (k_gn_blocks / k_gn_blocks3), the gather of H on the
+// What exists already and is used as it is: the per-measurement blocks (k_gn_blocks<DIM>), the gather of H on the
 // linear-mode handle's pattern (k_gn_gather_h, lambda = 0), the chain factorisation (derive_rho_data -> k_factor) and the
 // application of M^-1 to several vectors in one launch (launch_prec<PREC_INIT> with PrecArgs::n_vec: chains, the second
 // level of score_join.hpp, Jacobi on the landmark columns; the loop-closure correction is left out -- the preconditioner

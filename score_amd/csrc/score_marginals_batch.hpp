@@ -8,7 +8,7 @@
 // k W + c >= C_g gets r = 0 and done word 1 from the start.  NV is chosen per pass: the smallest of 1, 2, 4, 8, 16 that
 // holds the most live slots of any member.
 //
-// What exists already and is used as it is: the blocks of all members (k_gb_blocks / k_gb_blocks3), the gather of H on the
+// What exists already and is used as it is: the blocks of all members (k_gb_blocks<DIM>), the gather of H on the
 // union pattern (k_gb_gather_h, lambda = 0), one chain factorisation for all members (derive_rho_data -> k_factor), M^-1 on
 // several union vectors in one launch (launch_prec<PREC_INIT> with PrecArgs::n_vec), and the product of one tile
 // (mv_product_tile of score_marginals.hpp).  New here: every (member, slot) pair has its own alpha, beta, gate and done word.

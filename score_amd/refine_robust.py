@@ -72,7 +72,7 @@ def _bind(lib: C.CDLL) -> C.CDLL:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the residuals (the device's are csrc/score_gn.hpp: gn_range_resid, gn_rel_resid -- same operations, same order)
+# the residuals (the device's are csrc/score_gn.hpp: gn_robust_residual<DIM> -- same operations, same order)
 # ---------------------------------------------------------------------------------------------------------------------
 def _translations(prob, point):
     if isinstance(prob, _Problem3D):

@@ -1387,8 +1387,8 @@ def test_3d_chain_kernels_match_the_twin(n_poses, hip_lib, twin_lib):
 
 
 def test_3d_refinement_on_the_gpu(hip_lib, twin_lib):
-    """f4 in 3-D: SE(3) Gauss-Newton / LM behind score_refine_run on the device (k_gn_blocks3: 12 x 12 relative-pose
-    blocks; k_gn_trial3: the retraction R Exp(omega), t + v; normal equations through the chain-preconditioned PCG
+    """f4 in 3-D: SE(3) Gauss-Newton / LM behind score_refine_run on the device (k_gn_blocks<3>: 12 x 12 relative-pose
+    blocks; k_gn_trial<3>: the retraction R Exp(omega), t + v; normal equations through the chain-preconditioned PCG
     with the omega and v chains of every robot) -- against SciPy's least_squares / sparse LU (check_3d_refinement) and
     against the CPU twin of the same loop; then on a larger graph: same LM iterations as the twin."""
     from test_refine import _graph3, _noisy_truth3, check_3d_refinement

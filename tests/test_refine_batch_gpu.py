@@ -5,6 +5,7 @@ Tolerances are the project's own (tests/test_refine.py): between two device runs
 rounding of their conjugate-gradient solves, poses and landmarks agree to atol 1e-7 in 2-D and 1e-5 in 3-D; against SciPy's LU
 to 1e-5.  Every member ends with |g|_inf < 1e-5 max(1, cost) and a cost no larger than it started with."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -12,9 +13,13 @@ import pytest
 from marginals_helpers import undetermined_graph
 from refine_batch_helpers import (KEYS_2D, MILD, arrays_of, check_fixture, group, member, native_alone, noisy_truth, rough_start,
                                   twin_alone)
-from score_amd.manhattan import make_manhattan
+from refine_robust_helpers import point_of, start_of
+from score_amd import compat
+from score_amd.manhattan import make_manhattan, make_manhattan_3d
 from score_amd.refine import _as_results, refine_estimate
 from score_amd.refine_batch import RefineBatchHandle, _bind, _problem_of, refine_estimate_batch
+from score_amd.refine_robust import RobustRefineHandle
+from score_amd.robust import n_loop_closures_of
 
 pytestmark = pytest.mark.gpu
 
@@ -195,3 +200,56 @@ def test_errors_are_reported_not_faults(hip_lib):
     lib.score_refine_batch_destroy(None)
     with pytest.raises(RuntimeError, match="share dim"):
         RefineBatchHandle([p2, p3], hip_lib)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# One lane function per job: what a lane does with a measurement is the same code in the single handle's kernels and in the
+# group's (csrc/score_gn.hpp: gn_measurement, gn_robust_residual; csrc/score_gn_robust.hpp: gn_robust_weight), and a member's
+# measurements lie over workgroups as a handle on it alone lays them.  So a group of one IS the single handle, value for
+# value: equalities between two paths of the product, no tolerance.
+# ---------------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _two_workgroup_graph(dim):
+    """Two chains of 60 poses whose measurements, and whose ranges + loop closures, fill more than one workgroup of 256 and at
+    most two; range 0 and loop closure 1 re-attached to pose 0 (the pinned pose, which also has its odometry neighbour); one
+    landmark prior."""
+    make = make_manhattan if dim == 2 else make_manhattan_3d
+    fg = make(seed=7, n_robots=2, n_poses=60, n_beacons=4, p_range=0.6, n_loop_closures=4)
+    first = fg.pose_variables[0][0].name
+    m = fg.range_measurements[0]
+    m.association = (first, m.association[1])
+    fg.loop_closure_measurements[1].base_pose = first
+    lm = fg.landmark_variables[1]
+    prior = compat.LandmarkPrior2D if dim == 2 else compat.LandmarkPrior3D
+    fg.landmark_priors = [prior(lm.name, tuple(float(v) + 0.25 for v in lm.true_position), 2.0)]
+    start = start_of(fg)
+    a = point_of(fg, start)[0].a
+    n_rel, n_rng, n_lc, n_pri = len(a["rel_base"]), len(a["rng_a"]), n_loop_closures_of(a), len(a["lprior_lm"])
+    assert len(fg.pose_variables) == 2 and n_pri == 1 and n_lc == 4
+    assert 256 < n_rel + n_rng + n_pri <= 512 and 256 < n_rng + n_lc <= 512, (n_rel, n_rng, n_lc, n_pri)
+    assert a["rng_a"][0] == 0 and a["rel_base"][n_rel - n_lc + 1] == 0 and a["rel_base"][0] == 0 and a["rel_to"][0] == 1
+    return fg, start
+
+
+@pytest.mark.parametrize("dim", [2, 3])
+def test_group_of_one_residuals_and_weights_are_the_single_handle_s(dim, hip_lib):
+    fg, start = _two_workgroup_graph(dim)
+    prob, point = point_of(fg, start)
+    mu, c, c_rel = 0.7, 3.0, 2.5
+    with RobustRefineHandle(prob, hip_lib) as h:
+        single = h.residuals(point, mu, c, c_rel)
+    with RefineBatchHandle([prob], hip_lib) as h:
+        (alone,) = h.residuals([point], mu, c, c_rel)
+    for name, a, b in zip(("residuals", "loop-closure residuals", "weights", "loop-closure weights"), single, alone):
+        assert a.shape == b.shape and a.size > 0, name
+        np.testing.assert_array_equal(a, b, err_msg=name)
+    w, wl = single[2], single[3]
+    assert np.any(w == 1.0) and np.any(w < 1.0) and np.all((wl >= 0.0) & (wl <= 1.0))  # (the weight rule was at work)
+
+
+@pytest.mark.parametrize("dim", [2, 3])
+def test_group_of_one_starts_at_the_single_handle_s_cost(dim, hip_lib):
+    fg, start = _two_workgroup_graph(dim)
+    _, sinfo = refine_estimate(fg, start, max_iters=2, engine="native", lib_path=hip_lib)
+    ((_, info),) = refine_estimate_batch([fg], [start], max_iters=2, lib_path=hip_lib)
+    assert isinstance(info["cost_initial"], float) and info["cost_initial"] == sinfo["cost_initial"] > 0.0

@@ -23,7 +23,7 @@ SCHEDULE = {"G1": {}, "G2": {}, "G3": dict(max_iters=3, inner_iters=3)}
 
 
 def _g2_touching_the_pinned_pose():
-    """G2's graph with range 0 and loop closure 1 re-attached to pose 0 (the pinned pose: its point comes from `pin` in 2-D)."""
+    """G2's graph with range 0 and loop closure 1 re-attached to pose 0 (the pinned pose: the first entry of the state, which never receives a step)."""
     fg = make_manhattan(seed=9, n_robots=2, n_poses=25, n_beacons=2, p_range=0.5, n_loop_closures=3)
     corrupt(fg, 9, (0,))
     first = fg.pose_variables[0][0].name
