@@ -1,5 +1,5 @@
-"""Every array and counter the four refinement entry points return on the tests' small fixtures, for a bit-for-bit comparison of
-two builds of the library (a refactor of the refinement kernels must not move one bit).
+"""Every array and counter the refinement, marginals and spectrum entry points return on the tests' small fixtures, for a
+bit-for-bit comparison of two builds of the library (a refactor of their kernels or drivers must not move one bit).
 
   python profiles/scripts/refine_bits.py OUT.npz [--lib PATH]        record
   python profiles/scripts/refine_bits.py --compare A.npz B.npz        compare two records with array_equal (NaNs equal); exit 1
@@ -9,7 +9,12 @@ Runs, each on a fresh handle: refine_estimate on the 2-D members A..E and the 3-
 refine_estimate_batch on the 2-D group and on the 3-D group, refine_estimate_robust (both families) on G1..G4 and the clean 3-D
 graph of tests/refine_robust_batch_helpers.py, refine_estimate_robust_batch on (G1, G2, G4) and on (G3, clean 3-D).  Recorded per
 run: poses and landmarks in the graph's order and every numeric entry of the info record, nested ones included (iteration
-counters, costs, gradient norm, mu, weights, residuals, outlier sets); timings (*_ms) are left out."""
+counters, costs, gradient norm, mu, weights, residuals, outlier sets); timings (*_ms) are left out.
+
+Then, at the host-refined points of tests/refine_batch_helpers.py (twin_alone): marginal_covariances on A and 3D0 at block
+widths 0, 4 and 16, marginal_covariances_batch on the 2-D group and on the 3-D group at widths 4 and 16, information_spectrum
+(k = 4) on A.  Recorded per run: the matrices (joint and as computed), residuals, per-column step counts and the numeric info
+fields; for the spectrum the values, vectors and residuals."""
 import argparse
 import os
 import sys
@@ -66,6 +71,25 @@ def record(lib):
                                            engine="native", lib_path=lib, **SCHEDULE[keys[0]])
         for k, fg, (res, info) in zip(keys, fgs, got):
             keep(f"refine_estimate_robust_batch/{'+'.join(keys)}/{k}", fg, res, info)
+    from refine_batch_helpers import twin_alone
+    from score_amd.marginals import marginal_covariances
+    from score_amd.marginals_batch import marginal_covariances_batch
+    from score_amd.spectrum import information_spectrum
+
+    for k in ("A", "3D0"):
+        for width in (0, 4, 16):
+            _, info = marginal_covariances(member(k)[0], twin_alone(k)[0], joint=True, block_width=width, lib_path=lib)
+            flatten(f"marginal_covariances/{k}/width{width}", info, out)
+    for keys in (KEYS_2D, ("3D0", "3D1")):
+        for width in (4, 16):
+            got = marginal_covariances_batch([member(k)[0] for k in keys], [twin_alone(k)[0] for k in keys], joint=True,
+                                             block_width=width, lib_path=lib)
+            for k, (_, info) in zip(keys, got):
+                flatten(f"marginal_covariances_batch/{'+'.join(keys)}/width{width}/{k}", info, out)
+    modes, info = information_spectrum(member("A")[0], twin_alone("A")[0], k=4, lib_path=lib)
+    for what in ("values", "vectors", "residuals"):
+        out[f"information_spectrum/A/{what}"] = getattr(modes, what)
+    flatten("information_spectrum/A/info", info, out)
     return out
 
 

@@ -12,15 +12,9 @@
 // exactly as k_gn_blocks lays them (local measurement m in the member's workgroup m / kThreads), so a member's cost partials
 // are those of a handle on it alone.
 //
-// The conjugate-gradient iteration (modelled on score_marginals.hpp, with "column" replaced by "member"):
-//   k_gb_product    w = H p over the tiles of the live members (64 short rows x 4 lanes, or one long row over the workgroup),
-//                   per-tile partials of p'w
-//   k_gb_step       alpha_g = r'z / p'w (both re-reduced from the member's partials in a fixed order); x += alpha p, r -= alpha w
-//   launch_prec     z = M^-1 r (the whole group; a done member's z is scratch)
-//   k_gb_rz         per-workgroup partials of r'z
-//   k_gb_direction  beta_g = r'z_new / r'z_old, p = z + beta p; the gate r'z_new <= rel_tol^2 r0'z0 raises the member's done word
-// Done words: 1 converged, 2 broken down (a non-finite r'z or p'w, or p'w <= 0) -- the member's solve reports failure.  No
-// atomics: all workgroups of a member reduce the same partials in the same order and take the same decision.
+// The damped step of a round is one slot of the group's conjugate-gradient iteration (score_group_pcg.hpp, shared with the
+// marginals of a group): every member has its own alpha, beta, gate and done word, and a member the round leaves out starts
+// with done word 1.  The product's tiles of a member are cut by mv_tiles (score_marginals.hpp) from its own rows.
 #pragma once
 
 #include <algorithm>
@@ -32,6 +26,7 @@
 #include "../../include/score_refine_batch.h"
 #include "score_gn.hpp"
 #include "score_kernels.hpp"
+#include "score_marginals.hpp"
 
 namespace score {
 
@@ -154,10 +149,6 @@ inline int gb_lock_step(Backend& be, int count, int max_iters, double tol, doubl
 // ---------------------------------------------------------------------------
 // the union problem
 // ---------------------------------------------------------------------------
-constexpr int kGbLanes = 4;                       // lanes of a short row
-constexpr int kGbRows = kThreads / kGbLanes;      // short rows of a product tile
-constexpr int kGbLongRow = 128;                   // entries beyond which a row is a tile of its own
-
 struct GbMember {  // where member g lives in the union arrays
     long long Np, Nl, n, n_rel, n_rng, n_pri;
     long long rel0, rng0, pri0;        // first entry in the measurement arrays
@@ -244,15 +235,7 @@ inline void gb_build(const score_graph* graphs, int count, GbUnion& U) {
         M.rblk0 = (int)U.rblk_member.size(); U.rblk_member.insert(U.rblk_member.end(), (size_t)blocks(M.n_rng + M.n_lc), g); M.rblk1 = (int)U.rblk_member.size();
         // product tiles of the member's rows
         M.tile0 = (int)U.tiles.size();
-        auto len = [&](long long i) { return P.hptr[(size_t)i + 1] - P.hptr[(size_t)i]; };
-        long long row = 0;
-        while (row < P.n) {
-            if (len(row) > kGbLongRow) { U.tiles.push_back(make_int4((int)(M.col0 + row), (int)(M.col0 + row + 1), 1, g)); ++row; continue; }
-            long long end = row;
-            while (end < P.n && end - row < kGbRows && len(end) <= kGbLongRow) ++end;
-            U.tiles.push_back(make_int4((int)(M.col0 + row), (int)(M.col0 + end), 0, g));
-            row = end;
-        }
+        mv_tiles(P.hptr, P.n, U.tiles, M.col0, g);
         M.tile1 = (int)U.tiles.size();
         U.n += P.n;
         U.state_size += (long long)U.pose_scalars() * P.Np + (long long)U.dim * P.Nl;
@@ -347,156 +330,6 @@ __global__ __launch_bounds__(kThreads) void k_gb_gather_g(GbDev d, const int32_t
     }
     const double mx = block_max(a, red);
     if (threadIdx.x == 0) gmax_part[blockIdx.x] = mx;
-}
-
-// ---- the conjugate-gradient iteration, member by member ----
-struct GbPcg {
-    GbDev d;
-    const int32_t* ptr; const int32_t* col; const double* val;   // H on the union pattern
-    const int4* tiles;
-    int32_t* done;             // [member] done word
-    int32_t* iters;            // [member] steps executed
-    double* x; double* r; const double* z; double* p; double* w;
-    const double* rhs;
-    double* pw_part;           // [tile]
-    double* rz_part;           // [unknown workgroup]: k_gb_rz writes
-    const double* rz_new;      // partials of the last application of M^-1
-    const double* rz_old;
-    int first;                 // direction: p = z, the gate's threshold is set
-    double tol2;
-    double* ref;               // [member] rel_tol^2 r0'z0
-};
-
-__device__ __forceinline__ bool gb_finite(double v) { return fabs(v) <= 1.79769313486231570e308; }
-
-// x = 0, r = rhs on the members about to be solved (done word 0)
-__global__ __launch_bounds__(kThreads) void k_gb_pcg_begin(GbPcg a) {
-    const int g = a.d.ublk_member[blockIdx.x];
-    if (a.done[g]) return;
-    const GbMember M = a.d.members[g];
-    const long long li = (long long)((int)blockIdx.x - M.ublk0) * kThreads + threadIdx.x;
-    if (li < M.n) {
-        a.x[M.col0 + li] = 0.0;
-        a.r[M.col0 + li] = a.rhs[M.col0 + li];
-    }
-}
-
-// w = H p on the tiles of the live members, per-tile partial of p'w
-__global__ __launch_bounds__(kThreads) void k_gb_product(GbPcg a) {
-    __shared__ double red[4];
-    const int4 tile = a.tiles[blockIdx.x];
-    if (a.done[tile.w]) return;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    double acc = 0.0;
-    if (tile.z) {  // one long row over the workgroup
-        const int row = tile.x;
-        const int k1 = a.ptr[row + 1];
-        for (int k = a.ptr[row] + t; k < k1; k += kThreads) acc += a.val[k] * a.p[a.col[k]];
-        const double s = wave_sum(acc);
-        if (lane == 0) red[wave] = s;
-        __syncthreads();
-        if (t == 0) {
-            const double wv = (red[0] + red[1]) + (red[2] + red[3]);
-            a.w[row] = wv;
-            a.pw_part[blockIdx.x] = a.p[row] * wv;
-        }
-        return;
-    }
-    // short rows: kGbLanes lanes per row, their sums joined as (l0 + l1) + (l2 + l3)
-    const int row = tile.x + t / kGbLanes, sub = t % kGbLanes;
-    const bool mine = row < tile.y;
-    if (mine) {
-        const int k1 = a.ptr[row + 1];
-        for (int k = a.ptr[row] + sub; k < k1; k += kGbLanes) acc += a.val[k] * a.p[a.col[k]];
-    }
-    double s = acc;
-    s += __shfl_xor(s, 1, 64);
-    s += __shfl_xor(s, 2, 64);
-    double pw = 0.0;
-    if (mine && sub == 0) {
-        a.w[row] = s;
-        pw = a.p[row] * s;
-    }
-    pw = wave_sum(pw);
-    if (lane == 0) red[wave] = pw;
-    __syncthreads();
-    if (t == 0) a.pw_part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// alpha = r'z / p'w of the workgroup's member ; x += alpha p ; r -= alpha w
-__global__ __launch_bounds__(kThreads) void k_gb_step(GbPcg a) {
-    __shared__ double red[8];
-    const int g = a.d.ublk_member[blockIdx.x], t = threadIdx.x;
-    if (a.done[g]) return;
-    const GbMember M = a.d.members[g];
-    double rz = 0.0, pw = 0.0;
-    for (int i = M.ublk0 + t; i < M.ublk1; i += kThreads) rz += a.rz_new[i];
-    for (int i = M.tile0 + t; i < M.tile1; i += kThreads) pw += a.pw_part[i];
-    block_sum2(rz, pw, red);
-    const bool lead = (int)blockIdx.x == M.ublk0 && t == 0;
-    if (!(gb_finite(rz) && gb_finite(pw) && pw > 0.0)) {
-        if (lead) a.done[g] = 2;
-        return;
-    }
-    const double alpha = rz / pw;
-    const long long li = (long long)((int)blockIdx.x - M.ublk0) * kThreads + t;
-    if (li < M.n) {
-        const long long e = M.col0 + li;
-        a.x[e] += alpha * a.p[e];
-        a.r[e] -= alpha * a.w[e];
-    }
-    if (lead) a.iters[g] += 1;
-}
-
-// per-workgroup partials of r'z on the live members
-__global__ __launch_bounds__(kThreads) void k_gb_rz(GbPcg a) {
-    __shared__ double red[4];
-    const int g = a.d.ublk_member[blockIdx.x], t = threadIdx.x;
-    if (a.done[g]) return;
-    const GbMember M = a.d.members[g];
-    const long long li = (long long)((int)blockIdx.x - M.ublk0) * kThreads + t;
-    double v = 0.0;
-    if (li < M.n) v = a.r[M.col0 + li] * a.z[M.col0 + li];
-    const double s = block_sum(v, red);
-    if (t == 0) a.rz_part[blockIdx.x] = s;
-}
-
-// the gate of the workgroup's member, then p = z + beta p (first: p = z and the gate's threshold)
-__global__ __launch_bounds__(kThreads) void k_gb_direction(GbPcg a) {
-    __shared__ double red[8];
-    const int g = a.d.ublk_member[blockIdx.x], t = threadIdx.x;
-    if (a.done[g]) return;
-    const GbMember M = a.d.members[g];
-    double rzn = 0.0, rzo = 0.0;
-    for (int i = M.ublk0 + t; i < M.ublk1; i += kThreads) {
-        rzn += a.rz_new[i];
-        if (!a.first) rzo += a.rz_old[i];
-    }
-    block_sum2(rzn, rzo, red);
-    const bool lead = (int)blockIdx.x == M.ublk0 && t == 0;
-    double beta = 0.0;
-    if (a.first) {
-        if (!(gb_finite(rzn) && rzn > 0.0)) {  // (a zero right-hand side is solved by x = 0)
-            if (lead) a.done[g] = rzn == 0.0 ? 1 : 2;
-            return;
-        }
-        if (lead) a.ref[g] = a.tol2 * rzn;
-    } else {
-        if (!(gb_finite(rzn) && rzo > 0.0)) {
-            if (lead) a.done[g] = 2;
-            return;
-        }
-        if (rzn <= a.ref[g]) {
-            if (lead) a.done[g] = 1;
-            return;
-        }
-        beta = rzn / rzo;
-    }
-    const long long li = (long long)((int)blockIdx.x - M.ublk0) * kThreads + t;
-    if (li < M.n) {
-        const long long e = M.col0 + li;
-        a.p[e] = a.first ? a.z[e] : a.z[e] + beta * a.p[e];
-    }
 }
 
 }  // namespace score

@@ -338,6 +338,9 @@ struct ArenaScope {  // buffers allocated in this scope come from (and go back w
     ArenaScope(const ArenaScope&) = delete;
     ArenaScope& operator=(const ArenaScope&) = delete;
 };
+struct NoArena : ArenaScope {  // ... device allocations of their own: buffers that come after the handle's init and may grow
+    NoArena() : ArenaScope(nullptr) {}
+};
 
 // Uploads of a handle under construction go through pinned staging when they are SMALL.  hipMemcpyAsync from pageable
 // memory blocks the caller for the whole transfer and every array is followed by a stream synchronisation: a create issues
@@ -545,6 +548,23 @@ inline void staged_d2h(void* dst, const void* src, size_t bytes, hipStream_t st)
     }
     block_cache().give(pin, got, dev, true);
     HIP_CHECK(e);
+}
+
+// The schedule of a gated iteration queued on a stream: 16 iterations, then 32 at a time, never beyond max_iters.  step()
+// queues one iteration; after each chunk the launch error is checked and all_done() -- ONE host read of the done words --
+// says whether anything is left to do.  A solve that ends early has queued at most one chunk of iterations whose kernels
+// find their done words raised and return.
+template <class Step, class AllDone>
+inline void queue_in_chunks(int max_iters, Step step, AllDone all_done) {
+    int queued = 0;
+    bool done = false;
+    while (!done && queued < max_iters) {
+        const int chunk = std::min(max_iters - queued, queued == 0 ? 16 : 32);
+        for (int j = 0; j < chunk; ++j) step();
+        queued += chunk;
+        HIP_CHECK(hipGetLastError());
+        done = all_done();
+    }
 }
 
 __global__ __launch_bounds__(256) void k_zero16(uint4* __restrict__ p, size_t n16) {
@@ -2375,7 +2395,27 @@ struct HipBackend {
             hipLaunchKernelGGL(k_join_schur<BS>, dim3((unsigned)((n_join_chains + 63) / 64)), dim3(64), 0, stream, ja, n_join_chains);
         });
     }
-    double* join_vec_zb = nullptr;  // the separators' solutions of an INIT over several vectors, when the caller brings the buffer (score_marginals.hpp)
+    double* join_vec_zb = nullptr;  // the separators' solutions of an INIT over several vectors, when the caller brings the buffer (precondition_block)
+    // z = M^-1 r of K's chain preconditioner on a block of n_vec vectors, vector c at c * stride, in one launch of the chain
+    // kernel at depth join: chains, the second level of score_join.hpp, Jacobi on the remaining columns; no loop-closure
+    // correction (the marginals, the spectrum and the group iteration need one fixed SPD operator, no more).  scratch: a
+    // block the launch may write and nobody reads (its direction, solution and carried product); w: any block to read;
+    // done: a word that stays zero; rz_out: the launch's own partials of r'z, [c * n_prec + item]; zb: the separators'
+    // solutions of the block, bs * n_join_seps doubles per vector (may be null for one vector).
+    void precondition_block(double* r, double* z, double* scratch, const double* w, int n_vec, long long stride, int32_t* done,
+                            double* rz_out, double* zb) {
+        PrecArgs pa = prec_args(Kset);
+        pa.done = done;
+        prec_vectors(pa, r, r, z, scratch, w, scratch, scratch, nullptr);
+        pa.rz_in = nullptr; pa.rz_out = rz_out;
+        if (n_vec > 1) { pa.n_vec = n_vec; pa.vec_stride = stride; }
+        struct ZbScope {  // (the launch reads the member; it is null again whichever way the call ends)
+            HipBackend& be;
+            ZbScope(HipBackend& b, double* zb) : be(b) { be.join_vec_zb = zb; }
+            ~ZbScope() { be.join_vec_zb = nullptr; }
+        } zb_scope(*this, zb);
+        launch_prec<PREC_INIT>(Kset, pa, -1, PrecDepth::join);
+    }
     template <int MODE>
     void join_apply(const PrecSet& S, const PrecArgs& pa) {
         JoinArgs ja = join_args(S);
@@ -3255,13 +3295,11 @@ struct HipBackend {
         pcg_begin(q);
         q.pa.gate_flag = lin_flag.d; q.pa.gate_tol2 = lin_tol2.d; q.pa.gate_ref = lin_ref.d;
         int32_t state[2] = {0, 0};
-        while (!state[0] && q.queued < max_iters) {
-            const int chunk = std::min(max_iters - q.queued, q.queued == 0 ? 16 : 32);
-            for (int j = 0; j < chunk; ++j) pcg_step(q);
-            HIP_CHECK(hipGetLastError());
+        queue_in_chunks(max_iters, [&]() { pcg_step(q); }, [&]() {
             HIP_CHECK(hipMemcpyAsync(state, lin_flag.d, sizeof(state), hipMemcpyDeviceToHost, stream));
             HIP_CHECK(sync_stream(stream));
-        }
+            return state[0] != 0;
+        });
         if (used_out) *used_out = state[1];
         return state[0] != 0;
     }
@@ -4310,11 +4348,12 @@ struct score_refine {
 
 #include "score_gn_batch.hpp"
 #include "score_gn_robust_batch.hpp"
+#include "score_group_pcg.hpp"
 #include "score_marginals_batch.hpp"
 
 // Local refinement of a group of graphs in lock-step (score_gn_batch.hpp): the union state, blocks and gathers here, the
 // chain factorisation and M^-1 through the linear-mode handle `lin` on the union pattern, the per-member conjugate-gradient
-// iteration in the k_gb_* kernels.  This struct is the backend of gb_lock_step.
+// iteration in score_group_pcg.hpp.  This struct is the backend of gb_lock_step.
 struct score_refine_batch {
     score::GbUnion U;
     score_handle* lin = nullptr;
@@ -4324,10 +4363,10 @@ struct score_refine_batch {
     DevBuf<score::GbMember> members;
     DevBuf<int4> tiles;
     DevBuf<int32_t> mblk_member, ublk_member, sblk_member, rblk_member, rel_i, rel_j, rng_a, rng_b, pri_l, hc_ptr, hc_slot, gc_ptr, gc_slot, diag_member;
-    DevBuf<int32_t> mask, flags;  // flags: [done per member | steps per member | a zero (the chain kernel's done word)]
+    DevBuf<int32_t> mask;
     DevBuf<double> rel_t, rel_R, rel_kappa, rel_tau, rng_dist, rng_prec, pri_t, pri_prec;
     DevBuf<double> X, Xt, hblk, gblk, rhs, cost_part, gmax_part, lambda;
-    DevBuf<double> x, r, z, p, w, scratch, pw_part, rz0, rz1, rz_prec, ref;
+    score::GroupPcgWork pcg;  // the damped step: one slot of the group's iteration, its solution in pcg.x
     int n_mblocks = 0, n_ublocks = 0, n_sblocks = 0, n_hblocks = 0, n_tiles = 0;
     long long nnz = 0;
     std::vector<double> part_host;
@@ -4387,16 +4426,9 @@ struct score_refine_batch {
         X.alloc((size_t)U.state_size); Xt.alloc((size_t)U.state_size);
         hblk.alloc((size_t)std::max<long long>(1, U.hblk_size)); gblk.alloc((size_t)std::max<long long>(1, U.gblk_size));
         cost_part.alloc((size_t)n_mblocks); gmax_part.alloc((size_t)n_ublocks); lambda.alloc(G);
-        mask.alloc(G); flags.alloc(2 * G + 1);
-        DevBuf<double>* vecs[] = {&rhs, &x, &r, &z, &p, &w, &scratch};
-        for (DevBuf<double>* v : vecs) { v->alloc(n); v->zero(stream()); }
-        pw_part.alloc((size_t)n_tiles); pw_part.zero(stream());
-        rz0.alloc((size_t)n_ublocks); rz0.zero(stream());
-        rz1.alloc((size_t)n_ublocks); rz1.zero(stream());
-        // (every workgroup of a chain-kernel launch has a slot for its partial of r'z: written, never read here)
-        rz_prec.alloc((size_t)be().n_prec + 4096); rz_prec.zero(stream());
-        ref.alloc(G); ref.zero(stream());
-        flags.zero(stream());
+        mask.alloc(G);
+        rhs.alloc(n); rhs.zero(stream());
+        pcg.reserve(1, 1, G, n, (size_t)n_tiles, (size_t)n_ublocks, (size_t)be().n_prec, stream());
         be().linear_buffers(lin->solver.H);
         HIP_CHECK(sync_stream(stream()));
         // the lists live on the device now (the precisions a robust run re-weights stay: its checks and prec0 read them)
@@ -4455,10 +4487,10 @@ struct score_refine_batch {
     void trial(const std::vector<char>& m) {
         set_mask(m);
         if (U.dim == 2)
-            hipLaunchKernelGGL(score::k_gb_trial<2>, dim3(n_sblocks), dim3(kThreads), 0, stream(), dev(), (const double*)X.d, (const double*)x.d,
+            hipLaunchKernelGGL(score::k_gb_trial<2>, dim3(n_sblocks), dim3(kThreads), 0, stream(), dev(), (const double*)X.d, (const double*)pcg.x.d,
                                Xt.d, (const int32_t*)mask.d);
         else
-            hipLaunchKernelGGL(score::k_gb_trial<3>, dim3(n_sblocks), dim3(kThreads), 0, stream(), dev(), (const double*)X.d, (const double*)x.d,
+            hipLaunchKernelGGL(score::k_gb_trial<3>, dim3(n_sblocks), dim3(kThreads), 0, stream(), dev(), (const double*)X.d, (const double*)pcg.x.d,
                                Xt.d, (const int32_t*)mask.d);
     }
     void accept(const std::vector<char>& m) {  // the trial point of the masked members becomes their current one
@@ -4478,62 +4510,30 @@ struct score_refine_batch {
         hipLaunchKernelGGL(score::k_gb_gather_h, dim3(n_hblocks), dim3(kThreads), 0, st, (const int32_t*)hc_ptr.d, (const int32_t*)hc_slot.d,
                            (const double*)hblk.d, (const int32_t*)diag_member.d, (const double*)lambda.d, be().K0d.d, nnz);
     }
-    // (J'J + lambda_g I) step = -g on the masked members, the steps left in x; ok / used per masked member
+    // the union, its matrix and its tiles as the kernels of score_group_pcg.hpp see them
+    score::GbmArgs pcg_args() {
+        score::GbmArgs a{};
+        a.d = dev();
+        a.ptr = be().Kset.mat.ptr.d; a.col = be().Kset.mat.col.d; a.val = be().Kset.mat.val.d;
+        a.tiles = tiles.d; a.n_tiles = n_tiles; a.n_ublocks = n_ublocks; a.n = U.n;
+        return a;
+    }
+    // (J'J + lambda_g I) step = -g on the masked members, the steps left in pcg.x; ok / used per masked member
     void solve(const std::vector<char>& m, const double* lam, double rel_tol, char* ok, int32_t* used) {
         const int G = U.count;
-        HipBackend& b = be();
         hipStream_t st = stream();
         gather_h(lam);
-        b.derive_rho_data(false);  // K = K0, its chain factors and Jacobi inverses, for the whole group
-        word_host.assign((size_t)(2 * G + 1), 0);
+        be().derive_rho_data(false);  // K = K0, its chain factors and Jacobi inverses, for the whole group
+        word_host.assign((size_t)(2 * G + 1), 0);  // (steps and the chain kernel's done word: zero)
         for (int g = 0; g < G; ++g) word_host[(size_t)g] = m[(size_t)g] ? 0 : 1;
-        HIP_CHECK(hipMemcpyAsync(flags.d, word_host.data(), word_host.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(pcg.flags.d, word_host.data(), word_host.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
         HIP_CHECK(sync_stream(st));
-        score::GbPcg a{};
-        a.d = dev();
-        a.ptr = b.Kset.mat.ptr.d; a.col = b.Kset.mat.col.d; a.val = b.Kset.mat.val.d;
-        a.tiles = tiles.d; a.done = flags.d; a.iters = flags.d + G;
-        a.x = x.d; a.r = r.d; a.z = z.d; a.p = p.d; a.w = w.d; a.rhs = rhs.d; a.pw_part = pw_part.d;
-        a.tol2 = rel_tol * rel_tol; a.ref = ref.d;
-        const dim3 gu((unsigned)n_ublocks), gt((unsigned)n_tiles), bt(kThreads);
-        auto precondition = [&]() {  // z = M^-1 r over the whole group (score_marginals.hpp's use of the chain kernel, one vector)
-            PrecArgs pa = b.prec_args(b.Kset);
-            pa.done = flags.d + 2 * G;
-            b.prec_vectors(pa, r.d, r.d, z.d, scratch.d, w.d, scratch.d, scratch.d, nullptr);
-            pa.rz_in = nullptr; pa.rz_out = rz_prec.d;
-            b.launch_prec<PREC_INIT>(b.Kset, pa, -1, HipBackend::PrecDepth::join);
+        score::GbmArgs a = pcg_args();
+        a.tol2 = rel_tol * rel_tol;
+        auto begin = [&](const score::GbmArgs& b) {
+            hipLaunchKernelGGL(score::k_gb_pcg_begin, dim3((unsigned)n_ublocks), dim3(kThreads), 0, st, b, (const double*)rhs.d);
         };
-        double* rz_cur = rz0.d; double* rz_nxt = rz1.d;
-        hipLaunchKernelGGL(score::k_gb_pcg_begin, gu, bt, 0, st, a);
-        precondition();
-        a.rz_part = rz_cur;
-        hipLaunchKernelGGL(score::k_gb_rz, gu, bt, 0, st, a);
-        a.first = 1; a.rz_new = rz_cur; a.rz_old = nullptr;
-        hipLaunchKernelGGL(score::k_gb_direction, gu, bt, 0, st, a);
-        a.first = 0;
-        const int max_iters = 4000;
-        int queued = 0;
-        bool all_done = false;
-        while (!all_done && queued < max_iters) {
-            const int chunk = std::min(max_iters - queued, queued == 0 ? 16 : 32);
-            for (int j = 0; j < chunk; ++j) {
-                hipLaunchKernelGGL(score::k_gb_product, gt, bt, 0, st, a);
-                a.rz_new = rz_cur;
-                hipLaunchKernelGGL(score::k_gb_step, gu, bt, 0, st, a);
-                precondition();
-                a.rz_part = rz_nxt;
-                hipLaunchKernelGGL(score::k_gb_rz, gu, bt, 0, st, a);
-                a.rz_new = rz_nxt; a.rz_old = rz_cur;
-                hipLaunchKernelGGL(score::k_gb_direction, gu, bt, 0, st, a);
-                std::swap(rz_cur, rz_nxt);
-            }
-            queued += chunk;
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipMemcpyAsync(word_host.data(), flags.d, (size_t)(2 * G) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            HIP_CHECK(sync_stream(st));
-            all_done = true;
-            for (int g = 0; g < G; ++g) all_done = all_done && word_host[(size_t)g] != 0;
-        }
+        score::group_pcg(be(), a, pcg, 1, 4000, nullptr, begin, word_host);
         for (int g = 0; g < G; ++g) {
             if (!m[(size_t)g]) continue;
             ok[g] = word_host[(size_t)g] == 1 ? 1 : 0;

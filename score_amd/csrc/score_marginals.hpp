@@ -4,15 +4,17 @@
 //
 // What exists already and is used as it is: the per-measurement blocks (k_gn_blocks<DIM>), the gather of H on the
 // linear-mode handle's pattern (k_gn_gather_h, lambda = 0), the chain factorisation (derive_rho_data -> k_factor) and the
-// application of M^-1 to several vectors in one launch (launch_prec<PREC_INIT> with PrecArgs::n_vec: chains, the second
-// level of score_join.hpp, Jacobi on the landmark columns; the loop-closure correction is left out -- the preconditioner
-// only has to be one fixed SPD operator for the whole solve).  New here: the product over several vectors and the
-// vector updates of the block.
+// application of M^-1 to several vectors in one launch (HipBackend::precondition_block: chains, the second level of
+// score_join.hpp, Jacobi on the landmark columns; the loop-closure correction is left out -- the preconditioner only has to
+// be one fixed SPD operator for the whole solve).  New here: the product over several vectors and the vector updates of the
+// block.  Shared with the group's iteration (score_group_pcg.hpp) and the spectrum (score_spectrum.hpp): the tiles and the
+// product of one tile (mv_tiles, mv_product_tile), the slot counts (mv_slots, mv_with_slots), the breakdown test
+// (pcg_finite) and the variables' unknowns (mv_variable_unknowns).
 //
 // Vectors of a block are stored one after the other, stride n (the layout PrecArgs::vec_stride expects).  One iteration:
 //   k_mv_product    w_c = H p_c for every live column from ONE pass over the CSR matrix, per-workgroup partials of p_c'w_c
 //   k_mv_step       alpha_c = r'z / p'w (both re-reduced from the partials in a fixed order), x_c += alpha p_c, r_c -= alpha w_c
-//   launch_prec     z_c = M^-1 r_c, partials of r_c'z_c
+//   M^-1            z_c = M^-1 r_c and the chain kernel's own partials of r_c'z_c (precondition_block)
 //   k_mv_direction  beta = r'z_new / r'z_old, p_c = z_c + beta p_c; the gate r'z_new <= rel_tol^2 r0'z0 raises the column's
 //                   done word (the stopping rule of score_linear_solve)
 // Every kernel tests the column's done word first and leaves a done column's x, r and p as they are (the chain kernel
@@ -25,8 +27,11 @@
 // ONE long row spread over the workgroup and reduced through LDS.
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/score_marginals.h"
@@ -35,7 +40,7 @@
 namespace score {
 
 constexpr int kMvMaxWidth = 16;                  // columns of a block
-constexpr int kMvThreads = 256;
+constexpr int kMvThreads = kThreads;
 constexpr int kMvLanes = 4;                      // lanes of a short row
 constexpr int kMvRows = kMvThreads / kMvLanes;   // short rows of a tile
 constexpr int kMvLongRow = 128;                  // entries beyond which a row is a tile of its own
@@ -66,11 +71,26 @@ struct MvArgs {
     double* joint;             // C x C
 };
 
-__device__ __forceinline__ bool mv_finite(double v) { return fabs(v) <= 1.79769313486231570e308; }
+// (the breakdown test of every gated iteration here and in score_group_pcg.hpp: neither infinite nor NaN)
+__device__ __forceinline__ bool pcg_finite(double v) { return fabs(v) <= 1.79769313486231570e308; }
+
+// the slots a block of `most` live columns runs in, and f(std::integral_constant<int, NV>) for that count: the product kernels
+// are compiled for 1, 2, 4, 8 and 16 vectors
+inline int mv_slots(int most) { return most <= 1 ? 1 : most <= 2 ? 2 : most <= 4 ? 4 : most <= 8 ? 8 : 16; }
+template <class F>
+inline void mv_with_slots(int NV, F f) {
+    switch (NV) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        case 8: f(std::integral_constant<int, 8>{}); break;
+        default: f(std::integral_constant<int, 16>{}); break;
+    }
+}
 
 // The product of one tile: w_c = H p_in_c for the columns of `live`, the tile's partial of p_in_c'w_c into
 // pw_part[c * part_stride + part_slot].  Stated once: k_mv_product (the columns of one graph) and k_gbm_product
-// (score_marginals_batch.hpp: the slots of the tile's member inside a union) call it with their live mask and partial slot.
+// (score_group_pcg.hpp: the slots of the tile's member inside a union) call it with their live mask and partial slot.
 // NV: vectors of the block (compile time: the sums live in registers).  red: (kMvThreads / 64) * NV doubles of LDS.  Every
 // lane of the workgroup enters with the same tile and the same (non-empty) mask.
 template <int NV>
@@ -159,7 +179,7 @@ __global__ __launch_bounds__(kMvThreads) void k_mv_step(MvArgs a) {
     for (int i = t; i < a.n_tiles; i += kMvThreads) pw += a.pw_part[(size_t)c * a.n_tiles + i];
     block_sum2(rz, pw, red);
     const bool lead = blockIdx.x == 0 && t == 0;
-    if (!(mv_finite(rz) && mv_finite(pw) && pw > 0.0)) {
+    if (!(pcg_finite(rz) && pcg_finite(pw) && pw > 0.0)) {
         if (lead) a.flags[kMvDone + c] = 2;
         return;
     }
@@ -187,13 +207,13 @@ __global__ __launch_bounds__(kMvThreads) void k_mv_direction(MvArgs a) {
     const bool lead = blockIdx.x == 0 && t == 0;
     double beta = 0.0;
     if (a.first) {
-        if (!(mv_finite(rzn) && rzn > 0.0)) {  // (a zero right-hand side is solved by x = 0; anything else is no SPD preconditioner)
+        if (!(pcg_finite(rzn) && rzn > 0.0)) {  // (a zero right-hand side is solved by x = 0; anything else is no SPD preconditioner)
             if (lead) a.flags[kMvDone + c] = rzn == 0.0 ? 1 : 2;
             return;
         }
         if (lead) a.ref[c] = a.tol2 * rzn;
     } else {
-        if (!(mv_finite(rzn) && rzo > 0.0)) {
+        if (!(pcg_finite(rzn) && rzo > 0.0)) {
             if (lead) a.flags[kMvDone + c] = 2;
             return;
         }
@@ -244,35 +264,41 @@ __global__ __launch_bounds__(kMvThreads) void k_mv_gather(MvArgs a) {
     if (s < a.C) a.joint[s * a.C + a.c0 + c] = a.x[c * a.n + a.sel[s]];
 }
 
-// the product's tiles from the row pointers
-inline void mv_tiles(const std::vector<int32_t>& ptr, int64_t n, std::vector<int4>& tiles) {
-    tiles.clear();
+// the product's tiles {first row, end row, long row?, member} from the row pointers of a graph's n rows, appended; row0:
+// where the graph's rows start (a member of a union, score_gn_batch.hpp: its first unknown)
+inline void mv_tiles(const std::vector<int32_t>& ptr, int64_t n, std::vector<int4>& tiles, int64_t row0 = 0, int member = 0) {
     auto len = [&](int64_t i) { return ptr[(size_t)i + 1] - ptr[(size_t)i]; };
     int64_t row = 0;
     while (row < n) {
-        if (len(row) > kMvLongRow) { tiles.push_back(make_int4((int)row, (int)row + 1, 1, 0)); ++row; continue; }
+        if (len(row) > kMvLongRow) { tiles.push_back(make_int4((int)(row0 + row), (int)(row0 + row + 1), 1, member)); ++row; continue; }
         int64_t end = row;
         while (end < n && end - row < kMvRows && len(end) <= kMvLongRow) ++end;
-        tiles.push_back(make_int4((int)row, (int)end, 0, 0));
+        tiles.push_back(make_int4((int)(row0 + row), (int)(row0 + end), 0, member));
         row = end;
     }
 }
 
-// the unknowns of the selected variables, in the order of include/score_marginals.h
-inline void mv_columns(const GnProblem& P, const int32_t* vars, int32_t n_vars, std::vector<int32_t>& sel) {
-    if (!vars || n_vars <= 0) throw std::runtime_error("score_refine_marginals: no variables");
-    std::vector<char> seen((size_t)(P.Np + P.Nl), 0);
-    sel.clear();
+// The unknowns of the selected variables of one graph -- Np poses of dp unknowns each (pose 0 is fixed), then Nl landmarks of
+// dim -- appended to sel in the order of include/score_marginals.h.  who: the entry point's words in front of a message.
+inline void mv_variable_unknowns(int64_t Np, int64_t Nl, int dp, int dim, const int32_t* vars, int32_t n_vars, const std::string& who,
+                                 std::vector<int32_t>& sel) {
+    std::vector<char> seen((size_t)(Np + Nl), 0);
     for (int32_t k = 0; k < n_vars; ++k) {
         const int64_t v = vars[k];
-        if (v < 0 || v >= P.Np + P.Nl) throw std::runtime_error("score_refine_marginals: variable out of range");
-        if (v == 0) throw std::runtime_error("score_refine_marginals: pose 0 is fixed, it has no covariance");
-        if (seen[(size_t)v]) throw std::runtime_error("score_refine_marginals: a variable is listed twice");
+        if (v < 0 || v >= Np + Nl) throw std::runtime_error(who + "variable out of range");
+        if (v == 0) throw std::runtime_error(who + "pose 0 is fixed, it has no covariance");
+        if (seen[(size_t)v]) throw std::runtime_error(who + "a variable is listed twice");
         seen[(size_t)v] = 1;
-        const int64_t first = v < P.Np ? P.pose_col(v) : (int64_t)P.dp() * (P.Np - 1) + (int64_t)P.dim * (v - P.Np);
-        const int cnt = v < P.Np ? P.dp() : P.dim;
+        const int64_t first = v < Np ? (int64_t)dp * (v - 1) : (int64_t)dp * (Np - 1) + (int64_t)dim * (v - Np);
+        const int cnt = v < Np ? dp : dim;
         for (int a = 0; a < cnt; ++a) sel.push_back((int32_t)(first + a));
     }
+}
+
+inline void mv_columns(const GnProblem& P, const int32_t* vars, int32_t n_vars, std::vector<int32_t>& sel) {
+    if (!vars || n_vars <= 0) throw std::runtime_error("score_refine_marginals: no variables");
+    sel.clear();
+    mv_variable_unknowns(P.Np, P.Nl, P.dp(), P.dim, vars, n_vars, "score_refine_marginals: ", sel);
 }
 
 // The block's buffers: they stay with the refinement handle between calls (device allocations of their own, not the
@@ -284,11 +310,7 @@ struct MvWork {
     int n_tiles = 0;
     void reserve(const GnProblem& P, int n_prec, int zb_per_vector, hipStream_t st) {
         if (x.d) return;
-        struct NoArena {
-            DevArena* keep;
-            NoArena() : keep(tl_arena) { tl_arena = nullptr; }
-            ~NoArena() { tl_arena = keep; }
-        } no_arena;
+        NoArena no_arena;
         std::vector<int4> t;
         mv_tiles(P.hptr, P.n, t);
         n_tiles = (int)t.size();
@@ -331,17 +353,13 @@ int mv_solve(Refine& R, const double* poses, const double* landmarks, const int3
     if (!seq && be.split.active) throw std::runtime_error("score_refine_marginals: blocks of columns need the unsplit chain kernel (chain_split = 0)");
     if (!seq && be.n_prec == 0) throw std::runtime_error("score_refine_marginals: the handle has no preconditioner work (no unknowns?)");
     if (!seq) be.derive_rho_data(false);
-    const int NV = seq ? 1 : (block_width <= 1 ? 1 : block_width <= 2 ? 2 : block_width <= 4 ? 4 : block_width <= 8 ? 8 : 16);
+    const int NV = seq ? 1 : mv_slots(block_width);
     auto& W = R.mv;
     W.reserve(P, be.n_prec, be.H->bs * be.n_join_seps, st);
     DevBuf<int32_t> d_sel;
     DevBuf<double> d_joint;
     {
-        struct NoArena {
-            DevArena* keep;
-            NoArena() : keep(tl_arena) { tl_arena = nullptr; }
-            ~NoArena() { tl_arena = keep; }
-        } no_arena;
+        NoArena no_arena;
         d_sel.alloc((size_t)C); d_joint.alloc((size_t)C * (size_t)C);
     }
     staged_h2d(d_sel.d, sel.data(), (size_t)C * sizeof(int32_t), st);
@@ -353,25 +371,13 @@ int mv_solve(Refine& R, const double* poses, const double* landmarks, const int3
     a.n_prec = be.n_prec; a.tol2 = rel_tol * rel_tol; a.ref = W.ref.d;
     a.sel = d_sel.d; a.C = C; a.res_part = W.res_part.d; a.joint = d_joint.d;
     auto product = [&](const MvArgs& m) {
-        const dim3 g((unsigned)m.n_tiles), b(kMvThreads);
-        switch (NV) {
-            case 1: hipLaunchKernelGGL(k_mv_product<1>, g, b, 0, st, m); break;
-            case 2: hipLaunchKernelGGL(k_mv_product<2>, g, b, 0, st, m); break;
-            case 4: hipLaunchKernelGGL(k_mv_product<4>, g, b, 0, st, m); break;
-            case 8: hipLaunchKernelGGL(k_mv_product<8>, g, b, 0, st, m); break;
-            default: hipLaunchKernelGGL(k_mv_product<16>, g, b, 0, st, m); break;
-        }
+        mv_with_slots(NV, [&](auto nv) {
+            hipLaunchKernelGGL(k_mv_product<decltype(nv)::value>, dim3((unsigned)m.n_tiles), dim3(kMvThreads), 0, st, m);
+        });
     };
-    // z = M^-1 r of every column of the block, partials of r'z into `rz`
+    // z = M^-1 r of every column of the block, the chain kernel's partials of r'z into `rz`
     auto precondition = [&](double* rz) {
-        PrecArgs pa = be.prec_args(be.Kset);
-        pa.done = W.flags.d + kMvZero;
-        be.prec_vectors(pa, W.r.d, W.r.d, W.z.d, W.p_scratch.d, W.w.d, W.p_scratch.d, W.p_scratch.d, nullptr);
-        pa.rz_in = nullptr; pa.rz_out = rz;
-        if (NV > 1) { pa.n_vec = NV; pa.vec_stride = n; }
-        be.join_vec_zb = W.zb.d;
-        be.launch_prec<PREC_INIT>(be.Kset, pa, -1, HipBackend::PrecDepth::join);
-        be.join_vec_zb = nullptr;
+        be.precondition_block(W.r.d, W.z.d, W.p_scratch.d, W.w.d, NV, n, W.flags.d + kMvZero, rz, W.zb.d);
     };
     const double t1 = now_ms();
     std::vector<int32_t> flags((size_t)kMvFlagWords), col_done((size_t)C, 0), col_iters((size_t)C, 0);
@@ -394,26 +400,19 @@ int mv_solve(Refine& R, const double* poses, const double* landmarks, const int3
             a.first = 1; a.rz_new = rz_cur; a.rz_old = nullptr;
             hipLaunchKernelGGL(k_mv_direction, dim3((unsigned)n_rblocks, (unsigned)NV), dim3(kMvThreads), 0, st, a);
             a.first = 0;
-            int queued = 0;
-            bool all_done = false;
-            while (!all_done && queued < max_iters) {
-                const int chunk = std::min(max_iters - queued, queued == 0 ? 16 : 32);
-                for (int j = 0; j < chunk; ++j) {
-                    a.all_columns = 0; a.p_in = W.p.d;
-                    product(a);
-                    a.rz_new = rz_cur;
-                    hipLaunchKernelGGL(k_mv_step, dim3((unsigned)n_rblocks, (unsigned)NV), dim3(kMvThreads), 0, st, a);
-                    precondition(rz_nxt);
-                    a.rz_new = rz_nxt; a.rz_old = rz_cur;
-                    hipLaunchKernelGGL(k_mv_direction, dim3((unsigned)n_rblocks, (unsigned)NV), dim3(kMvThreads), 0, st, a);
-                    std::swap(rz_cur, rz_nxt);
-                }
-                queued += chunk;
-                HIP_CHECK(hipGetLastError());
+            queue_in_chunks(max_iters, [&]() {
+                a.all_columns = 0; a.p_in = W.p.d;
+                product(a);
+                a.rz_new = rz_cur;
+                hipLaunchKernelGGL(k_mv_step, dim3((unsigned)n_rblocks, (unsigned)NV), dim3(kMvThreads), 0, st, a);
+                precondition(rz_nxt);
+                a.rz_new = rz_nxt; a.rz_old = rz_cur;
+                hipLaunchKernelGGL(k_mv_direction, dim3((unsigned)n_rblocks, (unsigned)NV), dim3(kMvThreads), 0, st, a);
+                std::swap(rz_cur, rz_nxt);
+            }, [&]() {
                 staged_d2h(flags.data(), W.flags.d, (size_t)kMvFlagWords * sizeof(int32_t), st);
-                all_done = true;
-                for (int c = 0; c < NV; ++c) all_done = all_done && flags[(size_t)(kMvDone + c)] != 0;
-            }
+                return std::all_of(flags.begin() + kMvDone, flags.begin() + kMvDone + NV, [](int32_t f) { return f != 0; });
+            });
         }
         // the true residual of every column of the block (one more product, w = H x), the rows of S
         a.all_columns = 1; a.p_in = W.x.d;

@@ -3,8 +3,8 @@
 //
 // What exists already and is used as it is: the per-measurement blocks and the gather of H on the linear-mode handle's
 // pattern (gather_h(sigma)), the chain factorisation (derive_rho_data), the application of M^-1 to 16 vectors in one launch
-// (launch_prec<PREC_INIT>, PrecArgs::n_vec = 16, depth join, no loop-closure correction -- set up exactly as mv_solve's
-// `precondition` in score_marginals.hpp) and the product over 16 vectors (k_mv_product<16>, all_columns = 1).  M is the chain
+// (HipBackend::precondition_block, which mv_solve of score_marginals.hpp calls too: depth join, no loop-closure
+// correction) and the product over 16 vectors (k_mv_product<16>, all_columns = 1).  M is the chain
 // part of A -- tridiagonal pose blocks per chain, diagonal blocks of the landmarks -- and exists for a singular H because of
 // the shift.  New here: the Gram kernel, the combine kernel, and the small kernels around them (start block, residuals,
 // done words, max diag H).
@@ -250,11 +250,7 @@ struct SpWork {
     int n_tiles = 0, n_rblocks = 0, n_row_tiles = 0, n_gram_wgs = 0, n_hblocks = 0;
     void reserve(const GnProblem& P, int n_prec, int zb_per_vector, int hblocks, hipStream_t st) {
         if (x.d) return;
-        struct NoArena {
-            DevArena* keep;
-            NoArena() : keep(tl_arena) { tl_arena = nullptr; }
-            ~NoArena() { tl_arena = keep; }
-        } no_arena;
+        NoArena no_arena;
         std::vector<int4> t;
         mv_tiles(P.hptr, P.n, t);
         n_tiles = (int)t.size();
@@ -329,15 +325,8 @@ int sp_solve(Refine& R, const double* poses, const double* landmarks, int32_t k,
         m.p_in = in; m.w = out;
         hipLaunchKernelGGL(k_mv_product<kSpBlock>, dim3((unsigned)W.n_tiles), dim3(kMvThreads), 0, st, m);
     };
-    auto precondition = [&]() {  // W = M^-1 R, as mv_solve's
-        PrecArgs pa = be.prec_args(be.Kset);
-        pa.done = W.flags.d + kSpBlock;
-        be.prec_vectors(pa, W.r.d, W.r.d, W.w.d, W.p_scratch.d, W.aw.d, W.p_scratch.d, W.p_scratch.d, nullptr);
-        pa.rz_in = nullptr; pa.rz_out = W.rz.d;
-        pa.n_vec = kSpBlock; pa.vec_stride = n;
-        be.join_vec_zb = W.zb.d;
-        be.launch_prec<PREC_INIT>(be.Kset, pa, -1, HipBackend::PrecDepth::join);
-        be.join_vec_zb = nullptr;
+    auto precondition = [&]() {  // W = M^-1 R
+        be.precondition_block(W.r.d, W.w.d, W.p_scratch.d, W.aw.d, kSpBlock, n, W.flags.d + kSpBlock, W.rz.d, W.zb.d);
     };
     const dim3 g16((unsigned)W.n_rblocks, (unsigned)kSpBlock), g2((unsigned)W.n_rblocks, 2u), blk(kMvThreads);
     auto gram = [&]() {

@@ -153,3 +153,26 @@ def check_columns(ref, cols, A, rho, label):
     worst = int(np.argmax(err - bound))
     assert np.all(err <= bound), f"{label}: column {worst}: error {err[worst]:.3e} > bound {bound[worst]:.3e}"
     return figures, bound, delta
+
+
+def check_iteration_caps(run, label):
+    """The chunk boundaries of the queued iteration (16 iterations, then 32 at a time, never beyond max_iters).
+    ``run(max_iters)`` -> (return code, [(A, residuals, steps, converged), ...]) on ONE handle.  The full run converges
+    everywhere with step counts s; under a cap below max(s) -- max(s) - 1, and 16 and 17 where they are below max(s) -- a
+    column with s_c <= cap is the full run's bit for bit, one beyond it reports -(cap + 1) and the call returns 1."""
+    rc, full = run(4000)
+    assert rc == 0 and all(np.all(conv) for *_, conv in full), f"{label}: the full run did not converge"
+    top = max(int(steps.max()) for _, _, steps, _ in full)
+    caps = sorted({top - 1} | {c for c in (16, 17) if c < top})
+    print(f"{label}: max(s) = {top}, caps {caps}, steps {[steps.tolist() for _, _, steps, _ in full]}")
+    assert caps[0] >= 1
+    for cap in caps:
+        rc_c, capped = run(cap)
+        assert rc_c == 1, f"{label}, cap {cap}: return code {rc_c}"
+        for (A, res, steps, _), (A_c, res_c, steps_c, conv_c) in zip(full, capped):
+            reported = np.where(conv_c, steps_c, -(steps_c + 1))  # (what the C entry point wrote)
+            within = steps <= cap
+            assert np.array_equal(reported[within], steps[within]), f"{label}, cap {cap}: {reported} against {steps}"
+            assert np.all(reported[~within] == -(cap + 1)), f"{label}, cap {cap}: {reported} against {steps}"
+            assert np.array_equal(A_c[:, within], A[:, within]) and np.array_equal(res_c[within], res[within])
+    return top

@@ -18,7 +18,7 @@ from score_amd.refine import _initial_point, _Problem, _Problem3D, refine_estima
 
 MILD = (0.02, 0.1)    # sigma_theta, sigma_t of the start point around the truth
 ROUGH = (0.6, 1.5)
-TILE_ROWS, LONG_ROW = 64, 128  # of the product kernel (csrc/score_gn_batch.hpp: kGbRows, kGbLongRow)
+TILE_ROWS, LONG_ROW = 64, 128  # of the product's tiles (csrc/score_marginals.hpp: kMvRows, kMvLongRow; mv_tiles cuts a member's too)
 
 SPECS_2D = {
     "A": dict(seed=5, n_robots=3, n_poses=40, n_beacons=3, p_range=0.4, n_loop_closures=4),

@@ -15,7 +15,8 @@ import functools
 import numpy as np
 import pytest
 
-from marginals_helpers import Reference, check_columns, landmark_names, pose_names, reference, undetermined_graph
+from marginals_helpers import (Reference, check_columns, check_iteration_caps, landmark_names, pose_names, reference,
+                               undetermined_graph)
 from marginals_helpers import noisy_truth as plain_noisy_truth
 from refine_batch_helpers import KEYS_2D, group, member, rough_start, twin_alone
 from score_amd.manhattan import make_manhattan
@@ -148,6 +149,15 @@ def test_segmented_chain_inside_a_union(hip_lib):
     cols, *_ = _check("1100 poses", ref, wanted, out[0][1])
     assert len(cols) == 10
     _check("C beside it", ref_of("C"), None, out[1][1])
+
+
+def test_iteration_cap_at_the_chunk_boundaries(hip_lib):
+    """(A, C) at width 4 under max_iters at and around the boundaries of the queued chunks: see check_iteration_caps."""
+    keys = ("A", "C")
+    probs, points = zip(*[_problem_and_point(member(k)[0], twin_alone(k)[0], None, None) for k in keys])
+    ids = [_select(p, None)[1] for p in probs]
+    with RefineBatchHandle(probs, hip_lib) as h:
+        check_iteration_caps(lambda cap: h.marginals(list(points), ids, max_iters=cap, block_width=4)[:2], "(A, C), width 4")
 
 
 def test_undetermined_member_is_a_verdict_for_that_member_only(hip_lib):

@@ -4,9 +4,10 @@ library's own reported residual and the number format -- no tolerance is chosen.
 import numpy as np
 import pytest
 
-from marginals_helpers import (check_columns, graph_a, landmark_names, noisy_truth, pose_names, reference, two_pose_graph,
-                               undetermined_graph, Reference)
-from score_amd.marginals import _problem_and_point, _select, device_columns, marginal_covariances
+from marginals_helpers import (check_columns, check_iteration_caps, graph_a, landmark_names, noisy_truth, pose_names, reference,
+                               two_pose_graph, undetermined_graph, Reference)
+from refine_batch_helpers import member, twin_alone
+from score_amd.marginals import MarginalsHandle, _problem_and_point, _select, device_columns, marginal_covariances
 
 pytestmark = pytest.mark.gpu
 
@@ -91,6 +92,20 @@ def test_range_weights(hip_lib):
     plain = reference("a")[2]
     assert np.max(np.abs(ref.H - plain.H)) > 1e-3  # the three ranges matter
     _device("a, three ranges off", fg, results, ref, None, range_weights=w)
+
+
+def test_iteration_cap_at_the_chunk_boundaries(hip_lib):
+    """Member A of tests/refine_batch_helpers.py at width 4 under max_iters at and around the boundaries of the queued
+    chunks: see check_iteration_caps."""
+    prob, point = _problem_and_point(member("A")[0], twin_alone("A")[0], None, None)
+    ids = _select(prob, None)[1]
+
+    def run(cap):
+        rc, A, res, steps, converged, _ = h.columns(point, ids, max_iters=cap, block_width=4)
+        return rc, [(A, res, steps, converged)]
+
+    with MarginalsHandle(prob, hip_lib) as h:
+        check_iteration_caps(run, "A, width 4")
 
 
 def test_undetermined_variable_is_a_verdict(hip_lib):
