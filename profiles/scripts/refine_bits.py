@@ -2,6 +2,8 @@
 bit-for-bit comparison of two builds of the library (a refactor of their kernels or drivers must not move one bit).
 
   python profiles/scripts/refine_bits.py OUT.npz [--lib PATH]        record
+  python profiles/scripts/refine_bits.py OUT.npz --engine python     record the refinement runs only, with engine="python" and
+                                                                      SciPy's sparse LU: needs no library and no device
   python profiles/scripts/refine_bits.py --compare A.npz B.npz        compare two records with array_equal (NaNs equal); exit 1
                                                                       if any entry differs or is missing
 
@@ -39,7 +41,7 @@ def flatten(prefix, value, out):
         out[prefix] = np.asarray(value)
 
 
-def record(lib):
+def record(lib, engine="native"):
     from refine_batch_helpers import KEYS_2D, arrays_of, group, member
     from refine_robust_batch_helpers import CLEAN3, SCHEDULE, THRESHOLD, graph
     from score_amd.refine import refine_estimate
@@ -48,6 +50,8 @@ def record(lib):
     from score_amd.refine_robust_batch import refine_estimate_robust_batch
 
     out = {}
+    single = dict(engine=engine, lib_path=lib, **({"linear_solver": "scipy"} if engine == "python" else {}))
+    batch = dict(engine=engine, lib_path=lib)
 
     def keep(name, fg, res, info):
         poses, lms = arrays_of(fg, res)
@@ -56,21 +60,23 @@ def record(lib):
 
     for k in KEYS_2D + ("3D0", "3D1"):
         fg, start = member(k)
-        keep(f"refine_estimate/{k}", fg, *refine_estimate(fg, start, engine="native", lib_path=lib))
+        keep(f"refine_estimate/{k}", fg, *refine_estimate(fg, start, **single))
     for keys in (KEYS_2D, ("3D0", "3D1")):
         fgs, starts = group(keys)
-        for k, fg, (res, info) in zip(keys, fgs, refine_estimate_batch(fgs, starts, lib_path=lib)):
+        for k, fg, (res, info) in zip(keys, fgs, refine_estimate_batch(fgs, starts, **batch)):
             keep(f"refine_estimate_batch/{'+'.join(keys)}/{k}", fg, res, info)
     for k in ("G1", "G2", "G3", "G4", CLEAN3):
         fg, start = graph(k)[:2]
         keep(f"refine_estimate_robust/{k}", fg, *refine_estimate_robust(fg, start, inlier_threshold=THRESHOLD[k], robust_loop_closures=True,
-                                                                        engine="native", lib_path=lib, **SCHEDULE[k]))
+                                                                        **single, **SCHEDULE[k]))
     for keys in (("G1", "G2", "G4"), ("G3", CLEAN3)):
         fgs, starts = [graph(k)[0] for k in keys], [graph(k)[1] for k in keys]
         got = refine_estimate_robust_batch(fgs, starts, inlier_threshold=[THRESHOLD[k] for k in keys], robust_loop_closures=True,
-                                           engine="native", lib_path=lib, **SCHEDULE[keys[0]])
+                                           **batch, **SCHEDULE[keys[0]])
         for k, fg, (res, info) in zip(keys, fgs, got):
             keep(f"refine_estimate_robust_batch/{'+'.join(keys)}/{k}", fg, res, info)
+    if engine == "python":  # (the marginals and the spectrum are the library's)
+        return out
     from refine_batch_helpers import twin_alone
     from score_amd.marginals import marginal_covariances
     from score_amd.marginals_batch import marginal_covariances_batch
@@ -111,13 +117,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("paths", nargs="+")
     ap.add_argument("--lib", default=None)
+    ap.add_argument("--engine", default="native", choices=("native", "python"))
     ap.add_argument("--compare", action="store_true")
     args = ap.parse_args()
     if args.compare:
         if len(args.paths) != 2:
             ap.error("--compare takes two records")
         sys.exit(compare(*args.paths))
-    out = record(args.lib)
+    out = record(args.lib, args.engine)
     os.makedirs(os.path.dirname(os.path.abspath(args.paths[0])), exist_ok=True)
     np.savez(args.paths[0], **out)
     print(len(out), "entries ->", args.paths[0])

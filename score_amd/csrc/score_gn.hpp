@@ -25,8 +25,8 @@
 // the group alike), every entry of H = J'J and g = J'r then sums its contributions in a fixed order
 // (contribution lists built once on the host) -- no atomics, same sums on both backends.  The damped
 // normal equations go through the handle's linear mode (score_linear_solve's core: k_factor on the pose
-// chains, k_prec_pre + k_spmv PCG).  The LM loop (`gn_levenberg_marquardt`) mirrors
-// score_amd/refine.py::_lm_loop, which the tests run beside it with SciPy's sparse LU.
+// chains, k_prec_pre + k_spmv PCG).  The LM loop (`gn_lm_run`, score_refine_drivers.hpp) drives the step rule of score_refine_rule.hpp as
+// score_amd/refine.py::_lm_loop drives its Python twin, which the tests run beside it with SciPy's sparse LU.
 #pragma once
 
 #include <algorithm>
@@ -37,6 +37,7 @@
 
 #include "../../include/score_hip.h"
 #include "score_host.hpp"
+#include "score_refine_drivers.hpp"
 
 #if defined(__HIPCC__)
 #define SCORE_GN_HD __host__ __device__ __forceinline__
@@ -344,7 +345,6 @@ SCORE_GN_HD double gn_measurement(const GnView& v, int64_t m, bool with_blocks) 
 // functions without H / g -- with the MEASURED precisions, which the caller passes.
 //   kGnRobustRanges    range m:                sqrt(p0) | |p_a - p_b| - dist |
 //   kGnRobustClosures  relative-pose entry m:  sqrt(p0 |t_j - t_i - R_i t~|^2 + p1 |R_j - R_i R~|_F^2)   (p0 = kappa, p1 = tau)
-constexpr int kGnRobustRanges = 1, kGnRobustClosures = 2;   // the bits of `families`
 template <int DIM>
 SCORE_GN_HD double gn_robust_residual(const GnView& v, int family, int64_t m, double p0, double p1) {
     return sqrt(family == kGnRobustRanges ? gn_range_at<DIM>(v, m, p0, nullptr, nullptr) : gn_rel_at<DIM>(v, m, p0, p1, nullptr, nullptr));
@@ -620,50 +620,6 @@ inline void gn_build(const score_graph& g, GnProblem& P) {
         }
         p0 += g.chain_len[c];
     }
-}
-
-struct GnInfo {
-    double cost_initial = 0, cost_final = 0, grad_inf = 0;
-    int32_t iterations = 0, linear_solves = 0, pcg_iters = 0;
-};
-
-// Backend concept:  double eval(const double* u_or_null_for_current, bool with_blocks)  -> cost at the trial
-// (or current) point;  assemble() -> |g|_inf (H values and g from the blocks of the current point);
-// bool solve(lambda, rel_tol, &pcg_iters) -> step ready;  trial() makes u + step the trial point;
-// accept() makes the trial point current.
-template <class Backend>
-inline void gn_levenberg_marquardt(Backend& be, int max_iters, double tol, double pcg_rel_tol, GnInfo& info) {
-    double f = be.eval_current(true);
-    info.cost_initial = f;
-    double lam = 1e-6;
-    double gnorm = INFINITY;
-    int it = 0;
-    for (it = 1; it <= max_iters; ++it) {
-        gnorm = be.assemble();
-        if (gnorm <= tol * std::max(1.0, f)) break;
-        bool accepted = false;
-        double fn = f;
-        for (int k = 0; k < 12; ++k) {
-            int used = 0;
-            const bool ok = be.solve(lam, pcg_rel_tol, &used);
-            info.linear_solves += 1;
-            info.pcg_iters += used;
-            if (!ok) { lam *= 10.0; continue; }
-            fn = be.eval_trial();
-            if (fn < f) { accepted = true; break; }
-            lam *= 10.0;
-        }
-        if (!accepted) break;
-        const double dec = f - fn;
-        be.accept();
-        f = fn;
-        lam = std::max(lam * 0.1, 1e-12);
-        (void)be.eval_current(true);
-        if (dec <= 1e-14 * std::max(1.0, f)) break;
-    }
-    info.iterations = std::min(it, max_iters);
-    info.cost_final = f;
-    info.grad_inf = gnorm;
 }
 
 }  // namespace score

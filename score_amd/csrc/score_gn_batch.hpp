@@ -15,6 +15,8 @@
 // The damped step of a round is one slot of the group's conjugate-gradient iteration (score_group_pcg.hpp, shared with the
 // marginals of a group): every member has its own alpha, beta, gate and done word, and a member the round leaves out starts
 // with done word 1.  The product's tiles of a member are cut by mv_tiles (score_marginals.hpp) from its own rows.
+//
+// The controller is gb_lock_step (score_refine_drivers.hpp): one LmState per member, the step rule of score_refine_rule.hpp.
 #pragma once
 
 #include <algorithm>
@@ -29,122 +31,6 @@
 #include "score_marginals.hpp"
 
 namespace score {
-
-// ---------------------------------------------------------------------------
-// the controller: one state per member, the transitions as pure functions
-// ---------------------------------------------------------------------------
-enum GbPhase : int32_t { kGbGradient = 0, kGbSolve = 1, kGbStopped = 2 };
-
-struct GbState {
-    double f = 0, lam = 1e-6, gnorm = INFINITY, cost_initial = 0;
-    int32_t it = 1, attempts = 0, iterations = 0, linear_solves = 0, pcg_iters = 0;
-    GbPhase phase = kGbGradient;
-};
-
-inline void gb_stop(GbState& s, int max_iters) {
-    s.phase = kGbStopped;
-    s.iterations = std::min(s.it, (int32_t)max_iters);
-}
-// the member enters the loop with cost f at its start point
-inline void gb_begin(GbState& s, double f, int max_iters) {
-    s = GbState{};
-    s.f = s.cost_initial = f;
-    if (s.it > max_iters) gb_stop(s, max_iters);
-}
-// top of iteration s.it: the gradient of the current point is known
-inline void gb_after_gradient(GbState& s, double gnorm, double tol, int max_iters) {
-    s.gnorm = gnorm;
-    if (gnorm <= tol * std::max(1.0, s.f)) { gb_stop(s, max_iters); return; }
-    s.attempts = 0;
-    s.phase = kGbSolve;
-}
-// one attempt: the solve (ok, iterations used) and, where it succeeded, the cost at the trial point.  true: the step is
-// accepted (the trial point becomes the current one).
-inline bool gb_after_solve(GbState& s, bool ok, int used, double fn, int max_iters) {
-    s.linear_solves += 1;
-    s.pcg_iters += used;
-    if (ok && fn < s.f) {
-        const double dec = s.f - fn;
-        s.f = fn;
-        s.lam = std::max(s.lam * 0.1, 1e-12);
-        if (dec <= 1e-14 * std::max(1.0, s.f)) { gb_stop(s, max_iters); return true; }
-        s.it += 1;
-        if (s.it > max_iters) gb_stop(s, max_iters); else s.phase = kGbGradient;
-        return true;
-    }
-    s.lam *= 10.0;
-    s.attempts += 1;
-    if (s.attempts >= 12) gb_stop(s, max_iters);
-    return false;
-}
-
-// Backend concept (masks: one char per member):
-//   eval(mask, trial, with_blocks, cost_or_null)   blocks / cost of the current (or trial) point of the masked members
-//   gradient(mask, gnorm)                          g = J'r of the masked members from their blocks, |g|_inf
-//   solve(mask, lambda, rel_tol, ok, used)         (J'J + lambda_g I) step = -g for the masked members
-//   trial(mask)                                    trial = current + step;     accept(mask)  current = trial
-// what a round works with: one entry per member
-struct GbRoundWork {
-    std::vector<char> mask, tmask, acc, ok;
-    std::vector<double> val, lam;
-    std::vector<int32_t> used;
-    explicit GbRoundWork(size_t G) : mask(G, 1), tmask(G), acc(G), ok(G), val(G, 0.0), lam(G, 0.0), used(G, 0) {}
-    static bool any(const std::vector<char>& m) { return std::find(m.begin(), m.end(), (char)1) != m.end(); }
-};
-
-// One round: every member in phase kGbSolve gets one damped solve, one trial point and one cost, then decides for itself;
-// those that go on get the blocks and the gradient of their new point.  max_iters(g) / tol(g): the limits of member g's run.
-// false: no member is in phase kGbSolve (nothing was done).
-template <class Backend, class MaxIters, class Tol>
-inline bool gb_round(Backend& be, std::vector<GbState>& S, MaxIters max_iters, Tol tol, double pcg_rel_tol, GbRoundWork& W) {
-    const size_t G = S.size();
-    for (size_t g = 0; g < G; ++g) { W.mask[g] = S[g].phase == kGbSolve; W.lam[g] = S[g].lam; }
-    if (!W.any(W.mask)) return false;
-    be.solve(W.mask, W.lam.data(), pcg_rel_tol, W.ok.data(), W.used.data());
-    for (size_t g = 0; g < G; ++g) W.tmask[g] = W.mask[g] && W.ok[g];
-    if (W.any(W.tmask)) {
-        be.trial(W.tmask);
-        be.eval(W.tmask, true, false, W.val.data());
-    }
-    for (size_t g = 0; g < G; ++g)
-        W.acc[g] = W.mask[g] ? (gb_after_solve(S[g], W.ok[g] != 0, W.used[g], W.val[g], max_iters(g)) ? 1 : 0) : 0;
-    if (!W.any(W.acc)) return true;
-    be.accept(W.acc);
-    for (size_t g = 0; g < G; ++g) W.tmask[g] = W.acc[g] && S[g].phase == kGbGradient;
-    if (!W.any(W.tmask)) return true;
-    be.eval(W.tmask, false, true, nullptr);
-    be.gradient(W.tmask, W.val.data());
-    for (size_t g = 0; g < G; ++g)
-        if (W.tmask[g]) gb_after_gradient(S[g], W.val[g], tol(g), max_iters(g));
-    return true;
-}
-
-// The masked members enter a run at their current points: blocks and cost, gb_begin, then the gradient of those that iterate.
-template <class Backend, class MaxIters, class Tol>
-inline void gb_start(Backend& be, std::vector<GbState>& S, const std::vector<char>& members, MaxIters max_iters, Tol tol, GbRoundWork& W) {
-    const size_t G = S.size();
-    be.eval(members, false, true, W.val.data());
-    for (size_t g = 0; g < G; ++g)
-        if (members[g]) gb_begin(S[g], W.val[g], max_iters(g));
-    for (size_t g = 0; g < G; ++g) W.tmask[g] = members[g] && S[g].phase == kGbGradient;
-    if (!W.any(W.tmask)) return;
-    be.gradient(W.tmask, W.val.data());
-    for (size_t g = 0; g < G; ++g)
-        if (W.tmask[g]) gb_after_gradient(S[g], W.val[g], tol(g), max_iters(g));
-}
-
-template <class Backend>
-inline int gb_lock_step(Backend& be, int count, int max_iters, double tol, double pcg_rel_tol, std::vector<GbState>& S) {
-    const size_t G = (size_t)count;
-    S.assign(G, GbState{});
-    GbRoundWork W(G);
-    auto iters_of = [max_iters](size_t) { return max_iters; };
-    auto tol_of = [tol](size_t) { return tol; };
-    gb_start(be, S, std::vector<char>(G, 1), iters_of, tol_of, W);
-    int rounds = 0;
-    while (gb_round(be, S, iters_of, tol_of, pcg_rel_tol, W)) ++rounds;
-    return rounds;
-}
 
 // ---------------------------------------------------------------------------
 // the union problem

@@ -11,9 +11,9 @@
 //   k_gn_robust_weight  gn_robust_weight: w = gnc_tls_weight(r, mu, c_f) (score_robust.hpp, as it stands; mu is an argument,
 //                       mu = 0: w = 1) and, in mode kGbrNext, the next solve's precisions prec * max(w, min_weight) into the very
 //                       arrays k_gn_blocks reads (rng_prec, rel_kappa, rel_tau): the block kernels stay as they are.
-// Host: gn_robust_refine, a template over the backend concept of gn_levenberg_marquardt plus three hooks; the stop rule is the
-// pure function robust_decide of score_robust.hpp, the relaxation's.  One device-to-host read per outer iteration (the
-// partials) beyond what the LM loop reads.
+// Host: gn_robust_refine (score_refine_drivers.hpp), a template over the backend concept of gn_lm_run plus three hooks, drives
+// the schedule of score_refine_rule.hpp (GncState; its stop rule robust_decide is the relaxation's too).  One device-to-host
+// read per outer iteration (the partials) beyond what the LM loop reads.  Here: the settings' checks and the partials' fold.
 #pragma once
 
 #include "../../include/score_refine_robust.h"
@@ -23,14 +23,6 @@
 namespace score {
 
 constexpr int kGnRobustPart = 4;   // doubles per block in the partials: max r^2 (ranges, closures), non-binary weights (ranges, closures)
-
-// what a weight kernel does with a measurement (the group's k_gbr_weight: by member)
-enum GbrMode : int32_t {
-    kGbrNext = 0,     // w from r in the enabled families; precisions prec0 * max(w, min_weight) there
-    kGbrKeep = 1,     // precisions prec0 * w of the weights as they stand (every family: a family that is off holds w = 1)
-    kGbrRestore = 2,  // precisions prec0
-    kGbrInspect = 3,  // w from r in the enabled families; the precisions are not touched
-};
 
 struct GnRobustArrays {   // ranges in range order, loop closures in loop-closure order (kappa, tau: relative-pose order)
     const double *prec0, *kappa0, *tau0;   // the measured precisions
@@ -119,19 +111,6 @@ inline int64_t gn_n_loop_closures(const GnProblem& P) {  // the trailing n_rel -
     return P.n_rel() - odom;
 }
 
-// mu after the first solve: the smallest c_f^2 / (2 max r_f^2 - c_f^2) of the families with outliers (the most convex start)
-inline double gn_robust_mu0(const RobustSeen* seen, int n_seen) {
-#pragma clang fp contract(off)
-    double mu = 0.0;
-    for (const RobustSeen* s = seen; s < seen + n_seen; ++s) {
-        const double c2 = s->c * s->c;
-        if (!(s->n > 0 && 2.0 * s->r2max > c2)) continue;
-        const double m = c2 / (2.0 * s->r2max - c2);
-        if (mu == 0.0 || m < mu) mu = m;
-    }
-    return mu;
-}
-
 // the settings of a robust run and the measured precisions of the families they enable (prec: the ranges; kappa, tau: the
 // n_lc loop closures); who: the prefix of the message
 inline void gn_robust_check_settings(const std::string& who, const score_refine_robust_settings& s, const double* prec, int64_t n_rng,
@@ -170,47 +149,6 @@ inline void gn_robust_fold(const double* part, int b0, int b1, double r2[2], dou
             nonbin[f] += p[2 + f];
         }
     }
-}
-
-struct GnRobustResult {
-    int outer_iterations = 0, lm_iterations = 0;
-    bool converged = false;
-    double mu = 0.0, cost_initial = 0.0;
-    GnInfo gi;   // the last run's cost and gradient; linear solves and PCG iterations of all runs
-};
-
-// Backend concept: that of gn_levenberg_marquardt, and
-//   robust_begin()                         every weight 1, the block kernels' precisions the measured ones
-//   int robust_residuals(families, seen)   r of these families at the current point; fills one record per family (ranges first)
-//   robust_weights(families, mu)           the weights from the last residuals, the next solve's precisions
-template <class Backend>
-inline void gn_robust_refine(Backend& be, const score_refine_robust_settings& s, double pcg_rel_tol, GnRobustResult& R) {
-    GnInfo& gi = R.gi;
-    be.robust_begin();
-    gn_levenberg_marquardt(be, s.max_iters, s.tol, pcg_rel_tol, gi);   // solve 1: score_refine_run's
-    R.cost_initial = gi.cost_initial;
-    R.lm_iterations = gi.iterations;
-    int k = 1;
-    RobustNext what;
-    bool finite = true;
-    for (;;) {
-        RobustSeen seen[2];
-        const int n_seen = be.robust_residuals(s.families, seen);
-        what = robust_decide(k, s.max_outer, seen, n_seen);
-        for (int f = 0; f < n_seen; ++f) finite = finite && std::isfinite(seen[f].r2max);
-        if (what != RobustNext::go) break;
-        R.mu = k == 1 ? gn_robust_mu0(seen, n_seen) : R.mu * s.mu_step;
-        be.robust_weights(s.families, R.mu);
-        ++k;
-        gn_levenberg_marquardt(be, s.inner_iters, s.tol, pcg_rel_tol, gi);
-        R.lm_iterations += gi.iterations;
-    }
-    if (k > 1 && finite) {   // the final weights, to max_iters / tol  (not after a solve gone non-finite)
-        gn_levenberg_marquardt(be, s.max_iters, s.tol, pcg_rel_tol, gi);
-        R.lm_iterations += gi.iterations;
-    }
-    R.outer_iterations = k;
-    R.converged = what == RobustNext::converged;
 }
 
 }  // namespace score

@@ -4176,7 +4176,7 @@ struct score_refine {
     }
     ~score_refine() { if (lin) score_destroy(lin); }
 
-    // ---- the backend concept of gn_levenberg_marquardt ----
+    // ---- the backend concept of gn_lm_run ----
     double eval_at(const double* where, bool with_blocks) {
         if (P.dim == 2)
             hipLaunchKernelGGL(score::k_gn_blocks<2>, dim3(n_mblocks), dim3(kThreads), 0, stream(), view(where), cost_part.d, with_blocks ? 1 : 0);
@@ -4230,11 +4230,11 @@ struct score_refine {
         HIP_CHECK(sync_stream(stream()));
         return u0;
     }
-    void run(const double* poses_in, const double* lms_in, int max_iters, double tol, double* poses_out, double* lms_out,
-             score::GnInfo& info) {
+    score::LmState run(const double* poses_in, const double* lms_in, int max_iters, double tol, double* poses_out, double* lms_out) {
         std::vector<double> u0 = set_point(poses_in, lms_in);
-        score::gn_levenberg_marquardt(*this, max_iters, tol, 1e-9, info);
+        const score::LmState s = score::gn_lm_run(*this, max_iters, tol, 1e-9);
         read_point(u0, poses_out, lms_out);
+        return s;
     }
     // the current point (u) in the caller's layout; u0: scratch of the state's size
     void read_point(std::vector<double>& u0, double* poses_out, double* lms_out) {
@@ -4290,7 +4290,7 @@ struct score_refine {
         robust_weights(families, mu, rb_settings->inlier_threshold, rb_settings->rel_threshold, rb_settings->min_weight, true);
     }
     void robust_begin() { robust_weights(score::kGnRobustRanges | score::kGnRobustClosures, 0.0, 1.0, 1.0, 1.0, true); }
-    int robust_residuals(int families, score::RobustSeen* seen) {
+    void robust_residuals(int families, score::RobustSeen* seen) {  // seen[0]: the ranges, seen[1]: the loop closures
         const score::GnRobustDev a = robust_dev(families);
         const int64_t lanes = a.n_a + a.n_b;
         const int nb = (int)((lanes + kThreads - 1) / kThreads);
@@ -4303,12 +4303,8 @@ struct score_refine {
             HIP_CHECK(sync_stream(stream()));
             score::gn_robust_fold(part_host.data(), 0, nb, r2, nonbin);
         }
-        const double c[2] = {rb_settings ? rb_settings->inlier_threshold : 0.0, rb_settings ? rb_settings->rel_threshold : 0.0};
-        const int64_t items[2] = {P.n_rng(), rb_n_lc};
-        int n_seen = 0;
-        for (int f = 0; f < 2; ++f)
-            if (families & (1 << f)) seen[n_seen++] = score::RobustSeen{items[f], r2[f], c[f], (int32_t)nonbin[f]};
-        return n_seen;
+        seen[0] = score::RobustSeen{P.n_rng(), r2[0], 0.0, (int32_t)nonbin[0]};
+        seen[1] = score::RobustSeen{rb_n_lc, r2[1], 0.0, (int32_t)nonbin[1]};
     }
     void robust_run(const score_refine_robust_settings& s, const double* poses_in, const double* lms_in, double* poses_out, double* lms_out,
                     double* w, double* r, double* wl, double* rl, int32_t* outliers, int32_t* rel_outliers, score::GnRobustResult& R) {
@@ -4322,7 +4318,7 @@ struct score_refine {
         std::vector<double> u0 = set_point(poses_in, lms_in);
         score::gn_robust_refine(*this, s, 1e-9, R);
         score::RobustSeen seen[2];
-        (void)robust_residuals(score::kGnRobustRanges | score::kGnRobustClosures, seen);  // every family's r at the final estimate
+        robust_residuals(score::kGnRobustRanges | score::kGnRobustClosures, seen);  // every family's r at the final estimate
         std::vector<double> hw, hwl;
         robust_read(*this, w, r, wl, rl, hw, hwl);
         if (outliers) { *outliers = 0; for (double v : hw) *outliers += v < 0.5 ? 1 : 0; }
@@ -4339,7 +4335,7 @@ struct score_refine {
         (void)set_point(poses, lms);
         robust_begin();
         score::RobustSeen seen[2];
-        (void)robust_residuals(both, seen);
+        robust_residuals(both, seen);
         robust_weights(both, mu, c, c_rel, 1.0, false);
         std::vector<double> hw, hwl;
         robust_read(*this, w, r, wl, rl, hw, hwl);
@@ -4553,7 +4549,7 @@ struct score_refine_batch {
         return h;
     }
     void run(const double* poses_in, const double* lms_in, int max_iters, double tol, double* poses_out, double* lms_out,
-             std::vector<score::GbState>& S) {
+             std::vector<score::LmState>& S) {
         std::vector<double> h = set_point(poses_in, lms_in);
         rounds = score::gb_lock_step(*this, U.count, max_iters, tol, 1e-9, S);
         read_points(h, poses_out, lms_out);
@@ -4633,7 +4629,7 @@ struct score_refine_batch {
         if (!rb_ready) return;
         try { robust_all(0.0, 1.0, score::kGbrRestore); } catch (...) {}
     }
-    void robust_residuals(const std::vector<char>& m, score::GbrSeen* seen) {
+    void robust_residuals(const std::vector<char>& m, score::GncSeen* seen) {
         set_mask(m);
         const unsigned nb = (unsigned)U.rblk_member.size();
         if (U.dim == 2)
@@ -4657,7 +4653,7 @@ struct score_refine_batch {
     }
     // rs: one record per member
     void robust_run(const score_refine_robust_settings* rs, const double* poses_in, const double* lms_in, double* poses_out, double* lms_out,
-                    double* w, double* r, double* wl, double* rl, bool keep, std::vector<score::GbState>& S, std::vector<score::GbrState>& R,
+                    double* w, double* r, double* wl, double* rl, bool keep, std::vector<score::LmState>& S, std::vector<score::GncState>& R,
                     std::vector<int32_t>& outliers, std::vector<int32_t>& rel_outliers) {
         robust_reserve();
         struct Restore {  // unless the weights are kept, the handle ends with the measured precisions
@@ -4668,7 +4664,7 @@ struct score_refine_batch {
         std::vector<double> h = set_point(poses_in, lms_in);
         rounds = robust_rounds = score::gbr_lock_step(*this, U.count, rs, 1e-9, S, R, &stage_rounds);
         const std::vector<char> all((size_t)U.count, 1);
-        std::vector<score::GbrSeen> seen((size_t)U.count);
+        std::vector<score::GncSeen> seen((size_t)U.count);
         robust_residuals(all, seen.data());  // every family's r at the final estimates
         std::vector<double> hw, hwl;
         robust_read(*this, w, r, wl, rl, hw, hwl);
@@ -4699,7 +4695,7 @@ struct score_refine_batch {
         robust_reserve();
         (void)set_point(poses, lms);
         const std::vector<char> all((size_t)U.count, 1);
-        std::vector<score::GbrSeen> seen((size_t)U.count);
+        std::vector<score::GncSeen> seen((size_t)U.count);
         robust_residuals(all, seen.data());
         robust_weights(all, params.data());
         std::vector<double> hw, hwl;
@@ -4774,6 +4770,20 @@ void score_destroy(score_handle* h) {
         delete h;
     }
 }
+// the info records of a refinement, from the states of score_refine_rule.hpp: a single handle's and a group member's alike
+static void fill_refine_info(score_refine_info& info, const score::LmState& run, double setup_ms, double solve_ms) {
+    info.cost_initial = run.cost_initial; info.cost_final = run.f; info.grad_inf = run.gnorm;
+    info.iterations = run.iterations; info.linear_solves = run.linear_solves; info.pcg_iters = run.pcg_iters;
+    info.setup_ms = setup_ms; info.solve_ms = solve_ms;
+}
+static void fill_refine_robust_info(score_refine_robust_info& info, const score::GncState& loop, const score::LmState& last_run,
+                                    int32_t outliers, int32_t rel_outliers, double setup_ms, double solve_ms) {
+    info.outer_iterations = loop.k; info.converged = loop.converged ? 1 : 0;
+    info.outliers = outliers; info.rel_outliers = rel_outliers; info.mu = loop.mu;
+    info.lm_iterations = loop.lm_iterations; info.linear_solves = loop.linear_solves; info.pcg_iters = loop.pcg_iters;
+    info.cost_initial = loop.cost_initial; info.cost_final = last_run.f; info.grad_inf = last_run.gnorm;
+    info.setup_ms = setup_ms; info.solve_ms = solve_ms;
+}
 int score_refine_create(const score_graph* g, const score_settings* s, score_refine** out) {
     return abi_call([&] {
         require(g && out);
@@ -4790,13 +4800,8 @@ int score_refine_run(score_refine* r, const double* poses_in, const double* land
         require(r && poses_in && poses_out && (r->P.Nl == 0 || (landmarks_in && landmarks_out)));
         AbiEnv::Scope scope(r->device, false);
         const double t0 = score::now_ms();
-        score::GnInfo gi;
-        r->run(poses_in, landmarks_in, max_iters, tol, poses_out, landmarks_out, gi);
-        if (info) {
-            info->cost_initial = gi.cost_initial; info->cost_final = gi.cost_final; info->grad_inf = gi.grad_inf;
-            info->iterations = gi.iterations; info->linear_solves = gi.linear_solves; info->pcg_iters = gi.pcg_iters;
-            info->setup_ms = r->setup_ms; info->solve_ms = score::now_ms() - t0;
-        }
+        const score::LmState run = r->run(poses_in, landmarks_in, max_iters, tol, poses_out, landmarks_out);
+        if (info) fill_refine_info(*info, run, r->setup_ms, score::now_ms() - t0);
         return 0;
     });
 }
@@ -4836,13 +4841,7 @@ int score_refine_robust_run(score_refine* r, const score_refine_robust_settings*
         int32_t outliers = 0, rel_outliers = 0;
         r->robust_run(s, poses_in, landmarks_in, poses_out, landmarks_out, weights, residuals, rel_weights, rel_residuals, &outliers,
                       &rel_outliers, R);
-        if (info) {
-            info->outer_iterations = R.outer_iterations; info->converged = R.converged ? 1 : 0;
-            info->outliers = outliers; info->rel_outliers = rel_outliers; info->mu = R.mu;
-            info->lm_iterations = R.lm_iterations; info->linear_solves = R.gi.linear_solves; info->pcg_iters = R.gi.pcg_iters;
-            info->cost_initial = R.cost_initial; info->cost_final = R.gi.cost_final; info->grad_inf = R.gi.grad_inf;
-            info->setup_ms = r->setup_ms; info->solve_ms = score::now_ms() - t0;
-        }
+        if (info) fill_refine_robust_info(*info, R.loop, R.run, outliers, rel_outliers, r->setup_ms, score::now_ms() - t0);
         return 0;
     });
 }
@@ -4882,16 +4881,10 @@ int score_refine_batch_run(score_refine_batch* b, const double* poses_in, const 
         require(b && poses_in && poses_out && (b->U.lms_size == 0 || (landmarks_in && landmarks_out)));
         AbiEnv::Scope scope(b->device, false);
         const double t0 = score::now_ms();
-        std::vector<score::GbState> S;
+        std::vector<score::LmState> S;
         b->run(poses_in, landmarks_in, max_iters, tol, poses_out, landmarks_out, S);
         const double ms = score::now_ms() - t0;
-        for (int g = 0; infos && g < b->U.count; ++g) {
-            const score::GbState& m = S[(size_t)g];
-            score_refine_info& info = infos[g];
-            info.cost_initial = m.cost_initial; info.cost_final = m.f; info.grad_inf = m.gnorm;
-            info.iterations = m.iterations; info.linear_solves = m.linear_solves; info.pcg_iters = m.pcg_iters;
-            info.setup_ms = b->setup_ms; info.solve_ms = ms;
-        }
+        for (int g = 0; infos && g < b->U.count; ++g) fill_refine_info(infos[g], S[(size_t)g], b->setup_ms, ms);
         return 0;
     });
 }
@@ -4924,22 +4917,14 @@ int score_refine_batch_robust_run(score_refine_batch* b, const score_refine_robu
         const double t0 = score::now_ms();
         std::vector<score_refine_robust_settings> per((size_t)b->U.count);
         for (int g = 0; g < b->U.count; ++g) per[(size_t)g] = rs[n_settings == 1 ? 0 : g];
-        std::vector<score::GbState> S;
-        std::vector<score::GbrState> R;
+        std::vector<score::LmState> S;
+        std::vector<score::GncState> R;
         std::vector<int32_t> outliers, rel_outliers;
         b->robust_run(per.data(), poses_in, landmarks_in, poses_out, landmarks_out, weights, residuals, rel_weights, rel_residuals,
                       keep_weights != 0, S, R, outliers, rel_outliers);
         const double ms = score::now_ms() - t0;
-        for (int g = 0; infos && g < b->U.count; ++g) {
-            const score::GbState& m = S[(size_t)g];
-            const score::GbrState& o = R[(size_t)g];
-            score_refine_robust_info& info = infos[g];
-            info.outer_iterations = o.k; info.converged = o.converged ? 1 : 0;
-            info.outliers = outliers[(size_t)g]; info.rel_outliers = rel_outliers[(size_t)g]; info.mu = o.mu;
-            info.lm_iterations = o.lm_iterations; info.linear_solves = o.linear_solves; info.pcg_iters = o.pcg_iters;
-            info.cost_initial = o.cost_initial; info.cost_final = m.f; info.grad_inf = m.gnorm;
-            info.setup_ms = b->setup_ms; info.solve_ms = ms;
-        }
+        for (int g = 0; infos && g < b->U.count; ++g)
+            fill_refine_robust_info(infos[g], R[(size_t)g], S[(size_t)g], outliers[(size_t)g], rel_outliers[(size_t)g], b->setup_ms, ms);
         return 0;
     });
 }

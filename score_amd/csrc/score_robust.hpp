@@ -24,6 +24,7 @@
 #include <cmath>
 
 #include "score_assemble.hpp"
+#include "score_refine_rule.hpp"   // RobustSeen, robust_decide: the stop rule of the host loops
 #include "score_setup_device.hpp"
 
 namespace score {
@@ -54,23 +55,6 @@ struct RobustFamily {             // what the kernels need of any family
 };
 
 template <class Family> struct RobustArgs { RobustShared s; Family f; };
-
-// who stops, from what the re-weighted families saw in outer solve k (host: the relaxation's loop, score_robust_driver.hpp, and
-// the refinement's, score_gn_robust.hpp)
-struct RobustSeen { int64_t n; double r2max, c; int32_t nonbinary; };
-enum class RobustNext { go, converged, gave_up };
-inline RobustNext robust_decide(int k, int max_outer, const RobustSeen* seen, int n_seen) {
-    bool finite = true, outliers = false;
-    int32_t nonbinary = 0;
-    for (const RobustSeen* s = seen; s < seen + n_seen; ++s) {
-        finite = finite && std::isfinite(s->r2max);
-        outliers = outliers || (s->n > 0 && 2.0 * s->r2max > s->c * s->c);
-        nonbinary += s->nonbinary;
-    }
-    if (!finite) return RobustNext::gave_up;                                 // (a solve gone non-finite)
-    if (k == 1 ? !outliers : nonbinary == 0) return RobustNext::converged;   // no outliers at all | solved on binary weights
-    return k >= max_outer ? RobustNext::gave_up : RobustNext::go;
-}
 
 // the weight rule (the host twin is score_amd/robust.py: gnc_tls_weight -- same operations, same order)
 __device__ __forceinline__ double gnc_tls_weight(double r, double mu, double c) {

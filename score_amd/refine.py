@@ -425,14 +425,7 @@ def _refine_native(prob: _Problem, u0: np.ndarray, max_iters: int, tol: float, l
     if lib.score_refine_create(C.byref(g), C.byref(st), C.byref(h)) != 0:
         raise RuntimeError(f"score_refine_create failed: {lib.score_last_error().decode()}")
     try:
-        if isinstance(prob, _Problem3D):  # 3-D: [R (row-major) | t] per pose, landmarks x 3
-            R, t, lm = u0
-            poses_in = np.ascontiguousarray(np.concatenate([R.reshape(prob.Np, 9), t], axis=1), dtype=np.float64)
-            lms_in = np.ascontiguousarray(lm, dtype=np.float64).reshape(-1, 3)
-        else:
-            th, t, lm = prob.split(u0)
-            poses_in = np.ascontiguousarray(np.column_stack([th, t]), dtype=np.float64)
-            lms_in = np.ascontiguousarray(lm, dtype=np.float64).reshape(-1, 2)
+        poses_in, lms_in = _point_arrays(prob, u0)
         poses_out, lms_out = np.empty_like(poses_in), np.empty((max(1, len(lms_in)), lms_in.shape[1]))
         info = ScoreRefineInfo()
         rc = lib.score_refine_run(h, poses_in.ctypes.data_as(_f64p), lms_in.ctypes.data_as(_f64p) if len(lms_in) else None,
@@ -442,10 +435,14 @@ def _refine_native(prob: _Problem, u0: np.ndarray, max_iters: int, tol: float, l
             raise RuntimeError(f"score_refine_run failed: {lib.score_last_error().decode()}")
     finally:
         lib.score_refine_destroy(h)
-    if isinstance(prob, _Problem3D):
-        return (poses_out[:, :9].reshape(-1, 3, 3).copy(), poses_out[:, 9:12].copy(), lms_out[: len(lms_in)].copy()), info.as_dict()
-    u = prob.pack(poses_out[:, 0], poses_out[:, 1:3], lms_out[: len(lms_in)])
-    return u, info.as_dict()
+    return _point_from(prob, poses_out, lms_out), info.as_dict()
+
+
+def _native_info(ni: dict, iterations: str = "iterations") -> dict:
+    """``info`` as the refinement entry points report it, from a native info record (``iterations``: the record's field)."""
+    return {"cost_initial": ni["cost_initial"], "cost_final": ni["cost_final"], "iterations": ni[iterations],
+            "grad_inf": ni["grad_inf"], "linear_solver": "device", "engine": "native", "pcg_iters": ni["pcg_iters"],
+            "linear_solves": ni["linear_solves"], "setup_ms": ni["setup_ms"], "solve_ms": ni["solve_ms"]}
 
 
 def refine_estimate(data, results, max_iters: int = 50, tol: float = 1e-10, verbose: bool = False,
@@ -471,27 +468,18 @@ def refine_estimate(data, results, max_iters: int = 50, tol: float = 1e-10, verb
         u = _initial_point(prob, results)
     if engine == "native" and linear_solver == "device" and prob.n > 0:
         u, ni = _refine_native(prob, u, max_iters, tol, lib_path, solver_settings)
-        info = {"cost_initial": ni["cost_initial"], "cost_final": ni["cost_final"], "iterations": ni["iterations"],
-                "grad_inf": ni["grad_inf"], "linear_solver": "device", "engine": "native", "pcg_iters": ni["pcg_iters"],
-                "linear_solves": ni["linear_solves"], "setup_ms": ni["setup_ms"], "solve_ms": ni["solve_ms"]}
-        return _as_results(prob, u, results, ni["cost_final"]), info
+        return _as_results(prob, u, results, ni["cost_final"]), _native_info(ni)
     res, J = prob.residuals(u, jac=True)
-    f = float(res @ res)
-    f0 = f
-    lam = 1e-6
-    it = 0
-    gnorm = np.inf
     dev = _DeviceNormalEquations(prob, J, lib_path, solver_settings) if (linear_solver == "device" and prob.n > 0) else None
     try:
-        u, f, it, gnorm = _lm_loop(prob, u, res, J, f, lam, max_iters, tol, verbose, dev, pcg_rel_tol)
+        u, m = _lm_loop(prob, u, res, J, float(res @ res), max_iters, tol, verbose, dev, pcg_rel_tol)
     finally:
         pcg = (dev.pcg_iters, dev.solves) if dev else (0, 0)
         if dev:
             dev.close()
-    out = _as_results(prob, u, results, f)
-    info = {"cost_initial": f0, "cost_final": f, "iterations": it, "grad_inf": gnorm, "linear_solver": linear_solver,
-            "engine": "python", "pcg_iters": pcg[0], "linear_solves": pcg[1]}
-    return out, info
+    info = {"cost_initial": m.cost_initial, "cost_final": m.f, "iterations": m.iterations, "grad_inf": m.gnorm,
+            "linear_solver": linear_solver, "engine": "python", "pcg_iters": pcg[0], "linear_solves": pcg[1]}
+    return _as_results(prob, u, results, m.f), info
 
 
 def _as_results(prob, u, results, cost: float):
@@ -513,39 +501,117 @@ def _as_results(prob, u, results, cost: float):
                                 pose_chain_names=results.pose_chain_names, solver_cost=cost, info=dict(results.info or {}))
 
 
-def _lm_loop(prob, u, res, J, f, lam, max_iters, tol, verbose, dev, pcg_rel_tol):
-    it = 0
-    gnorm = np.inf
-    for it in range(1, max_iters + 1):
-        g = J.T @ res
-        gnorm = float(np.abs(g).max()) if g.size else 0.0
-        if gnorm <= tol * max(1.0, f):
+# ---------------------------------------------------------------------------------------------------------------------
+# the point in the C ABI's layout
+# ---------------------------------------------------------------------------------------------------------------------
+def _point_arrays(prob, point):
+    if isinstance(prob, _Problem3D):  # [R (row-major) | t] per pose, landmarks x 3
+        R, t, lm = point
+        poses = np.ascontiguousarray(np.concatenate([R.reshape(prob.Np, 9), t], axis=1), dtype=np.float64)
+        return poses, np.ascontiguousarray(lm, dtype=np.float64).reshape(-1, 3)
+    th, t, lm = prob.split(point)
+    return np.ascontiguousarray(np.column_stack([th, t]), dtype=np.float64), np.ascontiguousarray(lm, dtype=np.float64).reshape(-1, 2)
+
+
+def _point_from(prob, poses, lms):
+    if isinstance(prob, _Problem3D):
+        return poses[:, :9].reshape(-1, 3, 3).copy(), poses[:, 9:12].copy(), lms[: prob.Nl].copy()
+    return prob.pack(poses[:, 0], poses[:, 1:3], lms[: prob.Nl])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the Levenberg-Marquardt step rule (the library's is csrc/score_refine_rule.hpp: LmState and lm_*), and its drivers: _lm_loop
+# here, refine_batch._LockStep for a group
+# ---------------------------------------------------------------------------------------------------------------------
+GRADIENT, SOLVE, STOPPED = "gradient", "solve", "stopped"
+
+
+class _Member:
+    """The state of one Levenberg-Marquardt run, and its transitions (pure: they read and write this record only)."""
+
+    def __init__(self, f: float, max_iters: int):
+        self.f = self.cost_initial = float(f)
+        self.lam, self.gnorm = 1e-6, float("inf")
+        self.it, self.attempts, self.iterations, self.linear_solves, self.pcg_iters = 1, 0, 0, 0, 0
+        self.phase = GRADIENT
+        if self.it > max_iters:
+            self._stop(max_iters)
+
+    def _stop(self, max_iters: int) -> None:
+        self.phase = STOPPED
+        self.iterations = min(self.it, max_iters)
+
+    def after_gradient(self, gnorm: float, tol: float, max_iters: int) -> None:
+        """Top of iteration ``it``: the gradient of the current point is known."""
+        self.gnorm = float(gnorm)
+        if gnorm <= tol * max(1.0, self.f):
+            self._stop(max_iters)
+            return
+        self.attempts = 0
+        self.phase = SOLVE
+
+    def after_solve(self, ok: bool, used: int, fn: float, max_iters: int) -> bool:
+        """One attempt: the solve and, where it succeeded, the cost at the trial point.  True: the step is accepted."""
+        self.linear_solves += 1
+        self.pcg_iters += int(used)
+        if ok and fn < self.f:
+            dec = self.f - fn
+            self.f = float(fn)
+            self.lam = max(self.lam * 0.1, 1e-12)
+            if dec <= 1e-14 * max(1.0, self.f):
+                self._stop(max_iters)
+                return True
+            self.it += 1
+            if self.it > max_iters:
+                self._stop(max_iters)
+            else:
+                self.phase = GRADIENT
+            return True
+        self.lam *= 10.0
+        self.attempts += 1
+        if self.attempts >= 12:
+            self._stop(max_iters)
+        return False
+
+
+def _gradient(res, J):
+    """g = J'r and |g|_inf."""
+    g = J.T @ res
+    return g, float(np.abs(g).max()) if g.size else 0.0
+
+
+def _attempt(prob, u, H, g, lam: float, dev=None, pcg_rel_tol: float = 1e-9):
+    """One damped solve, trial point and cost: (solved, trial point, its cost)."""
+    try:
+        if dev:
+            step = dev.solve(H, lam, -g, pcg_rel_tol)
+        else:
+            step = spla.splu((H + lam * sp.identity(prob.n, format="csc")).tocsc()).solve(-g)
+    except RuntimeError:
+        return False, None, float("nan")
+    un = prob.retract(u, step)
+    return True, un, prob.cost(un)
+
+
+def _lm_loop(prob, u, res, J, f, max_iters, tol, verbose, dev, pcg_rel_tol):
+    """One run from ``u`` (``res``, ``J``, ``f``: residuals, Jacobian and cost there): (the point it ends at, its ``_Member``).
+    The residuals and the Jacobian of an accepted point are evaluated only when another iteration follows."""
+    m = _Member(f, max_iters)
+    while m.phase == GRADIENT:
+        g, gnorm = _gradient(res, J)
+        m.after_gradient(gnorm, tol, max_iters)
+        if m.phase != SOLVE:
             break
         H = (J.T @ J).tocsr() if dev else (J.T @ J).tocsc()
-        accepted = False
-        for _ in range(12):
-            try:
-                if dev:
-                    step = dev.solve(H, lam, -g, pcg_rel_tol)
-                else:
-                    step = spla.splu((H + lam * sp.identity(prob.n, format="csc")).tocsc()).solve(-g)
-            except RuntimeError:
-                lam *= 10.0
-                continue
-            un = prob.retract(u, step)
-            fn = prob.cost(un)
-            if fn < f:
-                accepted = True
-                break
-            lam *= 10.0
+        it, accepted = m.it, False
+        while m.phase == SOLVE and not accepted:
+            ok, un, fn = _attempt(prob, u, H, g, m.lam, dev, pcg_rel_tol)
+            accepted = m.after_solve(ok, 0, fn, max_iters)
         if not accepted:
             break
-        dec = f - fn
-        u, f = un, fn
-        lam = max(lam * 0.1, 1e-12)
-        res, J = prob.residuals(u, jac=True)
+        u = un
+        if m.phase == GRADIENT:
+            res, J = prob.residuals(u, jac=True)
         if verbose:
-            print(f"  refine it {it}: cost {f:.9g} |g| {gnorm:.3e} lambda {lam:.1e}")
-        if dec <= 1e-14 * max(1.0, f):
-            break
-    return u, f, it, gnorm
+            print(f"  refine it {it}: cost {m.f:.9g} |g| {m.gnorm:.3e} lambda {m.lam:.1e}")
+    return u, m

@@ -7,74 +7,21 @@ solve / trial / cost per ROUND for every member that needs one, and a controller
 never influence one another: every member takes exactly the decisions ``refine._lm_loop`` takes on it alone.
 
 ``engine="python"`` is the same lock-step controller in Python around ``refine._Problem`` / ``_Problem3D`` with SciPy's sparse
-LU -- the readable statement of the state machine (``_Member``: the library's is ``GbState`` with ``gb_begin`` /
-``gb_after_gradient`` / ``gb_after_solve``), and the twin the tests compare with: it only reorders independent work, so its
-results equal ``refine_estimate(engine="python", linear_solver="scipy")`` member by member, bit for bit.
+LU: the step rule is ``refine._Member``'s, the one ``refine._lm_loop`` drives (the library's: ``LmState`` and ``lm_*`` of
+csrc/score_refine_rule.hpp under ``gb_start`` / ``gb_round``).  It is the twin the tests compare with: it only reorders
+independent work, so its results equal ``refine_estimate(engine="python", linear_solver="scipy")`` member by member, bit for bit.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional, Sequence
+from typing import Optional, Sequence
 
 import numpy as np
-import scipy.sparse as sp
-import scipy.sparse.linalg as spla
 
-from .refine import _as_results, _initial_point, _Problem, _Problem3D, refine_estimate
-from .refine_robust import _point_arrays, _point_from
+from .refine import (GRADIENT, SOLVE, _as_results, _attempt, _gradient, _initial_point, _Member, _native_info, _point_arrays,
+                     _point_from, _Problem, _Problem3D, refine_estimate)
 
 REFINE_BATCH_SYMBOLS = ["score_refine_batch_create", "score_refine_batch_run", "score_refine_batch_destroy"]
-
-GRADIENT, SOLVE, STOPPED = "gradient", "solve", "stopped"
-
-
-class _Member:
-    """The controller's state of one member, and its transitions (pure: they read and write this record only)."""
-
-    def __init__(self, f: float, max_iters: int):
-        self.f = self.cost_initial = float(f)
-        self.lam, self.gnorm = 1e-6, float("inf")
-        self.it, self.attempts, self.iterations, self.linear_solves, self.pcg_iters = 1, 0, 0, 0, 0
-        self.phase = GRADIENT
-        if self.it > max_iters:
-            self._stop(max_iters)
-
-    def _stop(self, max_iters: int) -> None:
-        self.phase = STOPPED
-        self.iterations = min(self.it, max_iters)
-
-    def after_gradient(self, gnorm: float, tol: float, max_iters: int) -> None:
-        """Top of iteration ``it``: the gradient of the current point is known."""
-        self.gnorm = float(gnorm)
-        if gnorm <= tol * max(1.0, self.f):
-            self._stop(max_iters)
-            return
-        self.attempts = 0
-        self.phase = SOLVE
-
-    def after_solve(self, ok: bool, used: int, fn: float, max_iters: int) -> bool:
-        """One attempt: the solve and, where it succeeded, the cost at the trial point.  True: the step is accepted."""
-        self.linear_solves += 1
-        self.pcg_iters += int(used)
-        if ok and fn < self.f:
-            dec = self.f - fn
-            self.f = float(fn)
-            self.lam = max(self.lam * 0.1, 1e-12)
-            if dec <= 1e-14 * max(1.0, self.f):
-                self._stop(max_iters)
-                return True
-            self.it += 1
-            if self.it > max_iters:
-                self._stop(max_iters)
-            else:
-                self.phase = GRADIENT
-            return True
-        self.lam *= 10.0
-        self.attempts += 1
-        if self.attempts >= 12:
-            self._stop(max_iters)
-        return False
-
 
 def _weights_of(weights, count: int, what: str) -> list:
     if weights is None:
@@ -93,46 +40,50 @@ def _problem_of(data, results, rw, lw):
     return prob, _initial_point(prob, results)
 
 
+class _LockStep:
+    """The members' points, runs (``_Member``) and normal equations.  ``tol`` / ``cap``: the limits of a member's run."""
+
+    def __init__(self, probs, points):
+        self.probs, self.u = probs, list(points)
+        self.S, self.lin, self.grad, self.H = ([None] * len(probs) for _ in range(4))
+
+    def _gradient(self, g: int, tol: float, cap: int) -> None:
+        res, J = self.lin[g]  # of the current point
+        self.grad[g], gnorm = _gradient(res, J)
+        self.S[g].after_gradient(gnorm, tol, cap)
+        self.H[g] = (J.T @ J).tocsc() if self.S[g].phase == SOLVE else None
+
+    def start(self, g: int, tol: float, cap: int) -> None:
+        """Member ``g`` enters a run at its current point, under the precisions as they stand."""
+        self.lin[g] = self.probs[g].residuals(self.u[g], jac=True)
+        res = self.lin[g][0]
+        self.S[g] = _Member(float(res @ res), cap)
+        if self.S[g].phase == GRADIENT:
+            self._gradient(g, tol, cap)
+
+    def round(self, tol, cap) -> bool:
+        """Every member in phase SOLVE gets one damped solve, one trial point and one cost (limits ``tol(g)``, ``cap(g)``); then
+        each decides for itself.  False: no member is in phase SOLVE (nothing was done)."""
+        live = [g for g, s in enumerate(self.S) if s.phase == SOLVE]
+        for g in live:
+            ok, un, fn = _attempt(self.probs[g], self.u[g], self.H[g], self.grad[g], self.S[g].lam)
+            if self.S[g].after_solve(ok, 0, fn, cap(g)):
+                self.u[g] = un
+                if self.S[g].phase == GRADIENT:
+                    self.lin[g] = self.probs[g].residuals(un, jac=True)
+                    self._gradient(g, tol(g), cap(g))
+        return bool(live)
+
+
 def _python_lock_step(probs, points, max_iters: int, tol: float):
-    """The lock-step controller over ``probs`` from ``points``: returns (points, members).  Per round every member in phase
-    SOLVE gets one damped solve, one trial point and one cost; then each decides for itself."""
-    G = len(probs)
-    u = list(points)
-    lin = [prob.residuals(x, jac=True) for prob, x in zip(probs, u)]  # (res, J) of the current points
-    S = [_Member(float(res @ res), max_iters) for res, _ in lin]
-    grad: List[Optional[np.ndarray]] = [None] * G
-    H: List[Optional[sp.spmatrix]] = [None] * G
-
-    def gradient(g: int) -> None:
-        res, J = lin[g]
-        grad[g] = J.T @ res
-        S[g].after_gradient(float(np.abs(grad[g]).max()) if grad[g].size else 0.0, tol, max_iters)
-        H[g] = (J.T @ J).tocsc() if S[g].phase == SOLVE else None
-
-    for g in range(G):
-        if S[g].phase == GRADIENT:
-            gradient(g)
+    """The lock-step controller over ``probs`` from ``points``: returns (points, members, rounds)."""
+    L = _LockStep(probs, points)
+    for g in range(len(probs)):
+        L.start(g, tol, max_iters)
     rounds = 0
-    while any(s.phase == SOLVE for s in S):
+    while L.round(lambda g: tol, lambda g: max_iters):
         rounds += 1
-        for g in range(G):
-            if S[g].phase != SOLVE:
-                continue
-            prob = probs[g]
-            ok, un, fn = True, None, float("nan")
-            try:
-                step = spla.splu((H[g] + S[g].lam * sp.identity(prob.n, format="csc")).tocsc()).solve(-grad[g])
-            except RuntimeError:
-                ok = False
-            if ok:
-                un = prob.retract(u[g], step)
-                fn = prob.cost(un)
-            if S[g].after_solve(ok, 0, fn, max_iters):
-                u[g] = un
-                if S[g].phase == GRADIENT:
-                    lin[g] = prob.residuals(un, jac=True)
-                    gradient(g)
-    return u, S, rounds
+    return L.u, L.S, rounds
 
 
 def _bind(lib):
@@ -359,9 +310,7 @@ def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-1
                     if with_marginals:
                         covs = group_marginals(h, probs, pts, sels, [m[0] for m in chunk], number)
                 rounds = max(r["linear_solves"] for r in raw)
-                infos = [{"cost_initial": r["cost_initial"], "cost_final": r["cost_final"], "iterations": r["iterations"],
-                          "grad_inf": r["grad_inf"], "linear_solver": "device", "engine": "native", "pcg_iters": r["pcg_iters"],
-                          "linear_solves": r["linear_solves"], "setup_ms": r["setup_ms"], "solve_ms": r["solve_ms"]} for r in raw]
+                infos = [_native_info(r) for r in raw]
             for k, ((i, prob, _), pt, info) in enumerate(zip(chunk, pts, infos)):
                 info["group"], info["rounds"] = number, rounds
                 if with_marginals:

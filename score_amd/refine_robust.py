@@ -14,7 +14,8 @@ free.  ``refine_estimate_robust`` runs the GNC-TLS loop around the Levenberg-Mar
 
 ``engine="native"`` runs the whole loop behind the C ABI on one refinement handle (``score_refine_robust_run``: two streaming
 kernels per outer iteration at the point on the device, csrc/score_gn_robust.hpp); ``engine="python"`` is the readable twin --
-the same loop around ``refine._lm_loop`` with NumPy residuals in the device's operation order -- which the tests compare with.
+the same schedule (``_Stage``; the library's is ``GncState`` and ``gnc_*`` of csrc/score_refine_rule.hpp) around
+``refine._lm_loop`` with NumPy residuals in the device's operation order -- which the tests compare with.
 """
 from __future__ import annotations
 
@@ -23,7 +24,8 @@ from typing import Optional
 
 import numpy as np
 
-from .refine import _as_results, _DeviceNormalEquations, _initial_point, _lm_loop, _Problem, _Problem3D
+from .refine import (_as_results, _DeviceNormalEquations, _initial_point, _lm_loop, _Member, _native_info, _point_arrays, _point_from,
+                     _Problem, _Problem3D)
 from .robust import BINARY_TOL, _robust_info, gnc_tls_weight, initial_mu, n_loop_closures_of
 from .solver import ScoreSettings, _f64p, load_library
 
@@ -135,7 +137,7 @@ def loop_closure_residuals(prob, point, kappa, tau) -> np.ndarray:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the stop rule (the library's is csrc/score_robust.hpp: robust_decide)
+# the stop rule (the library's is csrc/score_refine_rule.hpp: robust_decide)
 # ---------------------------------------------------------------------------------------------------------------------
 def _nonbinary(w) -> int:
     w = np.asarray(w, dtype=np.float64)
@@ -157,24 +159,6 @@ def decide(k: int, max_outer: int, seen) -> str:
 def first_mu(seen) -> float:
     """mu after the first solve: the smallest c_f^2 / (2 max r_f^2 - c_f^2) of the families with outliers."""
     return min(initial_mu(r2, c) for n, r2, c, _ in seen if n > 0 and 2.0 * r2 > c * c)
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# the point in the C ABI's layout
-# ---------------------------------------------------------------------------------------------------------------------
-def _point_arrays(prob, point):
-    if isinstance(prob, _Problem3D):  # [R (row-major) | t] per pose, landmarks x 3
-        R, t, lm = point
-        poses = np.ascontiguousarray(np.concatenate([R.reshape(prob.Np, 9), t], axis=1), dtype=np.float64)
-        return poses, np.ascontiguousarray(lm, dtype=np.float64).reshape(-1, 3)
-    th, t, lm = prob.split(point)
-    return np.ascontiguousarray(np.column_stack([th, t]), dtype=np.float64), np.ascontiguousarray(lm, dtype=np.float64).reshape(-1, 2)
-
-
-def _point_from(prob, poses, lms):
-    if isinstance(prob, _Problem3D):
-        return poses[:, :9].reshape(-1, 3, 3).copy(), poses[:, 9:12].copy(), lms[: prob.Nl].copy()
-    return prob.pack(poses[:, 0], poses[:, 1:3], lms[: prob.Nl])
 
 
 class RobustRefineHandle:
@@ -260,69 +244,97 @@ class RobustRefineHandle:
 # ---------------------------------------------------------------------------------------------------------------------
 # engine="python": the readable twin
 # ---------------------------------------------------------------------------------------------------------------------
-def _python_loop(prob, u, families, c, c_rel, max_outer, inner_iters, min_weight, mu_step, max_iters, tol, linear_solver, lib_path,
-                 solver_settings, pcg_rel_tol=1e-9):
-    f_rng, f_rel = bool(families & FAMILY_RANGES), bool(families & FAMILY_LOOP_CLOSURES)
-    n_lc = n_loop_closures_of(prob.a)
-    first = len(prob.bi) - n_lc
-    prec0 = np.array(prob.a["rng_prec"], dtype=np.float64)
-    kappa0, tau0 = np.array(prob.a["rel_kappa"], dtype=np.float64)[first:], np.array(prob.a["rel_tau"], dtype=np.float64)[first:]
-    w, wl = np.ones(len(prec0)), np.ones(n_lc)
-    sk_all, st_all = prob.sk.copy(), prob.st.copy()
+FIRST, INNER, LAST, DONE = "first", "inner", "last", "done"
 
-    def weigh():  # the next solve's precisions: prec max(w, min_weight)
-        if f_rng:
-            prob.sw = np.sqrt(prec0 * np.maximum(w, min_weight))
-        if f_rel and n_lc:
-            f = np.maximum(wl, min_weight)
-            sk_all[first:], st_all[first:] = np.sqrt(kappa0 * f), np.sqrt(tau0 * f)
-            prob.sk, prob.st = sk_all, st_all
 
-    state = dict(u=u, dev=None, lm=0, f=0.0, g=np.inf)
+class _Stage:
+    """One graph's place in the schedule (first run, inner runs, last run), and what it does when one of its runs stops.
+    ``s``: families, c, c_rel, max_outer, inner_iters, min_weight, mu_step, max_iters, tol."""
 
-    def lm_run(iters):
-        res, J = prob.residuals(state["u"], jac=True)
-        f = float(res @ res)
-        if state["dev"] is None and linear_solver == "device" and prob.n > 0:
-            state["dev"] = _DeviceNormalEquations(prob, J, lib_path, solver_settings)
-        state["u"], state["f"], it, state["g"] = _lm_loop(prob, state["u"], res, J, f, 1e-6, iters, tol, False, state["dev"], pcg_rel_tol)
-        state["lm"] += it
-        return f
+    def __init__(self, prob, s: dict):
+        self.prob, self.s = prob, s
+        self.f_rng, self.f_rel = bool(s["families"] & FAMILY_RANGES), bool(s["families"] & FAMILY_LOOP_CLOSURES)
+        self.n_lc = n_loop_closures_of(prob.a)
+        self.first = len(prob.bi) - self.n_lc
+        self.prec0 = np.array(prob.a["rng_prec"], dtype=np.float64)
+        self.kappa0 = np.array(prob.a["rel_kappa"], dtype=np.float64)[self.first:]
+        self.tau0 = np.array(prob.a["rel_tau"], dtype=np.float64)[self.first:]
+        self.w, self.wl = np.ones(len(self.prec0)), np.ones(self.n_lc)
+        self.sk_all, self.st_all = prob.sk.copy(), prob.st.copy()
+        self.stage, self.k, self.mu, self.what = FIRST, 1, 0.0, "go"
+        self.lm = self.linear_solves = 0
+        self.cost_initial = 0.0
 
+    def cap(self) -> int:
+        """The iteration cap of the run the graph stands in."""
+        return self.s["inner_iters"] if self.stage == INNER else self.s["max_iters"]
+
+    def weigh(self, floor: Optional[float]) -> None:
+        """The precisions the cost reads: prec max(w, floor) in the enabled families (floor None: prec w)."""
+        prob = self.prob
+        fl = (lambda w: np.maximum(w, floor)) if floor is not None else (lambda w: w)
+        if self.f_rng:
+            prob.sw = np.sqrt(self.prec0 * fl(self.w))
+        if self.f_rel and self.n_lc:
+            f = fl(self.wl)
+            self.sk_all[self.first:], self.st_all[self.first:] = np.sqrt(self.kappa0 * f), np.sqrt(self.tau0 * f)
+            prob.sk, prob.st = self.sk_all, self.st_all
+
+    def run_stopped(self, u, member: _Member) -> bool:
+        """A run has stopped at ``u``: True when another run follows."""
+        s = self.s
+        if self.stage == FIRST:
+            self.cost_initial = member.cost_initial
+        self.lm += member.iterations
+        self.linear_solves += member.linear_solves
+        if self.stage == LAST:
+            self.stage = DONE
+            return False
+        seen = []
+        if self.f_rng:
+            r = range_residuals(self.prob, u, self.prec0)
+            seen.append((len(r), float(np.max(r * r)) if len(r) else 0.0, s["c"], _nonbinary(self.w)))
+        if self.f_rel:
+            rl = loop_closure_residuals(self.prob, u, self.kappa0, self.tau0)
+            seen.append((len(rl), float(np.max(rl * rl)) if len(rl) else 0.0, s["c_rel"], _nonbinary(self.wl)))
+        self.what = decide(self.k, s["max_outer"], seen)
+        if self.what == "go":
+            self.mu = first_mu(seen) if self.k == 1 else self.mu * s["mu_step"]
+            if self.f_rng:
+                self.w = gnc_tls_weight(r, self.mu, s["c"])
+            if self.f_rel:
+                self.wl = gnc_tls_weight(rl, self.mu, s["c_rel"])
+            self.weigh(s["min_weight"])
+            self.k += 1
+            self.stage = INNER
+            return True
+        if self.k > 1 and self.what != "non_finite":  # the final weights, to max_iters / tol
+            self.stage = LAST
+            return True
+        self.stage = DONE
+        return False
+
+
+def _python_loop(prob, u, s: dict, linear_solver, lib_path, solver_settings, pcg_rel_tol=1e-9):
+    """The runs of one ``_Stage`` (settings ``s``) from ``u``, one after the other."""
+    stage, dev = _Stage(prob, s), None
     try:
-        cost_initial = lm_run(max_iters)  # solve 1: refine_estimate's
-        k, mu = 1, 0.0
         while True:
-            seen = []
-            if f_rng:
-                r = range_residuals(prob, state["u"], prec0)
-                seen.append((len(r), float(np.max(r * r)) if len(r) else 0.0, c, _nonbinary(w)))
-            if f_rel:
-                rl = loop_closure_residuals(prob, state["u"], kappa0, tau0)
-                seen.append((len(rl), float(np.max(rl * rl)) if len(rl) else 0.0, c_rel, _nonbinary(wl)))
-            what = decide(k, max_outer, seen)
-            if what != "go":
+            res, J = prob.residuals(u, jac=True)
+            if dev is None and linear_solver == "device" and prob.n > 0:
+                dev = _DeviceNormalEquations(prob, J, lib_path, solver_settings)
+            u, m = _lm_loop(prob, u, res, J, float(res @ res), stage.cap(), s["tol"], False, dev, pcg_rel_tol)
+            if not stage.run_stopped(u, m):
                 break
-            mu = first_mu(seen) if k == 1 else mu * mu_step
-            if f_rng:
-                w = gnc_tls_weight(r, mu, c)
-            if f_rel:
-                wl = gnc_tls_weight(rl, mu, c_rel)
-            weigh()
-            k += 1
-            lm_run(inner_iters)
-        if k > 1 and what != "non_finite":  # the final weights, to max_iters / tol
-            lm_run(max_iters)
-        dev = state["dev"]
         pcg = (dev.pcg_iters, dev.solves) if dev else (0, 0)
     finally:
-        if state["dev"]:
-            state["dev"].close()
-    r = range_residuals(prob, state["u"], prec0)
-    rl = loop_closure_residuals(prob, state["u"], kappa0, tau0)
-    info = {"cost_initial": cost_initial, "cost_final": state["f"], "iterations": state["lm"], "grad_inf": state["g"],
+        if dev:
+            dev.close()
+    r = range_residuals(prob, u, stage.prec0)
+    rl = loop_closure_residuals(prob, u, stage.kappa0, stage.tau0)
+    info = {"cost_initial": stage.cost_initial, "cost_final": m.f, "iterations": stage.lm, "grad_inf": m.gnorm,
             "linear_solver": linear_solver, "engine": "python", "pcg_iters": pcg[0], "linear_solves": pcg[1]}
-    return state["u"], info, (w, r, wl, rl, k, mu, what == "converged")
+    return u, info, (stage.w, r, stage.wl, rl, stage.k, stage.mu, stage.what == "converged")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -349,6 +361,20 @@ def _check(inlier_threshold, c_rel, max_outer, inner_iters, min_weight, mu_step,
         raise ValueError("linear_solver must be 'device' or 'scipy'")
     if engine == "native" and linear_solver != "device":
         raise ValueError("engine='native' solves on the device: linear_solver='scipy' goes with engine='python'")
+
+
+def _check_precisions(prob, f_rng: bool, f_rel: bool, who: str) -> None:
+    """The measured precisions of the enabled families; ``who``: the prefix of the message."""
+    n_lc = n_loop_closures_of(prob.a)
+    if f_rng and len(prob.ra) and not (np.all(np.isfinite(prob.a["rng_prec"])) and np.all(np.asarray(prob.a["rng_prec"]) > 0)):
+        raise ValueError(f"{who}every range precision must be positive and finite")
+    if f_rel:
+        if n_lc < 0:
+            raise ValueError(f"{who}fewer relative-pose entries than odometry steps")
+        for key in ("rel_kappa", "rel_tau"):
+            v = np.asarray(prob.a[key], dtype=np.float64)[len(prob.bi) - n_lc:]
+            if v.size and not (np.all(np.isfinite(v)) and np.all(v > 0)):
+                raise ValueError(f"{who}every loop closure's precision ({key}) must be positive and finite")
 
 
 def _prior(weights, floor: float, enabled: bool):
@@ -390,16 +416,7 @@ def refine_estimate_robust(data, results, inlier_threshold: float = 3.0, robust_
     else:
         prob = _Problem(data, pw, pwl)
         u = _initial_point(prob, results)
-    n_lc = n_loop_closures_of(prob.a)
-    if f_rng and len(prob.ra) and not (np.all(np.isfinite(prob.a["rng_prec"])) and np.all(np.asarray(prob.a["rng_prec"]) > 0)):
-        raise ValueError("refine_estimate_robust: every range precision must be positive and finite")
-    if f_rel:
-        if n_lc < 0:
-            raise ValueError("refine_estimate_robust: fewer relative-pose entries than odometry steps")
-        for key in ("rel_kappa", "rel_tau"):
-            v = np.asarray(prob.a[key], dtype=np.float64)[len(prob.bi) - n_lc:]
-            if v.size and not (np.all(np.isfinite(v)) and np.all(v > 0)):
-                raise ValueError(f"refine_estimate_robust: every loop closure's precision ({key}) must be positive and finite")
+    _check_precisions(prob, f_rng, f_rel, "refine_estimate_robust: ")
     if engine == "native":
         with RobustRefineHandle(prob, lib_path, solver_settings) as h:
             rs = h.default_settings()
@@ -407,14 +424,12 @@ def refine_estimate_robust(data, results, inlier_threshold: float = 3.0, robust_
             rs.families, rs.max_outer, rs.inner_iters = families, int(max_outer), int(inner_iters)
             rs.max_iters, rs.tol = int(max_iters), float(tol)
             u, w, r, wl, rl, ni = h.robust_run(u, rs)
-        info = {"cost_initial": ni["cost_initial"], "cost_final": ni["cost_final"], "iterations": ni["lm_iterations"],
-                "grad_inf": ni["grad_inf"], "linear_solver": "device", "engine": "native", "pcg_iters": ni["pcg_iters"],
-                "linear_solves": ni["linear_solves"], "setup_ms": ni["setup_ms"], "solve_ms": ni["solve_ms"]}
+        info = _native_info(ni, "lm_iterations")
         k, mu, conv = ni["outer_iterations"], ni["mu"], bool(ni["converged"])
     else:
-        u, info, (w, r, wl, rl, k, mu, conv) = _python_loop(prob, u, families, c, c_rel, int(max_outer), int(inner_iters), float(min_weight),
-                                                            float(mu_step), int(max_iters), float(tol), linear_solver, lib_path,
-                                                            solver_settings)
+        s = dict(families=families, c=c, c_rel=c_rel, max_outer=int(max_outer), inner_iters=int(inner_iters), min_weight=float(min_weight),
+                 mu_step=float(mu_step), max_iters=int(max_iters), tol=float(tol))
+        u, info, (w, r, wl, rl, k, mu, conv) = _python_loop(prob, u, s, linear_solver, lib_path, solver_settings)
     if range_weights is not None:  # prior x GNC
         w = w * np.asarray(range_weights, dtype=np.float64)
     if loop_closure_weights is not None:

@@ -7,8 +7,8 @@ run).  When a member's Levenberg-Marquardt run stops it gets its residuals, the 
 again in the next round while others are mid-run or finished; members whose runs stop in the same round share the launches.
 Members never influence one another: member by member the result is ``refine_estimate_robust``'s.
 
-``engine="python"`` is the same controller in Python with SciPy's sparse LU (``_Stage`` is the library's ``GbrState``, around
-``refine_batch._Member``): it only reorders independent work, so member by member it EQUALS
+``engine="python"`` is the same controller in Python with SciPy's sparse LU (a ``refine_robust._Stage`` per member over the
+rounds of ``refine_batch._LockStep``): it only reorders independent work, so member by member it EQUALS
 ``refine_estimate_robust(engine="python", linear_solver="scipy")``.
 """
 from __future__ import annotations
@@ -17,21 +17,17 @@ import ctypes as C
 from typing import Optional
 
 import numpy as np
-import scipy.sparse as sp
-import scipy.sparse.linalg as spla
 
-from .refine import _as_results
-from .refine_batch import GRADIENT, SOLVE, STOPPED, RefineBatchHandle, _Member, _problem_of, _weights_of
-from .refine_robust import (FAMILY_LOOP_CLOSURES, FAMILY_RANGES, ScoreRefineRobustInfo, ScoreRefineRobustSettings, _check, _nonbinary,
-                            _prior, decide, first_mu, loop_closure_residuals, range_residuals, refine_estimate_robust)
-from .robust import _robust_info, gnc_tls_weight, n_loop_closures_of
+from .refine import STOPPED, _as_results, _native_info
+from .refine_batch import RefineBatchHandle, _LockStep, _problem_of, _weights_of
+from .refine_robust import (DONE, FAMILY_LOOP_CLOSURES, FAMILY_RANGES, ScoreRefineRobustInfo, ScoreRefineRobustSettings, _check,
+                            _check_precisions, _prior, _Stage, loop_closure_residuals, range_residuals, refine_estimate_robust)
+from .robust import _robust_info, n_loop_closures_of
 from .solver import _f64p
 
 # the symbols include/score_refine_robust_batch.h declares
 REFINE_ROBUST_BATCH_SYMBOLS = ["score_refine_batch_robust_run", "score_refine_batch_residuals", "score_refine_batch_restore",
                                "score_refine_batch_robust_rounds"]
-
-FIRST, INNER, LAST, DONE = "first", "inner", "last", "done"
 
 
 def _bind(lib: C.CDLL) -> C.CDLL:
@@ -62,127 +58,28 @@ def member_counts(probs):
 # ---------------------------------------------------------------------------------------------------------------------
 # engine="python": the lock-step twin
 # ---------------------------------------------------------------------------------------------------------------------
-class _Stage:
-    """One member's place in the loop of ``refine_estimate_robust`` (``refine_robust._python_loop``, the same operations in the
-    same order), and what it does when one of its runs stops."""
-
-    def __init__(self, prob, s: dict):
-        self.prob, self.s = prob, s
-        self.f_rng, self.f_rel = bool(s["families"] & FAMILY_RANGES), bool(s["families"] & FAMILY_LOOP_CLOSURES)
-        self.n_lc = n_loop_closures_of(prob.a)
-        self.first = len(prob.bi) - self.n_lc
-        self.prec0 = np.array(prob.a["rng_prec"], dtype=np.float64)
-        self.kappa0 = np.array(prob.a["rel_kappa"], dtype=np.float64)[self.first:]
-        self.tau0 = np.array(prob.a["rel_tau"], dtype=np.float64)[self.first:]
-        self.w, self.wl = np.ones(len(self.prec0)), np.ones(self.n_lc)
-        self.sk_all, self.st_all = prob.sk.copy(), prob.st.copy()
-        self.stage, self.k, self.mu, self.what = FIRST, 1, 0.0, "go"
-        self.lm = self.linear_solves = 0
-        self.cost_initial = 0.0
-
-    def cap(self) -> int:
-        return self.s["inner_iters"] if self.stage == INNER else self.s["max_iters"]
-
-    def weigh(self, floor: Optional[float]) -> None:
-        """The precisions the cost reads: prec max(w, floor) in the enabled families (floor None: prec w)."""
-        prob = self.prob
-        fl = (lambda w: np.maximum(w, floor)) if floor is not None else (lambda w: w)
-        if self.f_rng:
-            prob.sw = np.sqrt(self.prec0 * fl(self.w))
-        if self.f_rel and self.n_lc:
-            f = fl(self.wl)
-            self.sk_all[self.first:], self.st_all[self.first:] = np.sqrt(self.kappa0 * f), np.sqrt(self.tau0 * f)
-            prob.sk, prob.st = self.sk_all, self.st_all
-
-    def run_stopped(self, u, member: _Member) -> bool:
-        """The member's run has stopped at ``u``: True when another run follows."""
-        s = self.s
-        self.lm += member.iterations
-        self.linear_solves += member.linear_solves
-        if self.stage == LAST:
-            self.stage = DONE
-            return False
-        seen = []
-        if self.f_rng:
-            r = range_residuals(self.prob, u, self.prec0)
-            seen.append((len(r), float(np.max(r * r)) if len(r) else 0.0, s["c"], _nonbinary(self.w)))
-        if self.f_rel:
-            rl = loop_closure_residuals(self.prob, u, self.kappa0, self.tau0)
-            seen.append((len(rl), float(np.max(rl * rl)) if len(rl) else 0.0, s["c_rel"], _nonbinary(self.wl)))
-        self.what = decide(self.k, s["max_outer"], seen)
-        if self.what == "go":
-            self.mu = first_mu(seen) if self.k == 1 else self.mu * s["mu_step"]
-            if self.f_rng:
-                self.w = gnc_tls_weight(r, self.mu, s["c"])
-            if self.f_rel:
-                self.wl = gnc_tls_weight(rl, self.mu, s["c_rel"])
-            self.weigh(s["min_weight"])
-            self.k += 1
-            self.stage = INNER
-            return True
-        if self.k > 1 and self.what != "non_finite":  # the final weights, to max_iters / tol
-            self.stage = LAST
-            return True
-        self.stage = DONE
-        return False
-
-
 def _python_robust_lock_step(probs, points, settings):
     """``refine_batch._python_lock_step`` with a stage per member.  Returns (points, last-run members, stages, rounds, the
     passes in which some member changed stage)."""
     G = len(probs)
-    u = list(points)
     R = [_Stage(prob, s) for prob, s in zip(probs, settings)]
-    S: list = [None] * G
-    lin: list = [None] * G
-    grad: list = [None] * G
-    H: list = [None] * G
-
-    def gradient(g: int) -> None:
-        res, J = lin[g]
-        grad[g] = J.T @ res
-        S[g].after_gradient(float(np.abs(grad[g]).max()) if grad[g].size else 0.0, settings[g]["tol"], R[g].cap())
-        H[g] = (J.T @ J).tocsc() if S[g].phase == SOLVE else None
-
-    def start(g: int) -> None:  # a run from the member's current point, under the precisions as they stand
-        lin[g] = probs[g].residuals(u[g], jac=True)
-        res = lin[g][0]
-        S[g] = _Member(float(res @ res), R[g].cap())
-        if S[g].phase == GRADIENT:
-            gradient(g)
-
+    L = _LockStep(probs, points)
+    tol, cap = (lambda g: settings[g]["tol"]), (lambda g: R[g].cap())
     for g in range(G):
-        start(g)
-        R[g].cost_initial = S[g].cost_initial
+        L.start(g, tol(g), cap(g))
     rounds = stage_rounds = 0
     while True:
-        ended = [g for g in range(G) if R[g].stage != DONE and S[g].phase == STOPPED]
+        ended = [g for g in range(G) if R[g].stage != DONE and L.S[g].phase == STOPPED]
         if ended:
             stage_rounds += 1
             for g in ended:
-                if R[g].run_stopped(u[g], S[g]):
-                    start(g)
-            continue
-        live = [g for g in range(G) if S[g].phase == SOLVE]
-        if not live:
+                if R[g].run_stopped(L.u[g], L.S[g]):
+                    L.start(g, tol(g), cap(g))
+            continue  # (a run may stop where it starts)
+        if not L.round(tol, cap):
             break
         rounds += 1
-        for g in live:
-            prob, cap = probs[g], R[g].cap()
-            ok, un, fn = True, None, float("nan")
-            try:
-                step = spla.splu((H[g] + S[g].lam * sp.identity(prob.n, format="csc")).tocsc()).solve(-grad[g])
-            except RuntimeError:
-                ok = False
-            if ok:
-                un = prob.retract(u[g], step)
-                fn = prob.cost(un)
-            if S[g].after_solve(ok, 0, fn, cap):
-                u[g] = un
-                if S[g].phase == GRADIENT:
-                    lin[g] = prob.residuals(un, jac=True)
-                    gradient(g)
-    return u, S, R, rounds, stage_rounds
+    return L.u, L.S, R, rounds, stage_rounds
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -195,19 +92,6 @@ def _per_graph(value, count: int, what: str) -> list:
     if len(value) != count:
         raise ValueError(f"{what}: a scalar or one entry per graph expected ({count}), got {len(value)}")
     return value
-
-
-def _check_precisions(prob, f_rng: bool, f_rel: bool) -> None:
-    n_lc = n_loop_closures_of(prob.a)
-    if f_rng and len(prob.ra) and not (np.all(np.isfinite(prob.a["rng_prec"])) and np.all(np.asarray(prob.a["rng_prec"]) > 0)):
-        raise ValueError("every range precision must be positive and finite")
-    if f_rel:
-        if n_lc < 0:
-            raise ValueError("fewer relative-pose entries than odometry steps")
-        for key in ("rel_kappa", "rel_tau"):
-            v = np.asarray(prob.a[key], dtype=np.float64)[len(prob.bi) - n_lc:]
-            if v.size and not (np.all(np.isfinite(v)) and np.all(v > 0)):
-                raise ValueError(f"every loop closure's precision ({key}) must be positive and finite")
 
 
 def refine_estimate_robust_batch(datas, results, inlier_threshold=3.0, robust_ranges: bool = True, robust_loop_closures: bool = False,
@@ -266,10 +150,7 @@ def refine_estimate_robust_batch(datas, results, inlier_threshold=3.0, robust_ra
         if data.dimension not in (2, 3):
             raise ValueError(f"graph {i}: dimension must be 2 or 3")
         prob, point = _problem_of(data, res, _prior(rws[i], float(min_weight), f_rng), _prior(lws[i], float(min_weight), f_rel))
-        try:
-            _check_precisions(prob, f_rng, f_rel)
-        except ValueError as e:
-            raise ValueError(f"graph {i}: {e}") from None
+        _check_precisions(prob, f_rng, f_rel, f"graph {i}: ")
         if prob.n == 0:  # nothing to refine: the host's answer, as refine_estimate_robust gives it
             out[i] = refine_estimate_robust(data, res, inlier_threshold=cs[i], robust_ranges=f_rng, robust_loop_closures=f_rel,
                                             loop_closure_threshold=crs[i], max_outer=max_outer, inner_iters=inner_iters,
@@ -317,9 +198,7 @@ def refine_estimate_robust_batch(datas, results, inlier_threshold=3.0, robust_ra
                     if with_marginals:
                         covs = group_marginals(h, probs, pts, sels, idx, number)
                     rounds, stage_rounds = h.robust_rounds()
-                infos = [{"cost_initial": r["cost_initial"], "cost_final": r["cost_final"], "iterations": r["lm_iterations"],
-                          "grad_inf": r["grad_inf"], "linear_solver": "device", "engine": "native", "pcg_iters": r["pcg_iters"],
-                          "linear_solves": r["linear_solves"], "setup_ms": r["setup_ms"], "solve_ms": r["solve_ms"]} for r in raw]
+                infos = [_native_info(r, "lm_iterations") for r in raw]
                 loops = [(r["outer_iterations"], r["mu"], bool(r["converged"])) for r in raw]
             for k, (i, prob, pt, info, (w, r, wl, rl), (outer, mu, conv)) in enumerate(zip(idx, probs, pts, infos, per, loops)):
                 if rws[i] is not None:  # prior x GNC

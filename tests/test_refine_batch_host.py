@@ -2,6 +2,10 @@
 ``refine_estimate(engine="python", linear_solver="scipy")`` member by member.  The controller only reorders independent work --
 every member sees the operations of the single loop on the same numbers -- so iterations, costs, poses and landmarks are EQUAL,
 not close."""
+import os
+import shutil
+import subprocess
+
 import numpy as np
 import pytest
 
@@ -128,3 +132,19 @@ def test_member_transitions_follow_the_single_loop():
     m.after_gradient(1.0, 1e-10, 50)
     assert m.after_solve(True, 0, 10.0 - 1e-14, 50) and m.phase == "stopped"  # the decrease is below 1e-14 max(1, f)
     assert _Member(10.0, 0).phase == "stopped"
+
+
+def test_rule_and_drivers_on_scripted_runs_under_sanitizers(tmp_path):
+    """tests/tools/refine_rule_check.cpp: the step rule and the GNC-TLS schedule of csrc/score_refine_rule.hpp under their four
+    drivers, on scripted backends, against lambdas, mus and final states written by hand there; it exits non-zero unless the
+    scripts reach every exit of the rules."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is needed to build the stand-alone program"
+    exe = str(tmp_path / "refine_rule_check")
+    subprocess.run([gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-I", os.path.join(root, "score_amd", "csrc"), "-o", exe,
+                    os.path.join(root, "tests", "tools", "refine_rule_check.cpp")], check=True)
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0 and "ERROR" not in run.stderr and "runtime error" not in run.stderr, run.stderr
+    assert "every exit reached" in run.stdout
