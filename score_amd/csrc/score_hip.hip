@@ -4346,6 +4346,7 @@ struct score_refine {
 #include "score_gn_robust_batch.hpp"
 #include "score_group_pcg.hpp"
 #include "score_marginals_batch.hpp"
+#include "score_spectrum_batch.hpp"
 
 // Local refinement of a group of graphs in lock-step (score_gn_batch.hpp): the union state, blocks and gathers here, the
 // chain factorisation and M^-1 through the linear-mode handle `lin` on the union pattern, the per-member conjugate-gradient
@@ -4368,6 +4369,7 @@ struct score_refine_batch {
     std::vector<double> part_host;
     std::vector<int32_t> word_host;
     score::GbmWork mvb;  // marginal covariances of the members (score_marginals_batch.hpp)
+    score::GspWork spb;  // lowest eigenpairs of the members (score_spectrum_batch.hpp)
     // robust refinement (score_gn_robust_batch.hpp): the measured precisions beside rng_prec / rel_kappa / rel_tau (which hold the
     // weighted ones during a robust run, and after one with keep_weights), residuals, weights, per-workgroup partials, the
     // members' parameters; they come with the first robust call.  U keeps rng_prec / rel_kappa / rel_tau on the host for them.
@@ -4897,6 +4899,24 @@ int score_refine_batch_marginals(score_refine_batch* b, const double* poses, con
         require(poses && (b->U.lms_size == 0 || landmarks), "score_refine_batch_marginals: the points are missing");
         AbiEnv::Scope scope(b->device, false);
         return score::gbm_solve(*b, poses, landmarks, var_ptr, vars, rel_tol, max_iters, block_width, joint, residuals, iters, info);
+    });
+}
+int score_refine_batch_spectrum(score_refine_batch* b, const double* poses, const double* landmarks, int32_t k, double rel_tol,
+                                int32_t max_iters, double shift_rel, double* values, double* vectors, double* residuals,
+                                int32_t* iterations, double* h_max, score_spectrum_batch_info* info) {
+    return abi_call([&] {
+        require(b != nullptr, "score_refine_batch_spectrum: null handle");
+        require(poses && (b->U.lms_size == 0 || landmarks), "score_refine_batch_spectrum: the points are missing");
+        AbiEnv::Scope scope(b->device, false);
+        return score::gsp_solve(*b, poses, landmarks, k, rel_tol, max_iters, shift_rel, values, vectors, residuals, iterations, h_max, info);
+    });
+}
+int score_spectrum_ritz(int32_t count, const double* GA, const double* GB, double* theta, double* coef, int32_t* status, int32_t* kept) {
+    return abi_call([&] {
+        AbiEnv::require_device(0);
+        AbiEnv::Scope scope(0, false);
+        score::gsp_ritz_alone(count, GA, GB, theta, coef, status, kept);
+        return 0;
     });
 }
 int score_refine_batch_robust_run(score_refine_batch* b, const score_refine_robust_settings* rs, int32_t n_settings, const double* poses_in,

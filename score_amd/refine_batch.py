@@ -155,6 +155,14 @@ class RefineBatchHandle:
 
         return batch_columns(self, points, ids_per_member, rel_tol, max_iters, block_width)
 
+    def spectrum(self, points, k, rel_tol: float = 1e-9, max_iters: int = 200, shift: float = 1e-8):
+        """``score_refine_batch_spectrum`` at ``points`` (include/score_spectrum_batch.h): the ``k`` lowest eigenpairs of
+        every member's H = J'J.  Returns (return code, per member ``(values, vectors k x n_g, residuals, iterations,
+        converged, h_max)``, the call's info record); the handle is left as it was found."""
+        from .spectrum_batch import batch_spectrum
+
+        return batch_spectrum(self, points, k, rel_tol, max_iters, shift)
+
     def _flat_points(self, points):
         if len(points) != len(self.probs):
             raise ValueError("one point per member expected")
