@@ -52,13 +52,40 @@ SCORE_GN_HD const double* gn_point2(const double* X, int64_t Np, int64_t v) {
     return v < Np ? X + 3 * v + 1 : X + 3 * Np + 2 * (v - Np);
 }
 
-// relative-pose measurement i -> j.  Local unknowns [th_i, x_i, y_i, th_j, x_j, y_j].
-// Returns the cost r'r; with H / g non-null also J'J (6 x 6, row-major) and J'r (6).
-SCORE_GN_HD double gn_rel_block(double thi, double xi, double yi, double thj, double xj, double yj, const double* tm,
-                                const double* Rm, double kappa, double tau, double* H, double* g) {
+// What a measurement's block is made of, stated once per kind: gn_*_jac gives the whitened residual r and, with_jac, the
+// Jacobian J of r in the measurement's local unknowns (rows in the order of r[]); gn_*_block forms the cost r'r and the
+// products J'J and J'r of it (gn_normal_products), the posterior samples (score_samples.hpp) form J'z for their own z
+// (gn_jt_vec).
+template <int N>
+SCORE_GN_HD void gn_normal_products(const double (*J)[N], const double* r, double* H, double* g) {  // H = J'J (row-major), g = J'r
+    for (int a = 0; a < N; ++a) {
+        double ga = 0.0;
+        for (int k = 0; k < N; ++k) ga += J[k][a] * r[k];
+        g[a] = ga;
+        for (int b = 0; b < N; ++b) {
+            double h = 0.0;
+            for (int k = 0; k < N; ++k) h += J[k][a] * J[k][b];
+            H[a * N + b] = h;
+        }
+    }
+}
+template <int N>
+SCORE_GN_HD void gn_jt_vec(const double (*J)[N], const double* z, double* out) {  // out = J'z, summed over the rows in ascending order
+#pragma unroll
+    for (int a = 0; a < N; ++a) {
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < N; ++k) s += J[k][a] * z[k];
+        out[a] = s;
+    }
+}
+
+// relative-pose measurement i -> j.  Local unknowns [th_i, x_i, y_i, th_j, x_j, y_j].  r (6): sqrt(kappa) (t_j - t_i - R_i tm),
+// then sqrt(tau) (R_j - R_i Rm) row-major; with_jac: J = dr/d(local unknowns), 6 x 6.
+SCORE_GN_HD void gn_rel_jac(double thi, double xi, double yi, double thj, double xj, double yj, const double* tm,
+                            const double* Rm, double kappa, double tau, double* r, double (*J)[6], bool with_jac) {
     const double sk = sqrt(kappa), st = sqrt(tau);
     const double ci = cos(thi), si = sin(thi), cj = cos(thj), sj = sin(thj);
-    double r[6];
     r[0] = sk * (xj - xi - (ci * tm[0] - si * tm[1]));
     r[1] = sk * (yj - yi - (si * tm[0] + ci * tm[1]));
     // R_j - R_i Rm, row-major
@@ -66,10 +93,7 @@ SCORE_GN_HD double gn_rel_block(double thi, double xi, double yi, double thj, do
     r[3] = st * (-sj - (ci * Rm[1] - si * Rm[3]));
     r[4] = st * (sj - (si * Rm[0] + ci * Rm[2]));
     r[5] = st * (cj - (si * Rm[1] + ci * Rm[3]));
-    double cost = 0.0;
-    for (int k = 0; k < 6; ++k) cost += r[k] * r[k];
-    if (!H) return cost;
-    double J[6][6];
+    if (!with_jac) return;
     for (int a = 0; a < 6; ++a)
         for (int b = 0; b < 6; ++b) J[a][b] = 0.0;
     // d(R_i tm)/dth_i
@@ -82,29 +106,38 @@ SCORE_GN_HD double gn_rel_block(double thi, double xi, double yi, double thj, do
     J[4][0] = -st * (ci * Rm[0] - si * Rm[2]);
     J[5][0] = -st * (ci * Rm[1] - si * Rm[3]);
     J[2][3] = st * -sj; J[3][3] = st * -cj; J[4][3] = st * cj; J[5][3] = st * -sj;
-    for (int a = 0; a < 6; ++a) {
-        double ga = 0.0;
-        for (int k = 0; k < 6; ++k) ga += J[k][a] * r[k];
-        g[a] = ga;
-        for (int b = 0; b < 6; ++b) {
-            double h = 0.0;
-            for (int k = 0; k < 6; ++k) h += J[k][a] * J[k][b];
-            H[a * 6 + b] = h;
-        }
-    }
+}
+// Returns the cost r'r; with H / g non-null also J'J (6 x 6, row-major) and J'r (6).
+SCORE_GN_HD double gn_rel_block(double thi, double xi, double yi, double thj, double xj, double yj, const double* tm,
+                                const double* Rm, double kappa, double tau, double* H, double* g) {
+    double r[6], J[6][6];
+    gn_rel_jac(thi, xi, yi, thj, xj, yj, tm, Rm, kappa, tau, r, J, H != nullptr);
+    double cost = 0.0;
+    for (int k = 0; k < 6; ++k) cost += r[k] * r[k];
+    if (!H) return cost;
+    gn_normal_products<6>(J, r, H, g);
     return cost;
 }
 
-// range measurement between points a and b.  Local unknowns [xa, ya, xb, yb]; H 4 x 4, g 4.
-SCORE_GN_HD double gn_range_block(double xa, double ya, double xb, double yb, double dist, double prec, double* H, double* g) {
+// range measurement between points a and b.  Local unknowns [xa, ya, xb, yb].  Returns r = sqrt(prec) (|a - b| - dist); J
+// (with_jac): its one row (4).
+SCORE_GN_HD double gn_range_jac(double xa, double ya, double xb, double yb, double dist, double prec, double* J, bool with_jac) {
     const double sw = sqrt(prec);
     const double dx = xa - xb, dy = ya - yb;
     const double rho = sqrt(dx * dx + dy * dy);
     const double r = sw * (rho - dist);
-    if (H) {
+    if (with_jac) {
         const bool tiny = !(rho > 1e-12);
         const double g0 = tiny ? 0.0 : dx / rho, g1 = tiny ? 0.0 : dy / rho;
-        const double J[4] = {sw * g0, sw * g1, -sw * g0, -sw * g1};
+        J[0] = sw * g0; J[1] = sw * g1; J[2] = -sw * g0; J[3] = -sw * g1;
+    }
+    return r;
+}
+// the cost r'r; with H / g: H 4 x 4, g 4.
+SCORE_GN_HD double gn_range_block(double xa, double ya, double xb, double yb, double dist, double prec, double* H, double* g) {
+    double J[4];
+    const double r = gn_range_jac(xa, ya, xb, yb, dist, prec, J, H != nullptr);
+    if (H) {
         for (int a = 0; a < 4; ++a) {
             g[a] = J[a] * r;
             for (int b = 0; b < 4; ++b) H[a * 4 + b] = J[a] * J[b];
@@ -113,10 +146,17 @@ SCORE_GN_HD double gn_range_block(double xa, double ya, double xb, double yb, do
     return r * r;
 }
 
-// landmark prior.  Local unknowns [lx, ly]; H holds the two diagonal entries, g 2.
-SCORE_GN_HD double gn_prior_block(double lx, double ly, const double* t0, double prec, double* H, double* g) {
+// landmark prior.  Local unknowns [lx, ly].  r (2) = sqrt(prec) (l - t0); returns the Jacobian: sqrt(prec) times the identity.
+SCORE_GN_HD double gn_prior_jac(double lx, double ly, const double* t0, double prec, double* r) {
     const double sw = sqrt(prec);
-    const double r0 = sw * (lx - t0[0]), r1 = sw * (ly - t0[1]);
+    r[0] = sw * (lx - t0[0]); r[1] = sw * (ly - t0[1]);
+    return sw;
+}
+// the cost; H holds the two diagonal entries, g 2.
+SCORE_GN_HD double gn_prior_block(double lx, double ly, const double* t0, double prec, double* H, double* g) {
+    double r[2];
+    const double sw = gn_prior_jac(lx, ly, t0, prec, r);
+    const double r0 = r[0], r1 = r[1];
     if (H) { H[0] = prec; H[1] = prec; g[0] = sw * r0; g[1] = sw * r1; }
     return r0 * r0 + r1 * r1;
 }
@@ -157,14 +197,13 @@ SCORE_GN_HD const double* gn_point3(const double* X, int64_t Np, int64_t v) {
     return v < Np ? X + 12 * v + 9 : X + 12 * Np + 3 * (v - Np);
 }
 
-// relative-pose measurement i -> j in 3-D.  Local unknowns [om_i, v_i, om_j, v_j] (12).  Residuals (12):
-// sqrt(kappa) (t_j - t_i - R_i tm), sqrt(tau) (R_j - R_i Rm) row-major.  With H / g: J'J (12 x 12) and J'r.
-SCORE_GN_HD double gn_rel_block3(const double* Xi, const double* Xj, const double* tm, const double* Rm, double kappa, double tau,
-                                 double* H, double* g) {
+// relative-pose measurement i -> j in 3-D.  Local unknowns [om_i, v_i, om_j, v_j] (12).  Residuals r (12):
+// sqrt(kappa) (t_j - t_i - R_i tm), sqrt(tau) (R_j - R_i Rm) row-major; with_jac: J = dr/d(local unknowns), 12 x 12.
+SCORE_GN_HD void gn_rel_jac3(const double* Xi, const double* Xj, const double* tm, const double* Rm, double kappa, double tau,
+                             double* r, double (*J)[12], bool with_jac) {
     const double sk = sqrt(kappa), st = sqrt(tau);
     const double* Ri = Xi; const double* ti = Xi + 9;
     const double* Rj = Xj; const double* tj = Xj + 9;
-    double r[12];
     for (int a = 0; a < 3; ++a) {
         double rt = 0.0;
         for (int k = 0; k < 3; ++k) rt += Ri[a * 3 + k] * tm[k];
@@ -176,11 +215,8 @@ SCORE_GN_HD double gn_rel_block3(const double* Xi, const double* Xj, const doubl
             for (int k = 0; k < 3; ++k) rr += Ri[a * 3 + k] * Rm[k * 3 + b];
             r[3 + a * 3 + b] = st * (Rj[a * 3 + b] - rr);
         }
-    double cost = 0.0;
-    for (int k = 0; k < 12; ++k) cost += r[k] * r[k];
-    if (!H) return cost;
+    if (!with_jac) return;
     // J (12 x 12): columns [om_i 0..2 | v_i 3..5 | om_j 6..8 | v_j 9..11]
-    double J[12][12];
     for (int a = 0; a < 12; ++a)
         for (int b = 0; b < 12; ++b) J[a][b] = 0.0;
     // translation rows: d/dv_j = I, d/dv_i = -I, d/dom_i = R_i [tm]x
@@ -216,29 +252,36 @@ SCORE_GN_HD double gn_rel_block3(const double* Xi, const double* Xj, const doubl
                 J[3 + a * 3 + b][c] = -st * y;
             }
     }
-    for (int a = 0; a < 12; ++a) {
-        double ga = 0.0;
-        for (int k = 0; k < 12; ++k) ga += J[k][a] * r[k];
-        g[a] = ga;
-        for (int b = 0; b < 12; ++b) {
-            double h = 0.0;
-            for (int k = 0; k < 12; ++k) h += J[k][a] * J[k][b];
-            H[a * 12 + b] = h;
-        }
-    }
+}
+// the cost r'r; with H / g: J'J (12 x 12) and J'r.
+SCORE_GN_HD double gn_rel_block3(const double* Xi, const double* Xj, const double* tm, const double* Rm, double kappa, double tau,
+                                 double* H, double* g) {
+    double r[12], J[12][12];
+    gn_rel_jac3(Xi, Xj, tm, Rm, kappa, tau, r, J, H != nullptr);
+    double cost = 0.0;
+    for (int k = 0; k < 12; ++k) cost += r[k] * r[k];
+    if (!H) return cost;
+    gn_normal_products<12>(J, r, H, g);
     return cost;
 }
 
-// range between points a and b in 3-D.  Local unknowns [pa (3), pb (3)]; H 6 x 6, g 6.
-SCORE_GN_HD double gn_range_block3(const double* pa, const double* pb, double dist, double prec, double* H, double* g) {
+// range between points a and b in 3-D.  Local unknowns [pa (3), pb (3)].  Returns r; J (with_jac): its one row (6).
+SCORE_GN_HD double gn_range_jac3(const double* pa, const double* pb, double dist, double prec, double* J, bool with_jac) {
     const double sw = sqrt(prec);
     const double d[3] = {pa[0] - pb[0], pa[1] - pb[1], pa[2] - pb[2]};
     const double rho = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
     const double r = sw * (rho - dist);
-    if (H) {
+    if (with_jac) {
         const bool tiny = !(rho > 1e-12);
-        double J[6];
         for (int k = 0; k < 3; ++k) { J[k] = tiny ? 0.0 : sw * d[k] / rho; J[3 + k] = -J[k]; }
+    }
+    return r;
+}
+// the cost r'r; with H / g: H 6 x 6, g 6.
+SCORE_GN_HD double gn_range_block3(const double* pa, const double* pb, double dist, double prec, double* H, double* g) {
+    double J[6];
+    const double r = gn_range_jac3(pa, pb, dist, prec, J, H != nullptr);
+    if (H) {
         for (int a = 0; a < 6; ++a) {
             g[a] = J[a] * r;
             for (int b = 0; b < 6; ++b) H[a * 6 + b] = J[a] * J[b];
@@ -247,12 +290,19 @@ SCORE_GN_HD double gn_range_block3(const double* pa, const double* pb, double di
     return r * r;
 }
 
-// landmark prior in 3-D.  H holds the three diagonal entries, g 3.
-SCORE_GN_HD double gn_prior_block3(const double* l, const double* t0, double prec, double* H, double* g) {
+// landmark prior in 3-D.  r (3) = sqrt(prec) (l - t0); returns the Jacobian: sqrt(prec) times the identity.
+SCORE_GN_HD double gn_prior_jac3(const double* l, const double* t0, double prec, double* r) {
     const double sw = sqrt(prec);
+    for (int k = 0; k < 3; ++k) r[k] = sw * (l[k] - t0[k]);
+    return sw;
+}
+// the cost; H holds the three diagonal entries, g 3.
+SCORE_GN_HD double gn_prior_block3(const double* l, const double* t0, double prec, double* H, double* g) {
+    double r3[3];
+    const double sw = gn_prior_jac3(l, t0, prec, r3);
     double c = 0.0;
     for (int k = 0; k < 3; ++k) {
-        const double r = sw * (l[k] - t0[k]);
+        const double r = r3[k];
         c += r * r;
         if (H) { H[k] = prec; g[k] = sw * r; }
     }

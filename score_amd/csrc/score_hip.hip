@@ -4095,6 +4095,7 @@ struct AbiEnv {
 
 #include "score_marginals.hpp"
 #include "score_spectrum.hpp"
+#include "score_samples.hpp"
 #include "score_gn_robust.hpp"
 
 // Residuals and weights of a robust refinement handle (the single one or the group: rb_* buffers, ranges then loop closures) as
@@ -4127,6 +4128,7 @@ struct score_refine {
     std::vector<double> part_host;
     score::MvWork mv;  // marginal covariances (score_marginals.hpp)
     score::SpWork sp;  // lowest eigenpairs of H (score_spectrum.hpp)
+    score::PsWork ps;  // posterior samples (score_samples.hpp)
     // robust refinement (score_gn_robust.hpp): the measured precisions beside rng_prec / rel_kappa / rel_tau (which hold a robust
     // run's weighted ones while it lasts), residuals, weights, per-block partials; they come with the first robust call
     DevBuf<double> rb_prec0, rb_kappa0, rb_tau0, rb_r_rng, rb_r_lc, rb_w_rng, rb_w_lc, rb_part;
@@ -4814,6 +4816,17 @@ int score_refine_marginals(score_refine* r, const double* poses, const double* l
         require(r && poses && (r->P.Nl == 0 || landmarks));
         AbiEnv::Scope scope(r->device, false);
         return score::mv_solve(*r, poses, landmarks, vars, n_vars, rel_tol, max_iters, block_width, joint, residuals, iters, info);
+    });
+}
+int score_refine_samples(score_refine* r, const double* poses, const double* landmarks, uint64_t seed, int64_t first_sample,
+                         int32_t n_samples, const int32_t* vars, int32_t n_vars, double rel_tol, int32_t max_iters, int32_t block_width,
+                         double* moments, double* means, double* steps, double* rhs, double* noise, double* residuals, int32_t* iters,
+                         score_samples_info* info) {
+    return abi_call([&] {
+        require(r && poses && (r->P.Nl == 0 || landmarks));
+        AbiEnv::Scope scope(r->device, false);
+        return score::ps_solve(*r, poses, landmarks, seed, first_sample, n_samples, vars, n_vars, rel_tol, max_iters, block_width, moments,
+                               means, steps, rhs, noise, residuals, iters, info);
     });
 }
 int score_refine_spectrum(score_refine* r, const double* poses, const double* landmarks, int32_t k, double rel_tol, int32_t max_iters,

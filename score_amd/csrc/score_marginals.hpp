@@ -9,7 +9,8 @@
 // be one fixed SPD operator for the whole solve).  New here: the product over several vectors and the vector updates of the
 // block.  Shared with the group's iteration (score_group_pcg.hpp) and the spectrum (score_spectrum.hpp): the tiles and the
 // product of one tile (mv_tiles, mv_product_tile), the slot counts (mv_slots, mv_with_slots), the breakdown test
-// (pcg_finite) and the variables' unknowns (mv_variable_unknowns).
+// (pcg_finite) and the variables' unknowns (mv_variable_unknowns).  Shared with the posterior samples (score_samples.hpp):
+// the iteration itself (mv_block_pcg), from their own right-hand sides.
 //
 // Vectors of a block are stored one after the other, stride n (the layout PrecArgs::vec_stride expects).  One iteration:
 //   k_mv_product    w_c = H p_c for every live column from ONE pass over the CSR matrix, per-workgroup partials of p_c'w_c
@@ -330,6 +331,52 @@ struct MvWork {
     }
 };
 
+// w_c = H p_in_c as `m` says, compiled for NV vectors
+inline void mv_launch_product(const MvArgs& m, int NV, hipStream_t st) {
+    mv_with_slots(NV, [&](auto nv) {
+        hipLaunchKernelGGL(k_mv_product<decltype(nv)::value>, dim3((unsigned)m.n_tiles), dim3(kMvThreads), 0, st, m);
+    });
+}
+
+// The gated iteration of a block whose x, r and done words are set (k_mv_rhs here, k_ps_begin of score_samples.hpp): the
+// first application of M^-1 and direction, then at most max_iters iterations queued in chunks.  flags: the block's words as
+// last read.  Stated once: the marginals' columns and the posterior samples' draws both run it.
+inline void mv_block_pcg(HipBackend& be, MvWork& W, MvArgs& a, int NV, int n_rblocks, int max_iters, std::vector<int32_t>& flags,
+                         hipStream_t st) {
+    // z = M^-1 r of every column of the block, the chain kernel's partials of r'z into `rz`
+    auto precondition = [&](double* rz) {
+        be.precondition_block(W.r.d, W.z.d, W.p_scratch.d, W.w.d, NV, a.n, W.flags.d + kMvZero, rz, W.zb.d);
+    };
+    double* rz_cur = W.rz0.d; double* rz_nxt = W.rz1.d;
+    precondition(rz_cur);
+    a.first = 1; a.rz_new = rz_cur; a.rz_old = nullptr;
+    hipLaunchKernelGGL(k_mv_direction, dim3((unsigned)n_rblocks, (unsigned)NV), dim3(kMvThreads), 0, st, a);
+    a.first = 0;
+    queue_in_chunks(max_iters, [&]() {
+        a.all_columns = 0; a.p_in = W.p.d;
+        mv_launch_product(a, NV, st);
+        a.rz_new = rz_cur;
+        hipLaunchKernelGGL(k_mv_step, dim3((unsigned)n_rblocks, (unsigned)NV), dim3(kMvThreads), 0, st, a);
+        precondition(rz_nxt);
+        a.rz_new = rz_nxt; a.rz_old = rz_cur;
+        hipLaunchKernelGGL(k_mv_direction, dim3((unsigned)n_rblocks, (unsigned)NV), dim3(kMvThreads), 0, st, a);
+        std::swap(rz_cur, rz_nxt);
+    }, [&]() {
+        staged_d2h(flags.data(), W.flags.d, (size_t)kMvFlagWords * sizeof(int32_t), st);
+        return std::all_of(flags.begin() + kMvDone, flags.begin() + kMvDone + NV, [](int32_t f) { return f != 0; });
+    });
+}
+
+// The block's MvArgs on a refinement handle's matrix and buffers (the caller adds its own right-hand sides and outputs)
+inline MvArgs mv_block_args(HipBackend& be, MvWork& W, long long n, double rel_tol) {
+    MvArgs a{};
+    a.ptr = be.Kset.mat.ptr.d; a.col = be.Kset.mat.col.d; a.val = be.Kset.mat.val.d;
+    a.tiles = W.tiles.d; a.n_tiles = W.n_tiles; a.n = n; a.flags = W.flags.d;
+    a.x = W.x.d; a.r = W.r.d; a.z = W.z.d; a.p = W.p.d; a.w = W.w.d; a.pw_part = W.pw_part.d;
+    a.n_prec = be.n_prec; a.tol2 = rel_tol * rel_tol; a.ref = W.ref.d; a.res_part = W.res_part.d;
+    return a;
+}
+
 // The solve.  Refine: score_refine (its point, blocks and gather, its linear-mode handle, its MvWork).
 template <class Refine>
 int mv_solve(Refine& R, const double* poses, const double* landmarks, const int32_t* vars, int32_t n_vars, double rel_tol,
@@ -364,21 +411,8 @@ int mv_solve(Refine& R, const double* poses, const double* landmarks, const int3
     }
     staged_h2d(d_sel.d, sel.data(), (size_t)C * sizeof(int32_t), st);
     const int n_rblocks = (int)((n + kMvThreads - 1) / kMvThreads);
-    MvArgs a{};
-    a.ptr = be.Kset.mat.ptr.d; a.col = be.Kset.mat.col.d; a.val = be.Kset.mat.val.d;
-    a.tiles = W.tiles.d; a.n_tiles = W.n_tiles; a.n = n; a.flags = W.flags.d;
-    a.x = W.x.d; a.r = W.r.d; a.z = W.z.d; a.p = W.p.d; a.w = W.w.d; a.pw_part = W.pw_part.d;
-    a.n_prec = be.n_prec; a.tol2 = rel_tol * rel_tol; a.ref = W.ref.d;
-    a.sel = d_sel.d; a.C = C; a.res_part = W.res_part.d; a.joint = d_joint.d;
-    auto product = [&](const MvArgs& m) {
-        mv_with_slots(NV, [&](auto nv) {
-            hipLaunchKernelGGL(k_mv_product<decltype(nv)::value>, dim3((unsigned)m.n_tiles), dim3(kMvThreads), 0, st, m);
-        });
-    };
-    // z = M^-1 r of every column of the block, the chain kernel's partials of r'z into `rz`
-    auto precondition = [&](double* rz) {
-        be.precondition_block(W.r.d, W.z.d, W.p_scratch.d, W.w.d, NV, n, W.flags.d + kMvZero, rz, W.zb.d);
-    };
+    MvArgs a = mv_block_args(be, W, n, rel_tol);
+    a.sel = d_sel.d; a.C = C; a.joint = d_joint.d;
     const double t1 = now_ms();
     std::vector<int32_t> flags((size_t)kMvFlagWords), col_done((size_t)C, 0), col_iters((size_t)C, 0);
     std::vector<double> res_part((size_t)NV * (size_t)n_rblocks), col_res((size_t)C, 0.0);
@@ -395,28 +429,11 @@ int mv_solve(Refine& R, const double* poses, const double* landmarks, const int3
             HIP_CHECK(hipMemcpyAsync(W.x.d, be.xtu.d, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
             flags[kMvDone] = ok ? 1 : 0; flags[kMvIters] = used;
         } else {
-            double* rz_cur = W.rz0.d; double* rz_nxt = W.rz1.d;
-            precondition(rz_cur);
-            a.first = 1; a.rz_new = rz_cur; a.rz_old = nullptr;
-            hipLaunchKernelGGL(k_mv_direction, dim3((unsigned)n_rblocks, (unsigned)NV), dim3(kMvThreads), 0, st, a);
-            a.first = 0;
-            queue_in_chunks(max_iters, [&]() {
-                a.all_columns = 0; a.p_in = W.p.d;
-                product(a);
-                a.rz_new = rz_cur;
-                hipLaunchKernelGGL(k_mv_step, dim3((unsigned)n_rblocks, (unsigned)NV), dim3(kMvThreads), 0, st, a);
-                precondition(rz_nxt);
-                a.rz_new = rz_nxt; a.rz_old = rz_cur;
-                hipLaunchKernelGGL(k_mv_direction, dim3((unsigned)n_rblocks, (unsigned)NV), dim3(kMvThreads), 0, st, a);
-                std::swap(rz_cur, rz_nxt);
-            }, [&]() {
-                staged_d2h(flags.data(), W.flags.d, (size_t)kMvFlagWords * sizeof(int32_t), st);
-                return std::all_of(flags.begin() + kMvDone, flags.begin() + kMvDone + NV, [](int32_t f) { return f != 0; });
-            });
+            mv_block_pcg(be, W, a, NV, n_rblocks, max_iters, flags, st);
         }
         // the true residual of every column of the block (one more product, w = H x), the rows of S
         a.all_columns = 1; a.p_in = W.x.d;
-        product(a);
+        mv_launch_product(a, NV, st);
         hipLaunchKernelGGL(k_mv_residual, dim3((unsigned)n_rblocks, (unsigned)live), dim3(kMvThreads), 0, st, a);
         hipLaunchKernelGGL(k_mv_gather, dim3((unsigned)((C + kMvThreads - 1) / kMvThreads), (unsigned)live), dim3(kMvThreads), 0, st, a);
         HIP_CHECK(hipGetLastError());
