@@ -4348,6 +4348,7 @@ struct score_refine {
 #include "score_gn_robust_batch.hpp"
 #include "score_group_pcg.hpp"
 #include "score_marginals_batch.hpp"
+#include "score_samples_batch.hpp"
 #include "score_spectrum_batch.hpp"
 
 // Local refinement of a group of graphs in lock-step (score_gn_batch.hpp): the union state, blocks and gathers here, the
@@ -4372,6 +4373,7 @@ struct score_refine_batch {
     std::vector<int32_t> word_host;
     score::GbmWork mvb;  // marginal covariances of the members (score_marginals_batch.hpp)
     score::GspWork spb;  // lowest eigenpairs of the members (score_spectrum_batch.hpp)
+    score::GbsWork gbs;  // posterior samples of the members (score_samples_batch.hpp)
     // robust refinement (score_gn_robust_batch.hpp): the measured precisions beside rng_prec / rel_kappa / rel_tau (which hold the
     // weighted ones during a robust run, and after one with keep_weights), residuals, weights, per-workgroup partials, the
     // members' parameters; they come with the first robust call.  U keeps rng_prec / rel_kappa / rel_tau on the host for them.
@@ -4912,6 +4914,18 @@ int score_refine_batch_marginals(score_refine_batch* b, const double* poses, con
         require(poses && (b->U.lms_size == 0 || landmarks), "score_refine_batch_marginals: the points are missing");
         AbiEnv::Scope scope(b->device, false);
         return score::gbm_solve(*b, poses, landmarks, var_ptr, vars, rel_tol, max_iters, block_width, joint, residuals, iters, info);
+    });
+}
+int score_refine_batch_samples(score_refine_batch* b, const double* poses, const double* landmarks, const uint64_t* seeds,
+                               int64_t first_sample, const int32_t* n_samples, const int32_t* var_ptr, const int32_t* vars, double rel_tol,
+                               int32_t max_iters, int32_t block_width, double* moments, double* means, double* steps, double* rhs,
+                               double* noise, double* residuals, int32_t* iters, int32_t* determined, score_samples_batch_info* info) {
+    return abi_call([&] {
+        require(b != nullptr, "score_refine_batch_samples: null handle");
+        require(poses && (b->U.lms_size == 0 || landmarks), "score_refine_batch_samples: the points are missing");
+        AbiEnv::Scope scope(b->device, false);
+        return score::gbs_solve(*b, poses, landmarks, seeds, first_sample, n_samples, var_ptr, vars, rel_tol, max_iters, block_width,
+                                moments, means, steps, rhs, noise, residuals, iters, determined, info);
     });
 }
 int score_refine_batch_spectrum(score_refine_batch* b, const double* poses, const double* landmarks, int32_t k, double rel_tol,

@@ -163,6 +163,17 @@ class RefineBatchHandle:
 
         return batch_spectrum(self, points, k, rel_tol, max_iters, shift)
 
+    def samples(self, points, ids_per_member, n_samples, seeds, first_sample: int = 0, rel_tol: float = 1e-10, max_iters: int = 4000,
+                block_width: int = 16, with_rhs: bool = False, with_noise: bool = False):
+        """``score_refine_batch_samples`` at ``points`` (include/score_samples_batch.h): ``n_samples`` draws of every member
+        (an integer or one per member; 0: the member takes no part) from the streams of ``seeds``, the steps of the
+        member-local variables ``ids_per_member``.  Returns (return code, per member the dict of ``SamplesHandle.draw`` plus
+        ``determined``, the call's info record); the handle is left as it was found."""
+        from .samples_batch import batch_draws
+
+        return batch_draws(self, points, ids_per_member, n_samples, seeds, first_sample, rel_tol, max_iters, block_width, with_rhs,
+                           with_noise)
+
     def _flat_points(self, points):
         if len(points) != len(self.probs):
             raise ValueError("one point per member expected")
@@ -255,7 +266,7 @@ class RefineBatchHandle:
 
 def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-10, range_weights=None, loop_closure_weights=None,
                           engine: str = "native", lib_path: Optional[str] = None, solver_settings: Optional[dict] = None,
-                          max_group: int = 64, marginals=None):
+                          max_group: int = 64, marginals=None, samples=None, samples_seed: int = 0):
     """``refine_estimate`` for many graphs at once: ``datas`` and ``results`` member by member, ``range_weights`` /
     ``loop_closure_weights`` lists with one entry (an array as ``refine_estimate`` takes it, or None) per member -- they only
     scale precisions.  The members are grouped by dimension, in chunks of at most ``max_group``, each group one device handle
@@ -265,9 +276,14 @@ def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-1
     ``marginals``: True, or a list with one entry per graph as ``marginal_covariances_batch`` takes ``variables`` -- every
     group's handle then also computes the marginal covariances at the refined points before it is closed (one create for
     both), and ``info["marginals"]`` is the ``(cov, marginals_info)`` of ``marginal_covariances_batch`` for that graph (None
-    for a graph without unknowns)."""
+    for a graph without unknowns).
+    ``samples``: a number of draws S -- every group's handle then also draws S posterior samples of every member at the refined
+    points (``posterior_samples_batch``'s call on the same handle: default variables, graph i from the stream of
+    ``samples_seed + i``), and ``info["samples"]`` is that graph's ``(Samples, samples_info)`` (None for a graph without
+    unknowns).  Without the keyword nothing changes."""
     from .marginals import _select
     from .marginals_batch import _variables_of, group_marginals
+    from .samples_batch import _check_draw_arguments, group_samples
 
     if engine not in ("native", "python"):
         raise ValueError("engine must be 'native' or 'python'")
@@ -280,9 +296,13 @@ def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-1
     lws = _weights_of(loop_closure_weights, len(datas), "loop_closure_weights")
     with_marginals = marginals is not None and marginals is not False
     wanted = _variables_of(None if marginals is True else marginals, len(datas)) if with_marginals else None
+    with_samples = samples is not None and samples is not False
+    if with_samples:
+        _check_draw_arguments([samples], 0, 16, 1e-10, 4000)
     out: list = [None] * len(datas)
     groups: dict = {}
     sel_of: dict = {}
+    draw_sel_of: dict = {}
     for i, (data, res) in enumerate(zip(datas, results)):
         if data.dimension not in (2, 3):
             raise ValueError(f"graph {i}: dimension must be 2 or 3")
@@ -292,12 +312,16 @@ def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-1
                                      range_weights=rws[i], loop_closure_weights=lws[i])
             if with_marginals:
                 out[i][1]["marginals"] = None
+            if with_samples:
+                out[i][1]["samples"] = None
             continue
         if with_marginals:  # (the selection's errors before any work)
             try:
                 sel_of[i] = _select(prob, wanted[i])
             except ValueError as e:
                 raise ValueError(f"graph {i}: {e}") from None
+        if with_samples:
+            draw_sel_of[i] = _select(prob, None)
         groups.setdefault(data.dimension, []).append((i, prob, point))
     number = 0
     for dim in sorted(groups):
@@ -306,10 +330,21 @@ def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-1
             chunk = members[c0 : c0 + int(max_group)]
             probs, points = [m[1] for m in chunk], [m[2] for m in chunk]
             covs, sels = None, [sel_of.get(m[0]) for m in chunk]
+            idx = [m[0] for m in chunk]
+
+            def draws(handle, pts, costs, which):
+                """(Samples, info) per member at the refined points, retracted onto the refined estimates"""
+                ests = [_as_results(p, pt, results[i], f) for p, pt, i, f in zip(probs, pts, idx, costs)]
+                return group_samples(handle, probs, pts, ests, [draw_sel_of[i] for i in idx], idx, number, [int(samples)] * len(idx),
+                                     [int(samples_seed) + i for i in idx], engine=which)
+
+            drawn = None
             if engine == "python":
                 pts, S, rounds = _python_lock_step(probs, points, max_iters, tol)
                 if with_marginals:
                     covs = group_marginals(None, probs, pts, sels, [m[0] for m in chunk], number, engine="python")
+                if with_samples:
+                    drawn = draws(None, pts, [s.f for s in S], "python")
                 infos = [{"cost_initial": s.cost_initial, "cost_final": s.f, "iterations": s.iterations, "grad_inf": s.gnorm,
                           "linear_solver": "scipy", "engine": "python", "pcg_iters": 0, "linear_solves": s.linear_solves} for s in S]
             else:
@@ -317,12 +352,16 @@ def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-1
                     pts, raw = h.run(points, max_iters, tol)
                     if with_marginals:
                         covs = group_marginals(h, probs, pts, sels, [m[0] for m in chunk], number)
+                    if with_samples:
+                        drawn = draws(h, pts, [r["cost_final"] for r in raw], "device")
                 rounds = max(r["linear_solves"] for r in raw)
                 infos = [_native_info(r) for r in raw]
             for k, ((i, prob, _), pt, info) in enumerate(zip(chunk, pts, infos)):
                 info["group"], info["rounds"] = number, rounds
                 if with_marginals:
                     info["marginals"] = covs[k]
+                if with_samples:
+                    info["samples"] = drawn[k]
                 out[i] = (_as_results(prob, pt, results[i], info["cost_final"]), info)
             number += 1
     return out

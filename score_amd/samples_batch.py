@@ -1,0 +1,263 @@
+"""Posterior samples of many graphs at once (include/score_samples_batch.h, csrc/score_samples_batch.hpp).
+
+``posterior_samples`` takes one graph, builds one refinement handle and runs a block PCG whose launches are latency-bound on
+a small world.  ``posterior_samples_batch`` hands the graphs to the device as groups, as ``refine_estimate_batch`` does: the
+group handle's union matrix H = J'J is block diagonal, so one union vector carries one draw of every member, and a block of
+up to 16 union vectors advances 16 draws of all members per pass over the union matrix (``score_refine_batch_samples``).
+Every (member, draw) pair has its own alpha, beta, stopping gate and verdict, every member its own noise stream and its own
+probe column: graph i's draws are those ``posterior_samples(..., seed=seed_i)`` forms on it alone, up to the rounding of the
+two iterations (the noise is the same stream, the right-hand sides the same sums).
+
+``RefineBatchHandle.samples`` is the raw call on a kept group handle, so a study refines and draws with one create;
+``refine_estimate_batch(..., samples=S)`` does exactly that.  ``engine="python"`` is the dense twin
+``samples._python_draws`` graph by graph.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+
+from .marginals import MAX_BLOCK_WIDTH, _problem_and_point, _select
+from .marginals_batch import _variables_of
+from .refine import _Problem3D
+from .refine_robust import _point_arrays
+from .samples import Samples, _moment_sizes, _n_rows, _python_draws, accumulate_moments
+from .solver import _f64p, _i32p
+
+# the symbols include/score_samples_batch.h declares
+SAMPLES_BATCH_SYMBOLS = ["score_refine_batch_samples"]
+_u64p = C.POINTER(C.c_uint64)
+
+
+class ScoreSamplesBatchInfo(C.Structure):
+    _fields_ = [
+        ("members", C.c_int32), ("samples", C.c_int32), ("passes", C.c_int32), ("pcg_iters", C.c_int32), ("unconverged", C.c_int32),
+        ("singular", C.c_int32),
+        ("max_residual", C.c_double), ("setup_ms", C.c_double), ("rhs_ms", C.c_double), ("solve_ms", C.c_double),
+    ]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def _bind(lib: C.CDLL) -> C.CDLL:
+    if getattr(lib, "_score_samples_batch_bound", False):
+        return lib
+    for sym in SAMPLES_BATCH_SYMBOLS:
+        if not hasattr(lib, sym):
+            raise RuntimeError(f"{sym} is missing from the library: rebuild it (the CPU twin has no posterior samples: "
+                               "engine='python' runs there)")
+    lib.score_refine_batch_samples.argtypes = [C.c_void_p, _f64p, _f64p, _u64p, C.c_int64, _i32p, _i32p, _i32p, C.c_double, C.c_int32,
+                                               C.c_int32, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _i32p, _i32p,
+                                               C.POINTER(ScoreSamplesBatchInfo)]
+    lib.score_refine_batch_samples.restype = C.c_int
+    lib._score_samples_batch_bound = True
+    return lib
+
+
+def _per_member(value, count: int, what: str) -> list:
+    if np.ndim(value) == 0:
+        return [value] * count
+    value = list(value)
+    if len(value) != count:
+        raise ValueError(f"{what}: one entry per graph expected ({count}), got {len(value)}")
+    return value
+
+
+def batch_draws(handle, points, ids_per_member, n_samples, seeds, first_sample=0, rel_tol=1e-10, max_iters=4000,
+                block_width=MAX_BLOCK_WIDTH, with_rhs=False, with_noise=False):
+    """``score_refine_batch_samples`` as it is, on a ``RefineBatchHandle``: ``points`` in the problems' own form,
+    ``ids_per_member`` the member-local variable ids of every member (an empty list: no steps), ``n_samples`` and ``seeds`` an
+    integer or one per member (a member with 0 draws takes no part).  Returns (return code, one dict per member, the call's
+    info record).  A member's dict has the keys ``SamplesHandle.draw`` returns -- ``rc`` is 0 iff all ITS draws converged,
+    ``info`` the call's record with the member's own ``samples`` and ``batches`` -- plus ``determined`` (1: its probe passed,
+    0: it failed, -1: no draws)."""
+    probs = handle.probs
+    G = len(probs)
+    if len(points) != G or len(ids_per_member) != G:
+        raise ValueError("one point and one list of variables per member expected")
+    counts = [int(s) for s in _per_member(n_samples, G, "n_samples")]
+    keys = [int(s) & 0xFFFFFFFFFFFFFFFF for s in _per_member(seeds, G, "seeds")]
+    lib = _bind(handle.lib)
+    arrays = [_point_arrays(prob, x) for prob, x in zip(probs, points)]
+    poses = np.ascontiguousarray(np.concatenate([a[0].ravel() for a in arrays]))
+    lms = np.ascontiguousarray(np.concatenate([a[1].ravel() for a in arrays]))
+    ids = [np.asarray(v, dtype=np.int32).ravel() for v in ids_per_member]
+    var_ptr = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(v) for v in ids])]), dtype=np.int32)
+    flat = np.ascontiguousarray(np.concatenate(ids + [np.zeros(0, np.int32)]), dtype=np.int32)
+    dim = 3 if isinstance(probs[0], _Problem3D) else 2
+    ncol = [int(np.where(v < prob.Np, 3 * (dim - 1), dim).sum()) for prob, v in zip(probs, ids)]
+    on = [max(s, 0) for s in counts]  # (a negative count is the library's error to report)
+    n_mom = [_moment_sizes(p)[2] if s else 0 for p, s in zip(probs, on)]
+    n_mean = [p.n if s else 0 for p, s in zip(probs, on)]
+    total = sum(on)
+    moments, means = np.zeros(max(1, sum(n_mom))), np.zeros(max(1, sum(n_mean)))
+    steps = np.zeros(max(1, sum(s * c for s, c in zip(on, ncol))))
+    rhs = np.zeros(max(1, sum(s * p.n for s, p in zip(on, probs)))) if with_rhs else None
+    noise = np.zeros(max(1, sum(s * _n_rows(p) for s, p in zip(on, probs)))) if with_noise else None
+    res, its = np.zeros(max(1, total)), np.zeros(max(1, total), dtype=np.int32)
+    det = np.zeros(G, dtype=np.int32)
+    n_arr = np.ascontiguousarray(counts, dtype=np.int32)
+    seed_arr = np.ascontiguousarray(keys, dtype=np.uint64)
+    info = ScoreSamplesBatchInfo()
+
+    def ptr(a, kind=_f64p):
+        return a.ctypes.data_as(kind) if a is not None else None
+
+    rc = lib.score_refine_batch_samples(handle.h, ptr(poses), ptr(lms) if lms.size else None, ptr(seed_arr, _u64p), int(first_sample),
+                                        ptr(n_arr, _i32p), ptr(var_ptr, _i32p), ptr(flat, _i32p) if flat.size else None, float(rel_tol),
+                                        int(max_iters), int(block_width), ptr(moments), ptr(means), ptr(steps), ptr(rhs), ptr(noise),
+                                        ptr(res), ptr(its, _i32p), ptr(det, _i32p), C.byref(info))
+    if rc < 0:
+        raise RuntimeError(f"score_refine_batch_samples failed: {lib.score_last_error().decode()}")
+    rec = info.as_dict()
+    out = []
+    at = dict(mom=0, mean=0, steps=0, rhs=0, noise=0, draw=0)
+
+    def cut(flat_array, key, size, shape):
+        if flat_array is None:
+            return None
+        piece = flat_array[at[key] : at[key] + size].reshape(shape).copy()
+        at[key] += size
+        return piece
+
+    for g, prob in enumerate(probs):
+        S, c, rows = on[g], ncol[g], _n_rows(prob)
+        it = its[at["draw"] : at["draw"] + S].copy()
+        converged = it >= 0  # (a draw that did not converge reports -(steps + 1))
+        member = {
+            "moments": cut(moments, "mom", n_mom[g], (n_mom[g],)) if S else np.zeros(_moment_sizes(prob)[2]),
+            "means": cut(means, "mean", n_mean[g], (n_mean[g],)) if S else np.zeros(prob.n),
+            "steps": cut(steps, "steps", S * c, (S, c)), "rhs": cut(rhs, "rhs", S * prob.n, (S, prob.n)),
+            "noise": cut(noise, "noise", S * rows, (S, rows)), "residuals": res[at["draw"] : at["draw"] + S].copy(),
+            "iterations": np.where(converged, it, -it - 1), "converged": converged, "determined": int(det[g]),
+            "rc": 0 if np.all(converged) else 1,
+            "info": dict(rec, samples=S, batches=-(-S // int(block_width))),
+        }
+        at["draw"] += S
+        out.append(member)
+    return rc, out, rec
+
+
+def _failed(i, failed, total, max_iters):
+    return RuntimeError(f"posterior_samples_batch: graph {i}: {failed} of {total} draws did not converge (max_iters = {max_iters}): "
+                        "J'J is singular or nearly so -- information_spectrum(...).undetermined() names the variables the "
+                        "measurements do not determine")
+
+
+def group_samples(handle, probs, points, estimates, selections, indices, number, counts, seeds, first_sample=0, rel_tol=1e-10,
+                  max_iters=4000, block_width=MAX_BLOCK_WIDTH, engine="device"):
+    """The draws of one group: ``selections[k]`` is ``marginals._select`` of member k, ``estimates[k]`` the SolverResults its
+    draws are retracted onto, ``indices[k]`` its graph's number in the caller's list (for messages), ``handle`` the group's
+    ``RefineBatchHandle`` (None with ``engine="python"``).  Returns ``(Samples, info)`` per member."""
+    out = []
+    if engine == "python":
+        for prob, point, est, (names, _, size, cols), i, S, seed in zip(probs, points, estimates, selections, indices, counts, seeds):
+            delta, b, z, res = _python_draws(prob, point, seed, int(first_sample), S)
+            if delta is None:
+                raise _failed(i, S, S, max_iters)
+            moments, means = accumulate_moments(prob, delta)
+            info = {"pcg_iters": 0, "batches": 0, "setup_ms": 0.0, "rhs_ms": 0.0, "solve_ms": 0.0, "iterations": np.zeros(S, dtype=np.int64),
+                    "noise": z, "rhs": b, "order": names, "residuals": res, "engine": engine, "group": number, "passes": 0, "determined": 1}
+            out.append((Samples(prob, est, moments, means, S, names, size, np.ascontiguousarray(delta[:, cols]), first_sample), info))
+        return out
+    _, members, rec = handle.samples(points, [sel[1] for sel in selections], counts, seeds, first_sample, rel_tol, max_iters, block_width)
+    for prob, est, (names, _, size, _), i, S, m in zip(probs, estimates, selections, indices, counts, members):
+        failed = int(np.count_nonzero(~m["converged"]))
+        if failed:
+            raise _failed(i, failed, S, max_iters)
+        info = {"pcg_iters": int(rec["pcg_iters"]), "batches": int(m["info"]["batches"]), "setup_ms": float(rec["setup_ms"]),
+                "rhs_ms": float(rec["rhs_ms"]), "solve_ms": float(rec["solve_ms"]), "iterations": m["iterations"], "order": names,
+                "residuals": m["residuals"], "engine": engine, "group": number, "passes": int(rec["passes"]),
+                "determined": m["determined"]}
+        out.append((Samples(prob, est, m["moments"], m["means"], S, names, size, m["steps"], first_sample), info))
+    return out
+
+
+def _check_draw_arguments(counts, first_sample, block_width, rel_tol, max_iters):
+    for S in counts:
+        if int(S) != S or S < 1:
+            raise ValueError("n_samples must be an integer >= 1 (for every graph)")
+    if int(block_width) != block_width or not 1 <= int(block_width) <= MAX_BLOCK_WIDTH:
+        raise ValueError(f"block_width must be an integer in 1..{MAX_BLOCK_WIDTH}")
+    if int(first_sample) != first_sample or first_sample < 0 or first_sample + max(counts) > 2 ** 32:
+        raise ValueError("first_sample .. first_sample + n_samples must lie in 0 .. 2^32")
+    if not rel_tol > 0 or max_iters < 1:
+        raise ValueError("rel_tol must be positive and max_iters at least 1")
+
+
+def _seeds_of(seed, count: int) -> list:
+    """An integer: graph i draws from the stream of seed + i.  A list: one seed per graph."""
+    if np.ndim(seed) == 0:
+        return [int(seed) + i for i in range(count)]
+    return [int(s) for s in _per_member(seed, count, "seed")]
+
+
+def posterior_samples_batch(datas, results, n_samples=64, seed=0, first_sample: int = 0, variables=None, range_weights=None,
+                            loop_closure_weights=None, rel_tol: float = 1e-10, max_iters: int = 4000,
+                            block_width: int = MAX_BLOCK_WIDTH, engine: str = "device", lib_path: Optional[str] = None,
+                            solver_settings: Optional[dict] = None, max_group: int = 64):
+    """``posterior_samples`` for many graphs at once: ``datas`` and ``results`` graph by graph, ``variables`` None or a list
+    with one entry per graph (None: that graph's default, every landmark and the last pose of every chain; else a list of
+    names), ``range_weights`` / ``loop_closure_weights`` lists with one entry per graph.  ``n_samples``: an integer or one per
+    graph.  ``seed``: a list with one seed per graph, or an integer -- graph i then draws from the stream of ``seed + i``, so
+    that graph i's draws are those of ``posterior_samples(..., seed=seed + i)``; ``first_sample`` is shared.  The graphs are
+    grouped by dimension, in chunks of at most ``max_group``, as ``refine_estimate_batch`` groups them; each group is one device
+    handle and one ``score_refine_batch_samples`` call (``engine="device"``) or the dense twin graph by graph
+    (``engine="python"``).  Returns a list of ``(Samples, info)`` in input order: per graph what ``posterior_samples`` returns,
+    plus ``group`` (the group's number), ``passes`` (passes of the group's call; ``batches`` counts those in which the graph
+    itself had draws; ``pcg_iters``, ``setup_ms``, ``rhs_ms`` and ``solve_ms`` are the group's) and ``determined`` (the graph's
+    own probe).  The single call's ValueErrors are raised with ``graph i:`` in front; draws that do not converge raise
+    RuntimeError naming the first such graph."""
+    from .refine_batch import RefineBatchHandle, _weights_of
+
+    if engine not in ("device", "python"):
+        raise ValueError("engine must be 'device' or 'python'")
+    datas, results = list(datas), list(results)
+    if len(datas) != len(results):
+        raise ValueError(f"one estimate per graph expected: {len(datas)} graphs, {len(results)} estimates")
+    if int(max_group) < 1:
+        raise ValueError("max_group must be at least 1")
+    counts = _per_member(n_samples, len(datas), "n_samples")
+    if datas:
+        _check_draw_arguments(counts, first_sample, block_width, rel_tol, max_iters)
+    counts = [int(s) for s in counts]
+    seeds = _seeds_of(seed, len(datas))
+    rws = _weights_of(range_weights, len(datas), "range_weights")
+    lws = _weights_of(loop_closure_weights, len(datas), "loop_closure_weights")
+    wanted = _variables_of(variables, len(datas))
+    groups: dict = {}
+    for i, (data, res) in enumerate(zip(datas, results)):
+        if data.dimension not in (2, 3):
+            raise ValueError(f"graph {i}: dimension must be 2 or 3")
+        try:
+            prob, point = _problem_and_point(data, res, rws[i], lws[i])
+            sel = _select(prob, wanted[i])
+        except ValueError as e:
+            raise ValueError(f"graph {i}: {str(e).replace('marginal_covariances', 'posterior_samples')}") from None
+        if prob.n == 0:
+            raise ValueError(f"graph {i}: the graph has no unknowns")
+        groups.setdefault(data.dimension, []).append((i, prob, point, sel))
+    out: list = [None] * len(datas)
+    number = 0
+    for dim in sorted(groups):
+        members = groups[dim]
+        for c0 in range(0, len(members), int(max_group)):
+            chunk = members[c0 : c0 + int(max_group)]
+            idx, probs, points, sels = ([m[k] for m in chunk] for k in range(4))
+            args = (probs, points, [results[i] for i in idx], sels, idx, number, [counts[i] for i in idx], [seeds[i] for i in idx],
+                    int(first_sample), rel_tol, max_iters, int(block_width), engine)
+            if engine == "python":
+                got = group_samples(None, *args)
+            else:
+                with RefineBatchHandle(probs, lib_path, solver_settings) as h:
+                    got = group_samples(h, *args)
+            for i, g in zip(idx, got):
+                out[i] = g
+            number += 1
+    return out
+
+
+__all__ = ["posterior_samples_batch", "batch_draws", "group_samples", "SAMPLES_BATCH_SYMBOLS", "ScoreSamplesBatchInfo"]
