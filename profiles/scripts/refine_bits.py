@@ -16,7 +16,11 @@ counters, costs, gradient norm, mu, weights, residuals, outlier sets); timings (
 Then, at the host-refined points of tests/refine_batch_helpers.py (twin_alone): marginal_covariances on A and 3D0 at block
 widths 0, 4 and 16, marginal_covariances_batch on the 2-D group and on the 3-D group at widths 4 and 16, information_spectrum
 (k = 4) on A.  Recorded per run: the matrices (joint and as computed), residuals, per-column step counts and the numeric info
-fields; for the spectrum the values, vectors and residuals."""
+fields; for the spectrum the values, vectors and residuals.  At the same points: information_spectrum_batch (k = 4) on the
+2-D group and on the 3-D group (values, vectors, residuals, iterations, h_max); score_refine_samples on A and 3D0, 5 draws at
+block width 4 (right-hand sides, noise, steps, moments, means, residuals, step counts); score_refine_batch_samples at width 4
+on the 2-D group with 5, 2, 0, 7, 1 draws and on the 3-D group with 5, 2 and with 0, 5.  And marginal_covariances on the
+long-row graph "b" of tests/marginals_helpers.py."""
 import argparse
 import os
 import sys
@@ -96,6 +100,50 @@ def record(lib, engine="native"):
     for what in ("values", "vectors", "residuals"):
         out[f"information_spectrum/A/{what}"] = getattr(modes, what)
     flatten("information_spectrum/A/info", info, out)
+
+    from marginals_helpers import landmark_names, pose_names, reference
+    from score_amd.marginals import _problem_and_point, _select
+    from score_amd.refine_batch import RefineBatchHandle
+    from score_amd.samples import SamplesHandle
+    from score_amd.samples_batch import batch_draws
+    from score_amd.spectrum_batch import information_spectrum_batch
+
+    fg, results, _ = reference("b")  # the beacon's rows hold 600 entries: one product tile each
+    poses = pose_names(fg)[0]
+    _, info = marginal_covariances(fg, results, landmark_names(fg) + [poses[1], poses[150], poses[299]], joint=True, lib_path=lib)
+    flatten("marginal_covariances/long_row", info, out)
+
+    drawn = ("rhs", "noise", "steps", "moments", "means", "residuals", "iterations", "converged")
+
+    def at_twin(k):
+        prob, point = _problem_and_point(member(k)[0], twin_alone(k)[0], None, None)
+        return prob, point, _select(prob, None)[1]
+
+    for k in ("A", "3D0"):  # 5 draws at width 4: the last block is partial, and the probe runs
+        prob, point, ids = at_twin(k)
+        with SamplesHandle(prob, lib) as h:
+            got = h.draw(point, ids, 5, seed=11, block_width=4, with_rhs=True, with_noise=True)
+        for what in drawn:
+            out[f"posterior_samples/{k}/{what}"] = np.asarray(got[what])
+        flatten(f"posterior_samples/{k}/info", got["info"], out)
+    # unequal counts at width 4, a member without draws among them: two passes, members drop out after the first
+    for keys, counts in ((KEYS_2D, [5, 2, 0, 7, 1]), (("3D0", "3D1"), [5, 2]), (("3D0", "3D1"), [0, 5])):
+        probs, points, ids = zip(*[at_twin(k) for k in keys])
+        with RefineBatchHandle(list(probs), lib) as h:
+            rc, per, rec = batch_draws(h, list(points), list(ids), counts, [11 + i for i in range(len(keys))], block_width=4,
+                                       with_rhs=True, with_noise=True)
+        name = f"posterior_samples_batch/{'+'.join(keys)}/{'-'.join(map(str, counts))}"
+        out[f"{name}/rc"] = np.asarray(rc)
+        flatten(f"{name}/info", rec, out)
+        for k, got in zip(keys, per):
+            for what in drawn + ("determined",):
+                out[f"{name}/{k}/{what}"] = np.asarray(got[what])
+    for keys in (KEYS_2D, ("3D0", "3D1")):
+        got = information_spectrum_batch([member(k)[0] for k in keys], [twin_alone(k)[0] for k in keys], k=4, lib_path=lib)
+        for k, (modes, info) in zip(keys, got):
+            for what in ("values", "vectors", "residuals"):
+                out[f"information_spectrum_batch/{'+'.join(keys)}/{k}/{what}"] = getattr(modes, what)
+            flatten(f"information_spectrum_batch/{'+'.join(keys)}/{k}/info", info, out)  # (iterations, h_max, rounds)
     return out
 
 

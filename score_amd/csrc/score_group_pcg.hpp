@@ -19,6 +19,8 @@
 //                    (HipBackend::precondition_block; a done slot's z is scratch)
 //   k_gbm_rz         per-workgroup partials of r_c'z_c: a kernel of its own, so that no item straddles members
 //   k_gbm_direction  beta = r'z_new / r'z_old, p = z + beta p; the gate r'z_new <= rel_tol^2 r0'z0 raises the slot's done word
+// The decisions of k_gbm_step and k_gbm_direction are pcg_step_rule and pcg_direction_rule of score_marginals.hpp, the ones
+// k_mv_step and k_mv_direction take; the re-reduction over the member's own ranges and the word layout are this file's.
 // Done words: 1 converged (or nothing to solve), 2 broken down (a non-finite r'z or p'w, or p'w <= 0) -- reported as failure.
 // No atomics: all workgroups of a (member, slot) reduce the same partials in the same order and take the same decision.
 #pragma once
@@ -115,11 +117,11 @@ __global__ __launch_bounds__(kThreads) void k_gbm_step(GbmArgs a) {
     for (int i = M.tile0 + t; i < M.tile1; i += kThreads) pw += pwp[i];
     block_sum2(rz, pw, red);
     const bool lead = (int)blockIdx.x == M.ublk0 && t == 0;
-    if (!(pcg_finite(rz) && pcg_finite(pw) && pw > 0.0)) {
-        if (lead) a.done[word] = 2;
+    double alpha;
+    if (!pcg_step_rule(rz, pw, alpha)) {
+        if (lead) a.done[word] = kPcgBroken;
         return;
     }
-    const double alpha = rz / pw;
     const long long li = (long long)((int)blockIdx.x - M.ublk0) * kThreads + t;
     if (li < M.n) {
         const long long e = c * a.n + M.col0 + li;
@@ -161,24 +163,13 @@ __global__ __launch_bounds__(kThreads) void k_gbm_direction(GbmArgs a) {
     }
     block_sum2(rzn, rzo, red);
     const bool lead = (int)blockIdx.x == M.ublk0 && t == 0;
-    double beta = 0.0;
-    if (a.first) {
-        if (!(pcg_finite(rzn) && rzn > 0.0)) {  // (a zero right-hand side is solved by x = 0; anything else is no SPD preconditioner)
-            if (lead) a.done[word] = rzn == 0.0 ? 1 : 2;
-            return;
-        }
-        if (lead) a.ref[word] = a.tol2 * rzn;
-    } else {
-        if (!(pcg_finite(rzn) && rzo > 0.0)) {
-            if (lead) a.done[word] = 2;
-            return;
-        }
-        if (rzn <= a.ref[word]) {
-            if (lead) a.done[word] = 1;
-            return;
-        }
-        beta = rzn / rzo;
+    double beta;
+    const int verdict = pcg_direction_rule(a.first != 0, rzn, rzo, a.ref + word, beta);
+    if (verdict == kPcgConverged || verdict == kPcgBroken) {
+        if (lead) a.done[word] = verdict;
+        return;
     }
+    if (verdict == kPcgThreshold && lead) a.ref[word] = a.tol2 * rzn;
     const long long li = (long long)((int)blockIdx.x - M.ublk0) * kThreads + t;
     if (li < M.n) {
         const long long e = c * a.n + M.col0 + li;

@@ -4126,6 +4126,7 @@ struct score_refine {
     DevBuf<double> u, ut, hblk, gblk, rhs, cost_part, gmax_part;
     int n_mblocks = 0, n_ublocks = 0, n_hblocks = 0, n_sblocks = 0;
     std::vector<double> part_host;
+    score::MvTiles h_tiles;  // the product's tiles of H's rows: product_tiles()
     score::MvWork mv;  // marginal covariances (score_marginals.hpp)
     score::SpWork sp;  // lowest eigenpairs of H (score_spectrum.hpp)
     score::PsWork ps;  // posterior samples (score_samples.hpp)
@@ -4231,6 +4232,26 @@ struct score_refine {
         staged_h2d(u.d, u0.data(), u0.size() * sizeof(double), stream());
         HIP_CHECK(sync_stream(stream()));
         return u0;
+    }
+    // The head of an analysis at a point (marginals, weakest modes, posterior samples): the point, its blocks, H on the handle's
+    // pattern (lambda = 0).  who: the entry point's words in front of a message; block_needs: what a block of vectors asks of
+    // the chain kernel in those words (null: a call that runs the single solves, which refuse nothing here).
+    void h_at_point(const double* poses_in, const double* lms_in, const std::string& who, const char* block_needs) {
+        (void)set_point(poses_in, lms_in);
+        (void)eval_at(u.d, true);
+        gather_h(0.0);
+        if (!block_needs) return;
+        if (be().split.active) throw std::runtime_error(who + block_needs + " the unsplit chain kernel (chain_split = 0)");
+        if (be().n_prec == 0) throw std::runtime_error(who + "the handle has no preconditioner work (no unknowns?)");
+    }
+    // the product's tiles of H's rows: they come with the first analysis that multiplies by H, once for all of them
+    const score::MvTiles& product_tiles() {
+        if (!h_tiles.dev.d) {
+            NoArena no_arena;
+            h_tiles.add(P.hptr, P.n);
+            h_tiles.send(stream());
+        }
+        return h_tiles;
     }
     score::LmState run(const double* poses_in, const double* lms_in, int max_iters, double tol, double* poses_out, double* lms_out) {
         std::vector<double> u0 = set_point(poses_in, lms_in);

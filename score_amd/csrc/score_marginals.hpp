@@ -8,9 +8,12 @@
 // score_join.hpp, Jacobi on the landmark columns; the loop-closure correction is left out -- the preconditioner only has to
 // be one fixed SPD operator for the whole solve).  New here: the product over several vectors and the vector updates of the
 // block.  Shared with the group's iteration (score_group_pcg.hpp) and the spectrum (score_spectrum.hpp): the tiles and the
-// product of one tile (mv_tiles, mv_product_tile), the slot counts (mv_slots, mv_with_slots), the breakdown test
-// (pcg_finite) and the variables' unknowns (mv_variable_unknowns).  Shared with the posterior samples (score_samples.hpp):
-// the iteration itself (mv_block_pcg), from their own right-hand sides.
+// product of one tile (mv_tiles, MvTiles, mv_product_tile), the slot counts (mv_slots, mv_with_slots), the rule of the gated
+// iteration (pcg_finite, pcg_step_rule, pcg_direction_rule: one rule, two engines -- the group needs k_gbm_rz so that no
+// partial of r'z straddles members, this file takes r'z from the chain kernel's own partials), the variables' unknowns
+// (mv_variable_unknowns) and the verdict of a call from its columns (mv_report).  Shared with the posterior samples
+// (score_samples.hpp): the iteration itself (mv_block_pcg), from their own right-hand sides.  The refinement handle gives the
+// head of a call (h_at_point) and the product's tiles (product_tiles: cut once, read here and by the spectrum).
 //
 // Vectors of a block are stored one after the other, stride n (the layout PrecArgs::vec_stride expects).  One iteration:
 //   k_mv_product    w_c = H p_c for every live column from ONE pass over the CSR matrix, per-workgroup partials of p_c'w_c
@@ -74,6 +77,30 @@ struct MvArgs {
 
 // (the breakdown test of every gated iteration here and in score_group_pcg.hpp: neither infinite nor NaN)
 __device__ __forceinline__ bool pcg_finite(double v) { return fabs(v) <= 1.79769313486231570e308; }
+
+// The rule of the gated iteration, stated once: k_mv_step / k_mv_direction and k_gbm_step / k_gbm_direction
+// (score_group_pcg.hpp) re-reduce their own partials into r'z and p'w, ask here, and write the verdict into their own words.
+// The step: r'z and p'w finite and p'w > 0, then alpha = r'z / p'w; anything else is a breakdown (done word kPcgBroken).
+__device__ __forceinline__ bool pcg_step_rule(double rz, double pw, double& alpha) {
+    if (!(pcg_finite(rz) && pcg_finite(pw) && pw > 0.0)) return false;
+    alpha = rz / pw;
+    return true;
+}
+// The direction: kPcgGo -- p = z + beta p with beta = r'z_new / r'z_old; kPcgThreshold (the first direction) -- p = z and the
+// gate's threshold becomes tol2 r'z_new; kPcgConverged and kPcgBroken are the done words.  ref: the slot's threshold word,
+// read only where the gate is tested.
+constexpr int kPcgGo = 0, kPcgConverged = 1, kPcgBroken = 2, kPcgThreshold = 3;
+__device__ __forceinline__ int pcg_direction_rule(bool first, double rzn, double rzo, const double* ref, double& beta) {
+    beta = 0.0;
+    if (first) {  // (a zero right-hand side is solved by x = 0; anything else is no SPD preconditioner)
+        if (!(pcg_finite(rzn) && rzn > 0.0)) return rzn == 0.0 ? kPcgConverged : kPcgBroken;
+        return kPcgThreshold;
+    }
+    if (!(pcg_finite(rzn) && rzo > 0.0)) return kPcgBroken;
+    if (rzn <= *ref) return kPcgConverged;
+    beta = rzn / rzo;
+    return kPcgGo;
+}
 
 // the slots a block of `most` live columns runs in, and f(std::integral_constant<int, NV>) for that count: the product kernels
 // are compiled for 1, 2, 4, 8 and 16 vectors
@@ -180,11 +207,11 @@ __global__ __launch_bounds__(kMvThreads) void k_mv_step(MvArgs a) {
     for (int i = t; i < a.n_tiles; i += kMvThreads) pw += a.pw_part[(size_t)c * a.n_tiles + i];
     block_sum2(rz, pw, red);
     const bool lead = blockIdx.x == 0 && t == 0;
-    if (!(pcg_finite(rz) && pcg_finite(pw) && pw > 0.0)) {
-        if (lead) a.flags[kMvDone + c] = 2;
+    double alpha;
+    if (!pcg_step_rule(rz, pw, alpha)) {
+        if (lead) a.flags[kMvDone + c] = kPcgBroken;
         return;
     }
-    const double alpha = rz / pw;
     const long long i = (long long)blockIdx.x * kMvThreads + t;
     if (i < a.n) {
         const long long e = c * a.n + i;
@@ -206,24 +233,13 @@ __global__ __launch_bounds__(kMvThreads) void k_mv_direction(MvArgs a) {
     }
     block_sum2(rzn, rzo, red);
     const bool lead = blockIdx.x == 0 && t == 0;
-    double beta = 0.0;
-    if (a.first) {
-        if (!(pcg_finite(rzn) && rzn > 0.0)) {  // (a zero right-hand side is solved by x = 0; anything else is no SPD preconditioner)
-            if (lead) a.flags[kMvDone + c] = rzn == 0.0 ? 1 : 2;
-            return;
-        }
-        if (lead) a.ref[c] = a.tol2 * rzn;
-    } else {
-        if (!(pcg_finite(rzn) && rzo > 0.0)) {
-            if (lead) a.flags[kMvDone + c] = 2;
-            return;
-        }
-        if (rzn <= a.ref[c]) {
-            if (lead) a.flags[kMvDone + c] = 1;
-            return;
-        }
-        beta = rzn / rzo;
+    double beta;
+    const int verdict = pcg_direction_rule(a.first != 0, rzn, rzo, a.ref + c, beta);
+    if (verdict == kPcgConverged || verdict == kPcgBroken) {
+        if (lead) a.flags[kMvDone + c] = verdict;
+        return;
     }
+    if (verdict == kPcgThreshold && lead) a.ref[c] = a.tol2 * rzn;
     const long long i = (long long)blockIdx.x * kMvThreads + t;
     if (i < a.n) {
         const long long e = c * a.n + i;
@@ -279,6 +295,36 @@ inline void mv_tiles(const std::vector<int32_t>& ptr, int64_t n, std::vector<int
     }
 }
 
+// Tiles on the device: cut by mv_tiles from a graph's row pointers (add: once per member of a union, appended), sent once.
+struct MvTiles {
+    DevBuf<int4> dev;
+    int n = 0;
+    std::vector<int4> cut;  // on the host until they are sent
+    void add(const std::vector<int32_t>& ptr, int64_t rows, int64_t row0 = 0, int member = 0) { mv_tiles(ptr, rows, cut, row0, member); }
+    void send(hipStream_t st) {
+        n = (int)cut.size();
+        dev.alloc(cut.size());
+        staged_h2d(dev.d, cut.data(), cut.size() * sizeof(int4), st);
+        std::vector<int4>().swap(cut);
+    }
+};
+
+// The verdict of a call from its columns (or draws), stated once for mv_solve, ps_solve, gbm_solve and gbs_solve: a column
+// that is not done counts as unconverged; worst is the largest residual, infinite where one is not finite; the caller's
+// iters get the steps of a done column and -(steps + 1) of any other.  Returns the unconverged columns.
+inline int mv_report(const std::vector<int32_t>& done, const std::vector<int32_t>& steps, const std::vector<double>& res, double* residuals,
+                     int32_t* iters, double& worst) {
+    int unconverged = 0;
+    worst = 0.0;
+    for (size_t c = 0; c < done.size(); ++c) {
+        if (!done[c]) ++unconverged;
+        worst = std::isfinite(res[c]) ? std::max(worst, res[c]) : INFINITY;
+        if (residuals) residuals[c] = res[c];
+        if (iters) iters[c] = done[c] ? steps[c] : -(steps[c] + 1);
+    }
+    return unconverged;
+}
+
 // The unknowns of the selected variables of one graph -- Np poses of dp unknowns each (pose 0 is fixed), then Nl landmarks of
 // dim -- appended to sel in the order of include/score_marginals.h.  who: the entry point's words in front of a message.
 inline void mv_variable_unknowns(int64_t Np, int64_t Nl, int dp, int dim, const int32_t* vars, int32_t n_vars, const std::string& who,
@@ -307,16 +353,12 @@ inline void mv_columns(const GnProblem& P, const int32_t* vars, int32_t n_vars, 
 struct MvWork {
     DevBuf<double> x, r, z, p, w, p_scratch, pw_part, rz0, rz1, ref, res_part, zb;
     DevBuf<int32_t> flags;
-    DevBuf<int4> tiles;
+    const int4* tiles = nullptr;  // the product's tiles: the handle's (T), shared with the spectrum
     int n_tiles = 0;
-    void reserve(const GnProblem& P, int n_prec, int zb_per_vector, hipStream_t st) {
+    void reserve(const GnProblem& P, const MvTiles& T, int n_prec, int zb_per_vector, hipStream_t st) {
         if (x.d) return;
         NoArena no_arena;
-        std::vector<int4> t;
-        mv_tiles(P.hptr, P.n, t);
-        n_tiles = (int)t.size();
-        tiles.alloc(t.size());
-        staged_h2d(tiles.d, t.data(), t.size() * sizeof(int4), st);
+        tiles = T.dev.d; n_tiles = T.n;
         const size_t nv = (size_t)kMvMaxWidth, n = (size_t)P.n, rb = (n + kMvThreads - 1) / kMvThreads;
         DevBuf<double>* vecs[] = {&x, &r, &z, &p, &w, &p_scratch};
         for (DevBuf<double>* v : vecs) { v->alloc(nv * n); v->zero(st); }
@@ -371,7 +413,7 @@ inline void mv_block_pcg(HipBackend& be, MvWork& W, MvArgs& a, int NV, int n_rbl
 inline MvArgs mv_block_args(HipBackend& be, MvWork& W, long long n, double rel_tol) {
     MvArgs a{};
     a.ptr = be.Kset.mat.ptr.d; a.col = be.Kset.mat.col.d; a.val = be.Kset.mat.val.d;
-    a.tiles = W.tiles.d; a.n_tiles = W.n_tiles; a.n = n; a.flags = W.flags.d;
+    a.tiles = W.tiles; a.n_tiles = W.n_tiles; a.n = n; a.flags = W.flags.d;
     a.x = W.x.d; a.r = W.r.d; a.z = W.z.d; a.p = W.p.d; a.w = W.w.d; a.pw_part = W.pw_part.d;
     a.n_prec = be.n_prec; a.tol2 = rel_tol * rel_tol; a.ref = W.ref.d; a.res_part = W.res_part.d;
     return a;
@@ -393,16 +435,12 @@ int mv_solve(Refine& R, const double* poses, const double* landmarks, const int3
     const long long n = P.n;
     const double t0 = now_ms();
     // H at the point, on the handle's pattern; the chains factored once for the block path (the single solves factor per call)
-    R.set_point(poses, landmarks);
-    (void)R.eval_at(R.u.d, true);
-    R.gather_h(0.0);
     const bool seq = block_width == 0;
-    if (!seq && be.split.active) throw std::runtime_error("score_refine_marginals: blocks of columns need the unsplit chain kernel (chain_split = 0)");
-    if (!seq && be.n_prec == 0) throw std::runtime_error("score_refine_marginals: the handle has no preconditioner work (no unknowns?)");
+    R.h_at_point(poses, landmarks, "score_refine_marginals: ", seq ? nullptr : "blocks of columns need");
     if (!seq) be.derive_rho_data(false);
     const int NV = seq ? 1 : mv_slots(block_width);
     auto& W = R.mv;
-    W.reserve(P, be.n_prec, be.H->bs * be.n_join_seps, st);
+    W.reserve(P, R.product_tiles(), be.n_prec, be.H->bs * be.n_join_seps, st);
     DevBuf<int32_t> d_sel;
     DevBuf<double> d_joint;
     {
@@ -454,14 +492,8 @@ int mv_solve(Refine& R, const double* poses, const double* landmarks, const int3
     if (joint) staged_d2h(joint, d_joint.d, (size_t)C * (size_t)C * sizeof(double), st);
     HIP_CHECK(sync_stream(st));
     const double t2 = now_ms();
-    int unconverged = 0;
     double worst = 0.0;
-    for (int c = 0; c < C; ++c) {
-        if (!col_done[(size_t)c]) ++unconverged;
-        worst = std::isfinite(col_res[(size_t)c]) ? std::max(worst, col_res[(size_t)c]) : INFINITY;
-        if (residuals) residuals[c] = col_res[(size_t)c];
-        if (iters) iters[c] = col_done[(size_t)c] ? col_iters[(size_t)c] : -(col_iters[(size_t)c] + 1);
-    }
+    const int unconverged = mv_report(col_done, col_iters, col_res, residuals, iters, worst);
     if (info) {
         info->columns = C; info->batches = batches; info->pcg_iters = pcg_iters; info->unconverged = unconverged;
         info->max_residual = worst; info->setup_ms = t1 - t0; info->solve_ms = t2 - t1;

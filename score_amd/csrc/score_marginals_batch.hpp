@@ -10,7 +10,8 @@
 // residual of every column from one more product w = H x (k_gbm_residual) and the selected rows of x (k_gbm_gather).
 //
 // What exists already and is used as it is: the blocks of all members (k_gb_blocks<DIM>), the gather of H on the union
-// pattern (k_gb_gather_h, lambda = 0), one chain factorisation for all members (derive_rho_data -> k_factor).
+// pattern (k_gb_gather_h, lambda = 0), one chain factorisation for all members (derive_rho_data -> k_factor), the verdict of
+// a call from its columns (mv_report of score_marginals.hpp).
 #pragma once
 
 #include <algorithm>
@@ -201,14 +202,8 @@ int gbm_solve(Batch& B, const double* poses, const double* landmarks, const int3
         HIP_CHECK(sync_stream(st));
     }
     const double t2 = now_ms();
-    int unconverged = 0;
     double worst = 0.0;
-    for (int c = 0; c < n_sel; ++c) {
-        if (!col_done[(size_t)c]) ++unconverged;
-        worst = std::isfinite(col_res[(size_t)c]) ? std::max(worst, col_res[(size_t)c]) : INFINITY;
-        if (residuals) residuals[c] = col_res[(size_t)c];
-        if (iters) iters[c] = col_done[(size_t)c] ? col_iters[(size_t)c] : -(col_iters[(size_t)c] + 1);
-    }
+    const int unconverged = mv_report(col_done, col_iters, col_res, residuals, iters, worst);
     if (info) {
         info->columns = n_sel; info->passes = passes; info->pcg_iters = pcg_iters; info->unconverged = unconverged;
         info->max_residual = worst; info->setup_ms = t1 - t0; info->solve_ms = t2 - t1;

@@ -11,9 +11,11 @@
 //                     block buffer laid out as gblk (gblk_size() doubles per draw)
 //   k_ps_gather<NV>   b_c[i] = the sum of unknown i's contributions in list order, all live draws from one pass over the
 //                     lists; tiles as the product's (mv_tiles over gc_ptr): short lists four lanes each, a long list (a
-//                     landmark ranged from every pose) over the workgroup, both joined in a fixed order
-//   k_ps_probe_begin  once per call: a random vector as the right-hand side of one probe column, whose iteration says
-//                     whether H is singular (the draws' own right-hand sides lie in the range of H and cannot)
+//                     landmark ranged from every pose) over the workgroup, both joined in a fixed order -- the tile's body
+//                     is ps_gather_tile<NV>, which k_gbs_gather of score_samples_batch.hpp calls too
+//   k_ps_probe_begin  once per call: a random vector (ps_probe_value, the group's as well) as the right-hand side of one
+//                     probe column, whose iteration says whether H is singular (the draws' own right-hand sides lie in
+//                     the range of H and cannot)
 //   k_ps_begin        x = 0, r = b_c, the done / iteration words as k_mv_rhs sets them
 //   k_ps_residual     partials of |b_c - H x_c|^2
 //   k_ps_moments<DIM> per variable M_v += sum_s delta_v delta_v', mean_v += sum_s delta_v over the block's converged draws
@@ -155,55 +157,70 @@ __global__ __launch_bounds__(kThreads) void k_ps_blocks(PsArgs a) {
                         (int64_t)a.rows);
 }
 
-// One tile of unknowns per workgroup: b_c[i] = sum of blk_c[gc_slot[.]] over the list of i, the draws c < live.  A short list
-// is summed by kMvLanes lanes (entries sub, sub + 4, ... each in list order), joined as (l0 + l1) + (l2 + l3); a long list by
-// the workgroup (entries t, t + 256, ...), joined by the wave's tree and then (w0 + w1) + (w2 + w3).
+// The gather of one tile of unknowns: b_c[i] = sum of blk_c[gc_slot[.]] over the list of i, the draws c < live.  Stated once:
+// k_ps_gather (the draws of one graph) and k_gbs_gather (score_samples_batch.hpp: the live slots of the tile's member) call
+// it with their count.  A short list is summed by kMvLanes lanes (entries sub, sub + 4, ... each in list order), joined as
+// (l0 + l1) + (l2 + l3); a long list by the workgroup (entries t, t + 256, ...), joined by the wave's tree and then
+// (w0 + w1) + (w2 + w3).  red: (kMvThreads / 64) * NV doubles of LDS.  Every lane enters with the same tile and live > 0.
 template <int NV>
-__global__ __launch_bounds__(kMvThreads) void k_ps_gather(PsArgs a) {
-    __shared__ double red[(kMvThreads / 64) * NV];
-    const int4 tile = a.tiles[blockIdx.x];
+__device__ __forceinline__ void ps_gather_tile(const int32_t* gc_ptr, const int32_t* gc_slot, const int4 tile, const double* blk,
+                                               const long long gsz, double* b, const long long n, const int live, double* red) {
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     double acc[NV];
 #pragma unroll
     for (int c = 0; c < NV; ++c) acc[c] = 0.0;
     if (tile.z) {
         const int row = tile.x;
-        const int k1 = a.gc_ptr[row + 1];
-        for (int k = a.gc_ptr[row] + t; k < k1; k += kMvThreads) {
-            const long long slot = a.gc_slot[k];
+        const int k1 = gc_ptr[row + 1];
+        for (int k = gc_ptr[row] + t; k < k1; k += kMvThreads) {
+            const long long slot = gc_slot[k];
 #pragma unroll
             for (int c = 0; c < NV; ++c)
-                if (c < a.live) acc[c] += a.blk[c * a.gsz + slot];
+                if (c < live) acc[c] += blk[c * gsz + slot];
         }
 #pragma unroll
         for (int c = 0; c < NV; ++c)
-            if (c < a.live) {
+            if (c < live) {
                 const double s = wave_sum(acc[c]);
                 if (lane == 0) red[wave * NV + c] = s;
             }
         __syncthreads();
-        if (t < NV && t < a.live) a.b[t * a.n + row] = (red[t] + red[NV + t]) + (red[2 * NV + t] + red[3 * NV + t]);
+        if (t < NV && t < live) b[t * n + row] = (red[t] + red[NV + t]) + (red[2 * NV + t] + red[3 * NV + t]);
         return;
     }
     const int row = tile.x + t / kMvLanes, sub = t % kMvLanes;
     const bool mine = row < tile.y;
     if (mine) {
-        const int k1 = a.gc_ptr[row + 1];
-        for (int k = a.gc_ptr[row] + sub; k < k1; k += kMvLanes) {
-            const long long slot = a.gc_slot[k];
+        const int k1 = gc_ptr[row + 1];
+        for (int k = gc_ptr[row] + sub; k < k1; k += kMvLanes) {
+            const long long slot = gc_slot[k];
 #pragma unroll
             for (int c = 0; c < NV; ++c)
-                if (c < a.live) acc[c] += a.blk[c * a.gsz + slot];
+                if (c < live) acc[c] += blk[c * gsz + slot];
         }
     }
 #pragma unroll
     for (int c = 0; c < NV; ++c)
-        if (c < a.live) {
+        if (c < live) {
             double s = acc[c];
             s += __shfl_xor(s, 1, 64);
             s += __shfl_xor(s, 2, 64);
-            if (mine && sub == 0) a.b[c * a.n + row] = s;
+            if (mine && sub == 0) b[c * n + row] = s;
         }
+}
+
+// one tile of unknowns per workgroup, the block's draws
+template <int NV>
+__global__ __launch_bounds__(kMvThreads) void k_ps_gather(PsArgs a) {
+    __shared__ double red[(kMvThreads / 64) * NV];
+    ps_gather_tile<NV>(a.gc_ptr, a.gc_slot, a.tiles[blockIdx.x], a.blk, a.gsz, a.b, a.n, a.live, red);
+}
+
+// the probe's value of unknown i (member-local in a group): one standard normal of the Philox stream GEN_PROBE of (seed, i)
+__device__ __forceinline__ double ps_probe_value(uint64_t seed, long long i) {
+    double n0, n1;
+    gen_normal2(philox4x32_10(seed, GEN_PROBE, (uint32_t)i, 0u, 0u), n0, n1);
+    return n0;
 }
 
 // grid (row blocks, columns): x = 0, r = b_c (columns beyond `live`: zero, done from the start)
@@ -228,8 +245,7 @@ __global__ __launch_bounds__(kMvThreads) void k_ps_probe_begin(MvArgs a, uint64_
     const long long i = (long long)blockIdx.x * kMvThreads + t;
     const bool on = c == 0;
     if (i < a.n) {
-        double n0 = 0.0, n1 = 0.0;
-        if (on) gen_normal2(philox4x32_10(seed, GEN_PROBE, (uint32_t)i, 0u, 0u), n0, n1);
+        const double n0 = on ? ps_probe_value(seed, i) : 0.0;
         a.x[c * a.n + i] = 0.0;
         a.r[c * a.n + i] = n0;
         b[c * a.n + i] = n0;
@@ -301,16 +317,12 @@ __global__ __launch_bounds__(kMvThreads) void k_ps_select(MvArgs a, double* __re
 // The draws' buffers: they stay with the refinement handle between calls, as MvWork's do.
 struct PsWork {
     DevBuf<double> blk, b, mom, mean, noise;
-    DevBuf<int4> tiles;
-    int n_tiles = 0;
+    MvTiles tiles;  // of the gather, cut from the contribution lists
     void reserve(const GnProblem& P, bool with_noise, int64_t rows, hipStream_t st) {
         NoArena no_arena;
         if (!blk.d) {
-            std::vector<int4> t;
-            mv_tiles(P.gc_ptr, P.n, t);
-            n_tiles = (int)t.size();
-            tiles.alloc(t.size());
-            staged_h2d(tiles.d, t.data(), t.size() * sizeof(int4), st);
+            tiles.add(P.gc_ptr, P.n);
+            tiles.send(st);
             const size_t nv = (size_t)kMvMaxWidth;
             blk.alloc(nv * (size_t)std::max<int64_t>(1, P.gblk_size())); blk.zero(st);
             b.alloc(nv * (size_t)P.n); b.zero(st);
@@ -342,17 +354,13 @@ int ps_solve(Refine& R, const double* poses, const double* landmarks, uint64_t s
     const long long n = P.n;
     const double t0 = now_ms();
     // H at the point on the handle's pattern, the chains factored once: as mv_solve
-    R.set_point(poses, landmarks);
-    (void)R.eval_at(R.u.d, true);
-    R.gather_h(0.0);
-    if (be.split.active) throw std::runtime_error(who + "blocks of draws need the unsplit chain kernel (chain_split = 0)");
-    if (be.n_prec == 0) throw std::runtime_error(who + "the handle has no preconditioner work (no unknowns?)");
+    R.h_at_point(poses, landmarks, who, "blocks of draws need");
     be.derive_rho_data(false);
     const int NV = mv_slots(block_width);
     const int64_t rows = P.dim == 2 ? ps_rows<2>(P.n_rel(), P.n_rng(), P.n_pri()) : ps_rows<3>(P.n_rel(), P.n_rng(), P.n_pri());
     auto& W = R.mv;
     auto& Q = R.ps;
-    W.reserve(P, be.n_prec, be.H->bs * be.n_join_seps, st);
+    W.reserve(P, R.product_tiles(), be.n_prec, be.H->bs * be.n_join_seps, st);
     Q.reserve(P, noise != nullptr, rows, st);
     Q.mom.zero(st); Q.mean.zero(st);
     DevBuf<int32_t> d_sel;
@@ -368,7 +376,7 @@ int ps_solve(Refine& R, const double* poses, const double* landmarks, uint64_t s
     PsArgs q{};
     q.v = R.view(R.u.d); q.seed = seed; q.blk = Q.blk.d; q.gsz = P.gblk_size(); q.rows = rows; q.n = n;
     q.noise = noise ? Q.noise.d : nullptr;
-    q.gc_ptr = R.gc_ptr.d; q.gc_slot = R.gc_slot.d; q.tiles = Q.tiles.d; q.b = Q.b.d; q.x = W.x.d; q.mom = Q.mom.d; q.mean = Q.mean.d;
+    q.gc_ptr = R.gc_ptr.d; q.gc_slot = R.gc_slot.d; q.tiles = Q.tiles.dev.d; q.b = Q.b.d; q.x = W.x.d; q.mom = Q.mom.d; q.mean = Q.mean.d;
     const unsigned n_vblocks = (unsigned)std::max<int64_t>(1, (P.Np - 1 + P.Nl + kThreads - 1) / kThreads);
     std::vector<int32_t> flags((size_t)kMvFlagWords);
     // Is H singular?  The draws cannot tell: b = J'z lies in the range of J'J, so the iteration converges on a singular H as
@@ -414,7 +422,7 @@ int ps_solve(Refine& R, const double* poses, const double* landmarks, uint64_t s
         if (P.dim == 2) hipLaunchKernelGGL(k_ps_blocks<2>, dim3((unsigned)R.n_mblocks), dim3(kThreads), 0, st, q);
         else hipLaunchKernelGGL(k_ps_blocks<3>, dim3((unsigned)R.n_mblocks), dim3(kThreads), 0, st, q);
         mv_with_slots(NV, [&](auto nv) {
-            hipLaunchKernelGGL(k_ps_gather<decltype(nv)::value>, dim3((unsigned)Q.n_tiles), dim3(kMvThreads), 0, st, q);
+            hipLaunchKernelGGL(k_ps_gather<decltype(nv)::value>, dim3((unsigned)Q.tiles.n), dim3(kMvThreads), 0, st, q);
         });
         hipLaunchKernelGGL(k_ps_begin, dim3((unsigned)n_rblocks, (unsigned)NV), dim3(kMvThreads), 0, st, a, (const double*)Q.b.d);
         HIP_CHECK(hipGetLastError());
@@ -459,14 +467,8 @@ int ps_solve(Refine& R, const double* poses, const double* landmarks, uint64_t s
     if (means) staged_d2h(means, Q.mean.d, Q.mean.n * sizeof(double), st);
     HIP_CHECK(sync_stream(st));
     const double t2 = now_ms();
-    int unconverged = 0;
     double worst = 0.0;
-    for (int s = 0; s < n_samples; ++s) {
-        if (!s_done[(size_t)s]) ++unconverged;
-        worst = std::isfinite(s_res[(size_t)s]) ? std::max(worst, s_res[(size_t)s]) : INFINITY;
-        if (residuals) residuals[s] = s_res[(size_t)s];
-        if (iters) iters[s] = s_done[(size_t)s] ? s_iters[(size_t)s] : -(s_iters[(size_t)s] + 1);
-    }
+    const int unconverged = mv_report(s_done, s_iters, s_res, residuals, iters, worst);
     if (info) {
         info->samples = n_samples; info->batches = batches; info->pcg_iters = pcg_iters; info->unconverged = unconverged;
         info->max_residual = worst; info->setup_ms = t1 - t0; info->rhs_ms = rhs_ms; info->solve_ms = t2 - t1 - rhs_ms;

@@ -9,11 +9,12 @@
 // What exists already and is used as it is: ps_measurement<DIM> on the member's gb_view<DIM> (the Jacobian and the noise,
 // stated once), group_pcg with a right-hand-side callback, gbm_product for the true residuals, the blocks / gather of H /
 // chain factorisation of the group as gbm_solve runs them, GbmWork (B.mvb) for the iteration's vectors -- the marginals and
-// the samples share one allocation --, ps_accumulate for the order of the running sums.  New here:
+// the samples share one allocation --, ps_accumulate for the order of the running sums, ps_gather_tile<NV> for the gather
+// of one tile, ps_probe_value for the probe, MvTiles and mv_report of score_marginals.hpp.  New here:
 //   k_gbs_blocks<DIM>   grid over mblk_member, one lane per measurement of the workgroup's member: J once, then per live
 //                       draw of THAT member z and J'z into slot c's slice of a block buffer laid out as the union gblk
 //   k_gbs_gather<NV>    b_c[col0 + i] = the contributions of unknown i in gc_ptr / gc_slot order; tiles cut per member from
-//                       the union gc_ptr (member in .w), shapes and join orders of k_ps_gather
+//                       the union gc_ptr (member in .w); the tile itself is ps_gather_tile with the member's live slots
 //   k_gbs_begin         x = 0, r = b_c on the slots that carry a draw; the others r = 0 and done word 1
 //   k_gbs_probe_begin   the probe's xi_g into slot 0 of every member with draws
 //   k_gbs_residual      per-workgroup partials of |b_c - w_c|^2 on the live slots
@@ -79,55 +80,15 @@ __global__ __launch_bounds__(kThreads) void k_gbs_blocks(GbsArgs a) {
                         (int64_t)a.gsz, a.noise ? a.noise + a.row0[g] : nullptr, (int64_t)a.rows);
 }
 
-// One tile of one member's unknowns per workgroup: k_ps_gather with the member's live slots (same lanes, same join orders).
+// one tile of one member's unknowns per workgroup: ps_gather_tile with the member's live slots
 template <int NV>
 __global__ __launch_bounds__(kThreads) void k_gbs_gather(GbsArgs a) {
+    static_assert(kThreads == kMvThreads, "the gather's tile is the block iteration's workgroup");
     __shared__ double red[(kThreads / 64) * NV];
     const int4 tile = a.tiles[blockIdx.x];
     const int live = gbs_live(a, tile.w);
     if (live == 0) return;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    double acc[NV];
-#pragma unroll
-    for (int c = 0; c < NV; ++c) acc[c] = 0.0;
-    if (tile.z) {
-        const int row = tile.x;
-        const int k1 = a.gc_ptr[row + 1];
-        for (int k = a.gc_ptr[row] + t; k < k1; k += kThreads) {
-            const long long slot = a.gc_slot[k];
-#pragma unroll
-            for (int c = 0; c < NV; ++c)
-                if (c < live) acc[c] += a.blk[c * a.gsz + slot];
-        }
-#pragma unroll
-        for (int c = 0; c < NV; ++c)
-            if (c < live) {
-                const double s = wave_sum(acc[c]);
-                if (lane == 0) red[wave * NV + c] = s;
-            }
-        __syncthreads();
-        if (t < NV && t < live) a.b[t * a.n + row] = (red[t] + red[NV + t]) + (red[2 * NV + t] + red[3 * NV + t]);
-        return;
-    }
-    const int row = tile.x + t / kMvLanes, sub = t % kMvLanes;
-    const bool mine = row < tile.y;
-    if (mine) {
-        const int k1 = a.gc_ptr[row + 1];
-        for (int k = a.gc_ptr[row] + sub; k < k1; k += kMvLanes) {
-            const long long slot = a.gc_slot[k];
-#pragma unroll
-            for (int c = 0; c < NV; ++c)
-                if (c < live) acc[c] += a.blk[c * a.gsz + slot];
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < NV; ++c)
-        if (c < live) {
-            double s = acc[c];
-            s += __shfl_xor(s, 1, 64);
-            s += __shfl_xor(s, 2, 64);
-            if (mine && sub == 0) a.b[c * a.n + row] = s;
-        }
+    ps_gather_tile<NV>(a.gc_ptr, a.gc_slot, tile, a.blk, a.gsz, a.b, a.n, live, red);
 }
 
 // grid (unknown workgroups, NV): x = 0, r = b_c on the slots that carry a draw (the others: r = 0, done from the start)
@@ -156,8 +117,7 @@ __global__ __launch_bounds__(kThreads) void k_gbs_probe_begin(GbmArgs p, GbsArgs
     const bool on = c < gbs_live(a, g);
     const long long li = (long long)((int)blockIdx.x - M.ublk0) * kThreads + t;
     if (li < M.n) {
-        double n0 = 0.0, n1 = 0.0;
-        if (on) gen_normal2(philox4x32_10(a.seeds[g], GEN_PROBE, (uint32_t)li, 0u, 0u), n0, n1);
+        const double n0 = on ? ps_probe_value(a.seeds[g], li) : 0.0;
         const long long e = c * p.n + M.col0 + li;
         p.x[e] = 0.0;
         p.r[e] = n0;
@@ -223,10 +183,9 @@ __global__ __launch_bounds__(kThreads) void k_gbs_select(GbsArgs a, const double
 // first samples call -- score_refine_batch_create costs what it did -- and go with the handle.
 struct GbsWork {
     DevBuf<double> blk, b, mom, mean, noise;
-    DevBuf<int4> tiles;
+    MvTiles tiles;  // of the gather: {first unknown, end unknown, long list?, member}
     DevBuf<long long> row0, mom0;
     std::vector<long long> row0_host, mom0_host;
-    int n_tiles = 0;
     long long rows = 0, mom_size = 0;
     template <class Batch>
     void reserve(Batch& B, const std::vector<GbsShape>& shapes, bool with_noise, hipStream_t st) {
@@ -237,7 +196,6 @@ struct GbsWork {
             // back once and cut every member's tiles from its own lists
             std::vector<int32_t> ptr((size_t)U.n + 1);
             staged_d2h(ptr.data(), B.gc_ptr.d, ptr.size() * sizeof(int32_t), st);
-            std::vector<int4> t;
             std::vector<int32_t> own;
             std::vector<long long>& r0 = row0_host;
             rows = 0; mom_size = 0;
@@ -245,13 +203,12 @@ struct GbsWork {
             for (int g = 0; g < U.count; ++g) {
                 const GbMember& M = U.members[(size_t)g];
                 own.assign(ptr.begin() + (std::ptrdiff_t)M.col0, ptr.begin() + (std::ptrdiff_t)(M.col0 + M.n + 1));
-                mv_tiles(own, M.n, t, M.col0, g);
+                tiles.add(own, M.n, M.col0, g);
                 r0.push_back(rows); mom0_host.push_back(mom_size);
                 rows += shapes[(size_t)g].rows; mom_size += shapes[(size_t)g].moments;
             }
-            n_tiles = (int)t.size();
-            tiles.alloc(t.size()); row0.alloc(r0.size()); mom0.alloc(mom0_host.size());
-            staged_h2d(tiles.d, t.data(), t.size() * sizeof(int4), st);
+            tiles.send(st);
+            row0.alloc(r0.size()); mom0.alloc(mom0_host.size());
             staged_h2d(row0.d, r0.data(), r0.size() * sizeof(long long), st);
             staged_h2d(mom0.d, mom0_host.data(), mom0_host.size() * sizeof(long long), st);
             const size_t nv = (size_t)kMvMaxWidth;
@@ -332,7 +289,7 @@ int gbs_solve(Batch& B, const double* poses, const double* landmarks, const uint
     GbsArgs q{};
     q.d = B.dev(); q.X = B.X.d; q.seeds = d_seeds.d;
     q.blk = Q.blk.d; q.gsz = U.gblk_size; q.noise = noise ? Q.noise.d : nullptr; q.row0 = Q.row0.d; q.rows = Q.rows;
-    q.gc_ptr = B.gc_ptr.d; q.gc_slot = B.gc_slot.d; q.tiles = Q.tiles.d; q.b = Q.b.d; q.n = n;
+    q.gc_ptr = B.gc_ptr.d; q.gc_slot = B.gc_slot.d; q.tiles = Q.tiles.dev.d; q.b = Q.b.d; q.n = n;
     q.take = d_take.d; q.mom = Q.mom.d; q.mean = Q.mean.d; q.mom0 = Q.mom0.d;
     q.sel = d_sel.d; q.sel_member = d_sel_member.d; q.n_sel = n_sel; q.steps = d_steps.d;
     const dim3 bt(kThreads);
@@ -404,7 +361,7 @@ int gbs_solve(Batch& B, const double* poses, const double* landmarks, const uint
         if (U.dim == 2) hipLaunchKernelGGL(k_gbs_blocks<2>, dim3((unsigned)B.n_mblocks), bt, 0, st, q);
         else hipLaunchKernelGGL(k_gbs_blocks<3>, dim3((unsigned)B.n_mblocks), bt, 0, st, q);
         mv_with_slots(NV, [&](auto nv) {
-            hipLaunchKernelGGL(k_gbs_gather<decltype(nv)::value>, dim3((unsigned)Q.n_tiles), bt, 0, st, q);
+            hipLaunchKernelGGL(k_gbs_gather<decltype(nv)::value>, dim3((unsigned)Q.tiles.n), bt, 0, st, q);
         });
         HIP_CHECK(hipGetLastError());
         if (noise)
@@ -475,14 +432,8 @@ int gbs_solve(Batch& B, const double* poses, const double* landmarks, const uint
     }
     HIP_CHECK(sync_stream(st));
     const double t2 = now_ms();
-    int unconverged = 0;
     double worst = 0.0;
-    for (size_t s = 0; s < total; ++s) {
-        if (!s_done[s]) ++unconverged;
-        worst = std::isfinite(s_res[s]) ? std::max(worst, s_res[s]) : INFINITY;
-        if (residuals) residuals[s] = s_res[s];
-        if (iters) iters[s] = s_done[s] ? s_iters[s] : -(s_iters[s] + 1);
-    }
+    const int unconverged = mv_report(s_done, s_iters, s_res, residuals, iters, worst);
     for (int g = 0; determined && g < G; ++g) determined[g] = det[(size_t)g];
     if (info) {
         info->members = G; info->samples = (int32_t)plan.samples; info->passes = plan.passes; info->pcg_iters = pcg_iters;

@@ -7,7 +7,10 @@
 // correction) and the product over 16 vectors (k_mv_product<16>, all_columns = 1).  M is the chain
 // part of A -- tridiagonal pose blocks per chain, diagonal blocks of the landmarks -- and exists for a singular H because of
 // the shift.  New here: the Gram kernel, the combine kernel, and the small kernels around them (start block, residuals,
-// done words, max diag H).
+// done words, max diag H).  Stated here once for a graph and for the members of a group (score_spectrum_batch.hpp): the
+// start block's hash (sp_start_value), the directions in use (sp_active_mask), one row tile of the Gram pass and the store
+// of its partial matrices (sp_gram_tile, sp_gram_store).  The handle's head of a call and its product tiles: h_at_point,
+// product_tiles (score_marginals.hpp).
 //
 // The six blocks X, W, P (S) and AX, AW, AP (AS) are n x 16 each, column c at c * n (the layout PrecArgs::vec_stride
 // expects).  One iteration:
@@ -78,27 +81,85 @@ struct SpArgs {
     const double* coef;      // 48 x 16 row-major
 };
 
-// the directions of S in use, bit b * 16 + c for block b, column c
-__device__ __forceinline__ unsigned long long sp_active(const SpArgs& a) {
+// The bodies below are stated once for a graph and for a group: the kernels here and their k_gsp_ twins
+// (score_spectrum_batch.hpp) call them with their own row range, flags and coefficients.
+
+// the directions of S in use, bit b * 16 + c for block b, column c; flags: the 16 done words of the graph (of the member)
+__device__ __forceinline__ unsigned long long sp_active_mask(int x_only, int has_p, const int32_t* flags) {
     unsigned long long act = 0xFFFFull;
-    if (a.x_only) return act;
+    if (x_only) return act;
 #pragma unroll
     for (int c = 0; c < kSpBlock; ++c)
-        if (a.flags[c] == 0) act |= (1ull << (kSpBlock + c)) | (a.has_p ? 1ull << (2 * kSpBlock + c) : 0ull);
+        if (flags[c] == 0) act |= (1ull << (kSpBlock + c)) | (has_p ? 1ull << (2 * kSpBlock + c) : 0ull);
     return act;
 }
 
-// grid (row blocks, 16): the start block from a fixed integer hash of (unknown, column), in (-1, 1); the done words cleared
+// entry (i, c) of the start block: a fixed integer hash of (unknown, column), in (-1, 1); i is member-local in a group
+__device__ __forceinline__ double sp_start_value(long long i, int c) {
+    unsigned long long h = (unsigned long long)i * kSpBlock + (unsigned long long)c + 0x9E3779B97F4A7C15ull;
+    h = (h ^ (h >> 30)) * 0xBF58476D1CE4E5B9ull;
+    h = (h ^ (h >> 27)) * 0x94D049BB133111EBull;
+    h ^= h >> 31;
+    return (double)(h >> 11) * (2.0 / 9007199254740992.0) - 1.0;
+}
+
+// One row tile of the Gram pass (the head of the file): rows row0 .. row0 + 31 of the n_rows rows that start at `base` in
+// every column (column c of a block at c * stride) are staged into s and as -- a row beyond n_rows or a direction out of
+// use as zero --, then thread (ti, tj) adds the tile's rows IN ROW ORDER to its 3 x 3 entries (3 ti + x, 3 tj + y) of S'AS
+// (ga) and S'S (gb).  Every lane of the workgroup enters; s and as may be staged again on return.
+__device__ __forceinline__ void sp_gram_tile(double* const* S, double* const* AS, long long stride, long long base, long long row0,
+                                             long long n_rows, unsigned long long act, double* s, double* as, double (&ga)[3][3],
+                                             double (&gb)[3][3]) {
+    const int t = threadIdx.x, tj = t & 15, ti = t >> 4;
+    for (int e = t; e < 2 * kSpM * kSpRows; e += kMvThreads) {
+        const int col = e / kSpRows, rr = e % kSpRows, cc = col % kSpM;
+        const long long row = row0 + rr;
+        double v = 0.0;
+        if (row < n_rows && (act >> cc & 1)) {
+            const double* src = col < kSpM ? S[cc / kSpBlock] : AS[cc / kSpBlock];
+            v = src[(cc % kSpBlock) * stride + base + row];
+        }
+        (col < kSpM ? s : as)[cc * kSpLd + rr] = v;
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int rr = 0; rr < kSpRows; ++rr) {
+        double si[3], sj[3], aj[3];
+#pragma unroll
+        for (int x = 0; x < 3; ++x) {
+            si[x] = s[(3 * ti + x) * kSpLd + rr];
+            sj[x] = s[(3 * tj + x) * kSpLd + rr];
+            aj[x] = as[(3 * tj + x) * kSpLd + rr];
+        }
+#pragma unroll
+        for (int x = 0; x < 3; ++x)
+#pragma unroll
+            for (int y = 0; y < 3; ++y) {
+                gb[x][y] += si[x] * sj[y];
+                ga[x][y] += si[x] * aj[y];
+            }
+    }
+    __syncthreads();
+}
+
+// the workgroup's partial matrices, S'AS then S'S, 48 x 48 row-major each
+__device__ __forceinline__ void sp_gram_store(double* part, const double (&ga)[3][3], const double (&gb)[3][3]) {
+    const int t = threadIdx.x, tj = t & 15, ti = t >> 4;
+#pragma unroll
+    for (int x = 0; x < 3; ++x)
+#pragma unroll
+        for (int y = 0; y < 3; ++y) {
+            const int e = (3 * ti + x) * kSpM + 3 * tj + y;
+            part[e] = ga[x][y];
+            part[kSpM * kSpM + e] = gb[x][y];
+        }
+}
+
+// grid (row blocks, 16): the start block (sp_start_value of (unknown, column)); the done words cleared
 __global__ __launch_bounds__(kMvThreads) void k_sp_start(SpArgs a) {
     const int c = blockIdx.y;
     const long long i = (long long)blockIdx.x * kMvThreads + threadIdx.x;
-    if (i < a.n) {
-        unsigned long long h = (unsigned long long)i * kSpBlock + (unsigned long long)c + 0x9E3779B97F4A7C15ull;
-        h = (h ^ (h >> 30)) * 0xBF58476D1CE4E5B9ull;
-        h = (h ^ (h >> 27)) * 0x94D049BB133111EBull;
-        h ^= h >> 31;
-        a.S[0][c * a.n + i] = (double)(h >> 11) * (2.0 / 9007199254740992.0) - 1.0;
-    }
+    if (i < a.n) a.S[0][c * a.n + i] = sp_start_value(i, c);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         a.flags[c] = 0;
         if (c == 0) a.flags[kSpBlock] = 0;
@@ -147,54 +208,11 @@ __global__ __launch_bounds__(kThreads) void k_sp_done(SpArgs a) {
 // S'AS and S'S of the directions in use, per-workgroup partials (see the head of the file)
 __global__ __launch_bounds__(kMvThreads) void k_sp_gram(SpArgs a) {
     __shared__ double s[kSpM * kSpLd], as[kSpM * kSpLd];
-    const int t = threadIdx.x, tj = t & 15, ti = t >> 4;
-    const unsigned long long act = sp_active(a);
-    double ga[3][3], gb[3][3];
-#pragma unroll
-    for (int x = 0; x < 3; ++x)
-#pragma unroll
-        for (int y = 0; y < 3; ++y) ga[x][y] = gb[x][y] = 0.0;
-    for (int tile = blockIdx.x; tile < a.n_row_tiles; tile += gridDim.x) {
-        const long long row0 = (long long)tile * kSpRows;
-        for (int e = t; e < 2 * kSpM * kSpRows; e += kMvThreads) {
-            const int col = e / kSpRows, rr = e % kSpRows, cc = col % kSpM;
-            const long long row = row0 + rr;
-            double v = 0.0;
-            if (row < a.n && (act >> cc & 1)) {
-                const double* src = col < kSpM ? a.S[cc / kSpBlock] : a.AS[cc / kSpBlock];
-                v = src[(cc % kSpBlock) * a.n + row];
-            }
-            (col < kSpM ? s : as)[cc * kSpLd + rr] = v;
-        }
-        __syncthreads();
-#pragma unroll 4
-        for (int rr = 0; rr < kSpRows; ++rr) {
-            double si[3], sj[3], aj[3];
-#pragma unroll
-            for (int x = 0; x < 3; ++x) {
-                si[x] = s[(3 * ti + x) * kSpLd + rr];
-                sj[x] = s[(3 * tj + x) * kSpLd + rr];
-                aj[x] = as[(3 * tj + x) * kSpLd + rr];
-            }
-#pragma unroll
-            for (int x = 0; x < 3; ++x)
-#pragma unroll
-                for (int y = 0; y < 3; ++y) {
-                    gb[x][y] += si[x] * sj[y];
-                    ga[x][y] += si[x] * aj[y];
-                }
-        }
-        __syncthreads();
-    }
-    double* part = a.gram_part + (size_t)blockIdx.x * (size_t)kSpGramOut;
-#pragma unroll
-    for (int x = 0; x < 3; ++x)
-#pragma unroll
-        for (int y = 0; y < 3; ++y) {
-            const int e = (3 * ti + x) * kSpM + 3 * tj + y;
-            part[e] = ga[x][y];
-            part[kSpM * kSpM + e] = gb[x][y];
-        }
+    const unsigned long long act = sp_active_mask(a.x_only, a.has_p, a.flags);
+    double ga[3][3] = {}, gb[3][3] = {};
+    for (int tile = blockIdx.x; tile < a.n_row_tiles; tile += gridDim.x)  // (grid-stride: tiles in ascending order per workgroup)
+        sp_gram_tile(a.S, a.AS, a.n, 0, (long long)tile * kSpRows, a.n, act, s, as, ga, gb);
+    sp_gram_store(a.gram_part + (size_t)blockIdx.x * (size_t)kSpGramOut, ga, gb);
 }
 
 // grid (kSpGramOut / 256): the partial matrices summed in workgroup order
@@ -207,12 +225,13 @@ __global__ __launch_bounds__(kMvThreads) void k_sp_gram_sum(SpArgs a) {
 }
 
 // grid (row blocks, 2), one row per lane: y = 0: X <- S C, P <- [W | P] C_wp; y = 1: the same combination of AS into AX, AP.
-// A lane reads its row of all three blocks before it writes: in place.
+// A lane reads its row of all three blocks before it writes: in place.  (k_gsp_combine repeats the row's text: called through
+// a function of its own the 32 sums take 98 VGPRs here, not 96, and one wave per SIMD less -- profiles/block_bodies_resources.md.)
 __global__ __launch_bounds__(kMvThreads) void k_sp_combine(SpArgs a) {
     __shared__ double c[kSpM * kSpBlock];
     for (int e = threadIdx.x; e < kSpM * kSpBlock; e += kMvThreads) c[e] = a.coef[e];
     __syncthreads();
-    const unsigned long long act = sp_active(a);
+    const unsigned long long act = sp_active_mask(a.x_only, a.has_p, a.flags);
     const long long i = (long long)blockIdx.x * kMvThreads + threadIdx.x;
     if (i >= a.n) return;
     double* const* blk = blockIdx.y ? a.AS : a.S;
@@ -246,16 +265,12 @@ __global__ __launch_bounds__(kMvThreads) void k_sp_combine(SpArgs a) {
 struct SpWork {
     DevBuf<double> x, w, p, ax, aw, ap, r, p_scratch, pw_part, rz, zb, res_part, gram_part, out, coef, hmax_part;
     DevBuf<int32_t> flags;
-    DevBuf<int4> tiles;
+    const int4* tiles = nullptr;  // the product's tiles: the handle's (T), shared with the marginals
     int n_tiles = 0, n_rblocks = 0, n_row_tiles = 0, n_gram_wgs = 0, n_hblocks = 0;
-    void reserve(const GnProblem& P, int n_prec, int zb_per_vector, int hblocks, hipStream_t st) {
+    void reserve(const GnProblem& P, const MvTiles& T, int n_prec, int zb_per_vector, int hblocks, hipStream_t st) {
         if (x.d) return;
         NoArena no_arena;
-        std::vector<int4> t;
-        mv_tiles(P.hptr, P.n, t);
-        n_tiles = (int)t.size();
-        tiles.alloc(t.size());
-        staged_h2d(tiles.d, t.data(), t.size() * sizeof(int4), st);
+        tiles = T.dev.d; n_tiles = T.n;
         const size_t nv = (size_t)kSpBlock, n = (size_t)P.n;
         n_rblocks = (int)((n + kMvThreads - 1) / kMvThreads);
         n_row_tiles = (int)((n + kSpRows - 1) / kSpRows);
@@ -287,17 +302,13 @@ int sp_solve(Refine& R, const double* poses, const double* landmarks, int32_t k,
     HipBackend& be = R.be();
     hipStream_t st = R.stream();
     const long long n = P.n;
-    if (be.split.active) throw std::runtime_error("score_refine_spectrum: the block needs the unsplit chain kernel (chain_split = 0)");
-    if (be.n_prec == 0) throw std::runtime_error("score_refine_spectrum: the handle has no preconditioner work (no unknowns?)");
+    const double t0 = now_ms();
+    // the point, the blocks, H and max diag H; then A = H + sigma I on the handle's pattern and its chain factors
+    R.h_at_point(poses, landmarks, "score_refine_spectrum: ", "the block needs");
     if (n < kSpMinN)
         throw std::runtime_error("score_refine_spectrum: fewer than 48 unknowns -- use the dense solver (engine=\"python\") for a graph this small");
-    const double t0 = now_ms();
     auto& W = R.sp;
-    W.reserve(P, be.n_prec, be.H->bs * be.n_join_seps, R.n_hblocks, st);
-    // the point, the blocks, max diag H; then A = H + sigma I on the handle's pattern and its chain factors
-    R.set_point(poses, landmarks);
-    (void)R.eval_at(R.u.d, true);
-    R.gather_h(0.0);
+    W.reserve(P, R.product_tiles(), be.n_prec, be.H->bs * be.n_join_seps, R.n_hblocks, st);
     hipLaunchKernelGGL(k_sp_hmax, dim3((unsigned)W.n_hblocks), dim3(kThreads), 0, st, (const double*)be.K0d.d, (const int32_t*)R.is_diag.d,
                        (int64_t)P.hcol.size(), W.hmax_part.d);
     HIP_CHECK(hipGetLastError());
@@ -320,7 +331,7 @@ int sp_solve(Refine& R, const double* poses, const double* landmarks, int32_t k,
     a.out = W.out.d; a.coef = W.coef.d;
     MvArgs m{};
     m.ptr = be.Kset.mat.ptr.d; m.col = be.Kset.mat.col.d; m.val = be.Kset.mat.val.d;
-    m.tiles = W.tiles.d; m.n_tiles = W.n_tiles; m.n = n; m.flags = W.flags.d; m.all_columns = 1; m.pw_part = W.pw_part.d;
+    m.tiles = W.tiles; m.n_tiles = W.n_tiles; m.n = n; m.flags = W.flags.d; m.all_columns = 1; m.pw_part = W.pw_part.d;
     auto product = [&](const double* in, double* out) {
         m.p_in = in; m.w = out;
         hipLaunchKernelGGL(k_mv_product<kSpBlock>, dim3((unsigned)W.n_tiles), dim3(kMvThreads), 0, st, m);

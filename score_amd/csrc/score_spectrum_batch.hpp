@@ -14,16 +14,18 @@
 // modes and the rule that moves a member between them: score_spectrum_batch_rule.hpp).  No reduction crosses a member
 // boundary, the number and order of a member's partials depend on n_g alone, and there are no atomics: a member's results
 // do not depend on the group around it, and two calls give the same bits.
-//   k_gsp_start     the start block from k_sp_start's hash of (member-local unknown, column)
+//   k_gsp_start     the start block from sp_start_value of (member-local unknown, column)
 //   k_gsp_hmax      per-workgroup maxima of diag H_g (from the gathered matrix; the host joins a member's own workgroups)
 //   k_gsp_product   a verifying member: AX = A X on all 16 columns; an iterating one: AW = A W on its live columns
 //   k_gsp_residual  R_c = AX_c - theta_c X_c, per-workgroup partials of |R_c|^2 (theta stays on the device)
 //   k_gsp_done      one workgroup per member: the partials of [ublk0, ublk1) re-reduced in order, the done words
-//   k_gsp_gram      S'AS and S'S from one pass over the member's rows of the six blocks: k_sp_gram's tile (32 rows x 96
-//                   columns, column-major, leading dimension 33), kGspGramTiles tiles per workgroup, never across a member
+//   k_gsp_gram      S'AS and S'S from one pass over the member's rows of the six blocks: sp_gram_tile and sp_gram_store of
+//                   score_spectrum.hpp (32 rows x 96 columns, column-major, leading dimension 33) on the directions of
+//                   sp_active_mask, kGspGramTiles tiles per workgroup, never across a member
 //   k_gsp_gram_sum  the member's partial matrices summed in workgroup order; both matrices stay on the device
 //   k_gsp_ritz      Rayleigh-Ritz on the member's pencil, one workgroup per member (below)
-//   k_gsp_combine   k_sp_combine's form with the member's own C, broadcast from LDS
+//   k_gsp_combine   k_sp_combine's form with the member's own C, broadcast from LDS (the row's text stands in both kernels:
+//                   see k_sp_combine)
 //
 // k_gsp_ritz runs steps 1 to 5 of score_spectrum_rr.hpp, unchanged in meaning, with its thresholds.  The two
 // eigen-decompositions are Jacobi with a parallel ordering: a round-robin tournament over the m directions in use (m - 1
@@ -93,15 +95,9 @@ struct GspArgs {
 
 __device__ __forceinline__ int gsp_mode(const GspArgs& a, int g) { return a.ctl[g] & 0xff; }
 
-// the directions of member g's S in use, bit b * 16 + c for block b, column c
+// the directions of member g's S in use (sp_active_mask on the member's words)
 __device__ __forceinline__ unsigned long long gsp_active(const GspArgs& a, int g) {
-    unsigned long long act = 0xFFFFull;
-    if (a.x_only) return act;
-    const unsigned long long has_p = (unsigned long long)(a.ctl[g] >> 8 & 1);
-#pragma unroll
-    for (int c = 0; c < kSpBlock; ++c)
-        if (a.flags[g * kSpBlock + c] == 0) act |= (1ull << (kSpBlock + c)) | (has_p << (2 * kSpBlock + c));
-    return act;
+    return sp_active_mask(a.x_only, a.ctl[g] >> 8 & 1, a.flags + g * kSpBlock);
 }
 
 // grid (unknown workgroups, 16): the start block, keyed by (member-local unknown, column); the member's done words cleared
@@ -109,13 +105,7 @@ __global__ __launch_bounds__(kThreads) void k_gsp_start(GspArgs a) {
     const int g = a.d.ublk_member[blockIdx.x], c = blockIdx.y;
     const GbMember M = a.d.members[g];
     const long long li = (long long)((int)blockIdx.x - M.ublk0) * kThreads + threadIdx.x;
-    if (li < M.n) {
-        unsigned long long h = (unsigned long long)li * kSpBlock + (unsigned long long)c + 0x9E3779B97F4A7C15ull;
-        h = (h ^ (h >> 30)) * 0xBF58476D1CE4E5B9ull;
-        h = (h ^ (h >> 27)) * 0x94D049BB133111EBull;
-        h ^= h >> 31;
-        a.S[0][c * a.n + M.col0 + li] = (double)(h >> 11) * (2.0 / 9007199254740992.0) - 1.0;
-    }
+    if (li < M.n) a.S[0][c * a.n + M.col0 + li] = sp_start_value(li, c);
     if ((int)blockIdx.x == M.ublk0 && threadIdx.x == 0) {
         a.flags[g * kSpBlock + c] = 0;
         a.theta[g * kSpBlock + c] = 0.0;
@@ -200,62 +190,20 @@ __global__ __launch_bounds__(kThreads) void k_gsp_done(GspArgs a) {
     }
 }
 
-// grid (Gram workgroups): S'AS and S'S of the member's directions in use over the workgroup's row tiles (k_sp_gram's tile
-// and thread layout: thread (ti, tj) owns the 3 x 3 entries (3 ti + x, 3 tj + y) of both matrices)
+// grid (Gram workgroups): S'AS and S'S of the member's directions in use over the workgroup's row tiles (sp_gram_tile on
+// the member's rows, the workgroup's wg.z tiles one after the other)
 __global__ __launch_bounds__(kThreads) void k_gsp_gram(GspArgs a) {
+    static_assert(kThreads == kMvThreads, "the Gram tile's thread layout is the single graph's");
     __shared__ double s[kSpM * kSpLd], as[kSpM * kSpLd];
     const int4 wg = a.gram_wgs[blockIdx.x];
     const int g = wg.x;
     if (!a.x_only && gsp_mode(a, g) != kGspIterate) return;
     const GbMember M = a.d.members[g];
-    const int t = threadIdx.x, tj = t & 15, ti = t >> 4;
     const unsigned long long act = gsp_active(a, g);
-    double ga[3][3], gb[3][3];
-#pragma unroll
-    for (int x = 0; x < 3; ++x)
-#pragma unroll
-        for (int y = 0; y < 3; ++y) ga[x][y] = gb[x][y] = 0.0;
-    for (int tile = 0; tile < wg.z; ++tile) {
-        const long long row0 = (long long)wg.y + (long long)tile * kSpRows;
-        for (int e = t; e < 2 * kSpM * kSpRows; e += kThreads) {
-            const int col = e / kSpRows, rr = e % kSpRows, cc = col % kSpM;
-            const long long row = row0 + rr;
-            double v = 0.0;
-            if (row < M.n && (act >> cc & 1)) {
-                const double* src = col < kSpM ? a.S[cc / kSpBlock] : a.AS[cc / kSpBlock];
-                v = src[(cc % kSpBlock) * a.n + M.col0 + row];
-            }
-            (col < kSpM ? s : as)[cc * kSpLd + rr] = v;
-        }
-        __syncthreads();
-#pragma unroll 4
-        for (int rr = 0; rr < kSpRows; ++rr) {
-            double si[3], sj[3], aj[3];
-#pragma unroll
-            for (int x = 0; x < 3; ++x) {
-                si[x] = s[(3 * ti + x) * kSpLd + rr];
-                sj[x] = s[(3 * tj + x) * kSpLd + rr];
-                aj[x] = as[(3 * tj + x) * kSpLd + rr];
-            }
-#pragma unroll
-            for (int x = 0; x < 3; ++x)
-#pragma unroll
-                for (int y = 0; y < 3; ++y) {
-                    gb[x][y] += si[x] * sj[y];
-                    ga[x][y] += si[x] * aj[y];
-                }
-        }
-        __syncthreads();
-    }
-    double* part = a.gram_part + (size_t)blockIdx.x * (size_t)kSpGramOut;
-#pragma unroll
-    for (int x = 0; x < 3; ++x)
-#pragma unroll
-        for (int y = 0; y < 3; ++y) {
-            const int e = (3 * ti + x) * kSpM + 3 * tj + y;
-            part[e] = ga[x][y];
-            part[kSpM * kSpM + e] = gb[x][y];
-        }
+    double ga[3][3] = {}, gb[3][3] = {};
+    for (int tile = 0; tile < wg.z; ++tile)
+        sp_gram_tile(a.S, a.AS, a.n, M.col0, (long long)wg.y + (long long)tile * kSpRows, M.n, act, s, as, ga, gb);
+    sp_gram_store(a.gram_part + (size_t)blockIdx.x * (size_t)kSpGramOut, ga, gb);
 }
 
 // grid (kSpGramOut / 256, members): the member's partial matrices summed in workgroup order
