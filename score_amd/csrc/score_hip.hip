@@ -4096,6 +4096,7 @@ struct AbiEnv {
 #include "score_marginals.hpp"
 #include "score_spectrum.hpp"
 #include "score_samples.hpp"
+#include "score_leverage.hpp"
 #include "score_gn_robust.hpp"
 
 // Residuals and weights of a robust refinement handle (the single one or the group: rb_* buffers, ranges then loop closures) as
@@ -4130,6 +4131,7 @@ struct score_refine {
     score::MvWork mv;  // marginal covariances (score_marginals.hpp)
     score::SpWork sp;  // lowest eigenpairs of H (score_spectrum.hpp)
     score::PsWork ps;  // posterior samples (score_samples.hpp)
+    score::LvWork lv;  // range leverage and predicted range variances (score_leverage.hpp)
     // robust refinement (score_gn_robust.hpp): the measured precisions beside rng_prec / rel_kappa / rel_tau (which hold a robust
     // run's weighted ones while it lasts), residuals, weights, per-block partials; they come with the first robust call
     DevBuf<double> rb_prec0, rb_kappa0, rb_tau0, rb_r_rng, rb_r_lc, rb_w_rng, rb_w_lc, rb_part;
@@ -4848,8 +4850,32 @@ int score_refine_samples(score_refine* r, const double* poses, const double* lan
     return abi_call([&] {
         require(r && poses && (r->P.Nl == 0 || landmarks));
         AbiEnv::Scope scope(r->device, false);
-        return score::ps_solve(*r, poses, landmarks, seed, first_sample, n_samples, vars, n_vars, rel_tol, max_iters, block_width, moments,
-                               means, steps, rhs, noise, residuals, iters, info);
+        score::PsMoments use{vars, n_vars, moments, means, steps};
+        return score::ps_solve(*r, "score_refine_samples: ", poses, landmarks, seed, first_sample, n_samples, rel_tol, max_iters, block_width,
+                               rhs, noise, residuals, iters, info, use);
+    });
+}
+int score_refine_leverage(score_refine* r, const double* poses, const double* landmarks, uint64_t seed, int64_t first_sample,
+                          int32_t n_samples, const int32_t* pair_a, const int32_t* pair_b, int32_t n_pairs, double rel_tol,
+                          int32_t max_iters, int32_t block_width, double* lev_sum, double* lev_sq, double* red_sum, double* red_sq,
+                          double* pair_sum, double* pair_sq, double* residuals, int32_t* iters, score_samples_info* info) {
+    return abi_call([&] {
+        require(r && poses && (r->P.Nl == 0 || landmarks));
+        AbiEnv::Scope scope(r->device, false);
+        score::LvMeasure use{pair_a, pair_b, n_pairs, lev_sum, lev_sq, red_sum, red_sq, pair_sum, pair_sq};
+        return score::ps_solve(*r, "score_refine_leverage: ", poses, landmarks, seed, first_sample, n_samples, rel_tol, max_iters, block_width,
+                               nullptr, nullptr, residuals, iters, info, use);
+    });
+}
+int score_refine_range_variances(score_refine* r, const double* poses, const double* landmarks, const int32_t* pair_a,
+                                 const int32_t* pair_b, int32_t n_pairs, double rel_tol, int32_t max_iters, int32_t block_width,
+                                 double* variances, double* distances, double* residuals, int32_t* iters, double* solutions,
+                                 score_marginals_info* info) {
+    return abi_call([&] {
+        require(r && poses && (r->P.Nl == 0 || landmarks));
+        AbiEnv::Scope scope(r->device, false);
+        return score::lv_pair_solve(*r, poses, landmarks, pair_a, pair_b, n_pairs, rel_tol, max_iters, block_width, variances, distances,
+                                    residuals, iters, solutions, info);
     });
 }
 int score_refine_spectrum(score_refine* r, const double* poses, const double* landmarks, int32_t k, double rel_tol, int32_t max_iters,

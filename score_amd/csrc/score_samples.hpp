@@ -22,6 +22,8 @@
 //                     in ascending s, into running sums that stay on the device across the blocks
 //   k_ps_select       the selected variables' unknowns of every live draw
 // No atomics; every sum has a fixed order, so two calls give the same bits and a draw does not depend on its block.
+// The call itself (ps_solve) is written once and takes what is done with a solved block as a parameter: the moments and the
+// step selection here (PsMoments), the per-measurement sums of score_leverage.hpp.
 #pragma once
 
 #include <algorithm>
@@ -334,21 +336,68 @@ struct PsWork {
     }
 };
 
-// The call.  Refine: score_refine (its point, blocks and gather, its linear-mode handle, its MvWork and PsWork).
-template <class Refine>
-int ps_solve(Refine& R, const double* poses, const double* landmarks, uint64_t seed, int64_t first_sample, int32_t n_samples,
-             const int32_t* vars, int32_t n_vars, double rel_tol, int32_t max_iters, int32_t block_width, double* moments, double* means,
-             double* steps, double* rhs, double* noise, double* residuals, int32_t* iters, score_samples_info* info) {
+// What score_refine_samples does with a solved block -- the consumer ps_solve is given: the per-variable moments of the
+// converged draws and the selected variables' steps.
+struct PsMoments {
+    const int32_t* vars; int32_t n_vars;
+    double* moments; double* means; double* steps;
+    std::vector<int32_t> sel;
+    int C = 0;
+    DevBuf<int32_t> d_sel;
+    DevBuf<double> d_steps;
+    PsWork* Q = nullptr;
+    unsigned n_vblocks = 1;
+    void check(const GnProblem& P, const std::string& who) {
+        if (n_vars < 0 || (n_vars > 0 && !vars)) throw std::runtime_error(who + "n_vars variables without their list");
+        if (n_vars > 0) mv_variable_unknowns(P.Np, P.Nl, P.dp(), P.dim, vars, n_vars, who, sel);
+        C = (int)sel.size();
+        n_vblocks = (unsigned)std::max<int64_t>(1, (P.Np - 1 + P.Nl + kThreads - 1) / kThreads);
+    }
+    template <class Refine>
+    void begin(Refine& R, PsArgs& q, MvArgs& a, hipStream_t st) {
+        Q = &R.ps;
+        Q->mom.zero(st); Q->mean.zero(st);
+        if (C) {
+            NoArena no_arena;
+            d_sel.alloc((size_t)C); d_steps.alloc((size_t)kMvMaxWidth * (size_t)C);
+            staged_h2d(d_sel.d, sel.data(), (size_t)C * sizeof(int32_t), st);
+        }
+        a.sel = d_sel.d; a.C = C;
+        q.mom = Q->mom.d; q.mean = Q->mean.d;
+    }
+    template <class Refine>
+    void block(Refine& R, const PsArgs& q, const MvArgs& a, int k0, int live, hipStream_t st) {
+        if (q.take) {
+            if (R.P.dim == 2) hipLaunchKernelGGL(k_ps_moments<2>, dim3(n_vblocks), dim3(kThreads), 0, st, q);
+            else hipLaunchKernelGGL(k_ps_moments<3>, dim3(n_vblocks), dim3(kThreads), 0, st, q);
+        }
+        if (C) {
+            hipLaunchKernelGGL(k_ps_select, dim3((unsigned)((C + kMvThreads - 1) / kMvThreads), (unsigned)live), dim3(kMvThreads), 0, st, a, d_steps.d);
+            if (steps) staged_d2h(steps + (size_t)k0 * (size_t)C, d_steps.d, (size_t)live * (size_t)C * sizeof(double), st);
+        }
+    }
+    void end(hipStream_t st) {
+        if (moments) staged_d2h(moments, Q->mom.d, Q->mom.n * sizeof(double), st);
+        if (means) staged_d2h(means, Q->mean.d, Q->mean.n * sizeof(double), st);
+    }
+};
+
+// The draws of a call: the probe, then block after block the noise, J'z, the lock-step solve, the true residuals and the
+// verdict of every draw.  Refine: score_refine (its point, blocks and gather, its linear-mode handle, its MvWork and PsWork).
+// What is done with a solved block is the caller's (use): check(P, who) before any device work, begin(R, q, a, st) once the
+// buffers stand, block(R, q, a, k0, live, st) after the block's verdict -- q.take holds the draws that converged, q.live the
+// block's draws, q.x its solutions -- and end(st) before the clock stops.  score_refine_samples passes PsMoments,
+// score_refine_leverage (score_leverage.hpp) its per-measurement sums.
+template <class Refine, class Use>
+int ps_solve(Refine& R, const std::string& who, const double* poses, const double* landmarks, uint64_t seed, int64_t first_sample,
+             int32_t n_samples, double rel_tol, int32_t max_iters, int32_t block_width, double* rhs, double* noise, double* residuals,
+             int32_t* iters, score_samples_info* info, Use& use) {
     const GnProblem& P = R.P;
-    const std::string who = "score_refine_samples: ";
     if (n_samples < 1) throw std::runtime_error(who + "n_samples must be >= 1");
     if (block_width < 1 || block_width > kMvMaxWidth) throw std::runtime_error(who + "block_width must be 1..16");
     if (!(rel_tol > 0.0) || max_iters < 1) throw std::runtime_error(who + "rel_tol must be positive and max_iters >= 1");
     if (first_sample < 0 || first_sample + (int64_t)n_samples > ((int64_t)1 << 32)) throw std::runtime_error(who + "draw indices must lie in 0 .. 2^32 - 1");
-    if (n_vars < 0 || (n_vars > 0 && !vars)) throw std::runtime_error(who + "n_vars variables without their list");
-    std::vector<int32_t> sel;
-    if (n_vars > 0) mv_variable_unknowns(P.Np, P.Nl, P.dp(), P.dim, vars, n_vars, who, sel);
-    const int C = (int)sel.size();
+    use.check(P, who);
     HipBackend& be = R.be();
     hipStream_t st = R.stream();
     const long long n = P.n;
@@ -362,22 +411,13 @@ int ps_solve(Refine& R, const double* poses, const double* landmarks, uint64_t s
     auto& Q = R.ps;
     W.reserve(P, R.product_tiles(), be.n_prec, be.H->bs * be.n_join_seps, st);
     Q.reserve(P, noise != nullptr, rows, st);
-    Q.mom.zero(st); Q.mean.zero(st);
-    DevBuf<int32_t> d_sel;
-    DevBuf<double> d_steps;
-    if (C) {
-        NoArena no_arena;
-        d_sel.alloc((size_t)C); d_steps.alloc((size_t)kMvMaxWidth * (size_t)C);
-        staged_h2d(d_sel.d, sel.data(), (size_t)C * sizeof(int32_t), st);
-    }
     const int n_rblocks = (int)((n + kMvThreads - 1) / kMvThreads);
     MvArgs a = mv_block_args(be, W, n, rel_tol);
-    a.sel = d_sel.d; a.C = C;
     PsArgs q{};
     q.v = R.view(R.u.d); q.seed = seed; q.blk = Q.blk.d; q.gsz = P.gblk_size(); q.rows = rows; q.n = n;
     q.noise = noise ? Q.noise.d : nullptr;
-    q.gc_ptr = R.gc_ptr.d; q.gc_slot = R.gc_slot.d; q.tiles = Q.tiles.dev.d; q.b = Q.b.d; q.x = W.x.d; q.mom = Q.mom.d; q.mean = Q.mean.d;
-    const unsigned n_vblocks = (unsigned)std::max<int64_t>(1, (P.Np - 1 + P.Nl + kThreads - 1) / kThreads);
+    q.gc_ptr = R.gc_ptr.d; q.gc_slot = R.gc_slot.d; q.tiles = Q.tiles.dev.d; q.b = Q.b.d; q.x = W.x.d;
+    use.begin(R, q, a, st);
     std::vector<int32_t> flags((size_t)kMvFlagWords);
     // Is H singular?  The draws cannot tell: b = J'z lies in the range of J'J, so the iteration converges on a singular H as
     // well and returns draws without a component along the directions the measurements leave open.  One more column can: a
@@ -451,20 +491,12 @@ int ps_solve(Refine& R, const double* poses, const double* landmarks, uint64_t s
             if (ok) take |= 1u << c;
         }
         q.take = take;
-        if (take) {
-            if (P.dim == 2) hipLaunchKernelGGL(k_ps_moments<2>, dim3(n_vblocks), dim3(kThreads), 0, st, q);
-            else hipLaunchKernelGGL(k_ps_moments<3>, dim3(n_vblocks), dim3(kThreads), 0, st, q);
-        }
-        if (C) {
-            hipLaunchKernelGGL(k_ps_select, dim3((unsigned)((C + kMvThreads - 1) / kMvThreads), (unsigned)live), dim3(kMvThreads), 0, st, a, d_steps.d);
-            if (steps) staged_d2h(steps + (size_t)k0 * (size_t)C, d_steps.d, (size_t)live * (size_t)C * sizeof(double), st);
-        }
+        use.block(R, q, a, k0, live, st);
         HIP_CHECK(hipGetLastError());
         pcg_iters += most;
         ++batches;
     }
-    if (moments) staged_d2h(moments, Q.mom.d, Q.mom.n * sizeof(double), st);
-    if (means) staged_d2h(means, Q.mean.d, Q.mean.n * sizeof(double), st);
+    use.end(st);
     HIP_CHECK(sync_stream(st));
     const double t2 = now_ms();
     double worst = 0.0;
