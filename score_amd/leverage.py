@@ -28,36 +28,19 @@ from typing import Optional
 
 import numpy as np
 
-from .marginals import MAX_BLOCK_WIDTH, ScoreMarginalsInfo, _problem_and_point
-from .refine import _point_arrays, _Problem3D
-from .samples import SamplesHandle, ScoreSamplesInfo, _python_draws, measurement_rows, ordered_jacobian
-from .solver import _f64p, _i32p
+from .bindings import LEVERAGE, ScoreMarginalsInfo, ScoreSamplesInfo, bind, ptr, steps_and_converged
+from .marginals import MAX_BLOCK_WIDTH, _problem_and_point
+from .refine import _point_arrays, _Problem3D, unknown_sizes
+from .samples import SamplesHandle, _python_draws, measurement_rows, ordered_jacobian
+from .solver import _i32p
 
 # the symbols include/score_leverage.h declares
-LEVERAGE_SYMBOLS = ["score_refine_leverage", "score_refine_range_variances"]
+LEVERAGE_SYMBOLS = list(LEVERAGE)
 KINDS = ("relative_pose", "range", "prior")
 
 
 def _bind(lib: C.CDLL) -> C.CDLL:
-    if getattr(lib, "_score_leverage_bound", False):
-        return lib
-    for sym in LEVERAGE_SYMBOLS:
-        if not hasattr(lib, sym):
-            raise RuntimeError(f"{sym} is missing from the library: rebuild it (the CPU twin has no leverages: "
-                               "engine='python' runs there)")
-    lib.score_refine_leverage.argtypes = [C.c_void_p, _f64p, _f64p, C.c_uint64, C.c_int64, C.c_int32, _i32p, _i32p, C.c_int32,
-                                          C.c_double, C.c_int32, C.c_int32, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _i32p,
-                                          C.POINTER(ScoreSamplesInfo)]
-    lib.score_refine_leverage.restype = C.c_int
-    lib.score_refine_range_variances.argtypes = [C.c_void_p, _f64p, _f64p, _i32p, _i32p, C.c_int32, C.c_double, C.c_int32, C.c_int32,
-                                                 _f64p, _f64p, _f64p, _i32p, _f64p, C.POINTER(ScoreMarginalsInfo)]
-    lib.score_refine_range_variances.restype = C.c_int
-    lib._score_leverage_bound = True
-    return lib
-
-
-def _dim(prob) -> int:
-    return 3 if isinstance(prob, _Problem3D) else 2
+    return bind(lib, LEVERAGE)
 
 
 def measurement_counts(prob):
@@ -67,27 +50,17 @@ def measurement_counts(prob):
 
 def _row_groups(prob):
     """(first row, rows) of every measurement in the (m, q) order."""
-    d = _dim(prob)
+    d, _ = unknown_sizes(prob)
     n_rel, n_rng, n_pri = measurement_counts(prob)
     rows = np.concatenate([np.full(n_rel, d + d * d), np.ones(n_rng), np.full(n_pri, d)]).astype(np.int64)
     return np.concatenate([[0], np.cumsum(rows)[:-1]]).astype(np.int64), rows
-
-
-def _ptr(a, kind=_f64p):
-    return a.ctypes.data_as(kind) if a is not None and a.size else None
 
 
 class LeverageHandle(SamplesHandle):
     """A refinement handle kept for ``score_refine_leverage`` / ``score_refine_range_variances`` calls on one graph (and,
     being a ``SamplesHandle``, for ``score_refine_samples`` calls with the same draws)."""
 
-    def __init__(self, prob, lib_path: Optional[str] = None, solver_settings: Optional[dict] = None):
-        super().__init__(prob, lib_path, solver_settings)
-        try:
-            _bind(self.lib)
-        except Exception:
-            self.close()
-            raise
+    headers = SamplesHandle.headers + (LEVERAGE,)
 
     def leverage(self, point, pair_ids, n_samples, seed=0, first_sample=0, rel_tol=1e-10, max_iters=4000,
                  block_width=MAX_BLOCK_WIDTH) -> dict:
@@ -103,16 +76,16 @@ class LeverageHandle(SamplesHandle):
         psum, psq = np.zeros(len(pa)), np.zeros(len(pa))
         res, its = np.zeros(S), np.zeros(S, dtype=np.int32)
         info = ScoreSamplesInfo()
-        rc = self.lib.score_refine_leverage(self.h, _ptr(poses), _ptr(lms), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-                                            int(first_sample), int(n_samples), _ptr(pa, _i32p), _ptr(pb, _i32p), len(pa),
-                                            float(rel_tol), int(max_iters), int(block_width), _ptr(sums["lev_sum"]),
-                                            _ptr(sums["lev_sq"]), _ptr(sums["red_sum"]), _ptr(sums["red_sq"]), _ptr(psum), _ptr(psq),
-                                            _ptr(res), _ptr(its, _i32p), C.byref(info))
+        rc = self.lib.score_refine_leverage(self.h, ptr(poses), ptr(lms), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                                            int(first_sample), int(n_samples), ptr(pa, _i32p), ptr(pb, _i32p), len(pa),
+                                            float(rel_tol), int(max_iters), int(block_width), ptr(sums["lev_sum"]),
+                                            ptr(sums["lev_sq"]), ptr(sums["red_sum"]), ptr(sums["red_sq"]), ptr(psum), ptr(psq),
+                                            ptr(res), ptr(its, _i32p), C.byref(info))
         if rc < 0:
             raise RuntimeError(f"score_refine_leverage failed: {self.lib.score_last_error().decode()}")
-        converged = its >= 0  # (a draw that did not converge reports -(steps + 1))
-        out = {"rc": rc, "pair_sum": psum, "pair_sq": psq, "residuals": res, "iterations": np.where(converged, its, -its - 1),
-               "converged": converged, "info": info.as_dict()}
+        iterations, converged = steps_and_converged(its)
+        out = {"rc": rc, "pair_sum": psum, "pair_sq": psq, "residuals": res, "iterations": iterations, "converged": converged,
+               "info": info.as_dict()}
         out.update(sums)
         return out
 
@@ -127,14 +100,14 @@ class LeverageHandle(SamplesHandle):
         its = np.zeros(len(pa), dtype=np.int32)
         sol = np.zeros((len(pa), self.prob.n)) if with_solutions else None
         info = ScoreMarginalsInfo()
-        rc = self.lib.score_refine_range_variances(self.h, _ptr(poses), _ptr(lms), _ptr(pa, _i32p), _ptr(pb, _i32p), len(pa),
-                                                   float(rel_tol), int(max_iters), int(block_width), _ptr(var), _ptr(dist), _ptr(res),
-                                                   _ptr(its, _i32p), _ptr(sol), C.byref(info))
+        rc = self.lib.score_refine_range_variances(self.h, ptr(poses), ptr(lms), ptr(pa, _i32p), ptr(pb, _i32p), len(pa),
+                                                   float(rel_tol), int(max_iters), int(block_width), ptr(var), ptr(dist), ptr(res),
+                                                   ptr(its, _i32p), ptr(sol), C.byref(info))
         if rc < 0:
             raise RuntimeError(f"score_refine_range_variances failed: {self.lib.score_last_error().decode()}")
-        converged = its >= 0
-        return {"rc": rc, "variances": var, "distances": dist, "residuals": res, "iterations": np.where(converged, its, -its - 1),
-                "converged": converged, "solutions": sol, "info": info.as_dict()}
+        iterations, converged = steps_and_converged(its)
+        return {"rc": rc, "variances": var, "distances": dist, "residuals": res, "iterations": iterations, "converged": converged,
+                "solutions": sol, "info": info.as_dict()}
 
 
 def pair_ids(prob, pairs, who: str) -> np.ndarray:
@@ -166,8 +139,7 @@ def pair_gradients(prob, point, ids):
     """(G, distance): column c of G (n x C) is the gradient of |p_a - p_b| of pair c in the refinement's unknowns -- +u on the
     translation unknowns of a, -u on those of b, u the unit vector of p_a - p_b (zero where the distance is <= 1e-12, the
     rule of a range's Jacobian); the fixed first pose has no unknowns."""
-    d = _dim(prob)
-    dp = 6 if d == 3 else 3
+    d, dp = unknown_sizes(prob)
     ids = np.asarray(ids, dtype=np.int64).reshape(-1, 2)
     t, lm = _positions(prob, point)
     pa, pb = prob._point(ids[:, 0], t, lm), prob._point(ids[:, 1], t, lm)

@@ -15,44 +15,17 @@ from typing import Optional
 
 import numpy as np
 
-from .refine import _initial_point, _Problem, _Problem3D
-from .solver import ScoreSettings, _f64p, _i32p, load_library
+from .bindings import MARGINALS, ScoreMarginalsInfo, bind, ptr, steps_and_converged
+from .refine import RefineHandle, _point_arrays, _problem_and_point, unknown_sizes
+from .solver import _i32p
 
 # the symbols include/score_marginals.h declares
-MARGINALS_SYMBOLS = ["score_refine_marginals"]
+MARGINALS_SYMBOLS = list(MARGINALS)
 MAX_BLOCK_WIDTH = 16
 
 
-class ScoreMarginalsInfo(C.Structure):
-    _fields_ = [
-        ("columns", C.c_int32), ("batches", C.c_int32), ("pcg_iters", C.c_int32), ("unconverged", C.c_int32),
-        ("max_residual", C.c_double), ("setup_ms", C.c_double), ("solve_ms", C.c_double),
-    ]
-
-    def as_dict(self) -> dict:
-        return {k: getattr(self, k) for k, _ in self._fields_}
-
-
 def _bind(lib: C.CDLL) -> C.CDLL:
-    if getattr(lib, "_score_marginals_bound", False):
-        return lib
-    for sym in MARGINALS_SYMBOLS:
-        if not hasattr(lib, sym):
-            raise RuntimeError(f"{sym} is missing from the library: rebuild it (the oracle's CPU twin has no marginals: "
-                               "engine='python' runs there)")
-    lib.score_refine_marginals.argtypes = [C.c_void_p, _f64p, _f64p, _i32p, C.c_int32, C.c_double, C.c_int32, C.c_int32,
-                                           _f64p, _f64p, _i32p, C.POINTER(ScoreMarginalsInfo)]
-    lib.score_refine_marginals.restype = C.c_int
-    lib._score_marginals_bound = True
-    return lib
-
-
-def _problem_and_point(data, results, range_weights, loop_closure_weights):
-    if data.dimension == 3:
-        prob = _Problem3D(data, range_weights, loop_closure_weights)
-        return prob, prob.initial_state(results)
-    prob = _Problem(data, range_weights, loop_closure_weights)
-    return prob, _initial_point(prob, results)
+    return bind(lib, MARGINALS)
 
 
 def _select(prob, variables):
@@ -66,8 +39,7 @@ def _select(prob, variables):
         raise ValueError("marginal_covariances: no variables")
     pose_id = {nm: i for i, nm in enumerate(poses)}
     lm_id = {nm: i for i, nm in enumerate(lms)}
-    d = 3 if isinstance(prob, _Problem3D) else 2
-    dp = 6 if d == 3 else 3
+    d, dp = unknown_sizes(prob)
     ids, first, size, seen = [], [], [], set()
     for nm in variables:
         if nm in seen:
@@ -87,6 +59,12 @@ def _select(prob, variables):
     return variables, np.asarray(ids, dtype=np.int32), size, cols
 
 
+def n_columns(prob, ids) -> int:
+    """The unknowns of the variables ``ids`` (poses 0..Np-1, then the landmarks): the columns a call solves for them."""
+    d, dp = unknown_sizes(prob)
+    return int(np.where(np.asarray(ids) < prob.Np, dp, d).sum())
+
+
 def dense_information(prob, point) -> np.ndarray:
     """J'J at the point as a dense matrix (small graphs, tests)."""
     _, J = prob.residuals(point, jac=True)
@@ -104,66 +82,29 @@ def _python_columns(prob, point, cols):
     return X[cols, :], res
 
 
-class MarginalsHandle:
+class MarginalsHandle(RefineHandle):
     """A refinement handle (``score_refine_create``) kept for several ``score_refine_marginals`` calls on one graph: the
     pattern, the chain tables and the block's buffers are set up once."""
 
-    def __init__(self, prob, lib_path: Optional[str] = None, solver_settings: Optional[dict] = None):
-        from .native import score_graph_struct
-
-        self.prob = prob
-        self.lib = _bind(load_library(lib_path))
-        st = ScoreSettings()
-        self.lib.score_default_settings(C.byref(st))
-        for k, v in (solver_settings or {}).items():
-            if not hasattr(st, k):
-                raise ValueError(f"unknown solver setting {k}")
-            setattr(st, k, v)
-        g = score_graph_struct(prob.a)
-        self.h = C.c_void_p()
-        if self.lib.score_refine_create(C.byref(g), C.byref(st), C.byref(self.h)) != 0:
-            raise RuntimeError(f"score_refine_create failed: {self.lib.score_last_error().decode()}")
+    headers = RefineHandle.headers + (MARGINALS,)
 
     def columns(self, point, ids, rel_tol=1e-10, max_iters=4000, block_width=MAX_BLOCK_WIDTH):
         """``score_refine_marginals`` as it is: returns (return code, C x C matrix whose column c is x_c on the selected
         rows -- not symmetrised --, residuals, steps per column, converged mask, the call's info record)."""
         prob = self.prob
-        if isinstance(prob, _Problem3D):
-            R, t, lm = point
-            poses = np.ascontiguousarray(np.concatenate([R.reshape(prob.Np, 9), t], axis=1), dtype=np.float64)
-            lms = np.ascontiguousarray(lm, dtype=np.float64).reshape(-1, 3)
-            per = np.where(np.asarray(ids) < prob.Np, 6, 3)
-        else:
-            th, t, lm = prob.split(point)
-            poses = np.ascontiguousarray(np.column_stack([th, t]), dtype=np.float64)
-            lms = np.ascontiguousarray(lm, dtype=np.float64).reshape(-1, 2)
-            per = np.where(np.asarray(ids) < prob.Np, 3, 2)
+        poses, lms = _point_arrays(prob, point)
         ids = np.ascontiguousarray(ids, dtype=np.int32)
-        ncol = int(per.sum())
+        ncol = n_columns(prob, ids)
         joint = np.zeros((ncol, ncol))
         res = np.zeros(ncol)
         its = np.zeros(ncol, dtype=np.int32)
         info = ScoreMarginalsInfo()
-        rc = self.lib.score_refine_marginals(self.h, poses.ctypes.data_as(_f64p), lms.ctypes.data_as(_f64p) if len(lms) else None,
-                                             ids.ctypes.data_as(_i32p), len(ids), float(rel_tol), int(max_iters), int(block_width),
-                                             joint.ctypes.data_as(_f64p), res.ctypes.data_as(_f64p), its.ctypes.data_as(_i32p),
-                                             C.byref(info))
+        rc = self.lib.score_refine_marginals(self.h, ptr(poses), ptr(lms), ptr(ids, _i32p), len(ids), float(rel_tol), int(max_iters),
+                                             int(block_width), ptr(joint), ptr(res), ptr(its, _i32p), C.byref(info))
         if rc < 0:
             raise RuntimeError(f"score_refine_marginals failed: {self.lib.score_last_error().decode()}")
-        converged = its >= 0  # (a column that did not converge reports -(steps + 1))
-        steps = np.where(converged, its, -its - 1)
+        steps, converged = steps_and_converged(its)
         return rc, joint, res, steps, converged, info.as_dict()
-
-    def close(self) -> None:
-        if self.h:
-            self.lib.score_refine_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 def device_columns(prob, point, ids, rel_tol=1e-10, max_iters=4000, block_width=MAX_BLOCK_WIDTH, lib_path=None,
@@ -201,10 +142,17 @@ def marginal_covariances(data, results, variables=None, joint: bool = False, ran
     else:
         _, A, res, steps, converged, rec = device_columns(prob, point, ids, rel_tol, max_iters, int(block_width), lib_path,
                                                           solver_settings)
+    return _member_result("marginal_covariances", None, names, size, A, res, steps, converged, rec, engine, joint, max_iters)
+
+
+def _member_result(who, where, names, size, A, res, steps, converged, rec, engine, joint, max_iters):
+    """``(covariances, info)`` of one graph from its columns.  ``who`` and ``where`` (None: nothing) open the message about
+    columns that did not converge."""
     off = np.concatenate([[0], np.cumsum(size)])
     if not np.all(converged):
         bad = [nm for k, nm in enumerate(names) if not np.all(converged[off[k]:off[k + 1]])]
-        raise RuntimeError(f"marginal_covariances: the columns of {', '.join(bad)} did not converge in {max_iters} iterations "
+        at = f"{who}: {where}: " if where else f"{who}: "
+        raise RuntimeError(f"{at}the columns of {', '.join(bad)} did not converge in {max_iters} iterations "
                            "(a variable the measurements do not determine?)")
     S = 0.5 * (A + A.T)
     out = {nm: S[off[k]:off[k + 1], off[k]:off[k + 1]].copy() for k, nm in enumerate(names)}

@@ -18,37 +18,23 @@ from typing import Optional
 
 import numpy as np
 
-from .marginals import MAX_BLOCK_WIDTH, _problem_and_point, _python_columns, _select
-from .refine import _Problem3D
-from .refine_robust import _point_arrays
-from .solver import _f64p, _i32p
+from .bindings import MARGINALS_BATCH, ScoreMarginalsBatchInfo, bind, ptr, steps_and_converged
+from .marginals import MAX_BLOCK_WIDTH, _member_result, _problem_and_point, _python_columns, _select, n_columns
+from .solver import _i32p
 
 # the symbols include/score_marginals_batch.h declares
-MARGINALS_BATCH_SYMBOLS = ["score_refine_batch_marginals"]
-
-
-class ScoreMarginalsBatchInfo(C.Structure):
-    _fields_ = [
-        ("columns", C.c_int32), ("passes", C.c_int32), ("pcg_iters", C.c_int32), ("unconverged", C.c_int32),
-        ("max_residual", C.c_double), ("setup_ms", C.c_double), ("solve_ms", C.c_double),
-    ]
-
-    def as_dict(self) -> dict:
-        return {k: getattr(self, k) for k, _ in self._fields_}
+MARGINALS_BATCH_SYMBOLS = list(MARGINALS_BATCH)
 
 
 def _bind(lib: C.CDLL) -> C.CDLL:
-    if getattr(lib, "_score_marginals_batch_bound", False):
-        return lib
-    for sym in MARGINALS_BATCH_SYMBOLS:
-        if not hasattr(lib, sym):
-            raise RuntimeError(f"{sym} is missing from the library: rebuild it (the oracle's CPU twin has no marginals: "
-                               "engine='python' runs there)")
-    lib.score_refine_batch_marginals.argtypes = [C.c_void_p, _f64p, _f64p, _i32p, _i32p, C.c_double, C.c_int32, C.c_int32,
-                                                 _f64p, _f64p, _i32p, C.POINTER(ScoreMarginalsBatchInfo)]
-    lib.score_refine_batch_marginals.restype = C.c_int
-    lib._score_marginals_batch_bound = True
-    return lib
+    return bind(lib, MARGINALS_BATCH)
+
+
+def _flat_ids(ids_per_member):
+    """The members' variable ids as the group calls take them: (ids per member, var_ptr, all ids in a row)."""
+    ids = [np.asarray(v, dtype=np.int32).ravel() for v in ids_per_member]
+    var_ptr = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(v) for v in ids])]), dtype=np.int32)
+    return ids, var_ptr, np.ascontiguousarray(np.concatenate(ids + [np.zeros(0, np.int32)]), dtype=np.int32)
 
 
 def batch_columns(handle, points, ids_per_member, rel_tol=1e-10, max_iters=4000, block_width=MAX_BLOCK_WIDTH):
@@ -60,50 +46,24 @@ def batch_columns(handle, points, ids_per_member, rel_tol=1e-10, max_iters=4000,
     if len(points) != len(probs) or len(ids_per_member) != len(probs):
         raise ValueError("one point and one list of variables per member expected")
     lib = _bind(handle.lib)
-    arrays = [_point_arrays(prob, x) for prob, x in zip(probs, points)]
-    poses = np.ascontiguousarray(np.concatenate([a[0].ravel() for a in arrays]))
-    lms = np.ascontiguousarray(np.concatenate([a[1].ravel() for a in arrays]))
-    ids = [np.asarray(v, dtype=np.int32).ravel() for v in ids_per_member]
-    var_ptr = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(v) for v in ids])]), dtype=np.int32)
-    flat = np.ascontiguousarray(np.concatenate(ids + [np.zeros(0, np.int32)]), dtype=np.int32)
-    dim = 3 if isinstance(probs[0], _Problem3D) else 2
-    ncol = [int(np.where(v < prob.Np, 3 * (dim - 1), dim).sum()) for prob, v in zip(probs, ids)]
+    _, poses, lms = handle._flat_points(points)
+    ids, var_ptr, flat = _flat_ids(ids_per_member)
+    ncol = [n_columns(prob, v) for prob, v in zip(probs, ids)]
     joint = np.zeros(max(1, sum(c * c for c in ncol)))
     res = np.zeros(max(1, sum(ncol)))
     its = np.zeros(max(1, sum(ncol)), dtype=np.int32)
     info = ScoreMarginalsBatchInfo()
-    rc = lib.score_refine_batch_marginals(handle.h, poses.ctypes.data_as(_f64p), lms.ctypes.data_as(_f64p) if lms.size else None,
-                                          var_ptr.ctypes.data_as(_i32p), flat.ctypes.data_as(_i32p) if flat.size else None,
-                                          float(rel_tol), int(max_iters), int(block_width), joint.ctypes.data_as(_f64p),
-                                          res.ctypes.data_as(_f64p), its.ctypes.data_as(_i32p), C.byref(info))
+    rc = lib.score_refine_batch_marginals(handle.h, ptr(poses), ptr(lms), ptr(var_ptr, _i32p), ptr(flat, _i32p), float(rel_tol),
+                                          int(max_iters), int(block_width), ptr(joint), ptr(res), ptr(its, _i32p), C.byref(info))
     if rc < 0:
         raise RuntimeError(f"score_refine_batch_marginals failed: {lib.score_last_error().decode()}")
     out, j0, c0 = [], 0, 0
     for c in ncol:
-        it = its[c0 : c0 + c]
-        converged = it >= 0  # (a column that did not converge reports -(steps + 1))
-        out.append((joint[j0 : j0 + c * c].reshape(c, c).copy(), res[c0 : c0 + c].copy(), np.where(converged, it, -it - 1), converged))
+        steps, converged = steps_and_converged(its[c0 : c0 + c])
+        out.append((joint[j0 : j0 + c * c].reshape(c, c).copy(), res[c0 : c0 + c].copy(), steps, converged))
         j0 += c * c
         c0 += c
     return rc, out, info.as_dict()
-
-
-def _member_result(where, names, size, A, res, steps, converged, rec, engine, joint, max_iters):
-    """What ``marginal_covariances`` returns for one graph, from its columns (the same operations in the same order)."""
-    off = np.concatenate([[0], np.cumsum(size)])
-    if not np.all(converged):
-        bad = [nm for k, nm in enumerate(names) if not np.all(converged[off[k]:off[k + 1]])]
-        raise RuntimeError(f"marginal_covariances_batch: {where}: the columns of {', '.join(bad)} did not converge in {max_iters} "
-                           "iterations (a variable the measurements do not determine?)")
-    S = 0.5 * (A + A.T)
-    out = {nm: S[off[k]:off[k + 1], off[k]:off[k + 1]].copy() for k, nm in enumerate(names)}
-    info = {"order": names, "residuals": res, "iterations": steps, "asymmetry": float(np.max(np.abs(A - A.T))),
-            "pcg_iters": int(rec["pcg_iters"]), "batches": int(rec["batches"]), "setup_ms": float(rec["setup_ms"]),
-            "solve_ms": float(rec["solve_ms"]), "engine": engine}
-    if joint:
-        info["joint"] = S
-        info["joint_raw"] = A
-    return out, info
 
 
 def group_marginals(handle, probs, points, selections, indices, number, rel_tol=1e-10, max_iters=4000,
@@ -122,7 +82,8 @@ def group_marginals(handle, probs, points, selections, indices, number, rel_tol=
     out = []
     for (names, _, size, c), (A, res, steps, converged), i in zip(selections, cols, indices):
         mine = dict(rec, batches=0 if engine == "python" else -(-len(c) // int(block_width)))
-        cov, info = _member_result(f"graph {i}", names, size, A, res, steps, converged, mine, engine, joint, max_iters)
+        cov, info = _member_result("marginal_covariances_batch", f"graph {i}", names, size, A, res, steps, converged, mine, engine,
+                                   joint, max_iters)
         info["group"], info["passes"] = number, int(rec["passes"])
         out.append((cov, info))
     return out

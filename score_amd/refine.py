@@ -26,6 +26,7 @@ and trial points are device kernels too, the host only steers the Levenberg-Marq
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import Optional, Tuple
 
 import numpy as np
@@ -33,7 +34,9 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
 from . import compat
-from .native import graph_arrays
+from .bindings import bind, ptr
+from .native import graph_arrays, score_graph_struct
+from .solver import LinearSolver, ScoreRefineInfo, load_library, make_settings
 
 
 def _weighted_ranges(a: dict, range_weights) -> dict:
@@ -358,8 +361,6 @@ class _DeviceNormalEquations:
     with one chain per robot (node = pose: theta, x, y), and every solve maps the current values onto it."""
 
     def __init__(self, prob: _Problem, J: sp.csr_matrix, lib_path: Optional[str], settings: Optional[dict]):
-        from .solver import LinearSolver
-
         ones = J.copy()
         ones.data[:] = 1.0
         pat = (ones.T @ ones + sp.identity(prob.n, format="csr")).tocsr()
@@ -405,37 +406,72 @@ class _DeviceNormalEquations:
         self.solver.close()
 
 
+class _Handle:
+    """A handle of the library with the context manager that destroys it.  ``headers``: the tables (``bindings.Table``) of the
+    calls the handle makes; subclasses extend them.  They are bound before the handle is created, so a library that lacks a
+    symbol is refused with nothing to release."""
+
+    headers: tuple = ()
+    destroy = "score_refine_destroy"
+
+    def __init__(self, lib_path: Optional[str], solver_settings: Optional[dict]):
+        self.lib = load_library(lib_path)
+        for table in self.headers:
+            bind(self.lib, table)
+        self.h = C.c_void_p()
+        self._create(make_settings(self.lib, solver_settings))
+
+    def close(self) -> None:
+        if self.h:
+            getattr(self.lib, self.destroy)(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class RefineHandle(_Handle):
+    """A refinement handle (``score_refine_create``) on one graph: points go in and come out in the problem's own form
+    (``_Problem``: packed unknowns; ``_Problem3D``: (R, t, lm))."""
+
+    def __init__(self, prob, lib_path: Optional[str] = None, solver_settings: Optional[dict] = None):
+        self.prob = prob
+        super().__init__(lib_path, solver_settings)
+
+    def _create(self, st) -> None:
+        g = score_graph_struct(self.prob.a)
+        if self.lib.score_refine_create(C.byref(g), C.byref(st), C.byref(self.h)) != 0:
+            raise RuntimeError(f"score_refine_create failed: {self.lib.score_last_error().decode()}")
+
+    def run(self, point, max_iters: int = 50, tol: float = 1e-10):
+        """``score_refine_run`` (the whole LM loop behind the C ABI): (point, info dict)."""
+        poses_in, lms_in = _point_arrays(self.prob, point)
+        poses_out, lms_out = _point_outputs(poses_in, lms_in)
+        info = ScoreRefineInfo()
+        rc = self.lib.score_refine_run(self.h, ptr(poses_in), ptr(lms_in), int(max_iters), float(tol), ptr(poses_out), ptr(lms_out),
+                                       C.byref(info))
+        if rc != 0:
+            raise RuntimeError(f"score_refine_run failed: {self.lib.score_last_error().decode()}")
+        return _point_from(self.prob, poses_out, lms_out), info.as_dict()
+
+
+def _problem_and_point(data, results, range_weights=None, loop_closure_weights=None):
+    """The least-squares problem of ``data`` under the weights and ``results`` as a point of it."""
+    if data.dimension == 3:
+        prob = _Problem3D(data, range_weights, loop_closure_weights)
+        return prob, prob.initial_state(results)
+    prob = _Problem(data, range_weights, loop_closure_weights)
+    return prob, _initial_point(prob, results)
+
+
 def _refine_native(prob: _Problem, u0: np.ndarray, max_iters: int, tol: float, lib_path: Optional[str],
                    solver_settings: Optional[dict]):
-    """The whole LM loop behind the C ABI (score_refine_*).  Returns (u, info dict)."""
-    import ctypes as C
-
-    from .native import score_graph_struct
-    from .solver import ScoreRefineInfo, ScoreSettings, _f64p, load_library
-
-    lib = load_library(lib_path)
-    st = ScoreSettings()
-    lib.score_default_settings(C.byref(st))
-    for k, v in (solver_settings or {}).items():
-        if not hasattr(st, k):
-            raise ValueError(f"unknown solver setting {k}")
-        setattr(st, k, v)
-    g = score_graph_struct(prob.a)
-    h = C.c_void_p()
-    if lib.score_refine_create(C.byref(g), C.byref(st), C.byref(h)) != 0:
-        raise RuntimeError(f"score_refine_create failed: {lib.score_last_error().decode()}")
-    try:
-        poses_in, lms_in = _point_arrays(prob, u0)
-        poses_out, lms_out = np.empty_like(poses_in), np.empty((max(1, len(lms_in)), lms_in.shape[1]))
-        info = ScoreRefineInfo()
-        rc = lib.score_refine_run(h, poses_in.ctypes.data_as(_f64p), lms_in.ctypes.data_as(_f64p) if len(lms_in) else None,
-                                  int(max_iters), float(tol), poses_out.ctypes.data_as(_f64p), lms_out.ctypes.data_as(_f64p),
-                                  C.byref(info))
-        if rc != 0:
-            raise RuntimeError(f"score_refine_run failed: {lib.score_last_error().decode()}")
-    finally:
-        lib.score_refine_destroy(h)
-    return _point_from(prob, poses_out, lms_out), info.as_dict()
+    """One ``RefineHandle.run`` on a handle of its own.  Returns (u, info dict)."""
+    with RefineHandle(prob, lib_path, solver_settings) as h:
+        return h.run(u0, max_iters, tol)
 
 
 def _native_info(ni: dict, iterations: str = "iterations") -> dict:
@@ -460,12 +496,7 @@ def refine_estimate(data, results, max_iters: int = 50, tol: float = 1e-10, verb
         raise ValueError("linear_solver must be 'device' or 'scipy'")
     if engine not in ("native", "python"):
         raise ValueError("engine must be 'native' or 'python'")
-    if data.dimension == 3:
-        prob = _Problem3D(data, range_weights, loop_closure_weights)
-        u = prob.initial_state(results)
-    else:
-        prob = _Problem(data, range_weights, loop_closure_weights)
-        u = _initial_point(prob, results)
+    prob, u = _problem_and_point(data, results, range_weights, loop_closure_weights)
     if engine == "native" and linear_solver == "device" and prob.n > 0:
         u, ni = _refine_native(prob, u, max_iters, tol, lib_path, solver_settings)
         return _as_results(prob, u, results, ni["cost_final"]), _native_info(ni)
@@ -513,10 +544,20 @@ def _point_arrays(prob, point):
     return np.ascontiguousarray(np.column_stack([th, t]), dtype=np.float64), np.ascontiguousarray(lm, dtype=np.float64).reshape(-1, 2)
 
 
+def _point_outputs(poses_in, lms_in):
+    """Arrays for the point a call writes (the landmarks' is never empty)."""
+    return np.empty_like(poses_in), np.empty((max(1, len(lms_in)), lms_in.shape[1]))
+
+
 def _point_from(prob, poses, lms):
     if isinstance(prob, _Problem3D):
         return poses[:, :9].reshape(-1, 3, 3).copy(), poses[:, 9:12].copy(), lms[: prob.Nl].copy()
     return prob.pack(poses[:, 0], poses[:, 1:3], lms[: prob.Nl])
+
+
+def unknown_sizes(prob) -> Tuple[int, int]:
+    """(d, dp): the unknowns of a landmark and of a pose -- (2, 3) for (theta, x, y), (3, 6) for (omega, v)."""
+    return (3, 6) if isinstance(prob, _Problem3D) else (2, 3)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

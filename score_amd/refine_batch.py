@@ -18,10 +18,16 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from .refine import (GRADIENT, SOLVE, _as_results, _attempt, _gradient, _initial_point, _Member, _native_info, _point_arrays,
-                     _point_from, _Problem, _Problem3D, refine_estimate)
+from .bindings import REFINE_BATCH, REFINE_ROBUST_BATCH, ScoreRefineRobustInfo, ScoreRefineRobustSettings, bind, ptr
+from .native import ScoreGraph, score_graph_struct
+from .refine import (GRADIENT, SOLVE, _as_results, _attempt, _gradient, _Handle, _Member, _native_info, _point_arrays, _point_from,
+                     _problem_and_point as _problem_of, refine_estimate)
+from .robust import n_loop_closures_of
+from .solver import ScoreRefineInfo
 
-REFINE_BATCH_SYMBOLS = ["score_refine_batch_create", "score_refine_batch_run", "score_refine_batch_destroy"]
+# the symbols include/score_refine_batch.h declares
+REFINE_BATCH_SYMBOLS = list(REFINE_BATCH)
+
 
 def _weights_of(weights, count: int, what: str) -> list:
     if weights is None:
@@ -30,14 +36,6 @@ def _weights_of(weights, count: int, what: str) -> list:
     if len(weights) != count:
         raise ValueError(f"{what}: one entry per graph expected ({count}), got {len(weights)}")
     return weights
-
-
-def _problem_of(data, results, rw, lw):
-    if data.dimension == 3:
-        prob = _Problem3D(data, rw, lw)
-        return prob, prob.initial_state(results)
-    prob = _Problem(data, rw, lw)
-    return prob, _initial_point(prob, results)
 
 
 class _LockStep:
@@ -87,65 +85,62 @@ def _python_lock_step(probs, points, max_iters: int, tol: float):
 
 
 def _bind(lib):
-    from .native import ScoreGraph
-    from .solver import ScoreRefineInfo, ScoreSettings, _f64p
-
-    if getattr(lib, "_score_refine_batch_bound", False):
-        return lib
-    lib.score_refine_batch_create.argtypes = [C.POINTER(ScoreGraph), C.c_int32, C.POINTER(ScoreSettings), C.POINTER(C.c_void_p)]
-    lib.score_refine_batch_run.argtypes = [C.c_void_p, _f64p, _f64p, C.c_int32, C.c_double, _f64p, _f64p, C.POINTER(ScoreRefineInfo)]
-    lib.score_refine_batch_destroy.argtypes = [C.c_void_p]
-    lib.score_refine_batch_destroy.restype = None
-    lib._score_refine_batch_bound = True
-    return lib
+    return bind(lib, REFINE_BATCH)
 
 
-class RefineBatchHandle:
+def member_counts(probs):
+    """(ranges, loop closures) of every member."""
+    return [len(p.ra) for p in probs], [n_loop_closures_of(p.a) for p in probs]
+
+
+class RefineBatchHandle(_Handle):
     """A group handle (``score_refine_batch_create``) over ``probs`` (all of one dimension, every one with unknowns); ``run``
     takes and returns points in the problems' own form (``_Problem``: packed unknowns; ``_Problem3D``: (R, t, lm))."""
 
-    def __init__(self, probs: Sequence, lib_path: Optional[str] = None, solver_settings: Optional[dict] = None):
-        from .native import ScoreGraph, score_graph_struct
-        from .solver import ScoreSettings, load_library
+    headers = (REFINE_BATCH,)
+    destroy = "score_refine_batch_destroy"
 
+    def __init__(self, probs: Sequence, lib_path: Optional[str] = None, solver_settings: Optional[dict] = None):
         self.probs = list(probs)
-        self.lib = _bind(load_library(lib_path))
-        st = ScoreSettings()
-        self.lib.score_default_settings(C.byref(st))
-        for k, v in (solver_settings or {}).items():
-            if not hasattr(st, k):
-                raise ValueError(f"unknown solver setting {k}")
-            setattr(st, k, v)
+        super().__init__(lib_path, solver_settings)
+
+    def _create(self, st) -> None:
         graphs = (ScoreGraph * len(self.probs))(*[score_graph_struct(p.a) for p in self.probs])
-        self.h = C.c_void_p()
         if self.lib.score_refine_batch_create(graphs, len(self.probs), C.byref(st), C.byref(self.h)) != 0:
             raise RuntimeError(f"score_refine_batch_create failed: {self.lib.score_last_error().decode()}")
 
-    def run(self, points, max_iters: int = 50, tol: float = 1e-10):
-        """``score_refine_batch_run``: (points, info dicts), member by member."""
-        from .solver import ScoreRefineInfo, _f64p
-
+    def _flat_points(self, points):
+        """The members' points as the group calls take them: (the C arrays member by member, all poses, all landmarks)."""
         if len(points) != len(self.probs):
             raise ValueError("one point per member expected")
         arrays = [_point_arrays(prob, x) for prob, x in zip(self.probs, points)]
-        width = arrays[0][1].shape[1]
-        poses_in = np.ascontiguousarray(np.concatenate([a[0].ravel() for a in arrays]))
-        lms_in = np.ascontiguousarray(np.concatenate([a[1].ravel() for a in arrays]))
-        poses_out, lms_out = np.empty_like(poses_in), np.empty(max(1, lms_in.size))
-        infos = (ScoreRefineInfo * len(self.probs))()
-        p = lambda x: x.ctypes.data_as(_f64p)  # noqa: E731
-        rc = self.lib.score_refine_batch_run(self.h, p(poses_in), p(lms_in) if lms_in.size else None, int(max_iters), float(tol),
-                                             p(poses_out), p(lms_out), infos)
-        if rc != 0:
-            raise RuntimeError(f"score_refine_batch_run failed: {self.lib.score_last_error().decode()}")
+        poses = np.ascontiguousarray(np.concatenate([a[0].ravel() for a in arrays]))
+        lms = np.ascontiguousarray(np.concatenate([a[1].ravel() for a in arrays]))
+        return arrays, poses, lms
+
+    def _points_from(self, arrays, poses, lms):
+        """The way back: the members' points out of flat arrays laid out as ``_flat_points`` lays out ``arrays``."""
         out, p0, l0 = [], 0, 0
         for prob, (pa, la) in zip(self.probs, arrays):
-            po = poses_out[p0 : p0 + pa.size].reshape(pa.shape)
-            lo = lms_out[l0 : l0 + la.size].reshape(-1, width)
-            out.append(_point_from(prob, po, lo))
+            out.append(_point_from(prob, poses[p0 : p0 + pa.size].reshape(pa.shape), lms[l0 : l0 + la.size].reshape(la.shape)))
             p0 += pa.size
             l0 += la.size
-        return out, [infos[i].as_dict() for i in range(len(self.probs))]
+        return out
+
+    def _per_member(self, flat, counts):
+        offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        return [flat[offs[g] : offs[g + 1]].copy() for g in range(len(counts))]
+
+    def run(self, points, max_iters: int = 50, tol: float = 1e-10):
+        """``score_refine_batch_run``: (points, info dicts), member by member."""
+        arrays, poses_in, lms_in = self._flat_points(points)
+        poses_out, lms_out = np.empty_like(poses_in), np.empty(max(1, lms_in.size))
+        infos = (ScoreRefineInfo * len(self.probs))()
+        rc = self.lib.score_refine_batch_run(self.h, ptr(poses_in), ptr(lms_in), int(max_iters), float(tol), ptr(poses_out),
+                                             ptr(lms_out), infos)
+        if rc != 0:
+            raise RuntimeError(f"score_refine_batch_run failed: {self.lib.score_last_error().decode()}")
+        return self._points_from(arrays, poses_out, lms_out), [infos[i].as_dict() for i in range(len(self.probs))]
 
     def marginals(self, points, ids_per_member, rel_tol: float = 1e-10, max_iters: int = 4000, block_width: int = 16):
         """``score_refine_batch_marginals`` at ``points`` (include/score_marginals_batch.h): ``ids_per_member`` lists the
@@ -174,63 +169,43 @@ class RefineBatchHandle:
         return batch_draws(self, points, ids_per_member, n_samples, seeds, first_sample, rel_tol, max_iters, block_width, with_rhs,
                            with_noise)
 
-    def _flat_points(self, points):
-        if len(points) != len(self.probs):
-            raise ValueError("one point per member expected")
-        arrays = [_point_arrays(prob, x) for prob, x in zip(self.probs, points)]
-        poses = np.ascontiguousarray(np.concatenate([a[0].ravel() for a in arrays]))
-        lms = np.ascontiguousarray(np.concatenate([a[1].ravel() for a in arrays]))
-        return arrays, poses, lms
+    def _robust(self):
+        """The library with the calls of include/score_refine_robust_batch.h bound."""
+        return bind(self.lib, REFINE_ROBUST_BATCH)
 
-    def _per_member(self, flat, counts):
-        offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-        return [flat[offs[g] : offs[g + 1]].copy() for g in range(len(counts))]
+    def _robust_outputs(self):
+        """(ranges per member, loop closures per member, [weights, residuals, loop-closure weights, loop-closure residuals])."""
+        n_rng, n_lc = member_counts(self.probs)
+        return n_rng, n_lc, [np.ones(max(1, int(sum(n)))) for n in (n_rng, n_rng, n_lc, n_lc)]
 
     def robust_run(self, points, settings, keep_weights: bool = False):
         """``score_refine_batch_robust_run`` (include/score_refine_robust_batch.h): ``settings`` is one
         ``ScoreRefineRobustSettings`` (shared) or a sequence with one per member.  Returns (points, per member
         ``(weights, residuals, loop-closure weights, loop-closure residuals)``, info dicts)."""
-        from .refine_robust import ScoreRefineRobustInfo, ScoreRefineRobustSettings
-        from .refine_robust_batch import _bind as bind_robust, member_counts
-        from .solver import _f64p
-
-        lib = bind_robust(self.lib)
+        lib = self._robust()
         G = len(self.probs)
         recs = [settings] if isinstance(settings, ScoreRefineRobustSettings) else list(settings)
         rs = (ScoreRefineRobustSettings * max(1, len(recs)))(*recs)
         arrays, poses_in, lms_in = self._flat_points(points)
-        width = arrays[0][1].shape[1]
         poses_out, lms_out = np.empty_like(poses_in), np.empty(max(1, lms_in.size))
-        n_rng, n_lc = member_counts(self.probs)
-        w, r, wl, rl = (np.ones(max(1, int(sum(n)))) for n in (n_rng, n_rng, n_lc, n_lc))
+        n_rng, n_lc, (w, r, wl, rl) = self._robust_outputs()
         infos = (ScoreRefineRobustInfo * G)()
-        p = lambda x: x.ctypes.data_as(_f64p)  # noqa: E731
-        rc = lib.score_refine_batch_robust_run(self.h, rs, len(recs), p(poses_in), p(lms_in) if lms_in.size else None, p(poses_out),
-                                               p(lms_out), p(w), p(r), p(wl), p(rl), 1 if keep_weights else 0, infos)
+        rc = lib.score_refine_batch_robust_run(self.h, rs, len(recs), ptr(poses_in), ptr(lms_in), ptr(poses_out), ptr(lms_out), ptr(w),
+                                               ptr(r), ptr(wl), ptr(rl), 1 if keep_weights else 0, infos)
         if rc != 0:
             raise RuntimeError(f"score_refine_batch_robust_run failed: {self.lib.score_last_error().decode()}")
-        out, p0, l0 = [], 0, 0
-        for prob, (pa, la) in zip(self.probs, arrays):
-            out.append(_point_from(prob, poses_out[p0 : p0 + pa.size].reshape(pa.shape), lms_out[l0 : l0 + la.size].reshape(-1, width)))
-            p0 += pa.size
-            l0 += la.size
         per = list(zip(self._per_member(w, n_rng), self._per_member(r, n_rng), self._per_member(wl, n_lc), self._per_member(rl, n_lc)))
-        return out, per, [infos[i].as_dict() for i in range(G)]
+        return self._points_from(arrays, poses_out, lms_out), per, [infos[i].as_dict() for i in range(G)]
 
     def residuals(self, points, mu=0.0, c=3.0, c_rel=3.0):
         """``score_refine_batch_residuals`` at ``points``: ``mu``, ``c``, ``c_rel`` a scalar or one entry per member.  Returns
         per member ``(residuals, loop-closure residuals, weights, loop-closure weights)``."""
-        from .refine_robust_batch import _bind as bind_robust, member_counts
-        from .solver import _f64p
-
-        lib = bind_robust(self.lib)
+        lib = self._robust()
         G = len(self.probs)
         mu, c, c_rel = (np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (G,))) for v in (mu, c, c_rel))
         _, poses, lms = self._flat_points(points)
-        n_rng, n_lc = member_counts(self.probs)
-        w, r, wl, rl = (np.ones(max(1, int(sum(n)))) for n in (n_rng, n_rng, n_lc, n_lc))
-        p = lambda x: x.ctypes.data_as(_f64p)  # noqa: E731
-        rc = lib.score_refine_batch_residuals(self.h, p(poses), p(lms) if lms.size else None, p(mu), p(c), p(c_rel), p(r), p(rl), p(w), p(wl))
+        n_rng, n_lc, (w, r, wl, rl) = self._robust_outputs()
+        rc = lib.score_refine_batch_residuals(self.h, ptr(poses), ptr(lms), ptr(mu), ptr(c), ptr(c_rel), ptr(r), ptr(rl), ptr(w), ptr(wl))
         if rc != 0:
             raise RuntimeError(f"score_refine_batch_residuals failed: {self.lib.score_last_error().decode()}")
         return list(zip(self._per_member(r, n_rng), self._per_member(rl, n_lc), self._per_member(w, n_rng), self._per_member(wl, n_lc)))
@@ -238,30 +213,15 @@ class RefineBatchHandle:
     def robust_rounds(self):
         """``score_refine_batch_robust_rounds``: (lock-step rounds, passes in which some member changed stage) of the last
         ``robust_run``."""
-        from .refine_robust_batch import _bind as bind_robust
-
         rounds, stages = C.c_int32(0), C.c_int32(0)
-        if bind_robust(self.lib).score_refine_batch_robust_rounds(self.h, C.byref(rounds), C.byref(stages)) != 0:
+        if self._robust().score_refine_batch_robust_rounds(self.h, C.byref(rounds), C.byref(stages)) != 0:
             raise RuntimeError(f"score_refine_batch_robust_rounds failed: {self.lib.score_last_error().decode()}")
         return int(rounds.value), int(stages.value)
 
     def restore(self) -> None:
         """``score_refine_batch_restore``: the handle's cost reads the measured precisions again (after ``keep_weights``)."""
-        from .refine_robust_batch import _bind as bind_robust
-
-        if bind_robust(self.lib).score_refine_batch_restore(self.h) != 0:
+        if self._robust().score_refine_batch_restore(self.h) != 0:
             raise RuntimeError(f"score_refine_batch_restore failed: {self.lib.score_last_error().decode()}")
-
-    def close(self) -> None:
-        if self.h:
-            self.lib.score_refine_batch_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-10, range_weights=None, loop_closure_weights=None,

@@ -24,53 +24,19 @@ from typing import Optional
 
 import numpy as np
 
-from .refine import (_as_results, _DeviceNormalEquations, _initial_point, _lm_loop, _Member, _native_info, _point_arrays, _point_from,
-                     _Problem, _Problem3D)
+from .bindings import REFINE_ROBUST, ScoreRefineRobustInfo, ScoreRefineRobustSettings, bind, ptr
+from .refine import (RefineHandle, _as_results, _DeviceNormalEquations, _lm_loop, _Member, _native_info, _point_arrays, _point_from,
+                     _point_outputs, _problem_and_point, _Problem3D)
 from .robust import BINARY_TOL, _robust_info, gnc_tls_weight, initial_mu, n_loop_closures_of
-from .solver import ScoreSettings, _f64p, load_library
 
 # the symbols include/score_refine_robust.h declares
-REFINE_ROBUST_SYMBOLS = ["score_refine_robust_default_settings", "score_refine_robust_run", "score_refine_residuals"]
+REFINE_ROBUST_SYMBOLS = list(REFINE_ROBUST)
 
 FAMILY_RANGES, FAMILY_LOOP_CLOSURES = 1, 2
 
 
-class ScoreRefineRobustSettings(C.Structure):
-    _fields_ = [
-        ("inlier_threshold", C.c_double), ("rel_threshold", C.c_double), ("mu_step", C.c_double), ("min_weight", C.c_double),
-        ("families", C.c_int32), ("max_outer", C.c_int32), ("inner_iters", C.c_int32), ("max_iters", C.c_int32),
-        ("tol", C.c_double),
-    ]
-
-
-class ScoreRefineRobustInfo(C.Structure):
-    _fields_ = [
-        ("outer_iterations", C.c_int32), ("converged", C.c_int32), ("outliers", C.c_int32), ("rel_outliers", C.c_int32),
-        ("mu", C.c_double), ("lm_iterations", C.c_int32), ("linear_solves", C.c_int32), ("pcg_iters", C.c_int32),
-        ("cost_initial", C.c_double), ("cost_final", C.c_double), ("grad_inf", C.c_double),
-        ("setup_ms", C.c_double), ("solve_ms", C.c_double),
-    ]
-
-    def as_dict(self) -> dict:
-        return {k: getattr(self, k) for k, _ in self._fields_}
-
-
 def _bind(lib: C.CDLL) -> C.CDLL:
-    if getattr(lib, "_score_refine_robust_bound", False):
-        return lib
-    for sym in REFINE_ROBUST_SYMBOLS:
-        if not hasattr(lib, sym):
-            raise RuntimeError(f"{sym} is missing from the library: rebuild it (the CPU twin of the tests has no robust "
-                               "refinement: engine='python' runs there)")
-    lib.score_refine_robust_default_settings.argtypes = [C.POINTER(ScoreRefineRobustSettings)]
-    lib.score_refine_robust_default_settings.restype = None
-    lib.score_refine_robust_run.argtypes = [C.c_void_p, C.POINTER(ScoreRefineRobustSettings), _f64p, _f64p, _f64p, _f64p,
-                                            _f64p, _f64p, _f64p, _f64p, C.POINTER(ScoreRefineRobustInfo)]
-    lib.score_refine_robust_run.restype = C.c_int
-    lib.score_refine_residuals.argtypes = [C.c_void_p, _f64p, _f64p, C.c_double, C.c_double, C.c_double, _f64p, _f64p, _f64p, _f64p]
-    lib.score_refine_residuals.restype = C.c_int
-    lib._score_refine_robust_bound = True
-    return lib
+    return bind(lib, REFINE_ROBUST)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -161,25 +127,14 @@ def first_mu(seen) -> float:
     return min(initial_mu(r2, c) for n, r2, c, _ in seen if n > 0 and 2.0 * r2 > c * c)
 
 
-class RobustRefineHandle:
+class RobustRefineHandle(RefineHandle):
     """A refinement handle (``score_refine_create``) with the calls of include/score_refine_robust.h (and ``score_refine_run``)
     as they are: points go in and come out in the problem's own form (``_Problem``: packed unknowns; ``_Problem3D``: (R, t, lm))."""
 
-    def __init__(self, prob, lib_path: Optional[str] = None, solver_settings: Optional[dict] = None):
-        from .native import score_graph_struct
+    headers = RefineHandle.headers + (REFINE_ROBUST,)
 
-        self.prob = prob
-        self.lib = _bind(load_library(lib_path))
-        st = ScoreSettings()
-        self.lib.score_default_settings(C.byref(st))
-        for k, v in (solver_settings or {}).items():
-            if not hasattr(st, k):
-                raise ValueError(f"unknown solver setting {k}")
-            setattr(st, k, v)
-        g = score_graph_struct(prob.a)
-        self.h = C.c_void_p()
-        if self.lib.score_refine_create(C.byref(g), C.byref(st), C.byref(self.h)) != 0:
-            raise RuntimeError(f"score_refine_create failed: {self.lib.score_last_error().decode()}")
+    def __init__(self, prob, lib_path: Optional[str] = None, solver_settings: Optional[dict] = None):
+        super().__init__(prob, lib_path, solver_settings)
         self.n_rng, self.n_lc = len(prob.ra), n_loop_closures_of(prob.a)
 
     def default_settings(self) -> ScoreRefineRobustSettings:
@@ -193,12 +148,11 @@ class RobustRefineHandle:
     def robust_run(self, point, rs: ScoreRefineRobustSettings):
         """``score_refine_robust_run``: returns (point, weights, residuals, loop-closure weights, residuals, info dict)."""
         poses_in, lms_in = _point_arrays(self.prob, point)
-        poses_out, lms_out = np.empty_like(poses_in), np.empty((max(1, len(lms_in)), lms_in.shape[1]))
+        poses_out, lms_out = _point_outputs(poses_in, lms_in)
         w, r, wl, rl = self._outputs()
         info = ScoreRefineRobustInfo()
-        p = lambda x: x.ctypes.data_as(_f64p)  # noqa: E731
-        rc = self.lib.score_refine_robust_run(self.h, C.byref(rs), p(poses_in), p(lms_in) if len(lms_in) else None, p(poses_out),
-                                              p(lms_out), p(w), p(r), p(wl), p(rl), C.byref(info))
+        rc = self.lib.score_refine_robust_run(self.h, C.byref(rs), ptr(poses_in), ptr(lms_in), ptr(poses_out), ptr(lms_out), ptr(w),
+                                              ptr(r), ptr(wl), ptr(rl), C.byref(info))
         if rc != 0:
             raise RuntimeError(f"score_refine_robust_run failed: {self.lib.score_last_error().decode()}")
         return (_point_from(self.prob, poses_out, lms_out), w[: self.n_rng], r[: self.n_rng], wl[: self.n_lc], rl[: self.n_lc],
@@ -208,37 +162,11 @@ class RobustRefineHandle:
         """``score_refine_residuals``: (residuals, loop-closure residuals, weights, loop-closure weights) at ``point``."""
         poses_in, lms_in = _point_arrays(self.prob, point)
         w, r, wl, rl = self._outputs()
-        p = lambda x: x.ctypes.data_as(_f64p)  # noqa: E731
-        rc = self.lib.score_refine_residuals(self.h, p(poses_in), p(lms_in) if len(lms_in) else None, float(mu), float(c), float(c_rel),
-                                             p(r), p(rl), p(w), p(wl))
+        rc = self.lib.score_refine_residuals(self.h, ptr(poses_in), ptr(lms_in), float(mu), float(c), float(c_rel), ptr(r), ptr(rl),
+                                             ptr(w), ptr(wl))
         if rc != 0:
             raise RuntimeError(f"score_refine_residuals failed: {self.lib.score_last_error().decode()}")
         return r[: self.n_rng], rl[: self.n_lc], w[: self.n_rng], wl[: self.n_lc]
-
-    def run(self, point, max_iters: int = 50, tol: float = 1e-10):
-        """``score_refine_run`` on this handle: (point, info dict)."""
-        from .solver import ScoreRefineInfo
-
-        poses_in, lms_in = _point_arrays(self.prob, point)
-        poses_out, lms_out = np.empty_like(poses_in), np.empty((max(1, len(lms_in)), lms_in.shape[1]))
-        info = ScoreRefineInfo()
-        p = lambda x: x.ctypes.data_as(_f64p)  # noqa: E731
-        rc = self.lib.score_refine_run(self.h, p(poses_in), p(lms_in) if len(lms_in) else None, int(max_iters), float(tol),
-                                       p(poses_out), p(lms_out), C.byref(info))
-        if rc != 0:
-            raise RuntimeError(f"score_refine_run failed: {self.lib.score_last_error().decode()}")
-        return _point_from(self.prob, poses_out, lms_out), info.as_dict()
-
-    def close(self) -> None:
-        if self.h:
-            self.lib.score_refine_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -410,12 +338,7 @@ def refine_estimate_robust(data, results, inlier_threshold: float = 3.0, robust_
     _check(c, c_rel, max_outer, inner_iters, min_weight, mu_step, engine, linear_solver, f_rng, f_rel)
     families = (FAMILY_RANGES if f_rng else 0) | (FAMILY_LOOP_CLOSURES if f_rel else 0)
     pw, pwl = _prior(range_weights, float(min_weight), f_rng), _prior(loop_closure_weights, float(min_weight), f_rel)
-    if data.dimension == 3:
-        prob = _Problem3D(data, pw, pwl)
-        u = prob.initial_state(results)
-    else:
-        prob = _Problem(data, pw, pwl)
-        u = _initial_point(prob, results)
+    prob, u = _problem_and_point(data, results, pw, pwl)
     _check_precisions(prob, f_rng, f_rel, "refine_estimate_robust: ")
     if engine == "native":
         with RobustRefineHandle(prob, lib_path, solver_settings) as h:

@@ -18,41 +18,19 @@ from typing import Optional
 
 import numpy as np
 
+from .bindings import REFINE_ROBUST_BATCH, ScoreRefineRobustSettings, bind
 from .refine import STOPPED, _as_results, _native_info
 from .refine_batch import RefineBatchHandle, _LockStep, _problem_of, _weights_of
-from .refine_robust import (DONE, FAMILY_LOOP_CLOSURES, FAMILY_RANGES, ScoreRefineRobustInfo, ScoreRefineRobustSettings, _check,
-                            _check_precisions, _prior, _Stage, loop_closure_residuals, range_residuals, refine_estimate_robust)
-from .robust import _robust_info, n_loop_closures_of
-from .solver import _f64p
+from .refine_robust import (DONE, FAMILY_LOOP_CLOSURES, FAMILY_RANGES, _check, _check_precisions, _prior, _Stage,
+                            loop_closure_residuals, range_residuals, refine_estimate_robust)
+from .robust import _robust_info
 
 # the symbols include/score_refine_robust_batch.h declares
-REFINE_ROBUST_BATCH_SYMBOLS = ["score_refine_batch_robust_run", "score_refine_batch_residuals", "score_refine_batch_restore",
-                               "score_refine_batch_robust_rounds"]
+REFINE_ROBUST_BATCH_SYMBOLS = list(REFINE_ROBUST_BATCH)
 
 
 def _bind(lib: C.CDLL) -> C.CDLL:
-    if getattr(lib, "_score_refine_robust_batch_bound", False):
-        return lib
-    for sym in REFINE_ROBUST_BATCH_SYMBOLS:
-        if not hasattr(lib, sym):
-            raise RuntimeError(f"{sym} is missing from the library: rebuild it (the CPU twin of the tests has no robust "
-                               "refinement: engine='python' runs there)")
-    lib.score_refine_batch_robust_run.argtypes = [C.c_void_p, C.POINTER(ScoreRefineRobustSettings), C.c_int32, _f64p, _f64p, _f64p,
-                                                  _f64p, _f64p, _f64p, _f64p, _f64p, C.c_int32, C.POINTER(ScoreRefineRobustInfo)]
-    lib.score_refine_batch_robust_run.restype = C.c_int
-    lib.score_refine_batch_residuals.argtypes = [C.c_void_p] + [_f64p] * 9
-    lib.score_refine_batch_residuals.restype = C.c_int
-    lib.score_refine_batch_restore.argtypes = [C.c_void_p]
-    lib.score_refine_batch_restore.restype = C.c_int
-    lib.score_refine_batch_robust_rounds.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    lib.score_refine_batch_robust_rounds.restype = C.c_int
-    lib._score_refine_robust_batch_bound = True
-    return lib
-
-
-def member_counts(probs):
-    """(ranges, loop closures) of every member."""
-    return [len(p.ra) for p in probs], [n_loop_closures_of(p.a) for p in probs]
+    return bind(lib, REFINE_ROBUST_BATCH)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

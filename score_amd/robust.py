@@ -29,49 +29,17 @@ import numpy as np
 
 from . import compat
 from .assemble import QCQP_RELAXATION, SOCP_RELAXATION, check_valid_relaxation
-from .solver import ScoreInfo, ScoreSettings, _f64p, _i32p, load_library
+from .bindings import ROBUST, ScoreRobustInfo, ScoreRobustSettings, bind, ptr
+from .solver import ScoreInfo, _i32p, load_library, make_settings
 
 # the symbols include/score_robust.h declares (include/score_hip.h's list, solver.ABI_SYMBOLS, stays that header's)
-ROBUST_SYMBOLS = ["score_robust_default_settings", "score_robust_solve", "score_robust_solve_rel"]
+ROBUST_SYMBOLS = list(ROBUST)
 
 BINARY_TOL = 1e-6  # a weight within this of 0 or 1 counts as decided
 
 
-class ScoreRobustSettings(C.Structure):
-    _fields_ = [
-        ("inlier_threshold", C.c_double), ("mu_step", C.c_double), ("min_weight", C.c_double),
-        ("max_outer", C.c_int32), ("qcqp_directions", C.c_int32),
-    ]
-
-
-class ScoreRobustInfo(C.Structure):
-    _fields_ = [
-        ("outer_iterations", C.c_int32), ("converged", C.c_int32), ("outliers", C.c_int32), ("rel_outliers", C.c_int32),
-        ("mu", C.c_double), ("setup_ms", C.c_double), ("solve_ms", C.c_double), ("total_ms", C.c_double),
-    ]
-
-
 def _bind(lib: C.CDLL) -> C.CDLL:
-    from .native import ScoreGraph
-
-    if getattr(lib, "_score_robust_bound", False):
-        return lib
-    for sym in ROBUST_SYMBOLS:
-        if not hasattr(lib, sym):
-            raise RuntimeError(f"{sym} is missing from the library: rebuild it (the oracle's CPU twin has no robust loop: "
-                               "engine='python' runs there)")
-    lib.score_robust_default_settings.argtypes = [C.POINTER(ScoreRobustSettings)]
-    lib.score_robust_default_settings.restype = None
-    lib.score_robust_solve.argtypes = [C.POINTER(ScoreGraph), C.c_int32, C.POINTER(ScoreSettings), C.POINTER(ScoreRobustSettings),
-                                       _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, C.POINTER(C.c_int32), C.POINTER(ScoreInfo),
-                                       C.POINTER(ScoreRobustInfo)]
-    lib.score_robust_solve.restype = C.c_int
-    lib.score_robust_solve_rel.argtypes = [C.POINTER(ScoreGraph), C.c_int32, C.POINTER(ScoreSettings), C.POINTER(ScoreRobustSettings),
-                                           C.c_int32, C.c_double, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p,
-                                           C.POINTER(C.c_int32), C.POINTER(ScoreInfo), C.POINTER(ScoreRobustInfo)]
-    lib.score_robust_solve_rel.restype = C.c_int
-    lib._score_robust_bound = True
-    return lib
+    return bind(lib, ROBUST)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -294,12 +262,7 @@ def _device_group(datas, arrays, relaxation_type, c, max_outer, min_weight, mu_s
     count = len(arrays)
     d = int(arrays[0]["dim"])
     qdirs = relaxation_type == QCQP_RELAXATION
-    st = ScoreSettings()
-    lib.score_default_settings(C.byref(st))
-    for key, v in settings.items():
-        if not hasattr(st, key):
-            raise ValueError(f"unknown solver setting {key}")
-        setattr(st, key, v)
+    st = make_settings(lib, settings)
     rs = ScoreRobustSettings()
     lib.score_robust_default_settings(C.byref(rs))
     rs.inlier_threshold, rs.mu_step, rs.min_weight = float(c), float(mu_step), float(min_weight)
@@ -319,9 +282,7 @@ def _device_group(datas, arrays, relaxation_type, c, max_outer, min_weight, mu_s
     F = np.empty(sum(Np), dtype=np.int32)
     infos, rinfos = (ScoreInfo * count)(), (ScoreRobustInfo * count)()
     rc = lib.score_robust_solve_rel(gs, count, C.byref(st), C.byref(rs), (1 if f_rng else 0) | (2 if f_rel else 0), float(c_rel),
-                                    W.ctypes.data_as(_f64p), Rr.ctypes.data_as(_f64p), Wc.ctypes.data_as(_f64p), Rc.ctypes.data_as(_f64p),
-                                    T.ctypes.data_as(_f64p), B.ctypes.data_as(_f64p), Lm.ctypes.data_as(_f64p), Rg.ctypes.data_as(_f64p),
-                                    F.ctypes.data_as(_i32p), infos, rinfos)
+                                    ptr(W), ptr(Rr), ptr(Wc), ptr(Rc), ptr(T), ptr(B), ptr(Lm), ptr(Rg), ptr(F, _i32p), infos, rinfos)
     if rc != 0:
         raise ValueError(f"score_robust_solve failed: {lib.score_last_error().decode()}")
     backend = lib.score_backend().decode()

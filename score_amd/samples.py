@@ -25,13 +25,14 @@ from typing import Optional
 
 import numpy as np
 
-from .marginals import MAX_BLOCK_WIDTH, MarginalsHandle, _problem_and_point, _select
-from .refine import _Problem3D, so3_exp
-from .solver import _f64p, _i32p
+from .bindings import SAMPLES, ScoreSamplesInfo, bind, ptr, steps_and_converged
+from .marginals import MAX_BLOCK_WIDTH, MarginalsHandle, _problem_and_point, _select, n_columns
+from .refine import _point_arrays, so3_exp, unknown_sizes
+from .solver import _i32p
 from .spectrum import _layout
 
 # the symbols include/score_samples.h declares
-SAMPLES_SYMBOLS = ["score_refine_samples"]
+SAMPLES_SYMBOLS = list(SAMPLES)
 GEN_SAMPLE = 13  # the Philox purpose of the posterior noise (csrc/score_samples.hpp)
 
 _M0, _M1, _W0, _W1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
@@ -68,7 +69,7 @@ def ps_noise(seed, m, s, q):
 def measurement_rows(prob):
     """The residual rows in the library's (m, q) order: (perm, m, q) with row k of that order being row perm[k] of
     ``prob.residuals`` (which lists all translation rows, then all rotation rows, then ranges, then priors)."""
-    d = 3 if isinstance(prob, _Problem3D) else 2
+    d, _ = unknown_sizes(prob)
     n_rel, n_rng, n_pri = len(prob.bi), len(prob.ra), len(prob.pl)
     nr = d + d * d
     e = np.repeat(np.arange(n_rel, dtype=np.int64), nr)
@@ -94,52 +95,24 @@ def noise_block(prob, seed, first_sample, n_samples) -> np.ndarray:
     return ps_noise(seed, m[None, :], s[:, None], q[None, :])
 
 
-class ScoreSamplesInfo(C.Structure):
-    _fields_ = [
-        ("samples", C.c_int32), ("batches", C.c_int32), ("pcg_iters", C.c_int32), ("unconverged", C.c_int32),
-        ("max_residual", C.c_double), ("setup_ms", C.c_double), ("rhs_ms", C.c_double), ("solve_ms", C.c_double),
-    ]
-
-    def as_dict(self) -> dict:
-        return {k: getattr(self, k) for k, _ in self._fields_}
-
-
 def _bind(lib: C.CDLL) -> C.CDLL:
-    if getattr(lib, "_score_samples_bound", False):
-        return lib
-    for sym in SAMPLES_SYMBOLS:
-        if not hasattr(lib, sym):
-            raise RuntimeError(f"{sym} is missing from the library: rebuild it (the CPU twin has no posterior samples: "
-                               "engine='python' runs there)")
-    lib.score_refine_samples.argtypes = [C.c_void_p, _f64p, _f64p, C.c_uint64, C.c_int64, C.c_int32, _i32p, C.c_int32,
-                                         C.c_double, C.c_int32, C.c_int32, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _i32p,
-                                         C.POINTER(ScoreSamplesInfo)]
-    lib.score_refine_samples.restype = C.c_int
-    lib._score_samples_bound = True
-    return lib
+    return bind(lib, SAMPLES)
 
 
 def _moment_sizes(prob):
-    d = 3 if isinstance(prob, _Problem3D) else 2
-    dp = 6 if d == 3 else 3
+    d, dp = unknown_sizes(prob)
     return d, dp, dp * dp * (prob.Np - 1) + d * d * prob.Nl
 
 
 def _n_rows(prob):
-    d = 3 if isinstance(prob, _Problem3D) else 2
+    d, _ = unknown_sizes(prob)
     return (d + d * d) * len(prob.bi) + len(prob.ra) + d * len(prob.pl)
 
 
 class SamplesHandle(MarginalsHandle):
     """A refinement handle kept for several ``score_refine_samples`` calls on one graph."""
 
-    def __init__(self, prob, lib_path: Optional[str] = None, solver_settings: Optional[dict] = None):
-        super().__init__(prob, lib_path, solver_settings)
-        try:
-            _bind(self.lib)
-        except Exception:
-            self.close()
-            raise
+    headers = MarginalsHandle.headers + (SAMPLES,)
 
     def draw(self, point, ids, n_samples, seed=0, first_sample=0, rel_tol=1e-10, max_iters=4000, block_width=MAX_BLOCK_WIDTH,
              with_rhs=False, with_noise=False) -> dict:
@@ -147,18 +120,9 @@ class SamplesHandle(MarginalsHandle):
         lays them out), ``steps`` (n_samples x C), ``rhs`` / ``noise`` (asked for: else None), ``residuals``, ``iterations``,
         ``converged`` and ``info`` (the call's record)."""
         prob = self.prob
-        if isinstance(prob, _Problem3D):
-            R, t, lm = point
-            poses = np.ascontiguousarray(np.concatenate([R.reshape(prob.Np, 9), t], axis=1), dtype=np.float64)
-            lms = np.ascontiguousarray(lm, dtype=np.float64).reshape(-1, 3)
-            per = np.where(np.asarray(ids) < prob.Np, 6, 3)
-        else:
-            th, t, lm = prob.split(point)
-            poses = np.ascontiguousarray(np.column_stack([th, t]), dtype=np.float64)
-            lms = np.ascontiguousarray(lm, dtype=np.float64).reshape(-1, 2)
-            per = np.where(np.asarray(ids) < prob.Np, 3, 2)
+        poses, lms = _point_arrays(prob, point)
         ids = np.ascontiguousarray(ids, dtype=np.int32)
-        ncol = int(per.sum()) if len(ids) else 0
+        ncol = n_columns(prob, ids)
         S = max(int(n_samples), 0)
         moments = np.zeros(_moment_sizes(prob)[2])
         means = np.zeros(prob.n)
@@ -168,19 +132,15 @@ class SamplesHandle(MarginalsHandle):
         res = np.zeros(S)
         its = np.zeros(S, dtype=np.int32)
         info = ScoreSamplesInfo()
-
-        def ptr(a, kind=_f64p):
-            return a.ctypes.data_as(kind) if a is not None and a.size else None
-
         rc = self.lib.score_refine_samples(self.h, ptr(poses), ptr(lms), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
                                            int(first_sample), int(n_samples), ptr(ids, _i32p), len(ids), float(rel_tol),
                                            int(max_iters), int(block_width), ptr(moments), ptr(means), ptr(steps), ptr(rhs),
                                            ptr(noise), ptr(res), ptr(its, _i32p), C.byref(info))
         if rc < 0:
             raise RuntimeError(f"score_refine_samples failed: {self.lib.score_last_error().decode()}")
-        converged = its >= 0  # (a draw that did not converge reports -(steps + 1))
+        iterations, converged = steps_and_converged(its)
         return {"rc": rc, "moments": moments, "means": means, "steps": steps, "rhs": rhs, "noise": noise, "residuals": res,
-                "iterations": np.where(converged, its, -its - 1), "converged": converged, "info": info.as_dict()}
+                "iterations": iterations, "converged": converged, "info": info.as_dict()}
 
 
 def accumulate_moments(prob, delta):

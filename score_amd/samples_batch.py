@@ -19,42 +19,18 @@ from typing import Optional
 
 import numpy as np
 
-from .marginals import MAX_BLOCK_WIDTH, _problem_and_point, _select
-from .marginals_batch import _variables_of
-from .refine import _Problem3D
-from .refine_robust import _point_arrays
+from .bindings import SAMPLES_BATCH, ScoreSamplesBatchInfo, _u64p, bind, ptr, steps_and_converged
+from .marginals import MAX_BLOCK_WIDTH, _problem_and_point, _select, n_columns
+from .marginals_batch import _flat_ids, _variables_of
 from .samples import Samples, _moment_sizes, _n_rows, _python_draws, accumulate_moments
-from .solver import _f64p, _i32p
+from .solver import _i32p
 
 # the symbols include/score_samples_batch.h declares
-SAMPLES_BATCH_SYMBOLS = ["score_refine_batch_samples"]
-_u64p = C.POINTER(C.c_uint64)
-
-
-class ScoreSamplesBatchInfo(C.Structure):
-    _fields_ = [
-        ("members", C.c_int32), ("samples", C.c_int32), ("passes", C.c_int32), ("pcg_iters", C.c_int32), ("unconverged", C.c_int32),
-        ("singular", C.c_int32),
-        ("max_residual", C.c_double), ("setup_ms", C.c_double), ("rhs_ms", C.c_double), ("solve_ms", C.c_double),
-    ]
-
-    def as_dict(self) -> dict:
-        return {k: getattr(self, k) for k, _ in self._fields_}
+SAMPLES_BATCH_SYMBOLS = list(SAMPLES_BATCH)
 
 
 def _bind(lib: C.CDLL) -> C.CDLL:
-    if getattr(lib, "_score_samples_batch_bound", False):
-        return lib
-    for sym in SAMPLES_BATCH_SYMBOLS:
-        if not hasattr(lib, sym):
-            raise RuntimeError(f"{sym} is missing from the library: rebuild it (the CPU twin has no posterior samples: "
-                               "engine='python' runs there)")
-    lib.score_refine_batch_samples.argtypes = [C.c_void_p, _f64p, _f64p, _u64p, C.c_int64, _i32p, _i32p, _i32p, C.c_double, C.c_int32,
-                                               C.c_int32, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _i32p, _i32p,
-                                               C.POINTER(ScoreSamplesBatchInfo)]
-    lib.score_refine_batch_samples.restype = C.c_int
-    lib._score_samples_batch_bound = True
-    return lib
+    return bind(lib, SAMPLES_BATCH)
 
 
 def _per_member(value, count: int, what: str) -> list:
@@ -81,14 +57,9 @@ def batch_draws(handle, points, ids_per_member, n_samples, seeds, first_sample=0
     counts = [int(s) for s in _per_member(n_samples, G, "n_samples")]
     keys = [int(s) & 0xFFFFFFFFFFFFFFFF for s in _per_member(seeds, G, "seeds")]
     lib = _bind(handle.lib)
-    arrays = [_point_arrays(prob, x) for prob, x in zip(probs, points)]
-    poses = np.ascontiguousarray(np.concatenate([a[0].ravel() for a in arrays]))
-    lms = np.ascontiguousarray(np.concatenate([a[1].ravel() for a in arrays]))
-    ids = [np.asarray(v, dtype=np.int32).ravel() for v in ids_per_member]
-    var_ptr = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(v) for v in ids])]), dtype=np.int32)
-    flat = np.ascontiguousarray(np.concatenate(ids + [np.zeros(0, np.int32)]), dtype=np.int32)
-    dim = 3 if isinstance(probs[0], _Problem3D) else 2
-    ncol = [int(np.where(v < prob.Np, 3 * (dim - 1), dim).sum()) for prob, v in zip(probs, ids)]
+    _, poses, lms = handle._flat_points(points)
+    ids, var_ptr, flat = _flat_ids(ids_per_member)
+    ncol = [n_columns(prob, v) for prob, v in zip(probs, ids)]
     on = [max(s, 0) for s in counts]  # (a negative count is the library's error to report)
     n_mom = [_moment_sizes(p)[2] if s else 0 for p, s in zip(probs, on)]
     n_mean = [p.n if s else 0 for p, s in zip(probs, on)]
@@ -102,14 +73,10 @@ def batch_draws(handle, points, ids_per_member, n_samples, seeds, first_sample=0
     n_arr = np.ascontiguousarray(counts, dtype=np.int32)
     seed_arr = np.ascontiguousarray(keys, dtype=np.uint64)
     info = ScoreSamplesBatchInfo()
-
-    def ptr(a, kind=_f64p):
-        return a.ctypes.data_as(kind) if a is not None else None
-
-    rc = lib.score_refine_batch_samples(handle.h, ptr(poses), ptr(lms) if lms.size else None, ptr(seed_arr, _u64p), int(first_sample),
-                                        ptr(n_arr, _i32p), ptr(var_ptr, _i32p), ptr(flat, _i32p) if flat.size else None, float(rel_tol),
-                                        int(max_iters), int(block_width), ptr(moments), ptr(means), ptr(steps), ptr(rhs), ptr(noise),
-                                        ptr(res), ptr(its, _i32p), ptr(det, _i32p), C.byref(info))
+    rc = lib.score_refine_batch_samples(handle.h, ptr(poses), ptr(lms), ptr(seed_arr, _u64p), int(first_sample), ptr(n_arr, _i32p),
+                                        ptr(var_ptr, _i32p), ptr(flat, _i32p), float(rel_tol), int(max_iters), int(block_width),
+                                        ptr(moments), ptr(means), ptr(steps), ptr(rhs), ptr(noise), ptr(res), ptr(its, _i32p),
+                                        ptr(det, _i32p), C.byref(info))
     if rc < 0:
         raise RuntimeError(f"score_refine_batch_samples failed: {lib.score_last_error().decode()}")
     rec = info.as_dict()
@@ -125,14 +92,13 @@ def batch_draws(handle, points, ids_per_member, n_samples, seeds, first_sample=0
 
     for g, prob in enumerate(probs):
         S, c, rows = on[g], ncol[g], _n_rows(prob)
-        it = its[at["draw"] : at["draw"] + S].copy()
-        converged = it >= 0  # (a draw that did not converge reports -(steps + 1))
+        iterations, converged = steps_and_converged(its[at["draw"] : at["draw"] + S])
         member = {
             "moments": cut(moments, "mom", n_mom[g], (n_mom[g],)) if S else np.zeros(_moment_sizes(prob)[2]),
             "means": cut(means, "mean", n_mean[g], (n_mean[g],)) if S else np.zeros(prob.n),
             "steps": cut(steps, "steps", S * c, (S, c)), "rhs": cut(rhs, "rhs", S * prob.n, (S, prob.n)),
             "noise": cut(noise, "noise", S * rows, (S, rows)), "residuals": res[at["draw"] : at["draw"] + S].copy(),
-            "iterations": np.where(converged, it, -it - 1), "converged": converged, "determined": int(det[g]),
+            "iterations": iterations, "converged": converged, "determined": int(det[g]),
             "rc": 0 if np.all(converged) else 1,
             "info": dict(rec, samples=S, batches=-(-S // int(block_width))),
         }

@@ -50,18 +50,22 @@ class ScoreSettings(C.Structure):
     ]
 
 
-class ScoreRefineInfo(C.Structure):
+class InfoRecord(C.Structure):
+    """An info record the library fills in: ``as_dict`` is its fields by name."""
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class ScoreRefineInfo(InfoRecord):
     _fields_ = [
         ("cost_initial", C.c_double), ("cost_final", C.c_double), ("grad_inf", C.c_double),
         ("iterations", C.c_int32), ("linear_solves", C.c_int32), ("pcg_iters", C.c_int32),
         ("setup_ms", C.c_double), ("solve_ms", C.c_double),
     ]
 
-    def as_dict(self) -> dict:
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class ScoreInfo(C.Structure):
+class ScoreInfo(InfoRecord):
     _fields_ = [
         ("status", C.c_int32), ("iters", C.c_int32), ("cg_iters", C.c_int32), ("rho_updates", C.c_int32),
         ("rho", C.c_double), ("pobj", C.c_double), ("dobj", C.c_double),
@@ -69,9 +73,6 @@ class ScoreInfo(C.Structure):
         ("setup_ms", C.c_double), ("solve_ms", C.c_double), ("kkt_bytes", C.c_double),
         ("newton_iters", C.c_int32), ("newton_cg_iters", C.c_int32),
     ]
-
-    def as_dict(self) -> dict:
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 STATUS_NAMES = {0: "unsolved", 1: "solved", 2: "max_iters", 3: "numerical"}
@@ -135,6 +136,17 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     return lib
 
 
+def make_settings(lib: C.CDLL, overrides: Optional[dict] = None) -> ScoreSettings:
+    """The library's default settings (``score_default_settings``) with ``overrides`` (field -> value) written over them."""
+    st = ScoreSettings()
+    lib.score_default_settings(C.byref(st))
+    for k, v in (overrides or {}).items():
+        if not hasattr(st, k):
+            raise ValueError(f"unknown solver setting {k}")
+        setattr(st, k, v)
+    return st
+
+
 def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
 
@@ -188,13 +200,7 @@ class ConicSolver:
         self.lib = load_library(lib_path)
         self.lib.score_create_from_graphs.argtypes = [C.POINTER(ScoreGraph), C.c_int32, C.POINTER(ScoreSettings), C.POINTER(C.c_void_p)]
         self.count = len(arrays)
-        st = ScoreSettings()
-        self.lib.score_default_settings(C.byref(st))
-        for k, v in (settings or {}).items():
-            if not hasattr(st, k):
-                raise ValueError(f"unknown solver setting {k}")
-            setattr(st, k, v)
-        self.settings = st
+        self.settings = st = make_settings(self.lib, settings)
         # worlds of ONE generated batch (score_amd.generate), in a row: the library builds the handle from the arrays the
         # generator left on the device (score_create_from_generated) -- the same program, nothing of a world uploaded again
         # (and no ``struct score_graph`` made here: 0.1 ms a graph under the interpreter lock)
@@ -242,13 +248,7 @@ class ConicSolver:
         self.count = len(qps)
         self.ns = [int(qp.n) for qp in qps]
         self.ms = [int(qp.m) for qp in qps]
-        st = ScoreSettings()
-        self.lib.score_default_settings(C.byref(st))
-        for k, v in (settings or {}).items():
-            if not hasattr(st, k):
-                raise ValueError(f"unknown solver setting {k}")
-            setattr(st, k, v)
-        self.settings = st
+        self.settings = st = make_settings(self.lib, settings)
         self._keep = []  # borrowed arrays must outlive score_create
         probs = (ScoreProblem * self.count)()
         for i, qp in enumerate(qps):
@@ -433,13 +433,7 @@ class LinearSolver:
         self.n = int(P.shape[0])
         self.nnz = int(P.nnz)
         self.indptr, self.indices = _i32(P.indptr), _i32(P.indices)
-        st = ScoreSettings()
-        self.lib.score_default_settings(C.byref(st))
-        for k, v in (settings or {}).items():
-            if not hasattr(st, k):
-                raise ValueError(f"unknown solver setting {k}")
-            setattr(st, k, v)
-        self.settings = st
+        self.settings = st = make_settings(self.lib, settings)
         cp, nc = _i32(chain_ptr), _i32(node_first_col)
         zero_i, zero_d = np.zeros(1, np.int32), np.zeros(1)
         p = ScoreProblem()

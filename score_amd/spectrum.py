@@ -20,46 +20,24 @@ from typing import Optional
 
 import numpy as np
 
+from .bindings import SPECTRUM, ScoreSpectrumInfo, bind, ptr
 from .marginals import MarginalsHandle, _problem_and_point, _select, dense_information
-from .refine import _Problem3D
-from .solver import _f64p
+from .refine import _point_arrays, unknown_sizes
 
 # the symbols include/score_spectrum.h declares
-SPECTRUM_SYMBOLS = ["score_refine_spectrum"]
+SPECTRUM_SYMBOLS = list(SPECTRUM)
 MAX_MODES = 16
 MIN_DEVICE_UNKNOWNS = 48
 
 
-class ScoreSpectrumInfo(C.Structure):
-    _fields_ = [
-        ("modes", C.c_int32), ("block", C.c_int32), ("iterations", C.c_int32), ("unconverged", C.c_int32),
-        ("h_max", C.c_double), ("shift", C.c_double), ("max_residual", C.c_double),
-        ("setup_ms", C.c_double), ("solve_ms", C.c_double),
-    ]
-
-    def as_dict(self) -> dict:
-        return {k: getattr(self, k) for k, _ in self._fields_}
-
-
 def _bind(lib: C.CDLL) -> C.CDLL:
-    if getattr(lib, "_score_spectrum_bound", False):
-        return lib
-    for sym in SPECTRUM_SYMBOLS:
-        if not hasattr(lib, sym):
-            raise RuntimeError(f"{sym} is missing from the library: rebuild it (the oracle's CPU twin has no eigensolver: "
-                               "engine='python' runs there)")
-    lib.score_refine_spectrum.argtypes = [C.c_void_p, _f64p, _f64p, C.c_int32, C.c_double, C.c_int32, C.c_double,
-                                          _f64p, _f64p, _f64p, C.POINTER(ScoreSpectrumInfo)]
-    lib.score_refine_spectrum.restype = C.c_int
-    lib._score_spectrum_bound = True
-    return lib
+    return bind(lib, SPECTRUM)
 
 
 def _layout(prob):
     """Every variable with unknowns, in the order of the unknowns: (names, first unknown of each, size of each)."""
     poses, lms = list(prob.a["pose_names"]), list(prob.a["landmark_names"])
-    d = 3 if isinstance(prob, _Problem3D) else 2
-    dp = 6 if d == 3 else 3
+    d, dp = unknown_sizes(prob)
     names = [str(nm) for nm in poses[1:]] + [str(nm) for nm in lms]
     first = [dp * p for p in range(prob.Np - 1)] + [dp * (prob.Np - 1) + d * l for l in range(len(lms))]
     size = [dp] * (prob.Np - 1) + [d] * len(lms)
@@ -104,34 +82,19 @@ class Modes:
 class SpectrumHandle(MarginalsHandle):
     """A refinement handle kept for several ``score_refine_spectrum`` calls on one graph."""
 
-    def __init__(self, prob, lib_path: Optional[str] = None, solver_settings: Optional[dict] = None):
-        super().__init__(prob, lib_path, solver_settings)
-        try:
-            _bind(self.lib)
-        except Exception:
-            self.close()
-            raise
+    headers = MarginalsHandle.headers + (SPECTRUM,)
 
     def spectrum(self, point, k, rel_tol=1e-9, max_iters=200, shift=1e-8):
         """``score_refine_spectrum`` as it is: (return code, values (k), vectors (k x n), residuals (k), info record)."""
         prob = self.prob
-        if isinstance(prob, _Problem3D):
-            R, t, lm = point
-            poses = np.ascontiguousarray(np.concatenate([R.reshape(prob.Np, 9), t], axis=1), dtype=np.float64)
-            lms = np.ascontiguousarray(lm, dtype=np.float64).reshape(-1, 3)
-        else:
-            th, t, lm = prob.split(point)
-            poses = np.ascontiguousarray(np.column_stack([th, t]), dtype=np.float64)
-            lms = np.ascontiguousarray(lm, dtype=np.float64).reshape(-1, 2)
+        poses, lms = _point_arrays(prob, point)
         kk = max(0, min(int(k), MAX_MODES))
         values = np.full(kk, np.nan)
         vectors = np.full((kk, prob.n), np.nan)
         res = np.full(kk, np.nan)
         info = ScoreSpectrumInfo()
-        rc = self.lib.score_refine_spectrum(self.h, poses.ctypes.data_as(_f64p), lms.ctypes.data_as(_f64p) if len(lms) else None,
-                                            int(k), float(rel_tol), int(max_iters), float(shift),
-                                            values.ctypes.data_as(_f64p), vectors.ctypes.data_as(_f64p), res.ctypes.data_as(_f64p),
-                                            C.byref(info))
+        rc = self.lib.score_refine_spectrum(self.h, ptr(poses), ptr(lms), int(k), float(rel_tol), int(max_iters), float(shift),
+                                            ptr(values), ptr(vectors), ptr(res), C.byref(info))
         if rc < 0:
             raise RuntimeError(f"score_refine_spectrum failed: {self.lib.score_last_error().decode()}")
         return rc, values, vectors, res, info.as_dict()

@@ -19,42 +19,20 @@ from typing import Optional
 
 import numpy as np
 
+from .bindings import SPECTRUM_BATCH, ScoreSpectrumBatchInfo, bind, ptr, steps_and_converged
 from .marginals import _problem_and_point, _select
-from .refine_robust import _point_arrays
-from .solver import _f64p, _i32p
+from .solver import _i32p, load_library
 from .spectrum import MAX_MODES, MIN_DEVICE_UNKNOWNS, Modes, _layout, _python_spectrum
 
 # the symbols include/score_spectrum_batch.h declares
-SPECTRUM_BATCH_SYMBOLS = ["score_refine_batch_spectrum", "score_spectrum_ritz"]
+SPECTRUM_BATCH_SYMBOLS = list(SPECTRUM_BATCH)
 BLOCK = 16            # vectors iterated per member
 BASIS = 3 * BLOCK     # columns of [X | W | P]: the order of a pencil
 RITZ_OK, RITZ_NO_P, RITZ_BREAKDOWN = 0, 1, 2
 
 
-class ScoreSpectrumBatchInfo(C.Structure):
-    _fields_ = [
-        ("members", C.c_int32), ("modes", C.c_int32), ("block", C.c_int32), ("rounds", C.c_int32), ("unconverged", C.c_int32),
-        ("max_residual", C.c_double), ("setup_ms", C.c_double), ("solve_ms", C.c_double),
-    ]
-
-    def as_dict(self) -> dict:
-        return {k: getattr(self, k) for k, _ in self._fields_}
-
-
 def _bind(lib: C.CDLL) -> C.CDLL:
-    if getattr(lib, "_score_spectrum_batch_bound", False):
-        return lib
-    for sym in SPECTRUM_BATCH_SYMBOLS:
-        if not hasattr(lib, sym):
-            raise RuntimeError(f"{sym} is missing from the library: rebuild it (the oracle's CPU twin has no eigensolver: "
-                               "engine='python' runs there)")
-    lib.score_refine_batch_spectrum.argtypes = [C.c_void_p, _f64p, _f64p, C.c_int32, C.c_double, C.c_int32, C.c_double,
-                                                _f64p, _f64p, _f64p, _i32p, _f64p, C.POINTER(ScoreSpectrumBatchInfo)]
-    lib.score_refine_batch_spectrum.restype = C.c_int
-    lib.score_spectrum_ritz.argtypes = [C.c_int32, _f64p, _f64p, _f64p, _f64p, _i32p, _i32p]
-    lib.score_spectrum_ritz.restype = C.c_int
-    lib._score_spectrum_batch_bound = True
-    return lib
+    return bind(lib, SPECTRUM_BATCH)
 
 
 def batch_spectrum(handle, points, k, rel_tol=1e-9, max_iters=200, shift=1e-8):
@@ -62,12 +40,8 @@ def batch_spectrum(handle, points, k, rel_tol=1e-9, max_iters=200, shift=1e-8):
     (return code, per member ``(values (k), vectors (k x n_g), residuals (k), iterations, converged, h_max)``, the call's info
     record)."""
     probs = handle.probs
-    if len(points) != len(probs):
-        raise ValueError("one point per member expected")
+    _, poses, lms = handle._flat_points(points)
     lib = _bind(handle.lib)
-    arrays = [_point_arrays(prob, x) for prob, x in zip(probs, points)]
-    poses = np.ascontiguousarray(np.concatenate([a[0].ravel() for a in arrays]))
-    lms = np.ascontiguousarray(np.concatenate([a[1].ravel() for a in arrays]))
     G, kk = len(probs), max(0, min(int(k), MAX_MODES))
     sizes = [int(prob.n) for prob in probs]
     values = np.full(max(1, G * kk), np.nan)
@@ -76,18 +50,15 @@ def batch_spectrum(handle, points, k, rel_tol=1e-9, max_iters=200, shift=1e-8):
     its = np.zeros(G, dtype=np.int32)
     h_max = np.full(G, np.nan)
     info = ScoreSpectrumBatchInfo()
-    rc = lib.score_refine_batch_spectrum(handle.h, poses.ctypes.data_as(_f64p), lms.ctypes.data_as(_f64p) if lms.size else None,
-                                         int(k), float(rel_tol), int(max_iters), float(shift), values.ctypes.data_as(_f64p),
-                                         vectors.ctypes.data_as(_f64p), res.ctypes.data_as(_f64p), its.ctypes.data_as(_i32p),
-                                         h_max.ctypes.data_as(_f64p), C.byref(info))
+    rc = lib.score_refine_batch_spectrum(handle.h, ptr(poses), ptr(lms), int(k), float(rel_tol), int(max_iters), float(shift),
+                                         ptr(values), ptr(vectors), ptr(res), ptr(its, _i32p), ptr(h_max), C.byref(info))
     if rc < 0:
         raise RuntimeError(f"score_refine_batch_spectrum failed: {lib.score_last_error().decode()}")
+    iterations, converged = steps_and_converged(its)
     out, v0 = [], 0
     for g, n in enumerate(sizes):
-        it = int(its[g])
-        converged = it >= 0  # (a member that did not converge reports -(iterations + 1))
         out.append((values[g * kk:(g + 1) * kk].copy(), vectors[v0:v0 + kk * n].reshape(kk, n).copy(), res[g * kk:(g + 1) * kk].copy(),
-                    it if converged else -it - 1, converged, float(h_max[g])))
+                    int(iterations[g]), bool(converged[g]), float(h_max[g])))
         v0 += kk * n
     return rc, out, info.as_dict()
 
@@ -96,8 +67,6 @@ def device_ritz(GA, GB, lib_path: Optional[str] = None):
     """``score_spectrum_ritz``: the device Rayleigh-Ritz step alone on ``count`` pencils (GA, GB: count x 48 x 48).  Returns
     (theta (count x 16), coef (count x 48 x 16), status (count), kept (count)); theta and coef of a pencil that broke down
     are NaN."""
-    from .solver import load_library
-
     lib = _bind(load_library(lib_path))
     GA = np.ascontiguousarray(GA, dtype=np.float64)
     GB = np.ascontiguousarray(GB, dtype=np.float64)
@@ -108,8 +77,7 @@ def device_ritz(GA, GB, lib_path: Optional[str] = None):
     coef = np.full((count, BASIS, BLOCK), np.nan)
     status = np.full(count, -1, dtype=np.int32)
     kept = np.full(count, -1, dtype=np.int32)
-    rc = lib.score_spectrum_ritz(count, GA.ctypes.data_as(_f64p), GB.ctypes.data_as(_f64p), theta.ctypes.data_as(_f64p),
-                                 coef.ctypes.data_as(_f64p), status.ctypes.data_as(_i32p), kept.ctypes.data_as(_i32p))
+    rc = lib.score_spectrum_ritz(count, ptr(GA), ptr(GB), ptr(theta), ptr(coef), ptr(status, _i32p), ptr(kept, _i32p))
     if rc != 0:
         raise RuntimeError(f"score_spectrum_ritz failed: {lib.score_last_error().decode()}")
     return theta, coef, status, kept
