@@ -476,6 +476,16 @@ struct CpuBackend {
         else if (nm == "D") { src = h.D.data(); sz = h.n_tot; }
         else if (nm == "E") { src = h.E.data(); sz = h.m_tot; }
         else if (nm == "Kval") { src = h.K.val.data(); sz = (int64_t)h.K.val.size(); }
+        else if (nm == "rho") { src = h.rho.data(); sz = h.count; }  // the host values the loops read
+        else if (nm == "graph_launches") {  // (no launch graphs here)
+            if (out && len > 0) out[0] = 0.0;
+            return 1;
+        }
+        else if (nm == "Kptr" || nm == "Kcol") {  // pattern of the stored K (a replicated problem: replica 0 + tail rows)
+            const std::vector<int32_t>& v = nm == "Kptr" ? h.K.ptr : h.K.col;
+            if (out) for (int64_t i = 0; i < (int64_t)v.size() && i < len; ++i) out[i] = (double)v[(size_t)i];
+            return (int64_t)v.size();
+        }
         else if (nm == "rep") {
             const double v[3] = {(double)h.rep, (double)h.K.col.size(), (double)h.G1.col.size()};
             if (out && len > 0) std::memcpy(out, v, sizeof(double) * (size_t)std::min<int64_t>(len, 3));

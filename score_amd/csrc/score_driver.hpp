@@ -249,6 +249,7 @@ struct Solver {
                 double nr = std::min(1e6, std::max(1e-6, H.rho[p] * ratio));
                 if (nr > st.adaptive_rho_tol * H.rho[p] || nr < H.rho[p] / st.adaptive_rho_tol) {
                     H.rho[p] = nr;
+                    I.rho = nr;  // (the penalty the handle holds from here on, also when no later check restates it)
                     refresh_rho(H, p);
                     I.rho_updates++;
                     any_rho = true;

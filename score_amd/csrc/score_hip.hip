@@ -926,6 +926,7 @@ struct HipBackend {
     hipStream_t stream = nullptr;
     hipGraphExec_t graph_exec = nullptr;
     int graph_iters = 0;
+    int64_t graph_launches = 0;  // hipGraphLaunch calls of run() (score_debug_get "graph_launches")
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     DevArena arena;  // declared before every buffer: destroyed after them
 
@@ -3044,6 +3045,7 @@ struct HipBackend {
         if (st.use_graph && iters >= graph_min_iters()) {
             if (!graph_exec || graph_iters != iters) build_graph(iters);
             HIP_CHECK(hipGraphLaunch(graph_exec, stream));
+            ++graph_launches;
         } else {
             for (int i = 0; i < iters; ++i) enqueue_iteration(i == iters - 1, i == 0);
             HIP_CHECK(hipGetLastError());

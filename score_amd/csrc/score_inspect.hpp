@@ -263,6 +263,10 @@ int64_t chain_map(HipBackend& be, bool by_chain, double* out, int64_t len) {
 }
 int64_t get_chain_of_col(HipBackend& be, double* out, int64_t len) { return be.Q.available ? chain_map(be, false, out, len) : -1; }
 int64_t get_chain_id_of_col(HipBackend& be, double* out, int64_t len) { return chain_map(be, true, out, len); }
+int64_t get_graph_launches(HipBackend& be, double* out, int64_t len) {  // captured ADMM blocks replayed on this handle (HipBackend::run)
+    const double v = (double)be.graph_launches;
+    return copy_out_min(&v, 1, out, len);
+}
 
 int64_t get_vec(HipBackend& be, const char* name, double* out, int64_t len) {
     const HostSystem& h = *be.H;
@@ -279,6 +283,7 @@ int64_t get_vec(HipBackend& be, const char* name, double* out, int64_t len) {
         {"r", R::DevF64, be.r.d, n}, {"z", R::DevF64, be.z.d, n},
         {"p", R::DevF64, be.dbg_p ? be.dbg_p : ((be.cg_iters % 2 == 1) ? be.p.d : be.p2.d), n},  // last PCG direction
         {"w", R::DevF64, be.w.d, n}, {"kx", R::DevF64, be.kx.d, n},
+        {"rho", R::DevF64, be.rho.d, h.count},  // the per-problem penalties as the kernels read them
         {"D", ds ? R::DevF64 : R::HostF64, ds ? (const void*)be.Dd.d : h.D.data(), n},
         {"E", ds ? R::DevF64 : R::HostF64, ds ? (const void*)be.Ed.d : h.E.data(), m},
         {"K0", R::DevF64, be.K0d.d, nk}, {"K1", R::DevF64, be.K1d.d, nk}, {"Kval", R::DevF64, be.K.val.d, nk},
@@ -310,6 +315,7 @@ int64_t get_vec(HipBackend& be, const char* name, double* out, int64_t len) {
         {"polish_build_check", get_polish_build_check}, {"polish_assemble_at_x", get_polish_assemble_at_x},
         {"polish_prec_of_negg", get_polish_prec_of_negg},
         {"chain_of_col", get_chain_of_col}, {"chain_id_of_col", get_chain_id_of_col}, {"matrix_source", get_matrix_source},
+        {"graph_launches", get_graph_launches},
     };
     for (const Computed& c : computed)
         if (nm == c.name) return c.fn(be, out, len);

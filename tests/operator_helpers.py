@@ -13,7 +13,13 @@ a figure is accumulated in np.longdouble.
 The float-storage model (model_solve) is the reference for the float-factor figures: every chain's banded Cholesky factor of
 T (scipy.linalg.cholesky_banded, a sequential elimination from the first node to the last) rounded to float32, T32 = C32'C32
 rebuilt, the link blocks added in double, and the sparse system solved by SuperLU.  It is not a restatement of the kernels:
-they eliminate in a nested-dissection order, join segments through a second level and solve a capacitance system."""
+they eliminate in a nested-dissection order, join segments through a second level and solve a capacitance system.
+
+The second half of the file runs the loop as the benchmark drives it (penalty_update_run, changing_cg_run,
+replay_and_single_steps: 16-iteration blocks replayed from a captured graph, a penalty update at every check, a PCG count that
+changes between blocks) and models one iteration in np.longdouble (iteration_model: the right-hand side, the relaxation, the
+cone projections and the dual update, with forward-error bounds counted operation by operation).  K and T are built at each
+problem's own penalty, read back from the handle (score_debug_get "rho")."""
 import functools
 
 import numpy as np
@@ -269,43 +275,58 @@ def jacobi_ok(M, on, z, rhs):
 class ProblemView:
     """One problem of a handle: its slice of the handle's vectors and its references."""
 
-    def __init__(self, fg, mdl, xoff, roff, D, E, link_pairs):
+    def __init__(self, fg, mdl, xoff, roff, D, E, link_pairs, rho=RHO, sigma=SIGMA):
         qp = mdl.qp
         self.fg, self.mdl, self.qp, self.x0, self.x1 = fg, mdl, qp, xoff, xoff + qp.n
-        self.K = reference_K(qp, D[xoff : xoff + qp.n], E[roff : roff + qp.m])
-        self.chain, self.node = chain_nodes_of_problem(qp)
+        self.r0, self.r1, self.rho, self.sigma = roff, roff + qp.m, float(rho), float(sigma)
+        self.D, self.E = np.asarray(D[xoff : xoff + qp.n]), np.asarray(E[roff : roff + qp.m])
+        self.K = reference_K(qp, self.D, self.E, rho=self.rho, sigma=self.sigma)
         self.pairs = [(a - xoff, b - xoff) for a, b in link_pairs if xoff <= a < xoff + qp.n]
-        self.expected_pairs = loop_closure_pairs(fg, mdl)
+        if fg is None:  # a general conic program: no chains, no graph
+            self.chain = self.node = -np.ones(qp.n, dtype=np.int64)
+            self.expected_pairs = []
+        else:
+            self.chain, self.node = chain_nodes_of_problem(qp)
+            self.expected_pairs = loop_closure_pairs(fg, mdl)
         self.T, self.on = preconditioned_matrix(self.K, self.chain, self.node, int(qp.block_size), self.expected_pairs)
 
     def cut(self, v):
         return np.asarray(v)[self.x0 : self.x1]
 
+    def cut_rows(self, v):
+        return np.asarray(v)[self.r0 : self.r1]
 
-def problem_views(sol, models):
-    """The views of every problem of a handle created from `models` (list of (graph, model))."""
+
+def problem_views(sol, models, rho=None):
+    """The views of every problem of a handle created from `models` (list of (graph, model)); `rho`: the penalty of every
+    problem (default: RHO for all of them)."""
     D, E = sol.debug_get("D"), sol.debug_get("E")
     lp = sol.debug_get("link_pairs").astype(np.int64).reshape(-1, 2)
     pairs = sorted((int(min(a, b)), int(max(a, b))) for a, b in lp)
     out, xo, ro = [], 0, 0
-    for fg, mdl in models:
-        out.append(ProblemView(fg, mdl, xo, ro, D, E, pairs))
+    for k, (fg, mdl) in enumerate(models):
+        out.append(ProblemView(fg, mdl, xo, ro, D, E, pairs, rho=RHO if rho is None else float(rho[k])))
         xo += mdl.qp.n
         ro += mdl.qp.m
     return out
 
 
-def admm_snapshots(models, settings, lib_path):
-    """reset(), then steps(5) twice with the fixed settings: both end in a measured iteration (the last launch applies the
-    preconditioner to the final residual, so z = M^-1 r for the r read back).  Returns (views, [vectors after 5, after 10])."""
-    sol = ConicSolver([m.qp for _, m in models], dict(ADMM_SETTINGS, **settings), lib_path=lib_path)
+def admm_snapshots(models, settings, lib_path, counters=None):
+    """reset(), then steps(check_interval) twice with the fixed settings (5 iterations each unless `settings` says otherwise;
+    16 or more are replayed from a captured graph when use_graph = 1): both end in a measured iteration (the last launch
+    applies the preconditioner to the final residual, so z = M^-1 r for the r read back).  Returns (views, [vectors after
+    the first block, after the second]); `counters`, when given, receives the handle's "graph_launches"."""
+    st = dict(ADMM_SETTINGS, **settings)
+    sol = ConicSolver([m.qp for _, m in models], st, lib_path=lib_path)
     try:
         views = problem_views(sol, models)
         sol.reset()
         snaps = []
         for _ in range(2):
-            sol.steps(5)
+            sol.steps(st["check_interval"])
             snaps.append({v: sol.debug_get(v) for v in ADMM_VECS})
+        if counters is not None:
+            counters["graph_launches"] = int(sol.debug_get("graph_launches")[0])
     finally:
         sol.close()
     return views, snaps
@@ -346,3 +367,528 @@ def newton_figures(fg, model, H, g, z, pairs, float_factors):
     T, on = preconditioned_matrix(H, chain, node, int(qp.block_size), expected)
     bound, eta_m = eta_bound(T, qp, on, -g, float_factors)
     return dict(i4=eta_figure(T, on, z, -g), i4_bound=bound, i4_model=eta_m, jacobi=jacobi_ok(H, on, z, -g), pairs_ok=pairs == expected)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the loop as the benchmark drives it: penalty updates, a changing PCG count, replayed graphs
+# ---------------------------------------------------------------------------------------------------------------------
+BLOCK = 16  # iterations per block: the shortest one HipBackend::run replays from a captured graph
+RHO_SETTINGS = dict(ADMM_SETTINGS, adaptive_rho=1, adaptive_rho_interval=BLOCK, adaptive_rho_tol=1.0, check_interval=BLOCK, use_graph=1,
+                    max_iters=3 * BLOCK, eps_abs=1e-30, eps_rel=1e-30, polish=0, adaptive_cg=0, cg_iters=2)
+CG_SETTINGS = dict(RHO_SETTINGS, adaptive_rho=0, adaptive_cg=1, cg_iters=2, max_cg_iters=6, cg_target=1e-12)
+ALPHA = 1.8  # score_default_settings
+
+
+def scaled_data(view):
+    """As = E A D, bs = E b, qs = D q of a problem in np.longdouble (entries of As on the pattern of A, duplicates summed).
+    Returns (A pattern as CSR with double values, the np.longdouble values of As in that order, bs, qs)."""
+    qp = view.qp
+    A = sp.csr_matrix(qp.A, copy=True)
+    A.sum_duplicates()
+    A.sort_indices()
+    rows = np.repeat(np.arange(A.shape[0]), np.diff(A.indptr))
+    vals = view.E.astype(LD)[rows] * A.data.astype(LD) * view.D.astype(LD)[A.indices]
+    return A, vals, view.E.astype(LD) * np.asarray(qp.b).astype(LD), view.D.astype(LD) * np.asarray(qp.q).astype(LD)
+
+
+def _ld_rows(A, vals, v, absolute=False):
+    """(A with np.longdouble values `vals`) v, row by row in np.longdouble."""
+    vec = np.asarray(v).astype(LD)
+    data = vals
+    if absolute:
+        data, vec = np.abs(data), np.abs(vec)
+    prod = data * vec[A.indices]
+    out = np.zeros(A.shape[0], dtype=LD)
+    full = np.diff(A.indptr) > 0
+    if prod.size:
+        out[full] = np.add.reduceat(prod, A.indptr[:-1][full])
+    return out
+
+
+def _ld_cols(A, vals, v, absolute=False):
+    """(A with np.longdouble values `vals`)' v in np.longdouble."""
+    vec = np.asarray(v).astype(LD)
+    data = vals
+    if absolute:
+        data, vec = np.abs(data), np.abs(vec)
+    rows = np.repeat(np.arange(A.shape[0]), np.diff(A.indptr))
+    order = np.argsort(A.indices, kind="stable")
+    prod = (data * vec[rows])[order]
+    cols = A.indices[order]
+    out = np.zeros(A.shape[1], dtype=LD)
+    if prod.size:
+        first = np.nonzero(np.r_[True, cols[1:] != cols[:-1]])[0]
+        out[cols[first]] = np.add.reduceat(prod, first)
+    return out
+
+
+def _sum_by_key(keys, *vals):
+    """Entries with equal keys added up (np.longdouble); returns (sorted unique keys, sums ..., counts)."""
+    order = np.argsort(keys, kind="stable")
+    keys = keys[order]
+    first = np.nonzero(np.r_[True, keys[1:] != keys[:-1]])[0] if keys.size else np.zeros(0, dtype=np.int64)
+    sums = [np.add.reduceat(v[order], first) if keys.size else np.zeros(0, dtype=LD) for v in vals]
+    counts = np.diff(np.r_[first, keys.size])
+    return (keys[first], *sums, counts)
+
+
+def _lookup(keys, vals, query):
+    pos = np.minimum(np.searchsorted(keys, query), max(keys.size - 1, 0))
+    hit = (keys[pos] == query) if keys.size else np.zeros(query.shape, dtype=bool)
+    return np.where(hit, vals[pos] if keys.size else 0, 0).astype(vals.dtype), hit
+
+
+def reference_K_parts(view):
+    """K0 = D P D + sigma I and K1 = As'As of a problem, entry by entry in np.longdouble from the problem data and D, E:
+    (keys i * n + j, K0), (keys, K1, sum of |terms| of K1, number of terms of K1)."""
+    qp, n = view.qp, view.qp.n
+    P = sp.coo_matrix(qp.P)
+    Dl = view.D.astype(LD)
+    k0_keys = np.r_[P.row.astype(np.int64) * n + P.col, np.arange(n, dtype=np.int64) * (n + 1)]
+    k0_vals = np.r_[Dl[P.row] * P.data.astype(LD) * Dl[P.col], np.full(n, LD(view.sigma))]
+    k0k, k0v, _ = _sum_by_key(k0_keys, k0_vals)
+    A, vals, _, _ = scaled_data(view)
+    lens = np.diff(A.indptr)
+    keys, terms = [], []
+    for r in np.unique(lens[lens > 0]):
+        rows = np.nonzero(lens == r)[0]
+        at = A.indptr[rows][:, None] + np.arange(r)[None, :]
+        idx, val = A.indices[at].astype(np.int64), vals[at]
+        keys.append((idx[:, :, None] * n + idx[:, None, :]).ravel())
+        terms.append((val[:, :, None] * val[:, None, :]).ravel())
+    keys = np.concatenate(keys) if keys else np.zeros(0, dtype=np.int64)
+    terms = np.concatenate(terms) if terms else np.zeros(0, dtype=LD)
+    k1k, k1v, k1a, k1c = _sum_by_key(keys, terms, np.abs(terms))
+    return (k0k, k0v), (k1k, k1v, k1a, k1c)
+
+
+def stored_rows(view, rep):
+    """The rows of a problem the stored K holds: all of them, or -- a problem run with `rep` replicas -- replica 0's and
+    the tail's."""
+    n, nr = view.qp.n, int(getattr(view.qp, "rep_n", 0))
+    local = np.arange(n)
+    return np.ones(n, dtype=bool) if rep <= 1 else ((local < nr) | (local >= rep * nr))
+
+
+def kval_figures(view, rho, Kptr, Kcol, Kval, rep):
+    """Step 2a: the stored values of K = K0 + rho K1 of one problem against K0, K1 from the problem data, entry by entry on
+    the CSR pattern of the handle (score_debug_get "Kptr" / "Kcol": a replicated K holds replica 0's rows and the tail's, with
+    the columns of the full matrix).  Where the product streams a band view instead (case F), the copy k_band_pack makes of
+    these values is not read here: it is held through the fresh kx = K xt of the same step and through I1.
+
+    k_kval computes K0[k] + rho * K1[k]: one product and one sum (or one fused operation) on the stored K0, K1.  Were those
+    the correctly rounded values of the exact ones, the entry would carry 1/2 eps each from K0 and K1, 1/2 eps from the
+    product and 1/2 eps from the sum: |Kval - K|  <=  3 eps (|K0| + rho |K1|) with room to spare -- the bound of the test.
+    The stored K0 = fl(fl(P D_j) D_i) (+ sigma on the diagonal) and K1 = the double sum of t products of twice-rounded
+    entries of As are not correctly rounded; operation by operation they give (eps/2) (5 |K0| + rho (t + 6) sum|terms|),
+    returned as the second ratio (t = the terms of the entry; the test prints it beside the first).
+
+    Returns dict(ratio: worst |Kval - K_ref| / bound over the entries with a positive bound, exact: the others equal their
+    reference exactly, complete: every nonzero of the reference on a stored row is on the pattern and no other row holds
+    an entry, ratio_ops: the worst ratio to the operation count's bound, worst: (row, column) of `ratio`)."""
+    n = view.qp.n
+    (k0k, k0v), (k1k, k1v, k1a, k1c) = reference_K_parts(view)
+    ptr = np.asarray(Kptr).astype(np.int64)[view.x0 : view.x1 + 1]
+    col = np.asarray(Kcol).astype(np.int64)[ptr[0] : ptr[-1]] - view.x0
+    val = np.asarray(Kval)[ptr[0] : ptr[-1]].astype(LD)
+    row = np.repeat(np.arange(n), np.diff(ptr))
+    stored = stored_rows(view, rep)
+    in_range = bool(np.all((col >= 0) & (col < n)))
+    keys = row * n + col
+    k0, _ = _lookup(k0k, k0v, keys)
+    k1, _ = _lookup(k1k, k1v, keys)
+    k1abs, _ = _lookup(k1k, k1a, keys)
+    t, _ = _lookup(k1k, k1c.astype(np.int64), keys)
+    r = LD(rho)
+    err = np.abs(val - (k0 + r * k1))
+    bound = 3 * LD(EPS) * (np.abs(k0) + r * np.abs(k1))
+    ops = LD(EPS) / 2 * (5 * np.abs(k0) + r * (t + 6) * k1abs)
+    live = bound > 0
+    ratios = np.where(live, err / np.where(live, bound, 1), 0)
+    worst = int(np.argmax(ratios)) if ratios.size else 0
+    # every nonzero of the reference on a stored row must be on the pattern
+    ref_keys = np.union1d(k0k[k0v != 0], k1k[k1v != 0])
+    ref_keys = ref_keys[stored[ref_keys // n]]
+    complete = in_range and bool(np.all(np.isin(ref_keys, keys))) and bool(np.all(stored[row]))
+    return dict(ratio=float(ratios.max()) if ratios.size else 0.0, exact=bool(np.all(err[~live] == 0)), complete=complete,
+                ratio_ops=float((err[ops > 0] / ops[ops > 0]).max()) if np.any(ops > 0) else 0.0,
+                worst=(int(row[worst]), int(col[worst])) if ratios.size else (0, 0), terms=int(t.max()) if t.size else 0)
+
+
+def u_refresh_figures(view, rho, u, y, s):
+    """Step 2a, k_refresh_u: u = rho (bs - s) - y row by row.  The kernel rounds three times (difference, product,
+    difference) and reads bs = fl(E b): |u - u_ref|_i <= 3 eps (rho (|bs| + |s|) + |y|)_i.  Returns (worst ratio, rows with a
+    zero bound equal exactly)."""
+    _, _, bs, _ = scaled_data(view)
+    r, sl, yl = LD(rho), view.cut_rows(s).astype(LD), view.cut_rows(y).astype(LD)
+    err = np.abs(view.cut_rows(u).astype(LD) - (r * (bs - sl) - yl))
+    bound = 3 * LD(EPS) * (r * (np.abs(bs) + np.abs(sl)) + np.abs(yl))
+    live = bound > 0
+    return (float((err[live] / bound[live]).max()) if live.any() else 0.0), bool(np.all(err[~live] == 0))
+
+
+def fresh_product_figures(K, xt, kx):
+    """Step 2a: kx = K xt as ONE fresh product (HipBackend::upload_rho recomputes it after K changed) -- the cg_iters = 1
+    form of I1 without a direction update: |kx - K xt|_i <= (L + 4) eps (|K| |xt|)_i.  Returns (worst ratio, zero rows exact)."""
+    L = int(np.diff(K.indptr).max())
+    err = np.abs(np.asarray(kx).astype(LD) - ld_matvec(K, xt))
+    bound = (L + 4) * LD(EPS) * ld_matvec(K, xt, absolute=True)
+    live = bound > 0
+    return (float((err[live] / bound[live]).max()) if live.any() else 0.0), bool(np.all(err[~live] == 0))
+
+
+def penalty_update_run(models, settings, lib_path, iteration_after=False, through_reset=True):
+    """The sequence of part 2 on one handle: solve() with RHO_SETTINGS (three blocks of 16 iterations, a penalty update after
+    each, none latched), the read-outs of step a, steps(16) (step b: one replay under the new penalties), optionally one
+    more iteration for the long-double model (iteration_capture), and -- unless through_reset is off -- reset() and
+    steps(16) twice (step c).  Returns a dict; every view is built from the problem data, D, E and the penalties read back."""
+    st = dict(RHO_SETTINGS, **settings)
+    sol = ConicSolver([m.qp for _, m in models], st, lib_path=lib_path)
+    out = dict(settings=st)
+    try:
+        out["infos"] = [o.info for o in sol.solve()]
+        out["rho"] = sol.debug_get("rho")
+        out["a"] = {k: sol.debug_get(k) for k in ("Kval", "Kptr", "Kcol", "u", "y", "s", "xt", "kx")}
+        out["rep"] = int(sol.debug_get("rep")[0])
+        out["views"] = problem_views(sol, models, rho=out["rho"])
+        sol.steps(BLOCK)
+        out["b"] = {v: sol.debug_get(v) for v in ADMM_VECS}
+        if iteration_after:
+            out["iteration"] = iteration_capture(sol)
+        if not through_reset:
+            return out
+        sol.reset()
+        out["rho_reset"] = sol.debug_get("rho")
+        out["views_reset"] = problem_views(sol, models)
+        out["c"] = []
+        for _ in range(2):
+            sol.steps(BLOCK)
+            out["c"].append({v: sol.debug_get(v) for v in ADMM_VECS})
+        out["graph_launches"] = int(sol.debug_get("graph_launches")[0])
+    finally:
+        sol.close()
+    return out
+
+
+def cg_rule(cg_now, worst, st):
+    """The PCG count the driver chooses after a check: one more below 4, half as many again from 4 on, up to max_cg_iters,
+    when the worst measured reduction exceeds cg_target; fewer when it is far below.  A restatement of the rule in
+    Driver::check (score_driver.hpp, adaptive_cg) that must follow it: changing_cg_checks infers every check's verdict from
+    the counts this rule predicts, and would infer nothing if the two drifted apart (its "sequence" check pins 2, 3, 4, 6)."""
+    if worst > st["cg_target"]:
+        return min(st["max_cg_iters"], cg_now + 1 if cg_now < 4 else cg_now + cg_now // 2)
+    if worst < 0.01 * st["cg_target"] and cg_now > st["cg_iters"]:
+        return max(st["cg_iters"], cg_now - max(1, cg_now // 4))
+    return cg_now
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# one iteration against a long-double model
+# ---------------------------------------------------------------------------------------------------------------------
+ITER_VECS = ("x", "y", "s", "u", "xt", "r")
+
+
+def iteration_capture(sol):
+    """x0, y0, s0 as the handle holds them, then steps(1) -- a single measuring iteration, nothing deferred -- and
+    x1, y1, s1, u1, xt1, r1 (all in the solver's scaled variables)."""
+    before = {k + "0": sol.debug_get(k) for k in ("x", "y", "s")}
+    sol.steps(1)
+    return dict(before, **{k + "1": sol.debug_get(k) for k in ITER_VECS})
+
+
+def cone_layout(qp):
+    """(first row of every cone, its rows, SOC or zero) -- the z zero rows one cone each, then the second-order cones."""
+    dims = np.r_[np.ones(int(qp.z), dtype=np.int64), np.asarray(qp.soc_dims, dtype=np.int64)]
+    return np.r_[0, np.cumsum(dims)[:-1]].astype(np.int64), dims, np.r_[np.zeros(int(qp.z), dtype=bool), np.ones(len(qp.soc_dims), dtype=bool)]
+
+
+def iteration_model(view, cap, alpha=ALPHA):
+    """One ADMM iteration of a problem in np.longdouble from its data (As = E A D, bs, qs), alpha, sigma and its penalty rho,
+    given x0, y0, s0 and the xt1 the PCG produced:
+
+        v = alpha (bs - As xt1) + (1 - alpha) s0          w = v - y0 / rho           s_ref = Proj_K(w), zero cones -> 0
+        y_ref = y0 + rho (s_ref - v)                      u_ref = rho (bs - s_ref) - y_ref
+        x_ref = alpha xt1 + (1 - alpha) x0                rhs_ref = sigma x0 - qs + As'(rho (bs - s0) - y0)   (= r1 + K xt1)
+
+    and the forward-error bounds of the kernels' arithmetic, every rounding counted with eps = 2^-52 (twice the unit
+    roundoff: the margin over first order).  L_i = entries of row i of As (at most 2 in a SCORE model).
+
+      v   k_cone / k_cone_wave: the row product sums L_i products of entries rounded twice at setup (L_i + 2 roundings on
+          |As||xt1|), bs = fl(E b) (1), the difference (1), the product with alpha (1), fl(1 - alpha) and its product with s0
+          (2), the sum (1):                     e_v = eps (|alpha| (4 |bs| + (L_i + 5) |As||xt1|) + 3 |1 - alpha| |s0|)
+      w   fl(1 / rho), its product with y0, the difference (on |w| <= |v| + |y0| / rho):
+                                                e_w = eps (|alpha| (5 |bs| + (L_i + 6) |As||xt1|) + 4 |1 - alpha| |s0| + 3 |y0| / rho)
+      s   per cone, in the 2-norm: the projection is 1-Lipschitz, so the error of w passes at most unchanged; soc_scales rounds
+          the squared tail norm (dim - 1 roundings, halved by the root, + 1), the mean (1), the quotient (1) and the scaled tail
+          (1) -- at most (dim + 5) roundings on |w|_2 (a branch taken the other way at a boundary moves s by less, the
+          projection being continuous):         B_s = |e_w|_2 + (dim + 5) eps |w|_2          (zero cones: s = 0 exactly)
+      y   row by row: rho (B_s + e_v) from s and v, the difference, the product, the sum:
+                                                B_y = rho (B_s + e_v) + eps (3 rho (|s_ref| + |v|) + |y0|)
+      u   the same three operations on bs (rounded), s and y:
+                                                B_u = rho (eps |bs| + B_s) + B_y + eps (3 rho (|bs| + |s_ref|) + |y_ref|)
+      x   k_xupdate: two products, fl(1 - alpha), one sum:   B_x = 3 eps (|alpha| |xt1| + |1 - alpha| |x0|)
+
+    No bound holds a free constant; rows and cones whose bound is 0 must be equal exactly.  The right-hand-side identity
+    carries the PCG recurrence's error (r1 + kx1 telescopes exactly, kx1 = K xt1 only up to I2), so its figure is normwise with
+    the twin's own as yardstick (rhs_figure).  Returns a dict of the references, the bounds and `branch` per cone:
+    0 zero cone, 1 inside (kept), 2 polar (-> 0), 3 outside (projected onto the boundary)."""
+    qp = view.qp
+    A, vals, bs, qs = scaled_data(view)
+    rho, al, sig, eps = LD(view.rho), LD(alpha), LD(view.sigma), LD(EPS)
+    x0, y0, s0, xt1 = (view.cut(cap["x0"]).astype(LD), view.cut_rows(cap["y0"]).astype(LD), view.cut_rows(cap["s0"]).astype(LD),
+                       view.cut(cap["xt1"]).astype(LD))
+    Lr = np.diff(A.indptr).astype(LD)
+    axt, axt_abs = _ld_rows(A, vals, xt1), _ld_rows(A, vals, xt1, absolute=True)
+    v = al * (bs - axt) + (1 - al) * s0
+    w = v - y0 / rho
+    first, dims, soc = cone_layout(qp)
+    head = np.zeros(qp.m, dtype=bool)
+    head[first] = True
+    cone_of_row = np.repeat(np.arange(first.size), dims)
+    t0 = w[first]
+    nz = np.sqrt(np.add.reduceat(np.where(head, 0, w * w), first))
+    branch = np.where(~soc, 0, np.where(nz <= t0, 1, np.where(nz <= -t0, 2, 3)))
+    mean = (t0 + nz) / 2
+    head_val = np.where(branch == 1, t0, np.where(branch == 3, mean, 0))
+    tail_fac = np.where(branch == 1, 1, np.where(branch == 3, mean / np.where(nz > 0, nz, 1), 0))
+    s_ref = np.where(head, head_val[cone_of_row], tail_fac[cone_of_row] * w)
+    y_ref = y0 + rho * (s_ref - v)
+    u_ref = rho * (bs - s_ref) - y_ref
+    x_ref = al * xt1 + (1 - al) * x0
+    u0 = rho * (bs - s0) - y0
+    rhs_ref = sig * x0 - qs + _ld_cols(A, vals, u0)
+    rhs_scale = sig * np.abs(x0) + np.abs(qs) + _ld_cols(A, vals, rho * (np.abs(bs) + np.abs(s0)) + np.abs(y0), absolute=True)
+    a1, a2 = np.abs(al), np.abs(1 - al)
+    e_v = eps * (a1 * (4 * np.abs(bs) + (Lr + 5) * axt_abs) + 3 * a2 * np.abs(s0))
+    e_w = eps * (a1 * (5 * np.abs(bs) + (Lr + 6) * axt_abs) + 4 * a2 * np.abs(s0) + 3 * np.abs(y0) / rho)
+    B_s = np.where(soc, np.sqrt(np.add.reduceat(e_w * e_w, first)) + (dims + 5) * eps * np.sqrt(np.add.reduceat(w * w, first)), 0)
+    B_y = rho * (B_s[cone_of_row] + e_v) + eps * (3 * rho * (np.abs(s_ref) + np.abs(v)) + np.abs(y0))
+    B_u = rho * (eps * np.abs(bs) + B_s[cone_of_row]) + B_y + eps * (3 * rho * (np.abs(bs) + np.abs(s_ref)) + np.abs(y_ref))
+    B_x = 3 * eps * (a1 * np.abs(xt1) + a2 * np.abs(x0))
+    return dict(v=v, w=w, s=s_ref, y=y_ref, u=u_ref, x=x_ref, rhs=rhs_ref, rhs_scale=rhs_scale, branch=branch, first=first, dims=dims,
+                B_s=B_s, B_y=B_y, B_u=B_u, B_x=B_x)
+
+
+def _worst(err, bound):
+    live = bound > 0
+    return (float((err[live] / bound[live]).max()) if live.any() else 0.0), bool(np.all(err[~live] == 0))
+
+
+def rhs_figure(view, model, cap):
+    """e = |r1 + K xt1 - rhs_ref|_inf / (|K|_inf |xt1|_inf + |rhs scale|_inf): the right-hand side k_spmv<MODE_RHS> formed, as
+    the residual and the iterate it led to show it."""
+    xt1 = view.cut(cap["xt1"])
+    lhs = view.cut(cap["r1"]).astype(LD) + ld_matvec(view.K, xt1)
+    den = norm_inf_matrix(view.K) * float(np.abs(xt1).max()) + float(model["rhs_scale"].max())
+    return float(np.abs(lhs - model["rhs"]).max()) / den if den > 0 else 0.0
+
+
+def rhs_bound(view, e_twin):
+    """8 max(e_twin, (L + 4) eps), L = the longest row of K plus the longest column of As plus the two other terms: the
+    margin and the floor of I2 (i2_bound), for the same reason."""
+    A = sp.csc_matrix(view.qp.A)
+    L = int(np.diff(view.K.indptr).max()) + (int(np.diff(A.indptr).max()) if A.nnz else 0) + 2
+    return 8.0 * max(e_twin, (L + 4) * EPS)
+
+
+def iteration_figures(view, model, cap):
+    """The ratios of what one iteration left (x1, s1, y1, u1) to the bounds of iteration_model: dict of (worst ratio, zero-bound
+    entries exact) for x, y, u row by row and s cone by cone (2-norm), and the figure of the right-hand-side identity."""
+    x1, y1, s1, u1 = (view.cut(cap["x1"]).astype(LD), view.cut_rows(cap["y1"]).astype(LD), view.cut_rows(cap["s1"]).astype(LD),
+                      view.cut_rows(cap["u1"]).astype(LD))
+    ds = s1 - model["s"]
+    return dict(x=_worst(np.abs(x1 - model["x"]), model["B_x"]), s=_worst(np.sqrt(np.add.reduceat(ds * ds, model["first"])), model["B_s"]),
+                y=_worst(np.abs(y1 - model["y"]), model["B_y"]), u=_worst(np.abs(u1 - model["u"]), model["B_u"]),
+                rhs=rhs_figure(view, model, cap))
+
+
+def iteration_ok(f):
+    return all(f[k][0] <= 1.0 and f[k][1] for k in ("x", "s", "y", "u"))
+
+
+def general_conic_program(dims, seed=0):
+    """minimise 1/2 |x - c|^2 over a product of second-order cones (P = I, A = -I, b = 0, no chains): a program whose cones are
+    not SCORE's.  Of the cones with more than one row, c lies outside the first (projected onto its boundary), inside the second
+    and in the polar cone of the third, and so on in turn.  Returns (None, model-like with .qp)."""
+    import types
+
+    from score_amd.assemble import ConicQP
+
+    rng = np.random.default_rng(seed + int(sum(dims)))
+    n = int(sum(dims))
+    c = rng.normal(size=n)
+    off, kind = 0, 0
+    for dm in dims:
+        blk = c[off : off + dm]
+        if dm > 1:
+            nt = np.linalg.norm(blk[1:])
+            blk[0] = (0.3 * nt, 2.0 * nt + 0.1, -2.0 * nt - 0.1)[kind % 3]
+            kind += 1
+        off += dm
+    qp = ConicQP(P=sp.identity(n, format="csr"), q=-c, c0=0.5 * float(c @ c), A=(-sp.identity(n, format="csr")), b=np.zeros(n), z=0,
+                 soc_dims=np.asarray(dims, dtype=np.int32))
+    return None, types.SimpleNamespace(qp=qp)
+
+
+GENERAL_DIMS = {"Q": (3, 130, 1, 70),      # k_cone's register path (3 rows outside, 1 row); k_cone_wave inside (130) and polar (70)
+                "Q32": (20, 1, 7, 32),     # k_cone's general path: 5 to 32 rows, one lane per cone, in all three branches
+                "QW": (130, 70, 1, 100)}   # k_cone_wave (more than 32 rows, lanes striding by 64) outside, inside and polar
+
+
+def iteration_models(case):
+    """The (graph, model) list of a case of the iteration tests: a case of CASE_GRAPHS or a general conic program."""
+    return [general_conic_program(GENERAL_DIMS[case])] if case in GENERAL_DIMS else case_models(case)
+
+
+def iteration_at_start(models, settings, lib_path):
+    """reset(), steps(3), then one captured iteration at rho = settings.rho.  Returns (views, capture)."""
+    sol = ConicSolver([m.qp for _, m in models], dict(ADMM_SETTINGS, **settings), lib_path=lib_path)
+    try:
+        views = problem_views(sol, models)
+        sol.reset()
+        sol.steps(3)
+        cap = iteration_capture(sol)
+    finally:
+        sol.close()
+    return views, cap
+
+
+def replay_and_single_steps(models, settings, lib_path):
+    """Part 5: two handles from the same models -- reset(), steps(16) (one replay, 15 deferred updates) against use_graph = 0,
+    reset() and steps(1) sixteen times (nothing deferred).  Returns (vectors of the first, of the second, graph launches of
+    each)."""
+    st = dict(ADMM_SETTINGS, check_interval=BLOCK, **settings)
+    vecs = ("x", "y", "s", "xt", "kx")
+    out = []
+    for use_graph, blocks in ((1, (BLOCK,)), (0, (1,) * BLOCK)):
+        sol = ConicSolver([m.qp for _, m in models], dict(st, use_graph=use_graph), lib_path=lib_path)
+        try:
+            sol.reset()
+            for k in blocks:
+                sol.steps(k)
+            out.append(({v: sol.debug_get(v) for v in vecs}, int(sol.debug_get("graph_launches")[0])))
+        finally:
+            sol.close()
+    return out[0][0], out[1][0], (out[0][1], out[1][1])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the checks the GPU tests and the twin's tests share
+# ---------------------------------------------------------------------------------------------------------------------
+def identity_checks(view, vec, cg_iters, float_factors, label, yard=None):
+    """I1-I3 of one problem and one snapshot as {name: passed} and the OPID line; `yard`: (view, vectors) of the twin's run of
+    the same sequence, the yardstick of I2 (None: the floor of the bound alone, what the twin itself is held to)."""
+    f = admm_figures(view, vec, cg_iters, float_factors)
+    e_yard = 0.0 if yard is None else i2_figure(yard[0].K, yard[0].cut(yard[1]["xt"]), yard[0].cut(yard[1]["kx"]))
+    b2 = i2_bound(view.K, e_yard)
+    line = (f"OPID {label} n={view.qp.n} rho={view.rho:.6g} | I1 {f['i1']:.4f} | I2 {f['i2']:.3e} bound {b2:.3e} | "
+            f"I3 {f['i3']:.3e} bound {f['i3_bound']:.3e}")
+    return {"link pairs": f["pairs_ok"], "I1": f["i1"] <= 1.0 and f["i1_exact"], "I2": f["i2"] <= b2,
+            "I3": f["i3"] <= f["i3_bound"], "I3 Jacobi": f["jacobi"]}, line
+
+
+def penalty_update_checks(run, float_factors, label, yard=None, expect_launches=None):
+    """Every assertion of part 2 on the result of penalty_update_run, as (failures, OPID lines); `yard`: the twin's run
+    (I2's yardstick in steps b and c)."""
+    st, views, rho = run["settings"], run["views"], run["rho"]
+    cg, fails, lines = st["cg_iters"], [], []
+
+    def note(lab, checks):
+        fails.extend((lab, nm) for nm, ok in checks.items() if not ok)
+
+    a = run["a"]
+    note(label, {"three updates": all(i["rho_updates"] == 3 for i in run["infos"]),
+                 "rho read back == info": all(float(rho[k]) == i["rho"] for k, i in enumerate(run["infos"])),
+                 "penalties differ": len(set(float(r) for r in rho)) == len(rho),
+                 "rho after reset": bool(np.all(run["rho_reset"] == st["rho"])),
+                 "graph launches": expect_launches is None or run["graph_launches"] == expect_launches})
+    for k, v in enumerate(views):
+        lab = f"{label}[{k}]"
+        kv = kval_figures(v, rho[k], a["Kptr"], a["Kcol"], a["Kval"], run["rep"])
+        uf = u_refresh_figures(v, rho[k], a["u"], a["y"], a["s"])
+        kf = fresh_product_figures(v.K, v.cut(a["xt"]), v.cut(a["kx"]))
+        lines.append(f"OPID {lab} update rho={float(rho[k]):.6g} | Kval {kv['ratio']:.4f} of 3 eps (|K0| + rho |K1|) (terms <= {kv['terms']}: "
+                     f"{kv['ratio_ops']:.4f} of the operation count) | u {uf[0]:.4f} | kx {kf[0]:.4f}")
+        note(lab + " a", {"Kval": kv["ratio"] <= 1.0 and kv["exact"], "Kval pattern": kv["complete"], "u": uf[0] <= 1.0 and uf[1],
+                          "kx": kf[0] <= 1.0 and kf[1]})
+        yb = None if yard is None else (yard["views"][k], yard["b"])
+        checks, line = identity_checks(v, run["b"], cg, float_factors, lab + " b", yb)
+        lines.append(line)
+        note(lab + " b", checks)
+        for s, vec in enumerate(run["c"]):
+            yc = None if yard is None else (yard["views_reset"][k], yard["c"][s])
+            checks, line = identity_checks(run["views_reset"][k], vec, cg, float_factors, f"{lab} c{s + 1}", yc)
+            lines.append(line)
+            note(f"{lab} c{s + 1}", checks)
+    return fails, lines
+
+
+def iteration_checks(views, cap, label, yard=None, alpha=ALPHA):
+    """The figures of one captured iteration for every problem of a handle, as (failures, OPID lines, models); `yard`:
+    (views, capture) of the twin's run, the yardstick of the right-hand-side identity (None: its floor alone)."""
+    fails, lines, models = [], [], []
+    for k, v in enumerate(views):
+        m = iteration_model(v, cap, alpha)
+        f = iteration_figures(v, m, cap)
+        e_yard = 0.0 if yard is None else rhs_figure(yard[0][k], iteration_model(yard[0][k], yard[1], alpha), yard[1])
+        b = rhs_bound(v, e_yard)
+        lines.append(f"OPID {label}[{k}] iteration rho={v.rho:.6g} cones in/polar/out {[int((m['branch'] == c).sum()) for c in (1, 2, 3)]} | "
+                     f"x {f['x'][0]:.4f} | s {f['s'][0]:.4f} | y {f['y'][0]:.4f} | u {f['u'][0]:.4f} | rhs {f['rhs']:.3e} bound {b:.3e}")
+        fails += [(f"{label}[{k}]", nm) for nm in ("x", "s", "y", "u") if not (f[nm][0] <= 1.0 and f[nm][1])]
+        if not f["rhs"] <= b:
+            fails.append((f"{label}[{k}]", "rhs"))
+        models.append(m)
+    return fails, lines, models
+
+
+def iteration_after_updates(models, settings, lib_path):
+    """The part 2 sequence up to its step b, then one captured iteration at the updated per-problem penalties.
+    Returns (views, capture)."""
+    run = penalty_update_run(models, settings, lib_path, iteration_after=True, through_reset=False)
+    return run["views"], run["iteration"]
+
+
+def changing_cg_run(models, settings, lib_path):
+    """Part 3 on one handle: solve() with CG_SETTINGS (three blocks of 16 iterations, the PCG count re-chosen after each),
+    then steps(16) under the last count and the vectors it leaves."""
+    st = dict(CG_SETTINGS, **settings)
+    sol = ConicSolver([m.qp for _, m in models], st, lib_path=lib_path)
+    try:
+        infos = [o.info for o in sol.solve()]
+        after = [o.info for o in sol.steps(BLOCK)]
+        out = dict(settings=st, infos=infos, after=after, views=problem_views(sol, models), snap={v: sol.debug_get(v) for v in ADMM_VECS},
+                   graph_launches=int(sol.debug_get("graph_launches")[0]))
+    finally:
+        sol.close()
+    return out
+
+
+def changing_cg_checks(run, float_factors, label, yard=None, expect_launches=None):
+    """The assertions of part 3, as (failures, OPID lines).  The count after a check is a function of the count before it
+    and of the check's verdict (cg_rule: above the target, between, far below); the PCG iterations of the three blocks and
+    of the block after them are reported (info.cg_iters), and of the 27 verdict sequences only `above` three times gives
+    both figures -- so they show that the measured reduction exceeded the target at every check."""
+    import itertools
+
+    st, fails, lines = run["settings"], [], []
+    verdicts = dict(above=1.0, between=0.5 * st["cg_target"], below=0.0)
+    outcomes = {}
+    for names in itertools.product(verdicts, repeat=3):
+        seq = [st["cg_iters"]]
+        for nm in names:
+            seq.append(cg_rule(seq[-1], verdicts[nm], st))
+        outcomes.setdefault((BLOCK * sum(seq[:3]), seq[3]), []).append((names, seq))
+    (want_total, want_last), = [k for k, v in outcomes.items() if any(n == ("above",) * 3 for n, _ in v)]
+    seq = outcomes[(want_total, want_last)][0][1]
+    checks = {"sequence": seq == [2, 3, 4, 6] and want_total == BLOCK * (2 + 3 + 4),
+              "verdicts pinned": len(outcomes[(want_total, want_last)]) == 1,
+              "cg_iters of solve": all(i["cg_iters"] == want_total for i in run["infos"]),
+              "cg_iters of the block after": all(i["cg_iters"] - want_total == BLOCK * want_last for i in run["after"]),
+              "graph launches": expect_launches is None or run["graph_launches"] == expect_launches}
+    fails += [(label, nm) for nm, ok in checks.items() if not ok]
+    for k, v in enumerate(run["views"]):
+        y = None if yard is None else (yard["views"][k], yard["snap"])
+        c, line = identity_checks(v, run["snap"], want_last, float_factors, f"{label}[{k}] cg={seq}", y)
+        lines.append(line)
+        fails += [(f"{label}[{k}]", nm) for nm, ok in c.items() if not ok]
+    return fails, lines

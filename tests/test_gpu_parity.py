@@ -45,10 +45,24 @@ def test_iterates_match_cpu_twin(name, radix, cg, fp32, fixtures, hip_lib, twin_
     synth_b has loop closures: its preconditioner carries the link correction (score_link.hpp), restated
     independently in the twin (dense capacitance matrix, LU) -- with double factors the two agree to the same
     1e-9; with float factors the correction y - Z t cancels leading digits of two float-accurate terms, so the
-    preconditioned directions (and with a fixed PCG count the iterates) agree to 1e-3 only."""
+    preconditioned directions (and with a fixed PCG count the iterates) agree to 1e-3 only.
+    check_interval = 16 keeps every steps(k) one block: steps(9) is one run of 9 iterations with 8 deferred end-of-PCG
+    updates (it was 5 + 4 under check_interval = 5), and the last block, 16 iterations, is long enough to be replayed from
+    a captured graph (HipBackend::graph_min_iters): with use_graph = 1 the handle must report the launch, with
+    use_graph = 0 none.
+    After that block (31 iterations in all) the iterates x, xt, s, y, u and kx are held to the tolerances above.  The PCG
+    internals r, z, p, w have by then decayed -- synth_b: |p|_inf from 608 to 0.22, |r|_inf from 1.8 to 1.9e-4 -- while the
+    terms they cancel from (|kx|_inf = 4e2) have not, so their rounding no longer shrinks with them and the tolerance
+    relative to max(1, |v|_inf) of the vector itself asks for more than the twin defines: on synth_b with radix 4, cg 2
+    and double factors four builds of the twin (-march=native on two processors, without fused multiply-adds, generic)
+    differ from one another by 6e-10 .. 1.0e-9 in p, and the device differs from them by 9.2e-10 .. 1.54e-9 (use_graph 0
+    and 1 bit-identical) -- against 1e-9 the case passes or fails with the machine the twin was compiled on.  For this
+    block these four vectors are therefore measured against the largest |v|_inf the vector has had in the run (the scale
+    it had before it cancelled; same factors 1e-9 / 1e-4 / 1e-2), so that the absolute tolerance of the block does not fall
+    below that of the blocks before it; the blocks of 1, 5 and 9 iterations keep the vector's own scale."""
     _hip_only(hip_lib)
     qp = assemble(graph_by_name(name, fixtures), "SOCP").qp
-    st = dict(chain_radix=radix, cg_iters=cg, adaptive_cg=0, adaptive_rho=0, check_interval=5, fac_fp32=fp32)
+    st = dict(chain_radix=radix, cg_iters=cg, adaptive_cg=0, adaptive_rho=0, check_interval=16, fac_fp32=fp32)
     links = name == "synth_b"
     tol = (1e-3 if links else 2e-5) if fp32 else 1e-9
     xtol = (1e-3 if links else 1e-6) if fp32 else 1e-9
@@ -60,11 +74,13 @@ def test_iterates_match_cpu_twin(name, radix, cg, fp32, fixtures, hip_lib, twin_
         # the twin applies the full K the problem defines
         assert gpu.debug_get("rep")[0] == 2 and cpu.debug_get("rep")[0] == 1
         gpu.reset(); cpu.reset()
-        for k in (1, 5, 9):
+        peak = {v: 0.0 for v in VECS}  # largest |v|_inf of the twin's vector over the blocks run so far
+        for k in (1, 5, 9, 16):
             a, b = gpu.steps(k)[0], cpu.steps(k)[0]
             for v in VECS:
                 ga, gb = gpu.debug_get(v), cpu.debug_get(v)
-                scale = max(1.0, np.abs(gb).max())
+                peak[v] = max(peak[v], float(np.abs(gb).max()))
+                scale = max(1.0, peak[v] if (k == 16 and v in ("r", "z", "p", "w")) else np.abs(gb).max())
                 # (fp32 factors: the PCG internals r, z, p, w are small differences of large terms -- 1e-4)
                 vtol = (1e-2 if links else 1e-4) if (fp32 and v in ("r", "z", "p", "w")) else tol
                 assert np.abs(ga - gb).max() <= vtol * scale, (v, k, use_graph, np.abs(ga - gb).max(), scale)
@@ -72,6 +88,8 @@ def test_iterates_match_cpu_twin(name, radix, cg, fp32, fixtures, hip_lib, twin_
             assert a.info["res_pri"] == pytest.approx(b.info["res_pri"], rel=1e-2 if fp32 else 1e-6, abs=1e-12)
             assert a.info["res_dual"] == pytest.approx(b.info["res_dual"], rel=1e-2 if fp32 else 1e-6, abs=1e-2 if fp32 else 1e-9)
             assert a.info["pobj"] == pytest.approx(b.info["pobj"], rel=tol, abs=tol)
+        launches = int(gpu.debug_get("graph_launches")[0])
+        assert launches >= 1 if use_graph else launches == 0, (use_graph, launches)
         gpu.close(); cpu.close()
 
 

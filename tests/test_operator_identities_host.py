@@ -1,5 +1,6 @@
 """The operator identities of operator_helpers.py on the CPU twin, and the checker tested on itself: a planted value error in
-the vectors must fail exactly the identity it belongs to.  (The HIP kernels: test_operator_identities_gpu.py.)"""
+the vectors must fail exactly the identity it belongs to; the same for the figures of the loop under penalty updates and a
+changing PCG count and for the long-double model of one iteration.  (The HIP kernels: test_operator_identities_gpu.py.)"""
 import numpy as np
 import pytest
 
@@ -101,3 +102,121 @@ def test_the_checker_catches_a_dropped_update_of_the_carried_product(twin_lib):
     i = int(np.argmax(np.abs(vec["w"])))
     vec["kx"][i] -= a * vec["w"][i]
     assert _verdicts(view, vec, 1, True, e_clean) == dict(i1=True, i2=False, i3=True)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the loop as the benchmark drives it (penalty updates, a changing PCG count), on the twin: the check of the checker
+# ---------------------------------------------------------------------------------------------------------------------
+UPDATE_CASES = [("A", {}), ("B", {}), ("C1024", {}), ("D300", dict(chain_split=1)), ("E60", {}), ("F", {}), ("G", {})]
+
+
+@pytest.mark.parametrize("fp32", [0, 1])
+@pytest.mark.parametrize("case,extra", UPDATE_CASES, ids=[c for c, _ in UPDATE_CASES])
+def test_identities_after_penalty_updates_on_the_twin(case, extra, fp32, twin_lib):
+    """operator_helpers.penalty_update_run on the twin, held to the bounds the device is held to
+    (test_operator_identities_gpu.py::test_identities_after_penalty_updates states them): three updates, the penalties read
+    back, K = K0 + rho K1 entry by entry, u refreshed, kx a fresh product; I1-I3 after one more block under each problem's
+    own penalty; the settings' penalty and I1-I3 again after reset() (I2 under the floor of its bound)."""
+    run = oh.penalty_update_run(oh.case_models(case), dict(fac_fp32=fp32, **extra), twin_lib)
+    fails, lines = oh.penalty_update_checks(run, bool(fp32), f"twin {case} fp32={fp32}", expect_launches=0)
+    print("\n".join(lines))
+    assert not fails, fails
+
+
+@pytest.mark.parametrize("fp32", [0, 1])
+@pytest.mark.parametrize("case", ["A", "G"])
+def test_identities_under_a_changing_pcg_count_on_the_twin(case, fp32, twin_lib):
+    """The sequence of test_operator_identities_gpu.py::test_identities_under_a_changing_pcg_count on the twin."""
+    run = oh.changing_cg_run(oh.case_models(case), dict(fac_fp32=fp32), twin_lib)
+    fails, lines = oh.changing_cg_checks(run, bool(fp32), f"twin {case} fp32={fp32}", expect_launches=0)
+    print("\n".join(lines))
+    assert not fails, fails
+
+
+ITERATION_CASES = ["A", "E40", "F", "G", "Q", "Q32", "QW"]
+
+
+@pytest.mark.parametrize("case", ITERATION_CASES)
+def test_one_iteration_against_the_long_double_model_on_the_twin(case, twin_lib):
+    """One iteration of the twin against operator_helpers.iteration_model, at the start (reset(), steps(3)) and after the
+    penalty updates of part 2, under the bounds its docstring derives; the general conic programs must take the branches
+    their c was chosen for (outside, inside, polar -- in this order over the cones with more than one row)."""
+    models = oh.iteration_models(case)
+    for where, (views, cap) in (("start", oh.iteration_at_start(models, {}, twin_lib)),
+                                ("updated", oh.iteration_after_updates(models, {}, twin_lib))):
+        fails, lines, ms = oh.iteration_checks(views, cap, f"twin {case} {where}")
+        print("\n".join(lines))
+        assert not fails, fails
+        if case in oh.GENERAL_DIMS:
+            assert [int(b) for b, d in zip(ms[0]["branch"], ms[0]["dims"]) if d > 1] == [3, 1, 2], (where, ms[0]["branch"])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the checker catches what the new figures are for
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def updated_run(twin_lib):
+    """One run of the part 2 sequence on the batch G with one more captured iteration; shared and never changed."""
+    return oh.penalty_update_run(oh.case_models("G"), dict(fac_fp32=1), twin_lib, iteration_after=True)
+
+
+def test_the_checker_catches_an_entry_of_k_left_at_the_old_penalty(updated_run):
+    """One entry of Kval of problem 1 of the batch -- the off-diagonal one with the largest rho |K1| -- recomputed with the
+    settings' penalty instead of the problem's updated one: the Kval figure of step 2a fails, for that problem alone."""
+    run = updated_run
+    a, rho, k = run["a"], run["rho"], 1
+    v = run["views"][k]
+    assert all(oh.kval_figures(w, rho[j], a["Kptr"], a["Kcol"], a["Kval"], run["rep"])["ratio"] <= 1.0 for j, w in enumerate(run["views"]))
+    old = oh.reference_K(v.qp, v.D, v.E, rho=oh.RHO)
+    ptr = a["Kptr"].astype(np.int64)
+    rows = np.repeat(np.arange(ptr.size - 1), np.diff(ptr))
+    cols = a["Kcol"].astype(np.int64)
+    mine = (rows >= v.x0) & (rows < v.x1) & (rows != cols)
+    gap = np.where(mine, np.abs(a["Kval"] - np.asarray(old[np.minimum(np.maximum(rows - v.x0, 0), v.qp.n - 1), np.clip(cols - v.x0, 0, v.qp.n - 1)]).ravel()), 0.0)
+    e = int(np.argmax(gap))
+    assert gap[e] > 0
+    bad = a["Kval"].copy()
+    bad[e] = old[rows[e] - v.x0, cols[e] - v.x0]
+    verdict = [oh.kval_figures(w, rho[j], a["Kptr"], a["Kcol"], bad, run["rep"])["ratio"] <= 1.0 for j, w in enumerate(run["views"])]
+    assert verdict == [True, False, True]
+
+
+def test_the_checker_catches_a_u_not_refreshed_after_an_update(updated_run):
+    """u of one problem left at rho (bs - s) - y with the settings' penalty in place of the problem's updated one: the u figure
+    of step 2a fails for that problem alone."""
+    run = updated_run
+    a, rho, k = run["a"], run["rho"], 2
+    v = run["views"][k]
+    assert all(oh.u_refresh_figures(w, rho[j], a["u"], a["y"], a["s"])[0] <= 1.0 for j, w in enumerate(run["views"]))
+    _, _, bs, _ = oh.scaled_data(v)
+    stale = a["u"].copy()
+    stale[v.r0 : v.r1] = (oh.RHO * (bs - v.cut_rows(a["s"])) - v.cut_rows(a["y"])).astype(np.float64)
+    verdict = [oh.u_refresh_figures(w, rho[j], stale, a["y"], a["s"])[0] <= 1.0 for j, w in enumerate(run["views"])]
+    assert verdict == [True, True, False]
+
+
+def test_the_checker_catches_a_model_with_alpha_off(updated_run):
+    """The iteration model with alpha + 1e-9 in place of the handle's alpha: the s, y, u and x figures of part 4 fail."""
+    run = updated_run
+    v, cap = run["views"][0], run["iteration"]
+    assert oh.iteration_ok(oh.iteration_figures(v, oh.iteration_model(v, cap), cap))
+    f = oh.iteration_figures(v, oh.iteration_model(v, cap, alpha=oh.ALPHA + 1e-9), cap)
+    assert not oh.iteration_ok(f)
+    assert f["x"][0] > 1.0 and f["y"][0] > 1.0
+
+
+def test_the_checker_catches_a_cone_whose_dual_update_was_dropped(updated_run):
+    """y1 with the update of one cone dropped (its rows left at y0) -- the second-order cone whose update is largest: the y
+    figure of part 4 fails, x and s still hold (u is formed from y and fails with it)."""
+    run = updated_run
+    v, cap = run["views"][1], {k: w.copy() for k, w in run["iteration"].items()}
+    m = oh.iteration_model(v, cap)
+    assert oh.iteration_ok(oh.iteration_figures(v, m, cap))
+    first, dims = m["first"], m["dims"]
+    moved = np.maximum.reduceat(np.abs(v.cut_rows(cap["y1"]) - v.cut_rows(cap["y0"])), first)
+    c = int(np.argmax(np.where(dims > 1, moved, 0.0)))
+    assert moved[c] > 0
+    rows = slice(v.r0 + first[c], v.r0 + first[c] + dims[c])
+    cap["y1"][rows] = cap["y0"][rows]
+    f = oh.iteration_figures(v, m, cap)
+    assert f["y"][0] > 1.0 and f["x"][0] <= 1.0 and f["s"][0] <= 1.0
