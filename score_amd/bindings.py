@@ -200,8 +200,18 @@ LEVERAGE = Table("leverage", _NO_LEVERAGES, {
                                       _f64p, _i32p, _f64p, C.POINTER(ScoreMarginalsInfo)], C.c_int),
 })
 
+LEVERAGE_BATCH = Table("leverage_batch", _NO_LEVERAGES, {
+    "score_refine_batch_leverage": ([_handle, _f64p, _f64p, _u64p, C.c_int64, _i32p, _i32p, _i32p, _i32p, C.c_double, C.c_int32,
+                                     C.c_int32, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _i32p, _i32p,
+                                     C.POINTER(ScoreSamplesBatchInfo)], C.c_int),
+    "score_refine_batch_range_variances": ([_handle, _f64p, _f64p, _i32p, _i32p, _i32p, C.c_double, C.c_int32, C.c_int32, _f64p, _f64p,
+                                            _f64p, _i32p, C.POINTER(ScoreMarginalsBatchInfo)], C.c_int),
+})
+
 TABLES = (ROBUST, REFINE_ROBUST, REFINE_BATCH, REFINE_ROBUST_BATCH, MARGINALS, MARGINALS_BATCH, SPECTRUM, SPECTRUM_BATCH,
           SAMPLES, SAMPLES_BATCH, LEVERAGE)
+# the headers that came after those (TABLES itself is pinned by its test)
+LATER_TABLES = (LEVERAGE_BATCH,)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -4374,6 +4374,7 @@ struct score_refine {
 #include "score_group_pcg.hpp"
 #include "score_marginals_batch.hpp"
 #include "score_samples_batch.hpp"
+#include "score_leverage_batch.hpp"
 #include "score_spectrum_batch.hpp"
 
 // Local refinement of a group of graphs in lock-step (score_gn_batch.hpp): the union state, blocks and gathers here, the
@@ -4399,6 +4400,7 @@ struct score_refine_batch {
     score::GbmWork mvb;  // marginal covariances of the members (score_marginals_batch.hpp)
     score::GspWork spb;  // lowest eigenpairs of the members (score_spectrum_batch.hpp)
     score::GbsWork gbs;  // posterior samples of the members (score_samples_batch.hpp)
+    score::GblWork gbl;  // range leverage and predicted range variances of the members (score_leverage_batch.hpp)
     // robust refinement (score_gn_robust_batch.hpp): the measured precisions beside rng_prec / rel_kappa / rel_tau (which hold the
     // weighted ones during a robust run, and after one with keep_weights), residuals, weights, per-workgroup partials, the
     // members' parameters; they come with the first robust call.  U keeps rng_prec / rel_kappa / rel_tau on the host for them.
@@ -4973,8 +4975,35 @@ int score_refine_batch_samples(score_refine_batch* b, const double* poses, const
         require(b != nullptr, "score_refine_batch_samples: null handle");
         require(poses && (b->U.lms_size == 0 || landmarks), "score_refine_batch_samples: the points are missing");
         AbiEnv::Scope scope(b->device, false);
-        return score::gbs_solve(*b, poses, landmarks, seeds, first_sample, n_samples, var_ptr, vars, rel_tol, max_iters, block_width,
-                                moments, means, steps, rhs, noise, residuals, iters, determined, info);
+        score::GbsMoments use{var_ptr, vars, moments, means, steps};
+        return score::gbs_solve(*b, "score_refine_batch_samples: ", poses, landmarks, seeds, first_sample, n_samples, rel_tol, max_iters,
+                                block_width, rhs, noise, residuals, iters, determined, info, use);
+    });
+}
+int score_refine_batch_leverage(score_refine_batch* b, const double* poses, const double* landmarks, const uint64_t* seeds,
+                                int64_t first_sample, const int32_t* n_samples, const int32_t* pair_ptr, const int32_t* pair_a,
+                                const int32_t* pair_b, double rel_tol, int32_t max_iters, int32_t block_width, double* lev_sum,
+                                double* lev_sq, double* red_sum, double* red_sq, double* pair_sum, double* pair_sq, double* residuals,
+                                int32_t* iters, int32_t* determined, score_samples_batch_info* info) {
+    return abi_call([&] {
+        require(b != nullptr, "score_refine_batch_leverage: null handle");
+        require(poses && (b->U.lms_size == 0 || landmarks), "score_refine_batch_leverage: the points are missing");
+        AbiEnv::Scope scope(b->device, false);
+        score::GblMeasure use{pair_ptr, pair_a, pair_b, lev_sum, lev_sq, red_sum, red_sq, pair_sum, pair_sq};
+        return score::gbs_solve(*b, "score_refine_batch_leverage: ", poses, landmarks, seeds, first_sample, n_samples, rel_tol, max_iters,
+                                block_width, nullptr, nullptr, residuals, iters, determined, info, use);
+    });
+}
+int score_refine_batch_range_variances(score_refine_batch* b, const double* poses, const double* landmarks, const int32_t* pair_ptr,
+                                       const int32_t* pair_a, const int32_t* pair_b, double rel_tol, int32_t max_iters,
+                                       int32_t block_width, double* variances, double* distances, double* residuals, int32_t* iters,
+                                       score_marginals_batch_info* info) {
+    return abi_call([&] {
+        require(b != nullptr, "score_refine_batch_range_variances: null handle");
+        require(poses && (b->U.lms_size == 0 || landmarks), "score_refine_batch_range_variances: the points are missing");
+        AbiEnv::Scope scope(b->device, false);
+        return score::gbl_pair_solve(*b, poses, landmarks, pair_ptr, pair_a, pair_b, rel_tol, max_iters, block_width, variances, distances,
+                                     residuals, iters, info);
     });
 }
 int score_refine_batch_spectrum(score_refine_batch* b, const double* poses, const double* landmarks, int32_t k, double rel_tol,

@@ -15,6 +15,8 @@
 //   k_lv_pair_rhs<DIM>  x = 0, r = b = g_c for the block's live pairs, the done / iteration words as k_mv_rhs sets them
 //   k_lv_pair_dot<DIM>  variances[c] = g_c'x_c from its at most 2 DIM entries, distances[c]
 // No atomics and a fixed order: two calls give the same bits, and a measurement's sums do not depend on block_width.
+// What a lane of these kernels does is stated once, as __device__ functions on a GnView (lv_measure_lane, lv_pair_lane,
+// lv_pair_entry, lv_pair_dot_lane): the kernels here call them for a graph, score_leverage_batch.hpp's for a member of a group.
 //
 // Access pattern of k_lv_measure.  A lane reads delta only at its measurement's unknowns -- pose p >= 1 at DP (p - 1),
 // landmark l at DP (Np - 1) + DIM l, pose 0 nowhere -- ONCE per draw, before the rows are formed.  Consecutive relative
@@ -104,24 +106,28 @@ __device__ __forceinline__ void lv_read(const double* x, long long n, int c, lon
     for (int e = 0; e < K; ++e) d[e] = first >= 0 ? x[c * n + first + e] : 0.0;
 }
 
-// four running sums of one measurement: in before the loop over the draws, out after it
+// four running sums of one measurement: in before the loop over the draws, out after it.  sums: the lane's own entry of the
+// first sum, the other three `stride` apart (consecutive lanes, consecutive entries: a wave's loads and stores coalesce)
 struct LvSums {
     double t1, t2, v1, v2;
-    __device__ __forceinline__ void load(const LvArgs& a, long long m) {
-        t1 = a.sums[m]; t2 = a.sums[a.M + m]; v1 = a.sums[2 * a.M + m]; v2 = a.sums[3 * a.M + m];
+    __device__ __forceinline__ void load(const double* sums, long long stride) {
+        t1 = sums[0]; t2 = sums[stride]; v1 = sums[2 * stride]; v2 = sums[3 * stride];
     }
     __device__ __forceinline__ void add(double t, double v) { t1 += t; t2 += t * t; v1 += v; v2 += v * v; }
-    __device__ __forceinline__ void store(const LvArgs& a, long long m) const {
-        a.sums[m] = t1; a.sums[a.M + m] = t2; a.sums[2 * a.M + m] = v1; a.sums[3 * a.M + m] = v2;
+    __device__ __forceinline__ void store(double* sums, long long stride) const {
+        sums[0] = t1; sums[stride] = t2; sums[2 * stride] = v1; sums[3 * stride] = v2;
     }
 };
 
-// One lane per measurement (numbered as ps_measurement numbers them), then one lane per listed pair.
+// What one lane does for measurement m of the view (numbered as ps_measurement numbers them; m beyond them: nothing) --
+// stated once for a graph (k_lv_measure) and for a member of a group (k_gbl_measure of score_leverage_batch.hpp).  x: column
+// c of the block's solutions from x[c * n] (a member's: from its first unknown); seed: the noise stream; s0: the draw of
+// column 0; live / take: the block's columns and those that enter the sums; sums / stride: as LvSums.
 template <int DIM>
-__global__ __launch_bounds__(kThreads) void k_lv_measure(LvArgs a) {
+__device__ __forceinline__ void lv_measure_lane(const GnView& v, const long long m, const double* x, const long long n, const uint64_t seed,
+                                                const long long s0, const int live, const unsigned take, double* sums, const long long stride) {
     constexpr int PS = DIM == 2 ? 3 : 12, DP = DIM == 2 ? 3 : 6, NR = 2 * DP, NG = 2 * DIM;
-    const GnView& v = a.v;
-    const long long m = (long long)blockIdx.x * kThreads + threadIdx.x;
+    sums += m;
     if (m < v.n_rel) {
         double r[NR], J[NR][NR];
         const double* pi = v.X + PS * (int64_t)v.rel_i[m];
@@ -132,13 +138,13 @@ __global__ __launch_bounds__(kThreads) void k_lv_measure(LvArgs a) {
             gn_rel_jac3(pi, pj, v.rel_t + 3 * m, v.rel_R + 9 * m, v.rel_kappa[m], v.rel_tau[m], r, J, true);
         const long long fi = lv_pose_first<DIM>(v.rel_i[m]), fj = lv_pose_first<DIM>(v.rel_j[m]);
         LvSums S;
-        S.load(a, m);
-        for (int c = 0; c < a.live; ++c) {
-            if (!(a.take >> c & 1)) continue;
+        S.load(sums, stride);
+        for (int c = 0; c < live; ++c) {
+            if (!(take >> c & 1)) continue;
             double d[NR], z[NR];
-            lv_read<DP>(a.x, a.n, c, fi, d);
-            lv_read<DP>(a.x, a.n, c, fj, d + DP);
-            ps_noise_rows<NR>(a.seed, m, a.s0 + c, z);
+            lv_read<DP>(x, n, c, fi, d);
+            lv_read<DP>(x, n, c, fj, d + DP);
+            ps_noise_rows<NR>(seed, m, s0 + c, z);
             double t = 0.0, w = 0.0;
 #pragma unroll
             for (int q = 0; q < NR; ++q) {
@@ -151,7 +157,7 @@ __global__ __launch_bounds__(kThreads) void k_lv_measure(LvArgs a) {
             }
             S.add(t, w);
         }
-        S.store(a, m);
+        S.store(sums, stride);
     } else if (m < v.n_rel + v.n_rng) {
         const int64_t e = m - v.n_rel;
         double J[NG];
@@ -167,20 +173,20 @@ __global__ __launch_bounds__(kThreads) void k_lv_measure(LvArgs a) {
         }
         const long long fa = lv_point_first<DIM>(v.Np, v.rng_a[e]), fb = lv_point_first<DIM>(v.Np, v.rng_b[e]);
         LvSums S;
-        S.load(a, m);
-        for (int c = 0; c < a.live; ++c) {
-            if (!(a.take >> c & 1)) continue;
+        S.load(sums, stride);
+        for (int c = 0; c < live; ++c) {
+            if (!(take >> c & 1)) continue;
             double d[NG];
-            lv_read<DIM>(a.x, a.n, c, fa, d);
-            lv_read<DIM>(a.x, a.n, c, fb, d + DIM);
+            lv_read<DIM>(x, n, c, fa, d);
+            lv_read<DIM>(x, n, c, fb, d + DIM);
             double y = 0.0;
 #pragma unroll
             for (int k = 0; k < NG; ++k) y += J[k] * d[k];
-            const double o = ps_noise(a.seed, m, a.s0 + c, 0) - y;
+            const double o = ps_noise(seed, m, s0 + c, 0) - y;
             S.add(y * y, o * o);
         }
-        S.store(a, m);
-    } else if (m < a.M) {
+        S.store(sums, stride);
+    } else if (m < v.n_rel + v.n_rng + v.n_pri) {
         const int64_t e = m - v.n_rel - v.n_rng;
         const double* l = v.X + PS * v.Np + DIM * (int64_t)v.pri_l[e];
         double r[DIM], sw;
@@ -192,12 +198,12 @@ __global__ __launch_bounds__(kThreads) void k_lv_measure(LvArgs a) {
         }
         const long long fl = lv_point_first<DIM>(v.Np, v.Np + (int64_t)v.pri_l[e]);
         LvSums S;
-        S.load(a, m);
-        for (int c = 0; c < a.live; ++c) {
-            if (!(a.take >> c & 1)) continue;
+        S.load(sums, stride);
+        for (int c = 0; c < live; ++c) {
+            if (!(take >> c & 1)) continue;
             double d[DIM], z[DIM];
-            lv_read<DIM>(a.x, a.n, c, fl, d);
-            ps_noise_rows<DIM>(a.seed, m, a.s0 + c, z);
+            lv_read<DIM>(x, n, c, fl, d);
+            ps_noise_rows<DIM>(seed, m, s0 + c, z);
             double t = 0.0, w = 0.0;
 #pragma unroll
             for (int k = 0; k < DIM; ++k) {
@@ -207,41 +213,57 @@ __global__ __launch_bounds__(kThreads) void k_lv_measure(LvArgs a) {
             }
             S.add(t, w);
         }
-        S.store(a, m);
-    } else if (m < a.M + a.n_pairs) {
-        const long long p = m - a.M;
-        const int64_t ia = a.pa[p], ib = a.pb[p];
-        double u[DIM];
-        (void)lv_pair_direction<DIM>(v, ia, ib, u);
-        const long long fa = lv_point_first<DIM>(v.Np, ia), fb = lv_point_first<DIM>(v.Np, ib);
-        double s1 = a.pair_sums[p], s2 = a.pair_sums[a.n_pairs + p];
-        for (int c = 0; c < a.live; ++c) {
-            if (!(a.take >> c & 1)) continue;
-            double d[NG];
-            lv_read<DIM>(a.x, a.n, c, fa, d);
-            lv_read<DIM>(a.x, a.n, c, fb, d + DIM);
-            double y = 0.0;
-#pragma unroll
-            for (int k = 0; k < DIM; ++k) y += u[k] * d[k];
-#pragma unroll
-            for (int k = 0; k < DIM; ++k) y += -u[k] * d[DIM + k];
-            const double t = y * y;
-            s1 += t;
-            s2 += t * t;
-        }
-        a.pair_sums[p] = s1; a.pair_sums[a.n_pairs + p] = s2;
+        S.store(sums, stride);
     }
 }
 
-// entry i of g of pair p: +u on the translation unknowns of a, -u on those of b, zero elsewhere
+// What one lane does for the listed pair ia - ib of the view: (g'delta)^2 and its square over the taken columns into *s1 / *s2
+// (x, n, live, take: as lv_measure_lane) -- stated once for a graph and for a group (k_gbl_pairs).
 template <int DIM>
-__device__ __forceinline__ double lv_pair_entry(const LvPairArgs& a, long long p, long long i) {
-    const int64_t ia = a.pa[p], ib = a.pb[p];
-    const long long fa = lv_point_first<DIM>(a.v.Np, ia), fb = lv_point_first<DIM>(a.v.Np, ib);
+__device__ __forceinline__ void lv_pair_lane(const GnView& v, const int64_t ia, const int64_t ib, const double* x, const long long n,
+                                             const int live, const unsigned take, double* s1_at, double* s2_at) {
+    constexpr int NG = 2 * DIM;
+    double u[DIM];
+    (void)lv_pair_direction<DIM>(v, ia, ib, u);
+    const long long fa = lv_point_first<DIM>(v.Np, ia), fb = lv_point_first<DIM>(v.Np, ib);
+    double s1 = *s1_at, s2 = *s2_at;
+    for (int c = 0; c < live; ++c) {
+        if (!(take >> c & 1)) continue;
+        double d[NG];
+        lv_read<DIM>(x, n, c, fa, d);
+        lv_read<DIM>(x, n, c, fb, d + DIM);
+        double y = 0.0;
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) y += u[k] * d[k];
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) y += -u[k] * d[DIM + k];
+        const double t = y * y;
+        s1 += t;
+        s2 += t * t;
+    }
+    *s1_at = s1; *s2_at = s2;
+}
+
+// One lane per measurement, then one lane per listed pair.
+template <int DIM>
+__global__ __launch_bounds__(kThreads) void k_lv_measure(LvArgs a) {
+    const long long m = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (m < a.M) {
+        lv_measure_lane<DIM>(a.v, m, a.x, a.n, a.seed, a.s0, a.live, a.take, a.sums, a.M);
+    } else if (m < a.M + a.n_pairs) {
+        const long long p = m - a.M;
+        lv_pair_lane<DIM>(a.v, a.pa[p], a.pb[p], a.x, a.n, a.live, a.take, a.pair_sums + p, a.pair_sums + a.n_pairs + p);
+    }
+}
+
+// entry i of g of the pair ia - ib: +u on the translation unknowns of a, -u on those of b, zero elsewhere
+template <int DIM>
+__device__ __forceinline__ double lv_pair_entry(const GnView& v, const int64_t ia, const int64_t ib, const long long i) {
+    const long long fa = lv_point_first<DIM>(v.Np, ia), fb = lv_point_first<DIM>(v.Np, ib);
     const bool at_a = fa >= 0 && i >= fa && i < fa + DIM, at_b = fb >= 0 && i >= fb && i < fb + DIM;
     if (!at_a && !at_b) return 0.0;
     double u[DIM];
-    (void)lv_pair_direction<DIM>(a.v, ia, ib, u);
+    (void)lv_pair_direction<DIM>(v, ia, ib, u);
     double g = 0.0;
 #pragma unroll
     for (int k = 0; k < DIM; ++k) {
@@ -258,7 +280,7 @@ __global__ __launch_bounds__(kMvThreads) void k_lv_pair_rhs(MvArgs m, LvPairArgs
     const long long i = (long long)blockIdx.x * kMvThreads + t;
     const bool on = c < a.live;
     if (i < a.n) {
-        const double g = on ? lv_pair_entry<DIM>(a, a.c0 + c, i) : 0.0;
+        const double g = on ? lv_pair_entry<DIM>(a.v, a.pa[a.c0 + c], a.pb[a.c0 + c], i) : 0.0;
         m.x[c * a.n + i] = 0.0;
         m.r[c * a.n + i] = g;
         a.b[c * a.n + i] = g;
@@ -270,24 +292,31 @@ __global__ __launch_bounds__(kMvThreads) void k_lv_pair_rhs(MvArgs m, LvPairArgs
     }
 }
 
-// one lane per live pair of the block: variances = g'x over the entries of g in the order (a's, then b's), distances
+// What one lane does for a solved pair ia - ib of the view, its solution in column c of x: *var = g'x over the entries of g in
+// the order (a's, then b's), *dist = |p_a - p_b| -- stated once for a graph and for a group (k_gbl_pair_dot).
 template <int DIM>
-__global__ __launch_bounds__(64) void k_lv_pair_dot(LvPairArgs a) {
-    const int c = threadIdx.x;
-    if (c >= a.live) return;
-    const long long p = a.c0 + c;
-    const int64_t ia = a.pa[p], ib = a.pb[p];
+__device__ __forceinline__ void lv_pair_dot_lane(const GnView& v, const int64_t ia, const int64_t ib, const double* x, const long long n,
+                                                 const int c, double* var, double* dist) {
     double u[DIM], d[2 * DIM];
-    const double rho = lv_pair_direction<DIM>(a.v, ia, ib, u);
-    lv_read<DIM>(a.x, a.n, c, lv_point_first<DIM>(a.v.Np, ia), d);
-    lv_read<DIM>(a.x, a.n, c, lv_point_first<DIM>(a.v.Np, ib), d + DIM);
+    const double rho = lv_pair_direction<DIM>(v, ia, ib, u);
+    lv_read<DIM>(x, n, c, lv_point_first<DIM>(v.Np, ia), d);
+    lv_read<DIM>(x, n, c, lv_point_first<DIM>(v.Np, ib), d + DIM);
     double y = 0.0;
 #pragma unroll
     for (int k = 0; k < DIM; ++k) y += u[k] * d[k];
 #pragma unroll
     for (int k = 0; k < DIM; ++k) y += -u[k] * d[DIM + k];
-    a.var[p] = y;
-    a.dist[p] = rho;
+    *var = y;
+    *dist = rho;
+}
+
+// one lane per live pair of the block
+template <int DIM>
+__global__ __launch_bounds__(64) void k_lv_pair_dot(LvPairArgs a) {
+    const int c = threadIdx.x;
+    if (c >= a.live) return;
+    const long long p = a.c0 + c;
+    lv_pair_dot_lane<DIM>(a.v, a.pa[p], a.pb[p], a.x, a.n, c, a.var + p, a.dist + p);
 }
 
 // The buffers of both calls: they stay with the refinement handle between calls, as PsWork's do (the pairs' grow on demand).

@@ -22,6 +22,8 @@
 //   k_gbs_select        the selected rows of every live (member, slot) into a staging buffer
 // No atomics; every sum has a fixed order; every workgroup belongs to one member and returns at once where that member has
 // no live slot, so a member's numbers are those of a group that holds it alone.
+// What is done with a solved pass is a consumer's, as in ps_solve: GbsMoments (the moments and the selected steps) here,
+// GblMeasure (the per-measurement sums of score_leverage_batch.hpp) there.
 #pragma once
 
 #include <algorithm>
@@ -221,35 +223,143 @@ struct GbsWork {
     }
 };
 
-// The call.  Batch: score_refine_batch (its union, point, blocks and gather, its linear-mode handle, its GbmWork and GbsWork).
-template <class Batch>
-int gbs_solve(Batch& B, const double* poses, const double* landmarks, const uint64_t* seeds, int64_t first_sample, const int32_t* n_samples,
-              const int32_t* var_ptr, const int32_t* vars, double rel_tol, int32_t max_iters, int32_t block_width, double* moments,
-              double* means, double* steps, double* rhs, double* noise, double* residuals, int32_t* iters, int32_t* determined,
-              score_samples_batch_info* info) {
-    const GbUnion& U = B.U;
-    const std::string who = "score_refine_batch_samples: ";
-    const int G = U.count, W = block_width;
-    gbs_check(who, G, n_samples, seeds, var_ptr, first_sample, block_width);
-    if (!(rel_tol > 0.0) || max_iters < 1) throw std::runtime_error(who + "rel_tol must be positive and max_iters >= 1");
-    std::vector<int32_t> sel_ptr(1, 0), sel;
+// what the plan needs of every member (C: the scalar unknowns of its selected variables)
+template <class Columns>
+inline std::vector<GbsShape> gbs_shapes(const GbUnion& U, Columns columns) {
     std::vector<GbsShape> shapes;
     const int64_t dp = U.dp(), d = U.dim;
-    for (int g = 0; g < G; ++g) {
+    for (int g = 0; g < U.count; ++g) {
         const GbMember& M = U.members[(size_t)g];
-        const int32_t cnt = var_ptr[g + 1] - var_ptr[g];
-        if (cnt > 0 && !vars) throw std::runtime_error(who + "vars is null");
-        if (cnt > 0)
-            mv_variable_unknowns(M.Np, M.Nl, U.dp(), U.dim, vars + var_ptr[g], cnt, who + "member " + std::to_string(g) + ": ", sel);
-        if (sel.size() >= ((size_t)1 << 27)) throw std::runtime_error(who + "too many selected unknowns");
-        sel_ptr.push_back((int32_t)sel.size());
         const int64_t rows = U.dim == 2 ? ps_rows<2>(M.n_rel, M.n_rng, M.n_pri) : ps_rows<3>(M.n_rel, M.n_rng, M.n_pri);
-        shapes.push_back(GbsShape{M.n, rows, dp * dp * (M.Np - 1) + d * d * M.Nl, (int64_t)(sel_ptr[(size_t)g + 1] - sel_ptr[(size_t)g])});
+        shapes.push_back(GbsShape{M.n, rows, dp * dp * (M.Np - 1) + d * d * M.Nl, (int64_t)columns(g)});
     }
+    return shapes;
+}
+
+// A pass of gbs_solve as its consumer sees it: the plan and the members' shapes, the pass, its slots, the most live slots of
+// any member, whether any draw of the pass converged (then q.take holds the members' masks on the device), the pass's
+// solutions (slot c from x + c * n) and a host buffer for copies back.
+struct GbsPass {
+    const GbsPlan& plan;
+    const std::vector<GbsShape>& shapes;
+    int k, NV, most_live;
+    bool any;
+    const double* x;
+    std::vector<double>& host;
+};
+
+// one read of the pass's `slots` slices of `stride` doubles, then member g's part of slot c (from first(g), len(g) doubles) to
+// where draw k W + c of the member belongs in the caller's array
+template <class First, class Len>
+inline void gbs_copy_out(const GbsPlan& plan, std::vector<double>& host, hipStream_t st, double* out, const std::vector<int64_t>& off,
+                         const double* src, size_t stride, int slots, int k, First first, Len len) {
+    host.resize((size_t)slots * stride);
+    staged_d2h(host.data(), src, host.size() * sizeof(double), st);
+    for (int g = 0; g < plan.G; ++g)
+        for (int c = 0; c < plan.live(g, k); ++c) {
+            const double* from = host.data() + (size_t)c * stride + (size_t)first(g);
+            std::copy(from, from + len(g), out + off[(size_t)g] + (int64_t)plan.local_draw(g, c, k) * (int64_t)len(g));
+        }
+}
+
+// What score_refine_batch_samples does with a solved pass -- the consumer gbs_solve is given (as PsMoments is ps_solve's): the
+// per-variable moments of every member's converged draws and the selected variables' steps.
+struct GbsMoments {
+    const int32_t* var_ptr; const int32_t* vars;
+    double* moments; double* means; double* steps;
+    std::vector<int32_t> sel_ptr, sel, sel_member;
+    int n_sel = 0;
+    DevBuf<int32_t> d_sel, d_sel_member;
+    DevBuf<double> d_steps;
+    GbsWork* Q = nullptr;
+    const GbUnion* U = nullptr;
+    const int32_t* offsets(int) { return var_ptr; }
+    void check(const GbUnion& Un, const std::string& who, const int32_t*) {
+        U = &Un;
+        sel_ptr.assign(1, 0);
+        for (int g = 0; g < Un.count; ++g) {
+            const GbMember& M = Un.members[(size_t)g];
+            const int32_t cnt = var_ptr[g + 1] - var_ptr[g];
+            if (cnt > 0 && !vars) throw std::runtime_error(who + "vars is null");
+            if (cnt > 0)
+                mv_variable_unknowns(M.Np, M.Nl, Un.dp(), Un.dim, vars + var_ptr[g], cnt, who + "member " + std::to_string(g) + ": ", sel);
+            if (sel.size() >= ((size_t)1 << 27)) throw std::runtime_error(who + "too many selected unknowns");
+            sel_ptr.push_back((int32_t)sel.size());
+        }
+        n_sel = (int)sel.size();
+        sel_member.assign((size_t)n_sel, 0);
+        for (int g = 0; g < Un.count; ++g) std::fill(sel_member.begin() + sel_ptr[(size_t)g], sel_member.begin() + sel_ptr[(size_t)g + 1], g);
+    }
+    int64_t columns(int g) const { return sel_ptr[(size_t)g + 1] - sel_ptr[(size_t)g]; }
+    template <class Batch>
+    void begin(Batch& B, GbsArgs& q, const GbsPlan&, const std::vector<GbsShape>&, int widest, hipStream_t st) {
+        Q = &B.gbs;
+        Q->mom.zero(st); Q->mean.zero(st);
+        {
+            NoArena no_arena;
+            d_sel.alloc((size_t)n_sel); d_sel_member.alloc((size_t)n_sel);
+            d_steps.alloc((size_t)widest * (size_t)std::max(1, n_sel));
+        }
+        staged_h2d(d_sel.d, sel.data(), (size_t)n_sel * sizeof(int32_t), st);
+        staged_h2d(d_sel_member.d, sel_member.data(), (size_t)n_sel * sizeof(int32_t), st);
+        q.mom = Q->mom.d; q.mean = Q->mean.d; q.mom0 = Q->mom0.d;
+        q.sel = d_sel.d; q.sel_member = d_sel_member.d; q.n_sel = n_sel; q.steps = d_steps.d;
+    }
+    template <class Batch>
+    void pass(Batch& B, const GbsArgs& q, const GbsPass& p, hipStream_t st) {
+        const dim3 bt(kThreads);
+        if (p.any) {
+            if (U->dim == 2) hipLaunchKernelGGL(k_gbs_moments<2>, dim3((unsigned)B.n_sblocks), bt, 0, st, q, p.x);
+            else hipLaunchKernelGGL(k_gbs_moments<3>, dim3((unsigned)B.n_sblocks), bt, 0, st, q, p.x);
+        }
+        if (n_sel && steps) {
+            hipLaunchKernelGGL(k_gbs_select, dim3((unsigned)((n_sel + kThreads - 1) / kThreads), (unsigned)p.NV), bt, 0, st, q, p.x);
+            HIP_CHECK(hipGetLastError());
+            gbs_copy_out(p.plan, p.host, st, steps, p.plan.steps_off, d_steps.d, (size_t)n_sel, p.most_live, p.k,
+                         [&](int g) { return sel_ptr[(size_t)g]; }, [&](int g) { return p.shapes[(size_t)g].C; });
+        }
+    }
+    // the running sums of the members that took part, member after member
+    void end(const GbsPlan& plan, const std::vector<GbsShape>& shapes, std::vector<double>& host, hipStream_t st) {
+        const int G = U->count;
+        if (moments) {
+            host.resize((size_t)Q->mom_size);
+            staged_d2h(host.data(), Q->mom.d, host.size() * sizeof(double), st);
+            for (int g = 0; g < G; ++g)
+                if (plan.count[(size_t)g] > 0)
+                    std::copy(host.begin() + (std::ptrdiff_t)Q->mom0_host[(size_t)g], host.begin() + (std::ptrdiff_t)(Q->mom0_host[(size_t)g] + shapes[(size_t)g].moments),
+                              moments + plan.moments_off[(size_t)g]);
+        }
+        if (means) {
+            host.resize((size_t)U->n);
+            staged_d2h(host.data(), Q->mean.d, host.size() * sizeof(double), st);
+            for (int g = 0; g < G; ++g)
+                if (plan.count[(size_t)g] > 0) {
+                    const GbMember& M = U->members[(size_t)g];
+                    std::copy(host.begin() + (std::ptrdiff_t)M.col0, host.begin() + (std::ptrdiff_t)(M.col0 + M.n), means + plan.means_off[(size_t)g]);
+                }
+        }
+    }
+};
+
+// The draws of a call: per member the probe, then pass after pass the noise, J'z, the lock-step solve, the true residuals
+// and the verdict of every (member, draw).  Batch: score_refine_batch (its union, point, blocks and gather, its linear-mode
+// handle, its GbmWork and GbsWork).  What is done with a solved pass is the caller's (use): offsets(G) -- the per-member
+// offsets gbs_check holds to "start at 0, do not decrease" --, check(U, who, n_samples) before any device work,
+// columns(g) for the plan, begin(B, q, plan, shapes, widest, st) once the buffers stand, pass(B, q, GbsPass, st) after the
+// pass's verdicts and end(plan, shapes, host, st) before the clock stops.  score_refine_batch_samples passes GbsMoments,
+// score_refine_batch_leverage (score_leverage_batch.hpp) its per-measurement sums.
+template <class Batch, class Use>
+int gbs_solve(Batch& B, const std::string& who, const double* poses, const double* landmarks, const uint64_t* seeds, int64_t first_sample,
+              const int32_t* n_samples, double rel_tol, int32_t max_iters, int32_t block_width, double* rhs, double* noise,
+              double* residuals, int32_t* iters, int32_t* determined, score_samples_batch_info* info, Use& use) {
+    const GbUnion& U = B.U;
+    const int G = U.count, W = block_width;
+    gbs_check(who, G, n_samples, seeds, use.offsets(G), first_sample, block_width);
+    if (!(rel_tol > 0.0) || max_iters < 1) throw std::runtime_error(who + "rel_tol must be positive and max_iters >= 1");
+    use.check(U, who, n_samples);
+    const std::vector<GbsShape> shapes = gbs_shapes(U, [&](int g) { return use.columns(g); });
     const GbsPlan plan = gbs_plan(G, n_samples, first_sample, block_width, shapes);
-    const int n_sel = (int)sel.size();
-    std::vector<int32_t> sel_member((size_t)n_sel, 0);
-    for (int g = 0; g < G; ++g) std::fill(sel_member.begin() + sel_ptr[(size_t)g], sel_member.begin() + sel_ptr[(size_t)g + 1], g);
     HipBackend& be = B.be();
     hipStream_t st = B.stream();
     const long long n = U.n;
@@ -266,22 +376,16 @@ int gbs_solve(Batch& B, const double* poses, const double* landmarks, const uint
     const size_t zb_per_vector = (size_t)be.H->bs * (size_t)be.n_join_seps;
     K.reserve(widest, (size_t)G, (size_t)n, (size_t)B.n_tiles, (size_t)B.n_ublocks, (size_t)be.n_prec, zb_per_vector, st);
     Q.reserve(B, shapes, noise != nullptr, st);
-    Q.mom.zero(st); Q.mean.zero(st);
-    DevBuf<int32_t> d_cnt_ptr, d_probe_ptr, d_sel, d_sel_member;
+    DevBuf<int32_t> d_cnt_ptr, d_probe_ptr;
     DevBuf<uint64_t> d_seeds;
     DevBuf<uint32_t> d_take;
-    DevBuf<double> d_steps;
     {
         NoArena no_arena;
         d_cnt_ptr.alloc((size_t)G + 1); d_probe_ptr.alloc((size_t)G + 1);
-        d_sel.alloc((size_t)n_sel); d_sel_member.alloc((size_t)n_sel);
         d_seeds.alloc((size_t)G); d_take.alloc((size_t)G);
-        d_steps.alloc((size_t)widest * (size_t)std::max(1, n_sel));
     }
     staged_h2d(d_cnt_ptr.d, plan.cnt_ptr.data(), ((size_t)G + 1) * sizeof(int32_t), st);
     staged_h2d(d_probe_ptr.d, plan.probe_ptr.data(), ((size_t)G + 1) * sizeof(int32_t), st);
-    staged_h2d(d_sel.d, sel.data(), (size_t)n_sel * sizeof(int32_t), st);
-    staged_h2d(d_sel_member.d, sel_member.data(), (size_t)n_sel * sizeof(int32_t), st);
     staged_h2d(d_seeds.d, seeds, (size_t)G * sizeof(uint64_t), st);
     GbmArgs a = B.pcg_args();
     a.tol2 = rel_tol * rel_tol;
@@ -290,8 +394,8 @@ int gbs_solve(Batch& B, const double* poses, const double* landmarks, const uint
     q.d = B.dev(); q.X = B.X.d; q.seeds = d_seeds.d;
     q.blk = Q.blk.d; q.gsz = U.gblk_size; q.noise = noise ? Q.noise.d : nullptr; q.row0 = Q.row0.d; q.rows = Q.rows;
     q.gc_ptr = B.gc_ptr.d; q.gc_slot = B.gc_slot.d; q.tiles = Q.tiles.dev.d; q.b = Q.b.d; q.n = n;
-    q.take = d_take.d; q.mom = Q.mom.d; q.mean = Q.mean.d; q.mom0 = Q.mom0.d;
-    q.sel = d_sel.d; q.sel_member = d_sel_member.d; q.n_sel = n_sel; q.steps = d_steps.d;
+    q.take = d_take.d;
+    use.begin(B, q, plan, shapes, widest, st);
     const dim3 bt(kThreads);
     const size_t nub = (size_t)B.n_ublocks;
     std::vector<int32_t> words;
@@ -338,18 +442,6 @@ int gbs_solve(Batch& B, const double* poses, const double* landmarks, const uint
     double rhs_ms = 0.0;
     a.sel_ptr = d_cnt_ptr.d; a.width = W;
     q.cnt_ptr = d_cnt_ptr.d; q.width = W;
-    // one read of the pass's `slots` slices of `stride` doubles, then member g's part of slot c (from off0[g], `len` doubles)
-    // to where draw k W + c of the member belongs in the caller's array
-    auto copy_out = [&](double* out, const std::vector<int64_t>& off, const double* src, size_t stride, int slots, int k,
-                        auto first, auto len) {
-        host.resize((size_t)slots * stride);
-        staged_d2h(host.data(), src, host.size() * sizeof(double), st);
-        for (int g = 0; g < G; ++g)
-            for (int c = 0; c < plan.live(g, k); ++c) {
-                const double* from = host.data() + (size_t)c * stride + (size_t)first(g);
-                std::copy(from, from + len(g), out + off[(size_t)g] + (int64_t)plan.local_draw(g, c, k) * (int64_t)len(g));
-            }
-    };
     for (int k = 0; k < plan.passes; ++k) {
         const int NV = plan.nv(k);
         int most_live = 0;
@@ -365,12 +457,11 @@ int gbs_solve(Batch& B, const double* poses, const double* landmarks, const uint
         });
         HIP_CHECK(hipGetLastError());
         if (noise)
-            copy_out(noise, plan.noise_off, Q.noise.d, (size_t)Q.rows, most_live, k,
-                     [&](int g) { return Q.row0_host[(size_t)g]; },
-                     [&](int g) { return shapes[(size_t)g].rows; });
+            gbs_copy_out(plan, host, st, noise, plan.noise_off, Q.noise.d, (size_t)Q.rows, most_live, k,
+                         [&](int g) { return Q.row0_host[(size_t)g]; }, [&](int g) { return shapes[(size_t)g].rows; });
         if (rhs)
-            copy_out(rhs, plan.rhs_off, Q.b.d, (size_t)n, most_live, k, [&](int g) { return U.members[(size_t)g].col0; },
-                     [&](int g) { return shapes[(size_t)g].n; });
+            gbs_copy_out(plan, host, st, rhs, plan.rhs_off, Q.b.d, (size_t)n, most_live, k,
+                         [&](int g) { return U.members[(size_t)g].col0; }, [&](int g) { return shapes[(size_t)g].n; });
         HIP_CHECK(sync_stream(st));
         rhs_ms += now_ms() - tb;
         const dim3 gu((unsigned)B.n_ublocks, (unsigned)NV);
@@ -399,37 +490,11 @@ int gbs_solve(Batch& B, const double* poses, const double* landmarks, const uint
             any = any || take[(size_t)g] != 0u;
         }
         pcg_iters += most_steps;
-        if (any) {
-            staged_h2d(d_take.d, take.data(), (size_t)G * sizeof(uint32_t), st);
-            if (U.dim == 2) hipLaunchKernelGGL(k_gbs_moments<2>, dim3((unsigned)B.n_sblocks), bt, 0, st, q, (const double*)K.pcg.x.d);
-            else hipLaunchKernelGGL(k_gbs_moments<3>, dim3((unsigned)B.n_sblocks), bt, 0, st, q, (const double*)K.pcg.x.d);
-        }
-        if (n_sel && steps) {
-            hipLaunchKernelGGL(k_gbs_select, dim3((unsigned)((n_sel + kThreads - 1) / kThreads), (unsigned)NV), bt, 0, st, q, (const double*)K.pcg.x.d);
-            HIP_CHECK(hipGetLastError());
-            copy_out(steps, plan.steps_off, d_steps.d, (size_t)n_sel, most_live, k, [&](int g) { return sel_ptr[(size_t)g]; },
-                     [&](int g) { return shapes[(size_t)g].C; });
-        }
+        if (any) staged_h2d(d_take.d, take.data(), (size_t)G * sizeof(uint32_t), st);
+        use.pass(B, q, GbsPass{plan, shapes, k, NV, most_live, any, (const double*)K.pcg.x.d, host}, st);
         HIP_CHECK(hipGetLastError());
     }
-    // the running sums of the members that took part, member after member
-    if (moments) {
-        host.resize((size_t)Q.mom_size);
-        staged_d2h(host.data(), Q.mom.d, host.size() * sizeof(double), st);
-        for (int g = 0; g < G; ++g)
-            if (plan.count[(size_t)g] > 0)
-                std::copy(host.begin() + (std::ptrdiff_t)Q.mom0_host[(size_t)g], host.begin() + (std::ptrdiff_t)(Q.mom0_host[(size_t)g] + shapes[(size_t)g].moments),
-                          moments + plan.moments_off[(size_t)g]);
-    }
-    if (means) {
-        host.resize((size_t)n);
-        staged_d2h(host.data(), Q.mean.d, host.size() * sizeof(double), st);
-        for (int g = 0; g < G; ++g)
-            if (plan.count[(size_t)g] > 0) {
-                const GbMember& M = U.members[(size_t)g];
-                std::copy(host.begin() + (std::ptrdiff_t)M.col0, host.begin() + (std::ptrdiff_t)(M.col0 + M.n), means + plan.means_off[(size_t)g]);
-            }
-    }
+    use.end(plan, shapes, host, st);
     HIP_CHECK(sync_stream(st));
     const double t2 = now_ms();
     double worst = 0.0;
@@ -444,3 +509,4 @@ int gbs_solve(Batch& B, const double* poses, const double* landmarks, const uint
 }
 
 }  // namespace score
+

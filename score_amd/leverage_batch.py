@@ -1,0 +1,295 @@
+"""Range leverage and predicted range variances of many graphs at once (include/score_leverage_batch.h,
+csrc/score_leverage_batch.hpp).
+
+``range_leverage`` / ``predicted_range_variances`` take one graph, build one refinement handle and run block solves whose
+launches are latency-bound on a small world.  The questions they answer are study questions -- over 64 generated worlds,
+which share of the ranges is uncontrolled?  what variance does a candidate beacon-pose range have in each world? -- so
+``range_leverage_batch`` and ``predicted_range_variances_batch`` hand the graphs to the device as groups, as
+``posterior_samples_batch`` does: one union vector carries one draw (one pair's column) of every member.  Graph i's draws
+are those of ``range_leverage(..., seed=seed + i)`` on it alone (the same noise stream, the same right-hand sides), its sums
+those of that call up to the rounding of the two iterations.
+
+``RefineBatchHandle.leverage`` / ``.range_variances`` are the raw calls on a kept group handle, so a study refines and
+analyses with one create; ``refine_estimate_batch(..., leverage=S)`` does exactly that.  ``engine="python"`` is the single
+functions' python engine graph by graph.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+
+from .bindings import LEVERAGE_BATCH, ScoreMarginalsBatchInfo, ScoreSamplesBatchInfo, _u64p, bind, ptr, steps_and_converged
+from .leverage import (Leverage, PredictedRanges, _check_block, _singular, measurement_counts, pair_ids, predicted_range_variances,
+                       range_leverage)
+from .marginals import MAX_BLOCK_WIDTH, _problem_and_point
+from .samples_batch import _check_draw_arguments, _per_member, _seeds_of
+from .solver import _i32p
+
+# the symbols include/score_leverage_batch.h declares
+LEVERAGE_BATCH_SYMBOLS = list(LEVERAGE_BATCH)
+SUMS = ("lev_sum", "lev_sq", "red_sum", "red_sq")
+
+
+def _flat_pairs(pairs_per_member, count: int):
+    """(per member (C_g, 2) int32 ids, pair_ptr, pair_a, pair_b) of one list of id pairs (or None) per member."""
+    if len(pairs_per_member) != count:
+        raise ValueError(f"one list of pairs per member expected ({count}), got {len(pairs_per_member)}")
+    ids = [np.zeros((0, 2), dtype=np.int32) if p is None else np.asarray(p, dtype=np.int32).reshape(-1, 2) for p in pairs_per_member]
+    pair_ptr = np.concatenate([[0], np.cumsum([len(p) for p in ids])]).astype(np.int32)
+    flat = np.concatenate(ids) if ids else np.zeros((0, 2), dtype=np.int32)
+    return ids, pair_ptr, np.ascontiguousarray(flat[:, 0]), np.ascontiguousarray(flat[:, 1])
+
+
+def batch_leverage(handle, points, pairs_per_member, n_samples, seeds, first_sample=0, rel_tol=1e-10, max_iters=4000,
+                   block_width=MAX_BLOCK_WIDTH):
+    """``score_refine_batch_leverage`` as it is, on a ``RefineBatchHandle``: ``points`` in the problems' own form,
+    ``pairs_per_member`` the member-local variable id pairs of every member (None or an empty list: none), ``n_samples`` and
+    ``seeds`` an integer or one per member (a member with 0 draws takes no part).  Returns (return code, one dict per member,
+    the call's info record).  A member's dict has the keys ``LeverageHandle.leverage`` returns -- ``rc`` is 0 iff all ITS
+    draws converged, ``info`` the call's record with the member's own ``samples`` and ``batches`` -- plus ``determined``."""
+    probs = handle.probs
+    G = len(probs)
+    if len(points) != G:
+        raise ValueError("one point per member expected")
+    counts = [int(s) for s in _per_member(n_samples, G, "n_samples")]
+    keys = [int(s) & 0xFFFFFFFFFFFFFFFF for s in _per_member(seeds, G, "seeds")]
+    lib = bind(handle.lib, LEVERAGE_BATCH)
+    _, poses, lms = handle._flat_points(points)
+    ids, pair_ptr, pa, pb = _flat_pairs(pairs_per_member, G)
+    on = [max(s, 0) for s in counts]  # (a negative count is the library's error to report)
+    n_meas = [sum(measurement_counts(p)) for p in probs]
+    room = sum(m for m, s in zip(n_meas, on) if s)
+    sums = {k: np.zeros(max(1, room)) for k in SUMS}
+    psum, psq = np.zeros(max(1, len(pa))), np.zeros(max(1, len(pa)))
+    total = sum(on)
+    res, its = np.zeros(max(1, total)), np.zeros(max(1, total), dtype=np.int32)
+    det = np.zeros(G, dtype=np.int32)
+    n_arr = np.ascontiguousarray(counts, dtype=np.int32)
+    seed_arr = np.ascontiguousarray(keys, dtype=np.uint64)
+    info = ScoreSamplesBatchInfo()
+    rc = lib.score_refine_batch_leverage(handle.h, ptr(poses), ptr(lms), ptr(seed_arr, _u64p), int(first_sample), ptr(n_arr, _i32p),
+                                         pair_ptr.ctypes.data_as(_i32p), ptr(pa, _i32p), ptr(pb, _i32p), float(rel_tol), int(max_iters),
+                                         int(block_width), ptr(sums["lev_sum"]), ptr(sums["lev_sq"]), ptr(sums["red_sum"]),
+                                         ptr(sums["red_sq"]), ptr(psum), ptr(psq), ptr(res), ptr(its, _i32p), ptr(det, _i32p),
+                                         C.byref(info))
+    if rc < 0:
+        raise RuntimeError(f"score_refine_batch_leverage failed: {lib.score_last_error().decode()}")
+    rec = info.as_dict()
+    out, at_m, at_d = [], 0, 0
+    for g in range(G):
+        S, M = on[g], n_meas[g]
+        iterations, converged = steps_and_converged(its[at_d : at_d + S])
+        member = {k: (sums[k][at_m : at_m + M].copy() if S else np.zeros(M)) for k in SUMS}
+        member.update({
+            "pair_sum": psum[pair_ptr[g] : pair_ptr[g + 1]].copy(), "pair_sq": psq[pair_ptr[g] : pair_ptr[g + 1]].copy(),
+            "residuals": res[at_d : at_d + S].copy(), "iterations": iterations, "converged": converged, "determined": int(det[g]),
+            "rc": 0 if np.all(converged) else 1, "info": dict(rec, samples=S, batches=-(-S // int(block_width))),
+        })
+        at_m += M if S else 0
+        at_d += S
+        out.append(member)
+    return rc, out, rec
+
+
+def batch_range_variances(handle, points, pairs_per_member, rel_tol=1e-10, max_iters=4000, block_width=MAX_BLOCK_WIDTH):
+    """``score_refine_batch_range_variances`` as it is, on a ``RefineBatchHandle``.  Returns (return code, one dict per
+    member with the keys of ``LeverageHandle.range_variances`` except ``solutions`` -- ``rc`` is 0 iff all ITS columns
+    converged, ``info`` the call's record with the member's own ``columns`` --, the call's info record)."""
+    probs = handle.probs
+    G = len(probs)
+    if len(points) != G:
+        raise ValueError("one point per member expected")
+    lib = bind(handle.lib, LEVERAGE_BATCH)
+    _, poses, lms = handle._flat_points(points)
+    ids, pair_ptr, pa, pb = _flat_pairs(pairs_per_member, G)
+    n = max(1, len(pa))
+    var, dist, res, its = np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.int32)
+    info = ScoreMarginalsBatchInfo()
+    rc = lib.score_refine_batch_range_variances(handle.h, ptr(poses), ptr(lms), pair_ptr.ctypes.data_as(_i32p), ptr(pa, _i32p),
+                                                ptr(pb, _i32p), float(rel_tol), int(max_iters), int(block_width), ptr(var), ptr(dist),
+                                                ptr(res), ptr(its, _i32p), C.byref(info))
+    if rc < 0:
+        raise RuntimeError(f"score_refine_batch_range_variances failed: {lib.score_last_error().decode()}")
+    rec = info.as_dict()
+    out = []
+    for g in range(G):
+        cut = slice(int(pair_ptr[g]), int(pair_ptr[g + 1]))
+        iterations, converged = steps_and_converged(its[cut])
+        out.append({"rc": 0 if np.all(converged) else 1, "variances": var[cut].copy(), "distances": dist[cut].copy(),
+                    "residuals": res[cut].copy(), "iterations": iterations, "converged": converged,
+                    "info": dict(rec, columns=len(ids[g]))})
+    return rc, out, rec
+
+
+def _failed(who, i, failed, total, what, max_iters):
+    return _singular(f"{who}: graph {i}", failed, total, what, max_iters)
+
+
+def group_leverage(handle, probs, points, names, indices, number, counts, seeds, first_sample=0, rel_tol=1e-10, max_iters=4000,
+                   block_width=MAX_BLOCK_WIDTH):
+    """The leverages of one group on its ``RefineBatchHandle``: ``names[k]`` the name pairs of member k (or None),
+    ``indices[k]`` its graph's number in the caller's list (for messages).  Returns ``(Leverage, info)`` per member."""
+    ids = [pair_ids(p, nm, f"range_leverage_batch: graph {i}") if nm is not None else None for p, nm, i in zip(probs, names, indices)]
+    _, members, rec = handle.leverage(points, ids, counts, seeds, first_sample, rel_tol, max_iters, block_width)
+    out = []
+    for prob, point, nm, i, S, m in zip(probs, points, names, indices, counts, members):
+        failed = int(np.count_nonzero(~m["converged"]))
+        if failed:
+            raise _failed("range_leverage_batch", i, failed, S, "draws", max_iters)
+        info = {"pcg_iters": int(rec["pcg_iters"]), "batches": int(m["info"]["batches"]), "setup_ms": float(rec["setup_ms"]),
+                "rhs_ms": float(rec["rhs_ms"]), "solve_ms": float(rec["solve_ms"]), "iterations": m["iterations"],
+                "residuals": m["residuals"], "engine": "device", "group": number, "passes": int(rec["passes"]),
+                "determined": m["determined"]}
+        out.append((Leverage(prob, point, m, S, nm), info))
+    return out
+
+
+def _groups(datas, results, range_weights, loop_closure_weights, who):
+    """{dimension: [(graph number, problem, point)]} as ``posterior_samples_batch`` groups its graphs."""
+    from .refine_batch import _weights_of
+
+    datas, results = list(datas), list(results)
+    if len(datas) != len(results):
+        raise ValueError(f"one estimate per graph expected: {len(datas)} graphs, {len(results)} estimates")
+    rws = _weights_of(range_weights, len(datas), "range_weights")
+    lws = _weights_of(loop_closure_weights, len(datas), "loop_closure_weights")
+    groups: dict = {}
+    for i, (data, res) in enumerate(zip(datas, results)):
+        if data.dimension not in (2, 3):
+            raise ValueError(f"graph {i}: dimension must be 2 or 3")
+        try:
+            prob, point = _problem_and_point(data, res, rws[i], lws[i])
+        except ValueError as e:
+            raise ValueError(f"graph {i}: {str(e).replace('marginal_covariances', who)}") from None
+        if prob.n == 0:
+            raise ValueError(f"graph {i}: the graph has no unknowns")
+        groups.setdefault(data.dimension, []).append((i, prob, point))
+    return datas, results, rws, lws, groups
+
+
+def _pairs_of(pairs, count: int) -> list:
+    """One entry per graph: None (no pairs) or that graph's list of name pairs."""
+    if pairs is None:
+        return [None] * count
+    pairs = list(pairs)
+    if len(pairs) != count:
+        raise ValueError(f"pairs: one entry per graph expected ({count}), got {len(pairs)}")
+    return pairs
+
+
+def _ids_of(groups, names, who) -> dict:
+    """{graph number: (C, 2) variable ids or None} of the graphs' name pairs; a bad pair raises with ``graph i:`` in front."""
+    return {i: pair_ids(prob, names[i], f"{who}: graph {i}") if names[i] is not None else None
+            for members in groups.values() for i, prob, _ in members}
+
+
+def _chunks(groups, max_group):
+    number = 0
+    for dim in sorted(groups):
+        members = groups[dim]
+        for c0 in range(0, len(members), int(max_group)):
+            yield number, members[c0 : c0 + int(max_group)]
+            number += 1
+
+
+def range_leverage_batch(datas, results, n_samples=256, seed=0, first_sample: int = 0, pairs=None, range_weights=None,
+                         loop_closure_weights=None, rel_tol: float = 1e-10, max_iters: int = 4000,
+                         block_width: int = MAX_BLOCK_WIDTH, engine: str = "device", lib_path: Optional[str] = None,
+                         solver_settings: Optional[dict] = None, max_group: int = 64):
+    """``range_leverage`` for many graphs at once: ``datas`` and ``results`` graph by graph, ``pairs`` None or a list with one
+    entry per graph (None or a list of name pairs), ``range_weights`` / ``loop_closure_weights`` lists with one entry per
+    graph.  ``n_samples``: an integer or one per graph.  ``seed``: a list with one seed per graph, or an integer -- graph i then
+    draws from the stream of ``seed + i`` (``posterior_samples_batch``'s rule), so its draws are those of
+    ``range_leverage(..., seed=seed + i)``.  The graphs are grouped by dimension, in chunks of at most ``max_group``, as
+    ``posterior_samples_batch`` groups them; each group is one device handle and one ``score_refine_batch_leverage`` call
+    (``engine="device"``) or ``range_leverage(engine="python")`` graph by graph.  Returns a list of ``(Leverage, info)`` in input
+    order: per graph what ``range_leverage`` returns, plus ``group``, ``passes`` and ``determined`` on the device.  Draws that do
+    not converge raise RuntimeError naming the first such graph."""
+    from .refine_batch import RefineBatchHandle
+
+    _check_block(block_width, rel_tol, max_iters, engine)
+    if int(max_group) < 1:
+        raise ValueError("max_group must be at least 1")
+    datas, results = list(datas), list(results)
+    counts = _per_member(n_samples, len(datas), "n_samples")
+    if datas:
+        _check_draw_arguments(counts, first_sample, block_width, rel_tol, max_iters)
+    counts = [int(s) for s in counts]
+    seeds = _seeds_of(seed, len(datas))
+    names = _pairs_of(pairs, len(datas))
+    datas, results, rws, lws, groups = _groups(datas, results, range_weights, loop_closure_weights, "range_leverage")
+    _ids_of(groups, names, "range_leverage_batch")  # (the pairs' errors before any work)
+    out: list = [None] * len(datas)
+    if engine == "python":
+        for i, (data, res) in enumerate(zip(datas, results)):
+            try:
+                out[i] = range_leverage(data, res, counts[i], seeds[i], int(first_sample), names[i], rws[i], lws[i], rel_tol, max_iters,
+                                        int(block_width), engine="python")
+            except RuntimeError as e:
+                raise RuntimeError(str(e).replace("range_leverage:", f"range_leverage_batch: graph {i}:")) from None
+        return out
+    for number, chunk in _chunks(groups, max_group):
+        idx, probs, points = ([m[k] for m in chunk] for k in range(3))
+        with RefineBatchHandle(probs, lib_path, solver_settings) as h:
+            got = group_leverage(h, probs, points, [names[i] for i in idx], idx, number, [counts[i] for i in idx],
+                                 [seeds[i] for i in idx], int(first_sample), rel_tol, max_iters, int(block_width))
+        for i, g in zip(idx, got):
+            out[i] = g
+    return out
+
+
+def predicted_range_variances_batch(datas, results, pairs, range_weights=None, loop_closure_weights=None, rel_tol: float = 1e-10,
+                                    max_iters: int = 4000, block_width: int = MAX_BLOCK_WIDTH, engine: str = "device",
+                                    lib_path: Optional[str] = None, solver_settings: Optional[dict] = None, max_group: int = 64):
+    """``predicted_range_variances`` for many graphs at once: ``pairs`` is one list of name pairs per graph; a graph may list
+    none (its ``PredictedRanges`` is empty).  Grouped as ``range_leverage_batch``; each group is one device handle and one
+    ``score_refine_batch_range_variances`` call (``engine="device"``) or the dense solve graph by graph (``engine="python"``).
+    Returns a list of ``(PredictedRanges, info)`` in input order: per graph what ``predicted_range_variances`` returns, plus
+    ``group`` and ``passes`` on the device.  A column that does not converge raises RuntimeError naming the first such
+    graph."""
+    from .refine_batch import RefineBatchHandle
+
+    _check_block(block_width, rel_tol, max_iters, engine)
+    if int(max_group) < 1:
+        raise ValueError("max_group must be at least 1")
+    datas = list(datas)
+    names = [[tuple(p) for p in nm] if nm is not None else [] for nm in _pairs_of(pairs, len(datas))]
+    datas, results, rws, lws, groups = _groups(datas, results, range_weights, loop_closure_weights, "predicted_range_variances")
+    ids_of = _ids_of(groups, names, "predicted_range_variances_batch")  # (the pairs' errors before any work)
+    out: list = [None] * len(datas)
+
+    def empty():
+        return (PredictedRanges([], np.zeros(0), np.zeros(0)),
+                {"pcg_iters": 0, "batches": 0, "setup_ms": 0.0, "solve_ms": 0.0, "iterations": np.zeros(0, dtype=np.int64),
+                 "residuals": np.zeros(0), "engine": engine})
+
+    if engine == "python":
+        for i, (data, res) in enumerate(zip(datas, results)):
+            if not names[i]:
+                out[i] = empty()
+                continue
+            try:
+                out[i] = predicted_range_variances(data, res, names[i], rws[i], lws[i], rel_tol, max_iters, int(block_width), engine="python")
+            except RuntimeError as e:
+                raise RuntimeError(str(e).replace("predicted_range_variances:", f"predicted_range_variances_batch: graph {i}:")) from None
+        return out
+    for number, chunk in _chunks(groups, max_group):
+        idx, probs, points = ([m[k] for m in chunk] for k in range(3))
+        ids = [ids_of[i] for i in idx]
+        with RefineBatchHandle(probs, lib_path, solver_settings) as h:
+            _, members, rec = h.range_variances(points, ids, rel_tol, max_iters, int(block_width))
+        for i, m in zip(idx, members):
+            failed = int(np.count_nonzero(~m["converged"]))
+            if failed:
+                raise _failed("predicted_range_variances_batch", i, failed, len(names[i]), "columns", max_iters)
+            info = {"pcg_iters": int(rec["pcg_iters"]), "batches": -(-len(names[i]) // int(block_width)), "setup_ms": float(rec["setup_ms"]),
+                    "solve_ms": float(rec["solve_ms"]), "iterations": m["iterations"], "residuals": m["residuals"], "engine": engine,
+                    "group": number, "passes": int(rec["passes"])}
+            out[i] = (PredictedRanges(names[i], m["distances"], m["variances"]), info)
+    return out
+
+
+__all__ = ["range_leverage_batch", "predicted_range_variances_batch", "batch_leverage", "batch_range_variances", "group_leverage",
+           "LEVERAGE_BATCH_SYMBOLS"]

@@ -18,7 +18,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from .bindings import REFINE_BATCH, REFINE_ROBUST_BATCH, ScoreRefineRobustInfo, ScoreRefineRobustSettings, bind, ptr
+from .bindings import LEVERAGE_BATCH, REFINE_BATCH, REFINE_ROBUST_BATCH, ScoreRefineRobustInfo, ScoreRefineRobustSettings, bind, ptr
 from .native import ScoreGraph, score_graph_struct
 from .refine import (GRADIENT, SOLVE, _as_results, _attempt, _gradient, _Handle, _Member, _native_info, _point_arrays, _point_from,
                      _problem_and_point as _problem_of, refine_estimate)
@@ -97,7 +97,7 @@ class RefineBatchHandle(_Handle):
     """A group handle (``score_refine_batch_create``) over ``probs`` (all of one dimension, every one with unknowns); ``run``
     takes and returns points in the problems' own form (``_Problem``: packed unknowns; ``_Problem3D``: (R, t, lm))."""
 
-    headers = (REFINE_BATCH,)
+    headers = (REFINE_BATCH, LEVERAGE_BATCH)
     destroy = "score_refine_batch_destroy"
 
     def __init__(self, probs: Sequence, lib_path: Optional[str] = None, solver_settings: Optional[dict] = None):
@@ -169,6 +169,25 @@ class RefineBatchHandle(_Handle):
         return batch_draws(self, points, ids_per_member, n_samples, seeds, first_sample, rel_tol, max_iters, block_width, with_rhs,
                            with_noise)
 
+    def leverage(self, points, pairs_per_member, n_samples, seeds, first_sample: int = 0, rel_tol: float = 1e-10,
+                 max_iters: int = 4000, block_width: int = 16):
+        """``score_refine_batch_leverage`` at ``points`` (include/score_leverage_batch.h): the leverage and redundancy sums of
+        every member's measurements over ``n_samples`` draws (an integer or one per member; 0: the member takes no part) from
+        the streams of ``seeds``, and of the member-local variable id pairs ``pairs_per_member`` (None or empty: none).
+        Returns (return code, per member the dict of ``LeverageHandle.leverage`` plus ``determined``, the call's info
+        record); the handle is left as it was found."""
+        from .leverage_batch import batch_leverage
+
+        return batch_leverage(self, points, pairs_per_member, n_samples, seeds, first_sample, rel_tol, max_iters, block_width)
+
+    def range_variances(self, points, pairs_per_member, rel_tol: float = 1e-10, max_iters: int = 4000, block_width: int = 16):
+        """``score_refine_batch_range_variances`` at ``points``: the exact variance g'H^-1 g of every listed pair of every
+        member.  Returns (return code, per member the dict of ``LeverageHandle.range_variances`` without ``solutions``, the
+        call's info record); the handle is left as it was found."""
+        from .leverage_batch import batch_range_variances
+
+        return batch_range_variances(self, points, pairs_per_member, rel_tol, max_iters, block_width)
+
     def _robust(self):
         """The library with the calls of include/score_refine_robust_batch.h bound."""
         return bind(self.lib, REFINE_ROBUST_BATCH)
@@ -226,7 +245,8 @@ class RefineBatchHandle(_Handle):
 
 def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-10, range_weights=None, loop_closure_weights=None,
                           engine: str = "native", lib_path: Optional[str] = None, solver_settings: Optional[dict] = None,
-                          max_group: int = 64, marginals=None, samples=None, samples_seed: int = 0):
+                          max_group: int = 64, marginals=None, samples=None, samples_seed: int = 0, leverage=None,
+                          leverage_seed: int = 0):
     """``refine_estimate`` for many graphs at once: ``datas`` and ``results`` member by member, ``range_weights`` /
     ``loop_closure_weights`` lists with one entry (an array as ``refine_estimate`` takes it, or None) per member -- they only
     scale precisions.  The members are grouped by dimension, in chunks of at most ``max_group``, each group one device handle
@@ -240,7 +260,13 @@ def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-1
     ``samples``: a number of draws S -- every group's handle then also draws S posterior samples of every member at the refined
     points (``posterior_samples_batch``'s call on the same handle: default variables, graph i from the stream of
     ``samples_seed + i``), and ``info["samples"]`` is that graph's ``(Samples, samples_info)`` (None for a graph without
-    unknowns).  Without the keyword nothing changes."""
+    unknowns).  Without the keyword nothing changes.
+    ``leverage``: a number of draws S -- every group's handle then also forms the leverage and redundancy of every member's
+    measurements at the refined points (``range_leverage_batch``'s call on the same handle: no pairs, graph i from the stream
+    of ``leverage_seed + i``; ``engine="python"``: ``range_leverage``'s python engine), and ``info["leverage"]`` is that
+    graph's ``(Leverage, leverage_info)`` (None for a graph without unknowns).  Without the keyword nothing changes."""
+    from .leverage import range_leverage
+    from .leverage_batch import group_leverage
     from .marginals import _select
     from .marginals_batch import _variables_of, group_marginals
     from .samples_batch import _check_draw_arguments, group_samples
@@ -259,6 +285,9 @@ def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-1
     with_samples = samples is not None and samples is not False
     if with_samples:
         _check_draw_arguments([samples], 0, 16, 1e-10, 4000)
+    with_leverage = leverage is not None and leverage is not False
+    if with_leverage:
+        _check_draw_arguments([leverage], 0, 16, 1e-10, 4000)
     out: list = [None] * len(datas)
     groups: dict = {}
     sel_of: dict = {}
@@ -274,6 +303,8 @@ def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-1
                 out[i][1]["marginals"] = None
             if with_samples:
                 out[i][1]["samples"] = None
+            if with_leverage:
+                out[i][1]["leverage"] = None
             continue
         if with_marginals:  # (the selection's errors before any work)
             try:
@@ -298,13 +329,24 @@ def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-1
                 return group_samples(handle, probs, pts, ests, [draw_sel_of[i] for i in idx], idx, number, [int(samples)] * len(idx),
                                      [int(samples_seed) + i for i in idx], engine=which)
 
-            drawn = None
+            def leverages(handle, pts, costs):
+                """(Leverage, info) per member at the refined points"""
+                if handle is None:
+                    return [range_leverage(datas[i], _as_results(p, pt, results[i], f), int(leverage), int(leverage_seed) + i,
+                                           range_weights=rws[i], loop_closure_weights=lws[i], engine="python")
+                            for p, pt, i, f in zip(probs, pts, idx, costs)]
+                return group_leverage(handle, probs, pts, [None] * len(idx), idx, number, [int(leverage)] * len(idx),
+                                      [int(leverage_seed) + i for i in idx])
+
+            drawn = levs = None
             if engine == "python":
                 pts, S, rounds = _python_lock_step(probs, points, max_iters, tol)
                 if with_marginals:
                     covs = group_marginals(None, probs, pts, sels, [m[0] for m in chunk], number, engine="python")
                 if with_samples:
                     drawn = draws(None, pts, [s.f for s in S], "python")
+                if with_leverage:
+                    levs = leverages(None, pts, [s.f for s in S])
                 infos = [{"cost_initial": s.cost_initial, "cost_final": s.f, "iterations": s.iterations, "grad_inf": s.gnorm,
                           "linear_solver": "scipy", "engine": "python", "pcg_iters": 0, "linear_solves": s.linear_solves} for s in S]
             else:
@@ -314,6 +356,8 @@ def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-1
                         covs = group_marginals(h, probs, pts, sels, [m[0] for m in chunk], number)
                     if with_samples:
                         drawn = draws(h, pts, [r["cost_final"] for r in raw], "device")
+                    if with_leverage:
+                        levs = leverages(h, pts, [r["cost_final"] for r in raw])
                 rounds = max(r["linear_solves"] for r in raw)
                 infos = [_native_info(r) for r in raw]
             for k, ((i, prob, _), pt, info) in enumerate(zip(chunk, pts, infos)):
@@ -322,6 +366,8 @@ def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-1
                     info["marginals"] = covs[k]
                 if with_samples:
                     info["samples"] = drawn[k]
+                if with_leverage:
+                    info["leverage"] = levs[k]
                 out[i] = (_as_results(prob, pt, results[i], info["cost_final"]), info)
             number += 1
     return out
