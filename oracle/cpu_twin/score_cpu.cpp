@@ -481,6 +481,15 @@ struct CpuBackend {
             if (out && len > 0) out[0] = 0.0;
             return 1;
         }
+        else if (nm == "Aval") { src = h.A.val.data(); sz = (int64_t)h.A.val.size(); }  // the equilibrated problem as the loops read it
+        else if (nm == "G2val") { src = h.G2.val.data(); sz = (int64_t)h.G2.val.size(); }
+        else if (nm == "qs") { src = h.q.data(); sz = h.n_tot; }
+        else if (nm == "bs") { src = h.b.data(); sz = h.m_tot; }
+        else if (nm == "Aptr" || nm == "Acol" || nm == "G2ptr" || nm == "G2col" || nm == "G2split") {
+            const std::vector<int32_t>& v = nm == "Aptr" ? h.A.ptr : nm == "Acol" ? h.A.col : nm == "G2ptr" ? h.G2.ptr : nm == "G2col" ? h.G2.col : h.g2_split;
+            if (out) for (int64_t i = 0; i < (int64_t)v.size() && i < len; ++i) out[i] = (double)v[(size_t)i];
+            return (int64_t)v.size();
+        }
         else if (nm == "Kptr" || nm == "Kcol") {  // pattern of the stored K (a replicated problem: replica 0 + tail rows)
             const std::vector<int32_t>& v = nm == "Kptr" ? h.K.ptr : h.K.col;
             if (out) for (int64_t i = 0; i < (int64_t)v.size() && i < len; ++i) out[i] = (double)v[(size_t)i];

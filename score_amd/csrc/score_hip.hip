@@ -1071,6 +1071,11 @@ struct HipBackend {
     const double* last_rz = nullptr;  // r'z partials / direction of the pending end-of-PCG update
     const double* last_p = nullptr;
     const double* dbg_p = nullptr;   // the buffer the last queued iteration left its last direction in (score_debug_get "p")
+    // what the Newton polish leaves for score_debug_get (score_inspect.hpp), all from values the host holds anyway:
+    const double* dbg_eval_x = nullptr;      // [u | nu] buffer of the last evaluation ("polish_u" / "polish_nu")
+    std::vector<double> dbg_eval_F, dbg_eval_gn;  // per problem: F and max |g_i| / D_i as the last evaluation collected them
+    static constexpr int kTraceFields = 14;
+    std::vector<double> polish_trace;        // kTraceFields per Newton iteration and problem of the last polish_lockstep call
     double* h_pres = nullptr;  // pinned
     double* h_dres = nullptr;
     int n_cone_blocks = 0, n_prec = 0;  // n_prec: work items of the ACTIVE preconditioner launch (split or not)
@@ -3720,6 +3725,7 @@ struct HipBackend {
     // queue the evaluation of F and the gradient at Xbuf for the problems not skipped
     void newton_eval_enqueue(double* Xbuf) {
         PolishArgs pa = polish_args(Xbuf);
+        dbg_eval_x = Xbuf;
         hipLaunchKernelGGL(k_newton_cone_b, dim3(n_cone_blocks), dim3(kThreads), 0, stream, pa, batch_tables());
         SpmvArgs ga = spmv_args(G2, Xbuf);
         // (-g goes to its own buffer, not to the PCG residual r)
@@ -3736,6 +3742,7 @@ struct HipBackend {
     void newton_eval_collect(const std::vector<char>& which, std::vector<double>& F, std::vector<double>& gn) {
         const HostSystem& h = *H;
         if ((int)act_flips.size() != h.count) act_flips.assign((size_t)h.count, 0.0);
+        if ((int)dbg_eval_F.size() != h.count) { dbg_eval_F.assign((size_t)h.count, 0.0); dbg_eval_gn.assign((size_t)h.count, 0.0); }
         for (int p = 0; p < h.count; ++p) {
             if (!which[p]) continue;
             double f = 0.0, gmax = 0.0;
@@ -3749,6 +3756,7 @@ struct HipBackend {
             }
             F[p] = f;
             gn[p] = gmax;
+            dbg_eval_F[(size_t)p] = f; dbg_eval_gn[(size_t)p] = gmax;
         }
     }
     void newton_eval_batch(double* Xbuf, const std::vector<char>& which, std::vector<double>& F, std::vector<double>& gn) {
@@ -3856,6 +3864,7 @@ struct HipBackend {
                          int* newton_iters, int* cg_used, const std::vector<double>* dual_scale) {
         *newton_iters = 0; *cg_used = 0;
         pcg_used_total = 0;
+        polish_trace.clear();
         const double t_start = now_ms();
         release_prequeued();  // (nothing is pending between solves: every exit below releases; this is the belt to those braces)
         hassemble_queued = false;
@@ -3888,6 +3897,7 @@ struct HipBackend {
         std::vector<char> live(count), stalled(count, 0);
         int it = 0;
         const int it_max = newton_limit > 0 ? std::min(50, newton_limit) : 50;
+        polish_trace.reserve((size_t)kTraceFields * count * it_max);  // (once per call, kept between calls: no allocation inside the loop)
         for (; it < it_max; ++it) {
             any = false;
             for (int p = 0; p < count; ++p) { live[p] = part[p] && !stalled[p] && gn[p] > tolp[p]; any = any || live[p]; }
@@ -3919,6 +3929,15 @@ struct HipBackend {
                 int nre = 0;
                 for (int p = 0; p < count; ++p) if (live[p]) { mx = std::max(mx, act_flips[p]); nre += c_reref[p]; }
                 std::fprintf(stderr, "[score] newton it %d: active-set flips since the last factorisation (max over live problems) %.0f -> %d problems refactor\n", it + 1, mx, nre);
+            }
+            // the iteration's record for score_debug_get "polish_trace" (score_inspect.hpp names the fields), opened before the
+            // upload returns c_reref to "no"; the room was reserved when the call began
+            const size_t tr0 = polish_trace.size();
+            polish_trace.resize(tr0 + (size_t)kTraceFields * count, 0.0);
+            double* tr = polish_trace.data() + tr0;
+            for (int p = 0; p < count; ++p) {
+                double* o = tr + (size_t)kTraceFields * p;
+                o[0] = live[p]; o[1] = c_reref[p]; o[2] = eta[p]; o[5] = F[p]; o[6] = gn[p]; o[13] = tolp[p];
             }
             upload_skip(live, /*consume=*/true);
             newton_hessian(q_fskip.d, refactor);  // (a frozen problem's short entries keep their values, see k_hassemble)
@@ -3953,15 +3972,19 @@ struct HipBackend {
                     }
                     pcg_used_total += used_now;
                     probe_mark(*this, used_now);
+                    for (int p = 0; p < count; ++p)
+                        if (live[p]) { double* o = tr + (size_t)kTraceFields * p; o[3] = h_gate[count + p]; o[4] = h_gate[p]; o[7] = gd[p]; }
                 }
                 std::vector<int32_t> acc_now(count, 0);
                 bool any_acc = false, any_ls = false;
                 for (int p = 0; p < count; ++p) {
                     if (!ls[p]) continue;
+                    tr[(size_t)kTraceFields * p + 8] = k + 1;
                     const bool armijo = Ft[p] <= F[p] + 1e-4 * step[p] * gd[p];
                     const bool tiny = std::fabs(step[p] * gd[p]) <= 1e-13 * std::max(1.0, std::fabs(F[p]));
                     if ((Ft[p] == Ft[p]) && (armijo || (tiny && gt[p] < gn[p]))) {
                         F[p] = Ft[p]; gn[p] = gt[p];
+                        { double* o = tr + (size_t)kTraceFields * p; o[9] = step[p]; o[10] = Ft[p]; o[11] = gt[p]; }
                         accepted[p] = 1; acc_now[p] = 1; any_acc = true;
                         ls[p] = 0;
                     } else {
@@ -3992,7 +4015,7 @@ struct HipBackend {
             }
             bool any_stalled = false;
             for (int p = 0; p < count; ++p)
-                if (live[p] && !accepted[p]) { stalled[p] = 1; any_stalled = true; }
+                if (live[p] && !accepted[p]) { stalled[p] = 1; any_stalled = true; tr[(size_t)kTraceFields * p + 12] = 1.0; }
             if (st.verbose) {
                 for (int p = 0; p < count; ++p)
                     if (live[p]) std::fprintf(stderr, "[score] newton it %d prob %d F %.12g |g| %.3e step %.3g pcg %d (conv %d) t %.3f ms%s\n", it + 1, p, F[p], gn[p], step[p], h_gate[count + p], h_gate[p], now_ms() - t_start, stalled[p] ? " (stalled)" : "");

@@ -268,6 +268,76 @@ int64_t get_graph_launches(HipBackend& be, double* out, int64_t len) {  // captu
     return copy_out_min(&v, 1, out, len);
 }
 
+// ---- read-outs of the Newton polish (tests/test_polish_model_gpu.py): plain reads of buffers and host values that exist ----
+int64_t get_polish_eval(HipBackend& be, double* out, int64_t len) {
+    // per problem [F, max |g_i| / D_i, act_flips] as the last evaluation collected them (newton_eval_collect)
+    const int64_t cnt = be.H->count, sz = 3 * cnt;
+    if (!be.Q.available || (int64_t)be.dbg_eval_F.size() != cnt || (int64_t)be.act_flips.size() != cnt) return -1;
+    if (out && len >= sz)
+        for (int64_t p = 0; p < cnt; ++p) {
+            out[3 * p] = be.dbg_eval_F[(size_t)p]; out[3 * p + 1] = be.dbg_eval_gn[(size_t)p]; out[3 * p + 2] = be.act_flips[(size_t)p];
+        }
+    return sz;
+}
+int64_t get_polish_trace(HipBackend& be, double* out, int64_t len) {
+    // HipBackend::kTraceFields values per Newton iteration and problem of the last polish_lockstep call, iteration by iteration:
+    // [live, reref, eta, pcg_used, gate fired, F, gn, gd, trial steps taken, accepted step, F_new, gn_new, stalled, tolerance]
+    // (gn: max |g_i| / D_i; gd = g'delta; a problem that is not live in an iteration holds zeros from pcg_used to stalled)
+    if (!be.Q.available) return -1;
+    return copy_out_min(be.polish_trace.data(), (int64_t)be.polish_trace.size(), out, len);
+}
+int64_t get_polish_pcg(HipBackend& be, double* out, int64_t len) {
+    // the gate words of the last Newton PCG as the device holds them: [fired per problem | STEPs executed per problem]
+    if (!be.Q.available) return -1;
+    const int64_t sz = 2 * (int64_t)be.H->count;
+    if (out && len >= sz) copy_out_min(down_i32(be, be.q_pcgdone.d, (size_t)sz).data(), sz, out, sz);
+    return sz;
+}
+int64_t get_polish_gate(HipBackend& be, double* out, int64_t len) {
+    // what pcg_gate read in the last Newton PCG: [(relative tolerance)^2 per problem | threshold tol2 * r0'z0 per problem]
+    if (!be.Q.available) return -1;
+    const int64_t cnt = be.H->count;
+    if (out && len >= 2 * cnt) {
+        HIP_CHECK(sync_stream(be.stream));
+        const std::vector<double> t = down_f64(be, be.q_gate_tol2.d, (size_t)cnt), r = down_f64(be, be.q_gate_ref.d, (size_t)cnt);
+        std::copy(t.begin(), t.end(), out);
+        std::copy(r.begin(), r.end(), out + cnt);
+    }
+    return 2 * cnt;
+}
+int64_t get_polish_blocks(HipBackend& be, double* out, int64_t len) {
+    // how the polish splits its work: per problem [cone blocks, row blocks of the gradient product, row blocks of H] (the host
+    // adds one partial per block: F and g'delta), then the entries of H that take the long path of k_hassemble (positions in Hval)
+    const HostSystem& h = *be.H;
+    if (!be.Q.available) return -1;
+    const int64_t sz = 3 * (int64_t)h.count + (int64_t)be.Q.long_ent.size();
+    if (out && len >= sz) {
+        for (int p = 0; p < h.count; ++p) {
+            out[3 * p] = h.cone_part_ptr[p + 1] - h.cone_part_ptr[p];
+            out[3 * p + 1] = h.rbG2.part_ptr[p + 1] - h.rbG2.part_ptr[p];
+            out[3 * p + 2] = be.Q.rbH.part_ptr[p + 1] - be.Q.rbH.part_ptr[p];
+        }
+        std::copy(be.Q.long_ent.begin(), be.Q.long_ent.end(), out + 3 * h.count);
+    }
+    return sz;
+}
+int64_t get_polish_p(HipBackend& be, double* out, int64_t len) {
+    // the direction of the last product of the last Newton PCG (w = H p for it: "w"), problem by problem.  The products write
+    // p and p2 in turn, and a problem's launches are no-ops once its gate has fired: after `used` executed STEPs the
+    // direction of its last product is in p2 when `used` is odd and in p when it is even (HipBackend::pcg_step).
+    const HostSystem& h = *be.H;
+    if (!be.Q.available) return -1;
+    if (out && len >= h.n_tot) {
+        const std::vector<int32_t> g = down_i32(be, be.q_pcgdone.d, (size_t)2 * h.count);
+        const std::vector<double> a = down_f64(be, be.p.d, (size_t)h.n_tot), b = down_f64(be, be.p2.d, (size_t)h.n_tot);
+        for (int p = 0; p < h.count; ++p) {
+            const std::vector<double>& src = (g[(size_t)h.count + p] & 1) ? b : a;
+            std::copy(src.begin() + h.xoff[p], src.begin() + h.xoff[p + 1], out + h.xoff[p]);
+        }
+    }
+    return h.n_tot;
+}
+
 int64_t get_vec(HipBackend& be, const char* name, double* out, int64_t len) {
     const HostSystem& h = *be.H;
     const std::string nm(name);
@@ -292,6 +362,12 @@ int64_t get_vec(HipBackend& be, const char* name, double* out, int64_t len) {
         {"invD", R::DevF64, be.invD.d, n}, {"invE", R::DevF64, be.invE.d, m},
         {"fac", R::DevF64, be.Kset.fac.d, (int64_t)be.Kset.fac_doubles},
         {"polish_g", R::DevF64, be.q_g.d, polish ? n : 0}, {"Hval", R::DevF64, be.Hm.val.d, polish ? be.hm_nnz : 0},
+        // the last evaluation's point [u | nu], cone blocks and activity words; the step of the last Newton PCG
+        {"polish_u", R::DevF64, be.dbg_eval_x, n, polish && be.dbg_eval_x}, {"polish_nu", R::DevF64, be.dbg_eval_x ? be.dbg_eval_x + n : nullptr, m, polish && be.dbg_eval_x},
+        {"polish_B", R::DevF64, be.q_Bbuf.d, polish ? (int64_t)h.cone_row.size() * Q.T * Q.T : 0, polish},
+        {"polish_act", R::DevI32, be.q_act.d, polish ? (int64_t)h.cone_row.size() : 0, polish},
+        {"polish_delta", R::DevF64, be.q_delta.d, polish ? n : 0, polish},
+        {"polish_Pon", R::DevF64, be.q_Pon.d, polish ? be.hm_nnz : 0, polish},  // P (+ the regularisation) on the pattern of H: what k_hassemble starts every entry from
         {"Acol", R::DevI32, be.A_col.d, na}, {"Aptr", R::DevI32, be.A_ptr.d, m + 1},
         {"G1col", R::DevI32, be.G1.col.d, n1}, {"G1ptr", R::DevI32, be.G1.ptr.d, n + 1},
         {"G2col", R::DevI32, be.G2.col.d, n2}, {"G2ptr", R::DevI32, be.G2.ptr.d, n + 1}, {"G2split", R::DevI32, be.G2.split.d, n},
@@ -316,6 +392,7 @@ int64_t get_vec(HipBackend& be, const char* name, double* out, int64_t len) {
         {"polish_prec_of_negg", get_polish_prec_of_negg},
         {"chain_of_col", get_chain_of_col}, {"chain_id_of_col", get_chain_id_of_col}, {"matrix_source", get_matrix_source},
         {"graph_launches", get_graph_launches},
+        {"polish_eval", get_polish_eval}, {"polish_trace", get_polish_trace}, {"polish_pcg", get_polish_pcg}, {"polish_p", get_polish_p}, {"polish_gate", get_polish_gate}, {"polish_blocks", get_polish_blocks},
     };
     for (const Computed& c : computed)
         if (nm == c.name) return c.fn(be, out, len);
