@@ -1,6 +1,6 @@
 """ctypes bindings of the refinement family's headers (include/score_robust.h, score_refine_robust.h, score_refine_batch.h,
-score_refine_robust_batch.h, score_marginals.h, score_spectrum.h, score_samples.h, score_leverage.h and the three
-``*_batch.h`` analyses): their records, one ``Table`` per header -- ``{symbol: (argtypes, restype)}``, so the list of a
+score_refine_robust_batch.h, score_marginals.h, score_spectrum.h, score_samples.h, score_leverage.h, score_curvature.h and
+the ``*_batch.h`` analyses): their records, one ``Table`` per header -- ``{symbol: (argtypes, restype)}``, so the list of a
 header's symbols and their argument types are one text -- and the one ``bind`` that applies a table to a library.
 include/score_hip.h's own binding is ``solver.load_library``.
 """
@@ -69,6 +69,14 @@ class ScoreSpectrumInfo(InfoRecord):
     _fields_ = [
         ("modes", C.c_int32), ("block", C.c_int32), ("iterations", C.c_int32), ("unconverged", C.c_int32),
         ("h_max", C.c_double), ("shift", C.c_double), ("max_residual", C.c_double),
+        ("setup_ms", C.c_double), ("solve_ms", C.c_double),
+    ]
+
+
+class ScoreCurvatureInfo(InfoRecord):
+    _fields_ = [
+        ("modes", C.c_int32), ("block", C.c_int32), ("iterations", C.c_int32), ("unconverged", C.c_int32),
+        ("h_max", C.c_double), ("shift", C.c_double), ("c_max", C.c_double), ("max_residual", C.c_double),
         ("setup_ms", C.c_double), ("solve_ms", C.c_double),
     ]
 
@@ -212,6 +220,14 @@ TABLES = (ROBUST, REFINE_ROBUST, REFINE_BATCH, REFINE_ROBUST_BATCH, MARGINALS, M
           SAMPLES, SAMPLES_BATCH, LEVERAGE)
 # the headers that came after those (TABLES itself is pinned by its test)
 LATER_TABLES = (LEVERAGE_BATCH,)
+
+CURVATURE = Table("curvature", _NO_EIGENSOLVER, {
+    "score_refine_hessian_product": ([_handle, _f64p, _f64p, C.c_int32, _f64p, C.c_int32, _f64p], C.c_int),
+    "score_refine_curvature": ([_handle, _f64p, _f64p, C.c_int32, C.c_double, C.c_int32, C.c_double, _f64p, _f64p, _f64p, _f64p,
+                                C.POINTER(ScoreCurvatureInfo)], C.c_int),
+})
+# and those after them (LATER_TABLES is pinned too)
+TABLES_SINCE = (CURVATURE,)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

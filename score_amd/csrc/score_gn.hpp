@@ -107,15 +107,30 @@ SCORE_GN_HD void gn_rel_jac(double thi, double xi, double yi, double thj, double
     J[5][0] = -st * (ci * Rm[1] - si * Rm[3]);
     J[2][3] = st * -sj; J[3][3] = st * -cj; J[4][3] = st * cj; J[5][3] = st * -sj;
 }
-// Returns the cost r'r; with H / g non-null also J'J (6 x 6, row-major) and J'r (6).
+// The curvature term of the measurement, sum_q r_q grad^2 r_q, added to its 6 x 6 block H: d^2 R / d theta^2 = -R, and r is
+// additively separable in i and j, so only (th_i, th_i) and (th_j, th_j) get a term.  r: what gn_rel_jac gave at the point.
+SCORE_GN_HD void gn_rel_curv(double thi, double thj, const double* tm, const double* Rm, double kappa, double tau, const double* r,
+                             double* H) {
+    const double sk = sqrt(kappa), st = sqrt(tau);
+    const double ci = cos(thi), si = sin(thi), cj = cos(thj), sj = sin(thj);
+    // d^2 r / d th_i^2 = + sqrt(kappa) R_i tm (rows 0, 1), + sqrt(tau) R_i Rm (rows 2..5); d^2 r / d th_j^2 = - sqrt(tau) R_j
+    const double hi = sk * (r[0] * (ci * tm[0] - si * tm[1]) + r[1] * (si * tm[0] + ci * tm[1]))
+                    + st * (r[2] * (ci * Rm[0] - si * Rm[2]) + r[3] * (ci * Rm[1] - si * Rm[3])
+                          + r[4] * (si * Rm[0] + ci * Rm[2]) + r[5] * (si * Rm[1] + ci * Rm[3]));
+    const double hj = -st * (r[2] * cj - r[3] * sj + r[4] * sj + r[5] * cj);
+    H[0] += hi;
+    H[3 * 6 + 3] += hj;
+}
+// Returns the cost r'r; with H / g non-null also J'J (6 x 6, row-major) and J'r (6); exact: H is J'J plus the curvature term.
 SCORE_GN_HD double gn_rel_block(double thi, double xi, double yi, double thj, double xj, double yj, const double* tm,
-                                const double* Rm, double kappa, double tau, double* H, double* g) {
+                                const double* Rm, double kappa, double tau, double* H, double* g, bool exact = false) {
     double r[6], J[6][6];
     gn_rel_jac(thi, xi, yi, thj, xj, yj, tm, Rm, kappa, tau, r, J, H != nullptr);
     double cost = 0.0;
     for (int k = 0; k < 6; ++k) cost += r[k] * r[k];
     if (!H) return cost;
     gn_normal_products<6>(J, r, H, g);
+    if (exact) gn_rel_curv(thi, thj, tm, Rm, kappa, tau, r, H);
     return cost;
 }
 
@@ -133,14 +148,38 @@ SCORE_GN_HD double gn_range_jac(double xa, double ya, double xb, double yb, doub
     }
     return r;
 }
-// the cost r'r; with H / g: H 4 x 4, g 4.
-SCORE_GN_HD double gn_range_block(double xa, double ya, double xb, double yb, double dist, double prec, double* H, double* g) {
+// The curvature term of a range in D dimensions, r grad^2 r = r sqrt(prec) (I - u u') / rho with u = (a - b) / rho, added to the
+// 2 D x 2 D block H: on (a, a) and (b, b), with the opposite sign on (a, b) and (b, a); nothing where rho <= 1e-12, as the
+// Jacobian.  d = a - b.
+template <int D>
+SCORE_GN_HD void gn_range_curv(const double* d, double prec, double r, double* H) {
+    double rho2 = 0.0;
+    for (int k = 0; k < D; ++k) rho2 += d[k] * d[k];
+    const double rho = sqrt(rho2);
+    if (!(rho > 1e-12)) return;
+    const double s = r * sqrt(prec) / rho;
+    for (int a = 0; a < D; ++a)
+        for (int b = 0; b < D; ++b) {
+            const double t = s * ((a == b ? 1.0 : 0.0) - (d[a] / rho) * (d[b] / rho));
+            H[a * 2 * D + b] += t;
+            H[(D + a) * 2 * D + D + b] += t;
+            H[a * 2 * D + D + b] -= t;
+            H[(D + a) * 2 * D + b] -= t;
+        }
+}
+// the cost r'r; with H / g: H 4 x 4, g 4; exact: H with the curvature term.
+SCORE_GN_HD double gn_range_block(double xa, double ya, double xb, double yb, double dist, double prec, double* H, double* g,
+                                  bool exact = false) {
     double J[4];
     const double r = gn_range_jac(xa, ya, xb, yb, dist, prec, J, H != nullptr);
     if (H) {
         for (int a = 0; a < 4; ++a) {
             g[a] = J[a] * r;
             for (int b = 0; b < 4; ++b) H[a * 4 + b] = J[a] * J[b];
+        }
+        if (exact) {
+            const double d[2] = {xa - xb, ya - yb};
+            gn_range_curv<2>(d, prec, r, H);
         }
     }
     return r * r;
@@ -253,15 +292,54 @@ SCORE_GN_HD void gn_rel_jac3(const double* Xi, const double* Xj, const double* t
             }
     }
 }
-// the cost r'r; with H / g: J'J (12 x 12) and J'r.
+// The curvature term in 3-D, in the coordinates of the retraction R Exp(omega): d^2 (R Exp omega) / d omega_a d omega_b at
+// omega = 0 is R S_ab with S_ab = ([e_a]x [e_b]x + [e_b]x [e_a]x) / 2 = (e_a e_b' + e_b e_a') / 2 - delta_ab I, so for any N
+// trace(S_ab N) = (N_ab + N_ba) / 2 - delta_ab trace N.  Only the (om_i, om_i) and (om_j, om_j) 3 x 3 sub-blocks of the
+// 12 x 12 block H get a term:
+//   (om_i, om_i)  -sqrt(kappa) r_t' R_i S_ab tm - sqrt(tau) <r_R, R_i S_ab Rm>  = -trace(S_ab N_i),  N_i = tm (R_i' r_t)' sqrt(kappa)
+//                                                                                                   + Rm r_R' R_i sqrt(tau)
+//   (om_j, om_j)  +sqrt(tau) <r_R, R_j S_ab>                                    = +trace(S_ab N_j),  N_j = r_R' R_j sqrt(tau)
+// r: what gn_rel_jac3 gave at the point (r_t = r[0..2], r_R = r[3..11] row-major).
+SCORE_GN_HD void gn_rel_curv3(const double* Xi, const double* Xj, const double* tm, const double* Rm, double kappa, double tau,
+                              const double* r, double* H) {
+    const double sk = sqrt(kappa), st = sqrt(tau);
+    double u[3], A[9], Ni[9], Nj[9];  // u = R_i' r_t, A = r_R' R_i
+    for (int a = 0; a < 3; ++a) {
+        double s = 0.0;
+        for (int k = 0; k < 3; ++k) s += Xi[k * 3 + a] * r[k];
+        u[a] = s;
+    }
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) {
+            double x = 0.0, y = 0.0;
+            for (int k = 0; k < 3; ++k) { x += r[3 + k * 3 + a] * Xi[k * 3 + b]; y += r[3 + k * 3 + a] * Xj[k * 3 + b]; }
+            A[a * 3 + b] = x;
+            Nj[a * 3 + b] = st * y;
+        }
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) {
+            double x = 0.0;
+            for (int k = 0; k < 3; ++k) x += Rm[a * 3 + k] * A[k * 3 + b];
+            Ni[a * 3 + b] = sk * tm[a] * u[b] + st * x;
+        }
+    const double tri = Ni[0] + Ni[4] + Ni[8], trj = Nj[0] + Nj[4] + Nj[8];
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) {
+            const double d = a == b ? 1.0 : 0.0;
+            H[a * 12 + b] -= 0.5 * (Ni[a * 3 + b] + Ni[b * 3 + a]) - d * tri;
+            H[(6 + a) * 12 + 6 + b] += 0.5 * (Nj[a * 3 + b] + Nj[b * 3 + a]) - d * trj;
+        }
+}
+// the cost r'r; with H / g: J'J (12 x 12) and J'r; exact: H with the curvature term.
 SCORE_GN_HD double gn_rel_block3(const double* Xi, const double* Xj, const double* tm, const double* Rm, double kappa, double tau,
-                                 double* H, double* g) {
+                                 double* H, double* g, bool exact = false) {
     double r[12], J[12][12];
     gn_rel_jac3(Xi, Xj, tm, Rm, kappa, tau, r, J, H != nullptr);
     double cost = 0.0;
     for (int k = 0; k < 12; ++k) cost += r[k] * r[k];
     if (!H) return cost;
     gn_normal_products<12>(J, r, H, g);
+    if (exact) gn_rel_curv3(Xi, Xj, tm, Rm, kappa, tau, r, H);
     return cost;
 }
 
@@ -277,14 +355,19 @@ SCORE_GN_HD double gn_range_jac3(const double* pa, const double* pb, double dist
     }
     return r;
 }
-// the cost r'r; with H / g: H 6 x 6, g 6.
-SCORE_GN_HD double gn_range_block3(const double* pa, const double* pb, double dist, double prec, double* H, double* g) {
+// the cost r'r; with H / g: H 6 x 6, g 6; exact: H with the curvature term.
+SCORE_GN_HD double gn_range_block3(const double* pa, const double* pb, double dist, double prec, double* H, double* g,
+                                   bool exact = false) {
     double J[6];
     const double r = gn_range_jac3(pa, pb, dist, prec, J, H != nullptr);
     if (H) {
         for (int a = 0; a < 6; ++a) {
             g[a] = J[a] * r;
             for (int b = 0; b < 6; ++b) H[a * 6 + b] = J[a] * J[b];
+        }
+        if (exact) {
+            const double d[3] = {pa[0] - pb[0], pa[1] - pb[1], pa[2] - pb[2]};
+            gn_range_curv<3>(d, prec, r, H);
         }
     }
     return r * r;
@@ -322,27 +405,28 @@ struct GnView {
     double *hblk, *gblk;   // its block storage: relative-pose blocks, then range blocks, then prior blocks
 };
 
-// relative-pose entry m at the view's point with the precisions given: cost, with H / g also J'J and J'r
-template <int DIM>
+// relative-pose entry m at the view's point with the precisions given: cost, with H / g also J'J (EXACT: with the curvature
+// term, see gn_rel_curv) and J'r
+template <int DIM, bool EXACT = false>
 SCORE_GN_HD double gn_rel_at(const GnView& v, int64_t m, double kappa, double tau, double* H, double* g) {
     constexpr int PS = DIM == 2 ? 3 : 12;
     const double* pi = v.X + PS * (int64_t)v.rel_i[m];
     const double* pj = v.X + PS * (int64_t)v.rel_j[m];
-    if (DIM == 2) return gn_rel_block(pi[0], pi[1], pi[2], pj[0], pj[1], pj[2], v.rel_t + 2 * m, v.rel_R + 4 * m, kappa, tau, H, g);
-    return gn_rel_block3(pi, pj, v.rel_t + 3 * m, v.rel_R + 9 * m, kappa, tau, H, g);
+    if (DIM == 2) return gn_rel_block(pi[0], pi[1], pi[2], pj[0], pj[1], pj[2], v.rel_t + 2 * m, v.rel_R + 4 * m, kappa, tau, H, g, EXACT);
+    return gn_rel_block3(pi, pj, v.rel_t + 3 * m, v.rel_R + 9 * m, kappa, tau, H, g, EXACT);
 }
 // range r at the view's point with the precision given
-template <int DIM>
+template <int DIM, bool EXACT = false>
 SCORE_GN_HD double gn_range_at(const GnView& v, int64_t r, double prec, double* H, double* g) {
     if (DIM == 2) {
         const double* pa = gn_point2(v.X, v.Np, v.rng_a[r]);
         const double* pb = gn_point2(v.X, v.Np, v.rng_b[r]);
-        return gn_range_block(pa[0], pa[1], pb[0], pb[1], v.rng_dist[r], prec, H, g);
+        return gn_range_block(pa[0], pa[1], pb[0], pb[1], v.rng_dist[r], prec, H, g, EXACT);
     }
     const double* pa = gn_point3(v.X, v.Np, v.rng_a[r]);
     const double* pb = gn_point3(v.X, v.Np, v.rng_b[r]);
     const double a3[3] = {pa[0], pa[1], pa[2]}, b3[3] = {pb[0], pb[1], pb[2]};
-    return gn_range_block3(a3, b3, v.rng_dist[r], prec, H, g);
+    return gn_range_block3(a3, b3, v.rng_dist[r], prec, H, g, EXACT);
 }
 
 template <int N>
@@ -352,14 +436,16 @@ SCORE_GN_HD void gn_store(double* dst, const double* src) {
 }
 
 // measurement m of the view (relative poses, then ranges, then landmark priors; beyond them: nothing): its cost and,
-// with_blocks, its J'J / J'r block into the view's storage (2-D 36 + 6 / 16 + 4 / 2 + 2 scalars, 3-D 144 + 12 / 36 + 6 / 3 + 3)
-template <int DIM>
+// with_blocks, its J'J / J'r block into the view's storage (2-D 36 + 6 / 16 + 4 / 2 + 2 scalars, 3-D 144 + 12 / 36 + 6 / 3 + 3).
+// EXACT: the block is that of E = J'J + sum_q r_q grad^2 r_q (half the Hessian of the cost), in the same layout; a landmark
+// prior is linear and has no term.  A template argument, so that the Gauss-Newton instantiation is the code it was.
+template <int DIM, bool EXACT = false>
 SCORE_GN_HD double gn_measurement(const GnView& v, int64_t m, bool with_blocks) {
     constexpr int PS = DIM == 2 ? 3 : 12, NR = DIM == 2 ? 6 : 12, NG = 2 * DIM;
     double cost = 0.0;
     if (m < v.n_rel) {
         double H[NR * NR], g[NR];
-        cost = gn_rel_at<DIM>(v, m, v.rel_kappa[m], v.rel_tau[m], with_blocks ? H : nullptr, g);
+        cost = gn_rel_at<DIM, EXACT>(v, m, v.rel_kappa[m], v.rel_tau[m], with_blocks ? H : nullptr, g);
         if (with_blocks) {
             double* ho = v.hblk + NR * NR * m;
             for (int k = 0; k < NR * NR; ++k) ho[k] = H[k];
@@ -368,7 +454,7 @@ SCORE_GN_HD double gn_measurement(const GnView& v, int64_t m, bool with_blocks) 
     } else if (m < v.n_rel + v.n_rng) {
         const int64_t r = m - v.n_rel;
         double H[NG * NG], g[NG];
-        cost = gn_range_at<DIM>(v, r, v.rng_prec[r], with_blocks ? H : nullptr, g);
+        cost = gn_range_at<DIM, EXACT>(v, r, v.rng_prec[r], with_blocks ? H : nullptr, g);
         if (with_blocks) {
             gn_store<NG * NG>(v.hblk + NR * NR * v.n_rel + NG * NG * r, H);
             gn_store<NG>(v.gblk + NR * v.n_rel + NG * r, g);

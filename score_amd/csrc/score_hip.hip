@@ -4120,6 +4120,7 @@ struct AbiEnv {
 
 #include "score_marginals.hpp"
 #include "score_spectrum.hpp"
+#include "score_curvature.hpp"
 #include "score_samples.hpp"
 #include "score_leverage.hpp"
 #include "score_gn_robust.hpp"
@@ -4155,6 +4156,7 @@ struct score_refine {
     score::MvTiles h_tiles;  // the product's tiles of H's rows: product_tiles()
     score::MvWork mv;  // marginal covariances (score_marginals.hpp)
     score::SpWork sp;  // lowest eigenpairs of H (score_spectrum.hpp)
+    score::CvWork cv;  // half the Hessian of the cost: product and lowest eigenpairs (score_curvature.hpp)
     score::PsWork ps;  // posterior samples (score_samples.hpp)
     score::LvWork lv;  // range leverage and predicted range variances (score_leverage.hpp)
     // robust refinement (score_gn_robust.hpp): the measured precisions beside rng_prec / rel_kappa / rel_tau (which hold a robust
@@ -4911,6 +4913,23 @@ int score_refine_spectrum(score_refine* r, const double* poses, const double* la
         require(r && poses && (r->P.Nl == 0 || landmarks));
         AbiEnv::Scope scope(r->device, false);
         return score::sp_solve(*r, poses, landmarks, k, rel_tol, max_iters, shift_rel, values, vectors, residuals, info);
+    });
+}
+int score_refine_hessian_product(score_refine* r, const double* poses, const double* landmarks, int32_t exact, const double* V,
+                                 int32_t n_cols, double* out) {
+    return abi_call([&] {
+        require(r && poses && (r->P.Nl == 0 || landmarks) && V && out);
+        AbiEnv::Scope scope(r->device, false);
+        return score::cv_product(*r, poses, landmarks, exact, V, n_cols, out);
+    });
+}
+int score_refine_curvature(score_refine* r, const double* poses, const double* landmarks, int32_t k, double rel_tol, int32_t max_iters,
+                           double shift_rel, double* values, double* vectors, double* residuals, double* gn_quotients,
+                           score_curvature_info* info) {
+    return abi_call([&] {
+        require(r && poses && (r->P.Nl == 0 || landmarks));
+        AbiEnv::Scope scope(r->device, false);
+        return score::cv_solve(*r, poses, landmarks, k, rel_tol, max_iters, shift_rel, values, vectors, residuals, gn_quotients, info);
     });
 }
 void score_refine_robust_default_settings(score_refine_robust_settings* rs) {

@@ -46,6 +46,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "../../include/score_spectrum.h"
@@ -290,23 +291,44 @@ struct SpWork {
     }
 };
 
-// The solve.  Refine: score_refine (its point, blocks and gather, its linear-mode handle, its SpWork `sp`).
-template <class Refine>
-int sp_solve(Refine& R, const double* poses, const double* landmarks, int32_t k, double rel_tol, int32_t max_iters, double shift_rel,
-             double* values, double* vectors, double* residuals, score_spectrum_info* info) {
+// What a call of the iteration is about: whose words open its messages, the values the product reads, whether A may be
+// indefinite (the Ritz step's test of the lowest value), and what follows the iteration while X and the product still stand.
+// SpInformation: score_refine_spectrum, A = J'J + sigma I in the handle's own values.  score_curvature.hpp has the other.
+struct SpInformation {
+    static constexpr bool indefinite = false;
+    const char* who = "score_refine_spectrum: ";
+    template <class Refine>
+    const double* product_values(Refine& R, double) { return R.be().Kset.mat.val.d; }  // (after gather_h(sigma) and the factors)
+    template <class Refine, class Product>
+    void after_iteration(Refine&, Product&, double) {}
+};
+
+// what the iteration reports beside its outputs: the fields score_spectrum_info and score_curvature_info share
+struct SpOutcome {
+    int iterations = 0, unconverged = 0;
+    int column[kSpBlock] = {};  // pair j of the outputs is this column of X
+    double h_max = 0.0, sigma = 0.0, worst = 0.0, setup_ms = 0.0, solve_ms = 0.0;
+};
+
+// The solve, one body for both operators.  Refine: score_refine (its point, blocks and gather, its linear-mode handle, its
+// SpWork `sp`).  The preconditioner is that of J'J + sigma I whatever the product reads.
+template <class Refine, class Op>
+int sp_iterate(Refine& R, Op& op, const double* poses, const double* landmarks, int32_t k, double rel_tol, int32_t max_iters,
+               double shift_rel, double* values, double* vectors, double* residuals, SpOutcome& outcome) {
     const GnProblem& P = R.P;
-    if (k < 1 || k > kSpBlock) throw std::runtime_error("score_refine_spectrum: k must be 1..16");
+    const std::string who = op.who;
+    if (k < 1 || k > kSpBlock) throw std::runtime_error(who + "k must be 1..16");
     if (!(rel_tol > 0.0) || !std::isfinite(rel_tol) || max_iters < 1)
-        throw std::runtime_error("score_refine_spectrum: rel_tol must be positive and max_iters >= 1");
-    if (!(shift_rel > 0.0) || !std::isfinite(shift_rel)) throw std::runtime_error("score_refine_spectrum: shift_rel must be positive");
+        throw std::runtime_error(who + "rel_tol must be positive and max_iters >= 1");
+    if (!(shift_rel > 0.0) || !std::isfinite(shift_rel)) throw std::runtime_error(who + "shift_rel must be positive");
     HipBackend& be = R.be();
     hipStream_t st = R.stream();
     const long long n = P.n;
     const double t0 = now_ms();
     // the point, the blocks, H and max diag H; then A = H + sigma I on the handle's pattern and its chain factors
-    R.h_at_point(poses, landmarks, "score_refine_spectrum: ", "the block needs");
+    R.h_at_point(poses, landmarks, who, "the block needs");
     if (n < kSpMinN)
-        throw std::runtime_error("score_refine_spectrum: fewer than 48 unknowns -- use the dense solver (engine=\"python\") for a graph this small");
+        throw std::runtime_error(who + "fewer than 48 unknowns -- use the dense solver (engine=\"python\") for a graph this small");
     auto& W = R.sp;
     W.reserve(P, R.product_tiles(), be.n_prec, be.H->bs * be.n_join_seps, R.n_hblocks, st);
     hipLaunchKernelGGL(k_sp_hmax, dim3((unsigned)W.n_hblocks), dim3(kThreads), 0, st, (const double*)be.K0d.d, (const int32_t*)R.is_diag.d,
@@ -316,7 +338,7 @@ int sp_solve(Refine& R, const double* poses, const double* landmarks, int32_t k,
     staged_d2h(hpart.data(), W.hmax_part.d, hpart.size() * sizeof(double), st);
     double h_max = 0.0;
     for (double v : hpart) h_max = std::max(h_max, v);
-    if (!(h_max > 0.0) || !std::isfinite(h_max)) throw std::runtime_error("score_refine_spectrum: the diagonal of H is zero or not finite at this point");
+    if (!(h_max > 0.0) || !std::isfinite(h_max)) throw std::runtime_error(who + "the diagonal of H is zero or not finite at this point");
     const double sigma = shift_rel * h_max, tol = rel_tol * h_max;
     R.gather_h(sigma);
     be.derive_rho_data(false);
@@ -330,7 +352,7 @@ int sp_solve(Refine& R, const double* poses, const double* landmarks, int32_t k,
     a.gram_part = W.gram_part.d; a.n_gram_wgs = W.n_gram_wgs; a.n_row_tiles = W.n_row_tiles;
     a.out = W.out.d; a.coef = W.coef.d;
     MvArgs m{};
-    m.ptr = be.Kset.mat.ptr.d; m.col = be.Kset.mat.col.d; m.val = be.Kset.mat.val.d;
+    m.ptr = be.Kset.mat.ptr.d; m.col = be.Kset.mat.col.d; m.val = op.product_values(R, sigma);
     m.tiles = W.tiles; m.n_tiles = W.n_tiles; m.n = n; m.flags = W.flags.d; m.all_columns = 1; m.pw_part = W.pw_part.d;
     auto product = [&](const double* in, double* out) {
         m.p_in = in; m.w = out;
@@ -350,7 +372,7 @@ int sp_solve(Refine& R, const double* poses, const double* landmarks, int32_t k,
     int kept = 0;
     auto ritz_and_combine = [&]() -> bool {  // false: breakdown
         SpTheta next{};
-        const int status = sp_rayleigh_ritz(kSpM, kSpBlock, host.data(), host.data() + kSpM * kSpM, next.v, coef.data(), &kept);
+        const int status = sp_rayleigh_ritz(kSpM, kSpBlock, host.data(), host.data() + kSpM * kSpM, next.v, coef.data(), &kept, Op::indefinite);
         if (status == kSpRrBreakdown) return false;  // (X and its values stay as they are)
         th = next;
         staged_h2d(W.coef.d, coef.data(), coef.size() * sizeof(double), st);
@@ -412,6 +434,11 @@ int sp_solve(Refine& R, const double* poses, const double* landmarks, int32_t k,
         X.resize((size_t)k * (size_t)n);
         staged_d2h(X.data(), W.x.d, X.size() * sizeof(double), st);
     }
+    auto product_with = [&](const double* val, const double* in, double* out) {
+        m.val = val;
+        product(in, out);
+    };
+    op.after_iteration(R, product_with, sigma);
     HIP_CHECK(sync_stream(st));
     int unconverged = 0;
     double worst = 0.0;
@@ -432,12 +459,25 @@ int sp_solve(Refine& R, const double* poses, const double* landmarks, int32_t k,
         }
     }
     const double t2 = now_ms();
-    if (info) {
-        info->modes = k; info->block = kSpBlock; info->iterations = iterations; info->unconverged = unconverged;
-        info->h_max = h_max; info->shift = sigma; info->max_residual = worst;
-        info->setup_ms = t1 - t0; info->solve_ms = t2 - t1;
-    }
+    outcome.iterations = iterations; outcome.unconverged = unconverged;
+    for (int j = 0; j < k; ++j) outcome.column[j] = order[(size_t)j];
+    outcome.h_max = h_max; outcome.sigma = sigma; outcome.worst = worst;
+    outcome.setup_ms = t1 - t0; outcome.solve_ms = t2 - t1;
     return unconverged ? 1 : 0;
+}
+
+template <class Refine>
+int sp_solve(Refine& R, const double* poses, const double* landmarks, int32_t k, double rel_tol, int32_t max_iters, double shift_rel,
+             double* values, double* vectors, double* residuals, score_spectrum_info* info) {
+    SpInformation op;
+    SpOutcome o;
+    const int rc = sp_iterate(R, op, poses, landmarks, k, rel_tol, max_iters, shift_rel, values, vectors, residuals, o);
+    if (info) {
+        info->modes = k; info->block = kSpBlock; info->iterations = o.iterations; info->unconverged = o.unconverged;
+        info->h_max = o.h_max; info->shift = o.sigma; info->max_residual = o.worst;
+        info->setup_ms = o.setup_ms; info->solve_ms = o.solve_ms;
+    }
+    return rc;
 }
 
 }  // namespace score

@@ -15,6 +15,8 @@
 //      the combine kernel actually forms;
 //   5. a pencil that is non-finite, leaves fewer than nb directions, or has a non-positive lowest value (A = H + sigma I is
 //      positive definite: anything else is rounding gone wrong) is tried once more without the P block; then breakdown.
+//      `indefinite` lifts exactly the test of the lowest value: the pencil of an indefinite A (score_curvature.hpp: half the
+//      Hessian of the cost) has negative Ritz values by right, and nothing else of the step reads their sign.
 #pragma once
 
 #include <cmath>
@@ -89,7 +91,7 @@ inline bool sp_jacobi_eigh(int m, std::vector<double>& a, std::vector<double>& w
 
 // One attempt on the directions `use` (m flags).  theta: nb.  C: m x nb row-major.  kept: directions left after step 3.
 inline bool sp_rr_attempt(int m, int nb, const double* GA, const double* GB, const std::vector<char>& use, double* theta, double* C,
-                          int* kept) {
+                          int* kept, bool indefinite = false) {
     const size_t M = (size_t)m;
     std::vector<int> idx;
     std::vector<double> d;
@@ -136,7 +138,7 @@ inline bool sp_rr_attempt(int m, int nb, const double* GA, const double* GB, con
         }
     std::vector<double> mu, Z;
     if (!sp_jacobi_eigh((int)mk, T, mu, Z)) return false;
-    if (!(mu[0] > 0.0)) return false;
+    if (!indefinite && !(mu[0] > 0.0)) return false;
     for (size_t i = 0; i < M * (size_t)nb; ++i) C[i] = 0.0;
     std::vector<double> c(ma), t(ma);
     for (int j = 0; j < nb; ++j) {
@@ -162,12 +164,13 @@ inline bool sp_rr_attempt(int m, int nb, const double* GA, const double* GB, con
 // The nb lowest Ritz pairs of the pencil (GA, GB), both m x m row-major with m = 3 nb ([X | W | P]).  theta: nb ascending
 // (up to the Rayleigh correction of step 4).  C: m x nb row-major.  Returns kSpRrOk, kSpRrNoP (the P block was left out: the
 // caller's next P is what C says, as always) or kSpRrBreakdown (theta and C are not to be used).
-inline int sp_rayleigh_ritz(int m, int nb, const double* GA, const double* GB, double* theta, double* C, int* kept) {
+inline int sp_rayleigh_ritz(int m, int nb, const double* GA, const double* GB, double* theta, double* C, int* kept,
+                            bool indefinite = false) {
     std::vector<char> use((size_t)m, 1);
     int k = 0;
-    if (sp_rr_attempt(m, nb, GA, GB, use, theta, C, &k)) { if (kept) *kept = k; return kSpRrOk; }
+    if (sp_rr_attempt(m, nb, GA, GB, use, theta, C, &k, indefinite)) { if (kept) *kept = k; return kSpRrOk; }
     for (int i = 2 * nb; i < m; ++i) use[(size_t)i] = 0;
-    if (sp_rr_attempt(m, nb, GA, GB, use, theta, C, &k)) { if (kept) *kept = k; return kSpRrNoP; }
+    if (sp_rr_attempt(m, nb, GA, GB, use, theta, C, &k, indefinite)) { if (kept) *kept = k; return kSpRrNoP; }
     if (kept) *kept = k;
     return kSpRrBreakdown;
 }
