@@ -762,11 +762,7 @@ score_refine::~score_refine() { if (lin) score_destroy(lin); }
 void score_refine::create(const score_graph& g, const score_settings* s) {
     const double t0 = score::now_ms();
     score::gn_build(g, P);
-    score_problem pat{};
-    pat.n = (int32_t)P.n; pat.m = 0;
-    pat.P_rowptr = P.hptr.data(); pat.P_col = P.hcol.data();
-    pat.block_size = 3; pat.n_chains = (int32_t)P.chain_ptr.size() - 1;
-    pat.chain_ptr = P.chain_ptr.data(); pat.node_first_col = P.node_first_col.data();
+    const score_problem pat = score::gn_linear_pattern(P.n, P.hptr, P.hcol, P.chain_ptr, P.node_first_col);
     if (score_linear_create(&pat, s, &lin) != 0) throw std::runtime_error(g_err);
     u.assign((size_t)P.state_size(), 0.0); ut = u;
     step.assign((size_t)P.n, 0.0); rhs = step;

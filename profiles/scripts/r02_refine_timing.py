@@ -1,12 +1,34 @@
 """Local refinement after SCORE (f4) on the headline graph: normal equations on the GPU (score_linear_solve)
-against SciPy sparse LU, same Levenberg-Marquardt loop."""
-import os, sys, time
+against SciPy sparse LU, same Levenberg-Marquardt loop.
+
+  python profiles/scripts/r02_refine_timing.py                         the comparison of the engines
+  python profiles/scripts/r02_refine_timing.py --reps N [--lib PATH]   the library's own figures only (for two builds against each
+      other, a fresh process per library): N times score_refine_create + score_refine_run on the 4 x 1000-pose graph and
+      score_refine_batch_create + score_refine_batch_run on a group of four 4 x 250-pose graphs, a fresh handle each time, from
+      the SCORE estimates; one line per repetition: setup_ms and solve_ms of the single handle, then of the group."""
+import argparse, os, sys, time
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), "..", ".."))
 sys.path.insert(0, ROOT)
 import numpy as np
 from score_amd.manhattan import make_manhattan
 from score_amd.refine import refine_estimate, _DeviceNormalEquations, _Problem, _initial_point
 from score_amd.solve_score import solve_score
+ap = argparse.ArgumentParser()
+ap.add_argument("--lib", default=None)
+ap.add_argument("--reps", type=int, default=0)
+args = ap.parse_args()
+if args.reps:
+    from score_amd.refine_batch import refine_estimate_batch
+    fg = make_manhattan(n_robots=4, n_poses=1000, n_beacons=4, seed=3000)
+    res = solve_score(fg, "SOCP", lib_path=args.lib)
+    fgs = [make_manhattan(n_robots=4, n_poses=250, n_beacons=4, seed=3001 + i) for i in range(4)]
+    starts = [solve_score(g, "SOCP", lib_path=args.lib) for g in fgs]
+    for _ in range(args.reps):
+        _, one = refine_estimate(fg, res, lib_path=args.lib)
+        many = refine_estimate_batch(fgs, starts, lib_path=args.lib)[0][1]
+        print(f"single setup_ms {one['setup_ms']:.3f} solve_ms {one['solve_ms']:.3f} its {one['iterations']}  "
+              f"batch setup_ms {many['setup_ms']:.3f} solve_ms {many['solve_ms']:.3f} its {many['iterations']}", flush=True)
+    sys.exit(0)
 for (r, n, b) in ((4, 1000, 4), (20, 1000, 4)):
     fg = make_manhattan(n_robots=r, n_poses=n, n_beacons=b, seed=3000)
     res = solve_score(fg, "SOCP")

@@ -106,8 +106,7 @@ double cv_values(Refine& R, bool exact, double sigma) {
     if (exact) {
         GnView v = R.view(R.u.d);
         v.hblk = C.eblk.d; v.gblk = C.egblk.d;
-        if (P.dim == 2) hipLaunchKernelGGL(k_cv_blocks<2>, dim3((unsigned)R.n_mblocks), dim3(kThreads), 0, st, v);
-        else hipLaunchKernelGGL(k_cv_blocks<3>, dim3((unsigned)R.n_mblocks), dim3(kThreads), 0, st, v);
+        gn_dim(P.dim, [&](auto dim) { hipLaunchKernelGGL(k_cv_blocks<decltype(dim)::value>, dim3((unsigned)R.n_mblocks), dim3(kThreads), 0, st, v); });
     }
     hipLaunchKernelGGL(k_cv_gather, dim3((unsigned)R.n_hblocks), dim3(kThreads), 0, st, (const int32_t*)R.hc_ptr.d,
                        (const int32_t*)R.hc_slot.d, (const double*)R.hblk.d, exact ? (const double*)C.eblk.d : (const double*)nullptr,

@@ -33,6 +33,7 @@
 #include <cmath>
 #include <cstdint>
 #include <stdexcept>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/score_hip.h"
@@ -392,6 +393,36 @@ SCORE_GN_HD double gn_prior_block3(const double* l, const double* t0, double pre
     return c;
 }
 
+// The measurement arrays, stated once.  F<T> is how one array is held: a pointer (GnMeasPtr, what a lane reads), a host vector
+// (GnMeas below), a device buffer (score_refine_handles.hpp).
+template <template <class> class F>
+struct GnMeasT {
+    F<int32_t> rel_i, rel_j, rng_a, rng_b, pri_l;
+    F<double> rel_t, rel_R, rel_kappa, rel_tau, rng_dist, rng_prec, pri_t, pri_prec;
+};
+template <class T> using GnConstPtr = const T*;
+template <class T> using GnHostVec = std::vector<T>;
+using GnMeasPtr = GnMeasT<GnConstPtr>;
+
+// Every array of two forms side by side: f(a's, b's, family, width), family 0 the relative poses, 1 the ranges, 2 the landmark
+// priors; an entry holds dim^width scalars.  Every conversion between the forms, and a member's offsets, go through this list.
+template <class A, class B, class Fn>
+SCORE_GN_HD void gn_meas_each(A& a, B& b, Fn&& f) {
+    f(a.rel_i, b.rel_i, 0, 0); f(a.rel_j, b.rel_j, 0, 0); f(a.rng_a, b.rng_a, 1, 0); f(a.rng_b, b.rng_b, 1, 0); f(a.pri_l, b.pri_l, 2, 0);
+    f(a.rel_t, b.rel_t, 0, 1); f(a.rel_R, b.rel_R, 0, 2); f(a.rel_kappa, b.rel_kappa, 0, 0); f(a.rel_tau, b.rel_tau, 0, 0);
+    f(a.rng_dist, b.rng_dist, 1, 0); f(a.rng_prec, b.rng_prec, 1, 0); f(a.pri_t, b.pri_t, 2, 1); f(a.pri_prec, b.pri_prec, 2, 0);
+}
+// the table from entry rel0 / rng0 / pri0 of its families on: where a member of a union starts (score_gn_batch.hpp)
+template <int DIM>
+SCORE_GN_HD GnMeasPtr gn_meas_from(const GnMeasPtr& p, long long rel0, long long rng0, long long pri0) {
+    const long long first[3] = {rel0, rng0, pri0};
+    GnMeasPtr q;
+    gn_meas_each(q, p, [&](auto& dst, const auto& src, int family, int width) {
+        dst = src + (width == 0 ? 1 : width == 1 ? DIM : DIM * DIM) * first[family];
+    });
+    return q;
+}
+
 // ---------------------------------------------------------------------------
 // One graph as a lane sees it, and what a lane does with one measurement / one variable of it: stated here once, compiled
 // into the single handle's kernels (score_gn_kernels.hpp, score_gn_robust.hpp), the group's (score_gn_batch.hpp,
@@ -399,34 +430,41 @@ SCORE_GN_HD double gn_prior_block3(const double* l, const double* t0, double pre
 // ---------------------------------------------------------------------------
 struct GnView {
     int64_t Np, Nl, n_rel, n_rng, n_pri;
-    const int32_t *rel_i, *rel_j, *rng_a, *rng_b, *pri_l;   // the measurement arrays, from this graph's first entry
-    const double *rel_t, *rel_R, *rel_kappa, *rel_tau, *rng_dist, *rng_prec, *pri_t, *pri_prec;
+    GnMeasPtr meas;        // the measurement arrays, from this graph's first entry
     const double* X;       // its state: every pose (2-D [theta, x, y], 3-D [R | t]), then the landmarks
     double *hblk, *gblk;   // its block storage: relative-pose blocks, then range blocks, then prior blocks
 };
+
+// dim as a compile-time constant: f(std::integral_constant<int, 2>) for dim == 2, <int, 3> otherwise (gn_build has refused
+// every other value)
+template <class F>
+inline decltype(auto) gn_dim(int dim, F&& f) {
+    if (dim == 2) return f(std::integral_constant<int, 2>{});
+    return f(std::integral_constant<int, 3>{});
+}
 
 // relative-pose entry m at the view's point with the precisions given: cost, with H / g also J'J (EXACT: with the curvature
 // term, see gn_rel_curv) and J'r
 template <int DIM, bool EXACT = false>
 SCORE_GN_HD double gn_rel_at(const GnView& v, int64_t m, double kappa, double tau, double* H, double* g) {
     constexpr int PS = DIM == 2 ? 3 : 12;
-    const double* pi = v.X + PS * (int64_t)v.rel_i[m];
-    const double* pj = v.X + PS * (int64_t)v.rel_j[m];
-    if (DIM == 2) return gn_rel_block(pi[0], pi[1], pi[2], pj[0], pj[1], pj[2], v.rel_t + 2 * m, v.rel_R + 4 * m, kappa, tau, H, g, EXACT);
-    return gn_rel_block3(pi, pj, v.rel_t + 3 * m, v.rel_R + 9 * m, kappa, tau, H, g, EXACT);
+    const double* pi = v.X + PS * (int64_t)v.meas.rel_i[m];
+    const double* pj = v.X + PS * (int64_t)v.meas.rel_j[m];
+    if (DIM == 2) return gn_rel_block(pi[0], pi[1], pi[2], pj[0], pj[1], pj[2], v.meas.rel_t + 2 * m, v.meas.rel_R + 4 * m, kappa, tau, H, g, EXACT);
+    return gn_rel_block3(pi, pj, v.meas.rel_t + 3 * m, v.meas.rel_R + 9 * m, kappa, tau, H, g, EXACT);
 }
 // range r at the view's point with the precision given
 template <int DIM, bool EXACT = false>
 SCORE_GN_HD double gn_range_at(const GnView& v, int64_t r, double prec, double* H, double* g) {
     if (DIM == 2) {
-        const double* pa = gn_point2(v.X, v.Np, v.rng_a[r]);
-        const double* pb = gn_point2(v.X, v.Np, v.rng_b[r]);
-        return gn_range_block(pa[0], pa[1], pb[0], pb[1], v.rng_dist[r], prec, H, g, EXACT);
+        const double* pa = gn_point2(v.X, v.Np, v.meas.rng_a[r]);
+        const double* pb = gn_point2(v.X, v.Np, v.meas.rng_b[r]);
+        return gn_range_block(pa[0], pa[1], pb[0], pb[1], v.meas.rng_dist[r], prec, H, g, EXACT);
     }
-    const double* pa = gn_point3(v.X, v.Np, v.rng_a[r]);
-    const double* pb = gn_point3(v.X, v.Np, v.rng_b[r]);
+    const double* pa = gn_point3(v.X, v.Np, v.meas.rng_a[r]);
+    const double* pb = gn_point3(v.X, v.Np, v.meas.rng_b[r]);
     const double a3[3] = {pa[0], pa[1], pa[2]}, b3[3] = {pb[0], pb[1], pb[2]};
-    return gn_range_block3(a3, b3, v.rng_dist[r], prec, H, g, EXACT);
+    return gn_range_block3(a3, b3, v.meas.rng_dist[r], prec, H, g, EXACT);
 }
 
 template <int N>
@@ -445,7 +483,7 @@ SCORE_GN_HD double gn_measurement(const GnView& v, int64_t m, bool with_blocks) 
     double cost = 0.0;
     if (m < v.n_rel) {
         double H[NR * NR], g[NR];
-        cost = gn_rel_at<DIM, EXACT>(v, m, v.rel_kappa[m], v.rel_tau[m], with_blocks ? H : nullptr, g);
+        cost = gn_rel_at<DIM, EXACT>(v, m, v.meas.rel_kappa[m], v.meas.rel_tau[m], with_blocks ? H : nullptr, g);
         if (with_blocks) {
             double* ho = v.hblk + NR * NR * m;
             for (int k = 0; k < NR * NR; ++k) ho[k] = H[k];
@@ -454,20 +492,20 @@ SCORE_GN_HD double gn_measurement(const GnView& v, int64_t m, bool with_blocks) 
     } else if (m < v.n_rel + v.n_rng) {
         const int64_t r = m - v.n_rel;
         double H[NG * NG], g[NG];
-        cost = gn_range_at<DIM, EXACT>(v, r, v.rng_prec[r], with_blocks ? H : nullptr, g);
+        cost = gn_range_at<DIM, EXACT>(v, r, v.meas.rng_prec[r], with_blocks ? H : nullptr, g);
         if (with_blocks) {
             gn_store<NG * NG>(v.hblk + NR * NR * v.n_rel + NG * NG * r, H);
             gn_store<NG>(v.gblk + NR * v.n_rel + NG * r, g);
         }
     } else if (m < v.n_rel + v.n_rng + v.n_pri) {
         const int64_t e = m - v.n_rel - v.n_rng;
-        const double* l = v.X + PS * v.Np + DIM * (int64_t)v.pri_l[e];
+        const double* l = v.X + PS * v.Np + DIM * (int64_t)v.meas.pri_l[e];
         double H[DIM], g[DIM];
         if (DIM == 2) {
-            cost = gn_prior_block(l[0], l[1], v.pri_t + 2 * e, v.pri_prec[e], with_blocks ? H : nullptr, g);
+            cost = gn_prior_block(l[0], l[1], v.meas.pri_t + 2 * e, v.meas.pri_prec[e], with_blocks ? H : nullptr, g);
         } else {
             const double l3[3] = {l[0], l[1], l[2]};
-            cost = gn_prior_block3(l3, v.pri_t + 3 * e, v.pri_prec[e], with_blocks ? H : nullptr, g);
+            cost = gn_prior_block3(l3, v.meas.pri_t + 3 * e, v.meas.pri_prec[e], with_blocks ? H : nullptr, g);
         }
         if (with_blocks) {
             gn_store<DIM>(v.hblk + NR * NR * v.n_rel + NG * NG * v.n_rng + DIM * e, H);
@@ -535,7 +573,21 @@ SCORE_GN_HD void gn_point(const double* u, const double* pin, int64_t Np, int64_
 // ---------------------------------------------------------------------------
 // host side: the graph, the pattern of J'J, the contribution lists
 // ---------------------------------------------------------------------------
-struct GnProblem {
+struct GnMeas : GnMeasT<GnHostVec> {  // the measurement arrays on the host
+    int64_t n_rel() const { return (int64_t)rel_i.size(); }
+    int64_t n_rng() const { return (int64_t)rng_a.size(); }
+    int64_t n_pri() const { return (int64_t)pri_l.size(); }
+    void append(const GnMeas& o) {  // o's entries after these: a union grows by a member
+        gn_meas_each(*this, o, [](auto& dst, const auto& src, int, int) { dst.insert(dst.end(), src.begin(), src.end()); });
+    }
+    GnMeasPtr ptrs() const {
+        GnMeasPtr p;
+        gn_meas_each(p, *this, [](auto& dst, const auto& src, int, int) { dst = src.data(); });
+        return p;
+    }
+};
+
+struct GnProblem : GnMeas {
     int dim = 2;
     int64_t Np = 0, Nl = 0, n = 0;
     int dp() const { return dim == 2 ? 3 : 6; }          // unknowns per pose
@@ -543,12 +595,7 @@ struct GnProblem {
     int rng_nb() const { return 2 * dim; }
     int64_t state_size() const { return (dim == 2 ? 3 : 12) * Np + dim * Nl; }  // every pose (2-D [theta, x, y], 3-D [R | t]), landmarks
     std::vector<int32_t> chain_len;
-    std::vector<int32_t> rel_i, rel_j, rng_a, rng_b, pri_l;
-    std::vector<double> rel_t, rel_R, rel_kappa, rel_tau, rng_dist, rng_prec, pri_t, pri_prec;
     double pin[3] = {0, 0, 0};  // (not used any more: see gn_pose)
-    int64_t n_rel() const { return (int64_t)rel_i.size(); }
-    int64_t n_rng() const { return (int64_t)rng_a.size(); }
-    int64_t n_pri() const { return (int64_t)pri_l.size(); }
     // block storage: rel blocks (36 + 6 each), then range blocks (16 + 4), then prior blocks (2 + 2)
     int64_t hblk_size() const { return (int64_t)rel_nb() * rel_nb() * n_rel() + (int64_t)rng_nb() * rng_nb() * n_rng() + dim * n_pri(); }
     int64_t gblk_size() const { return (int64_t)rel_nb() * n_rel() + (int64_t)rng_nb() * n_rng() + dim * n_pri(); }
@@ -558,14 +605,24 @@ struct GnProblem {
     std::vector<int32_t> chain_ptr, node_first_col;
 
     GnView view(const double* X, double* hblk, double* gblk) const {  // the graph from host memory
-        return GnView{Np, Nl, n_rel(), n_rng(), n_pri(), rel_i.data(), rel_j.data(), rng_a.data(), rng_b.data(), pri_l.data(),
-                      rel_t.data(), rel_R.data(), rel_kappa.data(), rel_tau.data(), rng_dist.data(), rng_prec.data(), pri_t.data(),
-                      pri_prec.data(), X, hblk, gblk};
+        return GnView{Np, Nl, n_rel(), n_rng(), n_pri(), ptrs(), X, hblk, gblk};
     }
     int64_t pose_col(int64_t p) const { return p == 0 ? -1 : dp() * (p - 1); }
     // first column of the translation of a range endpoint (2-D: after theta; 3-D: after omega)
     int64_t point_col(int64_t v) const { return v < Np ? (v == 0 ? -1 : dp() * (v - 1) + (dp() - dim)) : dp() * (Np - 1) + dim * (v - Np); }
 };
+
+// What the linear-mode handle behind a refinement is created from: the pattern of H alone (the gathers write its values) with
+// the chain hint, 3 x 3 blocks.  The vectors must outlive the create.
+inline score_problem gn_linear_pattern(int64_t n, const std::vector<int32_t>& hptr, const std::vector<int32_t>& hcol,
+                                       const std::vector<int32_t>& chain_ptr, const std::vector<int32_t>& node_first_col) {
+    score_problem pat{};
+    pat.n = (int32_t)n; pat.m = 0;
+    pat.P_rowptr = hptr.data(); pat.P_col = hcol.data();
+    pat.block_size = 3; pat.n_chains = (int32_t)chain_ptr.size() - 1;
+    pat.chain_ptr = chain_ptr.data(); pat.node_first_col = node_first_col.data();
+    return pat;
+}
 
 inline void gn_build(const score_graph& g, GnProblem& P) {
     BuildScope scope;

@@ -48,13 +48,11 @@ struct GbMember {  // where member g lives in the union arrays
     int rblk0, rblk1;
 };
 
-struct GbUnion {
+struct GbUnion : GnMeas {  // (the measurement arrays: the members' one after the other)
     int dim = 2, count = 0;
     long long n = 0, state_size = 0, hblk_size = 0, gblk_size = 0, poses_size = 0, lms_size = 0, lcs_size = 0;
     std::vector<char> lc_short;  // [member] fewer relative-pose entries than odometry steps: its loop closures cannot be re-weighted
     std::vector<GbMember> members;
-    std::vector<int32_t> rel_i, rel_j, rng_a, rng_b, pri_l;
-    std::vector<double> rel_t, rel_R, rel_kappa, rel_tau, rng_dist, rng_prec, pri_t, pri_prec;
     std::vector<int32_t> hptr, hcol, hc_ptr, hc_slot, gc_ptr, gc_slot, diag_member;  // diag_member[k]: member + 1 on a diagonal entry, else 0
     std::vector<int32_t> chain_ptr, node_first_col;
     std::vector<int32_t> mblk_member, ublk_member, sblk_member, rblk_member;
@@ -62,9 +60,6 @@ struct GbUnion {
     int dp() const { return dim == 2 ? 3 : 6; }
     int pose_scalars() const { return dim == 2 ? 3 : 12; }
 };
-
-template <class T>
-inline void gb_append(std::vector<T>& dst, const std::vector<T>& src) { dst.insert(dst.end(), src.begin(), src.end()); }
 
 // gn_build member by member, the members' patterns and contribution lists laid one after the other with offsets
 inline void gb_build(const score_graph* graphs, int count, GbUnion& U) {
@@ -81,7 +76,7 @@ inline void gb_build(const score_graph* graphs, int count, GbUnion& U) {
         if (P.n <= 0) throw std::runtime_error("score_refine_batch: a member has no unknowns");
         GbMember M{};
         M.Np = P.Np; M.Nl = P.Nl; M.n = P.n; M.n_rel = P.n_rel(); M.n_rng = P.n_rng(); M.n_pri = P.n_pri();
-        M.rel0 = (long long)U.rel_i.size(); M.rng0 = (long long)U.rng_a.size(); M.pri0 = (long long)U.pri_l.size();
+        M.rel0 = U.n_rel(); M.rng0 = U.n_rng(); M.pri0 = U.n_pri();
         M.state0 = U.state_size; M.col0 = U.n; M.hblk0 = U.hblk_size; M.gblk0 = U.gblk_size;
         M.pose0 = U.poses_size; M.lm0 = U.lms_size;
         long long odometry = 0;
@@ -94,10 +89,7 @@ inline void gb_build(const score_graph* graphs, int count, GbUnion& U) {
             M.rel0 + M.n_rel >= lim || M.rng0 + M.n_rng >= lim || M.lc0 + M.n_lc >= lim ||
             4 * ((long long)U.rblk_member.size() + (M.n_rng + M.n_lc) / kThreads + 1) >= lim)
             throw std::runtime_error("score_refine_batch: the group is too large for 32-bit positions (use smaller groups)");
-        gb_append(U.rel_i, P.rel_i); gb_append(U.rel_j, P.rel_j); gb_append(U.rng_a, P.rng_a); gb_append(U.rng_b, P.rng_b);
-        gb_append(U.pri_l, P.pri_l); gb_append(U.rel_t, P.rel_t); gb_append(U.rel_R, P.rel_R); gb_append(U.rel_kappa, P.rel_kappa);
-        gb_append(U.rel_tau, P.rel_tau); gb_append(U.rng_dist, P.rng_dist); gb_append(U.rng_prec, P.rng_prec);
-        gb_append(U.pri_t, P.pri_t); gb_append(U.pri_prec, P.pri_prec);
+        U.append(P);
         for (long long i = 0; i < P.n; ++i) {
             U.hptr.push_back((int32_t)(nnz0 + P.hptr[(size_t)i + 1]));
             U.gc_ptr.push_back((int32_t)(gs0 + P.gc_ptr[(size_t)i + 1]));
@@ -137,22 +129,16 @@ inline void gb_build(const score_graph* graphs, int count, GbUnion& U) {
 struct GbDev {
     const GbMember* members;
     const int32_t *mblk_member, *ublk_member, *sblk_member, *rblk_member;
-    const int32_t *rel_i, *rel_j, *rng_a, *rng_b, *pri_l;
-    const double *rel_t, *rel_R, *rel_kappa, *rel_tau, *rng_dist, *rng_prec, *pri_t, *pri_prec;
+    GnMeasPtr meas;  // the union's measurement arrays
 };
 
-// member M of the group as a lane sees it (GnView, score_gn.hpp): the union arrays from its first entry, its state in X, its
-// block storage in hblk / gblk (null: none)
+// member M of the group as a lane sees it (GnView, score_gn.hpp): the union arrays from its first entry (gn_meas_from, which
+// the host can call too: tests/tools/refine_view_check.cpp), its state in X, its block storage in hblk / gblk (null: none)
 template <int DIM>
 __device__ __forceinline__ GnView gb_view(const GbDev& d, const GbMember& M, const double* X, double* hblk, double* gblk) {
     GnView v;
     v.Np = M.Np; v.Nl = M.Nl; v.n_rel = M.n_rel; v.n_rng = M.n_rng; v.n_pri = M.n_pri;
-    v.rel_i = d.rel_i + M.rel0; v.rel_j = d.rel_j + M.rel0; v.rng_a = d.rng_a + M.rng0; v.rng_b = d.rng_b + M.rng0;
-    v.pri_l = d.pri_l + M.pri0;
-    v.rel_t = d.rel_t + DIM * M.rel0; v.rel_R = d.rel_R + DIM * DIM * M.rel0;
-    v.rel_kappa = d.rel_kappa + M.rel0; v.rel_tau = d.rel_tau + M.rel0;
-    v.rng_dist = d.rng_dist + M.rng0; v.rng_prec = d.rng_prec + M.rng0;
-    v.pri_t = d.pri_t + DIM * M.pri0; v.pri_prec = d.pri_prec + M.pri0;
+    v.meas = gn_meas_from<DIM>(d.meas, M.rel0, M.rng0, M.pri0);
     v.X = X + M.state0;
     v.hblk = hblk ? hblk + M.hblk0 : nullptr; v.gblk = gblk ? gblk + M.gblk0 : nullptr;
     return v;

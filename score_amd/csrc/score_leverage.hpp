@@ -130,13 +130,14 @@ __device__ __forceinline__ void lv_measure_lane(const GnView& v, const long long
     sums += m;
     if (m < v.n_rel) {
         double r[NR], J[NR][NR];
-        const double* pi = v.X + PS * (int64_t)v.rel_i[m];
-        const double* pj = v.X + PS * (int64_t)v.rel_j[m];
+        const double* pi = v.X + PS * (int64_t)v.meas.rel_i[m];
+        const double* pj = v.X + PS * (int64_t)v.meas.rel_j[m];
         if constexpr (DIM == 2)
-            gn_rel_jac(pi[0], pi[1], pi[2], pj[0], pj[1], pj[2], v.rel_t + 2 * m, v.rel_R + 4 * m, v.rel_kappa[m], v.rel_tau[m], r, J, true);
+            gn_rel_jac(pi[0], pi[1], pi[2], pj[0], pj[1], pj[2], v.meas.rel_t + 2 * m, v.meas.rel_R + 4 * m, v.meas.rel_kappa[m],
+                       v.meas.rel_tau[m], r, J, true);
         else
-            gn_rel_jac3(pi, pj, v.rel_t + 3 * m, v.rel_R + 9 * m, v.rel_kappa[m], v.rel_tau[m], r, J, true);
-        const long long fi = lv_pose_first<DIM>(v.rel_i[m]), fj = lv_pose_first<DIM>(v.rel_j[m]);
+            gn_rel_jac3(pi, pj, v.meas.rel_t + 3 * m, v.meas.rel_R + 9 * m, v.meas.rel_kappa[m], v.meas.rel_tau[m], r, J, true);
+        const long long fi = lv_pose_first<DIM>(v.meas.rel_i[m]), fj = lv_pose_first<DIM>(v.meas.rel_j[m]);
         LvSums S;
         S.load(sums, stride);
         for (int c = 0; c < live; ++c) {
@@ -162,16 +163,16 @@ __device__ __forceinline__ void lv_measure_lane(const GnView& v, const long long
         const int64_t e = m - v.n_rel;
         double J[NG];
         if constexpr (DIM == 2) {
-            const double* pa = gn_point2(v.X, v.Np, v.rng_a[e]);
-            const double* pb = gn_point2(v.X, v.Np, v.rng_b[e]);
-            (void)gn_range_jac(pa[0], pa[1], pb[0], pb[1], v.rng_dist[e], v.rng_prec[e], J, true);
+            const double* pa = gn_point2(v.X, v.Np, v.meas.rng_a[e]);
+            const double* pb = gn_point2(v.X, v.Np, v.meas.rng_b[e]);
+            (void)gn_range_jac(pa[0], pa[1], pb[0], pb[1], v.meas.rng_dist[e], v.meas.rng_prec[e], J, true);
         } else {
-            const double* pa = gn_point3(v.X, v.Np, v.rng_a[e]);
-            const double* pb = gn_point3(v.X, v.Np, v.rng_b[e]);
+            const double* pa = gn_point3(v.X, v.Np, v.meas.rng_a[e]);
+            const double* pb = gn_point3(v.X, v.Np, v.meas.rng_b[e]);
             const double a3[3] = {pa[0], pa[1], pa[2]}, b3[3] = {pb[0], pb[1], pb[2]};
-            (void)gn_range_jac3(a3, b3, v.rng_dist[e], v.rng_prec[e], J, true);
+            (void)gn_range_jac3(a3, b3, v.meas.rng_dist[e], v.meas.rng_prec[e], J, true);
         }
-        const long long fa = lv_point_first<DIM>(v.Np, v.rng_a[e]), fb = lv_point_first<DIM>(v.Np, v.rng_b[e]);
+        const long long fa = lv_point_first<DIM>(v.Np, v.meas.rng_a[e]), fb = lv_point_first<DIM>(v.Np, v.meas.rng_b[e]);
         LvSums S;
         S.load(sums, stride);
         for (int c = 0; c < live; ++c) {
@@ -188,15 +189,15 @@ __device__ __forceinline__ void lv_measure_lane(const GnView& v, const long long
         S.store(sums, stride);
     } else if (m < v.n_rel + v.n_rng + v.n_pri) {
         const int64_t e = m - v.n_rel - v.n_rng;
-        const double* l = v.X + PS * v.Np + DIM * (int64_t)v.pri_l[e];
+        const double* l = v.X + PS * v.Np + DIM * (int64_t)v.meas.pri_l[e];
         double r[DIM], sw;
         if constexpr (DIM == 2) {
-            sw = gn_prior_jac(l[0], l[1], v.pri_t + 2 * e, v.pri_prec[e], r);
+            sw = gn_prior_jac(l[0], l[1], v.meas.pri_t + 2 * e, v.meas.pri_prec[e], r);
         } else {
             const double l3[3] = {l[0], l[1], l[2]};
-            sw = gn_prior_jac3(l3, v.pri_t + 3 * e, v.pri_prec[e], r);
+            sw = gn_prior_jac3(l3, v.meas.pri_t + 3 * e, v.meas.pri_prec[e], r);
         }
-        const long long fl = lv_point_first<DIM>(v.Np, v.Np + (int64_t)v.pri_l[e]);
+        const long long fl = lv_point_first<DIM>(v.Np, v.Np + (int64_t)v.meas.pri_l[e]);
         LvSums S;
         S.load(sums, stride);
         for (int c = 0; c < live; ++c) {
@@ -376,8 +377,7 @@ struct LvMeasure {
         if (!q.take) return;
         l.s0 = q.s0; l.live = live; l.take = q.take;
         const unsigned grid = (unsigned)std::max<long long>(1, (l.M + n_pairs + kThreads - 1) / kThreads);
-        if (R.P.dim == 2) hipLaunchKernelGGL(k_lv_measure<2>, dim3(grid), dim3(kThreads), 0, st, l);
-        else hipLaunchKernelGGL(k_lv_measure<3>, dim3(grid), dim3(kThreads), 0, st, l);
+        gn_dim(R.P.dim, [&](auto dim) { hipLaunchKernelGGL(k_lv_measure<decltype(dim)::value>, dim3(grid), dim3(kThreads), 0, st, l); });
     }
     void end(hipStream_t st) {
         const size_t M = (size_t)l.M, f8 = sizeof(double), np = (size_t)n_pairs;
@@ -427,15 +427,15 @@ int lv_pair_solve(Refine& R, const double* poses, const double* landmarks, const
         const int live = std::min<int>(block_width, n_pairs - c0);
         a.c0 = 0; a.live = live;
         l.c0 = c0; l.live = live;
-        if (P.dim == 2) hipLaunchKernelGGL(k_lv_pair_rhs<2>, dim3((unsigned)n_rblocks, (unsigned)NV), dim3(kMvThreads), 0, st, a, l);
-        else hipLaunchKernelGGL(k_lv_pair_rhs<3>, dim3((unsigned)n_rblocks, (unsigned)NV), dim3(kMvThreads), 0, st, a, l);
+        gn_dim(P.dim, [&](auto dim) {
+            hipLaunchKernelGGL(k_lv_pair_rhs<decltype(dim)::value>, dim3((unsigned)n_rblocks, (unsigned)NV), dim3(kMvThreads), 0, st, a, l);
+        });
         mv_block_pcg(be, W, a, NV, n_rblocks, max_iters, flags, st);
         // the true residual of every column of the block (one more product, w = H x) against its g, and g'x
         a.all_columns = 1; a.p_in = W.x.d;
         mv_launch_product(a, NV, st);
         hipLaunchKernelGGL(k_ps_residual, dim3((unsigned)n_rblocks, (unsigned)live), dim3(kMvThreads), 0, st, a, (const double*)L.b.d);
-        if (P.dim == 2) hipLaunchKernelGGL(k_lv_pair_dot<2>, dim3(1), dim3(64), 0, st, l);
-        else hipLaunchKernelGGL(k_lv_pair_dot<3>, dim3(1), dim3(64), 0, st, l);
+        gn_dim(P.dim, [&](auto dim) { hipLaunchKernelGGL(k_lv_pair_dot<decltype(dim)::value>, dim3(1), dim3(64), 0, st, l); });
         HIP_CHECK(hipGetLastError());
         staged_d2h(res_part.data(), W.res_part.d, (size_t)live * (size_t)n_rblocks * sizeof(double), st);
         if (solutions) staged_d2h(solutions + (size_t)c0 * (size_t)n, W.x.d, (size_t)live * (size_t)n * sizeof(double), st);

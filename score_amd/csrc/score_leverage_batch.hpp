@@ -189,13 +189,10 @@ struct GblMeasure {
         if (!p.any) return;
         const dim3 bt(kThreads);
         const unsigned pair_blocks = (unsigned)((plan.pairs + kThreads - 1) / kThreads);
-        if (dim == 2) {
-            hipLaunchKernelGGL(k_gbl_measure<2>, dim3((unsigned)B.n_mblocks), bt, 0, st, q, l, p.x);
-            if (pair_blocks) hipLaunchKernelGGL(k_gbl_pairs<2>, dim3(pair_blocks), bt, 0, st, q, l, p.x);
-        } else {
-            hipLaunchKernelGGL(k_gbl_measure<3>, dim3((unsigned)B.n_mblocks), bt, 0, st, q, l, p.x);
-            if (pair_blocks) hipLaunchKernelGGL(k_gbl_pairs<3>, dim3(pair_blocks), bt, 0, st, q, l, p.x);
-        }
+        gn_dim(dim, [&](auto d) {
+            hipLaunchKernelGGL(k_gbl_measure<decltype(d)::value>, dim3((unsigned)B.n_mblocks), bt, 0, st, q, l, p.x);
+            if (pair_blocks) hipLaunchKernelGGL(k_gbl_pairs<decltype(d)::value>, dim3(pair_blocks), bt, 0, st, q, l, p.x);
+        });
     }
     // the sums of the members that took part, member after member
     void end(const GbsPlan& draws, const std::vector<GbsShape>&, std::vector<double>& host, hipStream_t st) {
@@ -267,16 +264,16 @@ int gbl_pair_solve(Batch& B, const double* poses, const double* landmarks, const
         q.k0 = k * W;
         const dim3 gu((unsigned)B.n_ublocks, (unsigned)NV);
         group_pcg(be, a, K.pcg, NV, max_iters, K.zb.d, [&](const GbmArgs& p) {
-            if (U.dim == 2) hipLaunchKernelGGL(k_gbl_pair_rhs<2>, gu, bt, 0, st, p, q, l);
-            else hipLaunchKernelGGL(k_gbl_pair_rhs<3>, gu, bt, 0, st, p, q, l);
+            gn_dim(U.dim, [&](auto dim) { hipLaunchKernelGGL(k_gbl_pair_rhs<decltype(dim)::value>, gu, bt, 0, st, p, q, l); });
         }, words);
         // the true residual of every column of the pass (one more product, w = H x) against its g, and g'x
         a.all_slots = 1; a.p_in = K.pcg.x.d;
         gbm_product(a, st);
         hipLaunchKernelGGL(k_gbs_residual, gu, bt, 0, st, a, q, (const double*)a.w);
         const unsigned dot_blocks = (unsigned)((G * W + kThreads - 1) / kThreads);
-        if (U.dim == 2) hipLaunchKernelGGL(k_gbl_pair_dot<2>, dim3(dot_blocks), bt, 0, st, q, l, (const double*)K.pcg.x.d, G);
-        else hipLaunchKernelGGL(k_gbl_pair_dot<3>, dim3(dot_blocks), bt, 0, st, q, l, (const double*)K.pcg.x.d, G);
+        gn_dim(U.dim, [&](auto dim) {
+            hipLaunchKernelGGL(k_gbl_pair_dot<decltype(dim)::value>, dim3(dot_blocks), bt, 0, st, q, l, (const double*)K.pcg.x.d, G);
+        });
         HIP_CHECK(hipGetLastError());
         part.resize((size_t)NV * nub);
         staged_d2h(part.data(), K.res_part.d, part.size() * sizeof(double), st);

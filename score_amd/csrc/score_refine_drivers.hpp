@@ -4,7 +4,7 @@
 //   gb_lock_step       the runs of a group's members in lock-step: gb_start, then gb_round until no member solves
 //   gn_robust_refine   the GNC-TLS schedule around gn_lm_run on a single handle
 //   gbr_lock_step      the schedule per member around gb_start / gb_round
-// The backends are the HIP handles (score_hip.hip: score_refine, score_refine_batch), the CPU twin's score_refine, and the
+// The backends are the HIP handles (score_refine_handles.hpp: score_refine, score_refine_batch), the CPU twin's score_refine, and the
 // scripted one of tests/tools/refine_rule_check.cpp, which runs every script through all four.
 #pragma once
 

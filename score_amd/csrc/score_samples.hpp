@@ -73,12 +73,13 @@ SCORE_GN_HD void ps_measurement(const GnView& v, int64_t m, uint64_t seed, int64
     constexpr int PS = DIM == 2 ? 3 : 12, NR = DIM == 2 ? 6 : 12, NG = 2 * DIM;
     if (m < v.n_rel) {
         double r[NR], J[NR][NR];
-        const double* pi = v.X + PS * (int64_t)v.rel_i[m];
-        const double* pj = v.X + PS * (int64_t)v.rel_j[m];
+        const double* pi = v.X + PS * (int64_t)v.meas.rel_i[m];
+        const double* pj = v.X + PS * (int64_t)v.meas.rel_j[m];
         if constexpr (DIM == 2)
-            gn_rel_jac(pi[0], pi[1], pi[2], pj[0], pj[1], pj[2], v.rel_t + 2 * m, v.rel_R + 4 * m, v.rel_kappa[m], v.rel_tau[m], r, J, true);
+            gn_rel_jac(pi[0], pi[1], pi[2], pj[0], pj[1], pj[2], v.meas.rel_t + 2 * m, v.meas.rel_R + 4 * m, v.meas.rel_kappa[m],
+                       v.meas.rel_tau[m], r, J, true);
         else
-            gn_rel_jac3(pi, pj, v.rel_t + 3 * m, v.rel_R + 9 * m, v.rel_kappa[m], v.rel_tau[m], r, J, true);
+            gn_rel_jac3(pi, pj, v.meas.rel_t + 3 * m, v.meas.rel_R + 9 * m, v.meas.rel_kappa[m], v.meas.rel_tau[m], r, J, true);
         for (int k = 0; k < live; ++k) {
             double z[NR], b[NR];
             ps_noise_rows<NR>(seed, m, s0 + k, z);
@@ -90,14 +91,14 @@ SCORE_GN_HD void ps_measurement(const GnView& v, int64_t m, uint64_t seed, int64
         const int64_t e = m - v.n_rel;
         double J[NG];
         if constexpr (DIM == 2) {
-            const double* pa = gn_point2(v.X, v.Np, v.rng_a[e]);
-            const double* pb = gn_point2(v.X, v.Np, v.rng_b[e]);
-            (void)gn_range_jac(pa[0], pa[1], pb[0], pb[1], v.rng_dist[e], v.rng_prec[e], J, true);
+            const double* pa = gn_point2(v.X, v.Np, v.meas.rng_a[e]);
+            const double* pb = gn_point2(v.X, v.Np, v.meas.rng_b[e]);
+            (void)gn_range_jac(pa[0], pa[1], pb[0], pb[1], v.meas.rng_dist[e], v.meas.rng_prec[e], J, true);
         } else {
-            const double* pa = gn_point3(v.X, v.Np, v.rng_a[e]);
-            const double* pb = gn_point3(v.X, v.Np, v.rng_b[e]);
+            const double* pa = gn_point3(v.X, v.Np, v.meas.rng_a[e]);
+            const double* pb = gn_point3(v.X, v.Np, v.meas.rng_b[e]);
             const double a3[3] = {pa[0], pa[1], pa[2]}, b3[3] = {pb[0], pb[1], pb[2]};
-            (void)gn_range_jac3(a3, b3, v.rng_dist[e], v.rng_prec[e], J, true);
+            (void)gn_range_jac3(a3, b3, v.meas.rng_dist[e], v.meas.rng_prec[e], J, true);
         }
         for (int k = 0; k < live; ++k) {
             const double z = ps_noise(seed, m, s0 + k, 0);
@@ -109,13 +110,13 @@ SCORE_GN_HD void ps_measurement(const GnView& v, int64_t m, uint64_t seed, int64
         }
     } else if (m < v.n_rel + v.n_rng + v.n_pri) {
         const int64_t e = m - v.n_rel - v.n_rng;
-        const double* l = v.X + PS * v.Np + DIM * (int64_t)v.pri_l[e];
+        const double* l = v.X + PS * v.Np + DIM * (int64_t)v.meas.pri_l[e];
         double r[DIM], sw;
         if constexpr (DIM == 2) {
-            sw = gn_prior_jac(l[0], l[1], v.pri_t + 2 * e, v.pri_prec[e], r);
+            sw = gn_prior_jac(l[0], l[1], v.meas.pri_t + 2 * e, v.meas.pri_prec[e], r);
         } else {
             const double l3[3] = {l[0], l[1], l[2]};
-            sw = gn_prior_jac3(l3, v.pri_t + 3 * e, v.pri_prec[e], r);
+            sw = gn_prior_jac3(l3, v.meas.pri_t + 3 * e, v.meas.pri_prec[e], r);
         }
         for (int k = 0; k < live; ++k) {
             double z[DIM], b[DIM];
@@ -368,8 +369,7 @@ struct PsMoments {
     template <class Refine>
     void block(Refine& R, const PsArgs& q, const MvArgs& a, int k0, int live, hipStream_t st) {
         if (q.take) {
-            if (R.P.dim == 2) hipLaunchKernelGGL(k_ps_moments<2>, dim3(n_vblocks), dim3(kThreads), 0, st, q);
-            else hipLaunchKernelGGL(k_ps_moments<3>, dim3(n_vblocks), dim3(kThreads), 0, st, q);
+            gn_dim(R.P.dim, [&](auto dim) { hipLaunchKernelGGL(k_ps_moments<decltype(dim)::value>, dim3(n_vblocks), dim3(kThreads), 0, st, q); });
         }
         if (C) {
             hipLaunchKernelGGL(k_ps_select, dim3((unsigned)((C + kMvThreads - 1) / kMvThreads), (unsigned)live), dim3(kMvThreads), 0, st, a, d_steps.d);
@@ -406,7 +406,7 @@ int ps_solve(Refine& R, const std::string& who, const double* poses, const doubl
     R.h_at_point(poses, landmarks, who, "blocks of draws need");
     be.derive_rho_data(false);
     const int NV = mv_slots(block_width);
-    const int64_t rows = P.dim == 2 ? ps_rows<2>(P.n_rel(), P.n_rng(), P.n_pri()) : ps_rows<3>(P.n_rel(), P.n_rng(), P.n_pri());
+    const int64_t rows = gn_dim(P.dim, [&](auto dim) { return ps_rows<decltype(dim)::value>(P.n_rel(), P.n_rng(), P.n_pri()); });
     auto& W = R.mv;
     auto& Q = R.ps;
     W.reserve(P, R.product_tiles(), be.n_prec, be.H->bs * be.n_join_seps, st);
@@ -459,8 +459,7 @@ int ps_solve(Refine& R, const std::string& who, const double* poses, const doubl
         q.s0 = first_sample + k0; q.live = live;
         // the block's noise and right-hand sides
         const double tb = now_ms();
-        if (P.dim == 2) hipLaunchKernelGGL(k_ps_blocks<2>, dim3((unsigned)R.n_mblocks), dim3(kThreads), 0, st, q);
-        else hipLaunchKernelGGL(k_ps_blocks<3>, dim3((unsigned)R.n_mblocks), dim3(kThreads), 0, st, q);
+        gn_dim(P.dim, [&](auto dim) { hipLaunchKernelGGL(k_ps_blocks<decltype(dim)::value>, dim3((unsigned)R.n_mblocks), dim3(kThreads), 0, st, q); });
         mv_with_slots(NV, [&](auto nv) {
             hipLaunchKernelGGL(k_ps_gather<decltype(nv)::value>, dim3((unsigned)Q.tiles.n), dim3(kMvThreads), 0, st, q);
         });

@@ -230,7 +230,7 @@ inline std::vector<GbsShape> gbs_shapes(const GbUnion& U, Columns columns) {
     const int64_t dp = U.dp(), d = U.dim;
     for (int g = 0; g < U.count; ++g) {
         const GbMember& M = U.members[(size_t)g];
-        const int64_t rows = U.dim == 2 ? ps_rows<2>(M.n_rel, M.n_rng, M.n_pri) : ps_rows<3>(M.n_rel, M.n_rng, M.n_pri);
+        const int64_t rows = gn_dim(U.dim, [&](auto dim) { return ps_rows<decltype(dim)::value>(M.n_rel, M.n_rng, M.n_pri); });
         shapes.push_back(GbsShape{M.n, rows, dp * dp * (M.Np - 1) + d * d * M.Nl, (int64_t)columns(g)});
     }
     return shapes;
@@ -309,8 +309,7 @@ struct GbsMoments {
     void pass(Batch& B, const GbsArgs& q, const GbsPass& p, hipStream_t st) {
         const dim3 bt(kThreads);
         if (p.any) {
-            if (U->dim == 2) hipLaunchKernelGGL(k_gbs_moments<2>, dim3((unsigned)B.n_sblocks), bt, 0, st, q, p.x);
-            else hipLaunchKernelGGL(k_gbs_moments<3>, dim3((unsigned)B.n_sblocks), bt, 0, st, q, p.x);
+            gn_dim(U->dim, [&](auto dim) { hipLaunchKernelGGL(k_gbs_moments<decltype(dim)::value>, dim3((unsigned)B.n_sblocks), bt, 0, st, q, p.x); });
         }
         if (n_sel && steps) {
             hipLaunchKernelGGL(k_gbs_select, dim3((unsigned)((n_sel + kThreads - 1) / kThreads), (unsigned)p.NV), bt, 0, st, q, p.x);
@@ -450,8 +449,7 @@ int gbs_solve(Batch& B, const std::string& who, const double* poses, const doubl
         q.k0 = k * W; q.s0 = first_sample + (int64_t)k * W;
         // the pass's noise and right-hand sides
         const double tb = now_ms();
-        if (U.dim == 2) hipLaunchKernelGGL(k_gbs_blocks<2>, dim3((unsigned)B.n_mblocks), bt, 0, st, q);
-        else hipLaunchKernelGGL(k_gbs_blocks<3>, dim3((unsigned)B.n_mblocks), bt, 0, st, q);
+        gn_dim(U.dim, [&](auto dim) { hipLaunchKernelGGL(k_gbs_blocks<decltype(dim)::value>, dim3((unsigned)B.n_mblocks), bt, 0, st, q); });
         mv_with_slots(NV, [&](auto nv) {
             hipLaunchKernelGGL(k_gbs_gather<decltype(nv)::value>, dim3((unsigned)Q.tiles.n), bt, 0, st, q);
         });

@@ -148,3 +148,19 @@ def test_rule_and_drivers_on_scripted_runs_under_sanitizers(tmp_path):
     run = subprocess.run([exe], capture_output=True, text=True)
     assert run.returncode == 0 and "ERROR" not in run.stderr and "runtime error" not in run.stderr, run.stderr
     assert "every exit reached" in run.stdout
+
+
+def test_a_members_view_equals_the_view_of_a_handle_on_it_alone_under_sanitizers(tmp_path):
+    """tests/tools/refine_view_check.cpp: the group's measurement table advanced to a member (gn_meas_from of csrc/score_gn.hpp,
+    what gb_view hands a workgroup) against gn_build of that member alone, every integer and double compared with ==; a 2-D and
+    a 3-D group of three: one member with landmarks, ranges and priors, one without landmarks, one with ranges and no priors."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is needed to build the stand-alone program"
+    exe = str(tmp_path / "refine_view_check")
+    subprocess.run([gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-I", os.path.join(root, "score_amd", "csrc"), "-o", exe,
+                    os.path.join(root, "tests", "tools", "refine_view_check.cpp")], check=True)
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0 and "ERROR" not in run.stderr and "runtime error" not in run.stderr, run.stderr
+    assert "every member's view equals its own" in run.stdout
