@@ -231,7 +231,7 @@ TABLES_SINCE = (CURVATURE,)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# two conventions of the calls
+# three conventions of the calls
 # ---------------------------------------------------------------------------------------------------------------------
 def ptr(a, kind=_f64p):
     """The array's data as ``kind``; null for None or an empty array."""
@@ -243,3 +243,18 @@ def steps_and_converged(its):
     -(steps + 1)."""
     converged = its >= 0
     return np.where(converged, its, -its - 1), converged
+
+
+class Cutter:
+    """The members' consecutive pieces of a group call's flat outputs: ``cut(a, size, shape)`` is a copy of the next ``size``
+    entries of ``a`` (None stays None), every array counted for itself.  A member that took no room in ``a`` is not cut."""
+
+    def __init__(self):
+        self.at = {}
+
+    def __call__(self, flat, size, shape=None):
+        if flat is None:
+            return None
+        at = self.at.get(id(flat), 0)
+        self.at[id(flat)] = at + size
+        return flat[at : at + size].reshape((size,) if shape is None else shape).copy()

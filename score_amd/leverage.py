@@ -29,7 +29,7 @@ from typing import Optional
 import numpy as np
 
 from .bindings import LEVERAGE, ScoreMarginalsInfo, ScoreSamplesInfo, bind, ptr, steps_and_converged
-from .marginals import MAX_BLOCK_WIDTH, _problem_and_point
+from .marginals import MAX_BLOCK_WIDTH, _problem_and_point, check_block_solve
 from .refine import _point_arrays, _Problem3D, unknown_sizes
 from .samples import SamplesHandle, _python_draws, measurement_rows, ordered_jacobian
 from .solver import _i32p
@@ -264,10 +264,7 @@ class PredictedRanges:
 def _check_block(block_width, rel_tol, max_iters, engine):
     if engine not in ("device", "python"):
         raise ValueError("engine must be 'device' or 'python'")
-    if int(block_width) != block_width or not 1 <= int(block_width) <= MAX_BLOCK_WIDTH:
-        raise ValueError(f"block_width must be an integer in 1..{MAX_BLOCK_WIDTH}")
-    if not rel_tol > 0 or max_iters < 1:
-        raise ValueError("rel_tol must be positive and max_iters at least 1")
+    check_block_solve(block_width, rel_tol, max_iters)
 
 
 def _singular(who, failed, total, what, max_iters):

@@ -4,8 +4,8 @@ csrc/score_leverage_batch.hpp).
 ``range_leverage`` / ``predicted_range_variances`` take one graph, build one refinement handle and run block solves whose
 launches are latency-bound on a small world.  The questions they answer are study questions -- over 64 generated worlds,
 which share of the ranges is uncontrolled?  what variance does a candidate beacon-pose range have in each world? -- so
-``range_leverage_batch`` and ``predicted_range_variances_batch`` hand the graphs to the device as groups, as
-``posterior_samples_batch`` does: one union vector carries one draw (one pair's column) of every member.  Graph i's draws
+``range_leverage_batch`` and ``predicted_range_variances_batch`` hand the graphs to the device as groups, by the rule of
+``score_amd/groups.py``: one union vector carries one draw (one pair's column) of every member.  Graph i's draws
 are those of ``range_leverage(..., seed=seed + i)`` on it alone (the same noise stream, the same right-hand sides), its sums
 those of that call up to the rounding of the two iterations.
 
@@ -20,11 +20,12 @@ from typing import Optional
 
 import numpy as np
 
-from .bindings import LEVERAGE_BATCH, ScoreMarginalsBatchInfo, ScoreSamplesBatchInfo, _u64p, bind, ptr, steps_and_converged
+from .bindings import LEVERAGE_BATCH, Cutter, ScoreMarginalsBatchInfo, ScoreSamplesBatchInfo, _u64p, bind, ptr, steps_and_converged
+from .groups import group_size, grouped, paired, per_graph, run_chunks
 from .leverage import (Leverage, PredictedRanges, _check_block, _singular, measurement_counts, pair_ids, predicted_range_variances,
                        range_leverage)
 from .marginals import MAX_BLOCK_WIDTH, _problem_and_point
-from .samples_batch import _check_draw_arguments, _per_member, _seeds_of
+from .samples_batch import _check_draw_arguments, _seeds_of, draw_info
 from .solver import _i32p
 
 # the symbols include/score_leverage_batch.h declares
@@ -53,8 +54,8 @@ def batch_leverage(handle, points, pairs_per_member, n_samples, seeds, first_sam
     G = len(probs)
     if len(points) != G:
         raise ValueError("one point per member expected")
-    counts = [int(s) for s in _per_member(n_samples, G, "n_samples")]
-    keys = [int(s) & 0xFFFFFFFFFFFFFFFF for s in _per_member(seeds, G, "seeds")]
+    counts = [int(s) for s in per_graph(n_samples, G, "n_samples", none=False, scalar=True)]
+    keys = [int(s) & 0xFFFFFFFFFFFFFFFF for s in per_graph(seeds, G, "seeds", none=False, scalar=True)]
     lib = bind(handle.lib, LEVERAGE_BATCH)
     _, poses, lms = handle._flat_points(points)
     ids, pair_ptr, pa, pb = _flat_pairs(pairs_per_member, G)
@@ -76,19 +77,16 @@ def batch_leverage(handle, points, pairs_per_member, n_samples, seeds, first_sam
                                          C.byref(info))
     if rc < 0:
         raise RuntimeError(f"score_refine_batch_leverage failed: {lib.score_last_error().decode()}")
-    rec = info.as_dict()
-    out, at_m, at_d = [], 0, 0
+    rec, cut, out = info.as_dict(), Cutter(), []
     for g in range(G):
-        S, M = on[g], n_meas[g]
-        iterations, converged = steps_and_converged(its[at_d : at_d + S])
-        member = {k: (sums[k][at_m : at_m + M].copy() if S else np.zeros(M)) for k in SUMS}
+        S, M, n_pairs = on[g], n_meas[g], len(ids[g])
+        iterations, converged = steps_and_converged(cut(its, S))
+        member = {k: (cut(sums[k], M) if S else np.zeros(M)) for k in SUMS}
         member.update({
-            "pair_sum": psum[pair_ptr[g] : pair_ptr[g + 1]].copy(), "pair_sq": psq[pair_ptr[g] : pair_ptr[g + 1]].copy(),
-            "residuals": res[at_d : at_d + S].copy(), "iterations": iterations, "converged": converged, "determined": int(det[g]),
-            "rc": 0 if np.all(converged) else 1, "info": dict(rec, samples=S, batches=-(-S // int(block_width))),
+            "pair_sum": cut(psum, n_pairs), "pair_sq": cut(psq, n_pairs), "residuals": cut(res, S), "iterations": iterations,
+            "converged": converged, "determined": int(det[g]), "rc": 0 if np.all(converged) else 1,
+            "info": dict(rec, samples=S, batches=-(-S // int(block_width))),
         })
-        at_m += M if S else 0
-        at_d += S
         out.append(member)
     return rc, out, rec
 
@@ -112,14 +110,11 @@ def batch_range_variances(handle, points, pairs_per_member, rel_tol=1e-10, max_i
                                                 ptr(res), ptr(its, _i32p), C.byref(info))
     if rc < 0:
         raise RuntimeError(f"score_refine_batch_range_variances failed: {lib.score_last_error().decode()}")
-    rec = info.as_dict()
-    out = []
-    for g in range(G):
-        cut = slice(int(pair_ptr[g]), int(pair_ptr[g + 1]))
-        iterations, converged = steps_and_converged(its[cut])
-        out.append({"rc": 0 if np.all(converged) else 1, "variances": var[cut].copy(), "distances": dist[cut].copy(),
-                    "residuals": res[cut].copy(), "iterations": iterations, "converged": converged,
-                    "info": dict(rec, columns=len(ids[g]))})
+    rec, cut, out = info.as_dict(), Cutter(), []
+    for n_pairs in map(len, ids):
+        iterations, converged = steps_and_converged(cut(its, n_pairs))
+        out.append({"rc": 0 if np.all(converged) else 1, "variances": cut(var, n_pairs), "distances": cut(dist, n_pairs),
+                    "residuals": cut(res, n_pairs), "iterations": iterations, "converged": converged, "info": dict(rec, columns=n_pairs)})
     return rc, out, rec
 
 
@@ -138,60 +133,29 @@ def group_leverage(handle, probs, points, names, indices, number, counts, seeds,
         failed = int(np.count_nonzero(~m["converged"]))
         if failed:
             raise _failed("range_leverage_batch", i, failed, S, "draws", max_iters)
-        info = {"pcg_iters": int(rec["pcg_iters"]), "batches": int(m["info"]["batches"]), "setup_ms": float(rec["setup_ms"]),
-                "rhs_ms": float(rec["rhs_ms"]), "solve_ms": float(rec["solve_ms"]), "iterations": m["iterations"],
-                "residuals": m["residuals"], "engine": "device", "group": number, "passes": int(rec["passes"]),
-                "determined": m["determined"]}
-        out.append((Leverage(prob, point, m, S, nm), info))
+        out.append((Leverage(prob, point, m, S, nm), draw_info(rec, m, number, "device")))
     return out
 
 
-def _groups(datas, results, range_weights, loop_closure_weights, who):
-    """{dimension: [(graph number, problem, point)]} as ``posterior_samples_batch`` groups its graphs."""
-    from .refine_batch import _weights_of
+def _members(datas, results, range_weights, loop_closure_weights, who):
+    """(graphs, estimates, range weights, loop-closure weights, ``groups.grouped`` of (graph number, problem, point))."""
+    datas, results = paired(datas, results)
+    rws = per_graph(range_weights, len(datas), "range_weights")
+    lws = per_graph(loop_closure_weights, len(datas), "loop_closure_weights")
 
-    datas, results = list(datas), list(results)
-    if len(datas) != len(results):
-        raise ValueError(f"one estimate per graph expected: {len(datas)} graphs, {len(results)} estimates")
-    rws = _weights_of(range_weights, len(datas), "range_weights")
-    lws = _weights_of(loop_closure_weights, len(datas), "loop_closure_weights")
-    groups: dict = {}
-    for i, (data, res) in enumerate(zip(datas, results)):
-        if data.dimension not in (2, 3):
-            raise ValueError(f"graph {i}: dimension must be 2 or 3")
-        try:
-            prob, point = _problem_and_point(data, res, rws[i], lws[i])
-        except ValueError as e:
-            raise ValueError(f"graph {i}: {str(e).replace('marginal_covariances', who)}") from None
+    def member(i, data, res):
+        prob, point = _problem_and_point(data, res, rws[i], lws[i])
         if prob.n == 0:
-            raise ValueError(f"graph {i}: the graph has no unknowns")
-        groups.setdefault(data.dimension, []).append((i, prob, point))
-    return datas, results, rws, lws, groups
+            raise ValueError("the graph has no unknowns")
+        return prob, point
 
-
-def _pairs_of(pairs, count: int) -> list:
-    """One entry per graph: None (no pairs) or that graph's list of name pairs."""
-    if pairs is None:
-        return [None] * count
-    pairs = list(pairs)
-    if len(pairs) != count:
-        raise ValueError(f"pairs: one entry per graph expected ({count}), got {len(pairs)}")
-    return pairs
+    return datas, results, rws, lws, grouped(datas, results, member, who=who)
 
 
 def _ids_of(groups, names, who) -> dict:
     """{graph number: (C, 2) variable ids or None} of the graphs' name pairs; a bad pair raises with ``graph i:`` in front."""
     return {i: pair_ids(prob, names[i], f"{who}: graph {i}") if names[i] is not None else None
             for members in groups.values() for i, prob, _ in members}
-
-
-def _chunks(groups, max_group):
-    number = 0
-    for dim in sorted(groups):
-        members = groups[dim]
-        for c0 in range(0, len(members), int(max_group)):
-            yield number, members[c0 : c0 + int(max_group)]
-            number += 1
 
 
 def range_leverage_batch(datas, results, n_samples=256, seed=0, first_sample: int = 0, pairs=None, range_weights=None,
@@ -202,24 +166,21 @@ def range_leverage_batch(datas, results, n_samples=256, seed=0, first_sample: in
     entry per graph (None or a list of name pairs), ``range_weights`` / ``loop_closure_weights`` lists with one entry per
     graph.  ``n_samples``: an integer or one per graph.  ``seed``: a list with one seed per graph, or an integer -- graph i then
     draws from the stream of ``seed + i`` (``posterior_samples_batch``'s rule), so its draws are those of
-    ``range_leverage(..., seed=seed + i)``.  The graphs are grouped by dimension, in chunks of at most ``max_group``, as
-    ``posterior_samples_batch`` groups them; each group is one device handle and one ``score_refine_batch_leverage`` call
+    ``range_leverage(..., seed=seed + i)``.  The graphs are grouped by dimension, in chunks of at most ``max_group`` (the
+    rule of ``score_amd/groups.py``); each group is one device handle and one ``score_refine_batch_leverage`` call
     (``engine="device"``) or ``range_leverage(engine="python")`` graph by graph.  Returns a list of ``(Leverage, info)`` in input
     order: per graph what ``range_leverage`` returns, plus ``group``, ``passes`` and ``determined`` on the device.  Draws that do
     not converge raise RuntimeError naming the first such graph."""
-    from .refine_batch import RefineBatchHandle
-
     _check_block(block_width, rel_tol, max_iters, engine)
-    if int(max_group) < 1:
-        raise ValueError("max_group must be at least 1")
+    group_size(max_group)
     datas, results = list(datas), list(results)
-    counts = _per_member(n_samples, len(datas), "n_samples")
+    counts = per_graph(n_samples, len(datas), "n_samples", none=False, scalar=True)
     if datas:
         _check_draw_arguments(counts, first_sample, block_width, rel_tol, max_iters)
     counts = [int(s) for s in counts]
     seeds = _seeds_of(seed, len(datas))
-    names = _pairs_of(pairs, len(datas))
-    datas, results, rws, lws, groups = _groups(datas, results, range_weights, loop_closure_weights, "range_leverage")
+    names = per_graph(pairs, len(datas), "pairs")
+    datas, results, rws, lws, groups = _members(datas, results, range_weights, loop_closure_weights, "range_leverage")
     _ids_of(groups, names, "range_leverage_batch")  # (the pairs' errors before any work)
     out: list = [None] * len(datas)
     if engine == "python":
@@ -230,14 +191,12 @@ def range_leverage_batch(datas, results, n_samples=256, seed=0, first_sample: in
             except RuntimeError as e:
                 raise RuntimeError(str(e).replace("range_leverage:", f"range_leverage_batch: graph {i}:")) from None
         return out
-    for number, chunk in _chunks(groups, max_group):
-        idx, probs, points = ([m[k] for m in chunk] for k in range(3))
-        with RefineBatchHandle(probs, lib_path, solver_settings) as h:
-            got = group_leverage(h, probs, points, [names[i] for i in idx], idx, number, [counts[i] for i in idx],
-                                 [seeds[i] for i in idx], int(first_sample), rel_tol, max_iters, int(block_width))
-        for i, g in zip(idx, got):
-            out[i] = g
-    return out
+
+    def body(handle, number, idx, probs, points, extras):
+        return group_leverage(handle, probs, points, [names[i] for i in idx], idx, number, [counts[i] for i in idx],
+                              [seeds[i] for i in idx], int(first_sample), rel_tol, max_iters, int(block_width))
+
+    return run_chunks(groups, max_group, out, body, True, lib_path, solver_settings)
 
 
 def predicted_range_variances_batch(datas, results, pairs, range_weights=None, loop_closure_weights=None, rel_tol: float = 1e-10,
@@ -249,14 +208,11 @@ def predicted_range_variances_batch(datas, results, pairs, range_weights=None, l
     Returns a list of ``(PredictedRanges, info)`` in input order: per graph what ``predicted_range_variances`` returns, plus
     ``group`` and ``passes`` on the device.  A column that does not converge raises RuntimeError naming the first such
     graph."""
-    from .refine_batch import RefineBatchHandle
-
     _check_block(block_width, rel_tol, max_iters, engine)
-    if int(max_group) < 1:
-        raise ValueError("max_group must be at least 1")
+    group_size(max_group)
     datas = list(datas)
-    names = [[tuple(p) for p in nm] if nm is not None else [] for nm in _pairs_of(pairs, len(datas))]
-    datas, results, rws, lws, groups = _groups(datas, results, range_weights, loop_closure_weights, "predicted_range_variances")
+    names = [[tuple(p) for p in nm] if nm is not None else [] for nm in per_graph(pairs, len(datas), "pairs")]
+    datas, results, rws, lws, groups = _members(datas, results, range_weights, loop_closure_weights, "predicted_range_variances")
     ids_of = _ids_of(groups, names, "predicted_range_variances_batch")  # (the pairs' errors before any work)
     out: list = [None] * len(datas)
 
@@ -275,20 +231,19 @@ def predicted_range_variances_batch(datas, results, pairs, range_weights=None, l
             except RuntimeError as e:
                 raise RuntimeError(str(e).replace("predicted_range_variances:", f"predicted_range_variances_batch: graph {i}:")) from None
         return out
-    for number, chunk in _chunks(groups, max_group):
-        idx, probs, points = ([m[k] for m in chunk] for k in range(3))
-        ids = [ids_of[i] for i in idx]
-        with RefineBatchHandle(probs, lib_path, solver_settings) as h:
-            _, members, rec = h.range_variances(points, ids, rel_tol, max_iters, int(block_width))
+
+    def body(handle, number, idx, probs, points, extras):
+        _, members, rec = handle.range_variances(points, [ids_of[i] for i in idx], rel_tol, max_iters, int(block_width))
+        got = []
         for i, m in zip(idx, members):
             failed = int(np.count_nonzero(~m["converged"]))
             if failed:
                 raise _failed("predicted_range_variances_batch", i, failed, len(names[i]), "columns", max_iters)
-            info = {"pcg_iters": int(rec["pcg_iters"]), "batches": -(-len(names[i]) // int(block_width)), "setup_ms": float(rec["setup_ms"]),
-                    "solve_ms": float(rec["solve_ms"]), "iterations": m["iterations"], "residuals": m["residuals"], "engine": engine,
-                    "group": number, "passes": int(rec["passes"])}
-            out[i] = (PredictedRanges(names[i], m["distances"], m["variances"]), info)
-    return out
+            mine = dict(m, info={"batches": -(-len(names[i]) // int(block_width))})  # (the passes in which the graph had columns)
+            got.append((PredictedRanges(names[i], m["distances"], m["variances"]), draw_info(rec, mine, number, engine, draws=False)))
+        return got
+
+    return run_chunks(groups, max_group, out, body, True, lib_path, solver_settings)
 
 
 __all__ = ["range_leverage_batch", "predicted_range_variances_batch", "batch_leverage", "batch_range_variances", "group_leverage",

@@ -28,6 +28,16 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     return bind(lib, MARGINALS)
 
 
+def check_block_solve(block_width, rel_tol, max_iters, first_sample=None, n_samples=0):
+    """The arguments of a block solve whose width is 1..16; ``first_sample``: of one that draws, ``n_samples`` draws at most."""
+    if int(block_width) != block_width or not 1 <= int(block_width) <= MAX_BLOCK_WIDTH:
+        raise ValueError(f"block_width must be an integer in 1..{MAX_BLOCK_WIDTH}")
+    if first_sample is not None and (int(first_sample) != first_sample or first_sample < 0 or first_sample + n_samples > 2 ** 32):
+        raise ValueError("first_sample .. first_sample + n_samples must lie in 0 .. 2^32")
+    if not rel_tol > 0 or max_iters < 1:
+        raise ValueError("rel_tol must be positive and max_iters at least 1")
+
+
 def _select(prob, variables):
     """Names -> (names, variable ids, first column and size of each, all columns)."""
     poses, lms = list(prob.a["pose_names"]), list(prob.a["landmark_names"])

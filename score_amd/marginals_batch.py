@@ -1,10 +1,10 @@
 """Marginal covariances of many graphs at once (include/score_marginals_batch.h, csrc/score_marginals_batch.hpp).
 
 ``marginal_covariances`` takes one graph, builds one refinement handle and runs a block PCG whose launches are latency-bound
-on a small world.  ``marginal_covariances_batch`` hands the graphs to the device as groups, as ``refine_estimate_batch``
-does: the group handle's union matrix H = J'J is block diagonal, so one union vector carries one unit column of every
-member, and a block of up to 16 union vectors advances 16 columns of all members per pass over the union matrix
-(``score_refine_batch_marginals``).  Every (member, column) pair has its own alpha, beta, stopping gate and verdict: a
+on a small world.  ``marginal_covariances_batch`` hands the graphs to the device as groups, by the rule of
+``score_amd/groups.py``: the group handle's union matrix H = J'J is block diagonal, so one union vector carries one unit
+column of every member, and a block of up to 16 union vectors advances 16 columns of all members per pass over the union
+matrix (``score_refine_batch_marginals``).  Every (member, column) pair has its own alpha, beta, stopping gate and verdict: a
 member's result is what ``marginal_covariances`` computes on it alone, up to the rounding of the two iterations.
 
 ``RefineBatchHandle.marginals`` is the raw call on a kept group handle, so a study refines and takes covariances with one
@@ -18,8 +18,9 @@ from typing import Optional
 
 import numpy as np
 
-from .bindings import MARGINALS_BATCH, ScoreMarginalsBatchInfo, bind, ptr, steps_and_converged
-from .marginals import MAX_BLOCK_WIDTH, _member_result, _problem_and_point, _python_columns, _select, n_columns
+from .bindings import MARGINALS_BATCH, Cutter, ScoreMarginalsBatchInfo, bind, ptr, steps_and_converged
+from .groups import FollowUp, grouped, naming, paired, per_graph, run_chunks
+from .marginals import MAX_BLOCK_WIDTH, _member_result, _problem_and_point, _python_columns, _select, check_block_solve, n_columns
 from .solver import _i32p
 
 # the symbols include/score_marginals_batch.h declares
@@ -57,12 +58,10 @@ def batch_columns(handle, points, ids_per_member, rel_tol=1e-10, max_iters=4000,
                                           int(max_iters), int(block_width), ptr(joint), ptr(res), ptr(its, _i32p), C.byref(info))
     if rc < 0:
         raise RuntimeError(f"score_refine_batch_marginals failed: {lib.score_last_error().decode()}")
-    out, j0, c0 = [], 0, 0
+    cut, out = Cutter(), []
     for c in ncol:
-        steps, converged = steps_and_converged(its[c0 : c0 + c])
-        out.append((joint[j0 : j0 + c * c].reshape(c, c).copy(), res[c0 : c0 + c].copy(), steps, converged))
-        j0 += c * c
-        c0 += c
+        steps, converged = steps_and_converged(cut(its, c))
+        out.append((cut(joint, c * c, (c, c)), cut(res, c), steps, converged))
     return rc, out, info.as_dict()
 
 
@@ -89,13 +88,19 @@ def group_marginals(handle, probs, points, selections, indices, number, rel_tol=
     return out
 
 
-def _variables_of(variables, count: int) -> list:
-    if variables is None:
-        return [None] * count
-    variables = list(variables)
-    if len(variables) != count:
-        raise ValueError(f"variables: one entry per graph expected ({count}), got {len(variables)}")
-    return variables
+def marginals_follow_up(marginals, count: int) -> FollowUp:
+    """The ``marginals=`` keyword of the two refine front ends (True, or ``variables`` as ``marginal_covariances_batch`` takes
+    them): ``info["marginals"]`` is that call's ``(cov, info)`` at the refined points, on the group's handle."""
+    wanted = per_graph(None if marginals is True else marginals, count, "variables")
+
+    def prepare(i, prob):
+        with naming(i):
+            return _select(prob, wanted[i])
+
+    def run(handle, number, idx, probs, points, costs, selections):
+        return group_marginals(handle, probs, points, selections, idx, number, engine="python" if handle is None else "device")
+
+    return FollowUp("marginals", run, prepare)
 
 
 def marginal_covariances_batch(datas, results, variables=None, joint: bool = False, range_weights=None, loop_closure_weights=None,
@@ -105,55 +110,29 @@ def marginal_covariances_batch(datas, results, variables=None, joint: bool = Fal
     """``marginal_covariances`` for many graphs at once: ``datas`` and ``results`` graph by graph, ``variables`` None or a list
     with one entry per graph (None: that graph's default, every landmark and the last pose of every chain; else a list of
     names), ``range_weights`` / ``loop_closure_weights`` lists with one entry per graph.  The graphs are grouped by dimension,
-    in chunks of at most ``max_group``, as ``refine_estimate_batch`` groups them; each group is one device handle and one
+    in chunks of at most ``max_group`` (the rule of ``score_amd/groups.py``); each group is one device handle and one
     ``score_refine_batch_marginals`` call (``engine="device"``) or the dense inverse graph by graph (``engine="python"``).
     Returns a list of ``(dict name -> k x k ndarray, info)`` in input order: per graph what ``marginal_covariances`` returns,
     plus ``group`` (the group's number) and ``passes`` (passes of the group's call; ``batches`` counts those in which the
     graph itself had columns; ``pcg_iters``, ``setup_ms`` and ``solve_ms`` are the group's).
     ``block_width``: 1..16 columns of every member advance together.  The single call's ValueErrors are raised with
     ``graph i:`` in front; a column that does not converge raises RuntimeError naming the graph and the variable."""
-    from .refine_batch import RefineBatchHandle, _weights_of
-
     if engine not in ("device", "python"):
         raise ValueError("engine must be 'device' or 'python'")
-    if int(block_width) != block_width or not 1 <= int(block_width) <= MAX_BLOCK_WIDTH:
-        raise ValueError(f"block_width must be an integer in 1..{MAX_BLOCK_WIDTH}")
-    if not rel_tol > 0 or max_iters < 1:
-        raise ValueError("rel_tol must be positive and max_iters at least 1")
-    datas, results = list(datas), list(results)
-    if len(datas) != len(results):
-        raise ValueError(f"one estimate per graph expected: {len(datas)} graphs, {len(results)} estimates")
-    if int(max_group) < 1:
-        raise ValueError("max_group must be at least 1")
-    rws = _weights_of(range_weights, len(datas), "range_weights")
-    lws = _weights_of(loop_closure_weights, len(datas), "loop_closure_weights")
-    wanted = _variables_of(variables, len(datas))
-    groups: dict = {}
-    for i, (data, res) in enumerate(zip(datas, results)):
-        if data.dimension not in (2, 3):
-            raise ValueError(f"graph {i}: dimension must be 2 or 3")
-        try:
-            prob, point = _problem_and_point(data, res, rws[i], lws[i])
-            sel = _select(prob, wanted[i])
-        except ValueError as e:
-            raise ValueError(f"graph {i}: {e}") from None
-        groups.setdefault(data.dimension, []).append((i, prob, point, sel))
-    out: list = [None] * len(datas)
-    number = 0
-    for dim in sorted(groups):
-        members = groups[dim]
-        for c0 in range(0, len(members), int(max_group)):
-            chunk = members[c0 : c0 + int(max_group)]
-            idx, probs, points, sels = ([m[k] for m in chunk] for k in range(4))
-            if engine == "python":
-                got = group_marginals(None, probs, points, sels, idx, number, rel_tol, max_iters, int(block_width), engine, joint)
-            else:
-                with RefineBatchHandle(probs, lib_path, solver_settings) as h:
-                    got = group_marginals(h, probs, points, sels, idx, number, rel_tol, max_iters, int(block_width), engine, joint)
-            for i, g in zip(idx, got):
-                out[i] = g
-            number += 1
-    return out
+    check_block_solve(block_width, rel_tol, max_iters)
+    datas, results = paired(datas, results, max_group)
+    rws = per_graph(range_weights, len(datas), "range_weights")
+    lws = per_graph(loop_closure_weights, len(datas), "loop_closure_weights")
+    wanted = per_graph(variables, len(datas), "variables")
+
+    def member(i, data, res):
+        prob, point = _problem_and_point(data, res, rws[i], lws[i])
+        return prob, point, _select(prob, wanted[i])
+
+    def body(handle, number, idx, probs, points, extras):
+        return group_marginals(handle, probs, points, extras[0], idx, number, rel_tol, max_iters, int(block_width), engine, joint)
+
+    return run_chunks(grouped(datas, results, member), max_group, [None] * len(datas), body, engine == "device", lib_path, solver_settings)
 
 
 __all__ = ["marginal_covariances_batch", "batch_columns", "group_marginals", "MARGINALS_BATCH_SYMBOLS"]

@@ -19,6 +19,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from .bindings import LEVERAGE_BATCH, REFINE_BATCH, REFINE_ROBUST_BATCH, ScoreRefineRobustInfo, ScoreRefineRobustSettings, bind, ptr
+from .groups import FollowUp, follow, grouped, paired, per_graph, run_chunks
 from .native import ScoreGraph, score_graph_struct
 from .refine import (GRADIENT, SOLVE, _as_results, _attempt, _gradient, _Handle, _Member, _native_info, _point_arrays, _point_from,
                      _problem_and_point as _problem_of, refine_estimate)
@@ -27,15 +28,6 @@ from .solver import ScoreRefineInfo
 
 # the symbols include/score_refine_batch.h declares
 REFINE_BATCH_SYMBOLS = list(REFINE_BATCH)
-
-
-def _weights_of(weights, count: int, what: str) -> list:
-    if weights is None:
-        return [None] * count
-    weights = list(weights)
-    if len(weights) != count:
-        raise ValueError(f"{what}: one entry per graph expected ({count}), got {len(weights)}")
-    return weights
 
 
 class _LockStep:
@@ -249,10 +241,11 @@ def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-1
                           leverage_seed: int = 0):
     """``refine_estimate`` for many graphs at once: ``datas`` and ``results`` member by member, ``range_weights`` /
     ``loop_closure_weights`` lists with one entry (an array as ``refine_estimate`` takes it, or None) per member -- they only
-    scale precisions.  The members are grouped by dimension, in chunks of at most ``max_group``, each group one device handle
-    (``engine="native"``) or one lock-step loop in Python with SciPy's sparse LU (``engine="python"``).  Members without
-    unknowns are answered on the host.  Returns a list of ``(refined SolverResults, info)`` in input order; ``info`` as
-    ``refine_estimate`` reports it, plus ``group`` (the group's number) and ``rounds`` (lock-step rounds of the group).
+    scale precisions.  The members are grouped by dimension, in chunks of at most ``max_group`` (the rule of
+    ``score_amd/groups.py``), each group one device handle (``engine="native"``) or one lock-step loop in Python with SciPy's
+    sparse LU (``engine="python"``).  Members without unknowns are answered on the host.  Returns a list of ``(refined
+    SolverResults, info)`` in input order; ``info`` as ``refine_estimate`` reports it, plus ``group`` (the group's number) and
+    ``rounds`` (lock-step rounds of the group).
     ``marginals``: True, or a list with one entry per graph as ``marginal_covariances_batch`` takes ``variables`` -- every
     group's handle then also computes the marginal covariances at the refined points before it is closed (one create for
     both), and ``info["marginals"]`` is the ``(cov, marginals_info)`` of ``marginal_covariances_batch`` for that graph (None
@@ -268,106 +261,66 @@ def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-1
     from .leverage import range_leverage
     from .leverage_batch import group_leverage
     from .marginals import _select
-    from .marginals_batch import _variables_of, group_marginals
+    from .marginals_batch import marginals_follow_up
     from .samples_batch import _check_draw_arguments, group_samples
 
     if engine not in ("native", "python"):
         raise ValueError("engine must be 'native' or 'python'")
-    datas, results = list(datas), list(results)
-    if len(datas) != len(results):
-        raise ValueError(f"one estimate per graph expected: {len(datas)} graphs, {len(results)} estimates")
-    if int(max_group) < 1:
-        raise ValueError("max_group must be at least 1")
-    rws = _weights_of(range_weights, len(datas), "range_weights")
-    lws = _weights_of(loop_closure_weights, len(datas), "loop_closure_weights")
-    with_marginals = marginals is not None and marginals is not False
-    wanted = _variables_of(None if marginals is True else marginals, len(datas)) if with_marginals else None
-    with_samples = samples is not None and samples is not False
-    if with_samples:
+    datas, results = paired(datas, results, max_group)
+    rws = per_graph(range_weights, len(datas), "range_weights")
+    lws = per_graph(loop_closure_weights, len(datas), "loop_closure_weights")
+    follow_ups = []  # (on a group's handle in this order)
+    if marginals is not None and marginals is not False:
+        follow_ups.append(marginals_follow_up(marginals, len(datas)))
+    if samples is not None and samples is not False:
         _check_draw_arguments([samples], 0, 16, 1e-10, 4000)
-    with_leverage = leverage is not None and leverage is not False
-    if with_leverage:
+
+        def draws(handle, number, idx, probs, pts, costs, selections):
+            """(Samples, info) per member at the refined points, retracted onto the refined estimates"""
+            ests = [_as_results(p, pt, results[i], f) for p, pt, i, f in zip(probs, pts, idx, costs)]
+            return group_samples(handle, probs, pts, ests, selections, idx, number, [int(samples)] * len(idx),
+                                 [int(samples_seed) + i for i in idx], engine="python" if handle is None else "device")
+
+        follow_ups.append(FollowUp("samples", draws, lambda i, prob: _select(prob, None)))
+    if leverage is not None and leverage is not False:
         _check_draw_arguments([leverage], 0, 16, 1e-10, 4000)
+
+        def leverages(handle, number, idx, probs, pts, costs, kept):
+            """(Leverage, info) per member at the refined points"""
+            if handle is None:
+                return [range_leverage(datas[i], _as_results(p, pt, results[i], f), int(leverage), int(leverage_seed) + i,
+                                       range_weights=rws[i], loop_closure_weights=lws[i], engine="python")
+                        for p, pt, i, f in zip(probs, pts, idx, costs)]
+            return group_leverage(handle, probs, pts, [None] * len(idx), idx, number, [int(leverage)] * len(idx),
+                                  [int(leverage_seed) + i for i in idx])
+
+        follow_ups.append(FollowUp("leverage", leverages))
     out: list = [None] * len(datas)
-    groups: dict = {}
-    sel_of: dict = {}
-    draw_sel_of: dict = {}
-    for i, (data, res) in enumerate(zip(datas, results)):
-        if data.dimension not in (2, 3):
-            raise ValueError(f"graph {i}: dimension must be 2 or 3")
+
+    def member(i, data, res):
         prob, point = _problem_of(data, res, rws[i], lws[i])
         if prob.n == 0:  # nothing to refine: the host's answer, as refine_estimate gives it
             out[i] = refine_estimate(data, res, max_iters=max_iters, tol=tol, linear_solver="scipy", engine="python",
                                      range_weights=rws[i], loop_closure_weights=lws[i])
-            if with_marginals:
-                out[i][1]["marginals"] = None
-            if with_samples:
-                out[i][1]["samples"] = None
-            if with_leverage:
-                out[i][1]["leverage"] = None
-            continue
-        if with_marginals:  # (the selection's errors before any work)
-            try:
-                sel_of[i] = _select(prob, wanted[i])
-            except ValueError as e:
-                raise ValueError(f"graph {i}: {e}") from None
-        if with_samples:
-            draw_sel_of[i] = _select(prob, None)
-        groups.setdefault(data.dimension, []).append((i, prob, point))
-    number = 0
-    for dim in sorted(groups):
-        members = groups[dim]
-        for c0 in range(0, len(members), int(max_group)):
-            chunk = members[c0 : c0 + int(max_group)]
-            probs, points = [m[1] for m in chunk], [m[2] for m in chunk]
-            covs, sels = None, [sel_of.get(m[0]) for m in chunk]
-            idx = [m[0] for m in chunk]
+            out[i][1].update({f.key: None for f in follow_ups})
+            return None
+        for f in follow_ups:  # (the selections' errors before any work)
+            f.keep(i, prob)
+        return prob, point
 
-            def draws(handle, pts, costs, which):
-                """(Samples, info) per member at the refined points, retracted onto the refined estimates"""
-                ests = [_as_results(p, pt, results[i], f) for p, pt, i, f in zip(probs, pts, idx, costs)]
-                return group_samples(handle, probs, pts, ests, [draw_sel_of[i] for i in idx], idx, number, [int(samples)] * len(idx),
-                                     [int(samples_seed) + i for i in idx], engine=which)
+    def body(handle, number, idx, probs, points, extras):
+        if handle is None:
+            pts, S, rounds = _python_lock_step(probs, points, max_iters, tol)
+            infos = [{"cost_initial": s.cost_initial, "cost_final": s.f, "iterations": s.iterations, "grad_inf": s.gnorm,
+                      "linear_solver": "scipy", "engine": "python", "pcg_iters": 0, "linear_solves": s.linear_solves} for s in S]
+        else:
+            pts, raw = handle.run(points, max_iters, tol)
+            rounds = max(r["linear_solves"] for r in raw)
+            infos = [_native_info(r) for r in raw]
+        extra = follow(follow_ups, handle, number, idx, probs, pts, [info["cost_final"] for info in infos])
+        for info, more in zip(infos, extra):
+            info["group"], info["rounds"] = number, rounds
+            info.update(more)
+        return [(_as_results(prob, pt, results[i], info["cost_final"]), info) for i, prob, pt, info in zip(idx, probs, pts, infos)]
 
-            def leverages(handle, pts, costs):
-                """(Leverage, info) per member at the refined points"""
-                if handle is None:
-                    return [range_leverage(datas[i], _as_results(p, pt, results[i], f), int(leverage), int(leverage_seed) + i,
-                                           range_weights=rws[i], loop_closure_weights=lws[i], engine="python")
-                            for p, pt, i, f in zip(probs, pts, idx, costs)]
-                return group_leverage(handle, probs, pts, [None] * len(idx), idx, number, [int(leverage)] * len(idx),
-                                      [int(leverage_seed) + i for i in idx])
-
-            drawn = levs = None
-            if engine == "python":
-                pts, S, rounds = _python_lock_step(probs, points, max_iters, tol)
-                if with_marginals:
-                    covs = group_marginals(None, probs, pts, sels, [m[0] for m in chunk], number, engine="python")
-                if with_samples:
-                    drawn = draws(None, pts, [s.f for s in S], "python")
-                if with_leverage:
-                    levs = leverages(None, pts, [s.f for s in S])
-                infos = [{"cost_initial": s.cost_initial, "cost_final": s.f, "iterations": s.iterations, "grad_inf": s.gnorm,
-                          "linear_solver": "scipy", "engine": "python", "pcg_iters": 0, "linear_solves": s.linear_solves} for s in S]
-            else:
-                with RefineBatchHandle(probs, lib_path, solver_settings) as h:
-                    pts, raw = h.run(points, max_iters, tol)
-                    if with_marginals:
-                        covs = group_marginals(h, probs, pts, sels, [m[0] for m in chunk], number)
-                    if with_samples:
-                        drawn = draws(h, pts, [r["cost_final"] for r in raw], "device")
-                    if with_leverage:
-                        levs = leverages(h, pts, [r["cost_final"] for r in raw])
-                rounds = max(r["linear_solves"] for r in raw)
-                infos = [_native_info(r) for r in raw]
-            for k, ((i, prob, _), pt, info) in enumerate(zip(chunk, pts, infos)):
-                info["group"], info["rounds"] = number, rounds
-                if with_marginals:
-                    info["marginals"] = covs[k]
-                if with_samples:
-                    info["samples"] = drawn[k]
-                if with_leverage:
-                    info["leverage"] = levs[k]
-                out[i] = (_as_results(prob, pt, results[i], info["cost_final"]), info)
-            number += 1
-    return out
+    return run_chunks(grouped(datas, results, member, named=False), max_group, out, body, engine == "native", lib_path, solver_settings)

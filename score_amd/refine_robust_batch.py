@@ -19,8 +19,9 @@ from typing import Optional
 import numpy as np
 
 from .bindings import REFINE_ROBUST_BATCH, ScoreRefineRobustSettings, bind
+from .groups import follow, grouped, paired, per_graph, run_chunks
 from .refine import STOPPED, _as_results, _native_info
-from .refine_batch import RefineBatchHandle, _LockStep, _problem_of, _weights_of
+from .refine_batch import _LockStep, _problem_of
 from .refine_robust import (DONE, FAMILY_LOOP_CLOSURES, FAMILY_RANGES, _check, _check_precisions, _prior, _Stage,
                             loop_closure_residuals, range_residuals, refine_estimate_robust)
 from .robust import _robust_info
@@ -63,15 +64,6 @@ def _python_robust_lock_step(probs, points, settings):
 # ---------------------------------------------------------------------------------------------------------------------
 # public interface
 # ---------------------------------------------------------------------------------------------------------------------
-def _per_graph(value, count: int, what: str) -> list:
-    if value is None or np.ndim(value) == 0:
-        return [value] * count
-    value = list(value)
-    if len(value) != count:
-        raise ValueError(f"{what}: a scalar or one entry per graph expected ({count}), got {len(value)}")
-    return value
-
-
 def refine_estimate_robust_batch(datas, results, inlier_threshold=3.0, robust_ranges: bool = True, robust_loop_closures: bool = False,
                                  loop_closure_threshold=None, max_outer: int = 50, inner_iters: int = 5, min_weight: float = 1e-6,
                                  mu_step: float = 1.4, max_iters: int = 50, tol: float = 1e-10, engine: str = "native",
@@ -81,7 +73,7 @@ def refine_estimate_robust_batch(datas, results, inlier_threshold=3.0, robust_ra
     a sequence with one entry per graph (``loop_closure_threshold`` None: the graph's ``inlier_threshold``); ``range_weights`` /
     ``loop_closure_weights`` are lists with one entry per graph (prior weights as ``refine_estimate_robust`` takes them: floored
     at ``min_weight`` in a re-weighted family, and the returned weights are prior x GNC).  The graphs are grouped by dimension,
-    in chunks of at most ``max_group``, as ``refine_estimate_batch`` groups them: each group is one device handle and one
+    in chunks of at most ``max_group`` (the rule of ``score_amd/groups.py``): each group is one device handle and one
     ``score_refine_batch_robust_run`` (``engine="native"``) or one lock-step loop in Python with SciPy's sparse LU
     (``engine="python"``).  Graphs without unknowns are answered on the host.  Returns ``[(refined SolverResults, info), ...]``
     in input order, ``info`` as ``refine_estimate_robust`` builds it (``info["robust"]`` included) plus ``group``, ``rounds``
@@ -93,18 +85,13 @@ def refine_estimate_robust_batch(datas, results, inlier_threshold=3.0, robust_ra
     ``marginal_covariances_batch`` for that graph with the returned weights (None for a graph without unknowns).  Where a prior
     weight lies below ``min_weight`` in a re-weighted family, the kept precisions carry the floor (prec x min_weight x w), not
     the prior weight itself.  Errors about one graph are raised with ``graph i:`` in front."""
-    from .marginals import _select
-    from .marginals_batch import _variables_of, group_marginals
+    from .marginals_batch import marginals_follow_up
 
     f_rng, f_rel = bool(robust_ranges), bool(robust_loop_closures)
-    datas, results = list(datas), list(results)
-    if len(datas) != len(results):
-        raise ValueError(f"one estimate per graph expected: {len(datas)} graphs, {len(results)} estimates")
-    if int(max_group) < 1:
-        raise ValueError("max_group must be at least 1")
+    datas, results = paired(datas, results, max_group)
     N = len(datas)
-    cs = _per_graph(inlier_threshold, N, "inlier_threshold")
-    crs = _per_graph(loop_closure_threshold, N, "loop_closure_threshold")
+    cs = per_graph(inlier_threshold, N, "inlier_threshold", scalar=True)
+    crs = per_graph(loop_closure_threshold, N, "loop_closure_threshold", scalar=True)
     cs = [float(c) for c in cs]
     crs = [c if cr is None else float(cr) for c, cr in zip(cs, crs)]
     linear_solver = "scipy" if engine == "python" else "device"
@@ -115,18 +102,15 @@ def refine_estimate_robust_batch(datas, results, inlier_threshold=3.0, robust_ra
         except ValueError as e:
             raise ValueError(f"graph {i}: {e}") from None
     families = (FAMILY_RANGES if f_rng else 0) | (FAMILY_LOOP_CLOSURES if f_rel else 0)
-    rws = _weights_of(range_weights, N, "range_weights")
-    lws = _weights_of(loop_closure_weights, N, "loop_closure_weights")
+    rws = per_graph(range_weights, N, "range_weights")
+    lws = per_graph(loop_closure_weights, N, "loop_closure_weights")
     with_marginals = marginals is not None and marginals is not False
-    wanted = _variables_of(None if marginals is True else marginals, N) if with_marginals else None
+    follow_ups = [marginals_follow_up(marginals, N)] if with_marginals else []
     common = dict(max_outer=int(max_outer), inner_iters=int(inner_iters), min_weight=float(min_weight), mu_step=float(mu_step),
                   max_iters=int(max_iters), tol=float(tol), families=families)
     out: list = [None] * N
-    groups: dict = {}
-    sel_of: dict = {}
-    for i, (data, res) in enumerate(zip(datas, results)):
-        if data.dimension not in (2, 3):
-            raise ValueError(f"graph {i}: dimension must be 2 or 3")
+
+    def member(i, data, res):
         prob, point = _problem_of(data, res, _prior(rws[i], float(min_weight), f_rng), _prior(lws[i], float(min_weight), f_rel))
         _check_precisions(prob, f_rng, f_rel, f"graph {i}: ")
         if prob.n == 0:  # nothing to refine: the host's answer, as refine_estimate_robust gives it
@@ -134,62 +118,52 @@ def refine_estimate_robust_batch(datas, results, inlier_threshold=3.0, robust_ra
                                             loop_closure_threshold=crs[i], max_outer=max_outer, inner_iters=inner_iters,
                                             min_weight=min_weight, mu_step=mu_step, max_iters=max_iters, tol=tol, engine="python",
                                             linear_solver="scipy", range_weights=rws[i], loop_closure_weights=lws[i])
+            out[i][1].update({f.key: None for f in follow_ups})
+            return None
+        for f in follow_ups:  # (the selection's errors before any work)
+            f.keep(i, prob)
+        return prob, point
+
+    def body(handle, number, idx, probs, points, extras):
+        if handle is None:
+            settings = [dict(common, c=cs[i], c_rel=crs[i]) for i in idx]
+            pts, S, R, rounds, stage_rounds = _python_robust_lock_step(probs, points, settings)
+            per, infos, loops = [], [], []
+            for prob, pt, s, st in zip(probs, pts, S, R):
+                per.append((st.w, range_residuals(prob, pt, st.prec0), st.wl, loop_closure_residuals(prob, pt, st.kappa0, st.tau0)))
+                infos.append({"cost_initial": st.cost_initial, "cost_final": s.f, "iterations": st.lm, "grad_inf": s.gnorm,
+                              "linear_solver": "scipy", "engine": "python", "pcg_iters": 0, "linear_solves": st.linear_solves})
+                loops.append((st.k, st.mu, st.what == "converged"))
             if with_marginals:
-                out[i][1]["marginals"] = None
-            continue
-        if with_marginals:  # (the selection's errors before any work)
-            try:
-                sel_of[i] = _select(prob, wanted[i])
-            except ValueError as e:
-                raise ValueError(f"graph {i}: {e}") from None
-        groups.setdefault(data.dimension, []).append((i, prob, point))
-    number = 0
-    for dim in sorted(groups):
-        members = groups[dim]
-        for c0 in range(0, len(members), int(max_group)):
-            chunk = members[c0 : c0 + int(max_group)]
-            idx, probs, points = ([m[k] for m in chunk] for k in range(3))
-            sels, covs = [sel_of.get(i) for i in idx], None
-            if engine == "python":
-                settings = [dict(common, c=cs[i], c_rel=crs[i]) for i in idx]
-                pts, S, R, rounds, stage_rounds = _python_robust_lock_step(probs, points, settings)
-                per, infos, loops = [], [], []
-                for prob, pt, s, st in zip(probs, pts, S, R):
-                    per.append((st.w, range_residuals(prob, pt, st.prec0), st.wl, loop_closure_residuals(prob, pt, st.kappa0, st.tau0)))
-                    infos.append({"cost_initial": st.cost_initial, "cost_final": s.f, "iterations": st.lm, "grad_inf": s.gnorm,
-                                  "linear_solver": "scipy", "engine": "python", "pcg_iters": 0, "linear_solves": st.linear_solves})
-                    loops.append((st.k, st.mu, st.what == "converged"))
-                if with_marginals:
-                    for st in R:
-                        st.weigh(None)  # the kept precisions: prec w
-                    covs = group_marginals(None, probs, pts, sels, idx, number, engine="python")
-            else:
-                recs = []
-                for i in idx:
-                    rs = ScoreRefineRobustSettings()
-                    rs.inlier_threshold, rs.rel_threshold, rs.mu_step, rs.min_weight = cs[i], crs[i], float(mu_step), float(min_weight)
-                    rs.families, rs.max_outer, rs.inner_iters = families, int(max_outer), int(inner_iters)
-                    rs.max_iters, rs.tol = int(max_iters), float(tol)
-                    recs.append(rs)
-                with RefineBatchHandle(probs, lib_path, solver_settings) as h:
-                    pts, per, raw = h.robust_run(points, recs, keep_weights=with_marginals)
-                    if with_marginals:
-                        covs = group_marginals(h, probs, pts, sels, idx, number)
-                    rounds, stage_rounds = h.robust_rounds()
-                infos = [_native_info(r, "lm_iterations") for r in raw]
-                loops = [(r["outer_iterations"], r["mu"], bool(r["converged"])) for r in raw]
-            for k, (i, prob, pt, info, (w, r, wl, rl), (outer, mu, conv)) in enumerate(zip(idx, probs, pts, infos, per, loops)):
-                if rws[i] is not None:  # prior x GNC
-                    w = w * np.asarray(rws[i], dtype=np.float64)
-                if lws[i] is not None:
-                    wl = wl * np.asarray(lws[i], dtype=np.float64)
-                info["robust"] = _robust_info(w, r, outer, mu, conv, wl if f_rel else None, rl if f_rel else None)
-                info["group"], info["rounds"], info["stage_rounds"] = number, rounds, stage_rounds
-                if with_marginals:
-                    info["marginals"] = covs[k]
-                out[i] = (_as_results(prob, pt, results[i], info["cost_final"]), info)
-            number += 1
-    return out
+                for st in R:
+                    st.weigh(None)  # the kept precisions: prec w
+            extra = follow(follow_ups, None, number, idx, probs, pts, [info["cost_final"] for info in infos])
+        else:
+            recs = []
+            for i in idx:
+                rs = ScoreRefineRobustSettings()
+                rs.inlier_threshold, rs.rel_threshold, rs.mu_step, rs.min_weight = cs[i], crs[i], float(mu_step), float(min_weight)
+                rs.families, rs.max_outer, rs.inner_iters = families, int(max_outer), int(inner_iters)
+                rs.max_iters, rs.tol = int(max_iters), float(tol)
+                recs.append(rs)
+            pts, per, raw = handle.robust_run(points, recs, keep_weights=with_marginals)
+            extra = follow(follow_ups, handle, number, idx, probs, pts, [r["cost_final"] for r in raw])
+            rounds, stage_rounds = handle.robust_rounds()
+            infos = [_native_info(r, "lm_iterations") for r in raw]
+            loops = [(r["outer_iterations"], r["mu"], bool(r["converged"])) for r in raw]
+        got = []
+        for i, prob, pt, info, (w, r, wl, rl), (outer, mu, conv), more in zip(idx, probs, pts, infos, per, loops, extra):
+            if rws[i] is not None:  # prior x GNC
+                w = w * np.asarray(rws[i], dtype=np.float64)
+            if lws[i] is not None:
+                wl = wl * np.asarray(lws[i], dtype=np.float64)
+            info["robust"] = _robust_info(w, r, outer, mu, conv, wl if f_rel else None, rl if f_rel else None)
+            info["group"], info["rounds"], info["stage_rounds"] = number, rounds, stage_rounds
+            info.update(more)
+            got.append((_as_results(prob, pt, results[i], info["cost_final"]), info))
+        return got
+
+    return run_chunks(grouped(datas, results, member, named=False), max_group, out, body, engine != "python", lib_path, solver_settings)
 
 
 __all__ = ["refine_estimate_robust_batch", "REFINE_ROBUST_BATCH_SYMBOLS"]

@@ -1,9 +1,9 @@
 """Posterior samples of many graphs at once (include/score_samples_batch.h, csrc/score_samples_batch.hpp).
 
 ``posterior_samples`` takes one graph, builds one refinement handle and runs a block PCG whose launches are latency-bound on
-a small world.  ``posterior_samples_batch`` hands the graphs to the device as groups, as ``refine_estimate_batch`` does: the
-group handle's union matrix H = J'J is block diagonal, so one union vector carries one draw of every member, and a block of
-up to 16 union vectors advances 16 draws of all members per pass over the union matrix (``score_refine_batch_samples``).
+a small world.  ``posterior_samples_batch`` hands the graphs to the device as groups, by the rule of ``score_amd/groups.py``:
+the group handle's union matrix H = J'J is block diagonal, so one union vector carries one draw of every member, and a block
+of up to 16 union vectors advances 16 draws of all members per pass over the union matrix (``score_refine_batch_samples``).
 Every (member, draw) pair has its own alpha, beta, stopping gate and verdict, every member its own noise stream and its own
 probe column: graph i's draws are those ``posterior_samples(..., seed=seed_i)`` forms on it alone, up to the rounding of the
 two iterations (the noise is the same stream, the right-hand sides the same sums).
@@ -19,9 +19,10 @@ from typing import Optional
 
 import numpy as np
 
-from .bindings import SAMPLES_BATCH, ScoreSamplesBatchInfo, _u64p, bind, ptr, steps_and_converged
-from .marginals import MAX_BLOCK_WIDTH, _problem_and_point, _select, n_columns
-from .marginals_batch import _flat_ids, _variables_of
+from .bindings import SAMPLES_BATCH, Cutter, ScoreSamplesBatchInfo, _u64p, bind, ptr, steps_and_converged
+from .groups import grouped, paired, per_graph, run_chunks
+from .marginals import MAX_BLOCK_WIDTH, _problem_and_point, _select, check_block_solve, n_columns
+from .marginals_batch import _flat_ids
 from .samples import Samples, _moment_sizes, _n_rows, _python_draws, accumulate_moments
 from .solver import _i32p
 
@@ -31,15 +32,6 @@ SAMPLES_BATCH_SYMBOLS = list(SAMPLES_BATCH)
 
 def _bind(lib: C.CDLL) -> C.CDLL:
     return bind(lib, SAMPLES_BATCH)
-
-
-def _per_member(value, count: int, what: str) -> list:
-    if np.ndim(value) == 0:
-        return [value] * count
-    value = list(value)
-    if len(value) != count:
-        raise ValueError(f"{what}: one entry per graph expected ({count}), got {len(value)}")
-    return value
 
 
 def batch_draws(handle, points, ids_per_member, n_samples, seeds, first_sample=0, rel_tol=1e-10, max_iters=4000,
@@ -54,8 +46,8 @@ def batch_draws(handle, points, ids_per_member, n_samples, seeds, first_sample=0
     G = len(probs)
     if len(points) != G or len(ids_per_member) != G:
         raise ValueError("one point and one list of variables per member expected")
-    counts = [int(s) for s in _per_member(n_samples, G, "n_samples")]
-    keys = [int(s) & 0xFFFFFFFFFFFFFFFF for s in _per_member(seeds, G, "seeds")]
+    counts = [int(s) for s in per_graph(n_samples, G, "n_samples", none=False, scalar=True)]
+    keys = [int(s) & 0xFFFFFFFFFFFFFFFF for s in per_graph(seeds, G, "seeds", none=False, scalar=True)]
     lib = _bind(handle.lib)
     _, poses, lms = handle._flat_points(points)
     ids, var_ptr, flat = _flat_ids(ids_per_member)
@@ -79,31 +71,17 @@ def batch_draws(handle, points, ids_per_member, n_samples, seeds, first_sample=0
                                         ptr(det, _i32p), C.byref(info))
     if rc < 0:
         raise RuntimeError(f"score_refine_batch_samples failed: {lib.score_last_error().decode()}")
-    rec = info.as_dict()
-    out = []
-    at = dict(mom=0, mean=0, steps=0, rhs=0, noise=0, draw=0)
-
-    def cut(flat_array, key, size, shape):
-        if flat_array is None:
-            return None
-        piece = flat_array[at[key] : at[key] + size].reshape(shape).copy()
-        at[key] += size
-        return piece
-
+    rec, cut, out = info.as_dict(), Cutter(), []
     for g, prob in enumerate(probs):
         S, c, rows = on[g], ncol[g], _n_rows(prob)
-        iterations, converged = steps_and_converged(its[at["draw"] : at["draw"] + S])
-        member = {
-            "moments": cut(moments, "mom", n_mom[g], (n_mom[g],)) if S else np.zeros(_moment_sizes(prob)[2]),
-            "means": cut(means, "mean", n_mean[g], (n_mean[g],)) if S else np.zeros(prob.n),
-            "steps": cut(steps, "steps", S * c, (S, c)), "rhs": cut(rhs, "rhs", S * prob.n, (S, prob.n)),
-            "noise": cut(noise, "noise", S * rows, (S, rows)), "residuals": res[at["draw"] : at["draw"] + S].copy(),
-            "iterations": iterations, "converged": converged, "determined": int(det[g]),
-            "rc": 0 if np.all(converged) else 1,
-            "info": dict(rec, samples=S, batches=-(-S // int(block_width))),
-        }
-        at["draw"] += S
-        out.append(member)
+        iterations, converged = steps_and_converged(cut(its, S))
+        out.append({
+            "moments": cut(moments, n_mom[g]) if S else np.zeros(_moment_sizes(prob)[2]),
+            "means": cut(means, n_mean[g]) if S else np.zeros(prob.n),
+            "steps": cut(steps, S * c, (S, c)), "rhs": cut(rhs, S * prob.n, (S, prob.n)), "noise": cut(noise, S * rows, (S, rows)),
+            "residuals": cut(res, S), "iterations": iterations, "converged": converged, "determined": int(det[g]),
+            "rc": 0 if np.all(converged) else 1, "info": dict(rec, samples=S, batches=-(-S // int(block_width))),
+        })
     return rc, out, rec
 
 
@@ -111,6 +89,20 @@ def _failed(i, failed, total, max_iters):
     return RuntimeError(f"posterior_samples_batch: graph {i}: {failed} of {total} draws did not converge (max_iters = {max_iters}): "
                         "J'J is singular or nearly so -- information_spectrum(...).undetermined() names the variables the "
                         "measurements do not determine")
+
+
+def draw_info(rec, member, number, engine, draws=True) -> dict:
+    """A graph's ``info`` of a group's block solve: ``rec`` the call's record, ``member`` the graph's dict of the raw call,
+    ``number`` the group's.  ``draws``: the call drew samples (``rhs_ms`` and the probe's ``determined``)."""
+    info = {"pcg_iters": int(rec["pcg_iters"]), "batches": int(member["info"]["batches"]), "setup_ms": float(rec["setup_ms"]),
+            "solve_ms": float(rec["solve_ms"]), "iterations": member["iterations"], "residuals": member["residuals"], "engine": engine,
+            "group": number, "passes": int(rec["passes"])}
+    if draws:
+        info["rhs_ms"], info["determined"] = float(rec["rhs_ms"]), member["determined"]
+    return info
+
+
+HOST_RECORD = {"pcg_iters": 0, "passes": 0, "setup_ms": 0.0, "rhs_ms": 0.0, "solve_ms": 0.0}  # of a call that met no device
 
 
 def group_samples(handle, probs, points, estimates, selections, indices, number, counts, seeds, first_sample=0, rel_tol=1e-10,
@@ -125,8 +117,8 @@ def group_samples(handle, probs, points, estimates, selections, indices, number,
             if delta is None:
                 raise _failed(i, S, S, max_iters)
             moments, means = accumulate_moments(prob, delta)
-            info = {"pcg_iters": 0, "batches": 0, "setup_ms": 0.0, "rhs_ms": 0.0, "solve_ms": 0.0, "iterations": np.zeros(S, dtype=np.int64),
-                    "noise": z, "rhs": b, "order": names, "residuals": res, "engine": engine, "group": number, "passes": 0, "determined": 1}
+            m = {"info": {"batches": 0}, "iterations": np.zeros(S, dtype=np.int64), "residuals": res, "determined": 1}
+            info = dict(draw_info(HOST_RECORD, m, number, engine), noise=z, rhs=b, order=names)
             out.append((Samples(prob, est, moments, means, S, names, size, np.ascontiguousarray(delta[:, cols]), first_sample), info))
         return out
     _, members, rec = handle.samples(points, [sel[1] for sel in selections], counts, seeds, first_sample, rel_tol, max_iters, block_width)
@@ -134,11 +126,8 @@ def group_samples(handle, probs, points, estimates, selections, indices, number,
         failed = int(np.count_nonzero(~m["converged"]))
         if failed:
             raise _failed(i, failed, S, max_iters)
-        info = {"pcg_iters": int(rec["pcg_iters"]), "batches": int(m["info"]["batches"]), "setup_ms": float(rec["setup_ms"]),
-                "rhs_ms": float(rec["rhs_ms"]), "solve_ms": float(rec["solve_ms"]), "iterations": m["iterations"], "order": names,
-                "residuals": m["residuals"], "engine": engine, "group": number, "passes": int(rec["passes"]),
-                "determined": m["determined"]}
-        out.append((Samples(prob, est, m["moments"], m["means"], S, names, size, m["steps"], first_sample), info))
+        out.append((Samples(prob, est, m["moments"], m["means"], S, names, size, m["steps"], first_sample),
+                    dict(draw_info(rec, m, number, engine), order=names)))
     return out
 
 
@@ -146,19 +135,14 @@ def _check_draw_arguments(counts, first_sample, block_width, rel_tol, max_iters)
     for S in counts:
         if int(S) != S or S < 1:
             raise ValueError("n_samples must be an integer >= 1 (for every graph)")
-    if int(block_width) != block_width or not 1 <= int(block_width) <= MAX_BLOCK_WIDTH:
-        raise ValueError(f"block_width must be an integer in 1..{MAX_BLOCK_WIDTH}")
-    if int(first_sample) != first_sample or first_sample < 0 or first_sample + max(counts) > 2 ** 32:
-        raise ValueError("first_sample .. first_sample + n_samples must lie in 0 .. 2^32")
-    if not rel_tol > 0 or max_iters < 1:
-        raise ValueError("rel_tol must be positive and max_iters at least 1")
+    check_block_solve(block_width, rel_tol, max_iters, first_sample, max(counts))
 
 
 def _seeds_of(seed, count: int) -> list:
     """An integer: graph i draws from the stream of seed + i.  A list: one seed per graph."""
     if np.ndim(seed) == 0:
         return [int(seed) + i for i in range(count)]
-    return [int(s) for s in _per_member(seed, count, "seed")]
+    return [int(s) for s in per_graph(seed, count, "seed", none=False)]
 
 
 def posterior_samples_batch(datas, results, n_samples=64, seed=0, first_sample: int = 0, variables=None, range_weights=None,
@@ -170,60 +154,38 @@ def posterior_samples_batch(datas, results, n_samples=64, seed=0, first_sample: 
     names), ``range_weights`` / ``loop_closure_weights`` lists with one entry per graph.  ``n_samples``: an integer or one per
     graph.  ``seed``: a list with one seed per graph, or an integer -- graph i then draws from the stream of ``seed + i``, so
     that graph i's draws are those of ``posterior_samples(..., seed=seed + i)``; ``first_sample`` is shared.  The graphs are
-    grouped by dimension, in chunks of at most ``max_group``, as ``refine_estimate_batch`` groups them; each group is one device
+    grouped by dimension, in chunks of at most ``max_group`` (the rule of ``score_amd/groups.py``); each group is one device
     handle and one ``score_refine_batch_samples`` call (``engine="device"``) or the dense twin graph by graph
     (``engine="python"``).  Returns a list of ``(Samples, info)`` in input order: per graph what ``posterior_samples`` returns,
     plus ``group`` (the group's number), ``passes`` (passes of the group's call; ``batches`` counts those in which the graph
     itself had draws; ``pcg_iters``, ``setup_ms``, ``rhs_ms`` and ``solve_ms`` are the group's) and ``determined`` (the graph's
     own probe).  The single call's ValueErrors are raised with ``graph i:`` in front; draws that do not converge raise
     RuntimeError naming the first such graph."""
-    from .refine_batch import RefineBatchHandle, _weights_of
-
     if engine not in ("device", "python"):
         raise ValueError("engine must be 'device' or 'python'")
-    datas, results = list(datas), list(results)
-    if len(datas) != len(results):
-        raise ValueError(f"one estimate per graph expected: {len(datas)} graphs, {len(results)} estimates")
-    if int(max_group) < 1:
-        raise ValueError("max_group must be at least 1")
-    counts = _per_member(n_samples, len(datas), "n_samples")
+    datas, results = paired(datas, results, max_group)
+    counts = per_graph(n_samples, len(datas), "n_samples", none=False, scalar=True)
     if datas:
         _check_draw_arguments(counts, first_sample, block_width, rel_tol, max_iters)
     counts = [int(s) for s in counts]
     seeds = _seeds_of(seed, len(datas))
-    rws = _weights_of(range_weights, len(datas), "range_weights")
-    lws = _weights_of(loop_closure_weights, len(datas), "loop_closure_weights")
-    wanted = _variables_of(variables, len(datas))
-    groups: dict = {}
-    for i, (data, res) in enumerate(zip(datas, results)):
-        if data.dimension not in (2, 3):
-            raise ValueError(f"graph {i}: dimension must be 2 or 3")
-        try:
-            prob, point = _problem_and_point(data, res, rws[i], lws[i])
-            sel = _select(prob, wanted[i])
-        except ValueError as e:
-            raise ValueError(f"graph {i}: {str(e).replace('marginal_covariances', 'posterior_samples')}") from None
+    rws = per_graph(range_weights, len(datas), "range_weights")
+    lws = per_graph(loop_closure_weights, len(datas), "loop_closure_weights")
+    wanted = per_graph(variables, len(datas), "variables")
+
+    def member(i, data, res):
+        prob, point = _problem_and_point(data, res, rws[i], lws[i])
+        sel = _select(prob, wanted[i])
         if prob.n == 0:
-            raise ValueError(f"graph {i}: the graph has no unknowns")
-        groups.setdefault(data.dimension, []).append((i, prob, point, sel))
-    out: list = [None] * len(datas)
-    number = 0
-    for dim in sorted(groups):
-        members = groups[dim]
-        for c0 in range(0, len(members), int(max_group)):
-            chunk = members[c0 : c0 + int(max_group)]
-            idx, probs, points, sels = ([m[k] for m in chunk] for k in range(4))
-            args = (probs, points, [results[i] for i in idx], sels, idx, number, [counts[i] for i in idx], [seeds[i] for i in idx],
-                    int(first_sample), rel_tol, max_iters, int(block_width), engine)
-            if engine == "python":
-                got = group_samples(None, *args)
-            else:
-                with RefineBatchHandle(probs, lib_path, solver_settings) as h:
-                    got = group_samples(h, *args)
-            for i, g in zip(idx, got):
-                out[i] = g
-            number += 1
-    return out
+            raise ValueError("the graph has no unknowns")
+        return prob, point, sel
+
+    def body(handle, number, idx, probs, points, extras):
+        return group_samples(handle, probs, points, [results[i] for i in idx], extras[0], idx, number, [counts[i] for i in idx],
+                             [seeds[i] for i in idx], int(first_sample), rel_tol, max_iters, int(block_width), engine)
+
+    groups = grouped(datas, results, member, who="posterior_samples")
+    return run_chunks(groups, max_group, [None] * len(datas), body, engine == "device", lib_path, solver_settings)
 
 
 __all__ = ["posterior_samples_batch", "batch_draws", "group_samples", "SAMPLES_BATCH_SYMBOLS", "ScoreSamplesBatchInfo"]

@@ -1,8 +1,8 @@
 """The weakest modes of many refined estimates at once (include/score_spectrum_batch.h, csrc/score_spectrum_batch.hpp).
 
 ``information_spectrum`` takes one graph, builds one refinement handle and reads a 48 x 48 pencil back to the host in every
-LOBPCG iteration.  ``information_spectrum_batch`` hands the graphs to the device as groups, as ``refine_estimate_batch`` and
-``marginal_covariances_batch`` do: the group handle's union matrix H = J'J is block diagonal, so one union vector carries
+LOBPCG iteration.  ``information_spectrum_batch`` hands the graphs to the device as groups, by the rule of
+``score_amd/groups.py``: the group handle's union matrix H = J'J is block diagonal, so one union vector carries
 one vector of every member, and six blocks of 16 union vectors run the block eigensolver on every member in lock-step
 rounds (``score_refine_batch_spectrum``).  The Rayleigh-Ritz step runs on the device, one workgroup per member.  Every
 member has its own shift, tolerance, done words, mode and verdict: a member's result is what a group of that member alone
@@ -19,7 +19,8 @@ from typing import Optional
 
 import numpy as np
 
-from .bindings import SPECTRUM_BATCH, ScoreSpectrumBatchInfo, bind, ptr, steps_and_converged
+from .bindings import SPECTRUM_BATCH, Cutter, ScoreSpectrumBatchInfo, bind, ptr, steps_and_converged
+from .groups import chunks, grouped, paired, per_graph
 from .marginals import _problem_and_point, _select
 from .solver import _i32p, load_library
 from .spectrum import MAX_MODES, MIN_DEVICE_UNKNOWNS, Modes, _layout, _python_spectrum
@@ -55,11 +56,9 @@ def batch_spectrum(handle, points, k, rel_tol=1e-9, max_iters=200, shift=1e-8):
     if rc < 0:
         raise RuntimeError(f"score_refine_batch_spectrum failed: {lib.score_last_error().decode()}")
     iterations, converged = steps_and_converged(its)
-    out, v0 = [], 0
+    cut, out = Cutter(), []
     for g, n in enumerate(sizes):
-        out.append((values[g * kk:(g + 1) * kk].copy(), vectors[v0:v0 + kk * n].reshape(kk, n).copy(), res[g * kk:(g + 1) * kk].copy(),
-                    int(iterations[g]), bool(converged[g]), float(h_max[g])))
-        v0 += kk * n
+        out.append((cut(values, kk), cut(vectors, kk * n, (kk, n)), cut(res, kk), int(iterations[g]), bool(converged[g]), float(h_max[g])))
     return rc, out, info.as_dict()
 
 
@@ -104,14 +103,14 @@ def information_spectrum_batch(datas, results, k: int = 8, range_weights=None, l
                                lib_path: Optional[str] = None, solver_settings: Optional[dict] = None):
     """``information_spectrum`` for many graphs at once: ``datas`` and ``results`` graph by graph, ``range_weights`` /
     ``loop_closure_weights`` None or lists with one entry per graph.  The graphs are grouped by dimension, in chunks of at
-    most ``max_group``, as ``marginal_covariances_batch`` groups them; each group is one device handle and one
+    most ``max_group`` (the rule of ``score_amd/groups.py``); each group is one device handle and one
     ``score_refine_batch_spectrum`` call (``engine="device"``) or the dense ``eigh`` graph by graph (``engine="python"``).
     A graph with fewer than 48 unknowns is answered on the host by the dense path and says so in ``info["engine"]``.
     Returns a list of ``(Modes, info)`` in input order: per graph what ``information_spectrum`` returns, plus ``group`` (the
     group's number) and ``rounds`` (lock-step rounds of the group's call; ``setup_ms`` and ``solve_ms`` are the group's).
     The single call's ValueErrors are raised with ``graph i:`` in front; a graph with a pair that is not converged raises the
     single call's RuntimeError with the graph's index."""
-    from .refine_batch import RefineBatchHandle, _weights_of
+    from .refine_batch import RefineBatchHandle
 
     if engine not in ("device", "python"):
         raise ValueError("engine must be 'device' or 'python'")
@@ -123,53 +122,41 @@ def information_spectrum_batch(datas, results, k: int = 8, range_weights=None, l
         raise ValueError("max_iters must be at least 1")
     if not shift > 0 or not np.isfinite(shift):
         raise ValueError("shift must be positive")
-    datas, results = list(datas), list(results)
-    if len(datas) != len(results):
-        raise ValueError(f"one estimate per graph expected: {len(datas)} graphs, {len(results)} estimates")
-    if int(max_group) < 1:
-        raise ValueError("max_group must be at least 1")
+    datas, results = paired(datas, results, max_group)
     k = int(k)
-    rws = _weights_of(range_weights, len(datas), "range_weights")
-    lws = _weights_of(loop_closure_weights, len(datas), "loop_closure_weights")
-    groups: dict = {}
-    for i, (data, res) in enumerate(zip(datas, results)):
-        if data.dimension not in (2, 3):
-            raise ValueError(f"graph {i}: dimension must be 2 or 3")
-        try:
-            prob, point = _problem_and_point(data, res, rws[i], lws[i])
-        except ValueError as e:
-            raise ValueError(f"graph {i}: {e}") from None
+    rws = per_graph(range_weights, len(datas), "range_weights")
+    lws = per_graph(loop_closure_weights, len(datas), "loop_closure_weights")
+
+    def member(i, data, res):
+        prob, point = _problem_and_point(data, res, rws[i], lws[i])
         if k > prob.n:
-            raise ValueError(f"graph {i}: k = {k} modes of a graph with {prob.n} unknowns")
-        groups.setdefault(data.dimension, []).append((i, prob, point))
+            raise ValueError(f"k = {k} modes of a graph with {prob.n} unknowns")
+        return prob, point
+
     out: list = [None] * len(datas)
-    number = 0
-    for dim in sorted(groups):
-        members = groups[dim]
-        for c0 in range(0, len(members), int(max_group)):
-            chunk = members[c0 : c0 + int(max_group)]
-            rounds = 0
-            on_device = [m for m in chunk if engine == "device" and m[1].n >= MIN_DEVICE_UNKNOWNS]
-            for i, prob, point in chunk:
-                if engine == "python" or prob.n < MIN_DEVICE_UNKNOWNS:
-                    out[i] = _host_member(prob, point, k, rel_tol, shift)
-            if on_device:
-                probs, points = [m[1] for m in on_device], [m[2] for m in on_device]
-                with RefineBatchHandle(probs, lib_path, solver_settings) as h:
-                    _, per, rec = h.spectrum(points, k, rel_tol, int(max_iters), shift)
-                rounds = int(rec["rounds"])
-                for (i, prob, _), (values, Vt, res, its, converged, h_max) in zip(on_device, per):
-                    if not converged:
-                        bad = [j for j in range(k) if not res[j] <= rel_tol * h_max]
-                        what = ", ".join(f"mode {j} (residual {res[j]:.3e})" for j in bad) if bad else "the iteration broke down and"
-                        raise RuntimeError(f"information_spectrum_batch: graph {i}: {what} did not reach {rel_tol:g} * h_max = "
-                                           f"{rel_tol * h_max:.3e} in {max_iters} iterations")
-                    info = {"h_max": h_max, "shift": float(shift) * h_max, "iterations": int(its), "unconverged": 0,
-                            "setup_ms": float(rec["setup_ms"]), "solve_ms": float(rec["solve_ms"]), "engine": "device"}
-                    out[i] = (_modes_of(prob, values, np.ascontiguousarray(Vt.T), res, h_max, rel_tol), info)
-            for i, _, _ in chunk:
-                out[i][1]["group"], out[i][1]["rounds"] = number, rounds
-            number += 1
+    # (the placement is this call's own: a member below MIN_DEVICE_UNKNOWNS is answered on the host, the handle holds the rest)
+    for number, chunk in chunks(grouped(datas, results, member), max_group):
+        rounds = 0
+        on_device = [m for m in chunk if engine == "device" and m[1].n >= MIN_DEVICE_UNKNOWNS]
+        for i, prob, point in chunk:
+            if engine == "python" or prob.n < MIN_DEVICE_UNKNOWNS:
+                out[i] = _host_member(prob, point, k, rel_tol, shift)
+        if on_device:
+            probs, points = [m[1] for m in on_device], [m[2] for m in on_device]
+            with RefineBatchHandle(probs, lib_path, solver_settings) as h:
+                _, per, rec = h.spectrum(points, k, rel_tol, int(max_iters), shift)
+            rounds = int(rec["rounds"])
+            for (i, prob, _), (values, Vt, res, its, converged, h_max) in zip(on_device, per):
+                if not converged:
+                    bad = [j for j in range(k) if not res[j] <= rel_tol * h_max]
+                    what = ", ".join(f"mode {j} (residual {res[j]:.3e})" for j in bad) if bad else "the iteration broke down and"
+                    raise RuntimeError(f"information_spectrum_batch: graph {i}: {what} did not reach {rel_tol:g} * h_max = "
+                                       f"{rel_tol * h_max:.3e} in {max_iters} iterations")
+                info = {"h_max": h_max, "shift": float(shift) * h_max, "iterations": int(its), "unconverged": 0,
+                        "setup_ms": float(rec["setup_ms"]), "solve_ms": float(rec["solve_ms"]), "engine": "device"}
+                out[i] = (_modes_of(prob, values, np.ascontiguousarray(Vt.T), res, h_max, rel_tol), info)
+        for i, _, _ in chunk:
+            out[i][1]["group"], out[i][1]["rounds"] = number, rounds
     return out
 
 
