@@ -10,7 +10,9 @@
 //     k_prec<STEP> a = r'z / p'w ; xt += a p ; r -= a w ; z = M^-1 r ; partial r'z
 //     k_spmv<KPB>  p  = z + (r'z_new / r'z_old) p fused into the next w = K p
 //   (the last CG iteration replaces STEP/pupdate by k_xupdate:
-//                  xt += a p ; x = alpha xt + (1 - alpha) x)
+//                  xt += a p ; x = alpha xt + (1 - alpha) x
+//    -- deferred: applied by the next k_spmv<RHS>, or, for a single problem, by helper
+//    workgroups of the k_cone and the next k_prec<INIT> launches, see enqueue_iteration)
 //   k_cone         v = alpha (b - A xt) + (1 - alpha) s ; s = Proj_K(v - y/rho) ;
 //                  y += rho (s - v) ; u = rho (b - s) - y      one cone per lane
 //
@@ -954,7 +956,7 @@ struct HipBackend {
     DevBuf<PrecWork> prec_work, factor_work;   // factor_work: what a factorisation of K visits (HostSystem::factor_work)
     DevBuf<int64_t> q_entpart;                 // per problem: its entry range in the Newton matrix
     int64_t q_ent_max = 0;
-    static constexpr int64_t kHelpEntries = (int64_t)kPrecThreads * kPrecChunk;  // vector entries per update helper
+    static constexpr int64_t kHelpEntries = score::kHelpEntries;  // vector entries per update helper
     int n_help = 0;                            // update-helper records appended to both sets' PrecSet::rec
     DevBuf<int32_t> vb_first, vb_end, vb_prob; // blocks of <= 256 vector entries per problem (k_xupdate)
     int n_vblocks = 0;
@@ -2609,6 +2611,7 @@ struct HipBackend {
         a.cone_row = cone_row.d; a.cone_dim = cone_dim.d; a.cone_type = cone_type.d; a.cone_meta = cone_meta.d;
         a.cone_cols = (const int4*)cone_cols.d; a.cone_vals = (const double2*)cone_vals.d;
         a.uniform_cones = (H->count == 1) ? (int)H->cone_row.size() : 0;
+        a.cones_per_wg = kConesPerBlock;
         a.block_first = cone_block_first.d; a.block_prob = cone_block_prob.d;
         a.done = done.d; a.rho = rho.d; a.b = b.d; a.xt = gathered;
         a.s = s.d; a.y = xy.d + H->n_tot; a.u = xtu.d + H->n_tot;
@@ -2620,6 +2623,22 @@ struct HipBackend {
         a.skip_large = n_large_cones > 0 ? 1 : 0;
         return a;
     }
+    // The loop's cone launch of a single problem: kLoopConesPerWg cones per workgroup instead of one per lane -- returns the
+    // number of cone workgroups.  (k_pres, k_refresh_u and the batches keep the host's blocks of kConesPerBlock.)
+    static constexpr int kLoopConesPerWg = 128;
+    int loop_cone_blocks(ConeArgs& a) const {
+        if (a.uniform_cones <= 0) return n_cone_blocks;
+        a.cones_per_wg = kLoopConesPerWg;
+        return (a.uniform_cones + kLoopConesPerWg - 1) / kLoopConesPerWg;
+    }
+    // append the update helpers (sweep_help()) to a cone launch of `grid` workgroups: returns the new grid
+    unsigned cone_helpers(ConeArgs& a, unsigned grid) const {
+        a.help0 = (int)grid; a.help_n = (int)H->n_tot;
+        a.help_rep_end = H->rep > 1 ? (int)((int64_t)H->rep * H->rep_n[0]) : 0;
+        a.wfin = w.d; a.kx = kx.d; a.x = xy.d;
+        return grid + (unsigned)n_cone_help();
+    }
+    int n_cone_help() const { return (int)((H->n_tot + kConeHelpEntries - 1) / kConeHelpEntries); }
 
     void upload_rho(const HostSystem& h) {
         (void)h;
@@ -2788,11 +2807,22 @@ struct HipBackend {
         // loop closures (score_link.hpp): the Woodbury correction of the set's chain solve
         if (n_link_items && S.link_on && depth == PrecDepth::all) link_apply<MODE>(S, pa);
     }
+    // does a chain launch of set S run the kernel that has helper items (k_prec_pre), with helper records to read?
+    bool help_capable(const PrecSet& S) const {
+        if (n_help <= 0 || n_prec == 0 || split.active || S.rec.d == nullptr) return false;
+        return H->bs <= 3 ? ((prec_reg && S.use_fac32) || prec_pre) : (prec_pre && S.use_fac32);
+    }
+    // The ADMM loop finishes a PCG sweep on helper items (single-problem handles: the launches plus their helpers fit the
+    // chip): kx and x of the last step on the cone launch, xt on the next INIT, the measuring iteration's x on its extra
+    // STEP.  Without them -- batches, the split and the streaming chain kernels -- the next right-hand-side kernel applies
+    // the pending update on its own rows and a measuring iteration ends with k_xupdate.
+    bool sweep_help() const { return help_capable(Kset) && n_cone_blocks > 0; }
     template <int BS, int MODE>
     void launch_prec_bs(const PrecArgs& pa_in, int slot, bool use_fac32) {
-        // (the k_prec_pre launches of a STEP carry the update helpers of a single-problem handle, see the records)
+        // (the k_prec_pre launches of a STEP carry the update helpers of a single-problem handle, see the records; those of an
+        //  INIT of the ADMM loop carry them while the xt half of the last sweep's final step is pending -- PrecArgs::pend_p)
         PrecArgs pa = pa_in;
-        const bool help = MODE == PREC_STEP && n_help > 0 && pa.rec != nullptr && !pa.debug_skip;
+        const bool help = (MODE == PREC_STEP || pa.pend_p != nullptr) && n_help > 0 && pa.rec != nullptr && !pa.debug_skip;
         const int n_prec = this->n_prec + (help ? n_help : 0);
         pa.split_update = (help && MODE == PREC_STEP) ? 1 : 0;
         const unsigned nv = (MODE == PREC_INIT && pa.n_vec > 1) ? (unsigned)pa.n_vec : 1u;  // (several right-hand sides: PrecArgs::n_vec)
@@ -2970,13 +3000,17 @@ struct HipBackend {
     // kernel's gather; only a measuring iteration (the last of a launch graph) finalises it
     // itself, so the first iteration of a graph has nothing pending (`first`).
     // `ts` (score_time_iteration only): device slots, ts_stride per kernel of the iteration (KernelStamp)
+    // With sweep_help() the pending update never reaches the right-hand-side kernel: the helper workgroups of the cone
+    // launch have applied its kx and x halves, those of the next INIT launch apply the xt half (the cone blocks were
+    // gathering xt), and a measuring iteration's extra STEP relaxes x on its helpers instead of launching k_xupdate.
     size_t ts_stride = 0;
     void enqueue_iteration(bool measure, bool first, unsigned long long* ts = nullptr) {
         auto slot = [&](int k) -> unsigned long long* { return ts ? ts + ts_stride * k : nullptr; };
+        const bool sweep = sweep_help();
         {
             SpmvArgs ra = spmv_args(G1, xtu.d);
             ra.tstamp = slot(0);
-            ra.apply_update = first ? 0 : 1;
+            ra.apply_update = (first || sweep) ? 0 : 1;
             ra.pfin = last_p;
             launch_spmv<MODE_RHS>(G1, ra, 0);
         }
@@ -2986,9 +3020,15 @@ struct HipBackend {
         double* rz_cur = measure ? rz_meas0.d : rz_part0.d;
         double* p_cur = p.d;
         double* p_oth = p2.d;
+        if (sweep && !first && last_p) {
+            // (the helpers of this INIT read the pending direction while its chains write the new one: the other buffer)
+            if (last_p == p_cur) std::swap(p_cur, p_oth);
+            pa.pend_p = last_p; pa.pend_step = step.d;
+        }
         pa.p = p_cur; pa.rz_in = nullptr; pa.rz_out = rz_cur;
         pa.tstamp = slot(1);
         launch_prec<PREC_INIT>(Kset, pa, 1);
+        pa.pend_p = nullptr; pa.pend_step = nullptr;
         launch_kp(p_cur, slot(2), 2);
         for (int j = 2; j <= cg_iters; ++j) {
             double* rz_nxt = (rz_cur == rz_part0.d) ? rz_part1.d : rz_part0.d;
@@ -3004,20 +3044,22 @@ struct HipBackend {
         if (measure) {
             pa.tstamp = nullptr;
             pa.p = p_cur; pa.rz_in = rz_cur; pa.rz_out = rz_meas1.d;
+            if (sweep) { pa.x_relax = xy.d; pa.alpha_relax = st.alpha; }  // (its helpers relax x as well)
             launch_prec<PREC_STEP>(Kset, pa);  // also applies xt += a p, kx += a w, r -= a w
-            hipLaunchKernelGGL(k_xupdate, dim3(n_vblocks), dim3(kThreads), 0, stream, xupdate_args(p_cur, rz_cur, 0));
-        } else {
+            if (!sweep) hipLaunchKernelGGL(k_xupdate, dim3(n_vblocks), dim3(kThreads), 0, stream, xupdate_args(p_cur, rz_cur, 0));        } else {
             ca.apply_alpha = 1; ca.pfin = p_cur; ca.rz_in = rz_cur;
-            last_rz = rz_cur;  // what the next iteration's right-hand-side kernel has to apply
+            last_rz = rz_cur;  // what the next iteration has to apply: its right-hand-side kernel, or the helpers of its INIT
             last_p = p_cur;
         }
         ca.tstamp = slot(5);
         if (n_cone_blocks) {
             int chunk = 0;
-            const unsigned cgrid = xcd_grid_of(n_cone_blocks, chunk);
-            if (chunk) { ca.xcd_chunk = chunk; ca.n_blocks = n_cone_blocks; }
+            const int nb = loop_cone_blocks(ca);
+            unsigned cgrid = xcd_grid_of(nb, chunk);
+            if (chunk) { ca.xcd_chunk = chunk; ca.n_blocks = nb; }
+            if (sweep && !measure) cgrid = cone_helpers(ca, cgrid);
             launch_on_stream(k_cone, dim3(cgrid), dim3(kThreads), 0, 5, ca);
-            ca.xcd_chunk = 0;
+            ca.xcd_chunk = 0; ca.help0 = 0;
         }
         if (n_large_cones) {  // (general conic programs only: a SCORE model has none)
             ca.tstamp = nullptr;

@@ -267,6 +267,12 @@ int64_t get_graph_launches(HipBackend& be, double* out, int64_t len) {  // captu
     const double v = (double)be.graph_launches;
     return copy_out_min(&v, 1, out, len);
 }
+// how the ADMM loop ends a PCG sweep: {HipBackend::sweep_help(), update helpers per launch, entries per helper, cones per cone workgroup, helpers of the cone launch}
+int64_t get_sweep_help(HipBackend& be, double* out, int64_t len) {
+    const double v[5] = {be.sweep_help() ? 1.0 : 0.0, (double)be.n_help, (double)HipBackend::kHelpEntries, (double)(be.H->count == 1 ? HipBackend::kLoopConesPerWg : kConesPerBlock),
+                         (double)(be.sweep_help() ? be.n_cone_help() : 0)};
+    return copy_out_min(v, 5, out, len);
+}
 
 // ---- read-outs of the Newton polish (tests/test_polish_model_gpu.py): plain reads of buffers and host values that exist ----
 int64_t get_polish_eval(HipBackend& be, double* out, int64_t len) {
@@ -391,7 +397,7 @@ int64_t get_vec(HipBackend& be, const char* name, double* out, int64_t len) {
         {"polish_build_check", get_polish_build_check}, {"polish_assemble_at_x", get_polish_assemble_at_x},
         {"polish_prec_of_negg", get_polish_prec_of_negg},
         {"chain_of_col", get_chain_of_col}, {"chain_id_of_col", get_chain_id_of_col}, {"matrix_source", get_matrix_source},
-        {"graph_launches", get_graph_launches},
+        {"graph_launches", get_graph_launches}, {"sweep_help", get_sweep_help},
         {"polish_eval", get_polish_eval}, {"polish_trace", get_polish_trace}, {"polish_pcg", get_polish_pcg}, {"polish_p", get_polish_p}, {"polish_gate", get_polish_gate}, {"polish_blocks", get_polish_blocks},
     };
     for (const Computed& c : computed)
@@ -441,7 +447,9 @@ void time_kernel(HipBackend& be, const std::string& which, int reps, double* ms)
     const VecArgs va = be.xupdate_args(be.p.d, be.rz_part0.d, 1);
     const dim3 blk(kThreads);
     auto once = [&]() {
-        if (which == "rhs") { SpmvArgs ra = be.spmv_args(be.G1, be.xtu.d); ra.apply_update = 1; be.launch_spmv<MODE_RHS>(be.G1, ra); }
+        // (the loop's forms: with HipBackend::sweep_help() the right-hand-side kernel applies no pending update and the cone launch
+        //  carries the update helpers)
+        if (which == "rhs") { SpmvArgs ra = be.spmv_args(be.G1, be.xtu.d); ra.apply_update = be.sweep_help() ? 0 : 1; be.launch_spmv<MODE_RHS>(be.G1, ra); }
         else if (which.rfind("prec_init:", 0) == 0) { pa.debug_skip = std::atoi(which.c_str() + 10); be.launch_prec<PREC_INIT>(be.Kset, pa); }
         else if (which == "prec_init") be.launch_prec<PREC_INIT>(be.Kset, pa);
         else if (which.rfind("prec_step:", 0) == 0) { pa.debug_skip = std::atoi(which.c_str() + 10); be.launch_prec<PREC_STEP>(be.Kset, pa); }
@@ -456,7 +464,7 @@ void time_kernel(HipBackend& be, const std::string& which, int reps, double* ms)
         else if (which == "xupdate") hipLaunchKernelGGL(k_xupdate, dim3(be.n_vblocks), blk, 0, be.stream, va);
         // (the plain grid, not the XCD order the loop's cone launch takes -- HipBackend::xcd_grid_of: the measurement the
         //  profile scripts were calibrated with)
-        else if (which == "cone") { if (be.n_cone_blocks) { ConeArgs ca = be.cone_args(be.xtu.d); ca.apply_alpha = 1; hipLaunchKernelGGL(k_cone, dim3(be.n_cone_blocks), blk, 0, be.stream, ca); } }
+        else if (which == "cone") { if (be.n_cone_blocks) { ConeArgs ca = be.cone_args(be.xtu.d); ca.apply_alpha = 1; const unsigned nb = (unsigned)be.loop_cone_blocks(ca); const unsigned cg = be.sweep_help() ? be.cone_helpers(ca, nb) : nb; hipLaunchKernelGGL(k_cone, dim3(cg), blk, 0, be.stream, ca); } }
         else if (which == "nop") hipLaunchKernelGGL(k_nop, dim3(be.K.nblocks), blk, 0, be.stream, (int*)nullptr);
         else if (which == "nop1") hipLaunchKernelGGL(k_nop, dim3(1), dim3(64), 0, be.stream, (int*)nullptr);
         else if (which == "nop_load") hipLaunchKernelGGL(k_nop_load, dim3(be.K.nblocks), blk, 0, be.stream, be.K.blk_prob.d, be.done.d, (int*)nullptr);
@@ -493,7 +501,7 @@ void time_iteration(HipBackend& be, int warmup, int iters, double* us, int with_
     HIP_CHECK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, be.st.device));
     if (khz <= 0) throw std::runtime_error("score_time_iteration: no wall clock rate");
     for (int k = 0; k < 12; ++k) us[k] = 0.0;
-    const int maxb = std::max(std::max(be.G1.nblocks, be.Kset.blocks()) + 8, std::max(be.n_prec + be.n_help, be.n_cone_blocks + 8));  // (grids: XCD rounding, update helpers)
+    const int maxb = std::max(std::max(be.G1.nblocks, be.Kset.blocks()) + 8, std::max(be.n_prec + be.n_help, (be.H->count == 1 ? ((int)be.H->cone_row.size() + HipBackend::kLoopConesPerWg - 1) / HipBackend::kLoopConesPerWg : be.n_cone_blocks) + 8 + be.n_cone_help()));  // (grids: XCD rounding, update helpers)
     be.ts_stride = (size_t)2 * maxb;
     const size_t per_iter = 6 * be.ts_stride, nslot = per_iter * iters;
     {

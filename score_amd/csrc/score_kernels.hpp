@@ -1056,6 +1056,11 @@ struct PrecArgs {
     long long vec_stride;
     int split_update;      // STEP of k_prec_pre: xt += alpha p, kx += alpha w are done by the helper items (kind 2) of this
                            // launch, on CUs the chains leave idle, instead of by the chain / Jacobi workgroups themselves
+    // The end of the ADMM loop's PCG sweep on the same helper items (single-problem handles, HipBackend::sweep_help):
+    const double* pend_p;     // INIT: xt += step p of the PREVIOUS iteration's last PCG step is still pending -- the helper items
+    const double* pend_step;  //       apply it (step: per problem, published by that iteration's cone launch); null: nothing pending
+    double* x_relax;          // STEP of a measuring iteration: the helper items also relax x = al xt + (1 - al) x; null: not
+    double alpha_relax;
     // Device-side termination of a PCG solve (the Newton polish; null in the ADMM loop, whose PCG
     // count is fixed).  The first STEP of a solve (gate_first) turns r'z_0 into the problem's
     // threshold tol2[prob] * r'z_0; every later STEP compares the r'z it is about to use with it
@@ -1116,6 +1121,46 @@ constexpr int kPrecThreads = 512;
 constexpr int kPrecWaves = kPrecThreads / 64;
 constexpr int kPrecChunk = 6;   // entries per lane whose loads are issued together
 constexpr int kMaxLevels = 20;  // radix 2 .. 4: chains of up to 2^20 nodes (the host checks)
+constexpr int kHelpEntries = kPrecThreads * kPrecChunk;  // vector entries per update helper of a chain launch
+
+// Row-parallel end of a PCG step, CH entries per lane: xt += step p, kx += step w, x = al xt + (1 - al) x on the entries
+// first + u * stride below e_end.  load() requests every operand at once on clamped indices (a null vector is not read: it
+// counts as zero), apply() writes the vectors it is given.  One body for the update helpers of the chain launches
+// (k_prec_pre, work items of kind 2) and of the loop's cone launch (k_cone): the expressions, and with them what the
+// compiler contracts, are the same wherever the update runs.
+template <int CH>
+struct SweepRows {
+    int first, stride, e_end;
+    int idx[CH];
+    double pv[CH], wv[CH], xv[CH], kv[CH], rv[CH];
+    __device__ __forceinline__ void load(int first_, int stride_, int e_end_, const double* p, const double* w, const double* xt,
+                                         const double* kx, const double* x) {
+        first = first_; stride = stride_; e_end = e_end_;
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+            idx[u] = min(first + u * stride, e_end - 1);
+            pv[u] = p[idx[u]];
+            wv[u] = w ? w[idx[u]] : 0.0;
+            xv[u] = xt ? xt[idx[u]] : 0.0;
+            kv[u] = kx ? kx[idx[u]] : 0.0;
+            rv[u] = x ? x[idx[u]] : 0.0;
+        }
+    }
+    // The fused multiply-adds are spelled out.  The relaxed x keeps the rounding of the kernel that formed it before this
+    // body did: the right-hand-side kernel's epilogue on replicated rows (entries below rep_end; batches still run it there)
+    // rounds al xt first -- (1 - al) x + [al xt] --, its plain rows and k_xupdate (rep_end = 0) round (1 - al) x first.
+    __device__ __forceinline__ void apply(double step, double al, int rep_end, double* xt, double* kx, double* x) const {
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+            if (first + u * stride < e_end) {
+                const double xn = __builtin_fma(step, pv[u], xv[u]);
+                if (xt) NTSP(xt[idx[u]], xn);
+                if (kx) NTSP(kx[idx[u]], __builtin_fma(step, wv[u], kv[u]));
+                if (x) x[idx[u]] = idx[u] < rep_end ? __builtin_fma(1.0 - al, rv[u], al * xn) : __builtin_fma(al, xn, (1.0 - al) * rv[u]);
+            }
+        }
+    }
+};
 
 // Factor blocks of one run (thread j of level L): all loads unconditional on a
 // clamped position so that they are issued back to back.
@@ -1653,30 +1698,27 @@ __device__ __forceinline__ void prec_pre_body(const PrecArgs& a) {
     }
     double local = 0.0;
     if (wk.kind == 2) {
-        // update helper (STEP with split_update; appended after the problem's own items, so never the gate's lead and
+        // update helper (STEP with split_update, INIT with a pending xt update; appended after the problem's own items, so never the gate's lead and
         // outside the r'z partials): entries [index, index + count) of xt and kx.  alpha and the gate's verdict are
         // derived from the same partial sums in the same order as in the chain workgroups -- the same bits.
         if (dn || dn_late) return;
-        if (MODE == PREC_INIT) return;  // (helpers ride on STEP launches only)
-        const double gref = (a.gate_flag && !a.gate_first) ? a.gate_ref[prob] : 0.0;
         const int e_end = wk.index + wk.count;
-        int idx[kPrecChunk];
-        double pv[kPrecChunk], wv[kPrecChunk], xv[kPrecChunk], kv[kPrecChunk];
-#pragma unroll
-        for (int u = 0; u < kPrecChunk; ++u) {
-            idx[u] = min(wk.index + t + u * kPrecThreads, e_end - 1);
-            pv[u] = a.p[idx[u]]; wv[u] = a.w[idx[u]]; xv[u] = a.xt_zero ? 0.0 : a.xt[idx[u]]; kv[u] = a.kx[idx[u]];
+        SweepRows<kPrecChunk> rows;
+        if (MODE == PREC_INIT) {
+            // (INIT of the ADMM loop: the xt half of the previous iteration's last PCG step, whose kx and x halves rode on that
+            //  iteration's cone launch -- the cone blocks were gathering xt there.  The step is the one they published.)
+            if (!a.pend_p) return;
+            const double step = a.pend_step[prob];
+            rows.load(wk.index + t, kPrecThreads, e_end, a.pend_p, nullptr, a.xt, nullptr, nullptr);
+            rows.apply(step, 0.0, 0, a.xt, nullptr, nullptr);
+            return;
         }
+        const double gref = (a.gate_flag && !a.gate_first) ? a.gate_ref[prob] : 0.0;
+        rows.load(wk.index + t, kPrecThreads, e_end, a.p, a.w, a.xt_zero ? nullptr : a.xt, a.kx, a.x_relax);
         block_sum2_n<kPrecWaves>(acc_rz, acc_pw, red);
         const double alpha = acc_pw > 0.0 ? acc_rz / acc_pw : 0.0;
         if (a.gate_flag && (a.gate_first ? !(acc_rz > 0.0) : !(acc_rz > gref))) return;  // (pcg_gate's test, without its writes)
-#pragma unroll
-        for (int u = 0; u < kPrecChunk; ++u) {
-            if (wk.index + t + u * kPrecThreads < e_end) {
-                NTSP(a.xt[idx[u]], xv[u] + alpha * pv[u]);
-                NTSP(a.kx[idx[u]], kv[u] + alpha * wv[u]);
-            }
-        }
+        rows.apply(alpha, a.alpha_relax, 0, a.xt, a.kx, a.x_relax);
         return;
     }
     if (wk.kind == 1) {
@@ -2204,7 +2246,9 @@ struct ConeArgs {
     // so that they are requested together with the cone record instead of after it
     const int4* cone_cols;
     const double2* cone_vals;
-    int uniform_cones;      // > 0: one problem, block b holds cones [b * kConesPerBlock, ...) of uniform_cones
+    int uniform_cones;      // > 0: one problem, block b holds cones [b * cones_per_wg, ...) of uniform_cones
+    int cones_per_wg;       // (uniform_cones) <= 256: the lanes above it hold no cone -- they take part in the reduction of the
+                            //  step length, which keeps its shape over 256 lanes, and leave
     const int32_t* block_first;
     const int32_t* block_prob;
     const int32_t* done;
@@ -2229,6 +2273,15 @@ struct ConeArgs {
     double* step_out;   // per problem
     unsigned long long* tstamp;  // see KernelStamp
     int skip_large;     // k_cone leaves cones with more than kWaveCone rows to k_cone_wave
+    // Update helpers of the loop's cone launch (single-problem handles): the workgroups from help0 on hold no cones; helper
+    // h applies kx += a w and x = al (xt + a pfin) + (1 - al) x to entries [h * kConeHelpEntries, ...) of help_n.  The cone
+    // blocks read neither kx nor x; xt, which they gather, is left to the helper items of the next INIT launch.
+    int help0;          // 0: none
+    int help_n;
+    int help_rep_end;   // entries below it are replicated rows of the right-hand-side kernel (SweepRows::apply)
+    const double* wfin; // K pfin
+    double* kx;
+    double* x;
 };
 
 __device__ __forceinline__ double a_row_dot(const ConeArgs& a, int i, const double* __restrict__ v) {
@@ -2241,9 +2294,43 @@ constexpr int kSmallCone = 4;    // rows
 constexpr int kConeRowNnz = 2;   // entries per row handled by the register path
 constexpr int kWaveCone = 32;    // cones with more rows than this are projected by one wavefront each (k_cone_wave)
 
+// This lane's share of the partial sums of the last PCG step's r'z and p'w (k_cone: 256 lanes; block_sum2 finishes them)
+__device__ __forceinline__ void cone_step_partials(const ConeArgs& a, int prob, double& rz, double& pw) {
+    const int l0 = a.uni.on ? a.uni.l0 : a.prec_part_ptr[prob], l1 = a.uni.on ? a.uni.l1 : a.prec_part_ptr[prob + 1];
+    const int k0 = a.uni.on ? a.uni.k0 : a.kblk_part_ptr[prob], k1 = a.uni.on ? a.uni.k1 : a.kblk_part_ptr[prob + 1];
+    const int i0 = l0 + (int)threadIdx.x, j0 = k0 + (int)threadIdx.x;
+    if (i0 < l1) rz = a.rz_in[i0];
+    if (j0 < k1) pw = a.pw_in[j0];
+    for (int i = i0 + kThreads; i < l1; i += kThreads) rz += a.rz_in[i];
+    for (int i = j0 + kThreads; i < k1; i += kThreads) pw += a.pw_in[i];
+}
+
+// Update helper of the loop's cone launch (ConeArgs::help0): the step length from the same partial sums through the same
+// reduction as the cone blocks form it -- the same bits as the one they publish --, then kx and x on this workgroup's
+// kConeHelpEntries entries, kPrecChunk per lane, all requested in one trip: the helpers start with the cone blocks and must
+// not outlast them (two trips per helper did: profiles/TRIED.md).
+constexpr int kConeHelpEntries = kThreads * kPrecChunk;
+__device__ __forceinline__ void cone_help_body(const ConeArgs& a, double* red) {
+    const int dnv = a.done[0];
+    double rz = 0.0, pw = 0.0;
+    cone_step_partials(a, 0, rz, pw);
+    const int e0 = ((int)blockIdx.x - a.help0) * kConeHelpEntries;
+    const int e_end = min(e0 + kConeHelpEntries, a.help_n);
+    SweepRows<kPrecChunk> rows;
+    rows.load(e0 + (int)threadIdx.x, kThreads, e_end, a.pfin, a.wfin, a.xt, a.kx, a.x);
+    if (dnv) return;  // (uniform; nothing has been written)
+    block_sum2(rz, pw, red);
+    const double step = pw > 0.0 ? rz / pw : 0.0;
+    rows.apply(step, a.alpha_relax, a.help_rep_end, nullptr, a.kx, a.x);
+}
+
 __global__ __launch_bounds__(kThreads) void k_cone(ConeArgs a) {
     KernelStamp stamp(a.tstamp);
     __shared__ double red[8];
+    if (a.help0 > 0 && (int)blockIdx.x >= a.help0) {  // (uniform: an update helper, appended to the cone blocks' grid)
+        cone_help_body(a, red);
+        return;
+    }
     // (XCD-aware block order as in k_spmv: the cone blocks of one problem of a batch project through one L2)
     const int b = a.xcd_chunk > 0 ? (int)(blockIdx.x & 7) * a.xcd_chunk + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
     if (a.xcd_chunk > 0 && b >= a.n_blocks) return;
@@ -2254,15 +2341,7 @@ __global__ __launch_bounds__(kThreads) void k_cone(ConeArgs a) {
     // reduced (two barriers) only after the cone's own loads are in flight.
     const int dnv = a.done[prob];
     double rz = 0.0, pw = 0.0;
-    if (a.apply_alpha) {
-        const int l0 = a.uni.on ? a.uni.l0 : a.prec_part_ptr[prob], l1 = a.uni.on ? a.uni.l1 : a.prec_part_ptr[prob + 1];
-        const int k0 = a.uni.on ? a.uni.k0 : a.kblk_part_ptr[prob], k1 = a.uni.on ? a.uni.k1 : a.kblk_part_ptr[prob + 1];
-        const int i0 = l0 + (int)threadIdx.x, j0 = k0 + (int)threadIdx.x;
-        if (i0 < l1) rz = a.rz_in[i0];
-        if (j0 < k1) pw = a.pw_in[j0];
-        for (int i = i0 + kThreads; i < l1; i += kThreads) rz += a.rz_in[i];
-        for (int i = j0 + kThreads; i < k1; i += kThreads) pw += a.pw_in[i];
-    }
+    if (a.apply_alpha) cone_step_partials(a, prob, rz, pw);
     double step = 0.0;  // step length of the last PCG step (its xt update is applied on the fly)
     auto finish_step = [&]() {
         if (a.apply_alpha) {
@@ -2273,8 +2352,8 @@ __global__ __launch_bounds__(kThreads) void k_cone(ConeArgs a) {
         }
     };
     // (one problem: the block boundaries are arithmetic -- one dependent load less)
-    const int c_end = a.uniform_cones > 0 ? min((b + 1) * kConesPerBlock, a.uniform_cones) : a.block_first[b + 1];
-    const int c = (a.uniform_cones > 0 ? b * kConesPerBlock : a.block_first[b]) + threadIdx.x;
+    const int c_end = a.uniform_cones > 0 ? min((b + 1) * a.cones_per_wg, a.uniform_cones) : a.block_first[b + 1];
+    const int c = (a.uniform_cones > 0 ? b * a.cones_per_wg : a.block_first[b]) + threadIdx.x;
     // one 32-byte record per cone (first row, dimension, type, the row pointers of its first four
     // rows) instead of the chain cone_row -> A_ptr; loaded on a clamped index by every lane
     const int cl = min(c, c_end - 1);
