@@ -88,6 +88,14 @@ class ScoreSpectrumBatchInfo(InfoRecord):
     ]
 
 
+class ScoreCurvatureBatchInfo(InfoRecord):
+    _fields_ = [
+        ("members", C.c_int32), ("modes", C.c_int32), ("block", C.c_int32), ("rounds", C.c_int32), ("unconverged", C.c_int32),
+        ("saddles", C.c_int32),
+        ("max_residual", C.c_double), ("setup_ms", C.c_double), ("solve_ms", C.c_double),
+    ]
+
+
 class ScoreSamplesInfo(InfoRecord):
     _fields_ = [
         ("samples", C.c_int32), ("batches", C.c_int32), ("pcg_iters", C.c_int32), ("unconverged", C.c_int32),
@@ -228,6 +236,15 @@ CURVATURE = Table("curvature", _NO_EIGENSOLVER, {
 })
 # and those after them (LATER_TABLES is pinned too)
 TABLES_SINCE = (CURVATURE,)
+
+CURVATURE_BATCH = Table("curvature_batch", _NO_EIGENSOLVER, {
+    "score_refine_batch_hessian_product": ([_handle, _f64p, _f64p, C.c_int32, _f64p, C.c_int32, _f64p], C.c_int),
+    "score_refine_batch_curvature": ([_handle, _f64p, _f64p, C.c_int32, C.c_double, C.c_int32, C.c_double, _f64p, _f64p, _f64p, _f64p,
+                                      _i32p, _f64p, _f64p, C.POINTER(ScoreCurvatureBatchInfo)], C.c_int),
+    "score_curvature_ritz": ([C.c_int32, _f64p, _f64p, _f64p, _f64p, _i32p, _i32p], C.c_int),
+})
+# and the group forms that followed (TABLES_SINCE is pinned as well)
+TABLES_AFTER = (CURVATURE_BATCH,)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

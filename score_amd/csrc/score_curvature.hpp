@@ -31,10 +31,41 @@
 
 namespace score {
 
-// one measurement of the view per lane: its exact block into the view's storage (a lane beyond the measurements: nothing)
+// The per-lane bodies, stated once for a graph (the kernels below) and for a group (score_curvature_batch.hpp):
+//   cv_blocks_lane   measurement m of the view: its exact block and its J'r into the view's storage (a lane beyond the
+//                    measurements: nothing)
+//   cv_gather_entry  entry k of the pattern: the sum of its exact (or J'J) slots in list order, without the shift; diff =
+//                    |sum of exact slots - sum of J'J slots| with a NaN counted as +inf (eblk == nullptr: not asked, zero)
+//   cv_dot_terms     one row's terms of x'w and x'x
+template <int DIM>
+__device__ __forceinline__ void cv_blocks_lane(const GnView& v, int64_t m) {
+    (void)gn_measurement<DIM, true>(v, m, true);
+}
+__device__ __forceinline__ double cv_gather_entry(const int32_t* __restrict__ hc_ptr, const int32_t* __restrict__ hc_slot,
+                                                  const double* __restrict__ hblk, const double* __restrict__ eblk, int exact,
+                                                  int64_t k, double& diff) {
+    double h = 0.0, e = 0.0;
+    for (int32_t c = hc_ptr[k]; c < hc_ptr[k + 1]; ++c) {
+        const int32_t s = hc_slot[c];
+        h += hblk[s];
+        if (eblk) e += eblk[s];
+    }
+    diff = 0.0;
+    if (eblk) {
+        diff = fabs(e - h);
+        diff = diff == diff ? diff : INFINITY;  // (fmax would drop a NaN)
+    }
+    return exact ? e : h;
+}
+__device__ __forceinline__ void cv_dot_terms(double xi, double wi, double& xw, double& xx) {
+    xw += xi * wi;
+    xx += xi * xi;
+}
+
+// one measurement of the view per lane
 template <int DIM>
 __global__ __launch_bounds__(kThreads) void k_cv_blocks(GnView v) {
-    (void)gn_measurement<DIM, true>(v, (int64_t)blockIdx.x * kThreads + threadIdx.x, true);
+    cv_blocks_lane<DIM>(v, (int64_t)blockIdx.x * kThreads + threadIdx.x);
 }
 
 // one entry of the pattern per lane.  out = (exact ? sum of eblk slots : sum of hblk slots) (+ sigma on the diagonal);
@@ -47,18 +78,8 @@ __global__ __launch_bounds__(kThreads) void k_cv_gather(const int32_t* __restric
     const int64_t k = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     double d = 0.0;
     if (k < nnz) {
-        double h = 0.0, e = 0.0;
-        for (int32_t c = hc_ptr[k]; c < hc_ptr[k + 1]; ++c) {
-            const int32_t s = hc_slot[c];
-            h += hblk[s];
-            if (eblk) e += eblk[s];
-        }
-        const double v = exact ? e : h;
+        const double v = cv_gather_entry(hc_ptr, hc_slot, hblk, eblk, exact, k, d);
         out[k] = is_diag[k] ? v + sigma : v;
-        if (eblk) {
-            d = fabs(e - h);
-            d = d == d ? d : INFINITY;  // (fmax would drop a NaN)
-        }
     }
     d = block_max(d, red);
     if (threadIdx.x == 0) diff_part[blockIdx.x] = d;
@@ -73,9 +94,7 @@ __global__ __launch_bounds__(kThreads) void k_cv_column_dots(const double* __res
     const double* wc = w + (size_t)c * (size_t)n;
     double xw = 0.0, xx = 0.0;
     for (long long i = threadIdx.x; i < n; i += kThreads) {
-        const double xi = xc[i];
-        xw += xi * wc[i];
-        xx += xi * xi;
+        cv_dot_terms(xc[i], wc[i], xw, xx);
     }
     block_sum2(xw, xx, red);
     if (threadIdx.x == 0) { dots[2 * c] = xw; dots[2 * c + 1] = xx; }

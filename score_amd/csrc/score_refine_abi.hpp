@@ -246,6 +246,31 @@ int score_spectrum_ritz(int32_t count, const double* GA, const double* GB, doubl
         return 0;
     });
 }
+int score_refine_batch_hessian_product(score_refine_batch* b, const double* poses, const double* landmarks, int32_t exact, const double* V,
+                                       int32_t n_cols, double* out) {
+    return refine_call(b, "score_refine_batch_hessian_product: null handle", poses, landmarks,
+                       "score_refine_batch_hessian_product: the points are missing", [&] {
+        require(V && out, "score_refine_batch_hessian_product: V and out are missing");
+        return score::gbc_product(*b, poses, landmarks, exact, V, n_cols, out);
+    });
+}
+int score_refine_batch_curvature(score_refine_batch* b, const double* poses, const double* landmarks, int32_t k, double rel_tol,
+                                 int32_t max_iters, double shift_rel, double* values, double* vectors, double* residuals,
+                                 double* gn_quotients, int32_t* iterations, double* h_max, double* c_max,
+                                 score_curvature_batch_info* info) {
+    return refine_call(b, "score_refine_batch_curvature: null handle", poses, landmarks, "score_refine_batch_curvature: the points are missing", [&] {
+        return score::gbc_solve(*b, poses, landmarks, k, rel_tol, max_iters, shift_rel, values, vectors, residuals, gn_quotients, iterations,
+                                h_max, c_max, info);
+    });
+}
+int score_curvature_ritz(int32_t count, const double* GA, const double* GB, double* theta, double* coef, int32_t* status, int32_t* kept) {
+    return abi_call([&] {
+        AbiEnv::require_device(0);
+        AbiEnv::Scope scope(0, false);
+        score::gsp_ritz_alone(count, GA, GB, theta, coef, status, kept, true, "score_curvature_ritz: ");
+        return 0;
+    });
+}
 int score_refine_batch_robust_run(score_refine_batch* b, const score_refine_robust_settings* rs, int32_t n_settings, const double* poses_in,
                                   const double* landmarks_in, double* poses_out, double* landmarks_out, double* weights, double* residuals,
                                   double* rel_weights, double* rel_residuals, int32_t keep_weights, score_refine_robust_info* infos) {

@@ -19,6 +19,7 @@
 #include "score_samples_batch.hpp"
 #include "score_leverage_batch.hpp"
 #include "score_spectrum_batch.hpp"
+#include "score_curvature_batch.hpp"
 
 // the measurement arrays (score_gn.hpp) on the device
 struct GnMeasDev : score::GnMeasT<DevBuf> {
@@ -326,6 +327,7 @@ struct score_refine_batch : RefineBase {
     std::vector<int32_t> word_host;
     score::GbmWork mvb;  // marginal covariances of the members (score_marginals_batch.hpp)
     score::GspWork spb;  // lowest eigenpairs of the members (score_spectrum_batch.hpp)
+    score::GbcWork gbc;  // half the Hessian of the members' costs: product and lowest eigenpairs (score_curvature_batch.hpp)
     score::GbsWork gbs;  // posterior samples of the members (score_samples_batch.hpp)
     score::GblWork gbl;  // range leverage and predicted range variances of the members (score_leverage_batch.hpp)
     // robust refinement: the members' parameters beside the base's buffers.  U keeps rng_prec / rel_kappa / rel_tau on the host

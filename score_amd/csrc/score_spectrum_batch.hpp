@@ -41,7 +41,8 @@
 // second decomposition; the unscaled pencil is re-read from global memory (18 KB each, in L2) when the Rayleigh quotients
 // are formed -- plus the 48 x 16 coefficients and the small vectors: 63 KB of static LDS, under the 64 KB a kernel may
 // declare (CDNA4 has 160 KiB per CU: two such workgroups fit, and a group launches one per member).
-// It writes theta[g][16], C[g][48][16], status[g] and kept[g] with plain vector stores.
+// It writes theta[g][16], C[g][48][16], status[g] and kept[g] with plain vector stores.  GspRitzArgs::indefinite lifts the test
+// that the lowest value is positive, as the host routine's argument does, for the pencils of score_curvature_batch.hpp.
 #pragma once
 
 #include <algorithm>
@@ -344,7 +345,9 @@ __device__ __forceinline__ bool gsp_jacobi(int mm, double* a, double* v, GspRitz
 
 // One attempt on the pencil (GA, GB), 48 x 48 row-major in global memory, with or without the P block.  true: L.th holds
 // the 16 values, L.c * L.sc the coefficients of the directions L.idx[0 .. L.ma).  kept: directions left after step 3.
-__device__ __forceinline__ bool gsp_ritz_attempt(const double* __restrict__ GA, const double* __restrict__ GB, bool use_p, GspRitzLds& L, int* kept) {
+// indefinite: the pencil of an indefinite A (score_curvature_batch.hpp) -- lifts the test of the lowest value, nothing else.
+__device__ __forceinline__ bool gsp_ritz_attempt(const double* __restrict__ GA, const double* __restrict__ GB, bool use_p, bool indefinite,
+                                                 GspRitzLds& L, int* kept) {
     const int t = threadIdx.x;
     constexpr int nb = kSpBlock;
     __syncthreads();  // (a second attempt: the first one's reads of L are over)
@@ -404,7 +407,7 @@ __device__ __forceinline__ bool gsp_ritz_attempt(const double* __restrict__ GA, 
     }
     __syncthreads();
     if (!gsp_jacobi(mk, L.m0, L.m2, L)) return false;  // m0 = Z, ev = mu
-    if (!(L.ev[0] > 0.0)) return false;
+    if (!indefinite && !(L.ev[0] > 0.0)) return false;
     for (int e = t; e < ma * nb; e += kThreads) {  // c = D Y Z[:, :nb]
         const int i = e / nb, j = e % nb;
         double s = 0.0;
@@ -450,6 +453,7 @@ struct GspRitzArgs {
     const double* GB;
     long long stride;
     double* theta; double* coef; int32_t* status; int32_t* kept;
+    int32_t indefinite;    // non-zero: A may be indefinite (gsp_ritz_attempt)
 };
 
 // grid (members): the 16 lowest Ritz pairs of the member's pencil (the head of the file); a pencil that breaks down leaves
@@ -463,7 +467,7 @@ __global__ __launch_bounds__(kThreads) void k_gsp_ritz(GspRitzArgs a) {
     int kept = 0, status = kSpRrBreakdown;
 #pragma unroll 1
     for (int attempt = 0; attempt < 2; ++attempt)  // step 5: once more without the P block (kSpRrOk = 0, kSpRrNoP = 1)
-        if (gsp_ritz_attempt(GA, GB, attempt == 0, L, &kept)) { status = attempt; break; }
+        if (gsp_ritz_attempt(GA, GB, attempt == 0, a.indefinite != 0, L, &kept)) { status = attempt; break; }
     if (status != kSpRrBreakdown) {
         if (t < kSpM) L.perm[t] = -1;  // where direction t sits among those in use
         __syncthreads();
@@ -564,12 +568,38 @@ struct GspWork {
     }
 };
 
-// The solve.  Batch: score_refine_batch (its union, point, blocks and gather, its linear-mode handle, its GspWork `spb`).
-template <class Batch>
-int gsp_solve(Batch& B, const double* poses, const double* landmarks, int32_t k, double rel_tol, int32_t max_iters, double shift_rel,
-              double* values, double* vectors, double* residuals, int32_t* iterations, double* h_max_out, score_spectrum_batch_info* info) {
-    const GbUnion& U = B.U;
+// What a call of the group's iteration is about, as SpInformation / SpCurvature say it for one graph: whose words open its
+// messages, the values the product reads (asked for once the members' shifts stand in the handle's `lambda` and the chain
+// factors of J'J + sigma_g I are derived; it runs inside the setup), whether A may be indefinite (the Ritz step's test of the
+// lowest value), and what follows the rounds while X and the blocks still stand.
+// GspInformation: score_refine_batch_spectrum, A_g = J'J + sigma_g I in the handle's own values.  score_curvature_batch.hpp
+// has the other.
+struct GspInformation {
+    static constexpr bool indefinite = false;
     const char* who = "score_refine_batch_spectrum: ";
+    template <class Batch>
+    const double* product_values(Batch& B) { return B.be().Kset.mat.val.d; }
+    template <class Batch>
+    void after_iteration(Batch&, const GspArgs&) {}
+};
+
+// what the iteration reports beside its outputs: the fields score_spectrum_batch_info and score_curvature_batch_info share,
+// and per member its shift, its values (k, ascending, the shift taken out) and the column of X behind each of them
+struct GspOutcome {
+    int rounds = 0, unconverged = 0;
+    double worst = 0.0, setup_ms = 0.0, solve_ms = 0.0;
+    std::vector<double> h_max, sigma, value;
+    std::vector<int> column;
+};
+
+// The solve, one body for both operators.  Batch: score_refine_batch (its union, point, blocks and gather, its linear-mode
+// handle, its GspWork `spb`).  The preconditioner is that of J'J + sigma_g I whatever the product reads.
+template <class Batch, class Op>
+int gsp_iterate(Batch& B, Op& op, const double* poses, const double* landmarks, int32_t k, double rel_tol, int32_t max_iters,
+                double shift_rel, double* values, double* vectors, double* residuals, int32_t* iterations, double* h_max_out,
+                GspOutcome& outcome) {
+    const GbUnion& U = B.U;
+    const char* who = op.who;
     if (k < 1 || k > kSpBlock) throw std::runtime_error(std::string(who) + "k must be 1..16");
     if (!(rel_tol > 0.0) || !std::isfinite(rel_tol) || max_iters < 1)
         throw std::runtime_error(std::string(who) + "rel_tol must be positive and max_iters >= 1");
@@ -600,6 +630,7 @@ int gsp_solve(Batch& B, const double* poses, const double* landmarks, int32_t k,
     GspRitzArgs ra{};
     ra.ctl = W.ctl.d; ra.GA = W.gram.d; ra.GB = W.gram.d + kSpM * kSpM; ra.stride = kSpGramOut;
     ra.theta = W.theta.d; ra.coef = W.coef.d; ra.status = W.status.d; ra.kept = W.kept.d;
+    ra.indefinite = Op::indefinite ? 1 : 0;
 
     // the points, the blocks, max diag H_g; then A_g = H_g + sigma_g I on the union pattern and the chain factors of all members
     B.set_point(poses, landmarks);
@@ -622,6 +653,7 @@ int gsp_solve(Batch& B, const double* poses, const double* landmarks, int32_t k,
     B.gather_h(sigma.data());
     be.derive_rho_data(false);
     staged_h2d(W.tol.d, tol.data(), tol.size() * sizeof(double), st);  // (waits for the stream: sigma has been read)
+    a.val = op.product_values(B);
 
     std::vector<GspState> S((size_t)G);
     std::vector<int32_t> words((size_t)G), status((size_t)G, 0);
@@ -670,6 +702,7 @@ int gsp_solve(Batch& B, const double* poses, const double* landmarks, int32_t k,
         product(kGspIterate);
         ritz_and_combine();
     }
+    op.after_iteration(B, a);
     // ascending per member; unit 2-norm on the way out (X is orthonormal to the rounding of the combine step)
     std::vector<double> theta((size_t)G * kSpBlock), X;
     staged_d2h(theta.data(), W.theta.d, theta.size() * sizeof(double), st);
@@ -681,6 +714,7 @@ int gsp_solve(Batch& B, const double* poses, const double* landmarks, int32_t k,
     int unconverged = 0;
     double worst = 0.0;
     size_t vec0 = 0;
+    outcome.value.assign((size_t)G * (size_t)k, 0.0); outcome.column.assign((size_t)G * (size_t)k, 0);
     for (int g = 0; g < G; ++g) {
         const GbMember& M = U.members[(size_t)g];
         const GspState& s = S[(size_t)g];
@@ -694,6 +728,8 @@ int gsp_solve(Batch& B, const double* poses, const double* landmarks, int32_t k,
             const int c = order[(size_t)j];
             const double rho = nr[c];
             worst = std::isfinite(rho) ? std::max(worst, rho) : INFINITY;
+            outcome.value[(size_t)g * (size_t)k + (size_t)j] = th[c] - sigma[(size_t)g];
+            outcome.column[(size_t)g * (size_t)k + (size_t)j] = c;
             if (values) values[(size_t)g * (size_t)k + (size_t)j] = th[c] - sigma[(size_t)g];
             if (residuals) residuals[(size_t)g * (size_t)k + (size_t)j] = rho;
             if (vectors) {
@@ -710,17 +746,31 @@ int gsp_solve(Batch& B, const double* poses, const double* landmarks, int32_t k,
         if (h_max_out) h_max_out[g] = hmax[(size_t)g];
     }
     const double t2 = now_ms();
-    if (info) {
-        info->members = G; info->modes = k; info->block = kSpBlock; info->rounds = rounds; info->unconverged = unconverged;
-        info->max_residual = worst; info->setup_ms = t1 - t0; info->solve_ms = t2 - t1;
-    }
+    outcome.rounds = rounds; outcome.unconverged = unconverged; outcome.worst = worst;
+    outcome.setup_ms = t1 - t0; outcome.solve_ms = t2 - t1;
+    outcome.h_max = hmax; outcome.sigma = sigma;
     return unconverged ? 1 : 0;
 }
 
-// score_spectrum_ritz: k_gsp_ritz alone on the caller's pencils, on buffers of the call's own
-inline void gsp_ritz_alone(int32_t count, const double* GA, const double* GB, double* theta, double* coef, int32_t* status, int32_t* kept) {
-    if (count < 1) throw std::runtime_error("score_spectrum_ritz: count must be positive");
-    if (!GA || !GB) throw std::runtime_error("score_spectrum_ritz: the pencils are missing");
+template <class Batch>
+int gsp_solve(Batch& B, const double* poses, const double* landmarks, int32_t k, double rel_tol, int32_t max_iters, double shift_rel,
+              double* values, double* vectors, double* residuals, int32_t* iterations, double* h_max_out, score_spectrum_batch_info* info) {
+    GspInformation op;
+    GspOutcome o;
+    const int rc = gsp_iterate(B, op, poses, landmarks, k, rel_tol, max_iters, shift_rel, values, vectors, residuals, iterations, h_max_out, o);
+    if (info) {
+        info->members = B.U.count; info->modes = k; info->block = kSpBlock; info->rounds = o.rounds; info->unconverged = o.unconverged;
+        info->max_residual = o.worst; info->setup_ms = o.setup_ms; info->solve_ms = o.solve_ms;
+    }
+    return rc;
+}
+
+// score_spectrum_ritz (and, with the indefinite rule, score_curvature_ritz): k_gsp_ritz alone on the caller's pencils, on
+// buffers of the call's own
+inline void gsp_ritz_alone(int32_t count, const double* GA, const double* GB, double* theta, double* coef, int32_t* status, int32_t* kept,
+                           bool indefinite = false, const char* who = "score_spectrum_ritz: ") {
+    if (count < 1) throw std::runtime_error(std::string(who) + "count must be positive");
+    if (!GA || !GB) throw std::runtime_error(std::string(who) + "the pencils are missing");
     NoArena no_arena;
     hipStream_t st = nullptr;
     const size_t G = (size_t)count, mm = (size_t)kSpM * kSpM;
@@ -735,6 +785,7 @@ inline void gsp_ritz_alone(int32_t count, const double* GA, const double* GB, do
     GspRitzArgs ra{};
     ra.GA = dA.d; ra.GB = dB.d; ra.stride = (long long)mm;
     ra.theta = dth.d; ra.coef = dc.d; ra.status = dst.d; ra.kept = dk.d;
+    ra.indefinite = indefinite ? 1 : 0;
     hipLaunchKernelGGL(k_gsp_ritz, dim3((unsigned)count), dim3(kThreads), 0, st, ra);
     HIP_CHECK(hipGetLastError());
     if (theta) staged_d2h(theta, dth.d, G * kSpBlock * sizeof(double), st);

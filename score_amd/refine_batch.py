@@ -18,7 +18,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from .bindings import LEVERAGE_BATCH, REFINE_BATCH, REFINE_ROBUST_BATCH, ScoreRefineRobustInfo, ScoreRefineRobustSettings, bind, ptr
+from .bindings import CURVATURE_BATCH, LEVERAGE_BATCH, REFINE_BATCH, REFINE_ROBUST_BATCH, ScoreRefineRobustInfo, ScoreRefineRobustSettings, bind, ptr
 from .groups import FollowUp, follow, grouped, paired, per_graph, run_chunks
 from .native import ScoreGraph, score_graph_struct
 from .refine import (GRADIENT, SOLVE, _as_results, _attempt, _gradient, _Handle, _Member, _native_info, _point_arrays, _point_from,
@@ -89,7 +89,7 @@ class RefineBatchHandle(_Handle):
     """A group handle (``score_refine_batch_create``) over ``probs`` (all of one dimension, every one with unknowns); ``run``
     takes and returns points in the problems' own form (``_Problem``: packed unknowns; ``_Problem3D``: (R, t, lm))."""
 
-    headers = (REFINE_BATCH, LEVERAGE_BATCH)
+    headers = (REFINE_BATCH, LEVERAGE_BATCH, CURVATURE_BATCH)
     destroy = "score_refine_batch_destroy"
 
     def __init__(self, probs: Sequence, lib_path: Optional[str] = None, solver_settings: Optional[dict] = None):
@@ -149,6 +149,23 @@ class RefineBatchHandle(_Handle):
         from .spectrum_batch import batch_spectrum
 
         return batch_spectrum(self, points, k, rel_tol, max_iters, shift)
+
+    def curvature(self, points, k, rel_tol: float = 1e-9, max_iters: int = 200, shift: float = 1e-8):
+        """``score_refine_batch_curvature`` at ``points`` (include/score_curvature_batch.h): the ``k`` lowest eigenpairs of
+        every member's E, half the Hessian of its cost.  Returns (return code, per member ``(values, vectors k x n_g,
+        residuals, v'(J'J)v, iterations, converged, h_max, c_max)``, the call's info record); the handle is left as it was
+        found."""
+        from .curvature_batch import batch_curvature
+
+        return batch_curvature(self, points, k, rel_tol, max_iters, shift)
+
+    def hessian_product(self, points, V_per_member, exact: bool = True):
+        """``score_refine_batch_hessian_product`` at ``points``: per member A_g V_g with A = E (``exact``) or J'J;
+        ``V_per_member``: one n_g x c array per member (or a vector each), the same c in 1..16 for all.  Returns the products in
+        the shapes of the inputs; the handle is left as it was found."""
+        from .curvature_batch import batch_hessian_product
+
+        return batch_hessian_product(self, points, V_per_member, exact)
 
     def samples(self, points, ids_per_member, n_samples, seeds, first_sample: int = 0, rel_tol: float = 1e-10, max_iters: int = 4000,
                 block_width: int = 16, with_rhs: bool = False, with_noise: bool = False):
@@ -238,7 +255,7 @@ class RefineBatchHandle(_Handle):
 def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-10, range_weights=None, loop_closure_weights=None,
                           engine: str = "native", lib_path: Optional[str] = None, solver_settings: Optional[dict] = None,
                           max_group: int = 64, marginals=None, samples=None, samples_seed: int = 0, leverage=None,
-                          leverage_seed: int = 0):
+                          leverage_seed: int = 0, curvature=None):
     """``refine_estimate`` for many graphs at once: ``datas`` and ``results`` member by member, ``range_weights`` /
     ``loop_closure_weights`` lists with one entry (an array as ``refine_estimate`` takes it, or None) per member -- they only
     scale precisions.  The members are grouped by dimension, in chunks of at most ``max_group`` (the rule of
@@ -257,11 +274,18 @@ def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-1
     ``leverage``: a number of draws S -- every group's handle then also forms the leverage and redundancy of every member's
     measurements at the refined points (``range_leverage_batch``'s call on the same handle: no pairs, graph i from the stream
     of ``leverage_seed + i``; ``engine="python"``: ``range_leverage``'s python engine), and ``info["leverage"]`` is that
-    graph's ``(Leverage, leverage_info)`` (None for a graph without unknowns).  Without the keyword nothing changes."""
+    graph's ``(Leverage, leverage_info)`` (None for a graph without unknowns).  Without the keyword nothing changes.
+    ``curvature``: a number of modes k -- every group's handle then also runs the second-order check at the refined points
+    (``hessian_spectrum_batch``'s call on the same handle, after the other analyses: the k lowest eigenpairs of E, half the
+    Hessian of the cost, at its default tolerances; ``engine="python"``: the dense path), and ``info["curvature"]`` is that
+    graph's ``(Curvature, curvature_info)`` (None for a graph without unknowns).  A member with fewer than 48 unknowns is
+    answered by the dense path; the other members of its group then run on a handle of their own.  Without the keyword nothing
+    changes."""
     from .leverage import range_leverage
     from .leverage_batch import group_leverage
     from .marginals import _select
     from .marginals_batch import marginals_follow_up
+    from .curvature_batch import _check_arguments as _check_curvature_arguments, follow_up_curvature
     from .samples_batch import _check_draw_arguments, group_samples
 
     if engine not in ("native", "python"):
@@ -295,6 +319,18 @@ def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-1
                                   [int(leverage_seed) + i for i in idx])
 
         follow_ups.append(FollowUp("leverage", leverages))
+    if curvature is not None and curvature is not False:
+        _check_curvature_arguments(curvature, 1e-9, 200, 1e-8)
+
+        def curvatures(handle, number, idx, probs, pts, costs, kept):
+            """(Curvature, info) per member at the refined points"""
+            return follow_up_curvature(handle, number, idx, probs, pts, int(curvature), lib_path, solver_settings)
+
+        def enough_unknowns(i, prob):
+            if int(curvature) > prob.n:
+                raise ValueError(f"graph {i}: k = {int(curvature)} modes of a graph with {prob.n} unknowns")
+
+        follow_ups.append(FollowUp("curvature", curvatures, enough_unknowns))
     out: list = [None] * len(datas)
 
     def member(i, data, res):
