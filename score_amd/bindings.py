@@ -1,6 +1,6 @@
 """ctypes bindings of the refinement family's headers (include/score_robust.h, score_refine_robust.h, score_refine_batch.h,
-score_refine_robust_batch.h, score_marginals.h, score_spectrum.h, score_samples.h, score_leverage.h, score_curvature.h and
-the ``*_batch.h`` analyses): their records, one ``Table`` per header -- ``{symbol: (argtypes, restype)}``, so the list of a
+score_refine_robust_batch.h, score_marginals.h, score_spectrum.h, score_samples.h, score_leverage.h, score_curvature.h, the
+``*_batch.h`` analyses and score_relative.h): their records, one ``Table`` per header -- ``{symbol: (argtypes, restype)}``, so the list of a
 header's symbols and their argument types are one text -- and the one ``bind`` that applies a table to a library.
 include/score_hip.h's own binding is ``solver.load_library``.
 """
@@ -245,6 +245,13 @@ CURVATURE_BATCH = Table("curvature_batch", _NO_EIGENSOLVER, {
 })
 # and the group forms that followed (TABLES_SINCE is pinned as well)
 TABLES_AFTER = (CURVATURE_BATCH,)
+
+RELATIVE = Table("relative", "(the CPU twin has no relative-pose covariances: engine='python' runs there)", {
+    "score_refine_relative_covariances": ([_handle, _f64p, _f64p, _i32p, _i32p, C.c_int32, C.c_double, C.c_int32, C.c_int32, _f64p,
+                                           _f64p, _f64p, _f64p, _i32p, _f64p, C.POINTER(ScoreMarginalsInfo)], C.c_int),
+})
+# and the analyses of pairs of poses (TABLES_AFTER is pinned like the others)
+TABLES_LATEST = (RELATIVE,)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

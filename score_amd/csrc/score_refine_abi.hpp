@@ -1,6 +1,6 @@
 // score_refine_abi.hpp -- the entry points of the two refinement handles (score_refine_handles.hpp): include/score_hip.h's
 // score_refine_*, and score_refine_robust.h, score_marginals.h, score_spectrum.h, score_curvature.h, score_samples.h,
-// score_leverage.h with their *_batch.h forms.  Part of score_hip.hip's translation unit, included there once after the
+// score_leverage.h with their *_batch.h forms, and score_relative.h.  Part of score_hip.hip's translation unit, included there once after the
 // handles: every entry point goes through the frame of score_abi.hpp (abi_call, require, publish_new).
 #pragma once
 
@@ -114,6 +114,15 @@ int score_refine_range_variances(score_refine* r, const double* poses, const dou
     return refine_call(r, poses, landmarks, [&] {
         return score::lv_pair_solve(*r, poses, landmarks, pair_a, pair_b, n_pairs, rel_tol, max_iters, block_width, variances, distances,
                                     residuals, iters, solutions, info);
+    });
+}
+int score_refine_relative_covariances(score_refine* r, const double* poses, const double* landmarks, const int32_t* pair_a,
+                                      const int32_t* pair_b, int32_t n_pairs, double rel_tol, int32_t max_iters, int32_t block_width,
+                                      double* rotations, double* translations, double* covariances, double* residuals, int32_t* iters,
+                                      double* solutions, score_marginals_info* info) {
+    return refine_call(r, poses, landmarks, [&] {
+        return score::rp_solve(*r, poses, landmarks, pair_a, pair_b, n_pairs, rel_tol, max_iters, block_width, rotations, translations,
+                               covariances, residuals, iters, solutions, info);
     });
 }
 int score_refine_spectrum(score_refine* r, const double* poses, const double* landmarks, int32_t k, double rel_tol, int32_t max_iters,

@@ -11,6 +11,7 @@
 #include "score_curvature.hpp"
 #include "score_samples.hpp"
 #include "score_leverage.hpp"
+#include "score_relative.hpp"
 #include "score_gn_robust.hpp"
 #include "score_gn_batch.hpp"
 #include "score_gn_robust_batch.hpp"
@@ -100,6 +101,7 @@ struct score_refine : RefineBase {
     score::CvWork cv;  // half the Hessian of the cost: product and lowest eigenpairs (score_curvature.hpp)
     score::PsWork ps;  // posterior samples (score_samples.hpp)
     score::LvWork lv;  // range leverage and predicted range variances (score_leverage.hpp)
+    score::RpWork rp;  // predicted relative poses and their covariances (score_relative.hpp)
     int64_t rb_n_lc = 0;
     const score_refine_robust_settings* rb_settings = nullptr;  // of the robust run under way
 
