@@ -1,6 +1,6 @@
 """ctypes bindings of the refinement family's headers (include/score_robust.h, score_refine_robust.h, score_refine_batch.h,
 score_refine_robust_batch.h, score_marginals.h, score_spectrum.h, score_samples.h, score_leverage.h, score_curvature.h, the
-``*_batch.h`` analyses and score_relative.h): their records, one ``Table`` per header -- ``{symbol: (argtypes, restype)}``, so the list of a
+``*_batch.h`` analyses, score_relative.h and score_relative_batch.h): their records, one ``Table`` per header -- ``{symbol: (argtypes, restype)}``, so the list of a
 header's symbols and their argument types are one text -- and the one ``bind`` that applies a table to a library.
 include/score_hip.h's own binding is ``solver.load_library``.
 """
@@ -252,6 +252,13 @@ RELATIVE = Table("relative", "(the CPU twin has no relative-pose covariances: en
 })
 # and the analyses of pairs of poses (TABLES_AFTER is pinned like the others)
 TABLES_LATEST = (RELATIVE,)
+
+RELATIVE_BATCH = Table("relative_batch", "(the CPU twin has no relative-pose covariances: engine='python' runs there)", {
+    "score_refine_batch_relative_covariances": ([_handle, _f64p, _f64p, _i32p, _i32p, _i32p, C.c_double, C.c_int32, C.c_int32, _f64p,
+                                                 _f64p, _f64p, _f64p, _i32p, C.POINTER(ScoreMarginalsBatchInfo)], C.c_int),
+})
+# and their group form (TABLES_LATEST is pinned in its turn)
+TABLES_GROUP_PAIRS = (RELATIVE_BATCH,)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

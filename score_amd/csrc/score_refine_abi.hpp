@@ -1,6 +1,6 @@
 // score_refine_abi.hpp -- the entry points of the two refinement handles (score_refine_handles.hpp): include/score_hip.h's
 // score_refine_*, and score_refine_robust.h, score_marginals.h, score_spectrum.h, score_curvature.h, score_samples.h,
-// score_leverage.h with their *_batch.h forms, and score_relative.h.  Part of score_hip.hip's translation unit, included there once after the
+// score_leverage.h with their *_batch.h forms, and score_relative.h with score_relative_batch.h.  Part of score_hip.hip's translation unit, included there once after the
 // handles: every entry point goes through the frame of score_abi.hpp (abi_call, require, publish_new).
 #pragma once
 
@@ -238,6 +238,16 @@ int score_refine_batch_range_variances(score_refine_batch* b, const double* pose
                        "score_refine_batch_range_variances: the points are missing", [&] {
         return score::gbl_pair_solve(*b, poses, landmarks, pair_ptr, pair_a, pair_b, rel_tol, max_iters, block_width, variances, distances,
                                      residuals, iters, info);
+    });
+}
+int score_refine_batch_relative_covariances(score_refine_batch* b, const double* poses, const double* landmarks, const int32_t* pair_ptr,
+                                            const int32_t* pair_a, const int32_t* pair_b, double rel_tol, int32_t max_iters,
+                                            int32_t block_width, double* rotations, double* translations, double* covariances,
+                                            double* residuals, int32_t* iters, score_marginals_batch_info* info) {
+    return refine_call(b, "score_refine_batch_relative_covariances: null handle", poses, landmarks,
+                       "score_refine_batch_relative_covariances: the points are missing", [&] {
+        return score::grp_solve(*b, poses, landmarks, pair_ptr, pair_a, pair_b, rel_tol, max_iters, block_width, rotations, translations,
+                                covariances, residuals, iters, info);
     });
 }
 int score_refine_batch_spectrum(score_refine_batch* b, const double* poses, const double* landmarks, int32_t k, double rel_tol,

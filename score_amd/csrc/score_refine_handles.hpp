@@ -19,6 +19,7 @@
 #include "score_marginals_batch.hpp"
 #include "score_samples_batch.hpp"
 #include "score_leverage_batch.hpp"
+#include "score_relative_batch.hpp"
 #include "score_spectrum_batch.hpp"
 #include "score_curvature_batch.hpp"
 
@@ -332,6 +333,7 @@ struct score_refine_batch : RefineBase {
     score::GbcWork gbc;  // half the Hessian of the members' costs: product and lowest eigenpairs (score_curvature_batch.hpp)
     score::GbsWork gbs;  // posterior samples of the members (score_samples_batch.hpp)
     score::GblWork gbl;  // range leverage and predicted range variances of the members (score_leverage_batch.hpp)
+    score::GrpWork grp;  // predicted relative poses of the members and their covariances (score_relative_batch.hpp)
     // robust refinement: the members' parameters beside the base's buffers.  U keeps rng_prec / rel_kappa / rel_tau on the host
     // for its checks.
     DevBuf<score::GbrParam> rb_params;

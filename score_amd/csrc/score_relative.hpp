@@ -11,6 +11,8 @@
 //   k_rp_rhs<DIM>     x = 0, r = b = G_c'e_q for the block's live columns, the done / iteration words as k_lv_pair_rhs sets them
 //   k_rp_dot<DIM>     one lane per live column j = c DP + q: P_c[:, q] = G_c x_j from the at most 2 DP entries of x_j at the
 //                     pair's unknowns; the lane of q == 0 also writes R_ab and t_ab
+// The two kernels' bodies are the device functions rp_rhs_entry and rp_dot_lane on a GnView: the kernels here call them for a
+// graph, score_relative_batch.hpp's for a member of a group (the convention of lv_pair_entry / lv_pair_dot_lane).
 // Columns, not pairs, fill a block: column j = c DP + q, a block is block_width CONSECUTIVE columns, so a pair may straddle
 // two blocks and every slot of a full block is live.  An output entry is formed from its own column alone, in a fixed order,
 // without atomics: two calls give the same bits.
@@ -119,11 +121,33 @@ struct RpArgs {
     double* cov; double* rot; double* trans;  // per pair: DP x DP, DIM x DIM, DIM
 };
 
-// grid (row blocks, columns): x = 0, r = b = G_c'e_q of column j0 + c (columns beyond `live`: zero, done from the start).
-// A thread whose row is none of the pair's unknowns stores zeros and never evaluates the Jacobian.
+// What one thread does for row `row` of the column of error coordinate q of the pair ia - ib of the view: the entry of
+// G'e_q there -- stated once for a graph (k_rp_rhs) and for a member of a group (k_grp_rhs, score_relative_batch.hpp).  A row
+// that is none of the pair's unknowns is zero and never evaluates the Jacobian; the entry is picked by an unrolled
+// compare-select, so G stays in registers.
+template <int DIM>
+__device__ __forceinline__ double rp_rhs_entry(const GnView& v, const int64_t ia, const int64_t ib, const int q, const long long row) {
+    constexpr int DP = DIM == 2 ? 3 : 6, NC = 2 * DP;
+    const long long fa = lv_pose_first<DIM>(ia), fb = lv_pose_first<DIM>(ib);
+    const bool at_a = fa >= 0 && row >= fa && row < fa + DP, at_b = fb >= 0 && row >= fb && row < fb + DP;
+    double g = 0.0;
+    if (at_a || at_b) {
+        double Rab[DIM * DIM], tab[DIM], G[DP * NC];
+        rp_pair_jac<DIM>(v, ia, ib, Rab, tab, G);
+        const int col = at_a ? (int)(row - fa) : DP + (int)(row - fb);
+#pragma unroll
+        for (int qq = 0; qq < DP; ++qq)
+#pragma unroll
+            for (int k = 0; k < NC; ++k)
+                if (qq == q && k == col) g = G[qq * NC + k];
+    }
+    return g;
+}
+
+// grid (row blocks, columns): x = 0, r = b = G_c'e_q of column j0 + c (columns beyond `live`: zero, done from the start)
 template <int DIM>
 __global__ __launch_bounds__(kMvThreads) void k_rp_rhs(MvArgs m, RpArgs a) {
-    constexpr int DP = DIM == 2 ? 3 : 6, NC = 2 * DP;
+    constexpr int DP = DIM == 2 ? 3 : 6;
     const int c = blockIdx.y, t = threadIdx.x;
     const long long i = (long long)blockIdx.x * kMvThreads + t;
     const bool on = c < a.live;
@@ -131,20 +155,7 @@ __global__ __launch_bounds__(kMvThreads) void k_rp_rhs(MvArgs m, RpArgs a) {
         double g = 0.0;
         if (on) {
             const long long j = a.j0 + c, p = j / DP;
-            const int q = (int)(j - p * DP);
-            const int64_t ia = a.pa[p], ib = a.pb[p];
-            const long long fa = lv_pose_first<DIM>(ia), fb = lv_pose_first<DIM>(ib);
-            const bool at_a = fa >= 0 && i >= fa && i < fa + DP, at_b = fb >= 0 && i >= fb && i < fb + DP;
-            if (at_a || at_b) {
-                double Rab[DIM * DIM], tab[DIM], G[DP * NC];
-                rp_pair_jac<DIM>(a.v, ia, ib, Rab, tab, G);
-                const int col = at_a ? (int)(i - fa) : DP + (int)(i - fb);
-#pragma unroll
-                for (int qq = 0; qq < DP; ++qq)
-#pragma unroll
-                    for (int k = 0; k < NC; ++k)
-                        if (qq == q && k == col) g = G[qq * NC + k];
-            }
+            g = rp_rhs_entry<DIM>(a.v, a.pa[p], a.pb[p], (int)(j - p * DP), i);
         }
         m.x[c * a.n + i] = 0.0;
         m.r[c * a.n + i] = g;
@@ -157,20 +168,17 @@ __global__ __launch_bounds__(kMvThreads) void k_rp_rhs(MvArgs m, RpArgs a) {
     }
 }
 
-// one lane per live column of the block: P_c[q', q] = sum_k G_c[q', k] x_j[k] over the unknowns of a, then of b, ascending
+// What one lane does for the solved column of error coordinate q of the pair ia - ib, its solution in column `slot` of x:
+// P[q' DP] = sum_k G[q', k] x[k] over the unknowns of a, then of b, ascending (P: the pair's block at its column q); the lane
+// of q == 0 also writes R_ab and t_ab (rot, trans: the pair's own) -- stated once for a graph and for a group (k_grp_dot).
 template <int DIM>
-__global__ __launch_bounds__(64) void k_rp_dot(RpArgs a) {
+__device__ __forceinline__ void rp_dot_lane(const GnView& v, const int64_t ia, const int64_t ib, const int q, const double* x,
+                                            const long long n, const int slot, double* P, double* rot, double* trans) {
     constexpr int DP = DIM == 2 ? 3 : 6, NC = 2 * DP;
-    const int c = threadIdx.x;
-    if (c >= a.live) return;
-    const long long j = a.j0 + c, p = j / DP;
-    const int q = (int)(j - p * DP);
-    const int64_t ia = a.pa[p], ib = a.pb[p];
     double Rab[DIM * DIM], tab[DIM], G[DP * NC], d[NC];
-    rp_pair_jac<DIM>(a.v, ia, ib, Rab, tab, G);
-    lv_read<DP>(a.x, a.n, c, lv_pose_first<DIM>(ia), d);
-    lv_read<DP>(a.x, a.n, c, lv_pose_first<DIM>(ib), d + DP);
-    double* P = a.cov + p * (DP * DP) + q;
+    rp_pair_jac<DIM>(v, ia, ib, Rab, tab, G);
+    lv_read<DP>(x, n, slot, lv_pose_first<DIM>(ia), d);
+    lv_read<DP>(x, n, slot, lv_pose_first<DIM>(ib), d + DP);
 #pragma unroll
     for (int qq = 0; qq < DP; ++qq) {
         double y = 0.0;
@@ -180,10 +188,21 @@ __global__ __launch_bounds__(64) void k_rp_dot(RpArgs a) {
     }
     if (q == 0) {
 #pragma unroll
-        for (int k = 0; k < DIM * DIM; ++k) a.rot[p * (DIM * DIM) + k] = Rab[k];
+        for (int k = 0; k < DIM * DIM; ++k) rot[k] = Rab[k];
 #pragma unroll
-        for (int k = 0; k < DIM; ++k) a.trans[p * DIM + k] = tab[k];
+        for (int k = 0; k < DIM; ++k) trans[k] = tab[k];
     }
+}
+
+// one lane per live column of the block
+template <int DIM>
+__global__ __launch_bounds__(64) void k_rp_dot(RpArgs a) {
+    constexpr int DP = DIM == 2 ? 3 : 6;
+    const int c = threadIdx.x;
+    if (c >= a.live) return;
+    const long long j = a.j0 + c, p = j / DP;
+    const int q = (int)(j - p * DP);
+    rp_dot_lane<DIM>(a.v, a.pa[p], a.pb[p], q, a.x, a.n, c, a.cov + p * (DP * DP) + q, a.rot + p * (DIM * DIM), a.trans + p * DIM);
 }
 
 // The buffers of the call: they stay with the refinement handle between calls, as LvWork's do (the pairs' grow on demand).

@@ -197,6 +197,15 @@ class RefineBatchHandle(_Handle):
 
         return batch_range_variances(self, points, pairs_per_member, rel_tol, max_iters, block_width)
 
+    def relative_covariances(self, points, pairs_per_member, rel_tol: float = 1e-10, max_iters: int = 4000, block_width: int = 16):
+        """``score_refine_batch_relative_covariances`` at ``points`` (include/score_relative_batch.h): the predicted relative
+        pose of every listed pair of member-local pose ids of every member and its covariance G H^-1 G'.  Returns (return
+        code, per member the dict of ``RelativeHandle.relative_covariances`` without ``solutions``, the call's info record);
+        the handle is left as it was found."""
+        from .relative_batch import batch_relative_covariances
+
+        return batch_relative_covariances(self, points, pairs_per_member, rel_tol, max_iters, block_width)
+
     def _robust(self):
         """The library with the calls of include/score_refine_robust_batch.h bound."""
         return bind(self.lib, REFINE_ROBUST_BATCH)
@@ -255,7 +264,7 @@ class RefineBatchHandle(_Handle):
 def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-10, range_weights=None, loop_closure_weights=None,
                           engine: str = "native", lib_path: Optional[str] = None, solver_settings: Optional[dict] = None,
                           max_group: int = 64, marginals=None, samples=None, samples_seed: int = 0, leverage=None,
-                          leverage_seed: int = 0, curvature=None):
+                          leverage_seed: int = 0, curvature=None, relative=None):
     """``refine_estimate`` for many graphs at once: ``datas`` and ``results`` member by member, ``range_weights`` /
     ``loop_closure_weights`` lists with one entry (an array as ``refine_estimate`` takes it, or None) per member -- they only
     scale precisions.  The members are grouped by dimension, in chunks of at most ``max_group`` (the rule of
@@ -280,7 +289,12 @@ def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-1
     Hessian of the cost, at its default tolerances; ``engine="python"``: the dense path), and ``info["curvature"]`` is that
     graph's ``(Curvature, curvature_info)`` (None for a graph without unknowns).  A member with fewer than 48 unknowns is
     answered by the dense path; the other members of its group then run on a handle of their own.  Without the keyword nothing
-    changes."""
+    changes.
+    ``relative``: a list with one entry per graph, None or a list of pose name pairs as ``predicted_relative_poses_batch`` takes
+    ``pairs`` -- every group's handle then also predicts the relative poses of the listed pairs at the refined points with
+    their covariances (``predicted_relative_poses_batch``'s call on the same handle, after the other analyses;
+    ``engine="python"``: the dense path), and ``info["relative"]`` is that graph's ``(PredictedRelativePoses, info)`` (empty
+    for a graph that lists none, None for a graph without unknowns).  Without the keyword nothing changes."""
     from .leverage import range_leverage
     from .leverage_batch import group_leverage
     from .marginals import _select
@@ -331,6 +345,22 @@ def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-1
                 raise ValueError(f"graph {i}: k = {int(curvature)} modes of a graph with {prob.n} unknowns")
 
         follow_ups.append(FollowUp("curvature", curvatures, enough_unknowns))
+    if relative is not None and relative is not False:
+        from .relative import _pose_pair_ids, predicted_relative_poses
+        from .relative_batch import _empty, group_relative
+
+        pair_names = [[tuple(p) for p in nm] if nm is not None else [] for nm in per_graph(relative, len(datas), "relative", none=False)]
+
+        def relatives(handle, number, idx, probs, pts, costs, kept):
+            """(PredictedRelativePoses, info) per member at the refined points"""
+            if handle is None:
+                return [predicted_relative_poses(datas[i], _as_results(p, pt, results[i], f), pair_names[i], rws[i], lws[i], engine="python")
+                        if pair_names[i] else _empty(datas[i].dimension, 3 if datas[i].dimension == 2 else 6, "python")
+                        for p, pt, i, f in zip(probs, pts, idx, costs)]
+            return group_relative(handle, pts, [pair_names[i] for i in idx], kept, idx, number)
+
+        follow_ups.append(FollowUp("relative", relatives,
+                                   lambda i, prob: _pose_pair_ids(prob, pair_names[i], f"refine_estimate_batch: graph {i}")))
     out: list = [None] * len(datas)
 
     def member(i, data, res):
