@@ -19,7 +19,11 @@ The second half of the file runs the loop as the benchmark drives it (penalty_up
 replay_and_single_steps: 16-iteration blocks replayed from a captured graph, a penalty update at every check, a PCG count that
 changes between blocks) and models one iteration in np.longdouble (iteration_model: the right-hand side, the relaxation, the
 cone projections and the dual update, with forward-error bounds counted operation by operation).  K and T are built at each
-problem's own penalty, read back from the handle (score_debug_get "rho")."""
+problem's own penalty, read back from the handle (score_debug_get "rho").
+
+LINK_GRAPHS / LINK_PLANS put the loop-closure link plan (score_link.hpp) at its caps and one step beyond each; a view then takes
+"the pairs expected inside the preconditioner" (case_inside): every loop closure of the graph, or none beyond a cap, where T
+is the chain part alone (test_link_caps_gpu.py, test_link_caps_host.py)."""
 import functools
 
 import numpy as np
@@ -27,6 +31,7 @@ import scipy.linalg as sla
 import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
+from score_amd import compat
 from score_amd.assemble import assemble
 from score_amd.manhattan import make_manhattan, make_manhattan_3d
 from score_amd.solver import ConicSolver
@@ -58,9 +63,73 @@ GRAPHS = {
     "S150": lambda: make_manhattan(n_robots=1, n_poses=150, n_beacons=2, seed=2, p_range=0.6),
     "H": lambda: make_manhattan(n_robots=2, n_poses=1100, n_beacons=3, seed=21, n_loop_closures=3),
 }
-# a case: the graphs of one handle (G: a lock-step batch whose tiles straddle problems)
-CASE_GRAPHS = {k: (k,) for k in GRAPHS if k != "S150"}
+
+
+def lc(fg, rng, a, i, b, j):
+    """A loop closure from pose i of robot a to pose j of robot b, as test_loop_closure_edge_cases_in_the_link_correction
+    builds it: the true relative pose plus noise of 0.01 / 0.01 / 0.002 (2-D: x, y, theta; 3-D: 0.01 on the translation, the
+    true rotation) from `rng`, kappa = 1e4, tau = 2.5e5."""
+    A, B = fg.pose_variables[a][i], fg.pose_variables[b][j]
+    rel = np.linalg.inv(A.transformation_matrix) @ B.transformation_matrix
+    if fg.dimension == 3:
+        return compat.PoseMeasurement3D(A.name, B.name, rel[:3, 3] + 0.01 * rng.standard_normal(3), rel[:3, :3].copy(), 1e4, 2.5e5)
+    return compat.PoseMeasurement2D(A.name, B.name, float(rel[0, 2] + 0.01 * rng.standard_normal()), float(rel[1, 2] + 0.01 * rng.standard_normal()),
+                                    float(np.arctan2(rel[1, 0], rel[0, 0]) + 0.002 * rng.standard_normal()), 1e4, 2.5e5)
+
+
+def with_loop_closures(fg, ends):
+    """`fg` with the loop closures lc(a, i, b, j) of `ends`, the noise drawn in list order from np.random.default_rng(5)."""
+    rng = np.random.default_rng(5)
+    fg.loop_closure_measurements = [lc(fg, rng, *e) for e in ends]
+    return fg
+
+
+# The link plan at its caps (score_link.hpp: 96 unknowns in a group, 48 rounds on a chain, 256 linked nodes in a problem), one
+# step beyond each of them (the all-or-nothing fallbacks of make_link_plan: L97, R3over, N260) and the kernel variants below
+# the caps that the generators' own loop closures never reach: LINK_PLANS lists what each graph must give.
+_PAIRED = lambda n_pairs, per_pair: [(2 * pr, 2 + 2 * k, 2 * pr + 1, 33 - 2 * k) for pr in range(n_pairs) for k in range(per_pair)]
+_RING = [e for k in range(6) for e in ((0, 2 + 2 * k, 1, 3 + 2 * k), (1, 20 + 2 * k, 2, 3 + 2 * k), (2, 20 + 2 * k, 0, 21 + 2 * k))]
+LINK_GRAPHS = {
+    "L96": lambda: with_loop_closures(make_manhattan(n_robots=2, n_poses=40, n_beacons=3, seed=77, p_range=0.3), [(0, 2 + 2 * k, 1, 37 - 2 * k) for k in range(16)]),
+    "L97": lambda: with_loop_closures(make_manhattan(n_robots=2, n_poses=40, n_beacons=3, seed=77, p_range=0.3), [(0, 2 + 2 * k, 1, 37 - 2 * k) for k in range(17)]),
+    "HUB15": lambda: with_loop_closures(make_manhattan(n_robots=1, n_poses=60, n_beacons=3, seed=80, p_range=0.4), [(0, 5, 0, 12 + 3 * k) for k in range(15)]),
+    "HUB10": lambda: with_loop_closures(make_manhattan(n_robots=1, n_poses=60, n_beacons=3, seed=78, p_range=0.4), [(0, 5, 0, 12 + 3 * k) for k in range(10)]),
+    "HUB93": lambda: with_loop_closures(make_manhattan(n_robots=3, n_poses=40, n_beacons=3, seed=82, p_range=0.3),
+                                        [(0, 5, 1, 3 + 3 * k) for k in range(10)] + [(0, 8 + 3 * k, 2, 37 - 3 * k) for k in range(10)]),
+    "R3": lambda: with_loop_closures(make_manhattan(n_robots=3, n_poses=40, n_beacons=3, seed=79, p_range=0.3), _RING[:15]),
+    "R3over": lambda: with_loop_closures(make_manhattan(n_robots=3, n_poses=40, n_beacons=3, seed=79, p_range=0.3), _RING[:17]),
+    "E96": lambda: with_loop_closures(make_manhattan_3d(n_robots=2, n_poses=40, n_beacons=3, seed=32, p_range=0.3), [(0, 2 + 3 * k, 1, 37 - 3 * k) for k in range(12)]),
+    "N256": lambda: with_loop_closures(make_manhattan(n_robots=8, n_poses=36, n_beacons=3, seed=80, p_range=0.2), _PAIRED(4, 16)),
+    "N260": lambda: with_loop_closures(make_manhattan(n_robots=10, n_poses=36, n_beacons=3, seed=80, p_range=0.2), _PAIRED(4, 16) + [(8, 10, 9, 20)]),
+    "LS96": lambda: with_loop_closures(make_manhattan(n_robots=2, n_poses=1100, n_beacons=3, seed=21), [(0, 30 + 64 * k, 1, 1070 - 64 * k) for k in range(16)]),
+}
+GRAPHS.update(LINK_GRAPHS)
+# the twin's "links" read-out: [pairs, inside the preconditioner, unknowns, chains, rounds, singular, groups, largest group, most
+# chains of a group] (the HIP handle reports the first six)
+LINK_PLANS = {
+    "L96": [32, 32, 192, 4, 48, 0, 2, 96, 2],      # a group at the cap of 96 unknowns, 48 rounds on each of its two chains
+    "L97": [34, 0, 0, 0, 0, 0, 0, 0, 0],           # 51 rounds on a chain: the chain preconditioner alone
+    "HUB15": [30, 30, 96, 2, 48, 0, 2, 48, 1],     # one pose with 15 partners: rows of G with 45 nonzeros, 48 rounds on ONE chain
+    "HUB93": [40, 40, 186, 6, 33, 0, 2, 93, 3],    # a hub between robots: 93 unknowns, three chains to a group
+    "R3": [30, 30, 180, 6, 30, 0, 2, 90, 3],       # a ring of three robots: 90 unknowns, three chains to a group
+    "R3over": [34, 0, 0, 0, 0, 0, 0, 0, 0],        # a group of 102 unknowns (36 rounds a chain are fine): none
+    "E96": [36, 36, 288, 6, 48, 0, 3, 96, 2],      # 3-D: blocks of 4, three groups of 96
+    "N256": [128, 128, 768, 16, 48, 0, 8, 96, 2],  # exactly 256 linked nodes: eight groups of 96
+    "N260": [130, 0, 0, 0, 0, 0, 0, 0, 0],         # 258 linked nodes: none
+    "LS96": [32, 32, 192, 4, 48, 0, 2, 96, 2],     # L96 on chains cut into segments: items per segment, the join level
+    "HUB10": [20, 20, 66, 2, 33, 0, 2, 33, 1],
+}
+# The HIP backend cuts a chain beyond 1023 poses into segments (score_join.hpp) and lists an affected chain per segment (a
+# LinkItem each); the twin solves whole chains.  LS96: 2 robots x 2 matrix rows x 2 segments -- the one figure of the six in
+# which the two handles differ.
+LINK_CHAINS_ON_DEVICE = {"LS96": 8}
+LINK_FALLBACKS = ("L97", "R3over", "N260")  # no pair inside the preconditioner: T is the chain part alone
+LINK_CASES = ["L96", "L97", "HUB15", "HUB93", "R3", "R3over", "E96", "N256", "N260", "LS96", "GL"]
+
+# a case: the graphs of one handle (G, GL: a lock-step batch whose tiles straddle problems)
+CASE_GRAPHS = {k: (k,) for k in GRAPHS if k not in ("S150", "HUB10")}
 CASE_GRAPHS["G"] = ("A", "B", "S150")
+CASE_GRAPHS["GL"] = ("L96", "A", "HUB10")  # groups of 96, none and 33 unknowns in one launch
 
 
 @functools.lru_cache(maxsize=None)
@@ -72,6 +141,26 @@ def model_of(name):
 
 def case_models(case):
     return [model_of(g) for g in CASE_GRAPHS[case]]
+
+
+def case_inside(case):
+    """Per graph of a case, the pairs expected inside the preconditioner: None = every loop closure of the graph
+    (loop_closure_pairs), [] for the graphs beyond a cap of the link plan."""
+    return [[] if g in LINK_FALLBACKS else None for g in CASE_GRAPHS[case]]
+
+
+def case_link_plan(case):
+    """The twin's "links" read-out a case must give: the members' figures added up, rounds / largest group / most chains of a
+    group the largest of them."""
+    plans = np.array([LINK_PLANS.get(g, [0] * 9) for g in CASE_GRAPHS[case]])
+    return [int(plans[:, k].max() if k in (4, 7, 8) else plans[:, k].sum()) for k in range(9)]
+
+
+def device_link_plan(case):
+    """The six "links" figures the HIP handle of a case must report: the twin's first six, the chains counted per segment."""
+    plan = case_link_plan(case)[:6]
+    plan[3] += sum(LINK_CHAINS_ON_DEVICE[g] - LINK_PLANS[g][3] for g in CASE_GRAPHS[case] if g in LINK_CHAINS_ON_DEVICE)
+    return plan
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -263,6 +352,15 @@ def eta_bound(T, qp, on, rhs, float_factors):
     return (4.0 * eta_m if float_factors else 4.0 * max(eta_m, 4 * EPS)), eta_m
 
 
+def link_cap_bound(eta_model, eta_twin, float_factors):
+    """The bound of I3 and I4 for the DEVICE on the cases of LINK_CASES: 4 * max(eta of the model, eta of the twin), plus the 4 eps
+    floor with double factors.  The model is SuperLU on the assembled matrix and never forms y - Z t; the twin does form it (a
+    host restatement of the same Woodbury correction on the same plan), so with a link plan at its caps -- a pose with 15
+    partners, 96 unknowns on top of the join level -- the twin's own figure is the yardstick of that cancellation, as it is of
+    the carried product in I2.  The twin itself stays under eta_bound."""
+    return 4.0 * max(eta_model, eta_twin, 0.0 if float_factors else 4 * EPS)
+
+
 def jacobi_ok(M, on, z, rhs):
     """Off the chains the preconditioner is Jacobi: z = rhs / diag(M) to 4 eps."""
     off = ~on
@@ -275,7 +373,7 @@ def jacobi_ok(M, on, z, rhs):
 class ProblemView:
     """One problem of a handle: its slice of the handle's vectors and its references."""
 
-    def __init__(self, fg, mdl, xoff, roff, D, E, link_pairs, rho=RHO, sigma=SIGMA):
+    def __init__(self, fg, mdl, xoff, roff, D, E, link_pairs, rho=RHO, sigma=SIGMA, inside=None):
         qp = mdl.qp
         self.fg, self.mdl, self.qp, self.x0, self.x1 = fg, mdl, qp, xoff, xoff + qp.n
         self.r0, self.r1, self.rho, self.sigma = roff, roff + qp.m, float(rho), float(sigma)
@@ -287,7 +385,7 @@ class ProblemView:
             self.expected_pairs = []
         else:
             self.chain, self.node = chain_nodes_of_problem(qp)
-            self.expected_pairs = loop_closure_pairs(fg, mdl)
+            self.expected_pairs = loop_closure_pairs(fg, mdl) if inside is None else list(inside)
         self.T, self.on = preconditioned_matrix(self.K, self.chain, self.node, int(qp.block_size), self.expected_pairs)
 
     def cut(self, v):
@@ -297,29 +395,38 @@ class ProblemView:
         return np.asarray(v)[self.r0 : self.r1]
 
 
-def problem_views(sol, models, rho=None):
+def problem_views(sol, models, rho=None, inside=None):
     """The views of every problem of a handle created from `models` (list of (graph, model)); `rho`: the penalty of every
-    problem (default: RHO for all of them)."""
+    problem (default: RHO for all of them); `inside`: per problem, the pairs expected inside the preconditioner (case_inside;
+    default: every loop closure of the graph)."""
     D, E = sol.debug_get("D"), sol.debug_get("E")
     lp = sol.debug_get("link_pairs").astype(np.int64).reshape(-1, 2)
     pairs = sorted((int(min(a, b)), int(max(a, b))) for a, b in lp)
     out, xo, ro = [], 0, 0
     for k, (fg, mdl) in enumerate(models):
-        out.append(ProblemView(fg, mdl, xo, ro, D, E, pairs, rho=RHO if rho is None else float(rho[k])))
+        out.append(ProblemView(fg, mdl, xo, ro, D, E, pairs, rho=RHO if rho is None else float(rho[k]), inside=None if inside is None else inside[k]))
         xo += mdl.qp.n
         ro += mdl.qp.m
     return out
 
 
-def admm_snapshots(models, settings, lib_path, counters=None):
+def links_of(sol):
+    """The handle's "links" read-out as integers (six figures from the HIP library, nine from the twin)."""
+    return [int(v) for v in sol.debug_get("links")]
+
+
+def admm_snapshots(models, settings, lib_path, counters=None, inside=None):
     """reset(), then steps(check_interval) twice with the fixed settings (5 iterations each unless `settings` says otherwise;
     16 or more are replayed from a captured graph when use_graph = 1): both end in a measured iteration (the last launch
     applies the preconditioner to the final residual, so z = M^-1 r for the r read back).  Returns (views, [vectors after
-    the first block, after the second]); `counters`, when given, receives the handle's "graph_launches"."""
+    the first block, after the second]); `counters`, when given, receives the handle's "graph_launches", its "links" before the first
+    and after the last iteration and its "link_pairs"."""
     st = dict(ADMM_SETTINGS, **settings)
     sol = ConicSolver([m.qp for _, m in models], st, lib_path=lib_path)
     try:
-        views = problem_views(sol, models)
+        views = problem_views(sol, models, inside=inside)
+        if counters is not None:
+            counters["links"], counters["link_pairs"] = links_of(sol), sol.debug_get("link_pairs")
         sol.reset()
         snaps = []
         for _ in range(2):
@@ -327,6 +434,7 @@ def admm_snapshots(models, settings, lib_path, counters=None):
             snaps.append({v: sol.debug_get(v) for v in ADMM_VECS})
         if counters is not None:
             counters["graph_launches"] = int(sol.debug_get("graph_launches")[0])
+            counters["links_after"] = links_of(sol)
     finally:
         sol.close()
     return views, snaps
@@ -341,9 +449,10 @@ def admm_figures(view, vec, cg_iters, float_factors):
                 i3_bound=bound, i3_model=eta_m, jacobi=jacobi_ok(view.K, view.on, z, r), pairs_ok=view.pairs == view.expected_pairs)
 
 
-def newton_snapshot(model, settings, lib_path=None):
+def newton_snapshot(model, settings, lib_path=None, counters=None):
     """I4: 15 ADMM iterations, then the Newton set assembled and factored at that iterate (what the first Newton iteration
-    does) and z = M^-1 (-g) from PREC_INIT on it.  Returns (H as the device assembled it, g, z, link pairs of the handle)."""
+    does) and z = M^-1 (-g) from PREC_INIT on it.  Returns (H as the device assembled it, g, z, link pairs of the handle);
+    `counters`, when given, receives the handle's "links" read after it."""
     qp = model.qp
     sol = ConicSolver(qp, settings, lib_path=lib_path)
     try:
@@ -354,19 +463,56 @@ def newton_snapshot(model, settings, lib_path=None):
         H = sp.csr_matrix((sol.debug_get("Hval"), sol.debug_get("Hcol").astype(np.int64), sol.debug_get("Hptr").astype(np.int64)), shape=(n, n))
         g, z = sol.debug_get("polish_g"), sol.debug_get("polish_prec_of_negg")
         lp = sol.debug_get("link_pairs").astype(np.int64).reshape(-1, 2)
+        if counters is not None:
+            counters["links"] = links_of(sol)  # (after the Newton set's first refresh: both sets' singular systems counted)
     finally:
         sol.close()
     return H, g, z, sorted((int(min(a, b)), int(max(a, b))) for a, b in lp)
 
 
-def newton_figures(fg, model, H, g, z, pairs, float_factors):
-    """The figures of I4 for one problem: T_H z = -g on the chain columns, Jacobi elsewhere."""
+def newton_figures(fg, model, H, g, z, pairs, float_factors, inside=None):
+    """The figures of I4 for one problem: T_H z = -g on the chain columns, Jacobi elsewhere; `inside`: the pairs expected inside
+    the preconditioner (default: every loop closure of the graph)."""
     qp = model.qp
     chain, node = chain_nodes_of_problem(qp)
-    expected = loop_closure_pairs(fg, model)
+    expected = loop_closure_pairs(fg, model) if inside is None else list(inside)
     T, on = preconditioned_matrix(H, chain, node, int(qp.block_size), expected)
     bound, eta_m = eta_bound(T, qp, on, -g, float_factors)
     return dict(i4=eta_figure(T, on, z, -g), i4_bound=bound, i4_model=eta_m, jacobi=jacobi_ok(H, on, z, -g), pairs_ok=pairs == expected)
+
+
+def newton_twin_figures(fg, model, H, g, float_factors, twin_lib, inside=None):
+    """The twin as second yardstick of I4.  The twin has no Newton polish, but its linear mode (score_linear_create /
+    score_linear_solve: the host restatement of chain factors, float rounding, link plan and Woodbury correction) takes any
+    SPD matrix on a chain hint: handed the H the device assembled and the problem's chains, it factors H along them, finds the
+    link pairs in H's pattern and applies M^-1.  A linear solve takes at least one PCG step, so the pair read back is
+    (r, z = M^-1 r) with r the residual after one step from -g -- another vector of the same Krylov sequence, the same T_H, the
+    same factors and the same capacitance systems.  Returns the figures of newton_figures for it (against the model on ITS
+    r), its "links" and whether its pairs are the expected ones."""
+    from score_amd.solver import _f64p, _ptr, LinearSolver
+
+    qp = model.qp
+    bs = int(qp.block_size)
+    Hs = sp.csr_matrix(H, copy=True)
+    Hs.sum_duplicates()
+    Hs.sort_indices()
+    ls = LinearSolver(Hs, qp.chain_ptr, np.asarray(qp.node_cols)[::bs], bs, dict(fac_fp32=1 if float_factors else 0), lib_path=twin_lib)
+
+    def read(name):
+        size = ls.lib.score_debug_get(ls._h, name.encode(), None, 0)
+        out = np.empty(size)
+        ls.lib.score_debug_get(ls._h, name.encode(), _ptr(out, _f64p), size)
+        return out
+
+    try:
+        ls.solve(Hs.data, -np.asarray(g), rel_tol=1e-30, max_iters=1)
+        r, z, links = read("r"), read("z"), [int(v) for v in read("links")]
+        lp = read("link_pairs").astype(np.int64).reshape(-1, 2)
+    finally:
+        ls.close()
+    pairs = sorted((int(min(a, b)), int(max(a, b))) for a, b in lp)
+    f = newton_figures(fg, model, H, -r, z, pairs, float_factors, inside=inside)
+    return dict(f, links=links, r_max=float(np.abs(r).max()))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -537,7 +683,7 @@ def fresh_product_figures(K, xt, kx):
     return (float((err[live] / bound[live]).max()) if live.any() else 0.0), bool(np.all(err[~live] == 0))
 
 
-def penalty_update_run(models, settings, lib_path, iteration_after=False, through_reset=True):
+def penalty_update_run(models, settings, lib_path, iteration_after=False, through_reset=True, inside=None):
     """The sequence of part 2 on one handle: solve() with RHO_SETTINGS (three blocks of 16 iterations, a penalty update after
     each, none latched), the read-outs of step a, steps(16) (step b: one replay under the new penalties), optionally one
     more iteration for the long-double model (iteration_capture), and -- unless through_reset is off -- reset() and
@@ -550,7 +696,8 @@ def penalty_update_run(models, settings, lib_path, iteration_after=False, throug
         out["rho"] = sol.debug_get("rho")
         out["a"] = {k: sol.debug_get(k) for k in ("Kval", "Kptr", "Kcol", "u", "y", "s", "xt", "kx")}
         out["rep"] = int(sol.debug_get("rep")[0])
-        out["views"] = problem_views(sol, models, rho=out["rho"])
+        out["views"] = problem_views(sol, models, rho=out["rho"], inside=inside)
+        out["links"] = links_of(sol)
         sol.steps(BLOCK)
         out["b"] = {v: sol.debug_get(v) for v in ADMM_VECS}
         if iteration_after:
@@ -559,7 +706,7 @@ def penalty_update_run(models, settings, lib_path, iteration_after=False, throug
             return out
         sol.reset()
         out["rho_reset"] = sol.debug_get("rho")
-        out["views_reset"] = problem_views(sol, models)
+        out["views_reset"] = problem_views(sol, models, inside=inside)
         out["c"] = []
         for _ in range(2):
             sol.steps(BLOCK)
@@ -775,21 +922,25 @@ def replay_and_single_steps(models, settings, lib_path):
 # ---------------------------------------------------------------------------------------------------------------------
 # the checks the GPU tests and the twin's tests share
 # ---------------------------------------------------------------------------------------------------------------------
-def identity_checks(view, vec, cg_iters, float_factors, label, yard=None):
+def identity_checks(view, vec, cg_iters, float_factors, label, yard=None, link_caps=False):
     """I1-I3 of one problem and one snapshot as {name: passed} and the OPID line; `yard`: (view, vectors) of the twin's run of
-    the same sequence, the yardstick of I2 (None: the floor of the bound alone, what the twin itself is held to)."""
+    the same sequence, the yardstick of I2 (None: the floor of the bound alone, what the twin itself is held to); `link_caps`:
+    I3 under link_cap_bound, with the twin's figure of `yard` beside the model's."""
     f = admm_figures(view, vec, cg_iters, float_factors)
     e_yard = 0.0 if yard is None else i2_figure(yard[0].K, yard[0].cut(yard[1]["xt"]), yard[0].cut(yard[1]["kx"]))
     b2 = i2_bound(view.K, e_yard)
+    b3 = f["i3_bound"]
+    if link_caps and yard is not None:
+        b3 = link_cap_bound(f["i3_model"], eta_figure(yard[0].T, yard[0].on, yard[0].cut(yard[1]["z"]), yard[0].cut(yard[1]["r"])), float_factors)
     line = (f"OPID {label} n={view.qp.n} rho={view.rho:.6g} | I1 {f['i1']:.4f} | I2 {f['i2']:.3e} bound {b2:.3e} | "
-            f"I3 {f['i3']:.3e} bound {f['i3_bound']:.3e}")
+            f"I3 {f['i3']:.3e} bound {b3:.3e}")
     return {"link pairs": f["pairs_ok"], "I1": f["i1"] <= 1.0 and f["i1_exact"], "I2": f["i2"] <= b2,
-            "I3": f["i3"] <= f["i3_bound"], "I3 Jacobi": f["jacobi"]}, line
+            "I3": f["i3"] <= b3, "I3 Jacobi": f["jacobi"]}, line
 
 
-def penalty_update_checks(run, float_factors, label, yard=None, expect_launches=None):
+def penalty_update_checks(run, float_factors, label, yard=None, expect_launches=None, link_caps=False):
     """Every assertion of part 2 on the result of penalty_update_run, as (failures, OPID lines); `yard`: the twin's run
-    (I2's yardstick in steps b and c)."""
+    (I2's yardstick in steps b and c; with `link_caps` the second yardstick of I3 as well: identity_checks)."""
     st, views, rho = run["settings"], run["views"], run["rho"]
     cg, fails, lines = st["cg_iters"], [], []
 
@@ -812,12 +963,12 @@ def penalty_update_checks(run, float_factors, label, yard=None, expect_launches=
         note(lab + " a", {"Kval": kv["ratio"] <= 1.0 and kv["exact"], "Kval pattern": kv["complete"], "u": uf[0] <= 1.0 and uf[1],
                           "kx": kf[0] <= 1.0 and kf[1]})
         yb = None if yard is None else (yard["views"][k], yard["b"])
-        checks, line = identity_checks(v, run["b"], cg, float_factors, lab + " b", yb)
+        checks, line = identity_checks(v, run["b"], cg, float_factors, lab + " b", yb, link_caps)
         lines.append(line)
         note(lab + " b", checks)
         for s, vec in enumerate(run["c"]):
             yc = None if yard is None else (yard["views_reset"][k], yard["c"][s])
-            checks, line = identity_checks(run["views_reset"][k], vec, cg, float_factors, f"{lab} c{s + 1}", yc)
+            checks, line = identity_checks(run["views_reset"][k], vec, cg, float_factors, f"{lab} c{s + 1}", yc, link_caps)
             lines.append(line)
             note(f"{lab} c{s + 1}", checks)
     return fails, lines
