@@ -22,6 +22,7 @@ import pytest
 import scipy.linalg as sla
 
 import curvature_helpers as ch
+import ritz_pencils as rp
 from conftest import ROOT
 from curvature_helpers import EPS, MAX_ITERS, REL_TOL, SHIFT, CurvatureReference, check_pairs
 from refine_batch_helpers import group, member, rough_start, twin_alone
@@ -31,7 +32,7 @@ from score_amd.curvature_batch import CURVATURE_BATCH_SYMBOLS, _bind, _curvature
 from score_amd.marginals import _problem_and_point
 from score_amd.refine import refine_estimate
 from score_amd.refine_batch import RefineBatchHandle, _problem_of, refine_estimate_batch
-from score_amd.spectrum_batch import RITZ_BREAKDOWN, RITZ_OK, device_ritz
+from score_amd.spectrum_batch import RITZ_BREAKDOWN, RITZ_NO_P, RITZ_OK, device_ritz
 from test_curvature_gpu import _block_of_vectors
 from test_spectrum_batch_gpu import _deflated
 
@@ -395,6 +396,40 @@ def test_device_rayleigh_ritz_with_the_indefinite_rule(hip_lib):
     ortho = float(np.max(np.abs(coef[4].T @ Bsym @ coef[4] - np.eye(nb))))
     print("negated pencil: |C'BC - I| / bound:", ortho / (48 * EPS * np.linalg.cond(G) * 48))
     assert ortho <= 48 * EPS * np.linalg.cond(G) * 48
+
+
+@functools.lru_cache(maxsize=None)
+def _family_in_one_launch(hip_lib):
+    return rp.judge_launch(lambda GA, GB: indefinite_ritz(GA, GB, hip_lib), True)
+
+
+def test_device_rayleigh_ritz_on_the_family_with_the_indefinite_rule(hip_lib):
+    """score_curvature_ritz on the family of tests/ritz_pencils.py in ONE launch, under the assertions the host routine passes
+    with ``indefinite`` in test_spectrum_host.py::test_rayleigh_ritz_under_sanitizers.  The rule is read by one sign test: the
+    pencils without a negative value give the bits score_spectrum_ritz gives (a retry for a non-finite P block included), and
+    the two pencils the definite rule answers without P keep P here -- 16 negative values (negP), 3 among positive ones
+    (shift3).  profiles/ritz_pencils.md holds the measured ratios."""
+    per = _family_in_one_launch(hip_lib)
+    labels = [p.label for p in rp.family()]
+    by = dict(zip(labels, per))
+    assert [by[label][2:] for label in ("nanP", "infP", "negP", "shift3", "negated")] == [(RITZ_NO_P, 32)] * 2 + [(RITZ_OK, 48)] * 3
+    assert [int(np.sum(by[label][0] < 0.0)) for label in ("negP", "shift3", "negated")] == [16, 3, 16]
+    assert by["rank15"][2:] == (RITZ_BREAKDOWN, 15) and by["few"][2:] == (RITZ_BREAKDOWN, 0)
+    theta, coef, status, kept = device_ritz(*rp.stacked(rp.family()), hip_lib)
+    positive = rp.positive_labels()
+    assert len(positive) == len(labels) - 3
+    for label in positive:
+        i = labels.index(label)
+        assert rp.same_bits((theta[i], coef[i], status[i], kept[i]), by[label]), f"{label}: the rules give different bits"
+    for label in ("negP", "shift3"):  # the definite rule dropped P
+        i = labels.index(label)
+        assert (status[i], kept[i]) == (RITZ_NO_P, 32) and not coef[i][32:].any() and by[label][1][32:].any()
+
+
+def test_device_rayleigh_ritz_with_the_indefinite_rule_whatever_the_launch(hip_lib):
+    """A pencil's bits under the indefinite rule are those of the one launch of the family: in the family reversed, alone in a
+    launch, and among 600 pencils (two resident workgroups of the kernel on every CU)."""
+    rp.judge_launch_shapes(lambda GA, GB: indefinite_ritz(GA, GB, hip_lib), _family_in_one_launch(hip_lib))
 
 
 def test_through_the_modules(hip_lib):

@@ -18,13 +18,15 @@ import numpy as np
 import pytest
 import scipy.linalg as sla
 
+import ritz_pencils as rp
 from conftest import ROOT
 from refine_batch_helpers import group, member, rough_start, twin_alone
+from ritz_pencils import _deflated
 from spectrum_helpers import EPS, MAX_ITERS, REL_TOL, SHIFT, SpectrumReference, check_modes, reference
 from score_amd.marginals import _problem_and_point
 from score_amd.refine_batch import RefineBatchHandle, _problem_of
 from score_amd.spectrum import covariance_bracket
-from score_amd.spectrum_batch import (RITZ_BREAKDOWN, RITZ_OK, SPECTRUM_BATCH_SYMBOLS, _bind, device_ritz,
+from score_amd.spectrum_batch import (RITZ_BREAKDOWN, RITZ_NO_P, RITZ_OK, SPECTRUM_BATCH_SYMBOLS, _bind, device_ritz,
                                       information_spectrum_batch)
 
 pytestmark = pytest.mark.gpu
@@ -239,18 +241,6 @@ def test_errors_are_reported_not_faults(hip_lib):
         check_modes(ref, 4, modes.values, modes.vectors, REL_TOL, f"{key} of A..E")
 
 
-def _deflated(A, B, drop):
-    """tests/test_spectrum_host.py's: the pencil restricted as score_spectrum_rr.hpp does it."""
-    A, B = 0.5 * (A + A.T), 0.5 * (B + B.T)
-    use = np.nonzero(np.diag(B) > 0)[0]
-    d = 1.0 / np.sqrt(np.diag(B)[use])
-    As, Bs = A[np.ix_(use, use)] * np.outer(d, d), B[np.ix_(use, use)] * np.outer(d, d)
-    lam, Q = np.linalg.eigh(Bs)
-    keep = lam > drop * lam[-1]
-    Y = Q[:, keep]
-    return Y.T @ As @ Y, Y.T @ Bs @ Y, int(keep.sum())
-
-
 def test_device_rayleigh_ritz_alone(hip_lib):
     """score_spectrum_ritz on the three pencils of test_spectrum_host.py::test_rayleigh_ritz_under_sanitizers (full rank; S'S of
     rank 40; an empty P), one with a NaN entry and one with S'AS negated, in ONE launch; theta against scipy.linalg.eigh of the
@@ -294,6 +284,32 @@ def test_device_rayleigh_ritz_alone(hip_lib):
     again = device_ritz(np.array([p[0] for p in good]), np.array([p[1] for p in good]), hip_lib)
     np.testing.assert_array_equal(again[0], theta3)
     np.testing.assert_array_equal(again[1], coef3)
+
+
+@functools.lru_cache(maxsize=None)
+def _family_in_one_launch(hip_lib):
+    return rp.judge_launch(lambda GA, GB: device_ritz(GA, GB, hip_lib), False)
+
+
+def test_device_rayleigh_ritz_on_the_family(hip_lib):
+    """score_spectrum_ritz on the family of tests/ritz_pencils.py in ONE launch, under the assertions the host routine passes in
+    test_spectrum_host.py::test_rayleigh_ritz_under_sanitizers: status and kept as stated there (odd first and second
+    decompositions, kept == nb, kept < nb, ma < nb, scattered index maps, excluded diagonals, ties, exact zeros, graded, tiny
+    and huge scales), the three bounds, theta as the Rayleigh quotient of its vector, zero rows of the directions not in use,
+    the wrapper's NaN where the step broke down, and
+    the retry: a pencil whose P block is non-finite or negative ends without P, with the bits of the pencil whose P rows and
+    columns are zero.  profiles/ritz_pencils.md holds the measured ratios."""
+    per = _family_in_one_launch(hip_lib)
+    by = dict(zip([p.label for p in rp.family()], per))
+    assert [by[label][2:] for label in ("nanP", "infP", "negP", "shift3")] == [(RITZ_NO_P, 32)] * 4
+    assert [by[label][2:] for label in ("rank16", "rank15", "few", "negated")] == [(RITZ_OK, 16), (RITZ_BREAKDOWN, 15), (RITZ_BREAKDOWN, 0),
+                                                                                   (RITZ_BREAKDOWN, 32)]
+
+
+def test_device_rayleigh_ritz_whatever_the_launch(hip_lib):
+    """A pencil's bits are those of the one launch of the family: in the family reversed, alone in a launch, and among 600
+    pencils (two resident workgroups of the kernel on every CU)."""
+    rp.judge_launch_shapes(lambda GA, GB: device_ritz(GA, GB, hip_lib), _family_in_one_launch(hip_lib))
 
 
 def test_contract(hip_lib):

@@ -1,7 +1,8 @@
 // spectrum_rr_check.cpp -- score_spectrum_rr.hpp on pencils from a file, stand-alone (tests/test_spectrum_host.py builds it
 // with the host sanitizers and runs it as a child process; it is never loaded into Python and needs no GPU).
 //
-//   spectrum_rr_check IN OUT
+//   spectrum_rr_check IN OUT [indefinite]
+// A third argument, whatever it says, selects the indefinite rule (score_curvature.hpp): the lowest value may be negative.
 // IN : count, then per pencil "m nb" and the 2 m m entries of S'AS and S'S (row-major, %.17g).
 // OUT: per pencil "status kept", nb Ritz values, m nb coefficients (row-major).
 #include <cstdio>
@@ -11,7 +12,8 @@
 #include "score_spectrum_rr.hpp"
 
 int main(int argc, char** argv) {
-    if (argc != 3) { std::fprintf(stderr, "usage: %s IN OUT\n", argv[0]); return 2; }
+    if (argc != 3 && argc != 4) { std::fprintf(stderr, "usage: %s IN OUT [indefinite]\n", argv[0]); return 2; }
+    const bool indefinite = argc == 4;
     std::FILE* in = std::fopen(argv[1], "r");
     if (!in) { std::fprintf(stderr, "cannot read %s\n", argv[1]); return 2; }
     std::FILE* out = std::fopen(argv[2], "w");
@@ -29,7 +31,7 @@ int main(int argc, char** argv) {
             if (std::fscanf(in, "%lf", &GB[i]) != 1) rc = 3;
         if (rc) break;
         int kept = 0;
-        const int status = score::sp_rayleigh_ritz(m, nb, GA.data(), GB.data(), theta.data(), C.data(), &kept);
+        const int status = score::sp_rayleigh_ritz(m, nb, GA.data(), GB.data(), theta.data(), C.data(), &kept, indefinite);
         std::fprintf(out, "%d %d\n", status, kept);
         for (double v : theta) std::fprintf(out, "%.17g\n", v);
         for (double v : C) std::fprintf(out, "%.17g\n", v);
