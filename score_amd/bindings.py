@@ -1,6 +1,6 @@
 """ctypes bindings of the refinement family's headers (include/score_robust.h, score_refine_robust.h, score_refine_batch.h,
 score_refine_robust_batch.h, score_marginals.h, score_spectrum.h, score_samples.h, score_leverage.h, score_curvature.h, the
-``*_batch.h`` analyses, score_relative.h and score_relative_batch.h): their records, one ``Table`` per header -- ``{symbol: (argtypes, restype)}``, so the list of a
+``*_batch.h`` analyses, score_relative.h, score_relative_batch.h and score_select.h): their records, one ``Table`` per header -- ``{symbol: (argtypes, restype)}``, so the list of a
 header's symbols and their argument types are one text -- and the one ``bind`` that applies a table to a library.
 include/score_hip.h's own binding is ``solver.load_library``.
 """
@@ -109,6 +109,19 @@ class ScoreSamplesBatchInfo(InfoRecord):
         ("singular", C.c_int32),
         ("max_residual", C.c_double), ("setup_ms", C.c_double), ("rhs_ms", C.c_double), ("solve_ms", C.c_double),
     ]
+
+
+class ScoreSelectInfo(InfoRecord):
+    _fields_ = [
+        ("solve", ScoreMarginalsInfo),
+        ("candidates", C.c_int32), ("picked", C.c_int32), ("excluded", C.c_int32),
+        ("total_gain", C.c_double), ("asymmetry", C.c_double), ("cross_ms", C.c_double), ("greedy_ms", C.c_double),
+    ]
+
+    def as_dict(self) -> dict:
+        out = super().as_dict()
+        out["solve"] = self.solve.as_dict()
+        return out
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -259,6 +272,15 @@ RELATIVE_BATCH = Table("relative_batch", "(the CPU twin has no relative-pose cov
 })
 # and their group form (TABLES_LATEST is pinned in its turn)
 TABLES_GROUP_PAIRS = (RELATIVE_BATCH,)
+
+SELECT = Table("select", "(the CPU twin has no selection of ranges: engine='python' runs there)", {
+    "score_refine_select_ranges": ([_handle, _f64p, _f64p, _i32p, _i32p, _f64p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32,
+                                    C.c_int32, _i32p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _i32p, _f64p,
+                                    C.POINTER(ScoreSelectInfo)], C.c_int),
+    "score_select_greedy": ([_f64p, _f64p, _i32p, C.c_int32, C.c_int32, C.c_double, _i32p, _f64p, _f64p, _f64p, _i32p, _f64p], C.c_int),
+})
+# and the analyses of SETS of candidates (TABLES_GROUP_PAIRS is pinned as the others are)
+TABLES_SELECTION = (SELECT,)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -389,16 +389,29 @@ struct LvMeasure {
     }
 };
 
+// What lv_pair_solve does with a solved block beyond its variance -- the consumer it is given, as ps_solve is given LvMeasure:
+// check (the consumer's own arguments, before any work), begin (the block arguments stand), block (after k_lv_pair_dot of the
+// block c0 .. c0 + live, its solutions still in the block's x), end (every block solved and read: col_done[c] = 1 where column
+// c converged).  score_refine_range_variances has none; score_refine_select_ranges (score_select.hpp) forms the cross terms.
+struct LvPairOnly {
+    void check(int32_t, const std::string&) {}
+    template <class Refine>
+    void begin(Refine&, const LvPairArgs&, int32_t, hipStream_t) {}
+    template <class Refine>
+    void block(Refine&, int, int, hipStream_t) {}
+    void end(const std::vector<int32_t>&, hipStream_t) {}
+};
+
 // score_refine_range_variances.  Refine: score_refine (its point, blocks and gather, its linear-mode handle, its MvWork and LvWork).
-template <class Refine>
-int lv_pair_solve(Refine& R, const double* poses, const double* landmarks, const int32_t* pair_a, const int32_t* pair_b, int32_t n_pairs,
-                  double rel_tol, int32_t max_iters, int32_t block_width, double* variances, double* distances, double* residuals,
-                  int32_t* iters, double* solutions, score_marginals_info* info) {
+template <class Refine, class Use>
+int lv_pair_solve(Refine& R, const std::string& who, const double* poses, const double* landmarks, const int32_t* pair_a,
+                  const int32_t* pair_b, int32_t n_pairs, double rel_tol, int32_t max_iters, int32_t block_width, double* variances,
+                  double* distances, double* residuals, int32_t* iters, double* solutions, score_marginals_info* info, Use& use) {
     const GnProblem& P = R.P;
-    const std::string who = "score_refine_range_variances: ";
     if (block_width < 1 || block_width > kMvMaxWidth) throw std::runtime_error(who + "block_width must be 1..16");
     if (!(rel_tol > 0.0) || max_iters < 1) throw std::runtime_error(who + "rel_tol must be positive and max_iters >= 1");
     lv_check_pairs(P, pair_a, pair_b, n_pairs, who);
+    use.check(n_pairs, who);
     HipBackend& be = R.be();
     hipStream_t st = R.stream();
     const long long n = P.n;
@@ -418,6 +431,7 @@ int lv_pair_solve(Refine& R, const double* poses, const double* landmarks, const
     MvArgs a = mv_block_args(be, W, n, rel_tol);
     LvPairArgs l{};
     l.v = R.view(R.u.d); l.x = W.x.d; l.n = n; l.pa = L.pa.d; l.pb = L.pb.d; l.b = L.b.d; l.var = L.var.d; l.dist = L.dist.d;
+    use.begin(R, l, n_pairs, st);
     const double t1 = now_ms();
     const size_t C = (size_t)n_pairs;
     std::vector<int32_t> flags((size_t)kMvFlagWords), col_done(C, 0), col_iters(C, 0);
@@ -436,6 +450,7 @@ int lv_pair_solve(Refine& R, const double* poses, const double* landmarks, const
         mv_launch_product(a, NV, st);
         hipLaunchKernelGGL(k_ps_residual, dim3((unsigned)n_rblocks, (unsigned)live), dim3(kMvThreads), 0, st, a, (const double*)L.b.d);
         gn_dim(P.dim, [&](auto dim) { hipLaunchKernelGGL(k_lv_pair_dot<decltype(dim)::value>, dim3(1), dim3(64), 0, st, l); });
+        use.block(R, c0, live, st);
         HIP_CHECK(hipGetLastError());
         staged_d2h(res_part.data(), W.res_part.d, (size_t)live * (size_t)n_rblocks * sizeof(double), st);
         if (solutions) staged_d2h(solutions + (size_t)c0 * (size_t)n, W.x.d, (size_t)live * (size_t)n * sizeof(double), st);
@@ -462,6 +477,7 @@ int lv_pair_solve(Refine& R, const double* poses, const double* landmarks, const
         info->columns = n_pairs; info->batches = batches; info->pcg_iters = pcg_iters; info->unconverged = unconverged;
         info->max_residual = worst; info->setup_ms = t1 - t0; info->solve_ms = t2 - t1;
     }
+    use.end(col_done, st);
     return unconverged ? 1 : 0;
 }
 

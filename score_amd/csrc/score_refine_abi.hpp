@@ -1,6 +1,6 @@
 // score_refine_abi.hpp -- the entry points of the two refinement handles (score_refine_handles.hpp): include/score_hip.h's
 // score_refine_*, and score_refine_robust.h, score_marginals.h, score_spectrum.h, score_curvature.h, score_samples.h,
-// score_leverage.h with their *_batch.h forms, and score_relative.h with score_relative_batch.h.  Part of score_hip.hip's translation unit, included there once after the
+// score_leverage.h with their *_batch.h forms, score_relative.h with score_relative_batch.h, and score_select.h.  Part of score_hip.hip's translation unit, included there once after the
 // handles: every entry point goes through the frame of score_abi.hpp (abi_call, require, publish_new).
 #pragma once
 
@@ -112,8 +112,30 @@ int score_refine_range_variances(score_refine* r, const double* poses, const dou
                                  double* variances, double* distances, double* residuals, int32_t* iters, double* solutions,
                                  score_marginals_info* info) {
     return refine_call(r, poses, landmarks, [&] {
-        return score::lv_pair_solve(*r, poses, landmarks, pair_a, pair_b, n_pairs, rel_tol, max_iters, block_width, variances, distances,
-                                    residuals, iters, solutions, info);
+        score::LvPairOnly use;
+        return score::lv_pair_solve(*r, "score_refine_range_variances: ", poses, landmarks, pair_a, pair_b, n_pairs, rel_tol, max_iters,
+                                    block_width, variances, distances, residuals, iters, solutions, info, use);
+    });
+}
+int score_refine_select_ranges(score_refine* r, const double* poses, const double* landmarks, const int32_t* pair_a, const int32_t* pair_b,
+                               const double* precisions, int32_t n_pairs, int32_t k, double min_gain, double rel_tol, int32_t max_iters,
+                               int32_t block_width, int32_t* order, double* gains, double* pick_variances, double* variances,
+                               double* distances, double* remaining, double* residuals, int32_t* iters, double* matrix,
+                               score_select_info* info) {
+    return refine_call(r, poses, landmarks, [&] {
+        score::SelCross use{precisions, k, min_gain, score::SelOutputs{order, gains, pick_variances, remaining}, matrix, info};
+        return score::lv_pair_solve(*r, "score_refine_select_ranges: ", poses, landmarks, pair_a, pair_b, n_pairs, rel_tol, max_iters,
+                                    block_width, variances, distances, residuals, iters, nullptr, info ? &info->solve : nullptr, use);
+    });
+}
+int score_select_greedy(const double* matrix, const double* precisions, const int32_t* excluded, int32_t n, int32_t k, double min_gain,
+                        int32_t* order, double* gains, double* pick_variances, double* remaining, int32_t* picked, double* asymmetry) {
+    return abi_call([&] {
+        AbiEnv::require_device(0);
+        AbiEnv::Scope scope(0, false);
+        score::sel_greedy_alone(matrix, precisions, excluded, n, k, min_gain, score::SelOutputs{order, gains, pick_variances, remaining},
+                                picked, asymmetry);
+        return 0;
     });
 }
 int score_refine_relative_covariances(score_refine* r, const double* poses, const double* landmarks, const int32_t* pair_a,

@@ -12,6 +12,7 @@
 #include "score_samples.hpp"
 #include "score_leverage.hpp"
 #include "score_relative.hpp"
+#include "score_select.hpp"
 #include "score_gn_robust.hpp"
 #include "score_gn_batch.hpp"
 #include "score_gn_robust_batch.hpp"
@@ -103,6 +104,7 @@ struct score_refine : RefineBase {
     score::PsWork ps;  // posterior samples (score_samples.hpp)
     score::LvWork lv;  // range leverage and predicted range variances (score_leverage.hpp)
     score::RpWork rp;  // predicted relative poses and their covariances (score_relative.hpp)
+    score::SelWork sel;  // greedy selection of candidate ranges (score_select.hpp)
     int64_t rb_n_lc = 0;
     const score_refine_robust_settings* rb_settings = nullptr;  // of the robust run under way
 
