@@ -213,19 +213,36 @@ struct GblMeasure {
     }
 };
 
+// What gbl_pair_solve does with a solved pass beyond its variances -- the consumer it is given, as gbs_solve is given
+// GblMeasure and lv_pair_solve SelCross: check (the consumer's own arguments on the checked plan, before any work), nothing
+// (nobody lists a pair: the call ends there), begin (the pairs are on the device, the arguments of the passes stand), pass
+// (after k_gbl_pair_dot of pass k, its solutions still in x, column s at x + s n), end (every pass solved and read:
+// col_done[pair] = 1 where the pair's column converged).  score_refine_batch_range_variances has none;
+// score_refine_batch_select_ranges (score_select_batch.hpp) forms the members' cross terms.
+struct GblPairOnly {
+    void check(const GblPlan&, const std::string&) {}
+    void nothing(const GblPlan&) {}
+    template <class Batch>
+    void begin(Batch&, const GblPlan&, const GbsArgs&, const GblArgs&, hipStream_t) {}
+    template <class Batch>
+    void pass(Batch&, const GblPlan&, const GbsArgs&, int, const double*, hipStream_t) {}
+    void end(const GblPlan&, const std::vector<int32_t>&, hipStream_t) {}
+};
+
 // score_refine_batch_range_variances.  Batch: score_refine_batch (as gbm_solve; its GbsWork for the right-hand sides and its
 // GblWork for the pairs).
-template <class Batch>
-int gbl_pair_solve(Batch& B, const double* poses, const double* landmarks, const int32_t* pair_ptr, const int32_t* pair_a,
-                   const int32_t* pair_b, double rel_tol, int32_t max_iters, int32_t block_width, double* variances, double* distances,
-                   double* residuals, int32_t* iters, score_marginals_batch_info* info) {
+template <class Batch, class Use>
+int gbl_pair_solve(Batch& B, const std::string& who, const double* poses, const double* landmarks, const int32_t* pair_ptr,
+                   const int32_t* pair_a, const int32_t* pair_b, double rel_tol, int32_t max_iters, int32_t block_width, double* variances,
+                   double* distances, double* residuals, int32_t* iters, score_marginals_batch_info* info, Use& use) {
     const GbUnion& U = B.U;
-    const std::string who = "score_refine_batch_range_variances: ";
     const int G = U.count, W = block_width;
     const GblPlan plan = gbl_plan(who, G, block_width, nullptr, gbl_shapes(U), pair_ptr, pair_a, pair_b);
     if (!(rel_tol > 0.0) || max_iters < 1) throw std::runtime_error(who + "rel_tol must be positive and max_iters >= 1");
+    use.check(plan, who);
     if (plan.pairs == 0) {  // nothing listed: no device work
         if (info) *info = score_marginals_batch_info{};
+        use.nothing(plan);
         return 0;
     }
     HipBackend& be = B.be();
@@ -252,6 +269,7 @@ int gbl_pair_solve(Batch& B, const double* poses, const double* landmarks, const
     GbsArgs q{};
     q.d = B.dev(); q.X = B.X.d; q.cnt_ptr = L.pair_ptr.d; q.width = W; q.b = Q.b.d; q.n = n;
     const GblArgs l = L.args(plan);
+    use.begin(B, plan, q, l, st);
     const double t1 = now_ms();
     const dim3 bt(kThreads);
     const size_t nub = (size_t)B.n_ublocks, C = (size_t)plan.pairs;
@@ -274,6 +292,7 @@ int gbl_pair_solve(Batch& B, const double* poses, const double* landmarks, const
         gn_dim(U.dim, [&](auto dim) {
             hipLaunchKernelGGL(k_gbl_pair_dot<decltype(dim)::value>, dim3(dot_blocks), bt, 0, st, q, l, (const double*)K.pcg.x.d, G);
         });
+        use.pass(B, plan, q, k, (const double*)K.pcg.x.d, st);
         HIP_CHECK(hipGetLastError());
         part.resize((size_t)NV * nub);
         staged_d2h(part.data(), K.res_part.d, part.size() * sizeof(double), st);
@@ -303,6 +322,7 @@ int gbl_pair_solve(Batch& B, const double* poses, const double* landmarks, const
         info->columns = (int32_t)plan.pairs; info->passes = plan.passes; info->pcg_iters = pcg_iters; info->unconverged = unconverged;
         info->max_residual = worst; info->setup_ms = t1 - t0; info->solve_ms = t2 - t1;
     }
+    use.end(plan, col_done, st);
     return unconverged ? 1 : 0;
 }
 

@@ -1,6 +1,7 @@
 // score_refine_abi.hpp -- the entry points of the two refinement handles (score_refine_handles.hpp): include/score_hip.h's
 // score_refine_*, and score_refine_robust.h, score_marginals.h, score_spectrum.h, score_curvature.h, score_samples.h,
-// score_leverage.h with their *_batch.h forms, score_relative.h with score_relative_batch.h, and score_select.h.  Part of score_hip.hip's translation unit, included there once after the
+// score_leverage.h with their *_batch.h forms, score_relative.h with score_relative_batch.h, and score_select.h with
+// score_select_batch.h.  Part of score_hip.hip's translation unit, included there once after the
 // handles: every entry point goes through the frame of score_abi.hpp (abi_call, require, publish_new).
 #pragma once
 
@@ -258,8 +259,22 @@ int score_refine_batch_range_variances(score_refine_batch* b, const double* pose
                                        score_marginals_batch_info* info) {
     return refine_call(b, "score_refine_batch_range_variances: null handle", poses, landmarks,
                        "score_refine_batch_range_variances: the points are missing", [&] {
-        return score::gbl_pair_solve(*b, poses, landmarks, pair_ptr, pair_a, pair_b, rel_tol, max_iters, block_width, variances, distances,
-                                     residuals, iters, info);
+        score::GblPairOnly use;
+        return score::gbl_pair_solve(*b, "score_refine_batch_range_variances: ", poses, landmarks, pair_ptr, pair_a, pair_b, rel_tol, max_iters,
+                                     block_width, variances, distances, residuals, iters, info, use);
+    });
+}
+int score_refine_batch_select_ranges(score_refine_batch* b, const double* poses, const double* landmarks, const int32_t* pair_ptr,
+                                     const int32_t* pair_a, const int32_t* pair_b, const double* precisions, const int32_t* k,
+                                     double min_gain, double rel_tol, int32_t max_iters, int32_t block_width, int32_t* order, double* gains,
+                                     double* pick_variances, int32_t* picked, double* total_gains, double* variances, double* distances,
+                                     double* remaining, double* residuals, int32_t* iters, double* matrix, score_select_batch_info* info) {
+    return refine_call(b, "score_refine_batch_select_ranges: null handle", poses, landmarks,
+                       "score_refine_batch_select_ranges: the points are missing", [&] {
+        score::GbSelCross use{precisions, k, min_gain, score::GbSelOutputs{order, gains, pick_variances, remaining, picked, total_gains},
+                              matrix, info};
+        return score::gbl_pair_solve(*b, "score_refine_batch_select_ranges: ", poses, landmarks, pair_ptr, pair_a, pair_b, rel_tol, max_iters,
+                                     block_width, variances, distances, residuals, iters, info ? &info->solve : nullptr, use);
     });
 }
 int score_refine_batch_relative_covariances(score_refine_batch* b, const double* poses, const double* landmarks, const int32_t* pair_ptr,

@@ -21,6 +21,7 @@
 #include "score_samples_batch.hpp"
 #include "score_leverage_batch.hpp"
 #include "score_relative_batch.hpp"
+#include "score_select_batch.hpp"
 #include "score_spectrum_batch.hpp"
 #include "score_curvature_batch.hpp"
 
@@ -336,6 +337,7 @@ struct score_refine_batch : RefineBase {
     score::GbsWork gbs;  // posterior samples of the members (score_samples_batch.hpp)
     score::GblWork gbl;  // range leverage and predicted range variances of the members (score_leverage_batch.hpp)
     score::GrpWork grp;  // predicted relative poses of the members and their covariances (score_relative_batch.hpp)
+    score::GbSelWork gbsel;  // greedy selection of the members' candidate ranges (score_select_batch.hpp)
     // robust refinement: the members' parameters beside the base's buffers.  U keeps rng_prec / rel_kappa / rel_tau on the host
     // for its checks.
     DevBuf<score::GbrParam> rb_params;

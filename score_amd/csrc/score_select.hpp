@@ -69,12 +69,12 @@ __device__ __forceinline__ double sel_entry(double p, double q, int r, int c, co
     return r == c ? 1.0 + v : v;
 }
 
-// one workgroup per tile pair (i, j), (j, i), i <= j; kThreads = kSelTile x 8 lanes, lane (tx, ty) takes the rows ty + 8 q
-__global__ __launch_bounds__(kThreads) void k_sel_sym(double* P, const double* w, int C, int T, double* part) {
+// What one workgroup does for the tile pair (ti, tj), (tj, ti), ti <= tj, of the C x C matrix P with the precisions w -- stated
+// once for a graph (k_sel_sym) and for a member of a group (k_gbsel_sym of score_select_batch.hpp).  kThreads = kSelTile x 8
+// lanes, lane (tx, ty) takes the rows ty + 8 q; *part: the workgroup's max |P_cd - P_dc|.
+__device__ __forceinline__ void sel_sym_tile_pair(double* P, const double* w, const int C, const int ti, const int tj, double* part) {
     __shared__ double ta[kSelTile][kSelTile + 1], tb[kSelTile][kSelTile + 1];
     __shared__ double wave_max[kSelWaves];
-    int ti, tj;
-    sel_tile_pair((int)blockIdx.x, T, ti, tj);
     const int tx = threadIdx.x % kSelTile, ty = threadIdx.x / kSelTile;
     const int r0 = ti * kSelTile, c0 = tj * kSelTile;
     for (int rr = ty; rr < kSelTile; rr += kThreads / kSelTile) {
@@ -105,8 +105,15 @@ __global__ __launch_bounds__(kThreads) void k_sel_sym(double* P, const double* w
         double m = wave_max[0];
         for (int k = 1; k < kSelWaves; ++k)
             if (wave_max[k] > m) m = wave_max[k];
-        part[blockIdx.x] = m;
+        *part = m;
     }
+}
+
+// one workgroup per tile pair (i, j), (j, i), i <= j
+__global__ __launch_bounds__(kThreads) void k_sel_sym(double* P, const double* w, int C, int T, double* part) {
+    int ti, tj;
+    sel_tile_pair((int)blockIdx.x, T, ti, tj);
+    sel_sym_tile_pair(P, w, C, ti, tj, part + blockIdx.x);
 }
 
 struct SelGreedyArgs {
@@ -121,8 +128,9 @@ struct SelGreedyArgs {
     int32_t* picked;           // 1
 };
 
-// ONE workgroup: <<<1, kThreads>>>.  Lane t owns the candidates t + kThreads m, m < kSelOwn.
-__global__ __launch_bounds__(kThreads) void k_sel_greedy(SelGreedyArgs a) {
+// The whole factorisation by ONE workgroup of kThreads lanes -- stated once for a graph (k_sel_greedy) and for a member of a
+// group (k_gbsel_greedy of score_select_batch.hpp).  Lane t owns the candidates t + kThreads m, m < kSelOwn.
+__device__ __forceinline__ void sel_greedy_workgroup(const SelGreedyArgs& a) {
     __shared__ double d[kSelMaxCandidates];
     __shared__ unsigned char state[kSelMaxCandidates];
     __shared__ double row_p[kSelMaxPicks];
@@ -195,6 +203,9 @@ __global__ __launch_bounds__(kThreads) void k_sel_greedy(SelGreedyArgs a) {
         if (state[c] != kSelPicked) a.remaining[c] = (d[c] - 1.0) / a.w[c];
     if (t == 0) *a.picked = j;
 }
+
+// ONE workgroup: <<<1, kThreads>>>
+__global__ __launch_bounds__(kThreads) void k_sel_greedy(SelGreedyArgs a) { sel_greedy_workgroup(a); }
 
 // The buffers of the selection: they stay with the refinement handle between calls, as LvWork's do, and come with the first
 // call (P and L grow on demand).

@@ -1,7 +1,8 @@
 """How the batch front ends hand many graphs to ``score_refine_batch`` handles, stated once.
 
 ``refine_estimate_batch``, ``refine_estimate_robust_batch``, ``marginal_covariances_batch``, ``information_spectrum_batch``,
-``posterior_samples_batch``, ``range_leverage_batch``, ``predicted_range_variances_batch`` and ``predicted_relative_poses_batch`` all read: check the own arguments,
+``posterior_samples_batch``, ``range_leverage_batch``, ``predicted_range_variances_batch``, ``predicted_relative_poses_batch`` and
+``select_ranges_batch`` all read: check the own arguments,
 ``grouped`` with a callback that builds what is kept per graph, ``run_chunks`` with a body that answers one chunk.  THE RULE: the
 graphs are grouped by dimension, dimensions ascending; every dimension is cut into chunks of at most ``max_group`` graphs in input
 order; the chunks are numbered from 0 across the dimensions; a chunk is one group handle, created for it and destroyed after it;

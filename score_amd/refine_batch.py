@@ -206,6 +206,18 @@ class RefineBatchHandle(_Handle):
 
         return batch_relative_covariances(self, points, pairs_per_member, rel_tol, max_iters, block_width)
 
+    def select_ranges(self, points, pairs_per_member, precisions_per_member, k, min_gain: float = 0.0, rel_tol: float = 1e-10,
+                      max_iters: int = 4000, block_width: int = 16, with_matrix: bool = False):
+        """``score_refine_batch_select_ranges`` at ``points`` (include/score_select_batch.h): of every member's candidate
+        ranges ``pairs_per_member`` (member-local variable id pairs; None or empty: none) with ``precisions_per_member`` the
+        ``k`` (one integer, or one per member) the greedy rule picks.  Returns (return code, per member the dict of
+        ``SelectionHandle.select_ranges`` plus ``picked`` and ``total_gain``, the call's info record); the handle is left as it
+        was found."""
+        from .selection_batch import batch_select_ranges
+
+        return batch_select_ranges(self, points, pairs_per_member, precisions_per_member, k, min_gain, rel_tol, max_iters, block_width,
+                                   with_matrix)
+
     def _robust(self):
         """The library with the calls of include/score_refine_robust_batch.h bound."""
         return bind(self.lib, REFINE_ROBUST_BATCH)
@@ -264,7 +276,7 @@ class RefineBatchHandle(_Handle):
 def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-10, range_weights=None, loop_closure_weights=None,
                           engine: str = "native", lib_path: Optional[str] = None, solver_settings: Optional[dict] = None,
                           max_group: int = 64, marginals=None, samples=None, samples_seed: int = 0, leverage=None,
-                          leverage_seed: int = 0, curvature=None, relative=None):
+                          leverage_seed: int = 0, curvature=None, relative=None, select=None):
     """``refine_estimate`` for many graphs at once: ``datas`` and ``results`` member by member, ``range_weights`` /
     ``loop_closure_weights`` lists with one entry (an array as ``refine_estimate`` takes it, or None) per member -- they only
     scale precisions.  The members are grouped by dimension, in chunks of at most ``max_group`` (the rule of
@@ -294,7 +306,12 @@ def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-1
     ``pairs`` -- every group's handle then also predicts the relative poses of the listed pairs at the refined points with
     their covariances (``predicted_relative_poses_batch``'s call on the same handle, after the other analyses;
     ``engine="python"``: the dense path), and ``info["relative"]`` is that graph's ``(PredictedRelativePoses, info)`` (empty
-    for a graph that lists none, None for a graph without unknowns).  Without the keyword nothing changes."""
+    for a graph that lists none, None for a graph without unknowns).  Without the keyword nothing changes.
+    ``select``: a dict ``{"pairs": ..., "k": ..., "precision": 1.0, "min_gain": 0.0}`` with the arguments of those names of
+    ``select_ranges_batch`` (``pairs``: one entry per graph, None or a list of name pairs) -- every group's handle then also
+    picks k of each graph's candidate ranges at the refined points (``select_ranges_batch``'s call on the same handle, after
+    the other analyses; ``engine="python"``: the dense path), and ``info["selection"]`` is that graph's ``(Selection, info)``
+    (empty for a graph that lists none, None for a graph without unknowns).  Without the keyword nothing changes."""
     from .leverage import range_leverage
     from .leverage_batch import group_leverage
     from .marginals import _select
@@ -361,6 +378,29 @@ def refine_estimate_batch(datas, results, max_iters: int = 50, tol: float = 1e-1
 
         follow_ups.append(FollowUp("relative", relatives,
                                    lambda i, prob: _pose_pair_ids(prob, pair_names[i], f"refine_estimate_batch: graph {i}")))
+    if select is not None and select is not False:
+        from .leverage import pair_ids
+        from .selection_batch import _python_selection, group_selection, selection_arguments
+
+        unknown = set(select) - {"pairs", "k", "precision", "min_gain"}
+        if unknown or "pairs" not in select or "k" not in select:
+            raise ValueError("select: a dict with 'pairs' and 'k', and optionally 'precision' and 'min_gain'")
+        sel_gain = float(select.get("min_gain", 0.0))
+        sel_names = [[tuple(p) for p in nm] if nm is not None else []
+                     for nm in per_graph(select["pairs"], len(datas), "select['pairs']", none=False)]
+        sel_k, sel_w = selection_arguments(sel_names, select["k"], select.get("precision", 1.0), sel_gain, "refine_estimate_batch")
+
+        def selections(handle, number, idx, probs, pts, costs, kept):
+            """(Selection, info) per member at the refined points"""
+            if handle is None:
+                return [_python_selection(datas[i], _as_results(p, pt, results[i], f), sel_names[i], sel_k[i], sel_w[i], sel_gain, rws[i],
+                                          lws[i], i, "refine_estimate_batch")
+                        for p, pt, i, f in zip(probs, pts, idx, costs)]
+            return group_selection(handle, pts, [sel_names[i] for i in idx], kept, [sel_w[i] for i in idx], [sel_k[i] for i in idx],
+                                   number, sel_gain)
+
+        follow_ups.append(FollowUp("selection", selections,
+                                   lambda i, prob: pair_ids(prob, sel_names[i], f"refine_estimate_batch: graph {i}")))
     out: list = [None] * len(datas)
 
     def member(i, data, res):
