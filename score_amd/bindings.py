@@ -1,6 +1,6 @@
 """ctypes bindings of the refinement family's headers (include/score_robust.h, score_refine_robust.h, score_refine_batch.h,
 score_refine_robust_batch.h, score_marginals.h, score_spectrum.h, score_samples.h, score_leverage.h, score_curvature.h, the
-``*_batch.h`` analyses, score_relative.h, score_relative_batch.h, score_select.h and score_select_batch.h): their records, one ``Table`` per header -- ``{symbol: (argtypes, restype)}``, so the list of a
+``*_batch.h`` analyses, score_relative.h, score_relative_batch.h, score_select.h, score_select_batch.h and score_select_poses.h): their records, one ``Table`` per header -- ``{symbol: (argtypes, restype)}``, so the list of a
 header's symbols and their argument types are one text -- and the one ``bind`` that applies a table to a library.
 include/score_hip.h's own binding is ``solver.load_library``.
 """
@@ -112,6 +112,19 @@ class ScoreSamplesBatchInfo(InfoRecord):
 
 
 class ScoreSelectInfo(InfoRecord):
+    _fields_ = [
+        ("solve", ScoreMarginalsInfo),
+        ("candidates", C.c_int32), ("picked", C.c_int32), ("excluded", C.c_int32),
+        ("total_gain", C.c_double), ("asymmetry", C.c_double), ("cross_ms", C.c_double), ("greedy_ms", C.c_double),
+    ]
+
+    def as_dict(self) -> dict:
+        out = super().as_dict()
+        out["solve"] = self.solve.as_dict()
+        return out
+
+
+class ScoreSelectPosesInfo(InfoRecord):
     _fields_ = [
         ("solve", ScoreMarginalsInfo),
         ("candidates", C.c_int32), ("picked", C.c_int32), ("excluded", C.c_int32),
@@ -302,6 +315,16 @@ SELECT_BATCH = Table("select_batch", "(the CPU twin has no selection of ranges: 
 })
 # and their group form (TABLES_SELECTION is pinned in its turn)
 TABLES_GROUP_SELECTION = (SELECT_BATCH,)
+
+SELECT_POSES = Table("select_poses", "(the CPU twin has no selection of loop closures: engine='python' runs there)", {
+    "score_refine_select_relative_poses": ([_handle, _f64p, _f64p, _i32p, _i32p, _f64p, _f64p, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                            C.c_int32, C.c_int32, _i32p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _i32p, _f64p,
+                                            C.POINTER(ScoreSelectPosesInfo)], C.c_int),
+    "score_select_block_greedy": ([_f64p, _f64p, _f64p, _i32p, C.c_int32, C.c_int32, C.c_int32, C.c_double, _i32p, _f64p, _f64p, _f64p,
+                                   _i32p, _f64p], C.c_int),
+})
+# and the selection of BLOCK candidates, the relative poses (TABLES_GROUP_SELECTION is pinned like the rest)
+TABLES_POSE_SELECTION = (SELECT_POSES,)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 // score_refine_abi.hpp -- the entry points of the two refinement handles (score_refine_handles.hpp): include/score_hip.h's
 // score_refine_*, and score_refine_robust.h, score_marginals.h, score_spectrum.h, score_curvature.h, score_samples.h,
-// score_leverage.h with their *_batch.h forms, score_relative.h with score_relative_batch.h, and score_select.h with
-// score_select_batch.h.  Part of score_hip.hip's translation unit, included there once after the
+// score_leverage.h with their *_batch.h forms, score_relative.h with score_relative_batch.h, score_select.h with
+// score_select_batch.h, and score_select_poses.h.  Part of score_hip.hip's translation unit, included there once after the
 // handles: every entry point goes through the frame of score_abi.hpp (abi_call, require, publish_new).
 #pragma once
 
@@ -144,8 +144,34 @@ int score_refine_relative_covariances(score_refine* r, const double* poses, cons
                                       double* rotations, double* translations, double* covariances, double* residuals, int32_t* iters,
                                       double* solutions, score_marginals_info* info) {
     return refine_call(r, poses, landmarks, [&] {
-        return score::rp_solve(*r, poses, landmarks, pair_a, pair_b, n_pairs, rel_tol, max_iters, block_width, rotations, translations,
-                               covariances, residuals, iters, solutions, info);
+        score::RpOnly use;
+        return score::rp_solve(*r, "score_refine_relative_covariances: ", poses, landmarks, pair_a, pair_b, n_pairs, rel_tol, max_iters,
+                               block_width, rotations, translations, covariances, residuals, iters, solutions, info, use);
+    });
+}
+int score_refine_select_relative_poses(score_refine* r, const double* poses, const double* landmarks, const int32_t* pair_a,
+                                       const int32_t* pair_b, const double* translation_precisions, const double* rotation_precisions,
+                                       int32_t n_pairs, int32_t k, double min_gain, double rel_tol, int32_t max_iters, int32_t block_width,
+                                       int32_t* order, double* gains, double* pick_covariances, double* rotations, double* translations,
+                                       double* covariances, double* remaining, double* residuals, int32_t* iters, double* matrix,
+                                       score_select_poses_info* info) {
+    return refine_call(r, poses, landmarks, [&] {
+        score::SelpCross use{translation_precisions, rotation_precisions, k, min_gain,
+                             score::SelpOutputs{order, gains, pick_covariances, remaining}, matrix, info, r->P.dim};
+        return score::rp_solve(*r, "score_refine_select_relative_poses: ", poses, landmarks, pair_a, pair_b, n_pairs, rel_tol, max_iters,
+                               block_width, rotations, translations, covariances, residuals, iters, nullptr, info ? &info->solve : nullptr,
+                               use);
+    });
+}
+int score_select_block_greedy(const double* matrix, const double* translation_precisions, const double* rotation_precisions,
+                              const int32_t* excluded, int32_t n_candidates, int32_t dim, int32_t k, double min_gain, int32_t* order,
+                              double* gains, double* pick_covariances, double* remaining, int32_t* picked, double* asymmetry) {
+    return abi_call([&] {
+        AbiEnv::require_device(0);
+        AbiEnv::Scope scope(0, false);
+        score::selp_greedy_alone(matrix, translation_precisions, rotation_precisions, excluded, n_candidates, dim, k, min_gain,
+                                 score::SelpOutputs{order, gains, pick_covariances, remaining}, picked, asymmetry);
+        return 0;
     });
 }
 int score_refine_spectrum(score_refine* r, const double* poses, const double* landmarks, int32_t k, double rel_tol, int32_t max_iters,

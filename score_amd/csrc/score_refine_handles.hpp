@@ -13,6 +13,7 @@
 #include "score_leverage.hpp"
 #include "score_relative.hpp"
 #include "score_select.hpp"
+#include "score_select_poses.hpp"
 #include "score_gn_robust.hpp"
 #include "score_gn_batch.hpp"
 #include "score_gn_robust_batch.hpp"
@@ -106,6 +107,7 @@ struct score_refine : RefineBase {
     score::LvWork lv;  // range leverage and predicted range variances (score_leverage.hpp)
     score::RpWork rp;  // predicted relative poses and their covariances (score_relative.hpp)
     score::SelWork sel;  // greedy selection of candidate ranges (score_select.hpp)
+    score::SelpWork selp;  // and of candidate loop closures: what the blocks add (score_select_poses.hpp)
     int64_t rb_n_lc = 0;
     const score_refine_robust_settings* rb_settings = nullptr;  // of the robust run under way
 

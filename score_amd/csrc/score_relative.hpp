@@ -168,14 +168,15 @@ __global__ __launch_bounds__(kMvThreads) void k_rp_rhs(MvArgs m, RpArgs a) {
     }
 }
 
-// What one lane does for the solved column of error coordinate q of the pair ia - ib, its solution in column `slot` of x:
-// P[q' DP] = sum_k G[q', k] x[k] over the unknowns of a, then of b, ascending (P: the pair's block at its column q); the lane
-// of q == 0 also writes R_ab and t_ab (rot, trans: the pair's own) -- stated once for a graph and for a group (k_grp_dot).
+// The product of a pair's Jacobian with one solved column -- the body of rp_dot_lane, stated once: y[q'] = sum_k G[q', k] x[k]
+// over the unknowns of a, then of b, ascending, from column `slot` of x, stored at P[q' * stride]; Rab, tab: R_ab and t_ab of
+// the pair.  rp_dot_lane stores a pair's own DP x DP block (stride DP), k_selp_cross (score_select_poses.hpp) a column of the
+// N x N matrix of all candidates (stride N): the same operations in the same order, so the same bits.
 template <int DIM>
-__device__ __forceinline__ void rp_dot_lane(const GnView& v, const int64_t ia, const int64_t ib, const int q, const double* x,
-                                            const long long n, const int slot, double* P, double* rot, double* trans) {
+__device__ __forceinline__ void rp_dot_rows(const GnView& v, const int64_t ia, const int64_t ib, const double* x, const long long n,
+                                            const int slot, double* P, const long long stride, double* Rab, double* tab) {
     constexpr int DP = DIM == 2 ? 3 : 6, NC = 2 * DP;
-    double Rab[DIM * DIM], tab[DIM], G[DP * NC], d[NC];
+    double G[DP * NC], d[NC];
     rp_pair_jac<DIM>(v, ia, ib, Rab, tab, G);
     lv_read<DP>(x, n, slot, lv_pose_first<DIM>(ia), d);
     lv_read<DP>(x, n, slot, lv_pose_first<DIM>(ib), d + DP);
@@ -184,8 +185,19 @@ __device__ __forceinline__ void rp_dot_lane(const GnView& v, const int64_t ia, c
         double y = 0.0;
 #pragma unroll
         for (int k = 0; k < NC; ++k) y += G[qq * NC + k] * d[k];
-        P[qq * DP] = y;
+        P[qq * stride] = y;
     }
+}
+
+// What one lane does for the solved column of error coordinate q of the pair ia - ib, its solution in column `slot` of x:
+// P[q' DP] = sum_k G[q', k] x[k] over the unknowns of a, then of b, ascending (P: the pair's block at its column q); the lane
+// of q == 0 also writes R_ab and t_ab (rot, trans: the pair's own) -- stated once for a graph and for a group (k_grp_dot).
+template <int DIM>
+__device__ __forceinline__ void rp_dot_lane(const GnView& v, const int64_t ia, const int64_t ib, const int q, const double* x,
+                                            const long long n, const int slot, double* P, double* rot, double* trans) {
+    constexpr int DP = DIM == 2 ? 3 : 6;
+    double Rab[DIM * DIM], tab[DIM];
+    rp_dot_rows<DIM>(v, ia, ib, x, n, slot, P, DP, Rab, tab);
     if (q == 0) {
 #pragma unroll
         for (int k = 0; k < DIM * DIM; ++k) rot[k] = Rab[k];
@@ -235,16 +247,30 @@ inline void rp_check_pairs(const GnProblem& P, const int32_t* pair_a, const int3
     }
 }
 
+// What rp_solve does with a solved block beyond its covariances -- the consumer it is given, as lv_pair_solve is given
+// LvPairOnly / SelCross: check (the consumer's own arguments, before any work), begin (the block arguments stand), block (after
+// k_rp_dot of the columns j0 .. j0 + live, their solutions still in the block's x), end (every block solved and read:
+// col_done[j] = 1 where column j converged).  score_refine_relative_covariances has none;
+// score_refine_select_relative_poses (score_select_poses.hpp) forms the cross terms.
+struct RpOnly {
+    void check(int32_t, const std::string&) {}
+    template <class Refine>
+    void begin(Refine&, const RpArgs&, int32_t, hipStream_t) {}
+    template <class Refine>
+    void block(Refine&, long long, int, hipStream_t) {}
+    void end(const std::vector<int32_t>&, hipStream_t) {}
+};
+
 // score_refine_relative_covariances.  Refine: score_refine (its point, blocks and gather, its linear-mode handle, its MvWork and RpWork).
-template <class Refine>
-int rp_solve(Refine& R, const double* poses, const double* landmarks, const int32_t* pair_a, const int32_t* pair_b, int32_t n_pairs,
-             double rel_tol, int32_t max_iters, int32_t block_width, double* rotations, double* translations, double* covariances,
-             double* residuals, int32_t* iters, double* solutions, score_marginals_info* info) {
+template <class Refine, class Use>
+int rp_solve(Refine& R, const std::string& who, const double* poses, const double* landmarks, const int32_t* pair_a, const int32_t* pair_b,
+             int32_t n_pairs, double rel_tol, int32_t max_iters, int32_t block_width, double* rotations, double* translations,
+             double* covariances, double* residuals, int32_t* iters, double* solutions, score_marginals_info* info, Use& use) {
     const GnProblem& P = R.P;
-    const std::string who = "score_refine_relative_covariances: ";
     if (block_width < 1 || block_width > kMvMaxWidth) throw std::runtime_error(who + "block_width must be 1..16");
     if (!(rel_tol > 0.0) || max_iters < 1) throw std::runtime_error(who + "rel_tol must be positive and max_iters >= 1");
     rp_check_pairs(P, pair_a, pair_b, n_pairs, who);
+    use.check(n_pairs, who);
     if (n_pairs == 0) {
         if (info) *info = score_marginals_info{};
         return 0;
@@ -270,6 +296,7 @@ int rp_solve(Refine& R, const double* poses, const double* landmarks, const int3
     RpArgs l{};
     l.v = R.view(R.u.d); l.x = W.x.d; l.n = n; l.pa = L.pa.d; l.pb = L.pb.d; l.b = L.b.d;
     l.cov = L.cov.d; l.rot = L.rot.d; l.trans = L.trans.d;
+    use.begin(R, l, n_pairs, st);
     const double t1 = now_ms();
     const long long columns = (long long)n_pairs * DP;
     const size_t C = (size_t)columns;
@@ -289,6 +316,7 @@ int rp_solve(Refine& R, const double* poses, const double* landmarks, const int3
         mv_launch_product(a, NV, st);
         hipLaunchKernelGGL(k_ps_residual, dim3((unsigned)n_rblocks, (unsigned)live), dim3(kMvThreads), 0, st, a, (const double*)L.b.d);
         gn_dim(dim, [&](auto d) { hipLaunchKernelGGL(k_rp_dot<decltype(d)::value>, dim3(1), dim3(64), 0, st, l); });
+        use.block(R, j0, live, st);
         HIP_CHECK(hipGetLastError());
         staged_d2h(res_part.data(), W.res_part.d, (size_t)live * (size_t)n_rblocks * sizeof(double), st);
         if (solutions) staged_d2h(solutions + (size_t)j0 * (size_t)n, W.x.d, (size_t)live * (size_t)n * sizeof(double), st);
@@ -317,6 +345,7 @@ int rp_solve(Refine& R, const double* poses, const double* landmarks, const int3
         info->columns = (int32_t)columns; info->batches = batches; info->pcg_iters = pcg_iters; info->unconverged = unconverged;
         info->max_residual = worst; info->setup_ms = t1 - t0; info->solve_ms = t2 - t1;
     }
+    use.end(col_done, st);
     return unconverged ? 1 : 0;
 }
 
