@@ -3,7 +3,7 @@ host-refined points of tests/samples_batch_helpers.member_twin) and their dense 
 
 The group A..E lists [37, 0, 9, 260, 1] candidates with k = [12, 0, 9, 32, 1]: B takes no part, D's 260 candidates leave a partly
 filled ninth tile and its lanes run past one 256-lane workgroup, and the pair kernel's first workgroup spans A, C and D.  The
-group (3D0, 3D1) lists [20, 7] with k = [8, 7].  PRECONDITION holds every (member, candidates, k) whose pivot gap the host test
+group (3D0, 3D1) lists [20, 7] with k = [8, 7]; the group (D, B, C, A) lists [600, 37, 0, 513] with k = [40, 12, 0, 3].  PRECONDITION holds every (member, candidates, k) whose pivot gap the host test
 asserts on the dense P -- the GPU lists, and the smaller lists of B and D the issue's table names.  No bound is chosen here:
 every one is tests/selection_helpers.py's or tests/leverage_helpers.py's."""
 import functools
@@ -19,7 +19,13 @@ from selection_helpers import BASE_PRECISIONS, precisions
 KEYS_3D = ("3D0", "3D1")
 COUNTS_2D, KS_2D = [37, 0, 9, 260, 1], [12, 0, 9, 32, 1]
 COUNTS_3D, KS_3D = [20, 7], [8, 7]
-PRECONDITION = [("A", 37, 12), ("B", 5, 5), ("C", 9, 9), ("D", 70, 16), ("D", 260, 32), ("E", 1, 1), ("3D0", 20, 8), ("3D1", 7, 7)]
+# unequal members that straddle the ownership slots of sel_greedy_workgroup (lane t owns t + 256 m): D's 600 candidates reach the
+# third slot in 88 lanes under a coupled sweep of 40 steps, A's 513 reach it in one lane, B stays in the first, C takes no part;
+# the pair kernel runs five workgroups (1150 pairs), the first two inside D, the third across D, B and A.  Every member that
+# lists candidates is in PRECONDITION below, so every member's order is held to the reference
+KEYS_SLOTS, COUNTS_SLOTS, KS_SLOTS = ("D", "B", "C", "A"), [600, 37, 0, 513], [40, 12, 0, 3]
+PRECONDITION = [("A", 37, 12), ("B", 5, 5), ("C", 9, 9), ("D", 70, 16), ("D", 260, 32), ("E", 1, 1), ("3D0", 20, 8), ("3D1", 7, 7),
+                ("D", 600, 40), ("B", 37, 12), ("A", 513, 3)]
 
 
 def candidates(key, count):
@@ -45,5 +51,5 @@ def names_of(key, ids):
     return [(names[a], names[b]) for a, b in ids] if ids is not None else []
 
 
-__all__ = ["KEYS_2D", "KEYS_3D", "COUNTS_2D", "KS_2D", "COUNTS_3D", "KS_3D", "PRECONDITION", "BASE_PRECISIONS", "candidates",
+__all__ = ["KEYS_2D", "KEYS_3D", "COUNTS_2D", "KS_2D", "COUNTS_3D", "KS_3D", "KEYS_SLOTS", "COUNTS_SLOTS", "KS_SLOTS", "PRECONDITION", "BASE_PRECISIONS", "candidates",
            "dense_matrix", "names_of", "precisions", "member_twin"]

@@ -59,12 +59,30 @@ BASE_PRECISIONS = (4.0, 400.0)
 SIZES = (1, 2, 31, 32, 33, 64, 65, 257)
 SHAPES = [(c, kk) for c in SIZES for kk in sorted({min(c, 256), min(c, 3)})]
 SEEDS = {c: 100 + c for c in SIZES}
+# the ownership slots of k_sel_greedy (lane t owns the candidates t + 256 m, m < 16) and both caps: two full slots (16 tiles a
+# side), the first lane with three candidates at k = 256 (row_p full), slot 4 in one lane, slot 8 in a coupled sweep, one short of
+# the cap with a ragged last tile, and C = 4096 with k = 256 (d and state full, every slot live, L of 2^20 entries, 8256
+# workgroups of k_sel_sym).  Seeds 100 + C as above, checked on the CPU for the gap precondition (tests/test_selection_host.py)
+SLOT_SHAPES = [(512, 3), (513, 256), (1025, 3), (2049, 40), (4095, 3), (4096, 256)]
+SEEDS.update({c: 100 + c for c, _ in SLOT_SHAPES})
+# graph -> (candidates, k) of the long list on a handle: k_sel_cross with three workgroups a column, 41 solved blocks
+LONG_CASES = {"b": (650, 40)}
+CAP, CAP_PICKS = 4096, 256
 
 
 def candidates(key):
     """(ids, count, k) of the graph's candidate list: pair_list's pose - landmark, first pose - pose, pose - pose and landmark -
     pose pairs in turn."""
     count, k = CASES[key]
+    return pair_list(reference(key)[2].prob, count), count, k
+
+
+def long_candidates(key):
+    """(ids, count, k) of the graph's long candidate list (LONG_CASES): pair_list again.  On graph b its 650 ordered pairs are
+    all different, and 88 of them join two variables that another pair lists in the other direction; the two directions
+    carry different precisions (1 + 1/2 cos c), so no two leading pivots tie exactly and the list stays as pair_list gives it:
+    the gap precondition on the dense P is asserted in tests/test_selection_host.py."""
+    count, k = LONG_CASES[key]
     return pair_list(reference(key)[2].prob, count), count, k
 
 
@@ -90,6 +108,18 @@ def dense_candidates(key):
     for a in (G, dist, P, X):
         a.setflags(write=False)
     return G, dist, P, X
+
+
+@functools.lru_cache(maxsize=None)
+def dense_long_matrix(key):
+    """P_dense of the graph's long candidate list from the dense Cholesky factor; computed once and left unchanged."""
+    import scipy.linalg as sla
+
+    ref = reference(key)[2]
+    G, _ = pair_gradients(ref.prob, ref.point, long_candidates(key)[0])
+    P = G.T @ sla.cho_solve(ref.chol, G)
+    P.setflags(write=False)
+    return P
 
 
 @functools.lru_cache(maxsize=None)
@@ -128,6 +158,35 @@ def random_matrix(n, seed):
     P = B @ B.T / (2 * n) + 1e-9 * (R - R.T)
     w = 0.5 * 100.0 ** (rng.permutation(n) / max(n - 1, 1))
     return P, w
+
+
+@functools.lru_cache(maxsize=1)
+def slot_matrix(n):
+    """random_matrix(n, SEEDS[n]) of a slot shape, read-only; the last one asked for is kept (134 MB at the cap)."""
+    P, w = random_matrix(n, SEEDS[n])
+    P.setflags(write=False)
+    w.setflags(write=False)
+    return P, w
+
+
+@functools.lru_cache(maxsize=None)
+def slot_reference(n, k):
+    """bounded_reference of a slot shape: computed once a session (11 s of host time at the caps) and left unchanged."""
+    ref = bounded_reference(*slot_matrix(n), k)
+    for v in ref.values():
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return ref
+
+
+def graded(count, modulus):
+    """pi(c) = (1001 c) mod `modulus`, c < count <= modulus: 1001 is odd and the modulus a power of two, so pi is a bijection
+    of range(modulus) and takes `count` distinct values on range(count).  The diagonal 1 + pi / 4096 is exact in double, and
+    under precisions of 4 (sqrt 4 is exact) so is every pivot 5 + pi / 1024: the order of the picks is argsort(-pi)."""
+    assert count <= modulus <= 4096 and modulus & (modulus - 1) == 0
+    pi = (1001 * np.arange(count)) % modulus
+    assert len(set(pi.tolist())) == count
+    return pi, 1.0 + pi / 4096.0
 
 
 def bounded_reference(P, w, k, min_gain=0.0, excluded=None):
@@ -231,4 +290,5 @@ def total_gain_bound(P_ref, bound, w, order):
 
 
 __all__ = ["CASES", "BASE_PRECISIONS", "MIN_GAP", "SIZES", "SHAPES", "SEEDS", "candidates", "precisions", "dense_candidates", "dense_rtol", "slogdet_gains", "random_matrix",
-           "bounded_reference", "check_against_reference", "matrix_bound", "total_gain_bound", "twin", "reference"]
+           "bounded_reference", "check_against_reference", "matrix_bound", "total_gain_bound", "twin", "reference", "SLOT_SHAPES",
+           "LONG_CASES", "CAP", "CAP_PICKS", "long_candidates", "dense_long_matrix", "slot_matrix", "slot_reference", "graded"]

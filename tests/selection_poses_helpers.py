@@ -63,6 +63,14 @@ BASE_PRECISIONS = (4.0, 400.0)
 # the kernel tests: N = 63 / 66 around a wavefront and the 32-tiles, one candidate past k's cap (85, 42), one past the workgroup
 SIZES = {2: (1, 2, 21, 22, 64, 65, 86, 257), 3: (1, 2, 10, 11, 43, 65)}
 SHAPES = [(dim, c, kk) for dim in (2, 3) for c in SIZES[dim] for kk in sorted({min(c, 256 // (3 if dim == 2 else 6)), min(c, 3)})]
+# the ownership slots of k_selp_greedy (lane t owns the candidates t + 256 m; m < 3 in 3-D, m < 6 in 2-D) and the caps: in 3-D
+# the first lane with two candidates at k's cap, the third (last) slot, one short of the cap and the caps (N = 4092, K = 252);
+# in 2-D the third slot at k's cap, one short of the cap and the caps (N = 4095, K = 255, the sixth slot).  random_block_matrix's
+# seed 100 + C, checked on the CPU for the gap precondition (tests/test_selection_poses_host.py)
+SLOT_SHAPES = [(3, 257, 42), (3, 513, 3), (3, 681, 3), (3, 682, 42), (2, 513, 85), (2, 1364, 3), (2, 1365, 85)]
+CAPS = {2: (1365, 85), 3: (682, 42)}
+# graph -> (candidates, k) of the long list on a handle: N = 960 columns, two workgroups of k_selp_cross a column slot
+LONG_CASES = {"b": (320, 12)}
 
 
 def dof(dim):
@@ -128,6 +136,51 @@ def random_block_matrix(count, dim):
     for a in (P, kappa, tau):
         a.setflags(write=False)
     return P, kappa, tau
+
+
+@functools.lru_cache(maxsize=1)
+def slot_block_matrix(count, dim):
+    """random_block_matrix(count, dim) of a slot shape without that function's unbounded cache: the last one asked for is kept
+    (134 MB at the caps)."""
+    return random_block_matrix.__wrapped__(count, dim)
+
+
+@functools.lru_cache(maxsize=None)
+def slot_block_reference(dim, count, k):
+    """bounded_block_reference of a slot shape: computed once a session (10 s of host time at the caps) and left unchanged."""
+    ref = bounded_block_reference(*slot_block_matrix(count, dim), dim, k)
+    for v in ref.values():
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return ref
+
+
+def graded_blocks(count, dim):
+    """(pi, P): selection_helpers.graded with the modulus 2048 (1001 is odd: (1001 c) mod 2048 is a bijection of range(2048),
+    so it takes `count` <= 1365 distinct values on range(count)), and P = diag(1 + pi(c) / 4096 on all dp coordinates of c)."""
+    from selection_helpers import graded
+
+    pi, value = graded(count, 2048)
+    return pi, np.diag(np.repeat(value, dof(dim)))
+
+
+def long_candidates(key):
+    """(ids, count, k) of the graph's long candidate list (LONG_CASES): relative_helpers.pair_list again, whose first 320
+    pairs on graph b are 320 different unordered pairs -- no reversed duplicate, no exact tie."""
+    count, k = LONG_CASES[key]
+    return pair_list(reference(key)[2].prob, count), count, k
+
+
+@functools.lru_cache(maxsize=None)
+def dense_long_matrix(key):
+    """P = G'H^-1 G of the graph's long candidate list from the dense Cholesky factor; computed once and left unchanged."""
+    import scipy.linalg as sla
+
+    ref = reference(key)[2]
+    G, _, _ = relative_jacobians(ref.prob, ref.point, long_candidates(key)[0])
+    P = G.T @ sla.cho_solve(ref.chol, G)
+    P.setflags(write=False)
+    return P
 
 
 def _gain_bound(B, E_B, dp):
@@ -268,4 +321,5 @@ def total_gain_bound(P_ref, bound, w, dp, order):
 
 __all__ = ["CASES", "BASE_PRECISIONS", "MIN_GAP", "SIZES", "SHAPES", "dof", "candidates", "precisions", "dense_candidates",
            "slogdet_block_gains", "random_block_matrix", "bounded_block_reference", "check_against_reference", "matrix_bound",
-           "total_gain_bound", "twin", "reference"]
+           "total_gain_bound", "twin", "reference", "SLOT_SHAPES", "CAPS", "LONG_CASES", "slot_block_matrix", "slot_block_reference",
+           "graded_blocks", "long_candidates", "dense_long_matrix"]

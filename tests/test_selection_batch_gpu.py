@@ -8,7 +8,9 @@ that matrix, with the member alone in a group, under another width, in another m
 tolerance is chosen here: every bound is the derived one of tests/selection_helpers.py and tests/leverage_helpers.py.
 
 The group A..E (tests/selection_batch_helpers.py) lists [37, 0, 9, 260, 1] candidates with k = [12, 0, 9, 32, 1]; the group
-(3D0, 3D1) lists [20, 7] with k = [8, 7].  Everything runs on one handle per group, computed once."""
+(3D0, 3D1) lists [20, 7] with k = [8, 7]; the group "slots", (D, B, C, A), lists [600, 37, 0, 513] with k = [40, 12, 0, 3]: unequal
+members on either side of the ownership slots of the factorisation (a lane owns the candidates t + 256 m), every one of them held
+to the reference (its precondition is asserted on the CPU).  Everything runs on one handle per group, computed once."""
 import ctypes as C
 import functools
 
@@ -22,8 +24,8 @@ from score_amd.refine_batch import RefineBatchHandle, _problem_of, refine_estima
 from score_amd.refine_robust import _point_arrays
 from score_amd.selection import Selection, greedy_from_matrix
 from score_amd.selection_batch import select_ranges_batch
-from selection_batch_helpers import (BASE_PRECISIONS, COUNTS_2D, COUNTS_3D, KEYS_2D, KEYS_3D, KS_2D, KS_3D, candidates, member_twin,
-                                     names_of, precisions)
+from selection_batch_helpers import (BASE_PRECISIONS, COUNTS_2D, COUNTS_3D, COUNTS_SLOTS, KEYS_2D, KEYS_3D, KEYS_SLOTS, KS_2D, KS_3D, KS_SLOTS,
+                                     PRECONDITION, candidates, member_twin, names_of, precisions)
 from selection_helpers import bounded_reference, check_against_reference, matrix_bound, total_gain_bound
 
 pytestmark = pytest.mark.gpu
@@ -32,7 +34,8 @@ VALUES = ("order", "gains", "pick_variances", "remaining")
 COLUMNS = ("variances", "distances", "residuals", "iterations", "converged")
 EVERYTHING = VALUES + COLUMNS + ("matrix", "picked", "total_gain", "rc")
 SOLVE = ("columns", "passes", "pcg_iters", "unconverged", "max_residual")
-GROUPS = {"2d": (KEYS_2D, COUNTS_2D, KS_2D), "3d": (KEYS_3D, COUNTS_3D, KS_3D)}
+GROUPS = {"2d": (KEYS_2D, COUNTS_2D, KS_2D), "3d": (KEYS_3D, COUNTS_3D, KS_3D), "slots": (KEYS_SLOTS, COUNTS_SLOTS, KS_SLOTS)}
+CAPPED = ("2d", "3d")   # the groups that also run under an iteration cap
 
 
 def _same_bits(a, b, label, keys=EVERYTHING):
@@ -71,9 +74,10 @@ def runs_of(name, hip_lib):
         out["again"] = h.select_ranges(pts, ids, w4, ks, with_matrix=True)
         out["narrow"] = h.select_ranges(pts, ids, w4, ks, block_width=5, with_matrix=True)
         out["rv_after"] = {w: h.range_variances(pts, ids, block_width=w) for w in (16, 5)}
-        steps = np.concatenate([m["iterations"] for m in out["rv"][16][1]])
-        out["cap"] = int(steps.max()) - 1
-        out["capped"] = h.select_ranges(pts, ids, w4, ks, max_iters=out["cap"], with_matrix=True)
+        if name in CAPPED:
+            steps = np.concatenate([m["iterations"] for m in out["rv"][16][1]])
+            out["cap"] = int(steps.max()) - 1
+            out["capped"] = h.select_ranges(pts, ids, w4, ks, max_iters=out["cap"], with_matrix=True)
         if name == "2d":
             gains = out[BASE_PRECISIONS[0]][1][KEYS_2D.index("C")]["gains"]
             out["cut"] = 0.5 * (gains[4] + gains[5])
@@ -141,7 +145,8 @@ def test_order_and_gains_against_the_rule_on_the_members_own_matrix(hip_lib, nam
     keys, counts, ks = GROUPS[name]
     for base in BASE_PRECISIONS:
         for key, m, c, k in zip(keys, runs[base][1], counts, ks):
-            if c:
+            if c:   # (every list of every group has its precondition asserted on the CPU: tests/test_selection_batch_host.py)
+                assert (key, c, k) in PRECONDITION
                 check_against_reference(m, bounded_reference(m["matrix"], precisions(c, base), k), f"{key}, precision {base}")
 
 
@@ -169,6 +174,31 @@ def test_widths_and_repeats_give_the_same_bits(hip_lib, name):
     assert runs["narrow"][2]["solve"]["passes"] == -(-max(counts) // 5)
 
 
+@pytest.mark.parametrize("key", [k for k, c in zip(KEYS_SLOTS, COUNTS_SLOTS) if c])
+def test_a_member_of_the_unequal_group_alone_in_a_group(hip_lib, key):
+    """Contract 4 for (D, B, C, A) with [600, 37, 0, 513] candidates: every member that lists candidates, alone in a group of
+    one, gives its bits from the full group."""
+    runs = runs_of("slots", hip_lib)
+    g = KEYS_SLOTS.index(key)
+    c, k = COUNTS_SLOTS[g], KS_SLOTS[g]
+    with _handle((key,), hip_lib) as h:
+        rc, (alone,), rec = h.select_ranges(_points((key,)), _ids((key,), [c]), [precisions(c, BASE_PRECISIONS[0])], [k], with_matrix=True)
+    assert rc == 0 and rec["members"] == 1 and rec["candidates"] == c and rec["picked"] == k
+    _same_bits(alone, runs[BASE_PRECISIONS[0]][1][g], f"{key} alone against {key} in {KEYS_SLOTS}")
+
+
+def test_another_member_order_of_the_unequal_group(hip_lib):
+    """Contract 4: (D, B, C, A) as (A, C, D, B) -- the pair kernel's workgroups now begin in A -- gives each member the same bits."""
+    runs = runs_of("slots", hip_lib)
+    perm = [3, 2, 0, 1]
+    keys, counts, ks = ([v[p] for p in perm] for v in (KEYS_SLOTS, COUNTS_SLOTS, KS_SLOTS))
+    with _handle(keys, hip_lib) as h:
+        rc, members, rec = h.select_ranges(_points(keys), _ids(keys, counts), _weights(counts, BASE_PRECISIONS[0]), ks, with_matrix=True)
+    assert rc == 0 and rec["asymmetry"] == runs[BASE_PRECISIONS[0]][2]["asymmetry"] and rec["picked"] == sum(KS_SLOTS)
+    for p, key, m in zip(perm, keys, members):
+        _same_bits(m, runs[BASE_PRECISIONS[0]][1][p], f"{key} in the order {keys}")
+
+
 @pytest.mark.parametrize("key", ["A", "D"])
 def test_a_member_alone_in_a_group(hip_lib, key):
     """Contract 4: the member alone in a group of one gives its bits from the full group."""
@@ -193,7 +223,7 @@ def test_another_member_order(hip_lib):
         _same_bits(m, runs[BASE_PRECISIONS[0]][1][p], f"{key} in the order {keys}")
 
 
-@pytest.mark.parametrize("name", sorted(GROUPS))
+@pytest.mark.parametrize("name", CAPPED)
 def test_unconverged_columns_exclude_their_candidates(hip_lib, name):
     """max_iters = max(steps) - 1 over the group: the call returns 1, exactly the late columns are excluded in their members,
     those members follow the rule on the eligible set of their own matrix, and members with no late column keep their bits."""

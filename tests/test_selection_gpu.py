@@ -2,15 +2,18 @@
 csrc/score_select.hpp): the kernels alone on random matrices against the rule in np.longdouble on the same matrix, under the
 bounds derived in tests/selection_helpers.py, the exact ties and stops, and the call on a handle -- its columns bit for bit
 those of score_refine_range_variances, its matrix under the bound of the range variances, its order held to the rule on its
-OWN matrix (near-ties are in the data: never to the dense one)."""
+OWN matrix (near-ties are in the data: never to the dense one).  The same checks reach every ownership slot of k_sel_greedy
+and both caps (selection_helpers.SLOT_SHAPES, the exact graded diagonal and the identity at C = 4096, k = 256) and, on a
+handle, a list of 650 candidates on graph b."""
 import functools
 
 import numpy as np
 import pytest
 
 from marginals_helpers import EPS
-from selection_helpers import (BASE_PRECISIONS, CASES, SEEDS, SHAPES, bounded_reference, candidates, check_against_reference,
-                               matrix_bound, precisions, random_matrix, total_gain_bound, twin)
+from selection_helpers import (BASE_PRECISIONS, CAP, CAP_PICKS, CASES, LONG_CASES, SEEDS, SHAPES, SLOT_SHAPES, bounded_reference, candidates,
+                               check_against_reference, graded, long_candidates, matrix_bound, precisions, random_matrix, slot_matrix,
+                               slot_reference, total_gain_bound, twin)
 from score_amd.selection import SelectionHandle, greedy_from_matrix, greedy_reference, select_ranges
 
 pytestmark = pytest.mark.gpu
@@ -35,6 +38,83 @@ def test_kernels_against_the_reference(hip_lib, n, k):
     again = greedy_from_matrix(P, w, k, lib_path=hip_lib)
     _same_bits(out, again)
     assert again["asymmetry"] == out["asymmetry"]
+
+
+@pytest.mark.parametrize("n,k", SLOT_SHAPES)
+def test_kernels_against_the_reference_at_every_slot_and_cap(hip_lib, n, k):
+    """The checks above where a lane owns up to 16 candidates (selection_helpers.SLOT_SHAPES), up to both caps: the host's
+    share is the long-double reference (11 s at C = 4096, k = 256; computed once)."""
+    P, w = slot_matrix(n)
+    ref = slot_reference(n, k)
+    out = greedy_from_matrix(P, w, k, lib_path=hip_lib)
+    assert out["rc"] == 0 and out["picked"] == ref["picked"] == k
+    check_against_reference(out, ref, f"C = {n}, k = {k}")
+    assert out["asymmetry"] == float(np.max(np.abs(P - P.T)))  # (a subtraction of two doubles and a max: exact)
+    again = greedy_from_matrix(P, w, k, lib_path=hip_lib)
+    _same_bits(out, again)
+    assert again["asymmetry"] == out["asymmetry"]
+
+
+def _graded():
+    """(pi, the diagonal 1 + pi / 4096, its dense matrix, the precisions 4, the order argsort(-pi)) at the cap."""
+    pi, value = graded(CAP, 4096)
+    return pi, value, np.diag(value), np.full(CAP, 4.0), np.argsort(-pi, kind="stable")
+
+
+def _check_graded(out, value, order, picks, excluded=()):
+    """Every product is exact (sqrt 4 = 2, the diagonal a multiple of 2^-12 below 2, exact zeros elsewhere): d_c =
+    5 + pi(c) / 1024, the pick variance is the diagonal entry back, every l off the pivot an exact zero -- so `remaining` is
+    the diagonal whatever was picked.  The gain is the device's log of an exact d: 2 eps of 1/2 log d in long double, the
+    margin of the identity test."""
+    assert out["rc"] == 0 and out["picked"] == picks and out["asymmetry"] == 0.0
+    np.testing.assert_array_equal(out["order"][:picks], order[:picks])
+    assert np.all(out["order"][picks:] == -1) and np.all(out["gains"][picks:] == 0) and np.all(out["pick_variances"][picks:] == 0)
+    np.testing.assert_array_equal(out["pick_variances"][:picks], value[order[:picks]])
+    np.testing.assert_array_equal(out["remaining"], value)
+    want = 0.5 * np.log(np.asarray(1.0 + 4.0 * value[order[:picks]], dtype=np.longdouble))
+    assert np.all(np.abs(out["gains"][:picks] - want) <= 2 * EPS)
+    assert not np.any(np.isin(out["order"], np.asarray(excluded, dtype=np.int64)))
+
+
+def test_a_graded_diagonal_at_the_caps(hip_lib):
+    """C = 4096, P = diag(1 + pi(c) / 4096), pi(c) = (1001 c) mod 4096 (selection_helpers.graded), every precision 4: the argmax
+    across all 16 slots, the four waves and the 64 lanes bit for bit, k = 256 -- alone, with the 100 leading candidates
+    excluded (the next 256 are picked; the excluded keep their remaining variance), and under a min_gain between two gains."""
+    pi, value, P, w, order = _graded()
+    out = greedy_from_matrix(P, w, CAP_PICKS, lib_path=hip_lib)
+    _check_graded(out, value, order, CAP_PICKS)
+    assert np.all(np.diff(pi[out["order"]]) < 0) and pi[out["order"][0]] == CAP - 1
+    excluded = np.zeros(CAP, dtype=np.int32)
+    excluded[order[:100]] = 1
+    rest = greedy_from_matrix(P, w, CAP_PICKS, excluded=excluded, lib_path=hip_lib)
+    _check_graded(rest, value, order[100:], CAP_PICKS, excluded=order[:100])
+    np.testing.assert_array_equal(rest["gains"][:CAP_PICKS - 100], out["gains"][100:])
+    # min_gain between the gains of picks 9 and 10 (from 0): ten picks, the padding after them
+    d = np.asarray(1.0 + 4.0 * value[order[:11]], dtype=np.longdouble)
+    cut = float(0.25 * (np.log(d[9]) + np.log(d[10])))
+    assert out["gains"][10] < cut < out["gains"][9]
+    short = greedy_from_matrix(P, w, CAP_PICKS, min_gain=cut, lib_path=hip_lib)
+    _check_graded(short, value, order, 10)
+    np.testing.assert_array_equal(short["gains"][:10], out["gains"][:10])
+
+
+def test_identity_at_the_caps(hip_lib):
+    """P = I, every precision 4, C = 4096, k = 256: exact ties across every slot, wave and lane, broken to the lowest index; with
+    the first 3900 candidates excluded the 196 others are picked in index order and the rule stops."""
+    P, w = np.eye(CAP), np.full(CAP, 4.0)
+    out = greedy_from_matrix(P, w, CAP_PICKS, lib_path=hip_lib)
+    np.testing.assert_array_equal(out["order"], np.arange(CAP_PICKS))
+    assert out["rc"] == 0 and out["picked"] == CAP_PICKS and out["asymmetry"] == 0.0
+    np.testing.assert_array_equal(out["gains"], np.full(CAP_PICKS, out["gains"][0]))
+    assert abs(out["gains"][0] - 0.5 * np.log(5.0)) <= 2 * EPS and np.all(out["pick_variances"] == 1.0) and np.all(out["remaining"] == 1.0)
+    excluded = np.zeros(CAP, dtype=np.int32)
+    excluded[:3900] = 1
+    rest = greedy_from_matrix(P, w, CAP_PICKS, excluded=excluded, lib_path=hip_lib)
+    assert rest["rc"] == 0 and rest["picked"] == CAP - 3900 == 196
+    np.testing.assert_array_equal(rest["order"], np.concatenate([np.arange(3900, CAP), np.full(CAP_PICKS - 196, -1)]))
+    np.testing.assert_array_equal(rest["gains"], np.concatenate([out["gains"][:196], np.zeros(CAP_PICKS - 196)]))
+    np.testing.assert_array_equal(rest["pick_variances"], np.concatenate([np.ones(196), np.zeros(CAP_PICKS - 196)]))
+    assert np.all(rest["remaining"] == 1.0)
 
 
 def test_identity_and_equal_precisions_pick_in_index_order(hip_lib):
@@ -107,12 +187,23 @@ def test_the_library_refuses_bad_arguments(hip_lib):
 
 
 # ---- the call on a handle ----
+# the lists of CASES by their graph's name, and the long list of graph b (650 candidates, k = 40: three workgroups of k_sel_cross
+# a column, a third ownership slot in the factorisation) as "b650"
+LISTS = {**{key: (key, candidates) for key in CASES}, **{f"{key}{LONG_CASES[key][0]}": (key, long_candidates) for key in LONG_CASES}}
+
+
+def _list(name):
+    """(graph, ids, count, k) of a list of LISTS."""
+    key, get = LISTS[name]
+    return (key, *get(key))
+
+
 @functools.lru_cache(maxsize=None)
-def _runs(key, hip_lib):
-    """One handle per graph: the range variances, then the selection at both base precisions (the first twice, and at width
+def _runs(name, hip_lib):
+    """One handle per list: the range variances, then the selection at both base precisions (the first twice, and at width
     5).  Computed once and left unchanged."""
+    key, ids, count, k = _list(name)
     tw = twin(key)
-    ids, count, k = candidates(key)
     out = {}
     with SelectionHandle(tw.ref.prob, hip_lib) as h:
         out["variances"] = h.range_variances(tw.ref.point, ids)
@@ -124,10 +215,10 @@ def _runs(key, hip_lib):
     return out
 
 
-@pytest.mark.parametrize("key", sorted(CASES))
+@pytest.mark.parametrize("key", sorted(LISTS))
 def test_columns_are_those_of_the_range_variances(hip_lib, key):
     runs = _runs(key, hip_lib)
-    ids, count, k = candidates(key)
+    _, ids, count, k = _list(key)
     var = runs["variances"]
     assert var["rc"] == 0 and np.all(var["converged"])
     for name in (*BASE_PRECISIONS, "again"):
@@ -141,11 +232,11 @@ def test_columns_are_those_of_the_range_variances(hip_lib, key):
         np.testing.assert_array_equal(runs["after"][f], var[f], err_msg=f)
 
 
-@pytest.mark.parametrize("key", sorted(CASES))
+@pytest.mark.parametrize("key", sorted(LISTS))
 def test_matrix_and_total_gain_against_the_dense_reference(hip_lib, key):
     runs = _runs(key, hip_lib)
-    tw = twin(key)
-    ids, count, k = candidates(key)
+    graph, ids, count, k = _list(key)
+    tw = twin(graph)
     for base in BASE_PRECISIONS:
         sel = runs[base]
         P_ref, bound = matrix_bound(tw, ids, sel)
@@ -163,10 +254,10 @@ def test_matrix_and_total_gain_against_the_dense_reference(hip_lib, key):
         assert total == sum(sel["gains"][:k].tolist())  # (the host adds them in the order of the picks)
 
 
-@pytest.mark.parametrize("key", sorted(CASES))
+@pytest.mark.parametrize("key", sorted(LISTS))
 def test_order_and_gains_against_the_rule_on_the_calls_own_matrix(hip_lib, key):
     runs = _runs(key, hip_lib)
-    ids, count, k = candidates(key)
+    _, ids, count, k = _list(key)
     for base in BASE_PRECISIONS:
         sel = runs[base]
         ref = bounded_reference(sel["matrix"], precisions(count, base), k)
@@ -174,14 +265,26 @@ def test_order_and_gains_against_the_rule_on_the_calls_own_matrix(hip_lib, key):
         assert np.all(np.diff(sel["gains"]) <= 1e-12 * sel["gains"][:-1])
 
 
-@pytest.mark.parametrize("key", sorted(CASES))
+@pytest.mark.parametrize("key", sorted(LISTS))
 def test_widths_and_repeats_give_the_same_bits(hip_lib, key):
     runs = _runs(key, hip_lib)
     first = runs[BASE_PRECISIONS[0]]
     for other in ("again", "narrow"):
         np.testing.assert_array_equal(runs[other]["matrix"], first["matrix"], err_msg=other)
         _same_bits(first, runs[other])
-    assert runs["narrow"]["info"]["solve"]["batches"] == (CASES[key][0] + 4) // 5
+    assert runs["narrow"]["info"]["solve"]["batches"] == (_list(key)[2] + 4) // 5
+
+
+@pytest.mark.parametrize("key", sorted(LISTS))
+def test_the_call_equals_the_selection_alone_on_its_matrix(hip_lib, key):
+    """The handle's k_sel_sym and k_sel_greedy on its kept buffers against score_select_greedy on the returned matrix."""
+    runs = _runs(key, hip_lib)
+    _, ids, count, k = _list(key)
+    for base in BASE_PRECISIONS:
+        sel = runs[base]
+        alone = greedy_from_matrix(sel["matrix"], precisions(count, base), k, lib_path=hip_lib)
+        _same_bits(sel, alone)
+        assert alone["picked"] == sel["info"]["picked"] and alone["asymmetry"] == sel["info"]["asymmetry"]
 
 
 def test_unconverged_columns_exclude_their_candidates(hip_lib):

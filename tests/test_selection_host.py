@@ -15,8 +15,9 @@ from score_amd import bindings
 from score_amd.bindings import (LATER_TABLES, SELECT, TABLES, TABLES_AFTER, TABLES_GROUP_PAIRS, TABLES_LATEST, TABLES_SELECTION,
                                 TABLES_SINCE, ScoreMarginalsInfo, ScoreSelectInfo, bind)
 from score_amd.selection import SELECT_SYMBOLS, Selection, SelectionHandle, greedy_reference, select_ranges
-from selection_helpers import (BASE_PRECISIONS, CASES, MIN_GAP, SEEDS, SHAPES, bounded_reference, candidates, dense_candidates,
-                               dense_rtol, precisions, random_matrix, reference, slogdet_gains)
+from selection_helpers import (BASE_PRECISIONS, CASES, LONG_CASES, MIN_GAP, SEEDS, SHAPES, SLOT_SHAPES, bounded_reference, candidates,
+                               dense_candidates, dense_long_matrix, dense_rtol, long_candidates, precisions, random_matrix, reference,
+                               slogdet_gains, slot_matrix)
 from test_binding_tables_host import SCALARS, _declarations, _Stub
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -123,6 +124,32 @@ def test_the_seeds_of_the_kernel_tests_satisfy_the_gap_precondition(n, k):
     assert ref["picked"] == k and (n == 1 or ref["min_gap"] >= MIN_GAP)
     np.testing.assert_array_equal(greedy_reference(P, w, k)["order"], ref["order"])
     assert np.all(ref["gain_bound"] < 1e-9) and (ref["asymmetry"] > 0 or n == 1)
+
+
+@pytest.mark.parametrize("n,k", SLOT_SHAPES)
+def test_the_seeds_of_the_slot_shapes_satisfy_the_gap_precondition(n, k):
+    """The same for the shapes that reach the ownership slots and the caps, with the rule alone (the bounds, 11 s at the caps,
+    are the GPU test's, which asserts the whole precondition): the long-double rule's smallest relative pivot gap >= MIN_GAP,
+    and the double rule's order equal to it."""
+    P, w = slot_matrix(n)
+    ref = greedy_reference(P, w, k, dtype=np.longdouble)
+    print(f"C = {n}, k = {k}: smallest pivot gap {ref['min_gap']:.3e}")
+    assert ref["picked"] == k and ref["min_gap"] >= MIN_GAP and ref["asymmetry"] > 0
+    np.testing.assert_array_equal(greedy_reference(P, w, k)["order"], ref["order"])
+
+
+@pytest.mark.parametrize("base", BASE_PRECISIONS)
+@pytest.mark.parametrize("key", sorted(LONG_CASES))
+def test_the_long_list_satisfies_the_gap_precondition(key, base):
+    """The precondition of the long list of tests/test_selection_gpu.py on the dense P, at both base precisions: the smallest
+    gap >= MIN_GAP and the bound E_d of every pivot below half of it (bounded_reference asserts both; never skipped)."""
+    ids, count, k = long_candidates(key)
+    P, w = dense_long_matrix(key), precisions(count, base)
+    ref = bounded_reference(P, w, k)
+    pairs = {tuple(sorted(p)) for p in ids.tolist()}
+    print(f"{key}, C = {count} ({len(pairs)} different unordered pairs), k = {k}, base {base}: smallest pivot gap {ref['min_gap']:.3e}")
+    assert ref["picked"] == k and ref["min_gap"] >= MIN_GAP and 600 <= count <= 700 and k >= 16
+    np.testing.assert_array_equal(greedy_reference(P, w, k)["order"], ref["order"])
 
 
 @pytest.mark.parametrize("flags", [("-O2",), ("-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined")],

@@ -2,15 +2,19 @@
 csrc/score_select_poses.hpp): the kernels alone on random matrices against the rule in np.longdouble on the same matrix, under
 the bounds derived in tests/selection_poses_helpers.py, the exact ties and stops, and the call on a handle -- its relative
 outputs bit for bit those of score_refine_relative_covariances, its matrix under the bound of the relative covariances, its
-order held to the rule on its OWN matrix (never to the dense one)."""
+order held to the rule on its OWN matrix (never to the dense one).  The same checks reach every ownership slot of
+k_selp_greedy and the caps in both dimensions (selection_poses_helpers.SLOT_SHAPES, the exact graded diagonal and the identity
+at the caps), a list of 320 candidates on graph b, and the buffers a handle keeps between calls of other sizes."""
 import functools
 
 import numpy as np
 import pytest
 
 from marginals_helpers import EPS
-from selection_poses_helpers import (BASE_PRECISIONS, CASES, SHAPES, bounded_block_reference, candidates, check_against_reference, dof,
-                                     matrix_bound, precisions, random_block_matrix, total_gain_bound, twin)
+from selection_helpers import candidates as range_candidates, precisions as range_precisions
+from selection_poses_helpers import (BASE_PRECISIONS, CAPS, CASES, LONG_CASES, SHAPES, SLOT_SHAPES, bounded_block_reference, candidates,
+                                     check_against_reference, dof, graded_blocks, long_candidates, matrix_bound, precisions,
+                                     random_block_matrix, slot_block_matrix, slot_block_reference, total_gain_bound, twin)
 from score_amd.selection_poses import (PoseSelectionHandle, block_greedy_from_matrix, block_greedy_reference, column_precisions,
                                        select_loop_closures)
 
@@ -38,6 +42,94 @@ def test_kernels_against_the_reference(hip_lib, dim, n, k):
     again = block_greedy_from_matrix(P, kappa, tau, dim, k, lib_path=hip_lib)
     _same_bits(out, again)
     assert again["asymmetry"] == out["asymmetry"]
+
+
+@pytest.mark.parametrize("dim,n,k", SLOT_SHAPES)
+def test_kernels_against_the_reference_at_every_slot_and_cap(hip_lib, dim, n, k):
+    """The checks above where a lane owns up to 3 (3-D) or 6 (2-D) candidates (selection_poses_helpers.SLOT_SHAPES), up to the
+    caps: the host's share is the long-double reference (10 s at the caps; computed once)."""
+    P, kappa, tau = slot_block_matrix(n, dim)
+    ref = slot_block_reference(dim, n, k)
+    out = block_greedy_from_matrix(P, kappa, tau, dim, k, lib_path=hip_lib)
+    assert out["rc"] == 0 and out["picked"] == ref["picked"] == k
+    check_against_reference(out, ref, f"dim {dim}, C = {n}, k = {k}")
+    assert out["asymmetry"] == float(np.max(np.abs(P - P.T)))  # (a subtraction of two doubles and a max: exact)
+    np.testing.assert_array_equal(out["remaining"], np.swapaxes(out["remaining"], 1, 2))
+    again = block_greedy_from_matrix(P, kappa, tau, dim, k, lib_path=hip_lib)
+    _same_bits(out, again)
+    assert again["asymmetry"] == out["asymmetry"]
+
+
+def _check_graded(out, value, order, picks, dp, excluded=()):
+    """Every column weighs 4 (kappa = 4, tau = 2: sqrt 4 is exact), the diagonal 1 + pi(c) / 4096 is a multiple of 2^-12 below 2
+    and everything else an exact zero: every block is (5 + pi(c) / 1024) I exactly, every l off the pivot's own coordinate an
+    exact zero, so the pick covariance is the diagonal entry times I and `remaining` the diagonal blocks whatever was picked.
+    The gain is half a sum of dp device logarithms of an exact pivot: the (dp + 1) eps relative margin that
+    tests/test_selection_poses_host.py derives for two sides of this rule."""
+    assert out["rc"] == 0 and out["picked"] == picks and out["asymmetry"] == 0.0
+    np.testing.assert_array_equal(out["order"][:picks], order[:picks])
+    assert np.all(out["order"][picks:] == -1) and np.all(out["gains"][picks:] == 0) and np.all(out["pick_covariances"][picks:] == 0)
+    eye = np.eye(dp)
+    np.testing.assert_array_equal(out["pick_covariances"][:picks], value[order[:picks], None, None] * eye)
+    np.testing.assert_array_equal(out["remaining"], value[:, None, None] * eye)
+    want = 0.5 * dp * np.log(np.asarray(1.0 + 4.0 * value[order[:picks]], dtype=np.longdouble))
+    assert np.all(np.abs(out["gains"][:picks] - want) <= (dp + 1) * EPS * want)
+    assert not np.any(np.isin(out["order"], np.asarray(excluded, dtype=np.int64)))
+
+
+@pytest.mark.parametrize("dim", [2, 3])
+def test_a_graded_diagonal_at_the_caps(hip_lib, dim):
+    """C = 1365 | 682 and k = 85 | 42, P = 1 + pi(c) / 4096 on all dp coordinates of candidate c, pi(c) = (1001 c) mod 2048
+    (selection_poses_helpers.graded_blocks): the argmax across every ownership slot, the four waves and the 64 lanes bit for
+    bit -- alone, with the 100 leading candidates excluded (the next k are picked; the excluded keep their remaining
+    covariance), and under a min_gain between two gains."""
+    dp = dof(dim)
+    n, k = CAPS[dim]
+    pi, P = graded_blocks(n, dim)
+    value = 1.0 + pi / 4096.0
+    order = np.argsort(-pi, kind="stable")
+    kappa, tau = np.full(n, 4.0), np.full(n, 2.0)
+    np.testing.assert_array_equal(column_precisions(dim, kappa, tau, n), np.full(n * dp, 4.0))
+    out = block_greedy_from_matrix(P, kappa, tau, dim, k, lib_path=hip_lib)
+    _check_graded(out, value, order, k, dp)
+    excluded = np.zeros(n, dtype=np.int32)
+    excluded[order[:100]] = 1
+    rest = block_greedy_from_matrix(P, kappa, tau, dim, k, excluded=excluded, lib_path=hip_lib)
+    _check_graded(rest, value, order[100:], k, dp, excluded=order[:100])
+    # min_gain between the gains of picks 9 and 10 (from 0): ten picks, the padding after them
+    d = np.asarray(1.0 + 4.0 * value[order[:11]], dtype=np.longdouble)
+    cut = float(0.25 * dp * (np.log(d[9]) + np.log(d[10])))
+    assert out["gains"][10] < cut < out["gains"][9]
+    short = block_greedy_from_matrix(P, kappa, tau, dim, k, min_gain=cut, lib_path=hip_lib)
+    _check_graded(short, value, order, 10, dp)
+    np.testing.assert_array_equal(short["gains"][:10], out["gains"][:10])
+
+
+@pytest.mark.parametrize("dim", [2, 3])
+def test_identity_at_the_caps(hip_lib, dim):
+    """P = I, every column's weight 4, C and k at their caps: exact ties across every slot, wave and lane, broken to the lowest
+    index; with all but the last 40 candidates excluded those 40 are picked in index order and the rule stops short of k."""
+    dp = dof(dim)
+    n, k = CAPS[dim]
+    P, kappa, tau = np.eye(n * dp), np.full(n, 4.0), np.full(n, 2.0)
+    out = block_greedy_from_matrix(P, kappa, tau, dim, k, lib_path=hip_lib)
+    np.testing.assert_array_equal(out["order"], np.arange(k))
+    assert out["rc"] == 0 and out["picked"] == k and out["asymmetry"] == 0.0
+    np.testing.assert_array_equal(out["gains"], np.full(k, out["gains"][0]))
+    assert abs(out["gains"][0] - 0.5 * dp * np.log(5.0)) <= (dp + 1) * EPS * 0.5 * dp * np.log(5.0)
+    np.testing.assert_array_equal(out["pick_covariances"], np.broadcast_to(np.eye(dp), (k, dp, dp)))
+    np.testing.assert_array_equal(out["remaining"], np.broadcast_to(np.eye(dp), (n, dp, dp)))
+    left = 40
+    assert left < k
+    excluded = np.zeros(n, dtype=np.int32)
+    excluded[:n - left] = 1
+    rest = block_greedy_from_matrix(P, kappa, tau, dim, k, excluded=excluded, lib_path=hip_lib)
+    assert rest["rc"] == 0 and rest["picked"] == left
+    np.testing.assert_array_equal(rest["order"], np.concatenate([np.arange(n - left, n), np.full(k - left, -1)]))
+    np.testing.assert_array_equal(rest["gains"], np.concatenate([out["gains"][:left], np.zeros(k - left)]))
+    np.testing.assert_array_equal(rest["pick_covariances"][:left], np.broadcast_to(np.eye(dp), (left, dp, dp)))
+    assert np.all(rest["pick_covariances"][left:] == 0)
+    np.testing.assert_array_equal(rest["remaining"], np.broadcast_to(np.eye(dp), (n, dp, dp)))
 
 
 @pytest.mark.parametrize("dim", [2, 3])
@@ -123,12 +215,23 @@ def test_the_library_refuses_bad_arguments(hip_lib):
 
 
 # ---- the call on a handle ----
+# the lists of CASES by their graph's name, and the long list of graph b (320 candidates = 960 columns, k = 12: two workgroups of
+# k_selp_cross a column slot, 60 solved blocks, a second ownership slot in the factorisation) as "b320"
+LISTS = {**{key: (key, candidates) for key in CASES}, **{f"{key}{LONG_CASES[key][0]}": (key, long_candidates) for key in LONG_CASES}}
+
+
+def _list(name):
+    """(graph, ids, count, k) of a list of LISTS."""
+    key, get = LISTS[name]
+    return (key, *get(key))
+
+
 @functools.lru_cache(maxsize=None)
-def _runs(key, hip_lib):
-    """One handle per graph: the relative covariances, then the selection at both base precisions (the first twice, and at
+def _runs(name, hip_lib):
+    """One handle per list: the relative covariances, then the selection at both base precisions (the first twice, and at
     width 5).  Computed once and left unchanged."""
+    key, ids, count, k = _list(name)
     tw = twin(key)
-    ids, count, k = candidates(key)
     out = {}
     with PoseSelectionHandle(tw.ref.prob, hip_lib) as h:
         out["relative"] = h.relative_covariances(tw.ref.point, ids)
@@ -142,12 +245,12 @@ def _runs(key, hip_lib):
     return out
 
 
-@pytest.mark.parametrize("key", sorted(CASES))
+@pytest.mark.parametrize("key", sorted(LISTS))
 def test_relative_outputs_are_those_of_the_relative_covariances(hip_lib, key):
     """(i) and (ii): the relative outputs bit for bit, that call unchanged afterwards, every diagonal block of the matrix."""
     runs = _runs(key, hip_lib)
-    ids, count, k = candidates(key)
-    dp = dof(twin(key).fg.dimension)
+    graph, ids, count, k = _list(key)
+    dp = dof(twin(graph).fg.dimension)
     rel = runs["relative"]
     assert rel["rc"] == 0 and np.all(rel["converged"])
     for name in (*BASE_PRECISIONS, "again"):
@@ -163,12 +266,12 @@ def test_relative_outputs_are_those_of_the_relative_covariances(hip_lib, key):
         np.testing.assert_array_equal(runs["after"][f], rel[f], err_msg=f)  # (and the selection leaves the other call as it was)
 
 
-@pytest.mark.parametrize("key", sorted(CASES))
+@pytest.mark.parametrize("key", sorted(LISTS))
 def test_matrix_and_total_gain_against_the_dense_reference(hip_lib, key):
     """(iii)"""
     runs = _runs(key, hip_lib)
-    tw = twin(key)
-    ids, count, k = candidates(key)
+    graph, ids, count, k = _list(key)
+    tw = twin(graph)
     dim = tw.fg.dimension
     dp = dof(dim)
     for base in BASE_PRECISIONS:
@@ -188,12 +291,12 @@ def test_matrix_and_total_gain_against_the_dense_reference(hip_lib, key):
         assert total == sum(sel["gains"][:k].tolist())  # (the host adds them in the order of the picks)
 
 
-@pytest.mark.parametrize("key", sorted(CASES))
+@pytest.mark.parametrize("key", sorted(LISTS))
 def test_order_and_values_against_the_rule_on_the_calls_own_matrix(hip_lib, key):
     """(iv)"""
     runs = _runs(key, hip_lib)
-    ids, count, k = candidates(key)
-    dim = twin(key).fg.dimension
+    graph, ids, count, k = _list(key)
+    dim = twin(graph).fg.dimension
     for base in BASE_PRECISIONS:
         sel = runs[base]
         ref = bounded_block_reference(sel["matrix"], *precisions(count, base), dim, k)
@@ -201,16 +304,65 @@ def test_order_and_values_against_the_rule_on_the_calls_own_matrix(hip_lib, key)
         assert np.all(np.diff(sel["gains"]) <= 1e-12 * sel["gains"][:-1])
 
 
-@pytest.mark.parametrize("key", sorted(CASES))
+@pytest.mark.parametrize("key", sorted(LISTS))
 def test_widths_and_repeats_give_the_same_bits(hip_lib, key):
     """(v)"""
     runs = _runs(key, hip_lib)
     first = runs[BASE_PRECISIONS[0]]
-    dp = dof(twin(key).fg.dimension)
+    graph, _, count, _ = _list(key)
+    dp = dof(twin(graph).fg.dimension)
     for other in ("again", "narrow"):
         np.testing.assert_array_equal(runs[other]["matrix"], first["matrix"], err_msg=other)
         _same_bits(first, runs[other])
-    assert runs["narrow"]["info"]["solve"]["batches"] == (CASES[key][0] * dp + 4) // 5
+    assert runs["narrow"]["info"]["solve"]["batches"] == (count * dp + 4) // 5
+
+
+@pytest.mark.parametrize("key", sorted(LISTS))
+def test_the_call_equals_the_selection_alone_on_its_matrix(hip_lib, key):
+    """The handle's k_sel_sym and k_selp_greedy on its kept buffers against score_select_block_greedy on the returned matrix."""
+    runs = _runs(key, hip_lib)
+    graph, _, count, k = _list(key)
+    dim = twin(graph).fg.dimension
+    for base in BASE_PRECISIONS:
+        sel = runs[base]
+        alone = block_greedy_from_matrix(sel["matrix"], *precisions(count, base), dim, k, lib_path=hip_lib)
+        _same_bits(sel, alone)
+        assert alone["picked"] == sel["info"]["picked"] and alone["asymmetry"] == sel["info"]["asymmetry"]
+
+
+def test_the_kept_buffers_between_calls_of_other_sizes(hip_lib):
+    """SelWork::reserve and SelpWork::reserve on ONE handle of graph a: ranges (C = 37, k = 12), relative poses (C = 23, k = 8:
+    69 columns, P grows and L with it), ranges (C = 20, k = 20: L indexed at a stride below the room), the first call again,
+    ranges with every pair three times over two directions (C = 60, k = 30: 1800 entries of L against the 1656 kept, so L grows
+    at the room of 69 and is indexed at the stride 60) and the relative poses again.  Every call gives the bits of the same
+    call on a fresh handle; the fourth gives those of the first."""
+    tw = twin("a")
+    r_ids, r_count, r_k = range_candidates("a")
+    p_ids, p_count, p_k = candidates("a")
+    assert (r_count, r_k, p_count, p_k) == (37, 12, 23, 8)
+    many = np.concatenate([r_ids[:20], r_ids[:20][:, ::-1], r_ids[:20]])
+    calls = [("ranges", r_ids, range_precisions(37, 4.0), 12), ("poses", p_ids, precisions(23, 4.0), 8),
+             ("ranges", r_ids[:20], range_precisions(20, 4.0), 20), ("ranges", r_ids, range_precisions(37, 4.0), 12),
+             ("ranges", many, range_precisions(60, 4.0), 30), ("poses", p_ids, precisions(23, 4.0), 8)]
+
+    def call(h, kind, ids, w, k):
+        if kind == "ranges":
+            return h.select_ranges(tw.ref.point, ids, w, k, with_matrix=True)
+        return h.select_relative_poses(tw.ref.point, ids, *w, k, with_matrix=True)
+
+    with PoseSelectionHandle(tw.ref.prob, hip_lib) as h:
+        kept = [call(h, *c) for c in calls]
+    for i, (c, out) in enumerate(zip(calls, kept)):
+        with PoseSelectionHandle(tw.ref.prob, hip_lib) as h:
+            fresh = call(h, *c)
+        values = ("order", "gains", "remaining", "matrix", "residuals", "iterations", "rc") + (
+            ("pick_variances", "variances", "distances") if c[0] == "ranges" else ("pick_covariances", "covariances", "rotations", "translations"))
+        _same_bits(out, fresh, keys=values)
+        for f in ("candidates", "picked", "excluded", "total_gain", "asymmetry"):
+            assert out["info"][f] == fresh["info"][f], (i, f)
+        assert out["rc"] == 0 and out["info"]["picked"] == c[3], i
+    _same_bits(kept[3], kept[0], keys=("order", "gains", "pick_variances", "remaining", "matrix", "variances"))
+    _same_bits(kept[5], kept[1], keys=VALUES + ("matrix", "covariances"))
 
 
 @pytest.mark.parametrize("key", ["a", "d"])

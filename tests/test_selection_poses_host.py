@@ -21,8 +21,9 @@ from score_amd.bindings import (LATER_TABLES, SELECT_POSES, TABLES, TABLES_AFTER
 from score_amd.relative import measurement_noise, predicted_relative_poses
 from score_amd.selection_poses import (SELECT_POSES_SYMBOLS, PoseSelection, PoseSelectionHandle, block_greedy_reference,
                                        column_precisions, select_loop_closures)
-from selection_poses_helpers import (BASE_PRECISIONS, CASES, MIN_GAP, SHAPES, bounded_block_reference, candidates, dense_candidates,
-                                     dof, precisions, random_block_matrix, reference, slogdet_block_gains)
+from selection_poses_helpers import (BASE_PRECISIONS, CASES, LONG_CASES, MIN_GAP, SHAPES, SLOT_SHAPES, bounded_block_reference, candidates,
+                                     dense_candidates, dense_long_matrix, dof, long_candidates, precisions, random_block_matrix, reference,
+                                     slogdet_block_gains, slot_block_matrix)
 from test_binding_tables_host import SCALARS, _declarations, _Stub
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -194,6 +195,36 @@ def test_the_seeds_of_the_kernel_tests_satisfy_the_gap_precondition(dim, n, k):
     assert ref["picked"] == k and (n == 1 or ref["min_gap"] >= MIN_GAP)
     np.testing.assert_array_equal(block_greedy_reference(P, column_precisions(dim, kappa, tau, n), dof(dim), k)["order"], ref["order"])
     assert ref["asymmetry"] > 0
+
+
+@pytest.mark.parametrize("dim,n,k", SLOT_SHAPES)
+def test_the_seeds_of_the_slot_shapes_satisfy_the_gap_precondition(dim, n, k):
+    """The same for the shapes that reach the ownership slots and the caps, with the rule alone (the bounds, 10 s at the caps,
+    are the GPU test's, which asserts the whole precondition): the long-double rule's smallest relative gap >= MIN_GAP, and
+    the double rule's order equal to it."""
+    P, kappa, tau = slot_block_matrix(n, dim)
+    w = column_precisions(dim, kappa, tau, n)
+    ref = block_greedy_reference(P, w.astype(np.longdouble), dof(dim), k, dtype=np.longdouble)
+    print(f"dim {dim}, C = {n}, k = {k}: smallest gap {ref['min_gap']:.3e}")
+    assert ref["picked"] == k and ref["min_gap"] >= MIN_GAP and ref["asymmetry"] > 0
+    np.testing.assert_array_equal(block_greedy_reference(P, w, dof(dim), k)["order"], ref["order"])
+
+
+@pytest.mark.parametrize("base", BASE_PRECISIONS)
+@pytest.mark.parametrize("key", sorted(LONG_CASES))
+def test_the_long_list_satisfies_the_gap_precondition(key, base):
+    """The precondition of the long list of tests/test_selection_poses_gpu.py on the dense P, at both bases: the smallest gap
+    >= MIN_GAP and the bound of the two best gains below half their gap (bounded_block_reference asserts both; never
+    skipped)."""
+    ids, count, k = long_candidates(key)
+    dim = reference(key)[0].dimension
+    kappa, tau = precisions(count, base)
+    ref = bounded_block_reference(dense_long_matrix(key), kappa, tau, dim, k)
+    pairs = {tuple(sorted(p)) for p in ids.tolist()}
+    print(f"{key}, C = {count} ({len(pairs)} different unordered pairs), k = {k}, base {base}: smallest gap {ref['min_gap']:.3e}")
+    assert ref["picked"] == k and ref["min_gap"] >= MIN_GAP and 300 <= count <= 400 and k >= 8 and len(pairs) == count
+    want = block_greedy_reference(dense_long_matrix(key), column_precisions(dim, kappa, tau, count), dof(dim), k)["order"]
+    np.testing.assert_array_equal(want, ref["order"])
 
 
 def test_argument_errors():
